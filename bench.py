@@ -8,7 +8,10 @@ timed region.  One process per GPU.  Either launch N > 1 as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 or simply `python bench.py --gpus N`: with WORLD_SIZE unset the parent starts that launcher itself (before it touches the GPU, like the
 reference's own `-n_cudas N`, depth_main.py:72, needs no external launcher), relays rank 0's line and exits with the children's code.
-Rank 0 prints ONE JSON line (contract in the task statement; `roofline` and `cpu_baseline` described in DESIGN.md).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the headline figure (`value`, `ms_per_step`, `dtype`, `config`);
+--full adds the side measurements, each taken in passes of its own after the timed steps: forward + backward only (`fwd_bwd_*`), the per-conv kernel
+pass (`roofline`), every layer on the fp32-MFMA kernels (`fp32_mfma_only`) and the CPU port with its parity check (`cpu_baseline`,
+`parity_at_contract_batch`); DESIGN.md section 6 describes them.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 Protocol of BASELINE.md section 4: >= 10 warm-up and >= 50 timed steps by default, device-synchronised at both ends.
 """
 import argparse
@@ -87,6 +90,30 @@ def cpu_model():
     return 'unknown'
 
 
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: elements drawn from the parameter and gradient vectors (4 MB each in fp32)
+
+
+def dump_outputs(path, loss, trainer):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files of about 9 MB in all.  loss: the step's loss; spec_cam:
+    its 3-D joints [B, J, 3]; bn_running_stats: every floating-point buffer of the model (BatchNorm running means / variances) after the step, in
+    registration order; params_sample / grads_sample: the updated parameters and the step's gradients, all parameters flattened and concatenated in
+    registration order, at DUMP_SAMPLE positions drawn once from a fixed seed (all of them when there are fewer)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    params = trainer.optimizer.params
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([p.grad.detach().reshape(-1) for p in params])
+    n = flat_p.numel()
+    pick = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    pick = torch.from_numpy(pick).to(flat_p.device)
+    buffers = [b.detach().reshape(-1) for b in trainer.model.buffers() if b.is_floating_point()]
+    out = {'loss': loss.detach().float().reshape(1), 'spec_cam': trainer.last_spec_cam.detach().float(),
+           'bn_running_stats': torch.cat(buffers).float() if buffers else torch.zeros(0), 'params_sample': flat_p[pick], 'grads_sample': flat_g[pick]}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy().astype(np.float32))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: become the launcher.  Nothing here has touched the GPU (no HIP call, torch not
     even imported), so the children are ordinary subprocesses; their stdout (rank 0's single JSON line) is relayed and their exit code
@@ -120,7 +147,11 @@ def main():
     ap.add_argument('--augment', action='store_true', help='BASELINE config 5: colour + eraser augmentation and normalisation of a raw RGB batch on the GPU, inside the timed step')
     ap.add_argument('--half', action='store_true', help='informational: the -half_acc (fp16 NHWC) path; the contract line is fp32')
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--lean', action='store_true', help='profiling aid: only the warm-up and the timed steps (no fwd+bwd-only pass, no kernel pass, no fp32-MFMA pass); prints a reduced line')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also the side measurements: fwd+bwd-only pass, kernel pass (roofline), fp32-MFMA pass, '
+                                                         'CPU baseline and parity at the contract batch')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed (loss, 3-D joints, BatchNorm statistics, seeded samples of '
+                                                          'the updated parameters and of the gradients) as DIR/<name>.npy')
+    ap.add_argument('--lean', action='store_true', help='profiling aid: only the warm-up and the timed steps, with per-step events; prints a reduced line with the per-step spread')
     ap.add_argument('--cpu-steps', type=int, default=2)
     ap.add_argument('--cpu-batch', type=int, default=64, help='batch of the CPU baseline sample (the bench config; 8 = the survey container\'s sample)')
     opt = ap.parse_args()
@@ -230,6 +261,31 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss_value = float(loss)
+    if opt.dump_outputs and rank == 0:
+        dump_outputs(opt.dump_outputs, loss, trainer)
+
+    x3_on = sum(v[0] for v in paths['x3'].values()) // max(opt.steps, 1) > 0       # P3D_X3=0: every conv on the fp32-MFMA instruction -> its own dtype string and peak
+
+    def headline():
+        """The figure the run is for, from the timed steps alone (a plain run prints just this)."""
+        return {
+            'metric': 'crops/sec (fwd+bwd) ResNet-50 pose head, 256x256 bs=64/GPU',
+            'value': round(opt.batch * world * opt.steps / elapsed, 2), 'unit': 'crops/s', 'n_gpus': world, 'steps': opt.steps, 'warmup': opt.warmup,
+            'ms_per_step': round(elapsed / opt.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'dtype': 'f16 (fp32 accumulate, fp32 masters)' if opt.half else ('f32 (3xbf16 split, 6 products, f32 accumulate)' if x3_on else 'f32'), 'data': 'synthetic',
+            'config': {'workload': '%s %s pose head, 256x256 crops, batch %d/GPU, full step: fwd + soft-argmax + SmoothL1 + bwd + '
+                                   'RCCL grad all-reduce + clip + Adam%s' % (opt.family, opt.model, opt.batch, '; on-GPU colour + eraser augmentation + normalisation of the RGB batch' if opt.augment else ''),
+                       'global_batch': opt.batch * world, 'parallelism': 'dp%d' % world, 'final_loss': round(loss_value, 4),
+                       'dist_backend': dist_backend, 'dist_world_size': dist_world, 'rccl_overlap': rccl_overlap,
+                       'wgrad_stream_runs_beside_launch_stream': ops.SIDE_STREAM_OVERLAPS.get(device, ops.SIDE_STREAM_OVERLAPS.get(torch.device('cuda', local_rank)))}}
+
+    if not opt.full and not opt.lean:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     if opt.lean:
         if rank == 0:
@@ -355,20 +411,10 @@ def main():
         # rocprofv3 table: conv kernels + their reduce launches); `kernels_alone` prices the conv kernels' own durations.
         achieved = gflop_crop * opt.batch * ksteps / conv_total_ms             # GFLOP/ms == TFLOP/s
         step_tflops = value / world * gflop_crop / 1e3                          # crops/s x GFLOP/crop, whole step, per GPU
-        x3_on = coverage['x3_launches_per_step'] > 0            # P3D_X3=0: every conv on the fp32-MFMA instruction -> its own dtype string and peak
         peak = BF16_MFMA_PEAK_TFLOPS if opt.half else (X3_PEAK_TFLOPS if x3_on else FP32_MFMA_PEAK_TFLOPS)
-        out = {
-            'metric': 'crops/sec (fwd+bwd) ResNet-50 pose head, 256x256 bs=64/GPU',
-            'value': round(value, 2), 'unit': 'crops/s', 'n_gpus': world, 'steps': opt.steps, 'warmup': opt.warmup,
-            'ms_per_step': round(elapsed / opt.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak',
+        out = headline()
+        out.update({
             'fwd_bwd_crops_per_s': round(opt.batch * world * fsteps / fb_elapsed, 2), 'fwd_bwd_ms_per_step': round(fb_elapsed / fsteps * 1e3, 3),
-            'vs_baseline': None,
-            'dtype': 'f16 (fp32 accumulate, fp32 masters)' if opt.half else ('f32 (3xbf16 split, 6 products, f32 accumulate)' if x3_on else 'f32'), 'data': 'synthetic',
-            'config': {'workload': '%s %s pose head, 256x256 crops, batch %d/GPU, full step: fwd + soft-argmax + SmoothL1 + bwd + '
-                                   'RCCL grad all-reduce + clip + Adam%s' % (opt.family, opt.model, opt.batch, '; on-GPU colour + eraser augmentation + normalisation of the RGB batch' if opt.augment else ''),
-                       'global_batch': opt.batch * world, 'parallelism': 'dp%d' % world, 'final_loss': round(loss_value, 4),
-                       'dist_backend': dist_backend, 'dist_world_size': dist_world, 'rccl_overlap': rccl_overlap,
-                       'wgrad_stream_runs_beside_launch_stream': ops.SIDE_STREAM_OVERLAPS.get(device, ops.SIDE_STREAM_OVERLAPS.get(torch.device('cuda', local_rank)))},
             'roofline': {'bound': 'mfma',
                          'kernel': 'p3d::hconv_gather_kernel / hconv_wgrad_kernel (fp16 MFMA, NHWC)' if opt.half else
                                    ('p3d::fx_conv_kernel / fx16_conv_kernel / fx_wgrad_kernel (conv fwd/dgrad/wgrad: exact fp32 as 6 bf16 piece products on v_mfma_f32_32x32x16_bf16; the 64- and 96-row tiles on v_mfma_f32_16x16x32_bf16)' if x3_on else
@@ -393,7 +439,7 @@ def main():
                                      'with every kernel on one stream (%.3f ms/step)' % (ksteps, serial_elapsed / ksteps * 1e3),
                          'whole_step_tflops': round(step_tflops, 2), 'whole_step_frac': round(step_tflops / peak, 4),
                          'whole_step_frac_of_fp32_mfma_peak': None if opt.half else round(step_tflops / FP32_MFMA_PEAK_TFLOPS, 4)},
-        }
+        })
         if world == 1 and not opt.no_cpu_baseline and opt.family == 'depthnet' and not opt.half:
             del trainer, model, batches                     # the parity step builds its own model
             torch.cuda.empty_cache()

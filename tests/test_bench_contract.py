@@ -1,9 +1,10 @@
-"""bench.py prints exactly one JSON line with the contract's keys (driver contract + the `roofline` / `cpu_baseline` objects)."""
+"""bench.py prints exactly one JSON line with the contract's keys: a plain run the headline figure alone, --full also the `roofline` / `cpu_baseline` objects."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_schema():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--cpu-steps', '1'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '3', '--warmup', '1', '--cpu-steps', '1'],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -49,6 +50,34 @@ def test_bench_line_schema():
     par = line['parity_at_contract_batch']
     assert par['batch'] == 64 and par['loss_rel'] < 1e-3 and par['spec_cam_rel'] < 1e-3, par
     assert line['config']['dist_backend'] is None and line['config']['dist_world_size'] == 1          # N = 1: no process group
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline figure of its timed steps and nothing that takes passes of its own; --dump-outputs writes what the last
+    timed step computed as float .npy files (at most 64 MB)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1', '--dump-outputs', str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    for key, kind in (('metric', str), ('value', float), ('unit', str), ('higher_is_better', bool), ('dtype', str), ('ms_per_step', float), ('config', dict)):
+        assert isinstance(line[key], kind), key
+    assert line['unit'] == 'crops/s' and line['higher_is_better'] is True and line['steps'] == 4 and line['warmup'] == 1 and line['n_gpus'] == 1
+    x3 = os.environ.get('P3D_X3', '1') != '0'
+    assert line['dtype'].startswith('f32 (3xbf16 split') if x3 else line['dtype'] == 'f32'
+    assert line['value'] == pytest.approx(64 * 4 / (line['ms_per_step'] * 4 / 1e3), rel=1e-3)
+    for key in ('roofline', 'cpu_baseline', 'parity_at_contract_batch', 'fp32_mfma_only', 'fwd_bwd_crops_per_s'):
+        assert key not in line, key
+    files = {f.name: np.load(f) for f in tmp_path.iterdir()}
+    assert set(files) == {'loss.npy', 'spec_cam.npy', 'bn_running_stats.npy', 'params_sample.npy', 'grads_sample.npy'}
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20
+    for name, a in files.items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), name
+    assert files['spec_cam.npy'].shape == (64, 17, 3)
+    assert float(files['loss.npy'][0]) == pytest.approx(line['config']['final_loss'], abs=1e-4)
+    assert files['params_sample.npy'].shape == files['grads_sample.npy'].shape == (1 << 20,) and np.abs(files['grads_sample.npy']).max() > 0
 
 
 @pytest.mark.gpu

@@ -6,7 +6,7 @@ echo "probe: $probe ms per step" | tee $O/probe.txt
 if [ "$1" != "any" ] && python -c "import sys; sys.exit(0 if float('$probe') > 27.95 else 1)"; then echo "box at the slow end of the pool: not used for the committed set"; exit 0; fi
 timeout -k 10 900 python -m pytest tests/test_bench_contract.py -x -q -m gpu > $O/pytest_bench.txt 2>&1; echo "pytest exit $?" | tee -a $O/pytest_bench.txt
 grep -q "pytest exit 0" $O/pytest_bench.txt || exit 1
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
 bash tools/profile_r04.sh all > $O/profile.log 2>&1; tail -2 $O/profile.log | cut -c1-200
 bash tools/other_lines.sh 2>&1 | tee $O/other_configs.txt
 b() { python bench.py --lean --steps 20 --warmup 5 "$@" 2>/dev/null | tail -1 | sed 's/.*"value": \([0-9.]*\).*"ms_per_step": \([0-9.]*\).*/\1 crops\/s  \2 ms/'; }

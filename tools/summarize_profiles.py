@@ -48,9 +48,9 @@ def bench_line(log):
 
 def main():
     parts = []
-    for cfg, title in (('serial', 'P3D_WGRAD_STREAM=0 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline  (every kernel alone on the GPU)'),
-                       ('overlap', 'python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline  (product default: wgrad kernels on a second stream)'),
-                       ('half', 'python3 bench.py --half --steps 5 --warmup 2 --no-cpu-baseline  (-half_acc: fp16 NHWC path, informational)')):
+    for cfg, title in (('serial', 'P3D_WGRAD_STREAM=0 python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline  (every kernel alone on the GPU)'),
+                       ('overlap', 'python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline  (product default: wgrad kernels on a second stream)'),
+                       ('half', 'python3 bench.py --full --half --steps 5 --warmup 2 --no-cpu-baseline  (-half_acc: fp16 NHWC path, informational)')):
         src = os.path.join(ROOT, 'gpurun_out', 'prof_%s' % cfg, 'p_kernel_stats.csv')
         if not os.path.exists(src):
             continue
