@@ -22,6 +22,12 @@ class ConvDesc(ctypes.Structure):
                  'accumulate', 'reserved')]
 
 
+class FoldJob(ctypes.Structure):
+    """struct p3d_fold_job (p3d_fx_fold_bn_images)"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ('w', 'conv_bias', 'gamma', 'beta', 'mean', 'var', 'out', 'bias_out')] + \
+               [(n, ctypes.c_int32) for n in ('K', 'C', 'RS', 'c_offset', 'c_total', 'kind')] + [('eps', ctypes.c_float), ('reserved', ctypes.c_int32)]
+
+
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _ptr, _sz = ctypes.c_void_p, ctypes.c_size_t
 _desc = ctypes.POINTER(ConvDesc)
@@ -49,6 +55,11 @@ SIGNATURES = {
     'p3d_fx_weight_image_bytes': (_i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
     'p3d_fx_weight_images': (_i32, [_ptr, _i32, _i32, _i32, _ptr, _ptr, _ptr]),
     'p3d_fx_weight_images_batched': (_i32, [_ptr, _i32, _i32, _ptr]),
+    'p3d_fx_fold_bn_images': (_i32, [_ptr, _i32, _i32, _ptr]),
+    'p3d_fx_conv_fwd_infer_supported': (_i32, [_desc, _i32]),
+    'p3d_fx_conv_fwd_infer_workspace_bytes': (_sz, [_desc]),
+    'p3d_fx_conv_fwd_infer': (_i32, [_desc, _ptr, _ptr, _ptr, _sz, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
+    'p3d_stem_tail_infer': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
     'p3d_hblock_workspace_bytes': (_i32, [_ptr, _ptr, _ptr]),
     'p3d_hblock_fwd': (_i32, [_ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_hblock_bwd': (_i32, [_ptr, _ptr, _ptr, _sz, _ptr, _sz, _ptr, _ptr]),

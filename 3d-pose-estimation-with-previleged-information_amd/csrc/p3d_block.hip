@@ -945,6 +945,35 @@ int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const 
     return wgrad_finish(d, (float*)workspace, splits, d->R * d->S > 1, dw, (hipStream_t)stream);
 }
 
+// Inference with folded BatchNorm (include/p3d_hip.h): the fold of a whole network in one launch, and the forward on the folded images with the inference epilogue.
+int32_t p3d_fx_fold_bn_images(const void* jobs, int32_t njobs, int32_t blocks, void* stream) {
+    P3D_REQUIRE(jobs && njobs > 0 && blocks > 0, "fold_bn_images: bad argument");
+    return fx_fold_bn_images(jobs, njobs, blocks, (hipStream_t)stream);
+}
+
+int32_t p3d_fx_conv_fwd_infer_supported(const p3d_conv_desc* d, int32_t image_fed) {
+    if (!d || d->c_offset != 0 || d->c_total != d->C || d->accumulate < 0 || d->accumulate > 1 || !fx_fwd_applies(d, 32)) return 0;
+    return !image_fed || (d->C % 16 == 0 && (d->H * d->W) % 4 == 0) ? 1 : 0;
+}
+size_t p3d_fx_conv_fwd_infer_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_fwd_workspace(d) : 0; }
+
+int32_t p3d_fx_conv_fwd_infer(const p3d_conv_desc* d, const float* x, const void* x_img, const void* wimg, size_t wimg_bytes, const float* bias, const float* res,
+                              int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    P3D_REQUIRE(d && (x || x_img) && wimg && y, "fx_conv_fwd_infer: null argument");
+    P3D_REQUIRE(p3d_fx_conv_fwd_infer_supported(d, x_img != nullptr), "fx_conv_fwd_infer: shape outside the x3 kernels (N=%d C=%d %dx%d K=%d R=%d stride=%d c_offset=%d c_total=%d)",
+                d->N, d->C, d->H, d->W, d->K, d->R, d->stride, d->c_offset, d->c_total);
+    P3D_REQUIRE(wimg_bytes == fx_weight_image_bytes(d->K, d->C, d->R * d->S, false), "fx_conv_fwd_infer: weight image of %zu B does not belong to K=%d C=%d RS=%d (%zu B)",
+                wimg_bytes, d->K, d->C, d->R * d->S, fx_weight_image_bytes(d->K, d->C, d->R * d->S, false));
+    P3D_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(x_img) |
+                  reinterpret_cast<uintptr_t>(wimg) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "fx_conv_fwd_infer: operands must be 16-B aligned");
+    FxFuse f{};
+    f.act_img = x_img; f.wimg = wimg;
+    f.infer = 1; f.res = res; f.relu = relu ? 1 : 0;
+    ProfScope ps(0, d, (hipStream_t)stream);
+    fx_count(0, d);
+    return fx_conv_fwd(d, x_img ? nullptr : x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
+}
+
 // The stem conv1 = Conv2d(Cin <= 4, K, 7, stride 2, padding 3) (depthnet.py:138) on the x3 kernels: a 4x4 stride-1 convolution over a space-to-depth image of the
 // input (csrc/p3d_fx.hip).  The caller builds the input image once per batch (p3d_stem_image: forward and weight gradient both read it) and the weight image
 // once per optimizer step (p3d_stem_weight_image).

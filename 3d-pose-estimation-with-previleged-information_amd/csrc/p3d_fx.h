@@ -25,6 +25,8 @@ struct FxConvParams {
     const float* emask;     // EPI 4: per-pixel factor of the result, [N][1][YH][YW]
     const float* acc_src;   // dense unsplit launches with `accumulate`: what is added to the result instead of Y's own content (laid out like Y), after
     const unsigned char* acc_mask;   //   masking by these bytes when given (bit e of byte i: element 4 i + e passes): Y = result + src * mask, Y itself is only written
+    const float* ep_res;    // EPIX 8 (inference: conv + folded BatchNorm): residual added after bias and accumulation, laid out like Y, or null
+    int ep_relu;            // EPIX 8: ReLU last
     // EPI 3 (dense unsplit data gradient that writes a block's dx last): per (pixel tile, channel) partial sums of g, g (tail_c - mean), g (tail_rc - rmean) with
     // g = Y * [tail_mask bit], Y the final value (after accumulation): the opening sums of the backward pass of the block that produced this block's input
     const float* tail_c; const float* tail_tab; const float* tail_rc; const float* tail_rtab; const unsigned char* tail_mask; float* tail_partial;   // [tiles_n][M][4]
@@ -78,6 +80,11 @@ struct FxFuse {
     const unsigned char* acc_mask;
     // DGRAD (fx_dgrad_tail_applies): also reduce the opening sums of the producer block's backward pass over the final dx (FxConvParams::tail_*)
     const float* tail_c; const float* tail_tab; const float* tail_rc; const float* tail_rtab; const unsigned char* tail_mask; float* tail_partial;
+    // FWD, inference (a conv with its eval-mode BatchNorm folded into the weight image and the bias): y = conv + bias (+ y when accumulating) (+ res) (then ReLU), on
+    // the split-K path applied by the reduce pass after the slabs are summed
+    int infer;
+    const float* res;
+    int relu;
 };
 constexpr int FX_TAB = 8;   // floats per channel of a table
 
@@ -124,6 +131,8 @@ int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm,
 size_t fx_weight_image_bytes(int K, int C, int RS, bool bwd);
 int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_fwd, void* img_bwd, hipStream_t st, int ctot = 0, int coff = 0);      // ctot > 0: a window of C input channels at coff
 int32_t fx_build_weight_images_batched(const void* jobs, int njobs, int blocks, hipStream_t st);      // jobs: device array of {w, fwd, bwd, K, C, RS, pad} (40 B each)
+// eval-mode BatchNorm folded into forward weight images (p3d_fx_fold_bn_images): jobs = device array of p3d_fold_job
+int32_t fx_fold_bn_images(const void* jobs, int njobs, int blocks, hipStream_t st);
 int32_t fx_conv_wgrad_slabs(const p3d_conv_desc* d, const float* dy, const float* x, float* slabs, int splits, const FxFuse* fuse, hipStream_t st);
 // Pre-split activation images: a fp32 NCHW tensor [N][C][HW] (C % 16 == 0, HW % 4 == 0) as three bf16 planes [N][C/16][HW][16] (hi + mid + lo == value exactly):
 // what the x3 kernels stage into LDS with plain 16-B copies.  mode 0: the tensor itself; 1: relu(x * sc + sh) with the table's constants per channel;

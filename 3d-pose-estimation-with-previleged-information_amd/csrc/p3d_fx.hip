@@ -168,9 +168,10 @@ template <int AMODE, int PRO, int EPIX, bool TAPI = false>
 __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in) {
     static_assert(!TAPI || AMODE == 1, "the tap-inner K order is an image-fed instance");
     // EPIX 5 / 6 / 7 = EPI 1 / 2 / 0 with the result first multiplied by emask[pixel] (a partial convolution inside the residual-block executor: the BatchNorm sums are
-    // taken of the renormalised result); EPIX 4 = the per-layer partial convolution (factor, no sums)
-    constexpr int EPI = EPIX == 5 ? 1 : EPIX == 6 ? 2 : EPIX == 7 ? 0 : EPIX;
-    constexpr bool EM = EPIX == 4 || EPIX >= 5;
+    // taken of the renormalised result); EPIX 4 = the per-layer partial convolution (factor, no sums); EPIX 8 = EPI 0 then (+ ep_res) (ReLU): inference with a folded
+    // BatchNorm (the bias is the folded shift)
+    constexpr int EPI = EPIX == 5 ? 1 : EPIX == 6 ? 2 : EPIX == 7 || EPIX == 8 ? 0 : EPIX;
+    constexpr bool EM = EPIX == 4 || (EPIX >= 5 && EPIX <= 7);
     const FxConvParams p = fx_class_params(p_in);
     static_assert(AMODE == 0 || PRO == 0, "the partial-convolution factor is applied by the in-kernel split");
     // one shared array: two buffers of [3 pixel pieces][3 channel pieces]; after the K loop the result tile on its way out (33.8 KB) and, behind it, the
@@ -562,6 +563,10 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                     } else o4 = *dst;
                     v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3];
                 }
+                if constexpr (EPIX == 8) {
+                    if (p.ep_res) { const f32x4 r4 = *reinterpret_cast<const f32x4*>(p.ep_res + at); v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3]; }
+                    if (p.ep_relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                }
                 *dst = v;
             }
         }
@@ -893,6 +898,10 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
                     } else o4 = *dst;
                     v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3];
                 }
+                if constexpr (EPI == 8) {      // inference (fx_conv_kernel's EPIX 8)
+                    if (p.ep_res) { const f32x4 r4 = *reinterpret_cast<const f32x4*>(p.ep_res + at); v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3]; }
+                    if (p.ep_relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                }
                 *dst = v;
             }
         }
@@ -921,7 +930,8 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
 template <int EPI>
 __global__ __launch_bounds__(256) void fx_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ y, const float* __restrict__ bias, int nsplit,
                                                         size_t slab_stride, int N, int M, int OHW, int accumulate, const float* __restrict__ ep_c,
-                                                        const float* __restrict__ ep_tab, float* __restrict__ partial, const float* __restrict__ emask) {
+                                                        const float* __restrict__ ep_tab, float* __restrict__ partial, const float* __restrict__ emask,
+                                                        const float* __restrict__ res, int relu) {
     const int m = blockIdx.x, grp = blockIdx.y, ngrp = gridDim.y;
     const float bb = bias ? bias[m] : 0.f;
     float esc = 0.f, esh = 0.f, emean = 0.f;
@@ -943,6 +953,8 @@ __global__ __launch_bounds__(256) void fx_reduce_kernel(const float* __restrict_
             }
             f32x4* dst = reinterpret_cast<f32x4*>(y + base + 4 * i);
             if (accumulate) { const f32x4 o = *dst; v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; }
+            if (res) { const f32x4 r4 = *reinterpret_cast<const f32x4*>(res + base + 4 * i); v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3]; }      // inference
+            if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
             *dst = v;
             if constexpr (EPI == 1) {
 #pragma unroll
@@ -1644,6 +1656,7 @@ static int fx16_mode() {
 static int fx16_bm(int M, bool img, int pro, int epi) {
     const int mode = fx16_mode();
     if (epi == 5 || epi == 6 || epi == 7) epi = epi == 7 ? 0 : epi - 4;      // the masked epilogues run on the base instance with the factor pointer set
+    if (epi == 8) epi = 0;                                                     // (inference: EPI 0's tiles)
     if (!img || pro != 0 || (epi != 0 && epi != 1 && epi != 2) || mode == 0) return 0;
     if (M <= 64) return 64;
     if (ceil_div(M, 96) * 96 < ceil_div(M, 128) * 128) return 96;
@@ -1720,8 +1733,9 @@ int fx_partial_rows_dgrad(const p3d_conv_desc* d) {
 // position (tap, row tile, K step, row, half): eight fp32 weights -> three bf16 pieces (here the truncating split: piece = the top 16 bits of what is left;
 // exact like the rounding one), written where fx_conv_kernel's linear 12 KB copy wants them.
 // (ctot / coff: the image covers input channels coff .. coff + C of a weight with ctot of them -- the two halves of fusionnet's concat conv, fusionnet.py:138-139)
+// (scale, fold_bn_images: the forward image of w[m][c][tap] * scale[m], one rounded product per weight)
 __device__ __forceinline__ void fx_weight_image_chunks(const float* __restrict__ w, unsigned char* __restrict__ img, int K, int C, int RS, bool bwd, size_t first, size_t step,
-                                                       int ctot, int coff) {
+                                                       int ctot, int coff, const float* __restrict__ scale = nullptr) {
     const int rows = bwd ? C : K, red = bwd ? K : C;
     const int tiles = (rows + 127) / 128, ksteps = red / FX_BK;
     const size_t total = (size_t)RS * tiles * ksteps * 256;
@@ -1737,6 +1751,7 @@ __device__ __forceinline__ void fx_weight_image_chunks(const float* __restrict__
         for (int e = 0; e < 8; ++e) {
             float x = 0.f;
             if (m < rows) x = bwd ? w[((size_t)(k0 + e) * ctot + coff + m) * RS + tap] : w[((size_t)m * ctot + coff + k0 + e) * RS + tap];
+            if (scale && m < rows) x = x * scale[m];
             const unsigned hb = __builtin_bit_cast(unsigned, x) & 0xFFFF0000u;
             const float r1 = x - __builtin_bit_cast(float, hb);
             const unsigned mb = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
@@ -1770,6 +1785,49 @@ int32_t fx_build_weight_images_batched(const void* jobs, int njobs, int blocks, 
     return check_launch("fx_build_weight_images_batched");
 }
 
+// Eval-mode BatchNorm folded into the weights, for the whole network in ONE launch: grid (blocks, jobs).  Per job every block first computes the fold's
+// per-channel scale s = gamma / sqrtf(var + eps) into LDS (no BatchNorm: s = 1), then strides over the job's output: kind 0 the forward weight image of
+// w * s over input channels [c_offset, c_offset + C) (fx_weight_image_chunks, the layout p3d_fx_weight_images produces), kind 1 the folded fp32 weights
+// [K][C][RS] (the stem, whose image p3d_stem_weight_image restates).  Block 0 also writes b' = beta - mean * s (+ s * conv bias) when bias_out is given.
+// The operation order is fixed (a division, a correctly rounded sqrtf, one product per weight), so the image equals the one built from the fold done in torch.
+constexpr int FX_FOLD_MAX_K = 2048;
+__global__ __launch_bounds__(256) void fx_fold_bn_kernel(const p3d_fold_job* __restrict__ jobs) {
+    const p3d_fold_job j = jobs[blockIdx.y];
+    __shared__ float sc[FX_FOLD_MAX_K];
+    if (j.K <= 0 || j.K > FX_FOLD_MAX_K || j.C <= 0 || j.RS <= 0 || j.c_offset < 0 || j.c_offset + j.C > j.c_total || (j.kind == 0 && j.C % FX_BK != 0)) return;      // (checked by the caller)
+    const bool bn = j.gamma != nullptr;
+    for (int m = threadIdx.x; m < j.K; m += 256) {
+        const float s = bn ? j.gamma[m] / sqrtf(j.var[m] + j.eps) : 1.f;
+        sc[m] = s;
+        if (blockIdx.x == 0 && j.bias_out) {
+            float b = bn ? j.beta[m] - j.mean[m] * s : 0.f;
+            if (j.conv_bias) b = bn ? b + s * j.conv_bias[m] : j.conv_bias[m];
+            j.bias_out[m] = b;
+        }
+    }
+    __syncthreads();
+    const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
+    if (j.kind == 0) {
+        fx_weight_image_chunks(j.w, (unsigned char*)j.out, j.K, j.C, j.RS, false, first, step, j.c_total, j.c_offset, bn ? sc : nullptr);
+    } else {
+        float* out = (float*)j.out;
+        const size_t per = (size_t)j.C * j.RS, total = (size_t)j.K * per;
+        for (size_t i = first; i < total; i += step) {
+            const int m = (int)(i / per);
+            const size_t rest = i - (size_t)m * per;
+            const int c = (int)(rest / j.RS), tap = (int)(rest - (size_t)c * j.RS);
+            const float x = j.w[((size_t)m * j.c_total + j.c_offset + c) * j.RS + tap];
+            out[i] = bn ? x * sc[m] : x;
+        }
+    }
+}
+int32_t fx_fold_bn_images(const void* jobs, int njobs, int blocks, hipStream_t st) {
+    static_assert(sizeof(p3d_fold_job) == 96, "job table layout (infer.py builds it)");
+    if (njobs <= 0) return P3D_OK;
+    hipLaunchKernelGGL(fx_fold_bn_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks), (unsigned)njobs), dim3(256), 0, st, (const p3d_fold_job*)jobs);
+    return check_launch("fx_fold_bn_images");
+}
+
 int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_fwd, void* img_bwd, hipStream_t st, int ctot, int coff) {
     if (ctot <= 0) { ctot = C; coff = 0; }
     const size_t a = img_fwd ? fx_weight_image_bytes(K, C, RS, false) / 48 : 0, b = img_bwd ? fx_weight_image_bytes(K, C, RS, true) / 48 : 0;        // chunk positions (3 chunks each)
@@ -1796,20 +1854,24 @@ static void fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi,
     P3D_FX16_CASE(128, 0) P3D_FX16_CASE(128, 1) P3D_FX16_CASE(128, 2)
     P3D_FX16_CASE(96, 0) P3D_FX16_CASE(96, 1) P3D_FX16_CASE(96, 2)
     P3D_FX16_CASE(64, 0) P3D_FX16_CASE(64, 1) P3D_FX16_CASE(64, 2)
+    P3D_FX16_CASE(128, 8) P3D_FX16_CASE(96, 8) P3D_FX16_CASE(64, 8)
 #undef P3D_FX16_CASE
 #define P3D_FX_CASE(AM, PRO, EPI) if (am == AM && pro == PRO && epi == EPI) { hipLaunchKernelGGL((fx_conv_kernel<AM, PRO, EPI>), grid, dim3(256), 0, st, p); return; }
     P3D_FX_CASE(0, 0, 0) P3D_FX_CASE(0, 0, 1) P3D_FX_CASE(0, 0, 2) P3D_FX_CASE(0, 4, 0) P3D_FX_CASE(0, 4, 4) P3D_FX_CASE(0, 4, 5)
     P3D_FX_CASE(1, 0, 0) P3D_FX_CASE(1, 0, 1) P3D_FX_CASE(1, 0, 2) P3D_FX_CASE(1, 0, 3) P3D_FX_CASE(1, 0, 5) P3D_FX_CASE(1, 0, 6) P3D_FX_CASE(1, 0, 7)
+    P3D_FX_CASE(0, 0, 8) P3D_FX_CASE(1, 0, 8)
 #undef P3D_FX_CASE
+    set_error("fx_launch_conv: no kernel instance for img=%d pro=%d epi=%d bm=%d", am, pro, epi, bm);
 }
 
 static void fx_launch_reduce(int epi, dim3 grid, hipStream_t st, const float* slabs, float* y, const float* bias, int nsplit, size_t slab_stride, int N, int M,
-                             int OHW, int accumulate, const float* ep_c, const float* ep_tab, float* partial, const float* emask) {
-    if (epi == 5 || epi == 6 || epi == 7 || epi == 4) epi = epi == 5 ? 1 : epi == 6 ? 2 : 0;      // the masked epilogues: the base sums over the result times emask
+                             int OHW, int accumulate, const float* ep_c, const float* ep_tab, float* partial, const float* emask, const float* res = nullptr,
+                             int relu = 0) {
+    if (epi == 5 || epi == 6 || epi == 7 || epi == 4 || epi == 8) epi = epi == 5 ? 1 : epi == 6 ? 2 : 0;      // the masked epilogues: the base sums over the result times emask
     prof_kernel_done(st);
-    if (epi == 1) hipLaunchKernelGGL(fx_reduce_kernel<1>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask);
-    else if (epi == 2) hipLaunchKernelGGL(fx_reduce_kernel<2>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask);
-    else hipLaunchKernelGGL(fx_reduce_kernel<0>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask);
+    if (epi == 1) hipLaunchKernelGGL(fx_reduce_kernel<1>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask, res, relu);
+    else if (epi == 2) hipLaunchKernelGGL(fx_reduce_kernel<2>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask, res, relu);
+    else hipLaunchKernelGGL(fx_reduce_kernel<0>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask, res, relu);
 }
 
 // y = conv(x, w) (+ bias); fuse may be null (plain convolution from fp32 x, the weight image built here)
@@ -1820,10 +1882,16 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     // the renormalised result (the residual-block executor: epilogue 5).
     const bool img = fuse && fuse->act_img;
     const bool masked = fuse && (fuse->pmask || fuse->emask);
+    const bool infer = fuse && fuse->infer;
     const void* wimg = fuse ? fuse->wimg : nullptr;
     if (masked && (!fuse->emask || bias || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr))) {
         set_error("fx_conv_fwd: the partial-convolution instances take the output factor, the input factor exactly for an fp32 operand, and no bias"); return P3D_EINVAL;
     }
+    // a cached weight image covers exactly the C input channels it was built for: never pair one with an input-channel window of a wider weight
+    P3D_REQUIRE(!wimg || (d->c_offset == 0 && d->c_total == d->C), "fx_conv_fwd: a cached weight image with a channel window (c_offset %d, c_total %d, C %d)",
+                d->c_offset, d->c_total, d->C);
+    P3D_REQUIRE(!infer || (!masked && !fuse->partial && wimg), "fx_conv_fwd: the inference epilogue takes a cached folded weight image and no other fusion");
+    P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
     const size_t need = fx_fwd_workspace(d);
     if (need && (!workspace || workspace_bytes < need)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
     FxConvParams p{};
@@ -1846,6 +1914,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     if (fuse) {
         if (fuse->partial) { epi = 1; p.partial = fuse->partial; }
         if (masked) { pro = img ? 0 : 4; epi = fuse->partial ? 5 : (img ? 7 : 4); p.pmask = fuse->pmask; p.emask = fuse->emask; }
+        if (infer) { epi = 8; p.ep_res = fuse->res; p.ep_relu = fuse->relu; }
     }
     const int tiles_n = (int)ceil_div(p.NP, FX_BN);
     const FxSplit sp = fx_fwd_split(d);
@@ -1859,7 +1928,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
         p.emask = nullptr;             // (the slabs are raw partial products: the factor, like the sums, belongs to the reduce pass)
         fx_launch_conv(p, img, pro == 4 ? 4 : 0, 0, bm, dim3((unsigned)(p.tiles_m * tiles_n), (unsigned)sp.splits), st);
         fx_launch_reduce(epi, dim3((unsigned)d->K, (unsigned)(d->N < 16 ? d->N : 16)), st, (const float*)ws, y, bias, sp.splits, p.slab_stride, d->N, d->K,
-                         d->Ho * d->Wo, d->accumulate, nullptr, nullptr, p.partial, em);
+                         d->Ho * d->Wo, d->accumulate, nullptr, nullptr, p.partial, em, p.ep_res, p.ep_relu);
     } else {
         fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1), st);
     }
@@ -1874,6 +1943,8 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
     const bool img = fuse && fuse->act_img;
     const bool masked = fuse && (fuse->pmask || fuse->emask);
     const void* wimg = fuse ? fuse->wimg : nullptr;
+    P3D_REQUIRE(!wimg || (d->c_offset == 0 && d->c_total == d->C), "fx_conv_dgrad: a cached weight image with a channel window (c_offset %d, c_total %d, C %d)",
+                d->c_offset, d->c_total, d->C);
     if (masked && (!fuse->emask || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr) || (!img && fuse->partial))) {
         set_error("fx_conv_dgrad: the partial-convolution instances take the result factor and the operand factor exactly for an fp32 operand"); return P3D_EINVAL;
     }

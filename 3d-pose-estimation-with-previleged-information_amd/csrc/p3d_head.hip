@@ -101,6 +101,32 @@ __global__ __launch_bounds__(256) void maxpool_fwd4_kernel(const float* __restri
     }
 }
 
+// Stem tail at inference (p3d_stem_tail_infer): maxpool_fwd4_kernel's footprint on relu(c + bias) = relu(max(c) + bias), the max taken first (fp32 addition and
+// the ReLU are monotone, so the order changes no value); no argmax bytes.  W % 4 == 0.
+__global__ __launch_bounds__(256) void stem_tail_infer_kernel(const float* __restrict__ x, const float* __restrict__ bias, float* __restrict__ y, int C, int NC, int H,
+                                                              int W, int Ho, int Wo) {
+    const int W4 = W / 4;
+    const size_t total = (size_t)NC * Ho * W4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int j = (int)(i % W4);
+        const int ho = (int)((i / W4) % Ho);
+        const size_t nc = i / ((size_t)W4 * Ho);
+        const float* src = x + nc * H * W;
+        float b0 = -INFINITY, b1 = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int hi = 2 * ho - 1 + r;
+            if ((unsigned)hi >= (unsigned)H) continue;
+            const float4 q = *reinterpret_cast<const float4*>(src + (size_t)hi * W + 4 * j);
+            if (j > 0) b0 = fmaxf(b0, src[(size_t)hi * W + 4 * j - 1]);
+            b0 = fmaxf(b0, fmaxf(q.x, q.y));
+            b1 = fmaxf(b1, fmaxf(fmaxf(q.y, q.z), q.w));
+        }
+        const float bb = bias[nc % C];
+        *reinterpret_cast<float2*>(y + (nc * Ho + ho) * Wo + 2 * j) = make_float2(fmaxf(b0 + bb, 0.f), fmaxf(b1 + bb, 0.f));
+    }
+}
+
 __global__ __launch_bounds__(256) void maxpool_bwd4_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ idx, float* __restrict__ dx,
                                                            int NC, int H, int W, int Ho, int Wo) {
     const int W4 = W / 4;
@@ -393,6 +419,16 @@ __global__ __launch_bounds__(64) void recon_cam_bwd_kernel(const float* __restri
 using namespace p3d;
 
 extern "C" {
+
+int32_t p3d_stem_tail_infer(const float* c, const float* bias, float* y, int32_t N, int32_t C, int32_t H, int32_t W, void* stream) {
+    P3D_REQUIRE(c && bias && y && N > 0 && C > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 4 == 0, "stem_tail_infer: bad argument (N=%d C=%d %dx%d)", N, C, H, W);
+    P3D_REQUIRE((((uintptr_t)c & 15) | ((uintptr_t)y & 7)) == 0, "stem_tail_infer: c must be 16-B and y 8-B aligned");
+    const int Ho = H / 2, Wo = W / 2;
+    const int64_t total4 = (int64_t)N * C * Ho * (W / 4);
+    const unsigned blocks = (unsigned)(ceil_div(total4, 256) < 16384 ? ceil_div(total4, 256) : 16384);
+    hipLaunchKernelGGL(stem_tail_infer_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c, bias, y, C, N * C, H, W, Ho, Wo);
+    return check_launch("stem_tail_infer");
+}
 
 int32_t p3d_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int32_t NC, int32_t H, int32_t W, void* stream) {
     P3D_REQUIRE(x && y && NC > 0 && H > 0 && W > 0, "maxpool_fwd: bad argument");

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import dist as p3d_dist
-from . import augment, ops, ops_half, utils
+from . import augment, infer, ops, ops_half, utils
 from .optim import FlatAdam
 
 root_me = os.path.join(os.sep, 'globalwork', 'liu')      # depth_train.py:12; override with -metadata / $P3D_METADATA
@@ -88,6 +88,8 @@ class Trainer:
         self.do_freeze = args.do_freeze
         self.alpha_dest, self.alpha_init, self.alpha_span = args.alpha_dest, args.alpha_init, args.alpha_span
         self.teacher = None
+        self.folded_teacher = None            # P3D_FOLDED_EVAL=1: the teacher with its BatchNorm folded (infer.py), made once it is in eval mode
+        self._eval_net = None                 # P3D_FOLDED_EVAL=1, inside test(): the FoldedNet that evaluates the model
         self.semi_teach = bool(args.semi_teach)
         self.semi_loader = self.semi_worker = None
         # BASELINE config 5: colour / eraser augmentation + normalisation of the RGB stream on the GPU (augment.GpuAugment)
@@ -192,11 +194,11 @@ class Trainer:
         return image.to(device, non_blocking=True)
 
     def vanilla_infer(self, in_image, i_batch=0, ret_last=False):
-        cam_feat, last_feat = self.model(in_image)
+        cam_feat, last_feat = (self._eval_net or self.model)(in_image)
         return (cam_feat, last_feat) if ret_last else cam_feat
 
     def fusion_infer(self, color_image, depth_image, i_batch=0, ret_last=False):
-        cam_feat, last_feat = self.model(color_image, depth_image)
+        cam_feat, last_feat = (self._eval_net or self.model)(color_image, depth_image)
         return (cam_feat, last_feat) if ret_last else cam_feat
 
     # ---- the hot loop --------------------------------------------------------------------------
@@ -341,6 +343,18 @@ class Trainer:
             from . import ops_block                          # opt-in, because the next training epoch then re-allocates it (ops_block.release_buffers)
             torch.cuda.synchronize()
             ops_block.release_buffers(self.model)
+        if infer.enabled() and not self.half_acc:            # P3D_FOLDED_EVAL=1: BatchNorm folded into the x3 convolutions
+            net = getattr(self.model, 'module', self.model)
+            folded = self.__dict__.get('_folded_model')
+            if folded is None or folded.model is not net:
+                folded = self.__dict__['_folded_model'] = infer.fold(net)
+            else:
+                folded.refresh()
+            self._eval_net = folded
+            try:
+                return self._run_test(epoch, test_loader, self.list_params[0].device)
+            finally:
+                self._eval_net = None
         return self._run_test(epoch, test_loader, self.list_params[0].device)      # -do_teach evaluates the student (depth_train.py:613-614)
 
     # ---- distillation: the "privileged information" training (depth_train.py:107-129,161-283,641-647,682-691) --------
@@ -349,6 +363,9 @@ class Trainer:
         if self.half_acc:                                    # depth_train.py:107-108: the teacher runs in fp16 too
             teacher._p3d_half = True
             ops_half.refresh_weights(teacher)
+        self.folded_teacher = None
+        if infer.enabled() and not self.half_acc and not any(m.training for m in teacher.modules() if isinstance(m, torch.nn.BatchNorm2d)):
+            self.folded_teacher = infer.fold(teacher)
 
     def get_dist_weight(self, epoch):
         alphas = np.linspace(self.alpha_init, self.alpha_dest, self.alpha_span)
@@ -359,9 +376,14 @@ class Trainer:
         self.model.freeze_batchnorm()
 
     def teach_infer(self, color_image, depth_image):
+        teacher = self.teacher
+        if infer.enabled() and not self.half_acc and not any(m.training for m in teacher.modules() if isinstance(m, torch.nn.BatchNorm2d)):
+            if self.folded_teacher is None:                  # (the teacher is not trained: folded once, when it first runs in eval mode)
+                self.folded_teacher = infer.fold(teacher)
+            teacher = self.folded_teacher
         if self.do_fusion:
-            return self.teacher(color_image, depth_image)
-        return self.teacher(depth_image if self.depth_only else color_image)
+            return teacher(color_image, depth_image)
+        return teacher(depth_image if self.depth_only else color_image)
 
     def distill(self, batch, teach_last, last_feat, atten_map, weight=1.0, unit_grad=False):
         """Returns (weight * dist_loss, dist_loss); modes as in the reference: -bin_dist, -sigmoid, plain L2 norm."""

@@ -262,6 +262,37 @@ int32_t p3d_fx_conv_dgrad_img(const p3d_conv_desc* d, const void* dy_img, const 
 int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* Inference with eval-mode BatchNorm folded into the convolutions (infer.py): s = gamma / sqrt(var + eps), w' = w * s, b' = beta - mean * s (+ s * conv bias).
+ * p3d_fx_fold_bn_images: ONE launch for a table of jobs (device array of p3d_fold_job); per job kind 0 writes the forward weight image of w' over the input
+ * channels [c_offset, c_offset + C) of a weight with c_total of them -- the image p3d_fx_weight_images builds from the folded fp32 weight, bit for bit --, kind 1 the
+ * folded fp32 weight [K][C][RS] itself (the 7x7 stem: input of p3d_stem_weight_image); bias_out (or NULL) receives b'.  gamma == NULL: no BatchNorm (s = 1, b' = the
+ * conv bias or 0).  blocks: grid width per job.  K <= 2048. */
+typedef struct p3d_fold_job {
+    const float* w;             /* conv weight [K][c_total][RS] */
+    const float* conv_bias;     /* [K] or NULL */
+    const float* gamma;         /* BatchNorm weight, bias, running mean, running variance [K]; all NULL: no BatchNorm */
+    const float* beta;
+    const float* mean;
+    const float* var;
+    void* out;                  /* kind 0: p3d_fx_weight_image_bytes(K, C, RS) forward bytes; kind 1: K * C * RS floats */
+    float* bias_out;            /* [K] or NULL */
+    int32_t K, C, RS, c_offset, c_total, kind;
+    float eps;
+    int32_t reserved;
+} p3d_fold_job;
+int32_t p3d_fx_fold_bn_images(const void* jobs, int32_t njobs, int32_t blocks, void* stream);
+/* y = conv(x, w') + b' (+ y when d->accumulate) (+ res) (then ReLU when relu != 0) from a folded forward weight image of exactly this descriptor's C input channels
+ * (wimg_bytes must be its p3d_fx_weight_image_bytes; c_offset 0, c_total C: a channel window of a wider weight has an image of its own).  The activation comes as the
+ * fp32 x or, when x_img != NULL, as its p3d_fx_act_image; bias / res may be NULL.  Split-K launches apply the same epilogue after summing their slabs.
+ * supported: the forward of d runs on these kernels (image_fed: with an activation image); channel counts down to 32. */
+int32_t p3d_fx_conv_fwd_infer_supported(const p3d_conv_desc* d, int32_t image_fed);
+size_t p3d_fx_conv_fwd_infer_workspace_bytes(const p3d_conv_desc* d);
+int32_t p3d_fx_conv_fwd_infer(const p3d_conv_desc* d, const float* x, const void* x_img, const void* wimg, size_t wimg_bytes, const float* bias, const float* res,
+                              int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* Stem tail at inference behind p3d_stem_fwd on a folded stem image: y = maxpool3x3s2(relu(c + bias[channel])) = relu(maxpool(c) + bias) (both monotone per
+ * channel), no argmax output.  c [N][C][H][W] (H, W even), y [N][C][H/2][W/2]. */
+int32_t p3d_stem_tail_infer(const float* c, const float* bias, float* y, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
+
 /* The stem conv1 = Conv2d(Cin <= 4, K, 7, stride 2, padding 3) (depthnet.py:138) on the x3 kernels: restated as a 4x4 stride-1 convolution over a space-to-depth
  * image of the input (x'[c * 4 + pi * 2 + pj][i][j] = x[c][2 i + pi][2 j + pj], one 16-channel group).  p3d_stem_image: once per batch (forward and weight
  * gradient read it); p3d_stem_weight_image: once per weight update (workspace >= K * 256 floats).  H even, W % 8 == 0, K % 16 == 0, K <= 128. */
