@@ -1788,13 +1788,15 @@ int32_t fx_build_weight_images_batched(const void* jobs, int njobs, int blocks, 
 // Eval-mode BatchNorm folded into the weights, for the whole network in ONE launch: grid (blocks, jobs).  Per job every block first computes the fold's
 // per-channel scale s = gamma / sqrtf(var + eps) into LDS (no BatchNorm: s = 1), then strides over the job's output: kind 0 the forward weight image of
 // w * s over input channels [c_offset, c_offset + C) (fx_weight_image_chunks, the layout p3d_fx_weight_images produces), kind 1 the folded fp32 weights
-// [K][C][RS] (the stem, whose image p3d_stem_weight_image restates).  Block 0 also writes b' = beta - mean * s (+ s * conv bias) when bias_out is given.
+// [K][C][RS] (the stem, whose image p3d_stem_weight_image restates), kind 2 the fp16 forward image [K][RS][Cpad] of the fp16 path (the layout of
+// p3d_weight_images_f16; Cpad in `reserved`, channels C .. Cpad - 1 written as 0).  Block 0 also writes b' = beta - mean * s (+ s * conv bias) when bias_out is given.
 // The operation order is fixed (a division, a correctly rounded sqrtf, one product per weight), so the image equals the one built from the fold done in torch.
 constexpr int FX_FOLD_MAX_K = 2048;
 __global__ __launch_bounds__(256) void fx_fold_bn_kernel(const p3d_fold_job* __restrict__ jobs) {
     const p3d_fold_job j = jobs[blockIdx.y];
     __shared__ float sc[FX_FOLD_MAX_K];
-    if (j.K <= 0 || j.K > FX_FOLD_MAX_K || j.C <= 0 || j.RS <= 0 || j.c_offset < 0 || j.c_offset + j.C > j.c_total || (j.kind == 0 && j.C % FX_BK != 0)) return;      // (checked by the caller)
+    if (j.K <= 0 || j.K > FX_FOLD_MAX_K || j.C <= 0 || j.RS <= 0 || j.c_offset < 0 || j.c_offset + j.C > j.c_total || (j.kind == 0 && j.C % FX_BK != 0) ||
+        (j.kind == 2 && (j.reserved < j.C || j.reserved % 8 != 0))) return;      // (checked by the caller)
     const bool bn = j.gamma != nullptr;
     for (int m = threadIdx.x; m < j.K; m += 256) {
         const float s = bn ? j.gamma[m] / sqrtf(j.var[m] + j.eps) : 1.f;
@@ -1809,6 +1811,21 @@ __global__ __launch_bounds__(256) void fx_fold_bn_kernel(const p3d_fold_job* __r
     const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
     if (j.kind == 0) {
         fx_weight_image_chunks(j.w, (unsigned char*)j.out, j.K, j.C, j.RS, false, first, step, j.c_total, j.c_offset, bn ? sc : nullptr);
+    } else if (j.kind == 2) {
+        _Float16* out = (_Float16*)j.out;
+        const int Cpad = j.reserved;
+        const size_t total = (size_t)j.K * j.RS * Cpad;
+        for (size_t i = first; i < total; i += step) {
+            const int c = (int)(i % Cpad);
+            const int tap = (int)((i / Cpad) % j.RS);
+            const int m = (int)(i / ((size_t)Cpad * j.RS));
+            float x = 0.f;
+            if (c < j.C) {
+                x = j.w[((size_t)m * j.c_total + j.c_offset + c) * j.RS + tap];
+                if (bn) x = x * sc[m];
+            }
+            out[i] = (_Float16)x;
+        }
     } else {
         float* out = (float*)j.out;
         const size_t per = (size_t)j.C * j.RS, total = (size_t)j.K * per;

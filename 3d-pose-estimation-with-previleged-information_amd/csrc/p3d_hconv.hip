@@ -56,8 +56,9 @@ struct HGatherParams {
     const float* bmask;       // partial conv: {0,1} mask over the pixels of B ([N][Hb][Wb]); a masked pixel contributes 0.  or null
     const float* dscale;      // partial conv: per-pixel factor of the result ([N][Hd][Wd]): mult (forward) / mask_in (dgrad).  or null
     float* partial;           // EPI 2 / 3: per-(pixel tile, channel) sums [tiles_n][M / 8][16] (0..7: first sum of the group's 8 channels, 8..15: second), the layout of p3d_hbn.hip
-    const _Float16* ep_x;     // EPI 3: the raw conv output behind the BatchNorm this gradient enters, NHWC like D
+    const _Float16* ep_x;     // EPI 3: the raw conv output behind the BatchNorm this gradient enters, NHWC like D.  EPI 4: the residual (NHWC like D) or null
     const float4* ep_coef;    // EPI 3: that BatchNorm's {sc, sh, mean, invstd} per channel
+    int ep_relu;              // EPI 4: ReLU on the result
     int Hc[HMS], Wc[HMS];
     int r0[HMS], rstep[HMS], nr[HMS], hadd[HMS], hstep[HMS];
     int s0[HMS], sstep[HMS], ns[HMS], wadd[HMS], wstep[HMS];
@@ -72,6 +73,8 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
 // stores of one 256-B run.  EPI 2: + the statistics of the BatchNorm behind this convolution (sum y, sum y^2 of the ROUNDED fp16 values, i.e. what a pass over y would
 // read).  EPI 3: + the sums of the BatchNorm in front of a data gradient (sum g, sum g * xhat with g = the result masked by that layer's ReLU, recomputed from its raw
 // output and constants as hbn_bwd_reduce_kernel does).  EPI 2 / 3 need one pixel class (every block owns a full row of the partial table).
+// EPI 4: inference with a folded BatchNorm, y = fp16(relu?(acc * dscale + bias + res)) rounded once: the fp32 accumulators go through LDS in two passes of 64 channels
+// (EPI 1's 34 KB staging tile in the operand buffers holds 128 pixels x 64 fp32 channels), so the residual is read and the result written in 16-B runs.
 // PIPE: the K step in the order of the fp32 path's kernels -- the registers fetched during the previous step go to LDS behind the step's first MFMAs, then the loads of
 // the step after next are issued, then the rest of the MFMAs run: a fetch has a whole step to arrive and the LDS stores complete under MFMAs instead of in front of the barrier.
 template <int BK, int EPI, bool PIPE>
@@ -205,6 +208,70 @@ __global__ __launch_bounds__(256) void hconv_gather_kernel(HGatherParams p) {
 
     // ---- epilogue: C/D layout col = lane & 31 (pixel), row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (channel):
     //      registers 4g .. 4g+3 are four consecutive channels of one pixel -> one 8-B NHWC store ----
+    if constexpr (EPI == 4) {
+        constexpr int EPITCH = 272;                            // bytes per staged pixel row (64 fp32 channels + 16)
+        static_assert(128 * EPITCH <= 2 * (BM + BN) * ROWB, "the staging tile lives in the operand buffers");
+        float* T = reinterpret_cast<float*>(smem);             // (the K loop ended on a barrier)
+        float dsc[2] = {1.f, 1.f};                             // partial conv: the per-pixel factor of the result
+        if (p.dscale) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int n = n0 + wn * 64 + b * 32 + fr;
+                if (n < ncols) {
+                    const int img = n / (Hc * Wc), rem = n - img * (Hc * Wc);
+                    const int ii = rem / Wc, jj = rem - ii * Wc;
+                    dsc[b] = p.dscale[(size_t)(img * p.Hd + p.dmul * ii + ph) * p.Wd + p.dmul * jj + pw];
+                }
+            }
+        }
+        const int cc = t & 7, pr = t >> 3;                     // this thread: 8-channel chunk cc of pixel rows pr, pr + 32, pr + 64, pr + 96
+        const int npass = (narrow || m0 + 64 >= p.M) ? 1 : 2;
+        for (int h = 0; h < npass; ++h) {
+            if (h > 0) __syncthreads();                        // every read of the previous pass is done
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                const int rb = rbase + a * 32;                 // this sub-tile's first row: written in the pass of its 64-channel half
+                if (a >= na || (rb >> 6) != h) continue;
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        f32x4 o;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) o[e] = acc[a][b][4 * g + e] * dsc[b];
+                        *reinterpret_cast<f32x4*>(reinterpret_cast<unsigned char*>(T) + (wn * 64 + b * 32 + fr) * EPITCH + (rb - 64 * h + 8 * g + 4 * fh) * 4) = o;
+                    }
+            }
+            __syncthreads();
+            const int ch = m0 + 64 * h + cc * 8;
+            if (ch >= p.M) continue;                           // (M % 8 == 0: a chunk is all in or all out)
+            float bias[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) bias[e] = p.bias ? p.bias[ch + e] : 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int pl = pr + 32 * i, n = n0 + pl;
+                if (n >= ncols) continue;
+                const unsigned char* src = reinterpret_cast<const unsigned char*>(T) + pl * EPITCH + cc * 32;
+                const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 16);
+                const int img = n / (Hc * Wc), rem = n - img * (Hc * Wc);
+                const int ii = rem / Wc, jj = rem - ii * Wc;
+                const size_t off = ((size_t)(img * p.Hd + p.dmul * ii + ph) * p.Wd + p.dmul * jj + pw) * p.M + ch;
+                h8 r = {};
+                if (p.ep_x) r = *reinterpret_cast<const h8*>(p.ep_x + off);
+                h8 o;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    float y = (e < 4 ? v0[e] : v1[e - 4]) + bias[e];
+                    if (p.ep_x) y += (float)r[e];
+                    if (p.ep_relu) y = fmaxf(y, 0.f);
+                    o[e] = (_Float16)y;
+                }
+                *reinterpret_cast<h8*>(p.D + off) = o;
+            }
+        }
+        return;
+    }
     if constexpr (EPI != 0) {
         constexpr int EPITCH = 272;                            // bytes per staged pixel row (128 channels + 16: the b128 reads of a 16-lane phase spread over all banks)
         static_assert(128 * EPITCH <= 2 * (BM + BN) * ROWB, "the staging tile lives in the operand buffers");
@@ -652,15 +719,16 @@ static int32_t hvalidate(const p3d_conv_desc* d, const char* what) {
     return P3D_OK;
 }
 
-// epi: 0 plain, 2 + BatchNorm statistics, 3 + BatchNorm-backward sums (p.partial etc. set); a plain launch without bias / factor / accumulate stores through LDS (EPI 1)
+// epi: 0 plain, 2 + BatchNorm statistics, 3 + BatchNorm-backward sums (p.partial etc. set), 4 inference epilogue (bias, residual, ReLU); a plain launch without
+// bias / factor / accumulate stores through LDS (EPI 1)
 static bool g_hstage = [] { const char* e = getenv("P3D_HALF_STAGED_STORE"); return !(e && atoi(e) == 0); }();      // P3D_HALF_STAGED_STORE=0: A/B
 static void launch_gather(const HGatherParams& p, int ncls, int max_cols, hipStream_t st, int epi = 0) {
     const int tiles_n = (int)ceil_div(max_cols, 128);
     dim3 grid((unsigned)(p.tiles_m * tiles_n), (unsigned)ncls);
     static const bool pipe = [] { const char* e = getenv("P3D_HALF_PIPE"); return !(e && atoi(e) == 0); }();      // P3D_HALF_PIPE=0: A/B
-    const int e = epi == 2 ? 2 : epi == 3 ? 3 : (g_hstage && !p.bias && !(p.dscale && p.accumulate)) ? 1 : 0;      // (bias, and a factor on an accumulating launch, keep the single rounding of EPI 0)
+    const int e = epi >= 2 ? epi : (g_hstage && !p.bias && !(p.dscale && p.accumulate)) ? 1 : 0;      // (bias, and a factor on an accumulating launch, keep the single rounding of EPI 0)
 #define P3D_HG_CASE(E) if (e == E) { if (pipe) hipLaunchKernelGGL((hconv_gather_kernel<32, E, true>), grid, dim3(256), 0, st, p); else hipLaunchKernelGGL((hconv_gather_kernel<32, E, false>), grid, dim3(256), 0, st, p); return; }
-    P3D_HG_CASE(0) P3D_HG_CASE(1) P3D_HG_CASE(2) P3D_HG_CASE(3)
+    P3D_HG_CASE(0) P3D_HG_CASE(1) P3D_HG_CASE(2) P3D_HG_CASE(3) P3D_HG_CASE(4)
 #undef P3D_HG_CASE
 }
 
@@ -670,12 +738,8 @@ using namespace p3d;
 
 extern "C" {
 
-static int32_t hconv_fwd_impl(const p3d_conv_desc* d, const void* x, const void* w_krsc, const float* bias, const float* mask_in, const float* mult, void* y,
-                              float* partial, void* stream) {
-    if (int32_t e = hvalidate(d, "hconv2d_fwd")) return e;
-    P3D_REQUIRE(x && w_krsc && y, "hconv2d_fwd: null tensor");
+static HGatherParams hfwd_params(const p3d_conv_desc* d, const void* x, const void* w_krsc, const float* bias, const float* mask_in, const float* mult, void* y) {
     HGatherParams p = {};
-    p.partial = partial;
     p.A = (const _Float16*)w_krsc; p.B = (const _Float16*)x; p.D = (_Float16*)y; p.bias = bias;
     p.bmask = mask_in; p.dscale = mult;
     p.a_bytes = (size_t)d->K * d->R * d->S * d->C * 2; p.b_bytes = (size_t)d->N * d->H * d->W * d->C * 2;
@@ -686,8 +750,34 @@ static int32_t hconv_fwd_impl(const p3d_conv_desc* d, const void* x, const void*
     p.Hc[0] = d->Ho; p.Wc[0] = d->Wo;
     p.r0[0] = 0; p.rstep[0] = 1; p.nr[0] = d->R; p.hadd[0] = -d->pad; p.hstep[0] = d->dil;
     p.s0[0] = 0; p.sstep[0] = 1; p.ns[0] = d->S; p.wadd[0] = -d->pad; p.wstep[0] = d->dil;
+    return p;
+}
+
+static int32_t hconv_fwd_impl(const p3d_conv_desc* d, const void* x, const void* w_krsc, const float* bias, const float* mask_in, const float* mult, void* y,
+                              float* partial, void* stream) {
+    if (int32_t e = hvalidate(d, "hconv2d_fwd")) return e;
+    P3D_REQUIRE(x && w_krsc && y, "hconv2d_fwd: null tensor");
+    HGatherParams p = hfwd_params(d, x, w_krsc, bias, mask_in, mult, y);
+    p.partial = partial;
     launch_gather(p, 1, d->N * d->Ho * d->Wo, (hipStream_t)stream, partial ? 2 : 0);
     return check_launch("hconv2d_fwd");
+}
+
+/* inference with the BatchNorm folded into w_krsc / bias: y = fp16(relu?(conv(x * mask_in) * mult + bias + res)), one rounding, the result and residual moved in 16-B runs */
+int32_t p3d_hconv2d_fwd_infer_supported(const p3d_conv_desc* d) {
+    return hvalidate(d, "hconv2d_fwd_infer") == P3D_OK ? 1 : 0;
+}
+
+int32_t p3d_hconv2d_fwd_infer(const p3d_conv_desc* d, const void* x, const void* w_krsc, const float* bias, const float* mask_in, const float* mult, const void* res,
+                              int32_t relu, void* y, void* stream) {
+    if (int32_t e = hvalidate(d, "hconv2d_fwd_infer")) return e;
+    P3D_REQUIRE(x && w_krsc && y, "hconv2d_fwd_infer: null tensor");
+    P3D_REQUIRE(!d->accumulate, "hconv2d_fwd_infer: accumulate is not supported");
+    HGatherParams p = hfwd_params(d, x, w_krsc, bias, mask_in, mult, y);
+    p.ep_x = (const _Float16*)res;
+    p.ep_relu = relu != 0;
+    launch_gather(p, 1, d->N * d->Ho * d->Wo, (hipStream_t)stream, 4);
+    return check_launch("hconv2d_fwd_infer");
 }
 
 int32_t p3d_hconv2d_fwd(const p3d_conv_desc* d, const void* x, const void* w_krsc, const float* bias, const float* mask_in, const float* mult, void* y,

@@ -88,8 +88,8 @@ class Trainer:
         self.do_freeze = args.do_freeze
         self.alpha_dest, self.alpha_init, self.alpha_span = args.alpha_dest, args.alpha_init, args.alpha_span
         self.teacher = None
-        self.folded_teacher = None            # P3D_FOLDED_EVAL=1: the teacher with its BatchNorm folded (infer.py), made once it is in eval mode
-        self._eval_net = None                 # P3D_FOLDED_EVAL=1, inside test(): the FoldedNet that evaluates the model
+        self.folded_teacher = None            # P3D_FOLDED_EVAL(_HALF)=1: the teacher with its BatchNorm folded (infer.py), made once it is in eval mode
+        self._eval_net = None                 # P3D_FOLDED_EVAL(_HALF)=1, inside test(): the FoldedNet / HalfFoldedNet that evaluates the model
         self.semi_teach = bool(args.semi_teach)
         self.semi_loader = self.semi_worker = None
         # BASELINE config 5: colour / eraser augmentation + normalisation of the RGB stream on the GPU (augment.GpuAugment)
@@ -343,11 +343,12 @@ class Trainer:
             from . import ops_block                          # opt-in, because the next training epoch then re-allocates it (ops_block.release_buffers)
             torch.cuda.synchronize()
             ops_block.release_buffers(self.model)
-        if infer.enabled() and not self.half_acc:            # P3D_FOLDED_EVAL=1: BatchNorm folded into the x3 convolutions
+        if self._folding():                                  # P3D_FOLDED_EVAL=1 / -half_acc with P3D_FOLDED_EVAL_HALF=1: BatchNorm folded into the convolutions
             net = getattr(self.model, 'module', self.model)
-            folded = self.__dict__.get('_folded_model')
+            key = '_folded_half_model' if self.half_acc else '_folded_model'
+            folded = self.__dict__.get(key)
             if folded is None or folded.model is not net:
-                folded = self.__dict__['_folded_model'] = infer.fold(net)
+                folded = self.__dict__[key] = self._fold(net)
             else:
                 folded.refresh()
             self._eval_net = folded
@@ -357,6 +358,13 @@ class Trainer:
                 self._eval_net = None
         return self._run_test(epoch, test_loader, self.list_params[0].device)      # -do_teach evaluates the student (depth_train.py:613-614)
 
+    def _folding(self):
+        """Whether evaluation and the eval-mode teacher run folded: P3D_FOLDED_EVAL=1 in fp32, P3D_FOLDED_EVAL_HALF=1 under -half_acc."""
+        return infer.half_enabled() if self.half_acc else infer.enabled()
+
+    def _fold(self, net):
+        return infer.fold_half(net) if self.half_acc else infer.fold(net)
+
     # ---- distillation: the "privileged information" training (depth_train.py:107-129,161-283,641-647,682-691) --------
     def set_teacher(self, teacher):
         self.teacher = teacher
@@ -364,8 +372,8 @@ class Trainer:
             teacher._p3d_half = True
             ops_half.refresh_weights(teacher)
         self.folded_teacher = None
-        if infer.enabled() and not self.half_acc and not any(m.training for m in teacher.modules() if isinstance(m, torch.nn.BatchNorm2d)):
-            self.folded_teacher = infer.fold(teacher)
+        if self._folding() and not any(m.training for m in teacher.modules() if isinstance(m, torch.nn.BatchNorm2d)):
+            self.folded_teacher = self._fold(teacher)
 
     def get_dist_weight(self, epoch):
         alphas = np.linspace(self.alpha_init, self.alpha_dest, self.alpha_span)
@@ -377,9 +385,9 @@ class Trainer:
 
     def teach_infer(self, color_image, depth_image):
         teacher = self.teacher
-        if infer.enabled() and not self.half_acc and not any(m.training for m in teacher.modules() if isinstance(m, torch.nn.BatchNorm2d)):
+        if self._folding() and not any(m.training for m in teacher.modules() if isinstance(m, torch.nn.BatchNorm2d)):
             if self.folded_teacher is None:                  # (the teacher is not trained: folded once, when it first runs in eval mode)
-                self.folded_teacher = infer.fold(teacher)
+                self.folded_teacher = self._fold(teacher)
             teacher = self.folded_teacher
         if self.do_fusion:
             return teacher(color_image, depth_image)

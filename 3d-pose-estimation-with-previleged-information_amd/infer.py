@@ -12,13 +12,18 @@ p3d_fx_conv_fwd_infer, whose epilogue adds b', the residual and the ReLU, and on
 
 A conv the x3 forward cannot take (odd sizes, fx_fwd_applies) goes through today's eval path for that layer (ops.conv_bn_eval); so do the
 partial-convolution layers of the partial families (their stem and layer1/2, layer5/6), which run as the model's own modules.
+
+`fold_half(model)` is the same for the fp16 (-half_acc) network: kind-2 fold jobs write fp16 [K][R][S][Cpad] images of every w' (the layout
+p3d_weight_images_f16 produces) and `HalfFoldedNet(x[, y])` runs every conv on p3d_hconv2d_fwd_infer, whose epilogue adds b', the residual and the
+ReLU before the one rounding to fp16.  The partial-convolution layers fold too (mask_in in the operand fetch, mult in the epilogue), so an fp16 folded
+forward has no BatchNorm pass at all.
 """
 import ctypes
 import os
 
 import torch
 
-from . import ops
+from . import ops, ops_half
 from ._lib import FoldJob, P3DError, check, lib
 from .nn import _one
 
@@ -33,6 +38,11 @@ def enabled():
     return os.environ.get('P3D_FOLDED_EVAL', '0') == '1'
 
 
+def half_enabled():
+    """P3D_FOLDED_EVAL_HALF=1: under -half_acc, Trainer.test and the distillation teacher evaluate through a HalfFoldedNet."""
+    return os.environ.get('P3D_FOLDED_EVAL_HALF', '0') == '1'
+
+
 def _family(model):
     name = type(model).__module__.rsplit('.', 1)[-1]
     if name not in ('depthnet', 'resnet', 'fusionnet', 'partial_depthnet', 'partial_fusionnet'):
@@ -42,7 +52,7 @@ def _family(model):
 
 def _check_foldable(model):
     if getattr(model, '_p3d_half', False):
-        raise P3DError('infer.fold: a -half_acc (fp16) model cannot be folded; it keeps its own eval path')
+        raise P3DError('infer.fold: a -half_acc (fp16) model cannot be folded onto the fp32 kernels; use infer.fold_half')
     for name, m in model.named_modules():
         if isinstance(m, torch.nn.BatchNorm2d):
             if m.training:
@@ -371,3 +381,226 @@ def fold(model):
     model = getattr(model, 'module', model)
     _check_foldable(model)
     return FoldedNet(model)
+
+
+# ---- -half_acc: BatchNorm folded into the fp16 convolutions ------------------------------------------------------------------------------
+def _check_half_foldable(model):
+    for name, m in model.named_modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            if m.training:
+                raise P3DError('infer.fold_half: BatchNorm %r is in training mode; call model.eval() first (folding uses the running statistics)' % name)
+            if not (m.affine and m.track_running_stats):
+                raise P3DError('infer.fold_half: BatchNorm %r has no running statistics / affine parameters' % name)
+    for p in model.parameters():
+        if not p.is_cuda or p.dtype != torch.float32:
+            raise P3DError('infer.fold_half: parameters must be fp32 masters on the HIP device')
+
+
+class _HConv:
+    """One conv (+ BatchNorm) of the fp16 folded network: its fp16 image [K][R][S][Cpad] and b' in the buffer (fold kind 2).  A head whose K is not a
+    multiple of 8 (the 17-channel mat_regressor of -joint_space) runs with its image and bias padded to Kpad rows of zeros; its result is the first K channels."""
+
+    def __init__(self, conv, bn):
+        from .partial_conv import PartialConv
+        self.conv, self.bn = conv, bn
+        k, c, r, s = conv.weight.shape
+        self.k, self.kpad, self.c, self.cpad, self.r, self.s = k, ops_half.pad8(k), c, ops_half.pad8(c), r, s
+        self.stride, self.pad, self.dil = _one(conv.stride), _one(conv.padding), _one(conv.dilation)
+        self.partial = isinstance(conv, PartialConv)
+        self.foldable = k <= 2048                           # (the fold kernel's per-job scale table; else: today's fp16 path for this layer)
+        self.images = None                                  # fp16 images of the unfolded weight, for that path only
+        self.img_off = self.bias_off = None
+
+    def layout(self, at):
+        if not self.foldable:
+            return at
+        self.img_off = at
+        at = _up(at + 2 * self.kpad * self.r * self.s * self.cpad)           # (rows K .. Kpad - 1 stay zero: the buffer is zeroed once, the fold writes K rows)
+        self.bias_off = at
+        return _up(at + 4 * self.kpad)
+
+    def job(self, buf):
+        if not self.foldable:
+            return None
+        j = FoldJob()
+        j.w = self.conv.weight.data_ptr()
+        j.conv_bias = self.conv.bias.data_ptr() if self.conv.bias is not None else None
+        if self.bn is not None:
+            j.gamma, j.beta = self.bn.weight.data_ptr(), self.bn.bias.data_ptr()
+            j.mean, j.var = self.bn.running_mean.data_ptr(), self.bn.running_var.data_ptr()
+            j.eps = float(self.bn.eps)
+        j.out = buf.data_ptr() + self.img_off
+        j.bias_out = buf.data_ptr() + self.bias_off
+        j.K, j.C, j.RS, j.c_offset, j.c_total, j.kind, j.reserved = self.k, self.c, self.r * self.s, 0, self.c, 2, self.cpad
+        return j
+
+    def desc(self, x):
+        return ops._desc(tuple(x.shape), (self.kpad, self.cpad, self.r, self.s), self.stride, self.pad, self.dil)
+
+
+class HalfFoldedNet:
+    """The -half_acc model's eval forward with every BatchNorm folded into its fp16 convolution, partial-convolution layers included.  Holds one device
+    buffer with every fp16 weight image and b'; reads the fp32 master parameters and running statistics at fold / refresh() time only."""
+
+    def __init__(self, model):
+        _check_half_foldable(model)
+        self.model = model
+        self.family = _family(model)
+        self.device = next(model.parameters()).device
+        self.skip_relu = bool(getattr(model, 'skip_relu', False))
+        self.early_dist = bool(getattr(model, 'early_dist', False))
+        self.convs = []
+        fam = self.family
+        self.stems = {'conv1': self._add(_HConv(model.conv1, model.bn1))}
+        if fam in ('fusionnet', 'partial_fusionnet'):
+            self.stems['conv2'] = self._add(_HConv(model.conv2, model.bn2))
+        layers = {'depthnet': ('layer1', 'layer2', 'layer3', 'layer4'), 'resnet': ('layer1', 'layer2', 'layer3', 'layer4'),
+                  'fusionnet': ('layer1', 'layer2', 'layer3', 'layer4', 'layer5', 'layer6'), 'partial_depthnet': ('layer1', 'layer2', 'layer3', 'layer4'),
+                  'partial_fusionnet': ('layer1', 'layer2', 'layer3', 'layer4', 'layer5', 'layer6')}[fam]
+        self.blocks = {}
+        for lname in layers:
+            plans = []
+            for blk in getattr(model, lname):
+                plan = dict(block=blk, chain=[self._add(_HConv(getattr(blk, c), getattr(blk, b))) for c, b in blk._chain])
+                plan['ds'] = self._add(_HConv(blk.downsample[0], blk.downsample[1])) if blk.downsample is not None else None
+                plans.append(plan)
+            self.blocks[lname] = plans
+        if fam in ('fusionnet', 'partial_fusionnet'):
+            self.fusion = self._add(_HConv(model.fusion.conv, model.fusion.bn))
+        heads = ('cam_regressor', 'mat_regressor') if fam == 'resnet' else ('regressor',)
+        self.heads = [self._add(_HConv(getattr(model, h), None)) if getattr(model, h, None) is not None else None for h in heads]
+        at = 0
+        for c in self.convs:
+            at = c.layout(at)
+        self.buffer = torch.zeros(max(at, _ALIGN), dtype=torch.uint8, device=self.device)
+        self.refresh()
+
+    def _add(self, c):
+        self.convs.append(c)
+        return c
+
+    # ---- folding ------------------------------------------------------------------------------------------------
+    def refresh(self):
+        """Re-fold every conv from the current fp32 parameters and running statistics: one fold launch for the whole network."""
+        _check_half_foldable(self.model)
+        jobs = [j for j in (c.job(self.buffer) for c in self.convs) if j is not None]
+        if jobs:
+            table = (FoldJob * len(jobs))(*jobs)
+            self._jobs = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(self.device)     # (kept alive until the launch has read it)
+            check(lib().p3d_fx_fold_bn_images(ops._p(self._jobs), len(jobs), 64, ops._stream()), 'p3d_fx_fold_bn_images')
+        for c in self.convs:
+            if c.images is not None:
+                c.images.refresh(c.conv.weight)
+        return self
+
+    def _at(self, off):
+        return ctypes.c_void_p(self.buffer.data_ptr() + off)
+
+    def bias(self, c):
+        """b' of a folded conv as a tensor view of the buffer (tests)."""
+        return self.buffer[c.bias_off:c.bias_off + 4 * c.k].view(torch.float32)
+
+    def image(self, c):
+        """The fp16 folded forward image [K][R][S][Cpad] of a conv (tests)."""
+        return self.buffer[c.img_off:c.img_off + 2 * c.k * c.r * c.s * c.cpad].view(torch.float16).view(c.k, c.r, c.s, c.cpad)
+
+    # ---- forward ---------------------------------------------------------------------------------------------------
+    def _conv(self, c, x, res=None, relu=False, mask_in=None, mult=None):
+        """y = fp16(relu?(conv(x * mask_in) * mult + b' + res)) on the folded image; a conv the entry point cannot take runs on today's fp16 path."""
+        L = lib()
+        d = c.desc(x)
+        if c.foldable and L.p3d_hconv2d_fwd_infer_supported(ctypes.byref(d)):
+            y = ops_half._empty(d.N, d.K, d.Ho, d.Wo, x.device)
+            check(L.p3d_hconv2d_fwd_infer(ctypes.byref(d), ops._p(x), self._at(c.img_off), self._at(c.bias_off), ops._p(mask_in), ops._p(mult),
+                                          ops._p(res), int(bool(relu)), ops._p(y), ops._stream()), 'p3d_hconv2d_fwd_infer')
+            return y if c.kpad == c.k else y[:, :c.k]
+        if c.images is None:                                # per-layer fallback: the unfolded conv, then the eval-mode BatchNorm pass
+            c.images = ops_half.WeightImages(c.conv.weight, need_dgrad=False)
+            c.images.refresh(c.conv.weight)
+        y = ops_half.HConv2dFn.apply(x, c.conv.weight, c.conv.bias, c.images, c.stride, c.pad, c.dil, None, None, mask_in, mult)
+        if c.bn is None:
+            return ops_half.relu(y) if relu else y
+        bn = c.bn
+        return ops_half.batch_norm_act(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, res, relu, False, 0.0, bn.eps)
+
+    def _pconv(self, c, x, veil, res=None, relu=True):
+        """A partial convolution (partial_conv.py): mask_in = veil, mult and mask_out from its box count; returns (y, mask_out)."""
+        mult, mask_out = ops.mask_count(veil, c.r, c.stride, c.pad, c.dil)
+        return self._conv(c, x, res, relu, mask_in=veil.contiguous(), mult=mult), mask_out
+
+    def _pool(self, x):
+        """max pool 3x3 / 2 behind the folded stem (its ReLU already applied: max and ReLU commute per channel), no window codes."""
+        n, c, h, w = x.shape
+        y = ops_half._empty(n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1, x.device)
+        check(lib().p3d_hmaxpool3x3s2_fwd(ops._p(x), ops._p(y), None, n, h, w, c, ops._stream()), 'p3d_hmaxpool3x3s2_fwd')
+        return y
+
+    def _layer(self, name, x, veil=None):
+        for plan in self.blocks[name]:
+            blk = plan['block']
+            res = x if plan['ds'] is None else self._conv(plan['ds'], x)
+            out, last = x, len(plan['chain']) - 1
+            for i, c in enumerate(plan['chain']):
+                if blk.partial:                             # (the closing ReLU of a partial block is unconditional, partial_depthnet.py:70-75)
+                    out, veil = self._pconv(c, out, veil, res if i == last else None)
+                else:
+                    out = self._conv(c, out, res if i == last else None, relu=(i < last) or not blk.skip_relu)
+            x = out
+        return x if veil is None else (x, veil)
+
+    @staticmethod
+    def _in(x):
+        x = x.float() if x.dtype == torch.float16 else x
+        return ops_half.to_half_nhwc(x, ops_half.pad8(x.shape[1]))
+
+    @staticmethod
+    def _out(*tensors):
+        out = tuple(ops_half.to_float(t) for t in tensors)
+        return out if len(out) > 1 else out[0]
+
+    def __call__(self, x, y=None):
+        with torch.no_grad():
+            return self._forward(x, y)
+
+    def _forward(self, x, y):
+        m, fam = self.model, self.family
+        relu = ops_half.relu
+        if fam == 'partial_depthnet':
+            veil = ops.nonzero_mask(x.float())
+            h, veil = self._pconv(self.stems['conv1'], self._in(x), veil)
+            h, veil = self._pool(h), m.maxpool(veil)
+            h, veil = self._layer('layer1', h, veil)
+            h, _ = self._layer('layer2', h, veil)
+            h = self._layer('layer4', self._layer('layer3', h))
+            return self._out(self._conv(self.heads[0], h), h)
+        x = self._pool(self._conv(self.stems['conv1'], self._in(x), relu=True))
+        if fam == 'resnet':
+            for name in ('layer1', 'layer2', 'layer3', 'layer4'):
+                x = self._layer(name, x)
+            return self._out(*[self._conv(c, x) for c in self.heads if c is not None])
+        x = self._layer('layer2', self._layer('layer1', x))
+        if fam == 'fusionnet':
+            y = self._pool(self._conv(self.stems['conv2'], self._in(y), relu=True))
+            y = self._layer('layer6', self._layer('layer5', y))
+            x = self._conv(self.fusion, ops_half.concat(x, y), relu=True)
+        elif fam == 'partial_fusionnet':
+            veil = ops.nonzero_mask(y.float())
+            y, veil = self._pconv(self.stems['conv2'], self._in(y), veil)
+            y, veil = self._pool(y), m.maxpool(veil)
+            y, veil = self._layer('layer5', y, veil)
+            y, _ = self._layer('layer6', y, veil)
+            x = self._conv(self.fusion, ops_half.concat(x, y), relu=True)
+            x = self._layer('layer4', self._layer('layer3', x))
+            return self._out(self._conv(self.heads[0], x), x)
+        a = self._layer('layer3', x)
+        n = self._layer('layer4', relu(a) if self.skip_relu else a)
+        z = self._conv(self.heads[0], relu(n) if self.skip_relu else n)
+        return self._out(z, a if self.early_dist else n)
+
+
+def fold_half(model):
+    """HalfFoldedNet of a -half_acc network in eval mode: fp32 (or fp16) NCHW input, fp32 NCHW outputs, as model.eval()(x) returns them under
+    -half_acc.  Raises P3DError for a BatchNorm in training mode or parameters that are not fp32 on the HIP device."""
+    model = getattr(model, 'module', model)
+    _check_half_foldable(model)
+    return HalfFoldedNet(model)

@@ -265,8 +265,9 @@ int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const 
 /* Inference with eval-mode BatchNorm folded into the convolutions (infer.py): s = gamma / sqrt(var + eps), w' = w * s, b' = beta - mean * s (+ s * conv bias).
  * p3d_fx_fold_bn_images: ONE launch for a table of jobs (device array of p3d_fold_job); per job kind 0 writes the forward weight image of w' over the input
  * channels [c_offset, c_offset + C) of a weight with c_total of them -- the image p3d_fx_weight_images builds from the folded fp32 weight, bit for bit --, kind 1 the
- * folded fp32 weight [K][C][RS] itself (the 7x7 stem: input of p3d_stem_weight_image); bias_out (or NULL) receives b'.  gamma == NULL: no BatchNorm (s = 1, b' = the
- * conv bias or 0).  blocks: grid width per job.  K <= 2048. */
+ * folded fp32 weight [K][C][RS] itself (the 7x7 stem: input of p3d_stem_weight_image), kind 2 the fp16 forward image [K][RS][Cpad] of w' (-half_acc: the image
+ * p3d_weight_images_f16 builds from the folded fp32 weight, bit for bit; channels C .. Cpad - 1 are 0); bias_out (or NULL) receives b'.  gamma == NULL: no BatchNorm
+ * (s = 1, b' = the conv bias or 0).  Kinds may be mixed in one table.  blocks: grid width per job.  K <= 2048. */
 typedef struct p3d_fold_job {
     const float* w;             /* conv weight [K][c_total][RS] */
     const float* conv_bias;     /* [K] or NULL */
@@ -274,11 +275,11 @@ typedef struct p3d_fold_job {
     const float* beta;
     const float* mean;
     const float* var;
-    void* out;                  /* kind 0: p3d_fx_weight_image_bytes(K, C, RS) forward bytes; kind 1: K * C * RS floats */
+    void* out;                  /* kind 0: p3d_fx_weight_image_bytes(K, C, RS) forward bytes; kind 1: K * C * RS floats; kind 2: K * RS * Cpad halves */
     float* bias_out;            /* [K] or NULL */
     int32_t K, C, RS, c_offset, c_total, kind;
     float eps;
-    int32_t reserved;
+    int32_t reserved;           /* kind 2: Cpad, the padded channel count of the fp16 image (>= C, multiple of 8); kinds 0 / 1: unused */
 } p3d_fold_job;
 int32_t p3d_fx_fold_bn_images(const void* jobs, int32_t njobs, int32_t blocks, void* stream);
 /* y = conv(x, w') + b' (+ y when d->accumulate) (+ res) (then ReLU when relu != 0) from a folded forward weight image of exactly this descriptor's C input channels
@@ -485,6 +486,13 @@ int32_t p3d_normalize_rgb(float* img, int32_t B, int32_t HW, const float* mean3,
 int32_t p3d_hconv2d_fwd(const p3d_conv_desc* d, const void* x_nhwc, const void* w_krsc, const float* bias, const float* mask_in,
                         const float* mult, void* y_nhwc, void* stream);
 int32_t p3d_hscale_pixels(const void* src_nhwc, const float* scale, void* dst_nhwc, int64_t P, int32_t C, void* stream);
+/* Inference with an eval-mode BatchNorm folded into the weight image (infer.fold_half; w_krsc from p3d_fx_fold_bn_images kind 2, bias = b'):
+ * y = fp16(relu?(conv(x * mask_in) * mult + bias + res)), rounded once.  res is NHWC fp16 shaped like y, or NULL; bias, mask_in and mult may be NULL.
+ * The result leaves through LDS as 16-B stores, the residual is read in 16-B runs.  d->accumulate must be 0.
+ * supported: 1 when the descriptor runs on this entry point (else 0, the reason in p3d_last_error()). */
+int32_t p3d_hconv2d_fwd_infer_supported(const p3d_conv_desc* d);
+int32_t p3d_hconv2d_fwd_infer(const p3d_conv_desc* d, const void* x_nhwc, const void* w_krsc, const float* bias, const float* mask_in, const float* mult,
+                              const void* res_nhwc, int32_t relu, void* y_nhwc, void* stream);
 /* d->accumulate != 0: dx += result (joins the gradient another consumer of the same input already wrote) */
 int32_t p3d_hconv2d_dgrad(const p3d_conv_desc* d, const void* dy_nhwc, const void* w_crsk, const float* mask_in, void* dx_nhwc, void* stream);
 /* A convolution whose epilogue also leaves the channel sums of the BatchNorm next to it (round 4; what the fp32 path's EPI 1 / 2 do), so that the BatchNorm costs no
@@ -548,7 +556,7 @@ int32_t p3d_hbn_frozen_bwd(const void* dy, const void* x, const void* y, const f
 int32_t p3d_hconcat(void* a, void* b, void* cat, int64_t P, int32_t Ca, int32_t Cb, int32_t split, void* stream);
 /* standalone F.relu on fp16 (-skip_relu, depthnet.py:197-198): dy == NULL -> out = relu(x); else out = dy masked by x > 0 */
 int32_t p3d_hrelu(const void* x, const void* dy, void* out, int64_t n, void* stream);
-/* nn.MaxPool2d(3, 2, 1) on NHWC fp16; idx [N][Ho][Wo][C] uint8 window codes as in p3d_maxpool3x3s2_fwd */
+/* nn.MaxPool2d(3, 2, 1) on NHWC fp16; idx [N][Ho][Wo][C] uint8 window codes as in p3d_maxpool3x3s2_fwd, or NULL (inference: no window codes written) */
 int32_t p3d_hmaxpool3x3s2_fwd(const void* x, void* y, uint8_t* idx, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 int32_t p3d_hmaxpool3x3s2_bwd(const void* dy, const uint8_t* idx, void* dx, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 

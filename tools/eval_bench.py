@@ -4,7 +4,11 @@
 Legs, timed in the same process, alternating (device-synchronised, 10 warm-up + 50 timed iterations per round):
   fused     today's eval path: conv + BN (+ res + ReLU) per layer in one kernel (ops.conv_bn_eval, the fp32-MFMA kernel)
   folded    infer.fold(model): BatchNorm folded into the x3 convolutions (p3d_fx_conv_fwd_infer)
---separate adds the round-1 leg with stand-alone BatchNorm passes; --distill also times one distill_step with and without the folded teacher.
+--half replaces them with the -half_acc legs:
+  half          today's fp16 eval forward: fp16 conv, then a stand-alone eval-mode BatchNorm (+ res + ReLU) pass per layer
+  half_folded   infer.fold_half(model): BatchNorm folded into the fp16 convolutions (p3d_hconv2d_fwd_infer)
+--separate adds the round-1 leg with stand-alone BatchNorm passes; --distill also times one distill_step with and without the folded teacher
+(with --half: a -half_acc student and teacher, P3D_FOLDED_EVAL_HALF).
 Prints one line per leg and round, then a JSON summary line."""
 import argparse
 import importlib
@@ -28,6 +32,7 @@ ap.add_argument('--iters', type=int, default=50)
 ap.add_argument('--rounds', type=int, default=3)
 ap.add_argument('--separate', action='store_true')
 ap.add_argument('--distill', action='store_true')
+ap.add_argument('--half', action='store_true', help='-half_acc legs: half / half_folded')
 ap.add_argument('--only', default=None, help='time one leg only (profiling runs)')
 opt = ap.parse_args()
 
@@ -35,9 +40,15 @@ args = pkg.opts.parse(['-model', opt.model, '-suffix', 'b', '-data_name', 'h36m'
                        '-side_in', str(opt.side)])
 model = pkg.depth_main.create_model(args)[0].cuda().eval()
 x = torch.randn(opt.batch, 3, opt.side, opt.side, device='cuda')
-folded = pkg.infer.fold(model)
 fuse = pkg.ops.can_fuse_eval
-legs = {'fused': lambda: model(x), 'folded': lambda: folded(x)}
+if opt.half:
+    model._p3d_half = True                              # what the Trainer sets under -half_acc
+    pkg.ops_half.refresh_weights(model)
+    hfolded = pkg.infer.fold_half(model)
+    legs = {'half': lambda: model(x), 'half_folded': lambda: hfolded(x)}
+else:
+    folded = pkg.infer.fold(model)
+    legs = {'fused': lambda: model(x), 'folded': lambda: folded(x)}
 if opt.separate:
     legs['separate'] = lambda: model(x)
 if opt.only:
@@ -69,7 +80,8 @@ summary = {k: dict(ms_median=sorted(v)[len(v) // 2] * 1e3, ms_min=min(v) * 1e3, 
 
 if opt.distill:
     dargs = pkg.opts.parse(['-model', opt.model, '-suffix', 'b', '-data_name', 'h36m', '-save_path', '/tmp/p3d', '-criterion', 'SmoothL1', '-num_joints', '17',
-                            '-side_in', str(opt.side), '-do_teach', '-do_fusion'])
+                            '-side_in', str(opt.side), '-do_teach', '-do_fusion'] + (['-half_acc'] if opt.half else []))
+    switch = 'P3D_FOLDED_EVAL_HALF' if opt.half else 'P3D_FOLDED_EVAL'
     student = pkg.depthnet.__dict__[opt.model](dargs, False).cuda()
     teacher = pkg.fusionnet.__dict__[opt.model](dargs, False).cuda().eval()
     c, d, tc, tv = (torch.from_numpy(a).cuda() for a in pkg.synth.make_batch(opt.batch, side=opt.side, rank=0, step=0))
@@ -78,9 +90,10 @@ if opt.distill:
     res = {}
     for r in range(opt.rounds):
         for on in ('0', '1'):
-            os.environ['P3D_FOLDED_EVAL'] = on
+            os.environ[switch] = on
             tr = pkg.depth_train.Trainer(dargs, student, pkg.utils.get_info()) if r == 0 and on == '0' else tr
             tr.set_teacher(teacher)
+            assert (tr.folded_teacher is not None) == (on == '1')
             for _ in range(3):
                 tr.distill_step(1, c, d, tc, tv, att)
             torch.cuda.synchronize()
@@ -92,4 +105,4 @@ if opt.distill:
             res.setdefault('folded_teacher' if on == '1' else 'teacher', []).append(dt * 1e3)
             print('round %d  distill_step %-15s %.2f ms' % (r, 'folded_teacher' if on == '1' else 'teacher', dt * 1e3), flush=True)
     summary['distill_step_ms'] = {k: sorted(v) for k, v in res.items()}
-print(json.dumps(dict(model=opt.model, batch=opt.batch, side=opt.side, warmup=opt.warmup, iters=opt.iters, legs=summary)))
+print(json.dumps(dict(model=opt.model, half=opt.half, batch=opt.batch, side=opt.side, warmup=opt.warmup, iters=opt.iters, legs=summary)))
