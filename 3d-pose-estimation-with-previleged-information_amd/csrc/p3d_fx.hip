@@ -169,8 +169,9 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     static_assert(!TAPI || AMODE == 1, "the tap-inner K order is an image-fed instance");
     // EPIX 5 / 6 / 7 = EPI 1 / 2 / 0 with the result first multiplied by emask[pixel] (a partial convolution inside the residual-block executor: the BatchNorm sums are
     // taken of the renormalised result); EPIX 4 = the per-layer partial convolution (factor, no sums); EPIX 8 = EPI 0 then (+ ep_res) (ReLU): inference with a folded
-    // BatchNorm (the bias is the folded shift)
-    constexpr int EPI = EPIX == 5 ? 1 : EPIX == 6 ? 2 : EPIX == 7 || EPIX == 8 ? 0 : EPIX;
+    // BatchNorm (the bias is the folded shift); EPIX 9 = EPIX 8 of a partial convolution: acc * emask[pixel] + bias (+ ep_res) (ReLU), the factor BEFORE the
+    // folded shift (an empty window, emask = 0, gives relu(b' + res): the reference's partial conv writes 0 there and the BatchNorm behind it maps 0 to b')
+    constexpr int EPI = EPIX == 5 ? 1 : EPIX == 6 ? 2 : EPIX == 7 || EPIX == 8 || EPIX == 9 ? 0 : EPIX;
     constexpr bool EM = EPIX == 4 || (EPIX >= 5 && EPIX <= 7);
     const FxConvParams p = fx_class_params(p_in);
     static_assert(AMODE == 0 || PRO == 0, "the partial-convolution factor is applied by the in-kernel split");
@@ -479,7 +480,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                 const int m = m0 + wm * 64 + b * 32 + fr;
                 if (m >= p.M) continue;
                 f32x4 v = {acc[a][b][4 * g], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]};
-                if (!split) {
+                if (!split && EPIX != 9) {        // (EPIX 9: factor and bias in the staged store below, where no accumulator is live)
                     if (p.bias) { const float bb = p.bias[m]; v[0] += bb; v[1] += bb; v[2] += bb; v[3] += bb; }
                 }
                 if (dense) {
@@ -563,7 +564,12 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                     } else o4 = *dst;
                     v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3];
                 }
-                if constexpr (EPIX == 8) {
+                if constexpr (EPIX == 9) {        // (fx_conv_fwd launches it dense, unsplit and without accumulate: one factor per pixel, the plane of image n)
+                    const f32x4 em = *reinterpret_cast<const f32x4*>(p.emask + (size_t)n * OHW + rem);
+                    const float bb = p.bias ? p.bias[m] : 0.f;
+                    v[0] = v[0] * em[0] + bb; v[1] = v[1] * em[1] + bb; v[2] = v[2] * em[2] + bb; v[3] = v[3] * em[3] + bb;
+                }
+                if constexpr (EPIX == 8 || EPIX == 9) {
                     if (p.ep_res) { const f32x4 r4 = *reinterpret_cast<const f32x4*>(p.ep_res + at); v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3]; }
                     if (p.ep_relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
                 }
@@ -946,10 +952,17 @@ __global__ __launch_bounds__(256) void fx_reduce_kernel(const float* __restrict_
                 const f32x4 u = *reinterpret_cast<const f32x4*>(slabs + (size_t)z * slab_stride + base + 4 * i);
                 v[0] += u[0]; v[1] += u[1]; v[2] += u[2]; v[3] += u[3];
             }
-            v[0] += bb; v[1] += bb; v[2] += bb; v[3] += bb;
-            if (emask) {         // partial convolution: the per-pixel factor of the result (the split launches carry no epilogue)
+            if (emask && bias) {
+                // folded partial convolution at inference (EPIX 9): the factor first, then b', so that an empty window (factor 0) gives b'.  Only this pairing takes
+                // the order: the training instances pass no bias with a factor, and their (v + 0) * em keeps the sign of a zero that v * em + 0 would not.
                 const f32x4 em = *reinterpret_cast<const f32x4*>(emask + (size_t)n * OHW + 4 * i);
-                v[0] *= em[0]; v[1] *= em[1]; v[2] *= em[2]; v[3] *= em[3];
+                v[0] = v[0] * em[0] + bb; v[1] = v[1] * em[1] + bb; v[2] = v[2] * em[2] + bb; v[3] = v[3] * em[3] + bb;
+            } else {
+                v[0] += bb; v[1] += bb; v[2] += bb; v[3] += bb;
+                if (emask) {         // partial convolution: the per-pixel factor of the result (the split launches carry no epilogue)
+                    const f32x4 em = *reinterpret_cast<const f32x4*>(emask + (size_t)n * OHW + 4 * i);
+                    v[0] *= em[0]; v[1] *= em[1]; v[2] *= em[2]; v[3] *= em[3];
+                }
             }
             f32x4* dst = reinterpret_cast<f32x4*>(y + base + 4 * i);
             if (accumulate) { const f32x4 o = *dst; v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; }
@@ -1876,7 +1889,7 @@ static void fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi,
 #define P3D_FX_CASE(AM, PRO, EPI) if (am == AM && pro == PRO && epi == EPI) { hipLaunchKernelGGL((fx_conv_kernel<AM, PRO, EPI>), grid, dim3(256), 0, st, p); return; }
     P3D_FX_CASE(0, 0, 0) P3D_FX_CASE(0, 0, 1) P3D_FX_CASE(0, 0, 2) P3D_FX_CASE(0, 4, 0) P3D_FX_CASE(0, 4, 4) P3D_FX_CASE(0, 4, 5)
     P3D_FX_CASE(1, 0, 0) P3D_FX_CASE(1, 0, 1) P3D_FX_CASE(1, 0, 2) P3D_FX_CASE(1, 0, 3) P3D_FX_CASE(1, 0, 5) P3D_FX_CASE(1, 0, 6) P3D_FX_CASE(1, 0, 7)
-    P3D_FX_CASE(0, 0, 8) P3D_FX_CASE(1, 0, 8)
+    P3D_FX_CASE(0, 0, 8) P3D_FX_CASE(1, 0, 8) P3D_FX_CASE(0, 4, 9)
 #undef P3D_FX_CASE
     set_error("fx_launch_conv: no kernel instance for img=%d pro=%d epi=%d bm=%d", am, pro, epi, bm);
 }
@@ -1884,7 +1897,7 @@ static void fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi,
 static void fx_launch_reduce(int epi, dim3 grid, hipStream_t st, const float* slabs, float* y, const float* bias, int nsplit, size_t slab_stride, int N, int M,
                              int OHW, int accumulate, const float* ep_c, const float* ep_tab, float* partial, const float* emask, const float* res = nullptr,
                              int relu = 0) {
-    if (epi == 5 || epi == 6 || epi == 7 || epi == 4 || epi == 8) epi = epi == 5 ? 1 : epi == 6 ? 2 : 0;      // the masked epilogues: the base sums over the result times emask
+    if (epi == 5 || epi == 6 || epi == 7 || epi == 4 || epi == 8 || epi == 9) epi = epi == 5 ? 1 : epi == 6 ? 2 : 0;      // the masked epilogues: the base sums over the result times emask
     prof_kernel_done(st);
     if (epi == 1) hipLaunchKernelGGL(fx_reduce_kernel<1>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask, res, relu);
     else if (epi == 2) hipLaunchKernelGGL(fx_reduce_kernel<2>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask, res, relu);
@@ -1901,13 +1914,14 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     const bool masked = fuse && (fuse->pmask || fuse->emask);
     const bool infer = fuse && fuse->infer;
     const void* wimg = fuse ? fuse->wimg : nullptr;
-    if (masked && (!fuse->emask || bias || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr))) {
+    if (masked && (!fuse->emask || (bias && !infer) || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr))) {
         set_error("fx_conv_fwd: the partial-convolution instances take the output factor, the input factor exactly for an fp32 operand, and no bias"); return P3D_EINVAL;
     }
     // a cached weight image covers exactly the C input channels it was built for: never pair one with an input-channel window of a wider weight
     P3D_REQUIRE(!wimg || (d->c_offset == 0 && d->c_total == d->C), "fx_conv_fwd: a cached weight image with a channel window (c_offset %d, c_total %d, C %d)",
                 d->c_offset, d->c_total, d->C);
-    P3D_REQUIRE(!infer || (!masked && !fuse->partial && wimg), "fx_conv_fwd: the inference epilogue takes a cached folded weight image and no other fusion");
+    P3D_REQUIRE(!infer || (!fuse->partial && wimg && (!masked || (!img && !d->accumulate))),
+                "fx_conv_fwd: the inference epilogue takes a cached folded weight image, no other fusion, and a partial convolution only from an fp32 operand");
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
     const size_t need = fx_fwd_workspace(d);
     if (need && (!workspace || workspace_bytes < need)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
@@ -1931,7 +1945,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     if (fuse) {
         if (fuse->partial) { epi = 1; p.partial = fuse->partial; }
         if (masked) { pro = img ? 0 : 4; epi = fuse->partial ? 5 : (img ? 7 : 4); p.pmask = fuse->pmask; p.emask = fuse->emask; }
-        if (infer) { epi = 8; p.ep_res = fuse->res; p.ep_relu = fuse->relu; }
+        if (infer) { epi = masked ? 9 : 8; p.ep_res = fuse->res; p.ep_relu = fuse->relu; }      // (9: PRO 4 + the factor before b', fx_conv_kernel)
     }
     const int tiles_n = (int)ceil_div(p.NP, FX_BN);
     const FxSplit sp = fx_fwd_split(d);

@@ -10,8 +10,13 @@ p3d_fx_conv_fwd_infer, whose epilogue adds b', the residual and the ReLU, and on
     ...optimizer step / new running statistics...
     net.refresh()                       # re-fold from the current parameters (one launch)
 
-A conv the x3 forward cannot take (odd sizes, fx_fwd_applies) goes through today's eval path for that layer (ops.conv_bn_eval); so do the
-partial-convolution layers of the partial families (their stem and layer1/2, layer5/6), which run as the model's own modules.
+A conv the x3 forward cannot take (odd sizes, fx_fwd_applies) goes through today's eval path for that layer (ops.conv_bn_eval).
+
+The partial-convolution layers of partial_depthnet (stem, layer1, layer2) and partial_fusionnet (conv2, layer5, layer6) fold as well: each conv runs on
+p3d_fx_conv_fwd_infer_masked (mask_in multiplied into the operand, y = relu?(conv * mult + b' + res), the factor before b'), each with its own
+ops.mask_count, and the PartialConv stem on p3d_stem_image_masked + p3d_stem_fwd_masked (x mult) + p3d_stem_tail_infer.  A partial conv with a bias, a shape
+the masked entry refuses or a stem p3d_stem_masked_supported refuses (odd sides) runs as the model's own module, that layer only.  P3D_FOLD_PARTIAL=0
+(read when a network is folded) keeps every partial layer on the model's own modules, as before they folded.
 
 `fold_half(model)` is the same for the fp16 (-half_acc) network: kind-2 fold jobs write fp16 [K][R][S][Cpad] images of every w' (the layout
 p3d_weight_images_f16 produces) and `HalfFoldedNet(x[, y])` runs every conv on p3d_hconv2d_fwd_infer, whose epilogue adds b', the residual and the
@@ -23,7 +28,7 @@ import os
 
 import torch
 
-from . import ops, ops_half
+from . import ops, ops_block, ops_half
 from ._lib import FoldJob, P3DError, check, lib
 from .nn import _one
 
@@ -31,6 +36,11 @@ from .nn import _one
 # the 128-row tile (half of it padding).  DESIGN.md records the measurement behind the default.
 NARROW_IMAGE = os.environ.get('P3D_FOLD_NARROW_IMG', '0') != '0'
 _ALIGN = 256
+
+
+def fold_partial():
+    """P3D_FOLD_PARTIAL=0: FoldedNet leaves the partial-convolution stems and layers on the model's own modules (A/B; read when a network is folded)."""
+    return os.environ.get('P3D_FOLD_PARTIAL', '1') != '0'
 
 
 def enabled():
@@ -68,13 +78,17 @@ class _Conv:
     """One conv (+ BatchNorm) of the folded network: where its image and bias live in the buffer, and how to run it."""
 
     def __init__(self, conv, bn, c_offset=0, c_count=None, has_bias=True):
+        from .partial_conv import PartialConv
         self.conv, self.bn = conv, bn
         k, ct, r, s = conv.weight.shape
-        self.k, self.ct, self.rs = k, ct, r * s
+        self.k, self.ct, self.rs, self.r = k, ct, r * s, r
         self.c_offset, self.c = c_offset, ct if c_count is None else c_count
         self.stride, self.pad, self.dil = _one(conv.stride), _one(conv.padding), _one(conv.dilation)
         self.has_bias = has_bias
+        self.partial = isinstance(conv, PartialConv)
         self.foldable = self.c % 16 == 0 and r == s and (r & 1) == 1 and k % 16 == 0 and 32 <= k <= 2048      # (else: today's path)
+        if self.partial and conv.bias is not None:          # (no reference network has one: the module's own path)
+            self.foldable = False
         self.img_off = self.img_bytes = self.bias_off = None
 
     def layout(self, at):
@@ -118,7 +132,8 @@ class _Stem:
     def __init__(self, conv, bn):
         self.conv, self.bn = conv, bn
         self.k, self.cin = conv.weight.shape[0], conv.weight.shape[1]
-        self.foldable = (type(conv).__name__ == 'Conv2d' and conv.bias is None and tuple(conv.kernel_size) == (7, 7) and _one(conv.stride) == 2
+        self.masked = type(conv).__name__ == 'PartialConv'      # the partial families' stems: mask_in into the image, mult into the epilogue
+        self.foldable = (type(conv).__name__ in ('Conv2d', 'PartialConv') and conv.bias is None and tuple(conv.kernel_size) == (7, 7) and _one(conv.stride) == 2
                          and _one(conv.padding) == 3 and _one(conv.dilation) == 1 and 1 <= self.cin <= 4 and self.k % 16 == 0 and self.k <= 128)
 
     def layout(self, at):
@@ -217,9 +232,29 @@ class _Folded:
             y = ops.conv_bn_eval(x, c.conv, c.bn, res=res, relu=relu)
         return y
 
+    def _pconv(self, c, x, veil, res=None, relu=True):
+        """A partial convolution (partial_conv.py) + its folded BatchNorm: y = relu?(conv(x * veil, w') * mult + b' + res), mult and mask_out from the box count
+        of veil (ops.mask_count); returns (y, mask_out).  A conv the masked entry cannot take runs as the module, then the eval-mode BatchNorm pass."""
+        L = lib()
+        d = c.desc(x) if c.foldable else None
+        if d is None or not L.p3d_fx_conv_fwd_infer_masked_supported(ctypes.byref(d)):
+            y, mask_out = c.conv(x, veil)
+            return c.bn(y, res=res, relu=relu), mask_out
+        if tuple(veil.shape) != (d.N, 1, d.H, d.W) or veil.dtype != torch.float32:
+            raise P3DError('infer: the validity mask of a partial conv must be fp32 [N, 1, H, W] like its input, got %s %s' % (tuple(veil.shape), veil.dtype))
+        mult, mask_out = ops.mask_count(veil, c.r, c.stride, c.pad, c.dil)
+        x = x.contiguous()
+        y = torch.empty((d.N, d.K, d.Ho, d.Wo), dtype=torch.float32, device=x.device)
+        ws = self._ws(L.p3d_fx_conv_fwd_infer_workspace_bytes(ctypes.byref(d)))
+        check(L.p3d_fx_conv_fwd_infer_masked(ctypes.byref(d), ops._p(x), self._at(c.img_off), c.img_bytes, self._at(c.bias_off), ops._p(veil.contiguous()),
+                                             ops._p(mult), ops._p(None if res is None else res.contiguous()), int(bool(relu)), ops._p(y), ops._p(ws), ws.numel(),
+                                             ops._stream()), 'p3d_fx_conv_fwd_infer_masked')
+        return y, mask_out
+
 
 class FoldedConv(_Folded):
-    """One conv (no bias) + eval-mode BatchNorm, folded: FoldedConv(conv, bn)(x, res=None, relu=False) = relu(bn(conv(x)) + res)."""
+    """One conv (no bias) + eval-mode BatchNorm, folded: FoldedConv(conv, bn)(x, res=None, relu=False) = relu(bn(conv(x)) + res).  For a PartialConv
+    the validity mask comes along: FoldedConv(pconv, bn)(x, res, relu, veil=mask_in) = (relu(bn(pconv(x, mask_in)[0]) + res), mask_out)."""
 
     def __init__(self, conv, bn):
         self.model, self.stems = None, {}
@@ -231,9 +266,11 @@ class FoldedConv(_Folded):
         if self.conv.bn.training:
             raise P3DError('infer.FoldedConv: the BatchNorm is in training mode')
 
-    def __call__(self, x, res=None, relu=False):
+    def __call__(self, x, res=None, relu=False, veil=None):
+        if self.conv.partial != (veil is not None):
+            raise P3DError('infer.FoldedConv: a partial convolution takes its validity mask (veil=), a dense one none')
         with torch.no_grad():
-            return self._conv_bn(self.conv, x, res, relu)
+            return self._pconv(self.conv, x, veil, res, relu) if self.conv.partial else self._conv_bn(self.conv, x, res, relu)
 
 
 class FoldedNet(_Folded):
@@ -249,17 +286,17 @@ class FoldedNet(_Folded):
         self.early_dist = bool(getattr(model, 'early_dist', False))
         self.stems, self.convs = {}, []
         fam = self.family
-        if fam in ('depthnet', 'resnet', 'fusionnet'):
+        self.fold_partial = fold_partial()
+        partial = {'partial_depthnet': ('layer1', 'layer2'), 'partial_fusionnet': ('layer5', 'layer6')}.get(fam, ()) if self.fold_partial else ()
+        if fam != 'partial_depthnet' or self.fold_partial:
             self.stems['conv1'] = _Stem(model.conv1, model.bn1)
-        if fam == 'partial_fusionnet':
-            self.stems['conv1'] = _Stem(model.conv1, model.bn1)
-        if fam == 'fusionnet':
+        if fam == 'fusionnet' or (fam == 'partial_fusionnet' and self.fold_partial):
             self.stems['conv2'] = _Stem(model.conv2, model.bn2)
         dense = {'depthnet': ('layer1', 'layer2', 'layer3', 'layer4'), 'resnet': ('layer1', 'layer2', 'layer3', 'layer4'),
                  'fusionnet': ('layer1', 'layer2', 'layer3', 'layer4', 'layer5', 'layer6'), 'partial_depthnet': ('layer3', 'layer4'),
                  'partial_fusionnet': ('layer1', 'layer2', 'layer3', 'layer4')}[fam]
         self.blocks = {}
-        for lname in dense:
+        for lname in dense + partial:
             plans = []
             for blk in getattr(model, lname):
                 plan = dict(block=blk, chain=[self._add(_Conv(getattr(blk, c), getattr(blk, b))) for c, b in blk._chain])
@@ -282,7 +319,7 @@ class FoldedNet(_Folded):
     def _stem(self, s, x):
         n, cin, h, w = x.shape
         L = lib()
-        if not (s.foldable and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_supported(n, cin, h, w, s.k)
+        if not (s.foldable and not s.masked and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_supported(n, cin, h, w, s.k)
                 and (h // 2) % 2 == 0 and (w // 2) % 4 == 0):
             from ._trunk import stem
             return stem(s.conv, s.bn, self.model.maxpool, x)
@@ -296,16 +333,40 @@ class FoldedNet(_Folded):
         check(L.p3d_stem_tail_infer(ops._p(c), self._at(s.bias_off), ops._p(y), n, s.k, h // 2, w // 2, st), 'p3d_stem_tail_infer')
         return y
 
-    def _layer(self, name, x):
+    def _stem_masked(self, s, x, veil):
+        """The PartialConv stem + BatchNorm + ReLU + max pool (partial_depthnet.py:177): conv(x * veil) * mult on the restated stem, then relu(maxpool(.) + b')
+        (relu(maxpool(c mult) + b') = maxpool(relu(c mult + b')): both monotone per channel).  Returns (y, max-pooled mask_out)."""
+        n, cin, h, w = x.shape
+        L = lib()
+        if not (s.foldable and ops_block.MASKED_STEM and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_masked_supported(n, cin, h, w, s.k)
+                and (h // 2) % 2 == 0 and (w // 2) % 4 == 0):
+            from ._trunk import stem_tail
+            c, veil = s.conv(x, veil)                       # today's path (odd sides: the reference's default -side_in 257)
+            return stem_tail(s.bn, self.model.maxpool, c), self.model.maxpool(veil)
+        x, veil = x.contiguous(), veil.contiguous()
+        mult, mask_out = ops.mask_count(veil, 7, 2, 3, 1)
+        st = ops._stream()
+        x_img = torch.empty(L.p3d_stem_image_bytes(n, h, w), dtype=torch.uint8, device=x.device)
+        check(L.p3d_stem_image_masked(ops._p(x), ops._p(veil), ops._p(x_img), n, cin, h, w, st), 'p3d_stem_image_masked')
+        c = torch.empty((n, s.k, h // 2, w // 2), dtype=torch.float32, device=x.device)
+        check(L.p3d_stem_fwd_masked(ops._p(x_img), self._at(s.img_off), ops._p(c), ops._p(mult), n, cin, h, w, s.k, st), 'p3d_stem_fwd_masked')
+        y = torch.empty((n, s.k, h // 4, w // 4), dtype=torch.float32, device=x.device)
+        check(L.p3d_stem_tail_infer(ops._p(c), self._at(s.bias_off), ops._p(y), n, s.k, h // 2, w // 2, st), 'p3d_stem_tail_infer')
+        return y, self.model.maxpool(mask_out)
+
+    def _layer(self, name, x, veil=None):
         for plan in self.blocks[name]:
             blk = plan['block']
             res = x if plan['ds'] is None else self._conv_bn(plan['ds'], x)
             out = x
             last = len(plan['chain']) - 1
             for i, c in enumerate(plan['chain']):
-                out = self._conv_bn(c, out, relu=True) if i < last else self._conv_bn(c, out, res=res, relu=not blk.skip_relu)
+                if blk.partial:                             # (the closing ReLU of a partial block is unconditional: _trunk.py forward_partial)
+                    out, veil = self._pconv(c, out, veil, res if i == last else None)
+                else:
+                    out = self._conv_bn(c, out, relu=True) if i < last else self._conv_bn(c, out, res=res, relu=not blk.skip_relu)
             x = out
-        return x
+        return x if veil is None else (x, veil)
 
     def _fusion(self, x, y):
         a, b = self.fusion
@@ -351,26 +412,36 @@ class FoldedNet(_Folded):
             n = self._layer('layer4', relu(a) if self.skip_relu else a)
             z = self._head(self.heads[0], relu(n) if self.skip_relu else n)
             return z, (a if self.early_dist else n)
+        from ._trunk import stem_tail
         if fam == 'partial_depthnet':
-            from ._trunk import stem_tail
             veil = ops.nonzero_mask(x)
-            x, veil = m.conv1(x, veil)                      # the partial-convolution stem and layers: the model's own eval path
-            x = stem_tail(m.bn1, m.maxpool, x)
-            veil = m.maxpool(veil)
-            x, veil = m.layer1((x, veil))
-            x, veil = m.layer2((x, veil))
+            if self.fold_partial:
+                x, veil = self._stem_masked(self.stems['conv1'], x, veil)
+                x, veil = self._layer('layer1', x, veil)
+                x, _ = self._layer('layer2', x, veil)       # (layer2's mask_out feeds nothing)
+            else:
+                x, veil = m.conv1(x, veil)                  # P3D_FOLD_PARTIAL=0: the partial-convolution stem and layers on the model's own eval path
+                x = stem_tail(m.bn1, m.maxpool, x)
+                veil = m.maxpool(veil)
+                x, veil = m.layer1((x, veil))
+                x, veil = m.layer2((x, veil))
             x = self._layer('layer4', self._layer('layer3', x))
             return self._head(self.heads[0], x), x
         # partial_fusionnet
-        from ._trunk import stem_tail
         x = self._stem(self.stems['conv1'], x)
         veil = ops.nonzero_mask(y)
-        y, veil = m.conv2(y, veil)
-        y = stem_tail(m.bn2, m.maxpool, y)
-        veil = m.maxpool(veil)
-        x = self._layer('layer2', self._layer('layer1', x))
-        y, veil = m.layer5((y, veil))
-        y, veil = m.layer6((y, veil))
+        if self.fold_partial:
+            y, veil = self._stem_masked(self.stems['conv2'], y, veil)
+            x = self._layer('layer2', self._layer('layer1', x))
+            y, veil = self._layer('layer5', y, veil)
+            y, _ = self._layer('layer6', y, veil)
+        else:
+            y, veil = m.conv2(y, veil)
+            y = stem_tail(m.bn2, m.maxpool, y)
+            veil = m.maxpool(veil)
+            x = self._layer('layer2', self._layer('layer1', x))
+            y, veil = m.layer5((y, veil))
+            y, veil = m.layer6((y, veil))
         x = self._fusion(x, y)
         x = self._layer('layer4', self._layer('layer3', x))
         return self._head(self.heads[0], x), x

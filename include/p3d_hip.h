@@ -290,6 +290,13 @@ int32_t p3d_fx_conv_fwd_infer_supported(const p3d_conv_desc* d, int32_t image_fe
 size_t p3d_fx_conv_fwd_infer_workspace_bytes(const p3d_conv_desc* d);
 int32_t p3d_fx_conv_fwd_infer(const p3d_conv_desc* d, const float* x, const void* x_img, const void* wimg, size_t wimg_bytes, const float* bias, const float* res,
                               int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for a PARTIAL convolution (partial_conv.py:32-57) with its BatchNorm folded: y = relu?(conv(x * mask_in, w') * mult + b' + res), the factor applied before
+ * b' (an empty window, mult = 0, gives relu(b' + res), what the reference's BatchNorm makes of the 0 its partial conv writes there).  mask_in [N][1][H][W], mult
+ * [N][1][Ho][Wo] (ops.mask_count); fp32 x only, 16-B aligned operands, wimg as above; bias / res may be NULL.  Workspace: p3d_fx_conv_fwd_infer_workspace_bytes.
+ * supported: the forward of d runs on the masked x3 kernels (channel counts down to 64, no channel window, no accumulate; 0 under P3D_FX_MASKED=0); host only. */
+int32_t p3d_fx_conv_fwd_infer_masked_supported(const p3d_conv_desc* d);
+int32_t p3d_fx_conv_fwd_infer_masked(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* mask_in,
+                                     const float* mult, const float* res, int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream);
 /* Stem tail at inference behind p3d_stem_fwd on a folded stem image: y = maxpool3x3s2(relu(c + bias[channel])) = relu(maxpool(c) + bias) (both monotone per
  * channel), no argmax output.  c [N][C][H][W] (H, W even), y [N][C][H/2][W/2]. */
 int32_t p3d_stem_tail_infer(const float* c, const float* bias, float* y, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);

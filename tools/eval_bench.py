@@ -4,11 +4,14 @@
 Legs, timed in the same process, alternating (device-synchronised, 10 warm-up + 50 timed iterations per round):
   fused     today's eval path: conv + BN (+ res + ReLU) per layer in one kernel (ops.conv_bn_eval, the fp32-MFMA kernel)
   folded    infer.fold(model): BatchNorm folded into the x3 convolutions (p3d_fx_conv_fwd_infer)
+--family partial_depthnet / partial_fusionnet times those networks (depth ~ U[0, 1) with values < 0.3 zeroed; partial_depthnet: -depth_only) and adds
+  folded_nopartial  infer.fold(model) under P3D_FOLD_PARTIAL=0: the partial-convolution layers on the model's own modules
 --half replaces them with the -half_acc legs:
   half          today's fp16 eval forward: fp16 conv, then a stand-alone eval-mode BatchNorm (+ res + ReLU) pass per layer
   half_folded   infer.fold_half(model): BatchNorm folded into the fp16 convolutions (p3d_hconv2d_fwd_infer)
 --separate adds the round-1 leg with stand-alone BatchNorm passes; --distill also times one distill_step with and without the folded teacher
-(with --half: a -half_acc student and teacher, P3D_FOLDED_EVAL_HALF).
+(with --half: a -half_acc student and teacher, P3D_FOLDED_EVAL_HALF; with --family partial_fusionnet: a partial_fusionnet teacher, folded with
+P3D_FOLD_PARTIAL=1 and =0).
 Prints one line per leg and round, then a JSON summary line."""
 import argparse
 import importlib
@@ -34,23 +37,40 @@ ap.add_argument('--separate', action='store_true')
 ap.add_argument('--distill', action='store_true')
 ap.add_argument('--half', action='store_true', help='-half_acc legs: half / half_folded')
 ap.add_argument('--only', default=None, help='time one leg only (profiling runs)')
+ap.add_argument('--family', default='depthnet', choices=['depthnet', 'partial_depthnet', 'partial_fusionnet'])
 opt = ap.parse_args()
+if opt.distill and opt.family == 'partial_depthnet':
+    ap.error('--distill times a depthnet student with a fusionnet (--family depthnet) or partial_fusionnet (--family partial_fusionnet) teacher')
 
+flags = {'depthnet': [], 'partial_depthnet': ['-depth_only', '-partial_conv'], 'partial_fusionnet': ['-do_fusion', '-partial_conv']}[opt.family]
 args = pkg.opts.parse(['-model', opt.model, '-suffix', 'b', '-data_name', 'h36m', '-save_path', '/tmp/p3d', '-criterion', 'SmoothL1', '-num_joints', '17',
-                       '-side_in', str(opt.side)])
+                       '-side_in', str(opt.side)] + flags)
 model = pkg.depth_main.create_model(args)[0].cuda().eval()
+assert type(model).__module__.endswith('.' + opt.family)
 x = torch.randn(opt.batch, 3, opt.side, opt.side, device='cuda')
+if opt.family != 'depthnet':
+    depth = torch.rand(opt.batch, 1, opt.side, opt.side, device='cuda')
+    depth = depth * (depth >= 0.3)                      # the synthetic recipe: depth ~ U[0, 1), values < 0.3 zeroed
+    inputs = (depth,) if opt.family == 'partial_depthnet' else (x, depth)
+else:
+    inputs = (x,)
 fuse = pkg.ops.can_fuse_eval
 if opt.half:
     model._p3d_half = True                              # what the Trainer sets under -half_acc
     pkg.ops_half.refresh_weights(model)
     hfolded = pkg.infer.fold_half(model)
-    legs = {'half': lambda: model(x), 'half_folded': lambda: hfolded(x)}
+    legs = {'half': lambda: model(*inputs), 'half_folded': lambda: hfolded(*inputs)}
 else:
     folded = pkg.infer.fold(model)
-    legs = {'fused': lambda: model(x), 'folded': lambda: folded(x)}
+    legs = {'fused': lambda: model(*inputs), 'folded': lambda: folded(*inputs)}
+    if opt.family != 'depthnet':
+        os.environ['P3D_FOLD_PARTIAL'] = '0'            # (read when the net is folded)
+        nopartial = pkg.infer.fold(model)
+        os.environ.pop('P3D_FOLD_PARTIAL')
+        assert folded.fold_partial and not nopartial.fold_partial
+        legs['folded_nopartial'] = lambda: nopartial(*inputs)
 if opt.separate:
-    legs['separate'] = lambda: model(x)
+    legs['separate'] = lambda: model(*inputs)
 if opt.only:
     legs = {opt.only: legs[opt.only]}
 
@@ -68,32 +88,43 @@ def run(name, fn):
     return (time.perf_counter() - t0) / opt.iters
 
 
-gflop = 2 * 9.390 * opt.batch if (opt.model, opt.side) == ('resnet50', 256) else None
+gflop = 2 * 9.390 * opt.batch if (opt.family, opt.model, opt.side) == ('depthnet', 'resnet50', 256) else None
 times = {k: [] for k in legs}
 for r in range(opt.rounds):
     for name, fn in legs.items():
         dt = run(name, fn)
         times[name].append(dt)
-        print('round %d  %-9s %.2f ms / batch of %d = %.0f crops/s%s' % (r, name, dt * 1e3, opt.batch, opt.batch / dt,
+        print('round %d  %-16s %.2f ms / batch of %d = %.0f crops/s%s' % (r, name, dt * 1e3, opt.batch, opt.batch / dt,
                                                                         '  (%.0f TF)' % (gflop / dt / 1e3) if gflop else ''), flush=True)
 summary = {k: dict(ms_median=sorted(v)[len(v) // 2] * 1e3, ms_min=min(v) * 1e3, ms_max=max(v) * 1e3, crops_s=opt.batch / sorted(v)[len(v) // 2]) for k, v in times.items()}
 
 if opt.distill:
     dargs = pkg.opts.parse(['-model', opt.model, '-suffix', 'b', '-data_name', 'h36m', '-save_path', '/tmp/p3d', '-criterion', 'SmoothL1', '-num_joints', '17',
-                            '-side_in', str(opt.side), '-do_teach', '-do_fusion'] + (['-half_acc'] if opt.half else []))
+                            '-side_in', str(opt.side), '-do_teach', '-do_fusion'] + (['-half_acc'] if opt.half else []) +
+                           (['-partial_conv'] if opt.family == 'partial_fusionnet' else []))
     switch = 'P3D_FOLDED_EVAL_HALF' if opt.half else 'P3D_FOLDED_EVAL'
     student = pkg.depthnet.__dict__[opt.model](dargs, False).cuda()
-    teacher = pkg.fusionnet.__dict__[opt.model](dargs, False).cuda().eval()
+    teacher_family = pkg.partial_fusionnet if opt.family == 'partial_fusionnet' else pkg.fusionnet
+    teacher = teacher_family.__dict__[opt.model](dargs, False).cuda().eval()
+    # (teacher leg, value of the switch, P3D_FOLD_PARTIAL when the teacher is folded): with a partial teacher, its partial layers folded and not
+    configs = [('teacher', '0', None), ('folded_teacher', '1', None)]
+    if opt.family == 'partial_fusionnet' and not opt.half:
+        configs = [('teacher', '0', None), ('folded_teacher', '1', '1'), ('folded_teacher_nopartial', '1', '0')]
     c, d, tc, tv = (torch.from_numpy(a).cuda() for a in pkg.synth.make_batch(opt.batch, side=opt.side, rank=0, step=0))
     side_out = (opt.side - 1) // 16 + 1
     att = torch.ones(opt.batch, 1, side_out, side_out, device='cuda')
     res = {}
     for r in range(opt.rounds):
-        for on in ('0', '1'):
+        for leg, on, fold_partial in configs:
             os.environ[switch] = on
+            if fold_partial is not None:
+                os.environ['P3D_FOLD_PARTIAL'] = fold_partial
             tr = pkg.depth_train.Trainer(dargs, student, pkg.utils.get_info()) if r == 0 and on == '0' else tr
             tr.set_teacher(teacher)
+            os.environ.pop('P3D_FOLD_PARTIAL', None)
             assert (tr.folded_teacher is not None) == (on == '1')
+            if fold_partial is not None:
+                assert tr.folded_teacher.fold_partial == (fold_partial == '1')
             for _ in range(3):
                 tr.distill_step(1, c, d, tc, tv, att)
             torch.cuda.synchronize()
@@ -102,7 +133,7 @@ if opt.distill:
                 tr.distill_step(1, c, d, tc, tv, att)
             torch.cuda.synchronize()
             dt = (time.perf_counter() - t0) / 10
-            res.setdefault('folded_teacher' if on == '1' else 'teacher', []).append(dt * 1e3)
-            print('round %d  distill_step %-15s %.2f ms' % (r, 'folded_teacher' if on == '1' else 'teacher', dt * 1e3), flush=True)
+            res.setdefault(leg, []).append(dt * 1e3)
+            print('round %d  distill_step %-24s %.2f ms' % (r, leg, dt * 1e3), flush=True)
     summary['distill_step_ms'] = {k: sorted(v) for k, v in res.items()}
-print(json.dumps(dict(model=opt.model, half=opt.half, batch=opt.batch, side=opt.side, warmup=opt.warmup, iters=opt.iters, legs=summary)))
+print(json.dumps(dict(model=opt.model, family=opt.family, half=opt.half, batch=opt.batch, side=opt.side, warmup=opt.warmup, iters=opt.iters, legs=summary)))
