@@ -15,13 +15,17 @@ A conv the x3 forward cannot take (odd sizes, fx_fwd_applies) goes through today
 The partial-convolution layers of partial_depthnet (stem, layer1, layer2) and partial_fusionnet (conv2, layer5, layer6) fold as well: each conv runs on
 p3d_fx_conv_fwd_infer_masked (mask_in multiplied into the operand, y = relu?(conv * mult + b' + res), the factor before b'), each with its own
 ops.mask_count, and the PartialConv stem on p3d_stem_image_masked + p3d_stem_fwd_masked (x mult) + p3d_stem_tail_infer.  A partial conv with a bias, a shape
-the masked entry refuses or a stem p3d_stem_masked_supported refuses (odd sides) runs as the model's own module, that layer only.  P3D_FOLD_PARTIAL=0
-(read when a network is folded) keeps every partial layer on the model's own modules, as before they folded.
+the masked entry refuses or a stem p3d_stem_masked_supported refuses (odd sides) runs as the model's own module, that layer only.
 
 `fold_half(model)` is the same for the fp16 (-half_acc) network: kind-2 fold jobs write fp16 [K][R][S][Cpad] images of every w' (the layout
 p3d_weight_images_f16 produces) and `HalfFoldedNet(x[, y])` runs every conv on p3d_hconv2d_fwd_infer, whose epilogue adds b', the residual and the
 ReLU before the one rounding to fp16.  The partial-convolution layers fold too (mask_in in the operand fetch, mult in the epilogue), so an fp16 folded
 forward has no BatchNorm pass at all.
+
+Both precisions share the plan (stems, blocks, fusion, heads), the fold launch and the walk over the network (_Folded); FoldedNet and HalfFoldedNet
+supply the per-layer primitives.  Two A/B switches were measured and removed, because each only selected a slower path: leaving the partial stem
+and layers on the model's own modules (9.80 against 8.90 ms for R50 partial_depthnet, 13.10 against 12.22 ms for partial_fusionnet,
+profiles/eval_folded_partial.md), and feeding the 64-channel layers as an activation image (2.7 % slower, profiles/eval_folded.md).
 """
 import ctypes
 import os
@@ -31,16 +35,9 @@ import torch
 from . import ops, ops_block, ops_half
 from ._lib import FoldJob, P3DError, check, lib
 from .nn import _one
+from .partial_conv import PartialConv
 
-# Narrow layers (64 output channels): feed the activation as a pre-split image (p3d_fx_act_image + the 64-row fx16 tile) instead of the fp32 operand on
-# the 128-row tile (half of it padding).  DESIGN.md records the measurement behind the default.
-NARROW_IMAGE = os.environ.get('P3D_FOLD_NARROW_IMG', '0') != '0'
 _ALIGN = 256
-
-
-def fold_partial():
-    """P3D_FOLD_PARTIAL=0: FoldedNet leaves the partial-convolution stems and layers on the model's own modules (A/B; read when a network is folded)."""
-    return os.environ.get('P3D_FOLD_PARTIAL', '1') != '0'
 
 
 def enabled():
@@ -60,25 +57,44 @@ def _family(model):
     return name
 
 
-def _check_foldable(model):
-    if getattr(model, '_p3d_half', False):
-        raise P3DError('infer.fold: a -half_acc (fp16) model cannot be folded onto the fp32 kernels; use infer.fold_half')
+def _check_foldable(model, who, half):
+    """Refuse what folding would get wrong: a BatchNorm in training mode or without running statistics, parameters that are not fp32 on the HIP
+    device, and for the fp32 fold (half False) a -half_acc model."""
+    if not half and getattr(model, '_p3d_half', False):
+        raise P3DError('%s: a -half_acc (fp16) model cannot be folded onto the fp32 kernels; use infer.fold_half' % who)
     for name, m in model.named_modules():
         if isinstance(m, torch.nn.BatchNorm2d):
             if m.training:
-                raise P3DError('infer.fold: BatchNorm %r is in training mode; call model.eval() first (folding uses the running statistics)' % name)
+                raise P3DError('%s: BatchNorm %r is in training mode; call model.eval() first (folding uses the running statistics)' % (who, name))
             if not (m.affine and m.track_running_stats):
-                raise P3DError('infer.fold: BatchNorm %r has no running statistics / affine parameters' % name)
+                raise P3DError('%s: BatchNorm %r has no running statistics / affine parameters' % (who, name))
     for p in model.parameters():
         if not p.is_cuda or p.dtype != torch.float32:
-            raise P3DError('infer.fold: parameters must be fp32 on the HIP device')
+            raise P3DError('%s: parameters must be fp32%s on the HIP device' % (who, ' masters' if half else ''))
+
+
+def _fold_job(conv, bn, buf, out_off, bias_off):
+    """The FoldJob of conv (+ bn: None for a head) writing to buf at out_off and bias_off; the caller sets the kind and the shape fields."""
+    j = FoldJob()
+    j.w = conv.weight.data_ptr()
+    j.conv_bias = conv.bias.data_ptr() if conv.bias is not None else None
+    if bn is not None:
+        j.gamma, j.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
+        j.mean, j.var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+        j.eps = float(bn.eps)
+    j.out = buf.data_ptr() + out_off
+    j.bias_out = buf.data_ptr() + bias_off if bias_off is not None else None
+    return j
+
+
+def _up(v):
+    return (v + _ALIGN - 1) // _ALIGN * _ALIGN
 
 
 class _Conv:
     """One conv (+ BatchNorm) of the folded network: where its image and bias live in the buffer, and how to run it."""
 
     def __init__(self, conv, bn, c_offset=0, c_count=None, has_bias=True):
-        from .partial_conv import PartialConv
         self.conv, self.bn = conv, bn
         k, ct, r, s = conv.weight.shape
         self.k, self.ct, self.rs, self.r = k, ct, r * s, r
@@ -92,8 +108,6 @@ class _Conv:
         self.img_off = self.img_bytes = self.bias_off = None
 
     def layout(self, at):
-        if not self.foldable:
-            return at
         fb = ctypes.c_size_t()
         check(lib().p3d_fx_weight_image_bytes(self.k, self.c, self.rs, ctypes.byref(fb), None), 'p3d_fx_weight_image_bytes')
         self.img_off, self.img_bytes = at, fb.value
@@ -104,26 +118,12 @@ class _Conv:
         return at
 
     def job(self, buf):
-        if not self.foldable:
-            return None
-        j = FoldJob()
-        j.w = self.conv.weight.data_ptr()
-        j.conv_bias = self.conv.bias.data_ptr() if self.conv.bias is not None else None
-        if self.bn is not None:
-            j.gamma, j.beta = self.bn.weight.data_ptr(), self.bn.bias.data_ptr()
-            j.mean, j.var = self.bn.running_mean.data_ptr(), self.bn.running_var.data_ptr()
-            j.eps = float(self.bn.eps)
-        j.out = buf.data_ptr() + self.img_off
-        j.bias_out = buf.data_ptr() + self.bias_off if self.bias_off is not None else None
+        j = _fold_job(self.conv, self.bn, buf, self.img_off, self.bias_off)
         j.K, j.C, j.RS, j.c_offset, j.c_total, j.kind = self.k, self.c, self.rs, self.c_offset, self.ct, 0
         return j
 
     def desc(self, x, accumulate=0):
         return ops._desc(x.shape, (self.k, self.c, int(self.rs ** 0.5), int(self.rs ** 0.5)), self.stride, self.pad, self.dil, accumulate=accumulate)
-
-
-def _up(v):
-    return (v + _ALIGN - 1) // _ALIGN * _ALIGN
 
 
 class _Stem:
@@ -137,8 +137,6 @@ class _Stem:
                          and _one(conv.padding) == 3 and _one(conv.dilation) == 1 and 1 <= self.cin <= 4 and self.k % 16 == 0 and self.k <= 128)
 
     def layout(self, at):
-        if not self.foldable:
-            return at
         self.w_off = at
         at = _up(at + 4 * self.k * self.cin * 49)
         self.img_off = at
@@ -147,82 +145,202 @@ class _Stem:
         return _up(at + 4 * self.k)
 
     def job(self, buf):
-        if not self.foldable:
-            return None
-        j = FoldJob()
-        j.w = self.conv.weight.data_ptr()
-        j.gamma, j.beta = self.bn.weight.data_ptr(), self.bn.bias.data_ptr()
-        j.mean, j.var = self.bn.running_mean.data_ptr(), self.bn.running_var.data_ptr()
-        j.eps = float(self.bn.eps)
-        j.out = buf.data_ptr() + self.w_off
-        j.bias_out = buf.data_ptr() + self.bias_off
+        j = _fold_job(self.conv, self.bn, buf, self.w_off, self.bias_off)
         j.K, j.C, j.RS, j.c_offset, j.c_total, j.kind = self.k, self.cin, 49, 0, self.cin, 1
         return j
 
 
+class _HConv:
+    """One conv (+ BatchNorm) of the fp16 folded network: its fp16 image [K][R][S][Cpad] and b' in the buffer (fold kind 2).  A head whose K is not a
+    multiple of 8 (the 17-channel mat_regressor of -joint_space) runs with its image and bias padded to Kpad rows of zeros; its result is the first K channels."""
+
+    def __init__(self, conv, bn):
+        self.conv, self.bn = conv, bn
+        k, c, r, s = conv.weight.shape
+        self.k, self.kpad, self.c, self.cpad, self.r, self.s = k, ops_half.pad8(k), c, ops_half.pad8(c), r, s
+        self.stride, self.pad, self.dil = _one(conv.stride), _one(conv.padding), _one(conv.dilation)
+        self.partial = isinstance(conv, PartialConv)
+        self.foldable = k <= 2048                           # (the fold kernel's per-job scale table; else: today's fp16 path for this layer)
+        self.images = None                                  # fp16 images of the unfolded weight, for that path only
+        self.img_off = self.bias_off = None
+
+    def layout(self, at):
+        self.img_off = at
+        at = _up(at + 2 * self.kpad * self.r * self.s * self.cpad)           # (rows K .. Kpad - 1 stay zero: the buffer is zeroed once, the fold writes K rows)
+        self.bias_off = at
+        return _up(at + 4 * self.kpad)
+
+    def job(self, buf):
+        j = _fold_job(self.conv, self.bn, buf, self.img_off, self.bias_off)
+        j.K, j.C, j.RS, j.c_offset, j.c_total, j.kind, j.reserved = self.k, self.c, self.r * self.s, 0, self.c, 2, self.cpad
+        return j
+
+    def desc(self, x):
+        return ops._desc(tuple(x.shape), (self.kpad, self.cpad, self.r, self.s), self.stride, self.pad, self.dil)
+
+
 class _Folded:
-    """One device buffer with the folded images and biases of `stems` and `convs`, one workspace, and the conv launcher."""
+    """model.eval()'s forward with every BatchNorm folded into its convolution.  Holds the plan (stems, blocks, fusion, heads) and one device buffer
+    with every folded image and b', filled by one fold launch; parameters and running statistics are read at fold / refresh() time only (the
+    per-layer fallbacks read them live).  A subclass supplies the precision: its conv type (Conv), how a stem and the Fusion 1x1 fold, and the
+    primitives the walk calls (_in, _out, _stem, _stem_masked, _conv_bn, _pconv, _fusion, _head).  WHO names it in a refusal, HALF marks the
+    -half_acc fold."""
+
+    def __init__(self, model):
+        self.model = model
+        self.family = _family(model)
+        self.skip_relu = bool(getattr(model, 'skip_relu', False))
+        self.early_dist = bool(getattr(model, 'early_dist', False))
+        self.stems, self.convs, self.blocks = {}, [], {}
+        fusion = self.family in ('fusionnet', 'partial_fusionnet')
+        self.stems['conv1'] = self._plan_stem(model.conv1, model.bn1)
+        if fusion:
+            self.stems['conv2'] = self._plan_stem(model.conv2, model.bn2)
+        for lname in ('layer1', 'layer2', 'layer3', 'layer4') + (('layer5', 'layer6') if fusion else ()):
+            plans = []
+            for blk in getattr(model, lname):
+                plan = dict(block=blk, chain=[self._add(self.Conv(getattr(blk, c), getattr(blk, b))) for c, b in blk._chain])
+                plan['ds'] = self._add(self.Conv(blk.downsample[0], blk.downsample[1])) if blk.downsample is not None else None
+                plans.append(plan)
+            self.blocks[lname] = plans
+        if fusion:
+            self.fusion = self._plan_fusion(model.fusion)
+        heads = ('cam_regressor', 'mat_regressor') if self.family == 'resnet' else ('regressor',)
+        self.heads = [self._add(self.Conv(getattr(model, h), None)) if getattr(model, h, None) is not None else None for h in heads]
+        self._allocate(next(model.parameters()).device)
+
+    def _add(self, c):
+        self.convs.append(c)
+        return c
+
+    def _units(self):
+        """Everything the fold launch writes, in buffer order."""
+        return self.convs
 
     def _allocate(self, device):
         at = 0
-        for st in self.stems.values():
-            at = st.layout(at)
-        for c in self.convs:
-            at = c.layout(at)
-        self.buffer = torch.empty(max(at, _ALIGN), dtype=torch.uint8, device=device)
-        self.workspace = torch.empty(1 << 20, dtype=torch.uint8, device=device)
+        for u in self._units():
+            if u.foldable:
+                at = u.layout(at)
+        alloc = torch.zeros if self.HALF else torch.empty       # (fp16: the padding rows K .. Kpad - 1 of a head's image and bias are read)
+        self.buffer = alloc(max(at, _ALIGN), dtype=torch.uint8, device=device)
         self.refresh()
-
-    def _check(self):
-        _check_foldable(self.model)
 
     # ---- folding ------------------------------------------------------------------------------------------------
     def refresh(self):
-        """Re-fold every conv from the current parameters and running statistics: one fold launch (+ the stem's image restatement)."""
-        self._check()
-        jobs = [j for j in [st.job(self.buffer) for st in self.stems.values()] + [c.job(self.buffer) for c in self.convs] if j is not None]
-        if not jobs:
-            return self
-        table = (FoldJob * len(jobs))(*jobs)
-        host = torch.frombuffer(bytearray(table), dtype=torch.uint8)
-        self._jobs = host.to(self.buffer.device)           # (kept alive until the launch has read it: the next refresh replaces it in stream order)
-        L, st = lib(), ops._stream()
-        check(L.p3d_fx_fold_bn_images(ops._p(self._jobs), len(jobs), 64, st), 'p3d_fx_fold_bn_images')
-        for s in self.stems.values():
-            if s.foldable:
-                ws = self._ws(s.k * 256 * 4)
-                check(L.p3d_stem_weight_image(self._at(s.w_off), s.k, s.cin, self._at(s.img_off), ops._p(ws), ws.numel(), st), 'p3d_stem_weight_image')
+        """Re-fold every conv from the current parameters and running statistics: one fold launch for the whole network."""
+        _check_foldable(self.model, self.WHO, self.HALF)
+        jobs = [u.job(self.buffer) for u in self._units() if u.foldable]
+        if jobs:
+            table = (FoldJob * len(jobs))(*jobs)
+            self._jobs = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(self.buffer.device)     # (kept alive until the launch has read it)
+            check(lib().p3d_fx_fold_bn_images(ops._p(self._jobs), len(jobs), 64, ops._stream()), 'p3d_fx_fold_bn_images')
         return self
 
     def _at(self, off):
         return ctypes.c_void_p(self.buffer.data_ptr() + off)
+
+    def bias(self, c):
+        """b' of a folded conv as a tensor view of the buffer (tests)."""
+        return self.buffer[c.bias_off:c.bias_off + 4 * c.k].view(torch.float32)
+
+    # ---- forward ---------------------------------------------------------------------------------------------------
+    def _layer(self, name, x, veil=None):
+        for plan in self.blocks[name]:
+            blk = plan['block']
+            res = x if plan['ds'] is None else self._conv_bn(plan['ds'], x)
+            out, last = x, len(plan['chain']) - 1
+            for i, c in enumerate(plan['chain']):
+                if blk.partial:                             # (the closing ReLU of a partial block is unconditional: _trunk.py forward_partial)
+                    out, veil = self._pconv(c, out, veil, res if i == last else None)
+                else:
+                    out = self._conv_bn(c, out, res if i == last else None, relu=i < last or not blk.skip_relu)
+            x = out
+        return x if veil is None else (x, veil)
+
+    def _branch(self, stem, layers, x):
+        """A stem and its two layers.  A PartialConv stem starts the validity mask x != 0, which its layers carry (the last mask_out feeds nothing)."""
+        st = self.stems[stem]
+        if not isinstance(st.conv, PartialConv):
+            return self._layer(layers[1], self._layer(layers[0], self._stem(st, self._in(x))))
+        veil = ops.nonzero_mask(x.float())
+        x, veil = self._stem_masked(st, self._in(x), veil)
+        return self._layer(layers[1], *self._layer(layers[0], x, veil))[0]
+
+    def __call__(self, x, y=None):
+        with torch.no_grad():
+            out = tuple(self._out(t) for t in self._forward(x, y))
+        return out if len(out) > 1 else out[0]
+
+    def _forward(self, x, y):
+        """depthnet.py, resnet.py, fusionnet.py, partial_depthnet.py and partial_fusionnet.py: the x branch (stem, layer1, layer2); under fusion the
+        y branch (conv2, layer5, layer6) and the Fusion 1x1; layer3, layer4 (skip_relu: ReLU between them and before the head); the heads."""
+        x = self._branch('conv1', ('layer1', 'layer2'), x)
+        if 'conv2' in self.stems:
+            x = self._fusion(x, self._branch('conv2', ('layer5', 'layer6'), y))
+        a = self._layer('layer3', x)
+        n = self._layer('layer4', ops.relu(a) if self.skip_relu else a)
+        if self.family == 'resnet':
+            return tuple(self._head(c, n) for c in self.heads if c is not None)
+        return self._head(self.heads[0], ops.relu(n) if self.skip_relu else n), (a if self.early_dist else n)
+
+
+class FoldedNet(_Folded):
+    """The fp32 folded network, on the x3 kernels.  Besides the buffer it holds one workspace; the stems fold to fp32 weights, then each is restated
+    as the image the stem kernels read."""
+    WHO, HALF, Conv = 'infer.fold', False, _Conv
+
+    def _allocate(self, device):
+        self.workspace = torch.empty(1 << 20, dtype=torch.uint8, device=device)
+        super()._allocate(device)
+
+    def _plan_stem(self, conv, bn):
+        return _Stem(conv, bn)
+
+    def _plan_fusion(self, f):
+        """The Fusion 1x1 as its two input-channel windows: x's without b', then y's accumulated onto it with b' and the ReLU."""
+        half = f.conv.weight.shape[1] // 2
+        return self._add(_Conv(f.conv, f.bn, 0, half, has_bias=False)), self._add(_Conv(f.conv, f.bn, half, half))
+
+    def _units(self):
+        return list(self.stems.values()) + self.convs
+
+    def refresh(self):
+        """Re-fold every conv from the current parameters and running statistics: one fold launch (+ the stem's image restatement)."""
+        super().refresh()
+        for s in self.stems.values():
+            if s.foldable:
+                ws = self._ws(s.k * 256 * 4)
+                check(lib().p3d_stem_weight_image(self._at(s.w_off), s.k, s.cin, self._at(s.img_off), ops._p(ws), ws.numel(), ops._stream()),
+                      'p3d_stem_weight_image')
+        return self
 
     def _ws(self, nbytes):
         if self.workspace.numel() < nbytes:
             self.workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=self.buffer.device)
         return self.workspace
 
-    def bias(self, c):
-        """b' of a folded conv as a tensor view of the buffer (tests)."""
-        return self.buffer[c.bias_off:c.bias_off + 4 * c.k].view(torch.float32)
-
     def image(self, c):
         """The folded forward weight image of a conv (tests)."""
         return self.buffer[c.img_off:c.img_off + c.img_bytes]
 
-    def _conv(self, c, x, res=None, relu=False, out=None, accumulate=0, bias=True):
+    @staticmethod
+    def _in(x):
+        return x
+
+    _out = _in
+
+    def _conv(self, c, x, res=None, relu=False, out=None, accumulate=0):
         """y = conv(x, w') + b' (+ out) (+ res) (then ReLU) on the folded image; None when the x3 forward cannot take the conv."""
         L = lib()
         d = c.desc(x, accumulate) if c.foldable else None
-        image_fed = NARROW_IMAGE and c.k <= 64
-        if d is None or not L.p3d_fx_conv_fwd_infer_supported(ctypes.byref(d), int(image_fed)):
+        if d is None or not L.p3d_fx_conv_fwd_infer_supported(ctypes.byref(d), 0):
             return None
         x = x.contiguous()
         y = out if out is not None else torch.empty((d.N, d.K, d.Ho, d.Wo), dtype=torch.float32, device=x.device)
-        x_img = ops.act_image(x) if image_fed else None
         ws = self._ws(L.p3d_fx_conv_fwd_infer_workspace_bytes(ctypes.byref(d)))
-        check(L.p3d_fx_conv_fwd_infer(ctypes.byref(d), None if image_fed else ops._p(x), ops._p(x_img), self._at(c.img_off), c.img_bytes,
-                                      self._at(c.bias_off) if (bias and c.bias_off is not None) else None, ops._p(None if res is None else res.contiguous()),
+        check(L.p3d_fx_conv_fwd_infer(ctypes.byref(d), ops._p(x), None, self._at(c.img_off), c.img_bytes,
+                                      self._at(c.bias_off) if c.bias_off is not None else None, ops._p(None if res is None else res.contiguous()),
                                       int(bool(relu)), ops._p(y), ops._p(ws), ws.numel(), ops._stream()), 'p3d_fx_conv_fwd_infer')
         return y
 
@@ -251,71 +369,6 @@ class _Folded:
                                              ops._stream()), 'p3d_fx_conv_fwd_infer_masked')
         return y, mask_out
 
-
-class FoldedConv(_Folded):
-    """One conv (no bias) + eval-mode BatchNorm, folded: FoldedConv(conv, bn)(x, res=None, relu=False) = relu(bn(conv(x)) + res).  For a PartialConv
-    the validity mask comes along: FoldedConv(pconv, bn)(x, res, relu, veil=mask_in) = (relu(bn(pconv(x, mask_in)[0]) + res), mask_out)."""
-
-    def __init__(self, conv, bn):
-        self.model, self.stems = None, {}
-        self.conv = _Conv(conv, bn)
-        self.convs = [self.conv]
-        self._allocate(conv.weight.device)
-
-    def _check(self):
-        if self.conv.bn.training:
-            raise P3DError('infer.FoldedConv: the BatchNorm is in training mode')
-
-    def __call__(self, x, res=None, relu=False, veil=None):
-        if self.conv.partial != (veil is not None):
-            raise P3DError('infer.FoldedConv: a partial convolution takes its validity mask (veil=), a dense one none')
-        with torch.no_grad():
-            return self._pconv(self.conv, x, veil, res, relu) if self.conv.partial else self._conv_bn(self.conv, x, res, relu)
-
-
-class FoldedNet(_Folded):
-    """model.eval()'s forward with every BatchNorm folded into its convolution.  Holds one device buffer with every weight image and bias, and one
-    workspace.  Parameters and running statistics are read at fold / refresh() time only (the per-layer fallbacks read them live)."""
-
-    def __init__(self, model):
-        _check_foldable(model)
-        self.model = model
-        self.family = _family(model)
-        self.device = next(model.parameters()).device
-        self.skip_relu = bool(getattr(model, 'skip_relu', False))
-        self.early_dist = bool(getattr(model, 'early_dist', False))
-        self.stems, self.convs = {}, []
-        fam = self.family
-        self.fold_partial = fold_partial()
-        partial = {'partial_depthnet': ('layer1', 'layer2'), 'partial_fusionnet': ('layer5', 'layer6')}.get(fam, ()) if self.fold_partial else ()
-        if fam != 'partial_depthnet' or self.fold_partial:
-            self.stems['conv1'] = _Stem(model.conv1, model.bn1)
-        if fam == 'fusionnet' or (fam == 'partial_fusionnet' and self.fold_partial):
-            self.stems['conv2'] = _Stem(model.conv2, model.bn2)
-        dense = {'depthnet': ('layer1', 'layer2', 'layer3', 'layer4'), 'resnet': ('layer1', 'layer2', 'layer3', 'layer4'),
-                 'fusionnet': ('layer1', 'layer2', 'layer3', 'layer4', 'layer5', 'layer6'), 'partial_depthnet': ('layer3', 'layer4'),
-                 'partial_fusionnet': ('layer1', 'layer2', 'layer3', 'layer4')}[fam]
-        self.blocks = {}
-        for lname in dense + partial:
-            plans = []
-            for blk in getattr(model, lname):
-                plan = dict(block=blk, chain=[self._add(_Conv(getattr(blk, c), getattr(blk, b))) for c, b in blk._chain])
-                plan['ds'] = self._add(_Conv(blk.downsample[0], blk.downsample[1])) if blk.downsample is not None else None
-                plans.append(plan)
-            self.blocks[lname] = plans
-        if fam in ('fusionnet', 'partial_fusionnet'):
-            f = model.fusion
-            half = f.conv.weight.shape[1] // 2
-            self.fusion = (self._add(_Conv(f.conv, f.bn, 0, half, has_bias=False)), self._add(_Conv(f.conv, f.bn, half, half)))
-        heads = ('cam_regressor', 'mat_regressor') if fam == 'resnet' else ('regressor',)
-        self.heads = [self._add(_Conv(getattr(model, h), None)) if getattr(model, h, None) is not None else None for h in heads]
-        self._allocate(self.device)
-
-    def _add(self, c):
-        self.convs.append(c)
-        return c
-
-    # ---- forward ---------------------------------------------------------------------------------------------------
     def _stem(self, s, x):
         n, cin, h, w = x.shape
         L = lib()
@@ -354,23 +407,9 @@ class FoldedNet(_Folded):
         check(L.p3d_stem_tail_infer(ops._p(c), self._at(s.bias_off), ops._p(y), n, s.k, h // 2, w // 2, st), 'p3d_stem_tail_infer')
         return y, self.model.maxpool(mask_out)
 
-    def _layer(self, name, x, veil=None):
-        for plan in self.blocks[name]:
-            blk = plan['block']
-            res = x if plan['ds'] is None else self._conv_bn(plan['ds'], x)
-            out = x
-            last = len(plan['chain']) - 1
-            for i, c in enumerate(plan['chain']):
-                if blk.partial:                             # (the closing ReLU of a partial block is unconditional: _trunk.py forward_partial)
-                    out, veil = self._pconv(c, out, veil, res if i == last else None)
-                else:
-                    out = self._conv_bn(c, out, relu=True) if i < last else self._conv_bn(c, out, res=res, relu=not blk.skip_relu)
-            x = out
-        return x if veil is None else (x, veil)
-
     def _fusion(self, x, y):
         a, b = self.fusion
-        out = self._conv(a, x, bias=False)
+        out = self._conv(a, x)
         if out is not None:
             out2 = self._conv(b, y, relu=True, out=out, accumulate=1)
             if out2 is not None:
@@ -381,202 +420,64 @@ class FoldedNet(_Folded):
         y = self._conv(c, x)
         return c.conv(x) if y is None else y
 
-    def __call__(self, x, y=None):
-        with torch.no_grad():
-            return self._forward(x, y)
 
-    def _forward(self, x, y):
-        m, fam = self.model, self.family
-        relu = ops.relu
-        if fam == 'depthnet':
-            x = self._stem(self.stems['conv1'], x)
-            x = self._layer('layer2', self._layer('layer1', x))
-            a = self._layer('layer3', x)
-            n = self._layer('layer4', relu(a) if self.skip_relu else a)
-            z = self._head(self.heads[0], relu(n) if self.skip_relu else n)
-            return z, (a if self.early_dist else n)
-        if fam == 'resnet':
-            x = self._stem(self.stems['conv1'], x)
-            for name in ('layer1', 'layer2', 'layer3', 'layer4'):
-                x = self._layer(name, x)
-            if self.heads[1] is not None:
-                return self._head(self.heads[0], x), self._head(self.heads[1], x)
-            return self._head(self.heads[0], x)
-        if fam == 'fusionnet':
-            x = self._stem(self.stems['conv1'], x)
-            y = self._stem(self.stems['conv2'], y)
-            x = self._layer('layer2', self._layer('layer1', x))
-            y = self._layer('layer6', self._layer('layer5', y))
-            x = self._fusion(x, y)
-            a = self._layer('layer3', x)
-            n = self._layer('layer4', relu(a) if self.skip_relu else a)
-            z = self._head(self.heads[0], relu(n) if self.skip_relu else n)
-            return z, (a if self.early_dist else n)
-        from ._trunk import stem_tail
-        if fam == 'partial_depthnet':
-            veil = ops.nonzero_mask(x)
-            if self.fold_partial:
-                x, veil = self._stem_masked(self.stems['conv1'], x, veil)
-                x, veil = self._layer('layer1', x, veil)
-                x, _ = self._layer('layer2', x, veil)       # (layer2's mask_out feeds nothing)
-            else:
-                x, veil = m.conv1(x, veil)                  # P3D_FOLD_PARTIAL=0: the partial-convolution stem and layers on the model's own eval path
-                x = stem_tail(m.bn1, m.maxpool, x)
-                veil = m.maxpool(veil)
-                x, veil = m.layer1((x, veil))
-                x, veil = m.layer2((x, veil))
-            x = self._layer('layer4', self._layer('layer3', x))
-            return self._head(self.heads[0], x), x
-        # partial_fusionnet
-        x = self._stem(self.stems['conv1'], x)
-        veil = ops.nonzero_mask(y)
-        if self.fold_partial:
-            y, veil = self._stem_masked(self.stems['conv2'], y, veil)
-            x = self._layer('layer2', self._layer('layer1', x))
-            y, veil = self._layer('layer5', y, veil)
-            y, _ = self._layer('layer6', y, veil)
-        else:
-            y, veil = m.conv2(y, veil)
-            y = stem_tail(m.bn2, m.maxpool, y)
-            veil = m.maxpool(veil)
-            x = self._layer('layer2', self._layer('layer1', x))
-            y, veil = m.layer5((y, veil))
-            y, veil = m.layer6((y, veil))
-        x = self._fusion(x, y)
-        x = self._layer('layer4', self._layer('layer3', x))
-        return self._head(self.heads[0], x), x
+class FoldedConv(FoldedNet):
+    """One conv (no bias) + eval-mode BatchNorm, folded: FoldedConv(conv, bn)(x, res=None, relu=False) = relu(bn(conv(x)) + res).  For a PartialConv
+    the validity mask comes along: FoldedConv(pconv, bn)(x, res, relu, veil=mask_in) = (relu(bn(pconv(x, mask_in)[0]) + res), mask_out)."""
+    WHO = 'infer.FoldedConv'
+
+    def __init__(self, conv, bn):
+        self.model, self.stems = torch.nn.ModuleList([conv, bn]), {}      # (model: what refresh() checks)
+        self.conv = _Conv(conv, bn)
+        self.convs = [self.conv]
+        self._allocate(conv.weight.device)
+
+    def __call__(self, x, res=None, relu=False, veil=None):
+        if self.conv.partial != (veil is not None):
+            raise P3DError('infer.FoldedConv: a partial convolution takes its validity mask (veil=), a dense one none')
+        with torch.no_grad():
+            return self._pconv(self.conv, x, veil, res, relu) if self.conv.partial else self._conv_bn(self.conv, x, res, relu)
 
 
 def fold(model):
     """FoldedNet of a network in eval mode (every BatchNorm frozen); raises P3DError for a BatchNorm in training mode or a -half_acc model."""
-    model = getattr(model, 'module', model)
-    _check_foldable(model)
-    return FoldedNet(model)
+    return FoldedNet(getattr(model, 'module', model))
 
 
 # ---- -half_acc: BatchNorm folded into the fp16 convolutions ------------------------------------------------------------------------------
-def _check_half_foldable(model):
-    for name, m in model.named_modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            if m.training:
-                raise P3DError('infer.fold_half: BatchNorm %r is in training mode; call model.eval() first (folding uses the running statistics)' % name)
-            if not (m.affine and m.track_running_stats):
-                raise P3DError('infer.fold_half: BatchNorm %r has no running statistics / affine parameters' % name)
-    for p in model.parameters():
-        if not p.is_cuda or p.dtype != torch.float32:
-            raise P3DError('infer.fold_half: parameters must be fp32 masters on the HIP device')
+class HalfFoldedNet(_Folded):
+    """The -half_acc model's eval forward with every BatchNorm folded into its fp16 convolution, partial-convolution layers included; reads the fp32
+    master parameters.  The stems are convs like any other here (then the max pool), so they are in `convs`."""
+    WHO, HALF, Conv = 'infer.fold_half', True, _HConv
 
+    def _plan_stem(self, conv, bn):
+        return self._add(_HConv(conv, bn))
 
-class _HConv:
-    """One conv (+ BatchNorm) of the fp16 folded network: its fp16 image [K][R][S][Cpad] and b' in the buffer (fold kind 2).  A head whose K is not a
-    multiple of 8 (the 17-channel mat_regressor of -joint_space) runs with its image and bias padded to Kpad rows of zeros; its result is the first K channels."""
+    def _plan_fusion(self, f):
+        return self._add(_HConv(f.conv, f.bn))
 
-    def __init__(self, conv, bn):
-        from .partial_conv import PartialConv
-        self.conv, self.bn = conv, bn
-        k, c, r, s = conv.weight.shape
-        self.k, self.kpad, self.c, self.cpad, self.r, self.s = k, ops_half.pad8(k), c, ops_half.pad8(c), r, s
-        self.stride, self.pad, self.dil = _one(conv.stride), _one(conv.padding), _one(conv.dilation)
-        self.partial = isinstance(conv, PartialConv)
-        self.foldable = k <= 2048                           # (the fold kernel's per-job scale table; else: today's fp16 path for this layer)
-        self.images = None                                  # fp16 images of the unfolded weight, for that path only
-        self.img_off = self.bias_off = None
-
-    def layout(self, at):
-        if not self.foldable:
-            return at
-        self.img_off = at
-        at = _up(at + 2 * self.kpad * self.r * self.s * self.cpad)           # (rows K .. Kpad - 1 stay zero: the buffer is zeroed once, the fold writes K rows)
-        self.bias_off = at
-        return _up(at + 4 * self.kpad)
-
-    def job(self, buf):
-        if not self.foldable:
-            return None
-        j = FoldJob()
-        j.w = self.conv.weight.data_ptr()
-        j.conv_bias = self.conv.bias.data_ptr() if self.conv.bias is not None else None
-        if self.bn is not None:
-            j.gamma, j.beta = self.bn.weight.data_ptr(), self.bn.bias.data_ptr()
-            j.mean, j.var = self.bn.running_mean.data_ptr(), self.bn.running_var.data_ptr()
-            j.eps = float(self.bn.eps)
-        j.out = buf.data_ptr() + self.img_off
-        j.bias_out = buf.data_ptr() + self.bias_off
-        j.K, j.C, j.RS, j.c_offset, j.c_total, j.kind, j.reserved = self.k, self.c, self.r * self.s, 0, self.c, 2, self.cpad
-        return j
-
-    def desc(self, x):
-        return ops._desc(tuple(x.shape), (self.kpad, self.cpad, self.r, self.s), self.stride, self.pad, self.dil)
-
-
-class HalfFoldedNet:
-    """The -half_acc model's eval forward with every BatchNorm folded into its fp16 convolution, partial-convolution layers included.  Holds one device
-    buffer with every fp16 weight image and b'; reads the fp32 master parameters and running statistics at fold / refresh() time only."""
-
-    def __init__(self, model):
-        _check_half_foldable(model)
-        self.model = model
-        self.family = _family(model)
-        self.device = next(model.parameters()).device
-        self.skip_relu = bool(getattr(model, 'skip_relu', False))
-        self.early_dist = bool(getattr(model, 'early_dist', False))
-        self.convs = []
-        fam = self.family
-        self.stems = {'conv1': self._add(_HConv(model.conv1, model.bn1))}
-        if fam in ('fusionnet', 'partial_fusionnet'):
-            self.stems['conv2'] = self._add(_HConv(model.conv2, model.bn2))
-        layers = {'depthnet': ('layer1', 'layer2', 'layer3', 'layer4'), 'resnet': ('layer1', 'layer2', 'layer3', 'layer4'),
-                  'fusionnet': ('layer1', 'layer2', 'layer3', 'layer4', 'layer5', 'layer6'), 'partial_depthnet': ('layer1', 'layer2', 'layer3', 'layer4'),
-                  'partial_fusionnet': ('layer1', 'layer2', 'layer3', 'layer4', 'layer5', 'layer6')}[fam]
-        self.blocks = {}
-        for lname in layers:
-            plans = []
-            for blk in getattr(model, lname):
-                plan = dict(block=blk, chain=[self._add(_HConv(getattr(blk, c), getattr(blk, b))) for c, b in blk._chain])
-                plan['ds'] = self._add(_HConv(blk.downsample[0], blk.downsample[1])) if blk.downsample is not None else None
-                plans.append(plan)
-            self.blocks[lname] = plans
-        if fam in ('fusionnet', 'partial_fusionnet'):
-            self.fusion = self._add(_HConv(model.fusion.conv, model.fusion.bn))
-        heads = ('cam_regressor', 'mat_regressor') if fam == 'resnet' else ('regressor',)
-        self.heads = [self._add(_HConv(getattr(model, h), None)) if getattr(model, h, None) is not None else None for h in heads]
-        at = 0
-        for c in self.convs:
-            at = c.layout(at)
-        self.buffer = torch.zeros(max(at, _ALIGN), dtype=torch.uint8, device=self.device)
-        self.refresh()
-
-    def _add(self, c):
-        self.convs.append(c)
-        return c
-
-    # ---- folding ------------------------------------------------------------------------------------------------
     def refresh(self):
         """Re-fold every conv from the current fp32 parameters and running statistics: one fold launch for the whole network."""
-        _check_half_foldable(self.model)
-        jobs = [j for j in (c.job(self.buffer) for c in self.convs) if j is not None]
-        if jobs:
-            table = (FoldJob * len(jobs))(*jobs)
-            self._jobs = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(self.device)     # (kept alive until the launch has read it)
-            check(lib().p3d_fx_fold_bn_images(ops._p(self._jobs), len(jobs), 64, ops._stream()), 'p3d_fx_fold_bn_images')
+        super().refresh()
         for c in self.convs:
             if c.images is not None:
                 c.images.refresh(c.conv.weight)
         return self
 
-    def _at(self, off):
-        return ctypes.c_void_p(self.buffer.data_ptr() + off)
-
-    def bias(self, c):
-        """b' of a folded conv as a tensor view of the buffer (tests)."""
-        return self.buffer[c.bias_off:c.bias_off + 4 * c.k].view(torch.float32)
-
     def image(self, c):
         """The fp16 folded forward image [K][R][S][Cpad] of a conv (tests)."""
         return self.buffer[c.img_off:c.img_off + 2 * c.k * c.r * c.s * c.cpad].view(torch.float16).view(c.k, c.r, c.s, c.cpad)
 
-    # ---- forward ---------------------------------------------------------------------------------------------------
-    def _conv(self, c, x, res=None, relu=False, mask_in=None, mult=None):
+    @staticmethod
+    def _in(x):
+        x = x.float() if x.dtype == torch.float16 else x
+        return ops_half.to_half_nhwc(x, ops_half.pad8(x.shape[1]))
+
+    @staticmethod
+    def _out(x):
+        return ops_half.to_float(x)
+
+    def _conv_bn(self, c, x, res=None, relu=False, mask_in=None, mult=None):
         """y = fp16(relu?(conv(x * mask_in) * mult + b' + res)) on the folded image; a conv the entry point cannot take runs on today's fp16 path."""
         L = lib()
         d = c.desc(x)
@@ -597,7 +498,7 @@ class HalfFoldedNet:
     def _pconv(self, c, x, veil, res=None, relu=True):
         """A partial convolution (partial_conv.py): mask_in = veil, mult and mask_out from its box count; returns (y, mask_out)."""
         mult, mask_out = ops.mask_count(veil, c.r, c.stride, c.pad, c.dil)
-        return self._conv(c, x, res, relu, mask_in=veil.contiguous(), mult=mult), mask_out
+        return self._conv_bn(c, x, res, relu, mask_in=veil.contiguous(), mult=mult), mask_out
 
     def _pool(self, x):
         """max pool 3x3 / 2 behind the folded stem (its ReLU already applied: max and ReLU commute per channel), no window codes."""
@@ -606,72 +507,21 @@ class HalfFoldedNet:
         check(lib().p3d_hmaxpool3x3s2_fwd(ops._p(x), ops._p(y), None, n, h, w, c, ops._stream()), 'p3d_hmaxpool3x3s2_fwd')
         return y
 
-    def _layer(self, name, x, veil=None):
-        for plan in self.blocks[name]:
-            blk = plan['block']
-            res = x if plan['ds'] is None else self._conv(plan['ds'], x)
-            out, last = x, len(plan['chain']) - 1
-            for i, c in enumerate(plan['chain']):
-                if blk.partial:                             # (the closing ReLU of a partial block is unconditional, partial_depthnet.py:70-75)
-                    out, veil = self._pconv(c, out, veil, res if i == last else None)
-                else:
-                    out = self._conv(c, out, res if i == last else None, relu=(i < last) or not blk.skip_relu)
-            x = out
-        return x if veil is None else (x, veil)
+    def _stem(self, s, x):
+        return self._pool(self._conv_bn(s, x, relu=True))
 
-    @staticmethod
-    def _in(x):
-        x = x.float() if x.dtype == torch.float16 else x
-        return ops_half.to_half_nhwc(x, ops_half.pad8(x.shape[1]))
+    def _stem_masked(self, s, x, veil):
+        y, veil = self._pconv(s, x, veil)
+        return self._pool(y), self.model.maxpool(veil)
 
-    @staticmethod
-    def _out(*tensors):
-        out = tuple(ops_half.to_float(t) for t in tensors)
-        return out if len(out) > 1 else out[0]
+    def _fusion(self, x, y):
+        return self._conv_bn(self.fusion, ops_half.concat(x, y), relu=True)
 
-    def __call__(self, x, y=None):
-        with torch.no_grad():
-            return self._forward(x, y)
-
-    def _forward(self, x, y):
-        m, fam = self.model, self.family
-        relu = ops_half.relu
-        if fam == 'partial_depthnet':
-            veil = ops.nonzero_mask(x.float())
-            h, veil = self._pconv(self.stems['conv1'], self._in(x), veil)
-            h, veil = self._pool(h), m.maxpool(veil)
-            h, veil = self._layer('layer1', h, veil)
-            h, _ = self._layer('layer2', h, veil)
-            h = self._layer('layer4', self._layer('layer3', h))
-            return self._out(self._conv(self.heads[0], h), h)
-        x = self._pool(self._conv(self.stems['conv1'], self._in(x), relu=True))
-        if fam == 'resnet':
-            for name in ('layer1', 'layer2', 'layer3', 'layer4'):
-                x = self._layer(name, x)
-            return self._out(*[self._conv(c, x) for c in self.heads if c is not None])
-        x = self._layer('layer2', self._layer('layer1', x))
-        if fam == 'fusionnet':
-            y = self._pool(self._conv(self.stems['conv2'], self._in(y), relu=True))
-            y = self._layer('layer6', self._layer('layer5', y))
-            x = self._conv(self.fusion, ops_half.concat(x, y), relu=True)
-        elif fam == 'partial_fusionnet':
-            veil = ops.nonzero_mask(y.float())
-            y, veil = self._pconv(self.stems['conv2'], self._in(y), veil)
-            y, veil = self._pool(y), m.maxpool(veil)
-            y, veil = self._layer('layer5', y, veil)
-            y, _ = self._layer('layer6', y, veil)
-            x = self._conv(self.fusion, ops_half.concat(x, y), relu=True)
-            x = self._layer('layer4', self._layer('layer3', x))
-            return self._out(self._conv(self.heads[0], x), x)
-        a = self._layer('layer3', x)
-        n = self._layer('layer4', relu(a) if self.skip_relu else a)
-        z = self._conv(self.heads[0], relu(n) if self.skip_relu else n)
-        return self._out(z, a if self.early_dist else n)
+    def _head(self, c, x):
+        return self._conv_bn(c, x)
 
 
 def fold_half(model):
     """HalfFoldedNet of a -half_acc network in eval mode: fp32 (or fp16) NCHW input, fp32 NCHW outputs, as model.eval()(x) returns them under
     -half_acc.  Raises P3DError for a BatchNorm in training mode or parameters that are not fp32 on the HIP device."""
-    model = getattr(model, 'module', model)
-    _check_half_foldable(model)
-    return HalfFoldedNet(model)
+    return HalfFoldedNet(getattr(model, 'module', model))

@@ -2,7 +2,7 @@
 
 Every partial-conv class against a float64 partial conv + BatchNorm, empty windows exactly relu(b' + res); the masked stem; whole partial_depthnet and
 partial_fusionnet networks against today's eval forward and a float64 forward; no BatchNorm pass and no fp32-MFMA forward launch in a folded forward; the
-P3D_FOLD_PARTIAL switch and the per-layer fallback; refresh(); the Trainer."""
+per-layer fallback; refresh(); the Trainer."""
 import ctypes
 import json
 
@@ -232,13 +232,19 @@ def test_masked_stem_against_float64(pkg, family):
 
 
 # ---- 3. whole networks -------------------------------------------------------------------------------------------------------------------
+def _folds_partial_layers(fn):
+    """The masked stem and every partial conv of a FoldedNet are in its fold, none left on the model's own modules."""
+    partial = [c for c in fn.convs if c.partial]
+    return any(st.masked and st.foldable for st in fn.stems.values()) and len(partial) > 0 and all(c.foldable for c in partial)
+
+
 @pytest.mark.parametrize('family', ['partial_depthnet', 'partial_fusionnet'])
 @pytest.mark.parametrize('model,side,batch', [('resnet18', 128, 2), ('resnet50', 256, 64)], ids=['r18_128_b2', 'r50_256_b64'])
-def test_whole_partial_network(pkg, family, model, side, batch):
+def test_whole_partial_network_folded(pkg, family, model, side, batch):
     net = _net(pkg, family, model, side=side, seed=2)
     inputs = _inputs(family, batch, side, seed=1)
     fn = pkg.infer.fold(net)
-    assert fn.fold_partial
+    assert _folds_partial_layers(fn)
     got = fn(*inputs)
     with torch.no_grad():
         old = net(*inputs)
@@ -278,25 +284,7 @@ def test_folded_partial_forward_has_no_batchnorm_pass(pkg, monkeypatch, family):
     assert calls.count('batch_norm_act') > 0 and calls.count('p3d_bn_eval_fwd') > 0
 
 
-# ---- 5. the switch and the per-layer fallback --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('family', ['partial_depthnet', 'partial_fusionnet'])
-def test_fold_partial_switch_off(pkg, monkeypatch, family):
-    net = _net(pkg, family, 'resnet18', seed=6)
-    inputs = _inputs(family, 2, 128, seed=6)
-    on = pkg.infer.fold(net)
-    monkeypatch.setenv('P3D_FOLD_PARTIAL', '0')
-    off = pkg.infer.fold(net)
-    assert on.fold_partial and not off.fold_partial
-    assert len(off.convs) < len(on.convs)
-    calls = _count_bn(pkg, monkeypatch)
-    got_on = on(*inputs)
-    assert calls == []
-    got_off = off(*inputs)
-    assert calls.count('p3d_bn_eval_fwd') > 0                   # the partial layers' BatchNorm passes are back
-    for a, b in zip(got_on, got_off):
-        assert _rel(a, b) < 1e-4
-
-
+# ---- 5. the per-layer fallback ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('family', ['partial_depthnet', 'partial_fusionnet'])
 def test_odd_side_falls_back_per_layer(pkg, monkeypatch, family):
     net = _net(pkg, family, 'resnet18', side=129, seed=7)
@@ -406,7 +394,7 @@ def _distill_trainer(pkg):
     return trainer, batch, student
 
 
-def test_distill_step_with_folded_partial_teacher(pkg, monkeypatch):
+def test_distill_step_with_fully_folded_partial_teacher(pkg, monkeypatch):
     results = []
     for on in ('0', '1'):
         monkeypatch.setenv('P3D_FOLDED_EVAL', on)
@@ -416,7 +404,7 @@ def test_distill_step_with_folded_partial_teacher(pkg, monkeypatch):
         cam, dist = trainer.distill_step(1, c, d, tc, tv, att)
         assert (trainer.folded_teacher is not None) == (on == '1')
         if on == '1':
-            assert trainer.folded_teacher.family == 'partial_fusionnet' and trainer.folded_teacher.fold_partial
+            assert trainer.folded_teacher.family == 'partial_fusionnet' and _folds_partial_layers(trainer.folded_teacher)
         results.append((float(cam), float(dist), student.state_dict()['regressor.weight'].detach().clone()))
     (c0, d0, w0), (c1, d1, w1) = results
     assert c1 == pytest.approx(c0, rel=1e-4) and d1 == pytest.approx(d0, rel=1e-4)

@@ -1,7 +1,5 @@
-"""The folded partial-convolution entry points (p3d_fx_conv_fwd_infer_masked[_supported]) and the P3D_FOLD_PARTIAL switch (no GPU needed)."""
+"""The folded partial-convolution entry points (p3d_fx_conv_fwd_infer_masked[_supported]) (no GPU needed)."""
 import ctypes
-
-import pytest
 
 
 def test_masked_infer_symbols_are_bound(pkg):
@@ -22,11 +20,3 @@ def test_masked_infer_supported_query_is_host_only(pkg):
     assert L.p3d_fx_conv_fwd_infer_masked_supported(ctypes.byref(accumulate)) == 0
     assert L.p3d_fx_conv_fwd_infer_masked_supported(None) == 0
 
-
-@pytest.mark.parametrize('value,on', [(None, True), ('1', True), ('0', False)])
-def test_fold_partial_switch(pkg, monkeypatch, value, on):
-    if value is None:
-        monkeypatch.delenv('P3D_FOLD_PARTIAL', raising=False)
-    else:
-        monkeypatch.setenv('P3D_FOLD_PARTIAL', value)
-    assert pkg.infer.fold_partial() is on

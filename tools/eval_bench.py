@@ -4,14 +4,12 @@
 Legs, timed in the same process, alternating (device-synchronised, 10 warm-up + 50 timed iterations per round):
   fused     today's eval path: conv + BN (+ res + ReLU) per layer in one kernel (ops.conv_bn_eval, the fp32-MFMA kernel)
   folded    infer.fold(model): BatchNorm folded into the x3 convolutions (p3d_fx_conv_fwd_infer)
---family partial_depthnet / partial_fusionnet times those networks (depth ~ U[0, 1) with values < 0.3 zeroed; partial_depthnet: -depth_only) and adds
-  folded_nopartial  infer.fold(model) under P3D_FOLD_PARTIAL=0: the partial-convolution layers on the model's own modules
+--family partial_depthnet / partial_fusionnet times those networks (depth ~ U[0, 1) with values < 0.3 zeroed; partial_depthnet: -depth_only).
 --half replaces them with the -half_acc legs:
   half          today's fp16 eval forward: fp16 conv, then a stand-alone eval-mode BatchNorm (+ res + ReLU) pass per layer
   half_folded   infer.fold_half(model): BatchNorm folded into the fp16 convolutions (p3d_hconv2d_fwd_infer)
 --separate adds the round-1 leg with stand-alone BatchNorm passes; --distill also times one distill_step with and without the folded teacher
-(with --half: a -half_acc student and teacher, P3D_FOLDED_EVAL_HALF; with --family partial_fusionnet: a partial_fusionnet teacher, folded with
-P3D_FOLD_PARTIAL=1 and =0).
+(with --half: a -half_acc student and teacher, P3D_FOLDED_EVAL_HALF; with --family partial_fusionnet: a partial_fusionnet teacher).
 Prints one line per leg and round, then a JSON summary line."""
 import argparse
 import importlib
@@ -63,12 +61,6 @@ if opt.half:
 else:
     folded = pkg.infer.fold(model)
     legs = {'fused': lambda: model(*inputs), 'folded': lambda: folded(*inputs)}
-    if opt.family != 'depthnet':
-        os.environ['P3D_FOLD_PARTIAL'] = '0'            # (read when the net is folded)
-        nopartial = pkg.infer.fold(model)
-        os.environ.pop('P3D_FOLD_PARTIAL')
-        assert folded.fold_partial and not nopartial.fold_partial
-        legs['folded_nopartial'] = lambda: nopartial(*inputs)
 if opt.separate:
     legs['separate'] = lambda: model(*inputs)
 if opt.only:
@@ -106,25 +98,16 @@ if opt.distill:
     student = pkg.depthnet.__dict__[opt.model](dargs, False).cuda()
     teacher_family = pkg.partial_fusionnet if opt.family == 'partial_fusionnet' else pkg.fusionnet
     teacher = teacher_family.__dict__[opt.model](dargs, False).cuda().eval()
-    # (teacher leg, value of the switch, P3D_FOLD_PARTIAL when the teacher is folded): with a partial teacher, its partial layers folded and not
-    configs = [('teacher', '0', None), ('folded_teacher', '1', None)]
-    if opt.family == 'partial_fusionnet' and not opt.half:
-        configs = [('teacher', '0', None), ('folded_teacher', '1', '1'), ('folded_teacher_nopartial', '1', '0')]
     c, d, tc, tv = (torch.from_numpy(a).cuda() for a in pkg.synth.make_batch(opt.batch, side=opt.side, rank=0, step=0))
     side_out = (opt.side - 1) // 16 + 1
     att = torch.ones(opt.batch, 1, side_out, side_out, device='cuda')
     res = {}
     for r in range(opt.rounds):
-        for leg, on, fold_partial in configs:
+        for leg, on in (('teacher', '0'), ('folded_teacher', '1')):
             os.environ[switch] = on
-            if fold_partial is not None:
-                os.environ['P3D_FOLD_PARTIAL'] = fold_partial
             tr = pkg.depth_train.Trainer(dargs, student, pkg.utils.get_info()) if r == 0 and on == '0' else tr
             tr.set_teacher(teacher)
-            os.environ.pop('P3D_FOLD_PARTIAL', None)
             assert (tr.folded_teacher is not None) == (on == '1')
-            if fold_partial is not None:
-                assert tr.folded_teacher.fold_partial == (fold_partial == '1')
             for _ in range(3):
                 tr.distill_step(1, c, d, tc, tv, att)
             torch.cuda.synchronize()
