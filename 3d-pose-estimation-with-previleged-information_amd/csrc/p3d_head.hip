@@ -339,6 +339,84 @@ __global__ __launch_bounds__(256) void masked_loss_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-batch evaluation statistics of Trainer.test (the back-rotation of _run_test + utils.analyze, utils.py:237-276).  The coordinates and
+// distances repeat numpy's float32 operations in numpy's order: np.einsum('Bij,BCj->BCi') sums its three products left to right,
+// np.linalg.norm sums the squares left to right before a correctly rounded sqrt, `dist / rough` is a correctly rounded float32 division.
+// Contraction into FMAs is off here (plain operators under the pragma: HIP's __fmul_rn / __fadd_rn are inline `*` / `+` that the file's
+// contraction setting may still fuse), so the threshold tests and hence the class counts come out as numpy's.
+constexpr int EVAL_SUMS = 10;        // valid, sum dist, pck, sum auc, solid, close, depth, jitter, switch, fail (P3D_EVAL_* columns 0..9)
+
+__device__ __forceinline__ void rotate3_rn(const float* __restrict__ R, const float* __restrict__ v, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const float v0 = v[0], v1 = v[1], v2 = v[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) out[i] = (R[3 * i] * v0 + R[3 * i + 1] * v1) + R[3 * i + 2] * v2;
+}
+
+__device__ __forceinline__ float norm3_rn(const float* __restrict__ a, const float* __restrict__ b) {
+#pragma clang fp contract(off)
+    const float d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2];
+    return sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+}
+
+// One 256-thread block per batch; thread t walks the joints t, t + 256, ...  The block sums in a fixed order (butterfly per wave, then
+// waves 0..3), without atomics: the same batch gives the same row bits in every process.
+__global__ __launch_bounds__(256) void pose_eval_stats_kernel(const float* __restrict__ spec_cam, const float* __restrict__ true_cam,
+                                                              const float* __restrict__ rotate, const uint8_t* __restrict__ true_val,
+                                                              const int32_t* __restrict__ mirror, int B, int J, float solid, float close,
+                                                              float rough, const float* __restrict__ loss, double* __restrict__ row,
+                                                              float* __restrict__ spec_rot) {
+#pragma clang fp contract(off)
+    __shared__ double red[EVAL_SUMS][4];
+    const int t = threadIdx.x;
+    double acc[EVAL_SUMS];
+#pragma unroll
+    for (int k = 0; k < EVAL_SUMS; ++k) acc[k] = 0.0;
+    for (int i = t; i < B * J; i += 256) {
+        const int b = i / J, j = i - b * J;
+        const float* R = rotate + (size_t)b * 9;
+        float spec[3], truth[3], other[3];
+        rotate3_rn(R, spec_cam + (size_t)i * 3, spec);
+        if (spec_rot != nullptr) {
+            spec_rot[(size_t)i * 3 + 0] = spec[0];
+            spec_rot[(size_t)i * 3 + 1] = spec[1];
+            spec_rot[(size_t)i * 3 + 2] = spec[2];
+        }
+        if (!true_val[i]) continue;
+        rotate3_rn(R, true_cam + (size_t)i * 3, truth);
+        const int m = mirror[j];
+        float flip = __builtin_nanf("");                        // (an out-of-range mirror index reads nothing; the host checks the table)
+        if (m >= 0 && m < J) {
+            rotate3_rn(R, true_cam + ((size_t)b * J + m) * 3, other);
+            flip = norm3_rn(spec, other);
+        }
+        const float dist = norm3_rn(spec, truth);
+        const float dx = spec[0] - truth[0], dy = spec[1] - truth[1];
+        const float tangent = sqrtf(dx * dx + dy * dy);
+        const float q = dist / rough;
+        const float auc = 1.0f - q;
+        // utils.statistics: each joint is counted by the first test it passes
+        const int cls = dist <= solid ? 0 : dist <= close ? 1 : tangent <= close ? 2 : dist <= rough ? 3 : flip <= rough ? 4 : 5;
+        acc[0] += 1.0;
+        acc[1] += (double)dist;
+        acc[2] += q <= 1.0f ? 1.0 : 0.0;
+        acc[3] += (double)(auc < 0.0f ? 0.0f : auc);            // np.maximum(0, 1 - dist / rough) (a NaN stays NaN, as in numpy)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc[4 + k] += cls == k ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < EVAL_SUMS; ++k) {
+        const double v = wave_sum(acc[k]);
+        if ((t & 63) == 0) red[k][t >> 6] = v;
+    }
+    __syncthreads();
+    if (t < EVAL_SUMS) row[t] = ((red[t][0] + red[t][1]) + red[t][2]) + red[t][3];
+    else if (t == P3D_EVAL_LOSS) row[t] = (double)loss[0];
+    else if (t == P3D_EVAL_BATCH) row[t] = (double)B;
+    else if (t == P3D_EVAL_PRESENT) row[t] = 1.0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // utils.get_recon_cam (utils.py:335-366): least-squares position t of the unknown reference point such that the root-relative pose, moved by t,
 // projects onto the estimated image coordinates:  rows (1, 0, -nx_j | nx_j z_j - x_j), (0, 1, -ny_j | ny_j z_j - y_j) with n_j the first two
 // components of K^-1 (u_j, v_j, 1);  t = (A^T A)^-1 A^T b in closed form (A^T A depends on sum n, sum |n|^2 only);  recon_j = relat_j + t.
@@ -491,6 +569,17 @@ int32_t p3d_masked_loss_fwd_bwd(const float* pred, const float* target, const ui
     P3D_REQUIRE(criterion >= 0 && criterion <= 2, "masked_loss: bad criterion %d", criterion);
     hipLaunchKernelGGL(masked_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pred, target, valid, loss, dpred, rows, C, criterion, count_override);
     return check_launch("masked_loss");
+}
+
+int32_t p3d_pose_eval_stats(const float* spec_cam, const float* true_cam, const float* rotate, const uint8_t* true_val, const int32_t* mirror,
+                            int32_t B, int32_t J, float solid, float close, float rough, const float* loss, double* row, float* spec_rot_out,
+                            void* stream) {
+    P3D_REQUIRE(spec_cam && true_cam && rotate && true_val && mirror && loss && row, "pose_eval_stats: null tensor");
+    P3D_REQUIRE(B > 0 && J > 0 && (int64_t)B * J * 3 <= INT32_MAX, "pose_eval_stats: bad shape B=%d J=%d", B, J);
+    P3D_REQUIRE(rough > 0.f && solid == solid && close == close, "pose_eval_stats: bad thresholds solid=%g close=%g rough=%g", solid, close, rough);
+    hipLaunchKernelGGL(pose_eval_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, spec_cam, true_cam, rotate, true_val, mirror, B, J,
+                       solid, close, rough, loss, row, spec_rot_out);
+    return check_launch("pose_eval_stats");
 }
 
 int32_t p3d_recon_cam_fwd(const float* spec_mat, const float* relat_cam, const float* intrinsics, float* recon, int32_t B, int32_t J, void* stream) {

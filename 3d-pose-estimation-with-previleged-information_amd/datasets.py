@@ -15,12 +15,17 @@ import torch
 import torch.utils.data as data
 
 from . import cameralib, crops, synth
+from .dist import eval_batch_sampler
 from .depth_datasets import shard
 
 
 def data_loader(args, phase, data_info):
     dataset = Dataset(args, phase, data_info)
-    loader = data.DataLoader(dataset, args.batch_size, shuffle=(args.shuffle and phase == 'train'), num_workers=args.workers, pin_memory=True)
+    sampler = eval_batch_sampler(len(dataset), args.batch_size, phase)       # P3D_DEVICE_EVAL=1 under torchrun: only this rank's test batches
+    if sampler is not None:
+        loader = data.DataLoader(dataset, batch_sampler=sampler, num_workers=args.workers, pin_memory=True)
+    else:
+        loader = data.DataLoader(dataset, args.batch_size, shuffle=(args.shuffle and phase == 'train'), num_workers=args.workers, pin_memory=True)
     if dataset.synthetic:
         return loader
     return crops.GpuCropLoader(loader, args.side_in, dataset.raw_color)

@@ -293,6 +293,8 @@ class Trainer:
         reference's host-side metrics on the back-rotated coordinates."""
         if self.thresh is None:
             raise RuntimeError('evaluation needs the `thresholds` entry of metadata.json (-metadata / $P3D_METADATA)')
+        if utils.device_eval_enabled():
+            return self._run_test_device(epoch, test_loader, device)
         n_batches = len(test_loader)
         loss_avg, total, cam_stats = 0.0, 0, []
         side_out = (self.side_in - 1) // self.stride + 1
@@ -326,6 +328,66 @@ class Trainer:
                 print('| test Epoch[%d] [%d/%d]  Cam Loss %1.4f' % (epoch, i_batch, n_batches, value))
         record = dict(test_loss=loss_avg / max(total, 1))
         record.update(utils.parse_epoch(cam_stats))
+        if self.verbose:
+            print('\n=> test Epoch[%d]  Cam Loss: %1.4f\n' % (epoch, record['test_loss']))
+            print('=>[SPEC] cam_mean: %1.3f  [pck]: %1.3f  [auc]: %1.3f\n' % (record['cam_mean'], record['score_pck'], record['score_auc']))
+        return record
+
+    def _run_test_device(self, epoch, test_loader, device):
+        """P3D_DEVICE_EVAL=1: the forward, head and loss of _run_test, then the back-rotation and the metrics of one batch in one kernel
+        (ops.pose_eval_stats) into a device table with a row per global batch; nothing is read back before the loop ends.  Under a process
+        group of W > 1 ranks, rank r evaluates the batches i = r (mod W) -- a loader built on dist.EvalBatchSampler loads only those, any
+        other iterable is sharded by its enumeration index -- and one all-gather of the tables gives every rank the same record."""
+        import torch.distributed as tdist
+        world = tdist.get_world_size() if tdist.is_initialized() else 1
+        rank = tdist.get_rank() if world > 1 else 0
+        shard = p3d_dist.loader_shard(test_loader)
+        if shard is not None:
+            if (shard.rank, shard.world) != (rank, world):
+                raise RuntimeError('the test loader serves rank %d of %d, the process group is rank %d of %d' % (shard.rank, shard.world, rank, world))
+            n_batches, indices = shard.global_batches, shard.batch_indices
+        else:
+            n_batches = len(test_loader)
+            indices = None
+        mirror = np.asarray(self.data_info.mirror)
+        if mirror.shape != (self.num_joints,) or mirror.min() < 0 or mirror.max() >= self.num_joints:
+            raise ValueError('data_info.mirror must hold %d joint indices in [0, %d)' % (self.num_joints, self.num_joints))
+        mirror = torch.from_numpy(mirror.astype(np.int32)).to(device)
+        table = torch.zeros((max(-(-n_batches // world), 1), ops.EVAL_ROW), dtype=torch.float64, device=device)
+        side_out = (self.side_in - 1) // self.stride + 1
+        fusion = self.do_fusion and not self.do_teach           # under -do_teach the student (single stream) is what gets evaluated
+        for position, items in enumerate(to_test_worker(test_loader, self.no_depth, self.depth_only, fusion)):
+            if indices is not None:
+                i_batch = indices[position]
+            elif position % world != rank:
+                continue
+            else:
+                i_batch = position
+            color_image, depth_image, true_cam, true_val, color_br = items
+            color_image = None if color_image is None else self.to(color_image, device)
+            depth_image = None if depth_image is None else self.to(depth_image, device)
+            if self.gpu_augment is not None and color_image is not None:
+                color_image = self.gpu_augment(color_image.contiguous(), train=False)
+            true_cam = self.to(true_cam, device)
+            true_val = self.to(true_val, device)
+            rotate = self.to(torch.as_tensor(color_br, dtype=torch.float32), device)
+            with torch.no_grad():
+                if fusion:
+                    cam_feat = self.fusion_infer(color_image, depth_image, i_batch)
+                else:
+                    cam_feat = self.vanilla_infer(depth_image if self.depth_only else color_image, i_batch)
+                heat_cam = utils.to_heatmap(cam_feat, self.depth, self.num_joints, side_out, side_out)
+                relat_cam = utils.decode(heat_cam, self.depth_range)
+                loss, spec_cam = ops.pose_loss(relat_cam, true_cam, true_val, self.data_info.key_index, self.loss_div, self.criterion)
+                ops.pose_eval_stats(spec_cam, true_cam, rotate, true_val, mirror, self.thresh, loss, table, i_batch // world)
+        if world > 1:
+            rows = p3d_dist.gather_eval_rows(table, n_batches)
+        else:
+            rows = table[:n_batches].cpu().numpy()
+        if self.verbose:
+            for i_batch, row in enumerate(rows):
+                print('| test Epoch[%d] [%d/%d]  Cam Loss %1.4f' % (epoch, i_batch, n_batches, row[ops.EVAL_LOSS]))
+        record = utils.record_from_table(rows)
         if self.verbose:
             print('\n=> test Epoch[%d]  Cam Loss: %1.4f\n' % (epoch, record['test_loss']))
             print('=>[SPEC] cam_mean: %1.3f  [pck]: %1.3f  [auc]: %1.3f\n' % (record['cam_mean'], record['score_pck'], record['score_auc']))

@@ -276,3 +276,62 @@ def global_valid_divisor(true_val, group=None):
         world = dist.get_world_size(group)
         dist.all_reduce(count, op=dist.ReduceOp.SUM, group=group)
     return count * (3.0 / world)
+
+
+# ---- sharded evaluation (P3D_DEVICE_EVAL=1, Trainer.test) ---------------------------------------------------------------------------
+
+def shard_batches(n_batches, rank, world):
+    """Global indices of the test batches rank `rank` of `world` evaluates: i = rank (mod world), in increasing order.  The last
+    n_batches % world ranks get one batch fewer; none waits for another before the end-of-epoch exchange (gather_eval_rows)."""
+    return list(range(rank, n_batches, world))
+
+
+class EvalBatchSampler(torch.utils.data.Sampler):
+    """Batch sampler of one rank's test batches: the unshuffled sequence of `count` samples in batches of `batch_size` (what a single
+    process's DataLoader yields), of which this rank loads only shard_batches(...), each with its composition intact."""
+
+    def __init__(self, count, batch_size, rank, world):
+        self.count, self.batch_size, self.rank, self.world = count, batch_size, rank, world
+        self.global_batches = -(-count // batch_size)
+        self.batch_indices = shard_batches(self.global_batches, rank, world)
+
+    def __iter__(self):
+        for i in self.batch_indices:
+            yield list(range(i * self.batch_size, min((i + 1) * self.batch_size, self.count)))
+
+    def __len__(self):
+        return len(self.batch_indices)
+
+
+def eval_batch_sampler(count, batch_size, phase):
+    """The file-backed loaders' hook: for a valid / test phase with P3D_DEVICE_EVAL=1 and W > 1 ranks in torchrun's environment, this
+    rank's EvalBatchSampler; otherwise None (the loader is built exactly as without the switch)."""
+    from .utils import device_eval_enabled
+    rank, world, _ = env_ranks()
+    if phase == 'train' or world < 2 or not device_eval_enabled():
+        return None
+    return EvalBatchSampler(count, batch_size, rank, world)
+
+
+def loader_shard(loader):
+    """The EvalBatchSampler of a loader built on one (directly or under crops.GpuCropLoader), else None."""
+    sampler = getattr(getattr(loader, 'loader', loader), 'batch_sampler', None)
+    return sampler if isinstance(sampler, EvalBatchSampler) else None
+
+
+def gather_eval_rows(table, n_batches, group=None):
+    """End-of-epoch exchange of the sharded evaluation: rank r holds the row of its global batch r + k * world in table[k], every rank's
+    table padded to the same ceil(n_batches / world) rows (padding rows are zeros, i.e. not flagged present).  ONE all-gather -- of the
+    device tables under RCCL, of host copies under gloo -- and an interleave give every rank the full host table in batch order."""
+    world = dist.get_world_size(group)
+    if dist.get_backend(group) == 'nccl':
+        out = torch.empty((world,) + tuple(table.shape), dtype=table.dtype, device=table.device)
+        dist.all_gather_into_tensor(out, table.contiguous(), group=group)
+        gathered = out.cpu()
+    else:
+        host = table.cpu()
+        parts = [torch.empty_like(host) for _ in range(world)]
+        dist.all_gather(parts, host, group=group)
+        gathered = torch.stack(parts)
+    # [world, rows, C] -> [rows, world, C]: flat row k * world + r is global batch r + k * world
+    return gathered.transpose(0, 1).reshape(-1, table.shape[1])[:n_batches].numpy()

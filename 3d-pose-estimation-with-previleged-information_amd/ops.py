@@ -740,6 +740,41 @@ def masked_loss(pred, target, valid, criterion='SmoothL1', count_override=None):
     return MaskedLossFn.apply(pred, target, valid, criterion, count_override)
 
 
+# columns of a row of p3d_pose_eval_stats (include/p3d_hip.h P3D_EVAL_*)
+EVAL_VALID, EVAL_SUM_DIST, EVAL_PCK, EVAL_SUM_AUC, EVAL_SOLID, EVAL_LOSS, EVAL_BATCH, EVAL_PRESENT, EVAL_ROW = 0, 1, 2, 3, 4, 10, 11, 12, 13
+EVAL_CLASSES = ('solid', 'close', 'depth', 'jitter', 'switch', 'fail')           # columns EVAL_SOLID + 0..5
+
+
+def pose_eval_stats(spec_cam, true_cam, rotate, true_val, mirror, thresh, loss, table, row, rotated=False):
+    """Evaluation statistics of one test batch into table[row] (fp64 [rows, EVAL_ROW] device table), one launch, no host sync:
+    spec_cam / true_cam [B,J,3] fp32 are back-rotated by rotate [B,3,3], compared over the valid joints of true_val [B,J] (bool / uint8)
+    as utils.analyze does with thresh (dict solid / close / rough) and mirror (int32 [J] device tensor, entries in [0, J)); loss is the
+    device scalar ops.pose_loss returned.  rotated=True also returns the back-rotated spec_cam [B,J,3]."""
+    _need_gpu(spec_cam, true_cam, rotate, loss)
+    if not (true_val.is_cuda and mirror.is_cuda and table.is_cuda):
+        raise P3DError('pose_eval_stats: true_val, mirror and table must be on the HIP device')
+    spec_cam, true_cam, rotate = spec_cam.contiguous(), true_cam.contiguous(), rotate.contiguous()
+    val = true_val.contiguous().view(torch.uint8) if true_val.dtype == torch.bool else true_val.contiguous()
+    if spec_cam.dim() != 3 or spec_cam.shape[2] != 3 or true_cam.shape != spec_cam.shape:
+        raise P3DError('pose_eval_stats: spec_cam %s / true_cam %s must both be [B,J,3]' % (tuple(spec_cam.shape), tuple(true_cam.shape)))
+    b, j, _ = spec_cam.shape
+    if tuple(rotate.shape) != (b, 3, 3) or tuple(val.shape) != (b, j) or val.dtype != torch.uint8:
+        raise P3DError('pose_eval_stats: rotate %s must be [B,3,3] and true_val %s bool [B,J]' % (tuple(rotate.shape), tuple(true_val.shape)))
+    if loss.numel() != 1:
+        raise P3DError('pose_eval_stats: loss must be the 1-element loss of ops.pose_loss')
+    if mirror.dtype != torch.int32 or mirror.numel() != j or not mirror.is_contiguous():
+        raise P3DError('pose_eval_stats: mirror must be a contiguous int32 [J] tensor')
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != EVAL_ROW or not table.is_contiguous():
+        raise P3DError('pose_eval_stats: table must be a contiguous fp64 [rows, %d] tensor' % EVAL_ROW)
+    if not 0 <= row < table.shape[0]:
+        raise P3DError('pose_eval_stats: row %d outside the table of %d rows' % (row, table.shape[0]))
+    out = torch.empty_like(spec_cam) if rotated else None
+    check(lib().p3d_pose_eval_stats(_p(spec_cam), _p(true_cam), _p(rotate), _p(val), _p(mirror), b, j, float(thresh['solid']), float(thresh['close']),
+                                    float(thresh['rough']), _p(loss), ctypes.c_void_p(table[row].data_ptr()), _p(out), _stream()),
+          'p3d_pose_eval_stats')
+    return out
+
+
 class ReconCamFn(torch.autograd.Function):
     """utils.get_recon_cam (utils.py:335-366) with its analytic backward."""
 

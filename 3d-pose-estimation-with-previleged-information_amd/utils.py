@@ -135,3 +135,61 @@ def parse_epoch(stats):
     keys = ('solid', 'close', 'jitter', 'depth', 'switch', 'fail', 'score_pck', 'score_auc', 'cam_mean')
     weights = np.array([patch['batch_size'] for patch in stats], dtype=np.float64)
     return {key: float(np.sum(weights * np.array([patch[key] for patch in stats])) / np.sum(weights)) for key in keys}
+
+
+# ---- evaluation metrics on the device (P3D_DEVICE_EVAL=1): ops.pose_eval_stats rows -> the record of parse_epoch ---------------------
+
+def device_eval_enabled():
+    """P3D_DEVICE_EVAL=1: Trainer.test computes the metrics on the GPU, reads nothing back inside the batch loop and shards the test batches
+    over the ranks of a process group.  Off by default."""
+    import os
+    return os.environ.get('P3D_DEVICE_EVAL', '0') == '1'
+
+
+def record_from_table(table):
+    """Test record from the per-batch rows of ops.pose_eval_stats (fp64 [n_batches, ops.EVAL_ROW], batch order): test_loss the batch-size
+    weighted mean of the losses summed in batch order in Python floats (as _run_test sums loss.item() * batch), the joint metrics the
+    totals over the valid joints divided by the total valid count (parse_epoch of the per-batch analyze dicts, without its rounding).
+    A batch without a valid joint raises ZeroDivisionError, as utils.statistics does for it."""
+    rows = np.asarray(table, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != ops.EVAL_ROW:
+        raise ValueError('record_from_table: expected [n_batches, %d] rows, got %s' % (ops.EVAL_ROW, rows.shape))
+    if not (rows[:, ops.EVAL_PRESENT] == 1.0).all():
+        raise ValueError('record_from_table: rows %s were never written' % np.flatnonzero(rows[:, ops.EVAL_PRESENT] != 1.0).tolist())
+    empty = np.flatnonzero(rows[:, ops.EVAL_VALID] == 0)
+    if empty.size:
+        raise ZeroDivisionError('test batch %d has no valid joint (utils.statistics divides by the valid count)' % empty[0])
+    loss_avg, total = 0.0, 0
+    for row in rows:
+        loss_avg += float(row[ops.EVAL_LOSS]) * int(row[ops.EVAL_BATCH])
+        total += int(row[ops.EVAL_BATCH])
+    sums = rows.sum(axis=0)
+    count = sums[ops.EVAL_VALID]
+    record = dict(test_loss=loss_avg / max(total, 1))
+    for k, key in enumerate(ops.EVAL_CLASSES):
+        record[key] = float(sums[ops.EVAL_SOLID + k] / count)
+    record.update(score_pck=float(sums[ops.EVAL_PCK] / count), score_auc=float(sums[ops.EVAL_SUM_AUC] / count),
+                  cam_mean=float(sums[ops.EVAL_SUM_DIST] / count))
+    return record
+
+
+def eval_row(spec_cam, true_cam, valid_mask, mirror, thresh, loss, batch):
+    """Host twin of one ops.pose_eval_stats row from already back-rotated float32 coordinates (the tests' and tools' reference)."""
+    valid = np.asarray(valid_mask).reshape(-1).astype(bool)
+    dist = np.linalg.norm(spec_cam - true_cam, axis=-1).reshape(-1)[valid]
+    dist_flip = np.linalg.norm(spec_cam - true_cam[:, mirror], axis=-1).reshape(-1)[valid]
+    dist_tangent = np.linalg.norm(spec_cam[:, :, :2] - true_cam[:, :, :2], axis=-1).reshape(-1)[valid]
+    row = np.zeros(ops.EVAL_ROW, np.float64)
+    row[ops.EVAL_VALID] = dist.size
+    row[ops.EVAL_SUM_DIST] = np.sum(dist.astype(np.float64))
+    row[ops.EVAL_PCK] = np.count_nonzero(dist / thresh['rough'] <= 1.0)
+    row[ops.EVAL_SUM_AUC] = np.sum(np.maximum(0, 1 - dist / thresh['rough']).astype(np.float64))
+    alive = np.ones(dist.shape, dtype=bool)
+    for k, (values, limit) in enumerate(((dist, thresh['solid']), (dist, thresh['close']), (dist_tangent, thresh['close']),
+                                         (dist, thresh['rough']), (dist_flip, thresh['rough']))):
+        hit = alive & (values <= limit)
+        row[ops.EVAL_SOLID + k] = np.count_nonzero(hit)
+        alive &= ~hit
+    row[ops.EVAL_SOLID + 5] = np.count_nonzero(alive)
+    row[ops.EVAL_LOSS], row[ops.EVAL_BATCH], row[ops.EVAL_PRESENT] = loss, batch, 1.0
+    return row

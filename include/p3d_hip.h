@@ -410,6 +410,27 @@ int32_t p3d_pose_loss_fwd_bwd(const float* relat, const float* true_cam, const u
 int32_t p3d_masked_loss_fwd_bwd(const float* pred, const float* target, const uint8_t* valid, float* loss, float* dpred, int32_t rows, int32_t C,
                                 int32_t criterion, const float* count_override, void* stream);
 
+/* Evaluation statistics of one test batch (Trainer.test with P3D_DEVICE_EVAL=1: the back-rotation + utils.analyze), one launch:
+ *   spec = rotate[b] @ spec_cam[b,j], truth = rotate[b] @ true_cam[b,j]            rotate [B,3,3] (np.einsum('Bij,BCj->BCi'))
+ *   dist = |spec - truth|, flip = |spec - truth[b,mirror[j]]|, tangent = |(spec - truth).xy|      mirror int32 [J]
+ * in numpy's float32 operations and order (no FMA contraction), then over the valid joints (true_val uint8 [B,J]) one fp64 row of
+ * P3D_EVAL_ROW values at `row`: the columns below.  PCK counts dist / rough <= 1, AUC sums max(0, 1 - dist / rough) (float32 division);
+ * the six classes are utils.statistics' cascade solid -> close -> depth (tangent <= close) -> jitter (<= rough) -> switch (flip <= rough)
+ * -> fail.  `loss` is the device scalar p3d_pose_loss_fwd_bwd wrote.  spec_rot_out [B,J,3] (may be NULL) receives the rotated spec.
+ * One block, fixed-order reduction, no atomics: the same inputs give the same row bits. */
+#define P3D_EVAL_VALID 0
+#define P3D_EVAL_SUM_DIST 1
+#define P3D_EVAL_PCK 2
+#define P3D_EVAL_SUM_AUC 3
+#define P3D_EVAL_SOLID 4                 /* 4..9: solid, close, depth, jitter, switch, fail counts */
+#define P3D_EVAL_LOSS 10
+#define P3D_EVAL_BATCH 11
+#define P3D_EVAL_PRESENT 12              /* 1.0 in every written row (0 in the padding of a sharded table) */
+#define P3D_EVAL_ROW 13
+int32_t p3d_pose_eval_stats(const float* spec_cam, const float* true_cam, const float* rotate, const uint8_t* true_val, const int32_t* mirror,
+                            int32_t B, int32_t J, float solid, float close, float rough, const float* loss, double* row, float* spec_rot_out,
+                            void* stream);
+
 /* utils.get_recon_cam (utils.py:335-366): differentiable least-squares placement of the root-relative pose relat_cam [B,J,3] such that it projects
  * onto spec_mat [B,J,2] under intrinsics [B,3,3]: recon = relat_cam + (A^T A)^-1 A^T b.  bwd: gradients w.r.t. spec_mat and relat_cam. */
 int32_t p3d_recon_cam_fwd(const float* spec_mat, const float* relat_cam, const float* intrinsics, float* recon, int32_t B, int32_t J, void* stream);

@@ -10,6 +10,11 @@ Legs, timed in the same process, alternating (device-synchronised, 10 warm-up + 
   half_folded   infer.fold_half(model): BatchNorm folded into the fp16 convolutions (p3d_hconv2d_fwd_infer)
 --separate adds the round-1 leg with stand-alone BatchNorm passes; --distill also times one distill_step with and without the folded teacher
 (with --half: a -half_acc student and teacher, P3D_FOLDED_EVAL_HALF; with --family partial_fusionnet: a partial_fusionnet teacher).
+--test-loop times Trainer.test instead (depthnet; --test-batches batches of --batch, inputs in pinned host memory as a loader delivers them),
+for the folded fp32 net (P3D_FOLDED_EVAL=1) and the folded fp16 net (-half_acc, P3D_FOLDED_EVAL_HALF=1), each with its bare forward:
+  forward_<p>   the folded net alone on a device batch
+  host_<p>      Trainer.test with the per-batch host metrics (P3D_DEVICE_EVAL=0)
+  device_<p>    Trainer.test with the metrics on the GPU and one read-back per epoch (P3D_DEVICE_EVAL=1)
 Prints one line per leg and round, then a JSON summary line."""
 import argparse
 import importlib
@@ -35,10 +40,80 @@ ap.add_argument('--separate', action='store_true')
 ap.add_argument('--distill', action='store_true')
 ap.add_argument('--half', action='store_true', help='-half_acc legs: half / half_folded')
 ap.add_argument('--only', default=None, help='time one leg only (profiling runs)')
+ap.add_argument('--test-loop', action='store_true', help='time Trainer.test: host metrics against P3D_DEVICE_EVAL=1, fp32 and fp16 folded')
+ap.add_argument('--test-batches', type=int, default=50)
 ap.add_argument('--family', default='depthnet', choices=['depthnet', 'partial_depthnet', 'partial_fusionnet'])
 opt = ap.parse_args()
 if opt.distill and opt.family == 'partial_depthnet':
     ap.error('--distill times a depthnet student with a fusionnet (--family depthnet) or partial_fusionnet (--family partial_fusionnet) teacher')
+
+
+
+def test_loop():
+    """--test-loop: Trainer.test per batch, host metrics vs P3D_DEVICE_EVAL=1, next to the bare folded forward; legs alternate per round."""
+    import tempfile
+    import numpy as np
+    meta = os.path.join(tempfile.mkdtemp(), 'metadata.json')
+    with open(meta, 'w') as f:
+        json.dump(dict(loader=dict(h36m='depth_datasets'), no_depth=dict(h36m=False), thresholds=dict(h36m=dict(solid=40.0, close=80.0, rough=150.0))), f)
+    distinct = min(opt.test_batches, 10)                 # distinct pinned batches, cycled: 10 x 64 x 3 x 256^2 fp32 = 0.5 GB of pinned memory
+    pinned = []
+    for k in range(distinct):
+        c, d, tc, tv = pkg.synth.make_batch(opt.batch, side=opt.side, rank=0, step=k, invalid_frac=0.2)
+        rot = np.linalg.qr(np.random.Generator(np.random.PCG64(k)).standard_normal((opt.batch, 3, 3)))[0].astype(np.float32)
+        pinned.append(tuple(torch.from_numpy(a).pin_memory() for a in (c, d, tc, tv, rot)))
+    batches = [pinned[i % distinct] for i in range(opt.test_batches)]
+    x = pinned[0][0].cuda()
+    os.environ.update(P3D_FOLDED_EVAL='1', P3D_FOLDED_EVAL_HALF='1')
+    legs = {}
+    for prec, extra in (('fp32', []), ('fp16', ['-half_acc'])):
+        targs = pkg.opts.parse(['-model', opt.model, '-suffix', 'b', '-data_name', 'h36m', '-save_path', '/tmp/p3d', '-criterion', 'SmoothL1',
+                                '-num_joints', '17', '-side_in', str(opt.side), '-metadata', meta] + extra)
+        trainer = pkg.depth_train.Trainer(targs, pkg.depth_main.create_model(targs)[0].cuda(), pkg.utils.get_info())
+        trainer.verbose = False
+        trainer.test(1, batches[:2])                     # folds the net, plans and workspaces
+        net = trainer.__dict__['_folded_half_model' if trainer.half_acc else '_folded_model']     # the folded net Trainer.test runs
+
+        def forward(net=net):
+            with torch.no_grad():
+                for _ in batches:
+                    net(x)
+
+        def loop(trainer=trainer, switch='0'):
+            os.environ['P3D_DEVICE_EVAL'] = switch
+            try:
+                return trainer.test(1, batches)
+            finally:
+                os.environ.pop('P3D_DEVICE_EVAL')
+        legs['forward_' + prec] = forward
+        legs['host_' + prec] = loop
+        legs['device_' + prec] = lambda loop=loop: loop(switch='1')
+    if opt.only:
+        legs = {opt.only: legs[opt.only]}
+    times, records = {k: [] for k in legs}, {}
+    for r in range(opt.rounds):
+        for name, fn in legs.items():
+            fn()                                          # one warm pass per leg and round
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / len(batches)
+            times[name].append(dt)
+            if out is not None:
+                records[name] = out
+            print('round %d  %-16s %.3f ms / batch of %d' % (r, name, dt * 1e3, opt.batch), flush=True)
+    for prec in ('fp32', 'fp16'):
+        host, dev = records.get('host_' + prec), records.get('device_' + prec)
+        if host and dev:
+            assert host['test_loss'] == dev['test_loss'], (prec, host, dev)
+    summary = {k: dict(ms_median=sorted(v)[len(v) // 2] * 1e3, ms_min=min(v) * 1e3, ms_max=max(v) * 1e3) for k, v in times.items()}
+    print(json.dumps(dict(mode='test_loop', model=opt.model, batch=opt.batch, side=opt.side, batches=opt.test_batches, rounds=opt.rounds, legs=summary)))
+
+
+if opt.test_loop:
+    test_loop()
+    sys.exit(0)
 
 flags = {'depthnet': [], 'partial_depthnet': ['-depth_only', '-partial_conv'], 'partial_fusionnet': ['-do_fusion', '-partial_conv']}[opt.family]
 args = pkg.opts.parse(['-model', opt.model, '-suffix', 'b', '-data_name', 'h36m', '-save_path', '/tmp/p3d', '-criterion', 'SmoothL1', '-num_joints', '17',
