@@ -47,4 +47,25 @@ __device__ __forceinline__ float wave_max(float v) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// MXFP8 (OCP MX v1.0, e4m3fn elements, 32-element blocks) -- the one rule of the fold (p3d_fx.hip kind 3) and the fp8 convolution (p3d_f8conv.hip):
+// e = floor(log2(amax)) from the exponent bits, scale byte E8M0 = clamp(e - 8 + 127, 0, 254) (8: the exponent of 448), X = 2^(byte - 127),
+// q = e4m3fn(RNE(clamp(v / X, -448, 448))), subnormals kept; amax == 0: byte 0 and every element 0.
+__device__ __forceinline__ int mx_scale_byte_f32(float amax) {
+    const unsigned u = __builtin_bit_cast(unsigned, amax) & 0x7fffffffu;
+    if (u == 0) return 0;
+    const int ex = (int)(u >> 23);
+    const int e = ex ? ex - 127 : (31 - __builtin_clz(u)) - 149;
+    const int b = e + 119;
+    return b < 0 ? 0 : (b > 254 ? 254 : b);
+}
+// fp32 -> e4m3fn, round to nearest even, |x| clamped to 448 first (x finite; a NaN gives +-448)
+__device__ __forceinline__ unsigned f32_to_e4m3(float x) {
+    const unsigned sign = (__builtin_bit_cast(unsigned, x) >> 24) & 0x80u;
+    const float a = fabsf(x);
+    if (!(a < 448.f)) return sign | 0x7eu;
+    if (a < 0.015625f) return sign | (unsigned)(int)rintf(a * 512.f);          // subnormal range: multiples of 2^-9 (8 * 2^-9 is the encoding of 2^-6)
+    const unsigned ua = __builtin_bit_cast(unsigned, a);
+    return sign | ((((ua + 0x7ffffu + ((ua >> 20) & 1u)) >> 20) - (120u << 3)) & 0x7fu);      // 3 mantissa bits, RNE; exponent bias 127 -> 7
+}
+
 }  // namespace p3d

@@ -1802,14 +1802,16 @@ int32_t fx_build_weight_images_batched(const void* jobs, int njobs, int blocks, 
 // per-channel scale s = gamma / sqrtf(var + eps) into LDS (no BatchNorm: s = 1), then strides over the job's output: kind 0 the forward weight image of
 // w * s over input channels [c_offset, c_offset + C) (fx_weight_image_chunks, the layout p3d_fx_weight_images produces), kind 1 the folded fp32 weights
 // [K][C][RS] (the stem, whose image p3d_stem_weight_image restates), kind 2 the fp16 forward image [K][RS][Cpad] of the fp16 path (the layout of
-// p3d_weight_images_f16; Cpad in `reserved`, channels C .. Cpad - 1 written as 0).  Block 0 also writes b' = beta - mean * s (+ s * conv bias) when bias_out is given.
+// p3d_weight_images_f16; Cpad in `reserved`, channels C .. Cpad - 1 written as 0), kind 3 the MXFP8 image of the fp8 path (elements [K][RS][Cpad], then the
+// scale bytes [K][RS][Cpad / 32], by the MX rule of p3d_common.h from the same products as kind 2; Cpad in `reserved`, a multiple of 32).  Block 0 also writes
+// b' = beta - mean * s (+ s * conv bias) when bias_out is given.
 // The operation order is fixed (a division, a correctly rounded sqrtf, one product per weight), so the image equals the one built from the fold done in torch.
 constexpr int FX_FOLD_MAX_K = 2048;
 __global__ __launch_bounds__(256) void fx_fold_bn_kernel(const p3d_fold_job* __restrict__ jobs) {
     const p3d_fold_job j = jobs[blockIdx.y];
     __shared__ float sc[FX_FOLD_MAX_K];
     if (j.K <= 0 || j.K > FX_FOLD_MAX_K || j.C <= 0 || j.RS <= 0 || j.c_offset < 0 || j.c_offset + j.C > j.c_total || (j.kind == 0 && j.C % FX_BK != 0) ||
-        (j.kind == 2 && (j.reserved < j.C || j.reserved % 8 != 0))) return;      // (checked by the caller)
+        (j.kind == 2 && (j.reserved < j.C || j.reserved % 8 != 0)) || (j.kind == 3 && (j.reserved < j.C || j.reserved % 32 != 0))) return;      // (checked by the caller)
     const bool bn = j.gamma != nullptr;
     for (int m = threadIdx.x; m < j.K; m += 256) {
         const float s = bn ? j.gamma[m] / sqrtf(j.var[m] + j.eps) : 1.f;
@@ -1838,6 +1840,41 @@ __global__ __launch_bounds__(256) void fx_fold_bn_kernel(const p3d_fold_job* __r
                 if (bn) x = x * sc[m];
             }
             out[i] = (_Float16)x;
+        }
+    } else if (j.kind == 3) {
+        // one thread per 32-channel block of one (row, tap): the same w * s as kind 2, then the MX rule (p3d_common.h); elements [K][RS][Cpad], scales [K][RS][Cpad / 32]
+        unsigned char* out = (unsigned char*)j.out;
+        const int Cpad = j.reserved, CB = Cpad >> 5;
+        const size_t nblk = (size_t)j.K * j.RS * CB;
+        unsigned char* scales = out + nblk * 32;
+        for (size_t i = first; i < nblk; i += step) {
+            const int cb = (int)(i % CB);
+            const int tap = (int)((i / CB) % j.RS);
+            const int m = (int)(i / ((size_t)CB * j.RS));
+            float x[32];
+            float amax = 0.f;
+#pragma unroll
+            for (int e = 0; e < 32; ++e) {
+                const int c = cb * 32 + e;
+                float v = 0.f;
+                if (c < j.C) {
+                    v = j.w[((size_t)m * j.c_total + j.c_offset + c) * j.RS + tap];
+                    if (bn) v = v * sc[m];
+                }
+                x[e] = v;
+                amax = fmaxf(amax, fabsf(v));
+            }
+            const int sb = mx_scale_byte_f32(amax);
+            unsigned q[8];
+#pragma unroll
+            for (int d = 0; d < 8; ++d) {
+                q[d] = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) q[d] |= f32_to_e4m3(ldexpf(x[4 * d + e], 127 - sb)) << (8 * e);      // v / X, exact (X a power of two)
+            }
+            *reinterpret_cast<i32x4*>(out + i * 32) = i32x4{(int)q[0], (int)q[1], (int)q[2], (int)q[3]};
+            *reinterpret_cast<i32x4*>(out + i * 32 + 16) = i32x4{(int)q[4], (int)q[5], (int)q[6], (int)q[7]};
+            scales[i] = (unsigned char)sb;
         }
     } else {
         float* out = (float*)j.out;

@@ -14,7 +14,7 @@
 //                     transposed w.r.t. what the MFMA wants; they are stored as they come ([pixel][channel], 256-B rows, XOR
 //                     swizzle) and read back with ds_read_b64_tr_b16, the CDNA4 transposing LDS read.  Split over pixels,
 //                     fp32 slabs, one reduce kernel that also converts (tap, c) -> the master [K][C][R][S] layout.
-#include "p3d_common.h"
+#include "p3d_gather.h"
 
 namespace p3d {
 
@@ -26,18 +26,6 @@ using f32x16 = float __attribute__((ext_vector_type(16)));
 using f32x4 = float __attribute__((ext_vector_type(4)));
 using i32x4 = int __attribute__((ext_vector_type(4)));
 
-// 16-B buffer load, bound by intrinsic name (see p3d_conv.hip: the b128 builtin of this compiler lowers to a dword load)
-__device__ f32x4 hbuf_load16(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-
-__device__ __forceinline__ i32x4 hmake_rsrc(const void* base, size_t bytes) {
-    const unsigned n = bytes < 0x7ffffff0ull ? (unsigned)bytes : 0x7ffffff0u;
-    const uint64_t a = reinterpret_cast<uint64_t>(base);
-    i32x4 r;
-    r[0] = (int)(unsigned)a; r[1] = (int)((a >> 32) & 0xffff); r[2] = (int)n; r[3] = 0x00020000;
-    return r;
-}
-
-constexpr int HOOB = (int)0x80000000;      // a voffset with this bit set is past any buffer: the load returns 0
 constexpr int HMS = 4;                     // largest stride of the class tables
 
 struct HGatherParams {
@@ -63,11 +51,6 @@ struct HGatherParams {
     int r0[HMS], rstep[HMS], nr[HMS], hadd[HMS], hstep[HMS];
     int s0[HMS], sstep[HMS], ns[HMS], wadd[HMS], wstep[HMS];
 };
-
-__device__ __forceinline__ int xcd_remap(int b, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7, idx = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 // EPI 0: the accumulator goes to NHWC as it lies (8-B stores; bias, per-pixel factor, accumulate).  EPI 1: through LDS, so that a pixel's 128 channels leave as 16-B
 // stores of one 256-B run.  EPI 2: + the statistics of the BatchNorm behind this convolution (sum y, sum y^2 of the ROUNDED fp16 values, i.e. what a pass over y would

@@ -407,7 +407,7 @@ class Trainer:
             ops_block.release_buffers(self.model)
         if self._folding():                                  # P3D_FOLDED_EVAL=1 / -half_acc with P3D_FOLDED_EVAL_HALF=1: BatchNorm folded into the convolutions
             net = getattr(self.model, 'module', self.model)
-            key = '_folded_half_model' if self.half_acc else '_folded_model'
+            key = '_folded_fp8_model' if infer.fp8_enabled() else ('_folded_half_model' if self.half_acc else '_folded_model')
             folded = self.__dict__.get(key)
             if folded is None or folded.model is not net:
                 folded = self.__dict__[key] = self._fold(net)
@@ -421,10 +421,13 @@ class Trainer:
         return self._run_test(epoch, test_loader, self.list_params[0].device)      # -do_teach evaluates the student (depth_train.py:613-614)
 
     def _folding(self):
-        """Whether evaluation and the eval-mode teacher run folded: P3D_FOLDED_EVAL=1 in fp32, P3D_FOLDED_EVAL_HALF=1 under -half_acc."""
-        return infer.half_enabled() if self.half_acc else infer.enabled()
+        """Whether evaluation and the eval-mode teacher run folded: P3D_FOLDED_EVAL=1 in fp32, P3D_FOLDED_EVAL_HALF=1 under -half_acc,
+        P3D_FOLDED_EVAL_FP8=1 in both."""
+        return infer.fp8_enabled() or (infer.half_enabled() if self.half_acc else infer.enabled())
 
     def _fold(self, net):
+        if infer.fp8_enabled():                              # (takes precedence over the other two switches)
+            return infer.fold_fp8(net)
         return infer.fold_half(net) if self.half_acc else infer.fold(net)
 
     # ---- distillation: the "privileged information" training (depth_train.py:107-129,161-283,641-647,682-691) --------

@@ -22,8 +22,13 @@ p3d_weight_images_f16 produces) and `HalfFoldedNet(x[, y])` runs every conv on p
 ReLU before the one rounding to fp16.  The partial-convolution layers fold too (mask_in in the operand fetch, mult in the epilogue), so an fp16 folded
 forward has no BatchNorm pass at all.
 
-Both precisions share the plan (stems, blocks, fusion, heads), the fold launch and the walk over the network (_Folded); FoldedNet and HalfFoldedNet
-supply the per-layer primitives.  Two A/B switches were measured and removed, because each only selected a slower path: leaving the partial stem
+`fold_fp8(model)` is the fp16 folded network with block-scaled FP8 (MXFP8) convolutions in between: every conv of the residual blocks, the partial
+layers and the Fusion 1x1 that p3d_f8conv2d_fwd_infer accepts folds to a kind-3 MXFP8 image (e4m3 elements, one E8M0 scale per 32 input channels of a
+tap) and runs on that entry point, which quantizes its fp16 input by the same rule while staging it; the stems and the heads stay on the fp16 folded conv
+(the usual first / last layer rule), and so does a conv the entry point refuses.  One fold launch writes the kind-3 and the kind-2 images together.
+
+All three share the plan (stems, blocks, fusion, heads), the fold launch and the walk over the network (_Folded); FoldedNet, HalfFoldedNet and
+Fp8FoldedNet supply the per-layer primitives.  Two A/B switches were measured and removed, because each only selected a slower path: leaving the partial stem
 and layers on the model's own modules (9.80 against 8.90 ms for R50 partial_depthnet, 13.10 against 12.22 ms for partial_fusionnet,
 profiles/eval_folded_partial.md), and feeding the 64-channel layers as an activation image (2.7 % slower, profiles/eval_folded.md).
 """
@@ -48,6 +53,12 @@ def enabled():
 def half_enabled():
     """P3D_FOLDED_EVAL_HALF=1: under -half_acc, Trainer.test and the distillation teacher evaluate through a HalfFoldedNet."""
     return os.environ.get('P3D_FOLDED_EVAL_HALF', '0') == '1'
+
+
+def fp8_enabled():
+    """P3D_FOLDED_EVAL_FP8=1: Trainer.test and the distillation teacher evaluate through an Fp8FoldedNet, in fp32 and under -half_acc; it takes
+    precedence over P3D_FOLDED_EVAL and P3D_FOLDED_EVAL_HALF."""
+    return os.environ.get('P3D_FOLDED_EVAL_FP8', '0') == '1'
 
 
 def _family(model):
@@ -206,12 +217,15 @@ class _Folded:
         if fusion:
             self.fusion = self._plan_fusion(model.fusion)
         heads = ('cam_regressor', 'mat_regressor') if self.family == 'resnet' else ('regressor',)
-        self.heads = [self._add(self.Conv(getattr(model, h), None)) if getattr(model, h, None) is not None else None for h in heads]
+        self.heads = [self._add(self._plan_head(getattr(model, h))) if getattr(model, h, None) is not None else None for h in heads]
         self._allocate(next(model.parameters()).device)
 
     def _add(self, c):
         self.convs.append(c)
         return c
+
+    def _plan_head(self, conv):
+        return self.Conv(conv, None)
 
     def _units(self):
         """Everything the fold launch writes, in buffer order."""
@@ -486,6 +500,9 @@ class HalfFoldedNet(_Folded):
             check(L.p3d_hconv2d_fwd_infer(ctypes.byref(d), ops._p(x), self._at(c.img_off), self._at(c.bias_off), ops._p(mask_in), ops._p(mult),
                                           ops._p(res), int(bool(relu)), ops._p(y), ops._stream()), 'p3d_hconv2d_fwd_infer')
             return y if c.kpad == c.k else y[:, :c.k]
+        return self._unfolded(c, x, res, relu, mask_in, mult)
+
+    def _unfolded(self, c, x, res, relu, mask_in, mult):
         if c.images is None:                                # per-layer fallback: the unfolded conv, then the eval-mode BatchNorm pass
             c.images = ops_half.WeightImages(c.conv.weight, need_dgrad=False)
             c.images.refresh(c.conv.weight)
@@ -525,3 +542,69 @@ def fold_half(model):
     """HalfFoldedNet of a -half_acc network in eval mode: fp32 (or fp16) NCHW input, fp32 NCHW outputs, as model.eval()(x) returns them under
     -half_acc.  Raises P3DError for a BatchNorm in training mode or parameters that are not fp32 on the HIP device."""
     return HalfFoldedNet(getattr(model, 'module', model))
+
+
+# ---- block-scaled FP8 (MXFP8) between fp16 stems and heads ---------------------------------------------------------------------------------
+class _F8Conv(_HConv):
+    """A conv (+ BatchNorm) of the fp8 folded network: its kind-3 MXFP8 image (e4m3 elements [K][R][S][C], then the E8M0 scales [K][R][S][C / 32]) and
+    b' in the buffer.  Made only for convs whose C is a multiple of 32 (so Cpad = C) and whose K a multiple of 8."""
+
+    def layout(self, at):
+        self.img_off = at
+        self.img_bytes = lib().p3d_f8conv2d_weight_bytes(self.k, self.cpad, self.r * self.s)
+        at = _up(at + self.img_bytes)
+        self.bias_off = at
+        return _up(at + 4 * self.kpad)
+
+    def job(self, buf):
+        j = super().job(buf)
+        j.kind = 3
+        return j
+
+
+class Fp8FoldedNet(HalfFoldedNet):
+    """The -half_acc folded network with the convs between the stems and the heads on p3d_f8conv2d_fwd_infer (MXFP8 weights and activations, fp32
+    accumulation, fp16 NHWC in and out).  Takes the same inputs and gives the same outputs as HalfFoldedNet, from fp32 master parameters."""
+    WHO = 'infer.fold_fp8'
+
+    def Conv(self, conv, bn):
+        """_F8Conv when the fp8 entry point takes the conv's shape (queried on a nominal 1 x C x 64 x 64 input), else the fp16 folded _HConv."""
+        k, c, r, s = conv.weight.shape
+        d = ops._desc((1, c, 64, 64), (k, c, r, s), _one(conv.stride), _one(conv.padding), _one(conv.dilation))
+        fp8 = k <= 2048 and bool(lib().p3d_f8conv2d_fwd_infer_supported(ctypes.byref(d)))
+        return (_F8Conv if fp8 else _HConv)(conv, bn)
+
+    def _plan_head(self, conv):
+        return _HConv(conv, None)
+
+    def _plan_fusion(self, f):
+        return self._add(self.Conv(f.conv, f.bn))
+
+    def image(self, c):
+        """The fp16 image of an fp16 conv, as HalfFoldedNet.image; for an fp8 conv the pair (e4m3 elements [K][R][S][C] as uint8, E8M0 scale bytes
+        [K][R][S][C / 32]) (tests)."""
+        if not isinstance(c, _F8Conv):
+            return super().image(c)
+        n = c.k * c.r * c.s * c.cpad
+        img = self.buffer[c.img_off:c.img_off + n + n // 32]
+        return img[:n].view(c.k, c.r, c.s, c.cpad), img[n:].view(c.k, c.r, c.s, c.cpad // 32)
+
+    def _conv_bn(self, c, x, res=None, relu=False, mask_in=None, mult=None):
+        """y = fp16(relu?(conv(q(x * mask_in), w') * mult + b' + res)) on the MXFP8 image; an fp16 conv, as HalfFoldedNet; an fp8 conv the entry point
+        refuses at this input runs as HalfFoldedNet's per-layer fallback (the unfolded fp16 conv, then the eval-mode BatchNorm pass)."""
+        if not isinstance(c, _F8Conv):
+            return super()._conv_bn(c, x, res, relu, mask_in, mult)
+        L = lib()
+        d = c.desc(x)
+        if not L.p3d_f8conv2d_fwd_infer_supported(ctypes.byref(d)):
+            return self._unfolded(c, x, res, relu, mask_in, mult)
+        y = ops_half._empty(d.N, d.K, d.Ho, d.Wo, x.device)
+        check(L.p3d_f8conv2d_fwd_infer(ctypes.byref(d), ops._p(x), self._at(c.img_off), self._at(c.bias_off), ops._p(mask_in), ops._p(mult),
+                                       ops._p(res), int(bool(relu)), ops._p(y), ops._stream()), 'p3d_f8conv2d_fwd_infer')
+        return y
+
+
+def fold_fp8(model):
+    """Fp8FoldedNet of a network in eval mode (fp32 or -half_acc): fp32 (or fp16) NCHW input, fp32 NCHW outputs.  Raises P3DError for a BatchNorm in
+    training mode or parameters that are not fp32 on the HIP device."""
+    return Fp8FoldedNet(getattr(model, 'module', model))

@@ -267,7 +267,10 @@ int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const 
  * channels [c_offset, c_offset + C) of a weight with c_total of them -- the image p3d_fx_weight_images builds from the folded fp32 weight, bit for bit --, kind 1 the
  * folded fp32 weight [K][C][RS] itself (the 7x7 stem: input of p3d_stem_weight_image), kind 2 the fp16 forward image [K][RS][Cpad] of w' (-half_acc: the image
  * p3d_weight_images_f16 builds from the folded fp32 weight, bit for bit; channels C .. Cpad - 1 are 0); bias_out (or NULL) receives b'.  gamma == NULL: no BatchNorm
- * (s = 1, b' = the conv bias or 0).  Kinds may be mixed in one table.  blocks: grid width per job.  K <= 2048. */
+ * (s = 1, b' = the conv bias or 0).  Kind 3 writes the MXFP8 image of w' (infer.fold_fp8, p3d_f8conv2d_fwd_infer): per (row k, tap, 32 input channels) one block
+ * by OCP MX v1.0 with e4m3fn elements -- e = floor(log2(amax)) from the exponent bits, scale byte E8M0 = clamp(e - 8 + 127, 0, 254), X = 2^(byte - 127),
+ * q = e4m3fn(RNE(clamp(w' / X, -448, 448))) (amax 0: byte 0, elements 0) -- out holds the elements [K][RS][Cpad] (bytes), then the scale bytes [K][RS][Cpad / 32]
+ * (p3d_f8conv2d_weight_bytes in all); channels C .. Cpad - 1 are 0.  Kinds may be mixed in one table.  blocks: grid width per job.  K <= 2048. */
 typedef struct p3d_fold_job {
     const float* w;             /* conv weight [K][c_total][RS] */
     const float* conv_bias;     /* [K] or NULL */
@@ -279,7 +282,7 @@ typedef struct p3d_fold_job {
     float* bias_out;            /* [K] or NULL */
     int32_t K, C, RS, c_offset, c_total, kind;
     float eps;
-    int32_t reserved;           /* kind 2: Cpad, the padded channel count of the fp16 image (>= C, multiple of 8); kinds 0 / 1: unused */
+    int32_t reserved;           /* kind 2: Cpad, the padded channel count of the fp16 image (>= C, multiple of 8); kind 3: Cpad (>= C, multiple of 32); kinds 0 / 1: unused */
 } p3d_fold_job;
 int32_t p3d_fx_fold_bn_images(const void* jobs, int32_t njobs, int32_t blocks, void* stream);
 /* y = conv(x, w') + b' (+ y when d->accumulate) (+ res) (then ReLU when relu != 0) from a folded forward weight image of exactly this descriptor's C input channels
@@ -521,6 +524,16 @@ int32_t p3d_hscale_pixels(const void* src_nhwc, const float* scale, void* dst_nh
 int32_t p3d_hconv2d_fwd_infer_supported(const p3d_conv_desc* d);
 int32_t p3d_hconv2d_fwd_infer(const p3d_conv_desc* d, const void* x_nhwc, const void* w_krsc, const float* bias, const float* mask_in, const float* mult,
                               const void* res_nhwc, int32_t relu, void* y_nhwc, void* stream);
+/* Block-scaled FP8 (MXFP8) inference convolution (infer.fold_fp8): y = fp16(relu?(conv(q(x * mask_in), w_mx) * mult + bias + res)), rounded once, on
+ * v_mfma_scale_f32_32x32x64_f8f6f4.  w_mx is a kind-3 fold image (p3d_fx_fold_bn_images) of d->C input channels; x is NHWC fp16 with d->C channels, quantized
+ * on the fly by the same MX rule per (pixel, tap, 32 channels), so the result equals quantizing x once and convolving the dequantized operands with fp32
+ * accumulation.  res, bias, mask_in, mult as for p3d_hconv2d_fwd_infer.
+ * supported: 1 when the descriptor runs on this entry point, else 0 and the reason in p3d_last_error() (C not a multiple of 32, K not a multiple of 8,
+ * accumulate, a channel window, a tensor beyond the 2 GiB buffer window).  weight_bytes: the size of a kind-3 image (0 when C % 32 != 0). */
+int32_t p3d_f8conv2d_fwd_infer_supported(const p3d_conv_desc* d);
+size_t p3d_f8conv2d_weight_bytes(int32_t K, int32_t C, int32_t RS);
+int32_t p3d_f8conv2d_fwd_infer(const p3d_conv_desc* d, const void* x_nhwc, const void* w_mx, const float* bias, const float* mask_in, const float* mult,
+                               const void* res_nhwc, int32_t relu, void* y_nhwc, void* stream);
 /* d->accumulate != 0: dx += result (joins the gradient another consumer of the same input already wrote) */
 int32_t p3d_hconv2d_dgrad(const p3d_conv_desc* d, const void* dy_nhwc, const void* w_crsk, const float* mask_in, void* dx_nhwc, void* stream);
 /* A convolution whose epilogue also leaves the channel sums of the BatchNorm next to it (round 4; what the fp32 path's EPI 1 / 2 do), so that the BatchNorm costs no

@@ -8,6 +8,10 @@ Legs, timed in the same process, alternating (device-synchronised, 10 warm-up + 
 --half replaces them with the -half_acc legs:
   half          today's fp16 eval forward: fp16 conv, then a stand-alone eval-mode BatchNorm (+ res + ReLU) pass per layer
   half_folded   infer.fold_half(model): BatchNorm folded into the fp16 convolutions (p3d_hconv2d_fwd_infer)
+--fp8 (with --half) adds the block-scaled FP8 leg:
+  fp8_folded    infer.fold_fp8(model): MXFP8 convolutions between fp16 folded stems and heads (p3d_f8conv2d_fwd_infer)
+  and --distill then times the fp8 teacher (P3D_FOLDED_EVAL_FP8=1) beside the fp16 folded one; --deviation prints the relative L2 deviation of z and the
+  feature map of the fp8 net against the fp32 eval forward and fold_half (depthnet and fusionnet, seeded synthetic weights and inputs).
 --separate adds the round-1 leg with stand-alone BatchNorm passes; --distill also times one distill_step with and without the folded teacher
 (with --half: a -half_acc student and teacher, P3D_FOLDED_EVAL_HALF; with --family partial_fusionnet: a partial_fusionnet teacher).
 --test-loop times Trainer.test instead (depthnet; --test-batches batches of --batch, inputs in pinned host memory as a loader delivers them),
@@ -39,11 +43,17 @@ ap.add_argument('--rounds', type=int, default=3)
 ap.add_argument('--separate', action='store_true')
 ap.add_argument('--distill', action='store_true')
 ap.add_argument('--half', action='store_true', help='-half_acc legs: half / half_folded')
+ap.add_argument('--fp8', action='store_true', help='with --half (required): the fp8_folded leg (infer.fold_fp8), and an fp8 teacher under --distill')
+ap.add_argument('--deviation', action='store_true', help='with --fp8: relative L2 deviation of the fp8 net (not timed)')
 ap.add_argument('--only', default=None, help='time one leg only (profiling runs)')
 ap.add_argument('--test-loop', action='store_true', help='time Trainer.test: host metrics against P3D_DEVICE_EVAL=1, fp32 and fp16 folded')
 ap.add_argument('--test-batches', type=int, default=50)
 ap.add_argument('--family', default='depthnet', choices=['depthnet', 'partial_depthnet', 'partial_fusionnet'])
 opt = ap.parse_args()
+if opt.fp8 and not opt.half:
+    ap.error('--fp8 adds the fp8_folded leg beside the -half_acc legs: give it with --half')
+if opt.deviation and not opt.fp8:
+    ap.error('--deviation reports the fp8 net: give it with --half --fp8')
 if opt.distill and opt.family == 'partial_depthnet':
     ap.error('--distill times a depthnet student with a fusionnet (--family depthnet) or partial_fusionnet (--family partial_fusionnet) teacher')
 
@@ -133,6 +143,9 @@ if opt.half:
     pkg.ops_half.refresh_weights(model)
     hfolded = pkg.infer.fold_half(model)
     legs = {'half': lambda: model(*inputs), 'half_folded': lambda: hfolded(*inputs)}
+    if opt.fp8:
+        f8folded = pkg.infer.fold_fp8(model)
+        legs['fp8_folded'] = lambda: f8folded(*inputs)
 else:
     folded = pkg.infer.fold(model)
     legs = {'fused': lambda: model(*inputs), 'folded': lambda: folded(*inputs)}
@@ -170,6 +183,7 @@ if opt.distill:
                             '-side_in', str(opt.side), '-do_teach', '-do_fusion'] + (['-half_acc'] if opt.half else []) +
                            (['-partial_conv'] if opt.family == 'partial_fusionnet' else []))
     switch = 'P3D_FOLDED_EVAL_HALF' if opt.half else 'P3D_FOLDED_EVAL'
+    dlegs = (('teacher', {switch: '0'}), ('folded_teacher', {switch: '1'})) + ((('fp8_teacher', {switch: '1', 'P3D_FOLDED_EVAL_FP8': '1'}),) if opt.fp8 else ())
     student = pkg.depthnet.__dict__[opt.model](dargs, False).cuda()
     teacher_family = pkg.partial_fusionnet if opt.family == 'partial_fusionnet' else pkg.fusionnet
     teacher = teacher_family.__dict__[opt.model](dargs, False).cuda().eval()
@@ -178,11 +192,13 @@ if opt.distill:
     att = torch.ones(opt.batch, 1, side_out, side_out, device='cuda')
     res = {}
     for r in range(opt.rounds):
-        for leg, on in (('teacher', '0'), ('folded_teacher', '1')):
-            os.environ[switch] = on
-            tr = pkg.depth_train.Trainer(dargs, student, pkg.utils.get_info()) if r == 0 and on == '0' else tr
+        for leg, env in dlegs:
+            os.environ.update(env)
+            os.environ['P3D_FOLDED_EVAL_FP8'] = env.get('P3D_FOLDED_EVAL_FP8', '0')
+            tr = pkg.depth_train.Trainer(dargs, student, pkg.utils.get_info()) if r == 0 and leg == 'teacher' else tr
             tr.set_teacher(teacher)
-            assert (tr.folded_teacher is not None) == (on == '1')
+            assert (tr.folded_teacher is not None) == (leg != 'teacher')
+            assert isinstance(tr.folded_teacher, pkg.infer.Fp8FoldedNet) == (leg == 'fp8_teacher')
             for _ in range(3):
                 tr.distill_step(1, c, d, tc, tv, att)
             torch.cuda.synchronize()
@@ -194,4 +210,28 @@ if opt.distill:
             res.setdefault(leg, []).append(dt * 1e3)
             print('round %d  distill_step %-24s %.2f ms' % (r, leg, dt * 1e3), flush=True)
     summary['distill_step_ms'] = {k: sorted(v) for k, v in res.items()}
+if opt.fp8 and opt.deviation:
+    def rel_l2(a, b):
+        a, b = a.double(), b.double()
+        return float((a - b).norm() / b.norm())
+
+    dev = {}
+    for fam in ('depthnet', 'fusionnet'):
+        fargs = pkg.opts.parse(['-model', opt.model, '-suffix', 'b', '-data_name', 'h36m', '-save_path', '/tmp/p3d', '-criterion', 'SmoothL1', '-num_joints', '17',
+                                '-side_in', str(opt.side)] + (['-do_fusion'] if fam == 'fusionnet' else []))
+        torch.manual_seed(0)
+        net = (pkg.fusionnet.__dict__[opt.model](fargs, False) if fam == 'fusionnet' else pkg.depth_main.create_model(fargs)[0]).cuda().eval()
+        g = torch.Generator(device='cuda').manual_seed(1)
+        xin = (torch.randn(opt.batch, 3, opt.side, opt.side, device='cuda', generator=g),)
+        if fam == 'fusionnet':
+            xin = xin + (torch.rand(opt.batch, 1, opt.side, opt.side, device='cuda', generator=g),)
+        with torch.no_grad():
+            ref32 = net(*xin)
+        f8 = pkg.infer.fold_fp8(net)(*xin)
+        h16 = pkg.infer.fold_half(net)(*xin)
+        dev[fam] = {'z_vs_fp32': rel_l2(f8[0], ref32[0]), 'feat_vs_fp32': rel_l2(f8[1], ref32[1]),
+                    'z_vs_half': rel_l2(f8[0], h16[0]), 'feat_vs_half': rel_l2(f8[1], h16[1]),
+                    'half_z_vs_fp32': rel_l2(h16[0], ref32[0]), 'half_feat_vs_fp32': rel_l2(h16[1], ref32[1])}
+        print('deviation %-10s %s' % (fam, ' '.join('%s %.3e' % kv for kv in dev[fam].items())), flush=True)
+    summary['deviation_rel_l2'] = dev
 print(json.dumps(dict(model=opt.model, family=opt.family, half=opt.half, batch=opt.batch, side=opt.side, warmup=opt.warmup, iters=opt.iters, legs=summary)))
