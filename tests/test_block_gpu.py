@@ -111,11 +111,13 @@ def rel2(a, b):
 
 
 def make_case(pkg, kind, inplanes, planes, stride, dil, n, h, with_ds, want_clean):
-    """Block + data; with want_clean the seed is advanced until no pre-ReLU activation lies within 2e-6 of zero (see `reference`)."""
-    for seed in range(3, 13):
+    """Block + data (h: the side of a square map, or (H, W)); with want_clean the seed is advanced until no pre-ReLU activation lies within 2e-6 of
+    zero (see `reference`)."""
+    h, w = (h, h) if isinstance(h, int) else h
+    for seed in range(3, 43):
         block = build(pkg, kind, inplanes, planes, stride, dil, with_ds, seed=inplanes + planes + seed)
         gen = torch.Generator(device='cuda').manual_seed(seed)
-        x0 = torch.randn(n, inplanes, h, h, device='cuda', generator=gen).relu_()           # a block input is a ReLU output
+        x0 = torch.randn(n, inplanes, h, w, device='cuda', generator=gen).relu_()           # a block input is a ReLU output
         with torch.no_grad():
             shape = block(x0).shape
         dy = torch.randn(shape, device='cuda', generator=gen)
@@ -127,13 +129,18 @@ def make_case(pkg, kind, inplanes, planes, stride, dil, n, h, with_ds, want_clea
 
 @pytest.mark.parametrize('case', CASES, ids=['%s_c%d_p%d_s%d_d%d_n%d_h%d%s' % (c[0], c[1], c[2], c[3], c[4], c[5], c[6], '_ds' if c[7] else '') for c in CASES])
 def test_fused_block_matches_per_layer_path_and_float64(case, pkg):
-    kind, inplanes, planes, stride, dil, n, h, with_ds = case
-    small = n * h * h <= 8192
+    fused_block_case(pkg, *case)
+
+
+def fused_block_case(pkg, kind, inplanes, planes, stride, dil, n, h, with_ds, admitted=True):
+    """h: the side of a square map, or (H, W).  admitted=False: a shape p3d_block_supported refuses -- both settings then run the per-layer path, which is
+    held to the same bounds."""
+    small = n * (h * h if isinstance(h, int) else h[0] * h[1]) <= 8192
     block, x0, dy, (ref, xr, yr, closest) = make_case(pkg, kind, inplanes, planes, stride, dil, n, h, with_ds, want_clean=small)
-    assert pkg.ops_block.usable(block, x0)
+    assert pkg.ops_block.usable(block, x0) == admitted
     plain = run(pkg, block, x0, dy, fused=False)
     fused = run(pkg, block, x0, dy, fused=True)
-    assert not torch.equal(plain['y'], fused['y'])                                      # the other path really ran
+    assert torch.equal(plain['y'], fused['y']) != admitted                              # the other path really ran
     # no activation near zero: element-wise bounds; the batch-64 case (50 M activations behind ReLUs, some within 1e-8 of zero): norm-wise
     err, tol = (rel, 2e-5) if small else (rel2, 2e-3)
     for name, got in (('fused', fused), ('per-layer', plain)):
@@ -381,6 +388,10 @@ def test_pair_image_pass_equals_two_passes(pkg):
 
 @pytest.mark.parametrize('consumer', ['identity', 'downsample_s1', 'downsample_s2'])
 def test_opening_sums_from_the_consumer_blocks_epilogue(pkg, consumer):
+    opening_sums_case(pkg, consumer, 32, 32)
+
+
+def opening_sums_case(pkg, consumer, h, w):
     """A chain of two blocks: the second block's backward pass reduces the channel sums the FIRST block's backward pass opens with (sum g, sum g (c - mean) of its
     closing and downsample BatchNorm over g = dout [out > 0]) in the epilogue of the data gradient that writes dout, so the first block skips its pass over dout
     (p3d_block_io.tail_* / open_sums; depthnet.py:101-116 and its autograd).  Same gradients as with the opening pass (P3D_TAIL_SUMS=0) to fp32 summation-order
@@ -395,7 +406,7 @@ def test_opening_sums_from_the_consumer_blocks_epilogue(pkg, consumer):
     else:
         second = build(pkg, 'bottleneck', 256, 128, 2, 1, True, 4)
     gen = torch.Generator(device='cuda').manual_seed(9)
-    x0 = torch.randn(6, 128, 32, 32, device='cuda', generator=gen)
+    x0 = torch.randn(6, 128, h, w, device='cuda', generator=gen)
 
     def step(tail, extra_consumer=False):
         keep = ob.USE_TAIL_SUMS
@@ -454,11 +465,15 @@ MASKED_CASES = [('bottleneck', 64, 64, 1, 1, 3, 32, True),         # partial_dep
 
 @pytest.mark.parametrize('case', MASKED_CASES, ids=['%s_c%d_p%d_s%d_n%d_h%d%s' % (c[0], c[1], c[2], c[3], c[5], c[6], '_ds' if c[7] else '') for c in MASKED_CASES])
 def test_masked_block_on_the_executor_matches_the_per_layer_path(case, pkg):
+    kind, inplanes, planes, stride, dil, n, h, with_ds = case
+    masked_block_case(pkg, kind, inplanes, planes, stride, dil, n, h, h, with_ds)
+
+
+def masked_block_case(pkg, kind, inplanes, planes, stride, dil, n, h, w, with_ds):
     """A residual block of partial convolutions (partial_depthnet.py:62-75,140-157; partial_conv.py:32-57) as ONE executor call per direction -- mask_in multiplied
     into the activation images (or into the in-kernel split of the fp32 block input), mult into the conv epilogues in front of the BatchNorm statistics and into
     the gradient images -- against the per-layer path (one autograd node per PartialConv / BatchNorm, itself pinned to the reference's goldens): output, mask_out,
     input gradient, every parameter gradient, running statistics.  The mask has holes, fully masked windows included."""
-    kind, inplanes, planes, stride, dil, n, h, with_ds = case
     tr = pkg._trunk
     block_cls = tr.Bottleneck if kind == 'bottleneck' else tr.BasicBlock
     ds = None
@@ -473,8 +488,8 @@ def test_masked_block_on_the_executor_matches_the_per_layer_path(case, pkg):
     block = block.cuda().train()
     _decide_relus(block, 31)        # every ReLU is on or off for a whole channel: one flipped activation would move a whole channel's gradient through the BatchNorm sums
     gen = torch.Generator(device='cuda').manual_seed(21)
-    x0 = torch.randn(n, inplanes, h, h, device='cuda', generator=gen)
-    veil = (torch.rand(n, 1, h, h, device='cuda', generator=gen) > 0.3).float()
+    x0 = torch.randn(n, inplanes, h, w, device='cuda', generator=gen)
+    veil = (torch.rand(n, 1, h, w, device='cuda', generator=gen) > 0.3).float()
     veil[0, 0, :9, :11] = 0.0
     assert pkg.ops_block.usable(block, x0, veil)
 

@@ -157,15 +157,16 @@ def _check(got, want, tol):
                                                                       float(got.double()[bad][0]), float(want[bad][0]))
 
 
-def _conv_case(pkg, cin, hw, cout, k, stride, dil, n, seed, x=None, w=None):
+def _conv_case(pkg, cin, hw, cout, k, stride, dil, n, seed, x=None, w=None, pad=None):
+    """hw: the side of a square map, or (H, W); pad: None for dil * (k - 1) / 2"""
     torch.manual_seed(seed)
-    conv, bn = _layer(pkg, cin, cout, k, stride, dil, seed=seed)
+    conv, bn = _layer(pkg, cin, cout, k, stride, dil, seed=seed, pad=pad)
     wf = _torch_fold(conv, bn) if w is None else w
     q, sc = _emul_image(wf)
     img = torch.cat([q.reshape(-1), sc.reshape(-1)])
     bias = (bn.bias - bn.running_mean * (bn.weight / torch.sqrt(bn.running_var + bn.eps))).detach().float()
     if x is None:
-        x = torch.randn(n, cin, hw, hw, device='cuda')
+        x = torch.randn(n, cin, *((hw, hw) if isinstance(hw, int) else hw), device='cuda')
     x16 = pkg.ops_half.to_half_nhwc(x, cin)
     return conv, q, sc, img, bias, x16
 
@@ -269,10 +270,14 @@ def _fp16_blocks(n, c, h, w, seed):
 
 @pytest.mark.parametrize('c,k,side', [(128, 1, 16), (96, 1, 17), (128, 3, 17)], ids=['c128_1x1', 'c96_1x1_odd', 'c128_3x3_odd'])
 def test_activation_quantizer_bit_exact(pkg, c, k, side):
+    quantizer_identity_case(pkg, c, k, side, side)
+
+
+def quantizer_identity_case(pkg, c, k, h, w_):
     """An identity conv (w[o][i] = [o == i], the centre tap of a 3x3) with b' = 0 and no residual: every output is ONE product, q(x) X * 1, exact in the
     MFMA however it sums, then rounded to fp16 once.  So the result must equal fp16(dequantize(quantize(x))) bit for bit -- the kernel's quantizer
     against the rule, with the weight side exact (a block holding a single 1)."""
-    x = _fp16_blocks(2, c, side, side, seed=c + k).cuda()
+    x = _fp16_blocks(2, c, h, w_, seed=c + k).cuda()
     w = torch.zeros(c, c, k, k, device='cuda')
     w[:, :, k // 2, k // 2] = torch.eye(c, device='cuda')
     q, sc = _emul_image(w)
@@ -298,8 +303,13 @@ NETS = [('depthnet', 'resnet18', (), 128, 2), ('resnet', 'resnet18', ('-extra_ch
 
 @pytest.mark.parametrize('family,model,extra,side,n', NETS, ids=lambda v: v if isinstance(v, str) else ''.join(v) if isinstance(v, tuple) else str(v))
 def test_whole_network_layer_by_layer(pkg, monkeypatch, family, model, extra, side, n):
+    layer_by_layer_case(pkg, monkeypatch, family, model, extra, side, n)
+
+
+def layer_by_layer_case(pkg, monkeypatch, family, model, extra, side, n, hw=None):
+    """hw: (H, W) of the batch where it is not side x side"""
     net, args = _net(pkg, family, model, *extra, side=side, seed=len(extra))
-    x, y = _inputs(family, args, n, side)
+    x, y = _inputs(family, args, n, hw or side)
     f8 = pkg.infer.fold_fp8(net)
     hf = pkg.infer.fold_half(net)
     cls = pkg.infer.Fp8FoldedNet
@@ -324,6 +334,7 @@ def test_whole_network_layer_by_layer(pkg, monkeypatch, family, model, extra, si
     got = got if isinstance(got, tuple) else (got,)
     assert all(t.dtype == torch.float32 and torch.isfinite(t).all() for t in got)
     assert seen['fp8'] > 0 and seen['fp16'] >= 2
+    return seen
 
 
 # ---- 4. coverage: every conv but the stems and heads on the fp8 entry, no BatchNorm pass ----------------------------------------------------

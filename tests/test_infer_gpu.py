@@ -130,9 +130,9 @@ CLASSES = [  # cin, hw, cout, k, stride, dilation
 ]
 
 
-def _layer(pkg, cin, cout, k, stride, dil, seed):
+def _layer(pkg, cin, cout, k, stride, dil, seed, pad=None):
     torch.manual_seed(seed)
-    conv = pkg.nn.Conv2d(cin, cout, k, stride=stride, padding=dil * (k - 1) // 2, dilation=dil, bias=False)
+    conv = pkg.nn.Conv2d(cin, cout, k, stride=stride, padding=dil * (k - 1) // 2 if pad is None else pad, dilation=dil, bias=False)
     bn = pkg.nn.BatchNorm2d(cout)
     mod = _stats_(torch.nn.Sequential(conv, bn), seed).cuda().eval()
     return mod[0], mod[1]
@@ -247,15 +247,22 @@ NETS = [('depthnet', 'resnet18', ()), ('depthnet', 'resnet50', ()), ('depthnet',
 
 @pytest.mark.parametrize('family,model,extra', NETS, ids=lambda v: v if isinstance(v, str) else ''.join(v))
 def test_whole_network(pkg, family, model, extra):
+    whole_network_case(pkg, family, model, extra, 128, 128)
+
+
+def whole_network_case(pkg, family, model, extra, h, w, n=2):
+    """infer.fold(net) and the unfolded eval forward on an [n, Cin, h, w] batch against the float64 forward; returns the conv path counters of the folded forward"""
     net, args = _net(pkg, family, model, *extra, side=128, seed=len(extra))
     g = torch.Generator(device='cuda').manual_seed(0)
     cin = 1 if args.depth_only else 3
-    x = torch.randn(2, cin, 128, 128, device='cuda', generator=g)
+    x = torch.randn(n, cin, h, w, device='cuda', generator=g)
     if family == 'partial_depthnet':
-        x = x * (torch.rand(2, 1, 128, 128, device='cuda', generator=g) > 0.3)
-    y = torch.rand(2, 1, 128, 128, device='cuda', generator=g) if family == 'fusionnet' else None
+        x = x * (torch.rand(n, 1, h, w, device='cuda', generator=g) > 0.3)
+    y = torch.rand(n, 1, h, w, device='cuda', generator=g) if family == 'fusionnet' else None
     fn = pkg.infer.fold(net)
+    pkg.ops.conv_path_stats(reset=True)
     got = fn(x) if y is None else fn(x, y)
+    stats = pkg.ops.conv_path_stats(reset=True)
     with torch.no_grad():
         old = net(x) if y is None else net(x, y)
         want = _forward64(net, family, x, y)
@@ -265,6 +272,7 @@ def test_whole_network(pkg, family, model, extra):
         assert gt.shape == ot.shape == wt.shape
         assert _rel(gt, wt) < 1e-4 and _rel(ot, wt) < 1e-4
         assert _rel(gt, ot) < 1e-4
+    return stats
 
 
 # ---- 4. no round-1 kernel -----------------------------------------------------------------------------------------------------------

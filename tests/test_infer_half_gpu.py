@@ -161,16 +161,18 @@ def _forward64_partial_fusionnet(net, x, y):
 
 
 def _inputs(family, args, n, side, seed=0):
+    """side: the side of a square crop, or (H, W)"""
     g = torch.Generator(device='cuda').manual_seed(seed)
+    h, w = (side, side) if isinstance(side, int) else side
     cin = 1 if args.depth_only else (4 if getattr(args, 'extra_channel', False) else 3)
-    x = torch.randn(n, cin, side, side, device='cuda', generator=g)
+    x = torch.randn(n, cin, h, w, device='cuda', generator=g)
     if family == 'partial_depthnet':
-        x = x * (torch.rand(n, 1, side, side, device='cuda', generator=g) > 0.3)
+        x = x * (torch.rand(n, 1, h, w, device='cuda', generator=g) > 0.3)
     y = None
     if family in ('fusionnet', 'partial_fusionnet'):
-        y = torch.rand(n, 1, side, side, device='cuda', generator=g)
+        y = torch.rand(n, 1, h, w, device='cuda', generator=g)
         if family == 'partial_fusionnet':
-            y = y * (torch.rand(n, 1, side, side, device='cuda', generator=g) > 0.3)
+            y = y * (torch.rand(n, 1, h, w, device='cuda', generator=g) > 0.3)
     return x, y
 
 
@@ -188,8 +190,13 @@ NETS = [('depthnet', 'resnet18', (), 128, 2), ('depthnet', 'resnet18', ('-depth_
 
 @pytest.mark.parametrize('family,model,extra,side,n', NETS, ids=lambda v: v if isinstance(v, str) else ''.join(v) if isinstance(v, tuple) else str(v))
 def test_whole_network(pkg, family, model, extra, side, n):
+    whole_network_case(pkg, family, model, extra, side, n)
+
+
+def whole_network_case(pkg, family, model, extra, side, n, hw=None):
+    """hw: (H, W) of the batch where it is not side x side"""
     net, args = _net(pkg, family, model, *extra, side=side, seed=len(extra))
-    x, y = _inputs(family, args, n, side)
+    x, y = _inputs(family, args, n, hw or side)
     hf = pkg.infer.fold_half(net)
     got = hf(x) if y is None else hf(x, y)
     with torch.no_grad():

@@ -123,12 +123,13 @@ def _forward64(net, family, x, y=None):
 def _inputs(family, n, side, seed=0):
     """The synthetic recipe: color ~ N(0, 1), depth ~ U[0, 1) with values < 0.3 zeroed (partial_depthnet: the depth map is the input)."""
     g = torch.Generator(device='cuda').manual_seed(seed)
-    depth = torch.rand(n, 1, side, side, device='cuda', generator=g)
+    h, w = (side, side) if isinstance(side, int) else side      # (a square crop, or (H, W))
+    depth = torch.rand(n, 1, h, w, device='cuda', generator=g)
     depth = depth * (depth >= 0.3)
-    depth[0, :, :side // 8, :side // 8] = 0                      # a hole wider than the stem's 7x7 window
+    depth[0, :, :h // 8, :w // 8] = 0                            # a hole wider than the stem's 7x7 window
     if family == 'partial_depthnet':
         return (depth,)
-    return torch.randn(n, 3, side, side, device='cuda', generator=g), depth
+    return torch.randn(n, 3, h, w, device='cuda', generator=g), depth
 
 
 def _mask(n, hw, seed, block):
@@ -241,8 +242,13 @@ def _folds_partial_layers(fn):
 @pytest.mark.parametrize('family', ['partial_depthnet', 'partial_fusionnet'])
 @pytest.mark.parametrize('model,side,batch', [('resnet18', 128, 2), ('resnet50', 256, 64)], ids=['r18_128_b2', 'r50_256_b64'])
 def test_whole_partial_network_folded(pkg, family, model, side, batch):
+    whole_partial_network_case(pkg, family, model, side, batch)
+
+
+def whole_partial_network_case(pkg, family, model, side, batch, hw=None):
+    """hw: (H, W) of the batch where it is not side x side"""
     net = _net(pkg, family, model, side=side, seed=2)
-    inputs = _inputs(family, batch, side, seed=1)
+    inputs = _inputs(family, batch, hw or side, seed=1)
     fn = pkg.infer.fold(net)
     assert _folds_partial_layers(fn)
     got = fn(*inputs)

@@ -545,8 +545,54 @@ X3_CASES = [
 ]
 
 
+def x3_case(pkg, n, c, k, h, w, r, stride, pad, dil, with_bias, seed=None):
+    """One convolution on the default path with the x3 kernels off and on, against float64 (see test_x3_kernels_match_fp32_kernels); [N, C, H, W] input,
+    any padding.  Which passes the x3 kernels took is read from the library's own launch counters (ops.conv_path_stats), not from a mirror of its
+    predicates.  Returns that (fwd, dgrad, wgrad) triple."""
+    ops = pkg.ops
+    gen = torch.Generator(device='cuda').manual_seed(11 + c + k if seed is None else seed)
+    F = torch.nn.functional
+    x = torch.randn(n, c, h, w, device='cuda', generator=gen) * (torch.rand(n, c, h, w, device='cuda', generator=gen) * 4 - 2).exp2()
+    w0 = torch.randn(k, c, r, r, device='cuda', generator=gen) / (c * r * r) ** 0.5
+    b0 = torch.randn(k, device='cuda', generator=gen) if with_bias else None
+    xd = x.double().requires_grad_(True)
+    y_ref = F.conv2d(xd, w0.double(), None if b0 is None else b0.double(), stride, pad, dil)
+    dy = torch.randn(y_ref.shape, device='cuda', generator=gen)
+    y_ref.backward(dy.double())
+    dw_ref = torch.nn.grad.conv2d_weight(x.double(), w0.shape, dy.double(), stride, pad, dil)
+    res, stats = {}, {}
+    before = ops.set_x3(True)
+    try:
+        for on in (False, True):
+            ops.set_x3(on)
+            xr = x.clone().requires_grad_(True)
+            wt = w0.clone().requires_grad_(True)
+            b = None if b0 is None else b0.clone().requires_grad_(True)
+            ops.conv_path_stats(reset=True)
+            y = ops.conv2d(xr, wt, b, stride, pad, dil)
+            y.backward(dy)
+            ops.join_side_stream()
+            torch.cuda.synchronize()
+            stats[on] = ops.conv_path_stats(reset=True)
+            res[on] = (y.detach().double(), xr.grad.double(), wt.grad.double())
+    finally:
+        ops.set_x3(before)
+    names = ('fwd', 'dgrad', 'wgrad')
+    assert all(stats[False]['x3'][nm][0] == 0 and stats[False]['fp32'][nm][0] == 1 for nm in names), stats[False]
+    assert all(stats[True]['x3'][nm][0] + stats[True]['fp32'][nm][0] == 1 for nm in names), stats[True]
+    covered = tuple(stats[True]['x3'][nm][0] == 1 for nm in names)
+    for i, ref, name in ((0, y_ref.detach(), 'fwd'), (1, xd.grad, 'dgrad'), (2, dw_ref, 'wgrad')):
+        scale = ref.abs().max()
+        e32, e3 = ((res[False][i] - ref).abs().max() / scale).item(), ((res[True][i] - ref).abs().max() / scale).item()
+        # 4e-6 of the largest value: fp32 accumulation over the longest reduction here (128 x 5 x 5 = 3200 terms, six products each) stays below it
+        assert e3 < 4e-6 and e3 < 4 * e32 + 2e-7, (name, e32, e3)
+        assert torch.equal(res[False][i], res[True][i]) != covered[i], name
+    return covered
+
+
 def _x3_covers(n, c, k, h, r, stride, dil):
-    """Mirror of fx_fwd_applies / fx_dgrad_applies / fx_wgrad_applies (csrc/p3d_fx.hip) for the square shapes above."""
+    """What fx_fwd_applies / fx_dgrad_applies / fx_wgrad_applies (csrc/p3d_fx.hip) say for the square, same-padded shapes above, written out: the launch
+    counters x3_case reads must agree with it (a counter that stopped counting would otherwise pass for "not covered")."""
     ho = (h - 1) // stride + 1
     fwd = c % 16 == 0 and c >= 32 and ho % 4 == 0 and h % 4 == 0 and k >= 96
     dgrad = k % 16 == 0 and k >= 32 and c % 4 == 0 and c >= 96 and ho % 4 == 0 and (h % 4 == 0 if stride == 1 else (h % 8 == 0 and (r == 1 or dil == 1)))
@@ -560,63 +606,39 @@ def test_x3_kernels_match_fp32_kernels(case, pkg):
     data: forward, data gradient and weight gradient, for 1x1 / 3x3 / 5x5, stride 1 and 2, dilation 1 / 2 / 4, bias, output channel counts that are
     not multiples of the 128-row tile (272, 320, 336) and split-K grids.  Its error is bounded by the fp32 kernel's; where the shape is covered the
     other kernel really ran, where it is not both settings give the same bits."""
-    ops = pkg.ops
     n, c, k, h, r, stride, dil, with_bias = case
-    pad = dil * (r - 1) // 2
-    gen = torch.Generator(device='cuda').manual_seed(11 + c + k)
-    F = torch.nn.functional
-    x = torch.randn(n, c, h, h, device='cuda', generator=gen) * (torch.rand(n, c, h, h, device='cuda', generator=gen) * 4 - 2).exp2()
-    w0 = torch.randn(k, c, r, r, device='cuda', generator=gen) / (c * r * r) ** 0.5
-    b0 = torch.randn(k, device='cuda', generator=gen) if with_bias else None
-    xd = x.double().requires_grad_(True)
-    y_ref = F.conv2d(xd, w0.double(), None if b0 is None else b0.double(), stride, pad, dil)
-    dy = torch.randn(y_ref.shape, device='cuda', generator=gen)
-    y_ref.backward(dy.double())
-    dw_ref = torch.nn.grad.conv2d_weight(x.double(), w0.shape, dy.double(), stride, pad, dil)
-    res = {}
-    before = ops.set_x3(True)
-    try:
-        for on in (False, True):
-            ops.set_x3(on)
-            xr = x.clone().requires_grad_(True)
-            w = w0.clone().requires_grad_(True)
-            b = None if b0 is None else b0.clone().requires_grad_(True)
-            y = ops.conv2d(xr, w, b, stride, pad, dil)
-            y.backward(dy)
-            res[on] = (y.detach().double(), xr.grad.double(), w.grad.double())
-    finally:
-        ops.set_x3(before)
-    covered = _x3_covers(n, c, k, h, r, stride, dil)
-    for i, ref, name in ((0, y_ref.detach(), 'fwd'), (1, xd.grad, 'dgrad'), (2, dw_ref, 'wgrad')):
-        scale = ref.abs().max()
-        e32, e3 = ((res[False][i] - ref).abs().max() / scale).item(), ((res[True][i] - ref).abs().max() / scale).item()
-        # 4e-6 of the largest value: fp32 accumulation over the longest reduction here (128 x 5 x 5 = 3200 terms, six products each) stays below it
-        assert e3 < 4e-6 and e3 < 4 * e32 + 2e-7, (name, e32, e3)
-        assert torch.equal(res[False][i], res[True][i]) != covered[i], name
+    covered = x3_case(pkg, n, c, k, h, h, r, stride, dil * (r - 1) // 2, dil, with_bias)
+    assert covered == _x3_covers(n, c, k, h, r, stride, dil)
 
 
 def test_x3_accumulates_into_existing_gradients(pkg):
     """accumulate = 1 on the default path: a weight gradient added onto an existing .grad, and a data gradient joined onto the shortcut's (GradJoin)."""
+    accumulate_case(pkg, 4, 256, 128, 16, 16, 3, 1, 1, 1)
+
+
+def accumulate_case(pkg, n, c, k, h, w_, r, stride, pad, dil):
     ops = pkg.ops
     gen = torch.Generator(device='cuda').manual_seed(5)
-    x = torch.randn(4, 256, 16, 16, device='cuda', generator=gen)
-    w = (torch.randn(128, 256, 3, 3, device='cuda', generator=gen) / 48).requires_grad_(True)
-    dy = torch.randn(4, 128, 16, 16, device='cuda', generator=gen)
-    d = ops._desc(x.shape, w.shape, 1, 1, 1, accumulate=1)
+    x = torch.randn(n, c, h, w_, device='cuda', generator=gen)
+    w = (torch.randn(k, c, r, r, device='cuda', generator=gen) / (c * r * r) ** 0.5).requires_grad_(True)
+    d = ops._desc(x.shape, w.shape, stride, pad, dil, accumulate=1)
+    dy = torch.randn(n, k, d.Ho, d.Wo, device='cuda', generator=gen)
     import ctypes
     L = pkg._lib.lib()
     dx = torch.randn(x.shape, device='cuda', generator=gen)
     dx0 = dx.clone()
     ws = ops.workspace(x.device, L.p3d_conv2d_dgrad_workspace_bytes(ctypes.byref(d)))
+    ops.conv_path_stats(reset=True)
     pkg._lib.check(L.p3d_conv2d_dgrad(ctypes.byref(d), ops._p(dy), ops._p(w.detach()), None, None, ops._p(dx), ops._p(ws), ws.numel(), ops._stream()), 'dgrad')
-    want = torch.nn.grad.conv2d_input(x.shape, w.detach().double(), dy.double(), 1, 1, 1) + dx0.double()
+    want = torch.nn.grad.conv2d_input(x.shape, w.detach().double(), dy.double(), stride, pad, dil) + dx0.double()
     assert ((dx.double() - want).abs().max() / want.abs().max()).item() < 3e-6
     dw = torch.randn(w.shape, device='cuda', generator=gen)
     dw0 = dw.clone()
     ws = ops.workspace(x.device, L.p3d_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
     pkg._lib.check(L.p3d_conv2d_wgrad(ctypes.byref(d), ops._p(dy), ops._p(x), None, None, ops._p(dw), ops._p(ws), ws.numel(), ops._stream()), 'wgrad')
-    want = torch.nn.grad.conv2d_weight(x.double(), w.shape, dy.double(), 1, 1, 1) + dw0.double()
+    want = torch.nn.grad.conv2d_weight(x.double(), w.shape, dy.double(), stride, pad, dil) + dw0.double()
     assert ((dw.double() - want).abs().max() / want.abs().max()).item() < 3e-6
+    return ops.conv_path_stats(reset=True)
 
 
 def test_paste_over_and_brightness_contrast_match_reference_golden(pkg):
@@ -652,25 +674,28 @@ def _image_planes(img, n, c, hw):
 
 def test_activation_image_is_an_exact_split(pkg):
     """hi + mid + lo == x bit for bit, each piece a bf16, laid out [n][c/16][pixel][16]; modes 1 / 2 apply relu(bn) / the BatchNorm-backward map first."""
+    act_image_split_case(pkg, 3, 48, 12, 12)
+
+
+def act_image_split_case(pkg, n, c, h, w):
     ops = pkg.ops
     gen = torch.Generator(device='cuda').manual_seed(3)
-    n, c, h = 3, 48, 12
-    x = torch.randn(n, c, h, h, device='cuda', generator=gen) * torch.logspace(-6, 6, c, device='cuda').view(1, c, 1, 1)
-    planes = _image_planes(ops.act_image(x), n, c, h * h)
+    x = torch.randn(n, c, h, w, device='cuda', generator=gen) * torch.logspace(-6, 6, c, device='cuda').view(1, c, 1, 1)
+    planes = _image_planes(ops.act_image(x), n, c, h * w)
     back = (planes[0].double() + planes[1].double() + planes[2].double()).float().reshape(x.shape)
     assert torch.equal(back, x)
     assert (planes[1].abs() <= planes[0].abs() * 2.0 ** -7 + 1e-45).all() and (planes[2].abs() <= planes[0].abs() * 2.0 ** -15 + 1e-45).all()
     tab = torch.randn(c, 8, device='cuda', generator=gen)
-    x = torch.randn(n, c, h, h, device='cuda', generator=gen)
-    c2 = torch.randn(n, c, h, h, device='cuda', generator=gen)
+    x = torch.randn(n, c, h, w, device='cuda', generator=gen)
+    c2 = torch.randn(n, c, h, w, device='cuda', generator=gen)
     col = lambda j: tab[:, j].view(1, c, 1, 1)
     want1 = torch.relu(torch.addcmul(col(1), x, col(0)))
-    got1 = _image_planes(ops.act_image(x, 1, table=tab), n, c, h * h).double().sum(0).float().reshape(x.shape)
+    got1 = _image_planes(ops.act_image(x, 1, table=tab), n, c, h * w).double().sum(0).float().reshape(x.shape)
     assert (got1 - want1).abs().max() <= 1e-6 * want1.abs().max()
     for masked in (False, True):
         g = torch.where(torch.addcmul(col(1), c2, col(0)) > 0, x, torch.zeros_like(x)) if masked else x
         want2 = col(4) * g + (col(5) * c2 + col(6))
-        got2 = _image_planes(ops.act_image(x, 2, x2=c2, table=tab, masked=masked), n, c, h * h).double().sum(0).float().reshape(x.shape)
+        got2 = _image_planes(ops.act_image(x, 2, x2=c2, table=tab, masked=masked), n, c, h * w).double().sum(0).float().reshape(x.shape)
         assert (got2 - want2).abs().max() <= 2e-6 * want2.abs().max()
 
 
@@ -681,37 +706,50 @@ IMG_CASES = [(2, 64, 16, 64, 3, 1, 1), (2, 128, 16, 272, 3, 1, 1), (3, 256, 16, 
              (2, 64, 16, 128, 3, 1, 1), (3, 64, 32, 48, 3, 1, 1), (2, 64, 32, 64, 3, 2, 1), (2, 64, 16, 64, 5, 1, 1), (2, 64, 16, 32, 3, 1, 2)]
 
 
+def image_fed_case(pkg, n, c, h, w, k, ks, st, pad, dil, seed=None, dgrad=True):
+    """The body of test_image_fed_kernels_match_the_oracle for an [N, C, H, W] input and any padding; dgrad=False leaves the data gradient out (a shape whose
+    strided data gradient p3d_fx_conv_img_supported refuses)."""
+    ops = pkg.ops
+    gen = torch.Generator(device='cuda').manual_seed(c + k + ks + st if seed is None else seed)
+    x = torch.randn(n, c, h, w, device='cuda', generator=gen).requires_grad_(True)
+    wt = (torch.randn(k, c, ks, ks, device='cuda', generator=gen) / (c * ks * ks) ** 0.5).requires_grad_(True)
+    y0 = ops.conv2d(x, wt, None, st, pad, dil)
+    dy = torch.randn(y0.shape, device='cuda', generator=gen)
+    y0.backward(dy)
+    x_img, dy_img = ops.act_image(x.detach()), ops.act_image(dy)
+    ops.conv_path_stats(reset=True)
+    y = ops.conv2d_img('fwd', x.shape, wt.detach(), st, pad, dil, x_img=x_img)
+    dx = ops.conv2d_img('dgrad', x.shape, wt.detach(), st, pad, dil, dy_img=dy_img) if dgrad else None
+    dw = ops.conv2d_img('wgrad', x.shape, wt.detach(), st, pad, dil, dy_img=dy_img, x_img=x_img)
+    dw2 = ops.conv2d_img('wgrad', x.shape, wt.detach(), st, pad, dil, dy_img=dy_img, x=x.detach())
+    ops.join_side_stream()
+    torch.cuda.synchronize()
+    stats = ops.conv_path_stats(reset=True)
+    assert [stats['x3'][nm][0] for nm in ('fwd', 'dgrad', 'wgrad')] == [1, int(dgrad), 2] and not any(v[0] for v in stats['fp32'].values()), stats
+    xh, wh, dyh = host(x), host(wt), host(dy)
+    want_y = ref.conv2d_fwd(xh, wh, None, st, pad, dil)
+    want_dx = ref.conv2d_dgrad(dyh, wh, x.shape, st, pad, dil)
+    want_dw = ref.conv2d_wgrad(dyh, xh, wt.shape, st, pad, dil)
+    for name, got, want, tol in (('fwd', y, want_y, 2e-5), ('dgrad', dx, want_dx, 2e-5), ('wgrad', dw, want_dw, 5e-5), ('wgrad fp32 x', dw2, want_dw, 5e-5)):
+        if got is None:
+            continue
+        err = np.abs(host(got) - want).max() / np.abs(want).max()
+        assert err < tol, (name, err)
+    for name, got, other in (('fwd', y, y0.detach()), ('dgrad', dx, x.grad), ('wgrad', dw, wt.grad)):
+        assert got is None or (got - other).abs().max() <= 4e-6 * other.abs().max(), name
+    if dgrad:
+        acc = torch.ones_like(x.detach())
+        ops.conv2d_img('dgrad', x.shape, wt.detach(), st, pad, dil, dy_img=dy_img, accumulate_into=acc)
+        assert (acc - 1 - dx).abs().max() <= 4e-6 * dx.abs().max()
+    return dict(y=y, dx=dx, dw=dw, x=x.detach(), w=wt.detach(), dy=dy, want_dx=want_dx)
+
+
 @pytest.mark.parametrize('case', IMG_CASES, ids=['n%d_c%d_h%d_k%d_%dx%d_s%d_d%d' % (c[0], c[1], c[2], c[3], c[4], c[4], c[5], c[6]) for c in IMG_CASES])
 def test_image_fed_kernels_match_the_oracle(case, pkg):
     """Forward, data gradient and weight gradient fed by pre-split activation images (AMODE 1 / AIMG / BIMG instances of csrc/p3d_fx.hip) against the float64
     oracle, and against the same kernels fed fp32 tensors (the in-kernel split): the two must agree to rounding of the accumulation order."""
-    ops = pkg.ops
     n, c, h, k, ks, st, dil = case
-    pad = dil * (ks - 1) // 2
-    gen = torch.Generator(device='cuda').manual_seed(c + k + ks + st)
-    x = torch.randn(n, c, h, h, device='cuda', generator=gen).requires_grad_(True)
-    w = (torch.randn(k, c, ks, ks, device='cuda', generator=gen) / (c * ks * ks) ** 0.5).requires_grad_(True)
-    y0 = ops.conv2d(x, w, None, st, pad, dil)
-    dy = torch.randn(y0.shape, device='cuda', generator=gen)
-    y0.backward(dy)
-    x_img, dy_img = ops.act_image(x.detach()), ops.act_image(dy)
-    y = ops.conv2d_img('fwd', x.shape, w.detach(), st, pad, dil, x_img=x_img)
-    dx = ops.conv2d_img('dgrad', x.shape, w.detach(), st, pad, dil, dy_img=dy_img)
-    dw = ops.conv2d_img('wgrad', x.shape, w.detach(), st, pad, dil, dy_img=dy_img, x_img=x_img)
-    dw2 = ops.conv2d_img('wgrad', x.shape, w.detach(), st, pad, dil, dy_img=dy_img, x=x.detach())
-    torch.cuda.synchronize()
-    xh, wh, dyh = host(x), host(w), host(dy)
-    want_y = ref.conv2d_fwd(xh, wh, None, st, pad, dil)
-    want_dx = ref.conv2d_dgrad(dyh, wh, x.shape, st, pad, dil)
-    want_dw = ref.conv2d_wgrad(dyh, xh, w.shape, st, pad, dil)
-    for name, got, want, tol in (('fwd', y, want_y, 2e-5), ('dgrad', dx, want_dx, 2e-5), ('wgrad', dw, want_dw, 5e-5), ('wgrad fp32 x', dw2, want_dw, 5e-5)):
-        err = np.abs(host(got) - want).max() / np.abs(want).max()
-        assert err < tol, (name, err)
-    for name, got, other in (('fwd', y, y0.detach()), ('dgrad', dx, x.grad), ('wgrad', dw, w.grad)):
-        assert (got - other).abs().max() <= 4e-6 * other.abs().max(), name
-    acc = torch.ones_like(x.detach())
-    ops.conv2d_img('dgrad', x.shape, w.detach(), st, pad, dil, dy_img=dy_img, accumulate_into=acc)
-    assert (acc - 1 - dx).abs().max() <= 4e-6 * dx.abs().max()
+    image_fed_case(pkg, n, c, h, h, k, ks, st, dil * (ks - 1) // 2, dil)
 
 
 @pytest.mark.parametrize('case', [(2, 3, 64, 64, 64), (3, 1, 48, 64, 64), (2, 3, 32, 32, 96), (5, 3, 128, 128, 64), (2, 4, 64, 64, 64)], ids=lambda c: 'n%d_c%d_%dx%d_k%d' % c)
