@@ -17,22 +17,9 @@ extern "C" {
 int32_t p3d_version(void) { return P3D_VERSION; }
 const char* p3d_last_error(void) { return p3d::g_err; }
 
-// A HIP stream of a chosen priority class (-1 high, 0 normal, 1 low) on the current device.  The runtime keeps one pool of hardware queues per priority
-// (at most GPU_MAX_HW_QUEUES = 4 each) and multiplexes streams of equal priority onto them: a second stream of the launch stream's own priority can end
-// up on the launch stream's queue (it does once an RCCL communicator has taken queues first), which serialises the two and turns every cross-stream event
-// into a queue barrier.  The weight-gradient stream is therefore created LOW: its kernels are fillers behind the dgrad chain, and its queue is its own.
-int32_t p3d_stream_create(int32_t priority_class, void** stream) {
-    using namespace p3d;
-    P3D_REQUIRE(stream != nullptr, "stream_create: null output");
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { set_error("stream_create: no priority range"); return P3D_ELAUNCH; }
-    const int prio = priority_class > 0 ? least : (priority_class < 0 ? greatest : (least + greatest) / 2);
-    hipStream_t s = nullptr;
-    if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio) != hipSuccess) { set_error("stream_create: hipStreamCreateWithPriority(%d) failed", prio); return P3D_ELAUNCH; }
-    *stream = s;
-    return P3D_OK;
-}
-// A second stream that demonstrably runs beside `main_stream`: candidates are created one after the other and probed with two one-wave kernels that
+// A second stream that demonstrably runs beside `main_stream`.  The runtime keeps one pool of hardware queues per priority (at most GPU_MAX_HW_QUEUES = 4 each) and
+// multiplexes streams of equal priority onto them: a second stream can end up on the launch stream's queue (it does once an RCCL communicator has taken queues
+// first), which serialises the two and turns every cross-stream event into a queue barrier.  So candidates are created one after the other and probed with two one-wave kernels that
 // each spin for 200 us of the constant-rate clock, one per stream; on separate hardware queues the pair takes ~200 us, multiplexed onto one queue ~400.
 // Up to 8 candidates (each new stream goes to the least-used queue of the pool); the rejected ones are destroyed.  *overlaps = 0 if none passed (the
 // last candidate is returned anyway: correct, just serial).
@@ -74,8 +61,8 @@ int32_t p3d_stream_create_beside(void* main_stream, void** stream, int32_t* over
     return P3D_OK;
 }
 // A stream whose kernels may only run on the compute units whose bit is set in `mask` (bit i of word i / 32; 256 CUs = 8 words on MI355X).  A CU mask is a property
-// of the hardware queue, so such a stream has a queue of its own.  Used to give the weight-gradient stream a fixed share of the chip (ops._side_stream,
-// P3D_SIDE_CUS) so that the launch stream's short memory-bound passes always find free CUs instead of waiting for long weight-gradient blocks to retire.
+// of the hardware queue, so such a stream has a queue of its own.  Used by ops.masked_stream
+// (bench.py's P3D_MAIN_CUS, tools/cumask_probe.py); giving the weight-gradient stream a fixed share of the chip lost by 2-15 ms per step (profiles/r04_summary.md section 2).
 int32_t p3d_stream_create_cumask(const uint32_t* mask, int32_t words, void** stream) {
     using namespace p3d;
     P3D_REQUIRE(stream != nullptr && mask != nullptr && words > 0, "stream_create_cumask: bad argument");

@@ -707,9 +707,9 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
 
 // ---- the same block on the fp16 NHWC kernels (-half_acc): host-side fusion of the per-layer entry points into one call per block and direction -------------------
 static bool hblock_slot(const p3d_block_desc* b, int i) { return i < b->nconv || (i == 3 && b->has_downsample); }
-// BatchNorm sums in the conv epilogues (p3d_hconv2d_fwd_stats / p3d_hconv2d_dgrad_sums); P3D_HALF_FUSED=0: the stand-alone statistics / reduce passes (A/B, and the
+// BatchNorm sums in the conv epilogues (p3d_hconv2d_fwd_stats / p3d_hconv2d_dgrad_sums); p3d_hblock_fuse_sums(0): the stand-alone statistics / reduce passes (the
 // configuration in which the executor is bit-identical to the per-layer path)
-static int g_hblock_fused = [] { const char* e = getenv("P3D_HALF_FUSED"); return (e && atoi(e) == 0) ? 0 : 1; }();
+static int g_hblock_fused = 1;
 static bool hblock_fused() { return g_hblock_fused != 0; }
 // main workspace of a layer: [the partial table: max(512 stand-alone blocks, pixel tiles of either pass) rows][K float4 of constants]
 static size_t hblock_rows(const p3d_conv_desc* d) {

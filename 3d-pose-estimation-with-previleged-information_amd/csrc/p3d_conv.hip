@@ -940,18 +940,11 @@ static IgemmParams base_params(const p3d_conv_desc* d) {
 // ---- tile configurations --------------------------------------------------------------------------------
 struct TileCfg { int bm, bn, bk; double eff; };
 //                               128x128           64x256            96x128            64x128            128x64            64x64
-static const TileCfg kCfgs[8] = {{128, 128, 16, 1.0}, {64, 256, 16, 0.95}, {96, 128, 16, 0.95}, {64, 128, 16, 0.85}, {128, 64, 16, 0.85}, {64, 64, 32, 0.7},
-                                 {128, 128, 32, 1.0}, {64, 128, 32, 0.85}};     // 6, 7: experimental BK = 32 shapes (P3D_FORCE_CFG only)
+static const TileCfg kCfgs[6] = {{128, 128, 16, 1.0}, {64, 256, 16, 0.95}, {96, 128, 16, 0.95}, {64, 128, 16, 0.85}, {128, 64, 16, 0.85}, {64, 64, 32, 0.7}};
 constexpr int kSlots = 512;   // blocks resident at once (2 per CU) used to price the tail of a launch
 
 // cost ~ rounds of resident blocks x tile area / efficiency; `zmult` = extra grid factor (classes)
-static int forced_cfg() {      // tuning aid: P3D_FORCE_CFG=0..5 pins the tile shape (tools/conv_bench.py --sweep)
-    static const int v = [] { const char* e = getenv("P3D_FORCE_CFG"); return e ? atoi(e) : -1; }();
-    return v;
-}
-
 static int pick_cfg(int M, int Ncols, int64_t zmult) {
-    if (forced_cfg() >= 0 && forced_cfg() < 8) return forced_cfg();
     int best = 0;
     double best_cost = 1e300;
     for (int i = 0; i < 6; ++i) {
@@ -965,8 +958,7 @@ static int pick_cfg(int M, int Ncols, int64_t zmult) {
 
 template <int MODE, int BM, int BN, int WM, int WN, int BK>
 static void launch_variant(bool tapm, bool masked, int wv, dim3 grid, hipStream_t st, const IgemmParams& p) {
-    constexpr bool ALLOW_MASK = BK == 16 || (BM == 64 && BN == 64);          // every production shape; not the BK = 32 experiments (cfg 6, 7)
-    if constexpr (MODE == MODE_WGRAD && ALLOW_MASK) {
+    if constexpr (MODE == MODE_WGRAD) {
         if (masked && wv == 2) {
             if (tapm) hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, BK, true, true, 2>), grid, dim3(256), 0, st, p);
             else hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, BK, false, true, 2>), grid, dim3(256), 0, st, p);
@@ -990,24 +982,17 @@ static void launch_variant(bool tapm, bool masked, int wv, dim3 grid, hipStream_
             return;
         }
     }
-    if constexpr (ALLOW_MASK) {
-        if (masked) {
-            if constexpr (MODE != MODE_DGRAD) {
-                if (!tapm) { hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, BK, false, true>), grid, dim3(256), 0, st, p); return; }
-            }
-            hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, BK, true, true>), grid, dim3(256), 0, st, p);
-            return;
+    if (masked) {
+        if constexpr (MODE != MODE_DGRAD) {
+            if (!tapm) { hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, BK, false, true>), grid, dim3(256), 0, st, p); return; }
         }
+        hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, BK, true, true>), grid, dim3(256), 0, st, p);
+        return;
     }
     if constexpr (MODE != MODE_DGRAD) {
         if (!tapm) { hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, BK, false, false>), grid, dim3(256), 0, st, p); return; }
     }
     hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, BK, true, false>), grid, dim3(256), 0, st, p);
-}
-
-static int mask_cfg(int cfg, bool masked) {   // masked (partial-conv) variants exist for the production shapes 0..5
-    if (masked && cfg > 5) return (kCfgs[cfg].bm == 64) ? 3 : 0;
-    return cfg;
 }
 
 template <int MODE>
@@ -1020,8 +1005,6 @@ static void launch_igemm(int cfg, bool tapm, bool masked, IgemmParams& p, int ny
         case 2: launch_variant<MODE, 96, 128, 1, 4, 16>(tapm, masked, wv, grid, st, p); break;
         case 3: launch_variant<MODE, 64, 128, 2, 2, 16>(tapm, masked, wv, grid, st, p); break;
         case 4: launch_variant<MODE, 128, 64, 2, 2, 16>(tapm, masked, wv, grid, st, p); break;
-        case 6: launch_variant<MODE, 128, 128, 2, 2, 32>(tapm, false, wv, grid, st, p); break;
-        case 7: launch_variant<MODE, 64, 128, 2, 2, 32>(tapm, false, wv, grid, st, p); break;
         default: launch_variant<MODE, 64, 64, 2, 2, 32>(tapm, masked, wv, grid, st, p); break;
     }
 }
@@ -1036,10 +1019,7 @@ static WgradPlan plan_wgrad(const p3d_conv_desc* d, bool masked) {
     int cfg = -1;
     bool tapm = false;
     double best = 1e300;
-    for (int i = 0; i < 8; ++i) {
-        if (masked && i >= 6) break;                      // no masked instances of the experimental shapes
-        if (!masked && forced_cfg() >= 0 && i != forced_cfg()) continue;
-        if (forced_cfg() < 0 && i >= 6) break;            // experimental shapes only when forced
+    for (int i = 0; i < 6; ++i) {
         const bool tm = d->C % kCfgs[i].bn == 0;
         double cost = (double)ceil_div(M, kCfgs[i].bm) * kCfgs[i].bm * ceil_div(Ncols, kCfgs[i].bn) * kCfgs[i].bn / kCfgs[i].eff;
         if (!tm && d->R * d->S > 1) cost *= 1.3;          // generic per-element tap decode is slower
@@ -1047,7 +1027,7 @@ static WgradPlan plan_wgrad(const p3d_conv_desc* d, bool masked) {
     }
     {   // weight tensors of at most four 128x128 tiles (layer1, the stems): 64x64 tiles need a quarter of the splits -> less slab traffic
         const int64_t t128 = ceil_div(M, 128) * ceil_div(Ncols, 128);
-        if (!masked && forced_cfg() < 0 && t128 <= 4 && d->C % 64 == 0) { cfg = 5; tapm = true; }
+        if (!masked && t128 <= 4 && d->C % 64 == 0) { cfg = 5; tapm = true; }
     }
     const int bk = kCfgs[cfg].bk;
     const int64_t tiles = ceil_div(M, kCfgs[cfg].bm) * ceil_div(Ncols, kCfgs[cfg].bn);
@@ -1161,9 +1141,9 @@ static FwdPlan plan_fwd(const p3d_conv_desc* d, bool masked, bool allow_split) {
     FwdPlan pl;
     const int M = d->K, Ncols = d->N * d->Ho * d->Wo;
     pl.tapm = d->C >= 16;
-    pl.cfg = mask_cfg(pick_cfg(M, Ncols, 1), masked);
+    pl.cfg = pick_cfg(M, Ncols, 1);
     pl.splits = 1; pl.kchunk = 0;
-    if (!allow_split || masked || !pl.tapm || forced_cfg() >= 0) return pl;
+    if (!allow_split || masked || !pl.tapm) return pl;
     // candidate: the tile with the least padded work if the grid had no tail; if that leaves <= 400 long blocks, split K
     int cfgA = 0;
     double best = 1e300;
@@ -1182,7 +1162,7 @@ static FwdPlan plan_fwd(const p3d_conv_desc* d, bool masked, bool allow_split) {
     pl.cfg = cfgA;
     pl.kchunk = (int)ceil_div(nk, splits);
     pl.splits = (int)ceil_div(nk, pl.kchunk);
-    if (pl.splits < 2) { pl.splits = 1; pl.kchunk = 0; pl.cfg = mask_cfg(pick_cfg(M, Ncols, 1), masked); }
+    if (pl.splits < 2) { pl.splits = 1; pl.kchunk = 0; pl.cfg = pick_cfg(M, Ncols, 1); }
     return pl;
 }
 
@@ -1282,9 +1262,9 @@ static FwdPlan plan_dgrad1(const p3d_conv_desc* d, bool masked) {
     FwdPlan pl;
     const int M = d->C, Ncols = d->N * d->H * d->W;
     pl.tapm = true;
-    pl.cfg = mask_cfg(pick_cfg(M, Ncols, 1), masked);
+    pl.cfg = pick_cfg(M, Ncols, 1);
     pl.splits = 1; pl.kchunk = 0;
-    if (masked || forced_cfg() >= 0) return pl;
+    if (masked) return pl;
     int cfgA = 0;
     double best = 1e300;
     for (int i = 0; i < 6; ++i) {
@@ -1302,7 +1282,7 @@ static FwdPlan plan_dgrad1(const p3d_conv_desc* d, bool masked) {
     pl.cfg = cfgA;
     pl.kchunk = (int)ceil_div(nk, splits);
     pl.splits = (int)ceil_div(nk, pl.kchunk);
-    if (pl.splits < 2) { pl.splits = 1; pl.kchunk = 0; pl.cfg = mask_cfg(pick_cfg(M, Ncols, 1), masked); }
+    if (pl.splits < 2) { pl.splits = 1; pl.kchunk = 0; pl.cfg = pick_cfg(M, Ncols, 1); }
     return pl;
 }
 
@@ -1360,7 +1340,7 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
     p.Ncols = d->N * hc * wc;                    // the largest class (0,0) sizes the grid
     int nlive = 0;
     for (int c = 0; c < p.ncls; ++c) nlive += (live >> c) & 1;
-    const int cfg = mask_cfg(pick_cfg(p.M, p.Ncols, nlive > 0 ? nlive : 1), masked);     // classes no tap reaches exit at once
+    const int cfg = pick_cfg(p.M, p.Ncols, nlive > 0 ? nlive : 1);     // classes no tap reaches exit at once
     p.cpad = (int)ceil_div(d->K, kCfgs[cfg].bk) * kCfgs[cfg].bk;
     if (st == 1) {
         const FwdPlan pl = plan_dgrad1(d, masked);

@@ -44,8 +44,6 @@ struct FxConvParams {
     int tiles_m;
     int tap_inner;          // K-step order of a multi-tap launch: 0 tap outer (all channel steps of a tap, then the next tap), 1 tap inner (the taps of a 16-channel
                             // step back to back: the shifted windows of one channel group are the same cache lines, which a wide layer otherwise re-fetches per tap)
-    int order;              // block order inside an XCD's run of logical ids: 0 channel tile fastest (consecutive blocks share an activation tile), 1 pixel tile fastest
-                            // (consecutive blocks share a weight tile and stream its K steps together: layers whose weight image outweighs what an L2 holds)
     int ncls;               // > 0: a strided data gradient whose parity classes run as ONE launch, class blockIdx.z overriding the fields above from cls[]
     FxConvClass cls[4];
 };

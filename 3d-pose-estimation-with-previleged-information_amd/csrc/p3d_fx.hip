@@ -94,22 +94,6 @@ __device__ __forceinline__ int fx_live_subtiles(int first, int limit) {
 // out-of-range bit 0x80000000 for padding pixels / rows beyond the tensor, which the resource's range check turns into zeros), the per-K-step part of an
 // address is a wave-uniform scalar offset.  So a K step's fetch is loads only: no branches, no per-step address arithmetic.
 constexpr int FX_OOB = (int)0x80000000;
-// tuning ablation (wrong results, timing only): P3D_FX_ABL_NOLOAD fetches every K step from the first step's addresses (cache-hot operands)
-#if (defined(P3D_FX_ABL_NOLOAD) || defined(P3D_FX_ABL_NOREAD) || defined(P3D_FX_ABL_NOSTAGE) || defined(P3D_FX_ABL_NOBAR)) && !defined(P3D_TIMING_ONLY_BUILD)
-#error "P3D_FX_ABL_* builds compute wrong results: define P3D_TIMING_ONLY_BUILD as well (tools/ablate.sh does) and never ship the library"
-#endif
-#ifdef P3D_FX_ABL_NOLOAD
-#define FX_SO(x) 0
-#else
-#define FX_SO(x) (x)
-#endif
-// further timing-only ablations of fx_conv_kernel's K loop (wrong results): P3D_FX_ABL_NOREAD reads the MFMA fragments from LDS in the first step only,
-// P3D_FX_ABL_NOSTAGE never stores a fetched step to LDS, P3D_FX_ABL_NOBAR drops the loop's barrier (tools/ablate.sh builds and times them)
-#ifdef P3D_FX_ABL_NOREAD
-#define FX_ABL_READ(kt) ((kt) == 0)
-#else
-#define FX_ABL_READ(kt) true
-#endif
 __device__ f32x4 fx_buffer_load_f32x4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
 __device__ i32x4 fx_buffer_load_i32x4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4i32");
 __device__ float fx_buffer_load_f32(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
@@ -187,8 +171,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
         const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
-    const int tiles_n_all = gridDim.x / p.tiles_m;
-    const int tile_m = p.order ? bid / tiles_n_all : bid % p.tiles_m, tile_n = p.order ? bid % tiles_n_all : bid / p.tiles_m;
+    const int tile_m = bid % p.tiles_m, tile_n = bid / p.tiles_m;
     const int m0 = tile_m * FX_BM, n0 = tile_n * FX_BN;
     const int OHW = p.OH * p.OW;
     const int HWi = p.Hi * p.Wi;
@@ -276,20 +259,20 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
         {
             const int so = w_tapoff + (f_k >> 4) * (3 * FX_PIECE);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) rwi[j] = fx_buffer_load_i32x4(rW, w_voff[j], FX_SO(so), 0);
+            for (int j = 0; j < 3; ++j) rwi[j] = fx_buffer_load_i32x4(rW, w_voff[j], so, 0);
         }
         if constexpr (AMODE != 0) {
             const int so = (f_k >> 4) * HWi * 32;                  // wave-uniform: the K step's channel group
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) rxi[pc] = fx_buffer_load_i32x4(rXi[pc], x_voff[0], FX_SO(so), 0);
+            for (int pc = 0; pc < 3; ++pc) rxi[pc] = fx_buffer_load_i32x4(rXi[pc], x_voff[0], so, 0);
         } else {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int so = (f_k + 8 * i) * HWi * 4;             // wave-uniform: reduction chunk + this pass's 8-row step
-                if (x_vec) rx[i] = fx_buffer_load_f32x4(rX, x_voff[0], FX_SO(so), 0);
+                if (x_vec) rx[i] = fx_buffer_load_f32x4(rX, x_voff[0], so, 0);
                 else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) rx[i][e] = fx_buffer_load_f32(rX, x_voff[e], FX_SO(so), 0);
+                    for (int e = 0; e < 4; ++e) rx[i][e] = fx_buffer_load_f32(rX, x_voff[e], so, 0);
                 }
             }
             if constexpr (PRO == 4) smask = tmask;            // (the factor of the tap these loads belong to: the next fetch may already be at another tap)
@@ -369,23 +352,19 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
             // that issues its six LDS stores before its first MFMA leaves the matrix pipe idle for their issue time): fragments of the first two products,
             // the first product's MFMAs, under them the LDS stores of step kt + 1 and the loads of step kt + 2, then the rest.
             if constexpr (NB > 0) {
-                if (FX_ABL_READ(kt)) { read_p(2); read_c(0); read_p(0); read_c(2); }
+                read_p(2); read_c(0); read_p(0); read_c(2);
                 __builtin_amdgcn_sched_barrier(0);
                 P3D_FX_PRODUCTS_RANGE(acc, pf, cf, 2, NB, 0, 1)
                 __builtin_amdgcn_sched_barrier(0);
             }
-#ifndef P3D_FX_ABL_NOSTAGE
             if constexpr (decltype(st)::value) stage(buf ^ 1);
-#endif
             if constexpr (decltype(fe)::value) fetch();
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (NB > 0) {
-                if (FX_ABL_READ(kt)) { read_p(1); read_c(1); }
+                read_p(1); read_c(1);
                 P3D_FX_PRODUCTS_RANGE(acc, pf, cf, 2, NB, 1, 6)
             }
-#ifndef P3D_FX_ABL_NOBAR
             __syncthreads();
-#endif
         };
         // (the two last steps are peeled so that the body of the main loop has no branch around its LDS stores: the wait in front of the first MFMA can then
         // count exactly the reads it needs instead of draining the stores too)
@@ -618,8 +597,8 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
 // adds P_X C_X' + P_Y C_Y' into the accumulator.  The six products of a step are three such pairs, smallest first:
 //     (P_hi | P_lo) x (C_lo | C_hi)      (P_hi | P_mid) x (C_mid | C_mid)      (P_hi | P_mid) x (C_hi | C_hi)
 // = 3 x 16 instructions of 16 passes per wave and step instead of 6 x 4 of 32 passes: the same matrix-pipe cycles, 20 fragment reads per wave instead of 12, and a
-// shape on which the chip holds a higher clock (MI355X_MICROARCH.md, DVFS item 7).  16 x 16 sub-tiles also make the channel tile a template parameter: BM = 128
-// (wave 64 channels x 64 pixels) or 96 (wave 48 x 64: the 272-channel regressor is 96 + 96 + 80 instead of 128 + 128 + 16).
+// shape on which the chip holds a higher clock (MI355X_MICROARCH.md, DVFS item 7).  16 x 16 sub-tiles also make the channel tile a template parameter: BM = 96
+// (wave 48 channels x 64 pixels: the 272-channel regressor is 96 + 96 + 80 instead of 128 + 128 + 16) or 64 (wave 32 x 64); 128-row tiles stay on fx_conv_kernel (fx16_bm).
 // LDS images: "rc" rows of 32 B (row = pixel or channel, 16 k), NOT swizzled: a 16-lane group of the fragment read takes rows r .. r+3 / r+12 .. r+15 of one half
 // and rows r+4 .. r+11 of the other, which are 16 different bank quads as they lie.  The weight image keeps the swizzle of fx_rc_off; the staging copy undoes it
 // by fetching, for LDS position 16 t, the chunk that belongs there.
@@ -628,7 +607,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
 template <int BM, int EPI, bool TAPI = false>
 __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_in) {
     const FxConvParams p = fx_class_params(p_in);
-    static_assert(BM == 128 || BM == 96 || BM == 64, "channel tile");
+    static_assert(BM == 96 || BM == 64, "channel tile");
     constexpr int GA = 4, GB = BM / 32;                 // 16-pixel / 16-channel groups of a wave (2 x 2 waves; a wave: 64 pixels x BM / 2 channels)
     constexpr int WCH = BM / 2;
     constexpr int PIECE_P = 128 * 32, PIECE_C = BM * 32;
@@ -642,8 +621,7 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
         const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
-    const int tiles_n_all = gridDim.x / p.tiles_m;
-    const int tile_m = p.order ? bid / tiles_n_all : bid % p.tiles_m, tile_n = p.order ? bid % tiles_n_all : bid / p.tiles_m;
+    const int tile_m = bid % p.tiles_m, tile_n = bid / p.tiles_m;
     const int m0 = tile_m * BM, n0 = tile_n * FX_BN;
     const int OHW = p.OH * p.OW;
     const int HWi = p.Hi * p.Wi;
@@ -1109,16 +1087,16 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
                 const int voff = (a3_ok && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi) ? ((icg & 3) * HWi + hi * p.Wi + wi) * 32 + 16 * ih : FX_OOB;
                 const int x_so = f_img * CG * HWi * 32;
 #pragma unroll
-                for (int pc = 0; pc < 3; ++pc) rai[pc] = fx_buffer_load_i32x4(rBi[pc], voff, FX_SO(x_so), 0);
+                for (int pc = 0; pc < 3; ++pc) rai[pc] = fx_buffer_load_i32x4(rBi[pc], voff, x_so, 0);
             } else {
                 const int a_so = (f_img * KG * OHW + f_p) * 32;
 #pragma unroll
-                for (int pc = 0; pc < 3; ++pc) rai[pc] = fx_buffer_load_i32x4(rAi[pc], ai_voff, FX_SO(a_so), 0);
+                for (int pc = 0; pc < 3; ++pc) rai[pc] = fx_buffer_load_i32x4(rAi[pc], ai_voff, a_so, 0);
             }
         } else {
             const int a_so = (f_img * p.K * OHW + f_p) * 4;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) ra[i] = fx_buffer_load_f32x4(rA, a_voff[i], FX_SO(a_so), 0);
+            for (int i = 0; i < 2; ++i) ra[i] = fx_buffer_load_f32x4(rA, a_voff[i], a_so, 0);
             if constexpr (MASKED) ram = fx_buffer_load_f32x4(rAM, 16 * kq, (f_img * OHW + f_p) * 4, 0);
         }
         // operand B (x at this block's filter tap)
@@ -1133,7 +1111,7 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
                 voff = (bi_ok && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi) ? (b_cg * HWi + hi * p.Wi + wi) * 32 + 16 * ih : FX_OOB;
             }
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) rbi[pc] = fx_buffer_load_i32x4(rBi[pc], voff, FX_SO(b_so), 0);
+            for (int pc = 0; pc < 3; ++pc) rbi[pc] = fx_buffer_load_i32x4(rBi[pc], voff, b_so, 0);
         } else {
             int b_so = f_img * p.C * HWi * 4;
             if (simple) {
@@ -1153,10 +1131,10 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
             for (int i = 0; i < 2; ++i) {
                 const int so = b_so + i * 64 * HWi * 4;
                 const int rowbad = b_ok[i] ? 0 : FX_OOB;
-                if (vec) rb[i] = fx_buffer_load_f32x4(rB, b_voff[0] | rowbad, FX_SO(so), 0);
+                if (vec) rb[i] = fx_buffer_load_f32x4(rB, b_voff[0] | rowbad, so, 0);
                 else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) rb[i][e] = fx_buffer_load_f32(rB, b_voff[e] | rowbad, FX_SO(so), 0);
+                    for (int e = 0; e < 4; ++e) rb[i][e] = fx_buffer_load_f32(rB, b_voff[e] | rowbad, so, 0);
                 }
             }
             if constexpr (MASKED) {        // the factor at the four input pixels: the x offsets without the channel row
@@ -1628,62 +1606,43 @@ bool fx_wgrad_applies(const p3d_conv_desc* d, int min_m) {
     return fx_common(d) && d->K >= min_m && d->C >= min_m && (d->Ho * d->Wo) % FX_BK == 0 && d->Wo % 4 == 0 && d->W % 4 == 0 && (d->R == 1 || d->C % 64 == 0);
 }
 
-// tuning aid (p3d_fx_tune): forced split counts, 0 = the built-in plan
+// p3d_fx_tune(0 / 1 / 2, n): forced split counts (weight gradient, forward / data gradient) and a forced weight-gradient block target; 0 = the built-in plan
 static int g_force_conv_splits = 0, g_force_wgrad_splits = 0, g_wgrad_target = 0;
-// image-fed forward / data gradient on v_mfma_f32_16x16x32_bf16 (fx16_conv_kernel): -1 = environment (P3D_FX16), 0 never, 1 (default) where its 64- and 96-row
-// channel tiles fit the layer better than 128 rows, 2 everywhere (the A/B of the two MFMA shapes: profiles/r04_fx16.md -- at 128 rows the 16x16x32 form is 1-3 %
-// SLOWER on the large layers, 20 fragment reads per step against 12, and the chip holds no higher clock on it in these kernels)
-// image-fed multi-tap launches with at least this many reduction channels walk the taps innermost (0: never; p3d_fx_tune(10, v)).  Measured (tools/r04/r4_i.sh): the
+// image-fed multi-tap launches with at least this many reduction channels walk the taps innermost.  Measured (profiles/r04_summary.md section 4): the
 // regressor's forward (2048 channels x 9 taps) fetches 5.5x fewer bytes beyond L2 and runs 2 % faster; the 512-channel 3x3 layers fetch 3.1x fewer but run 2 % slower
-// (a tap change per K step costs more than their re-reads out of the Infinity Cache): 1024 takes the first and leaves the second
-static int g_tap_inner_min = [] { const char* e = getenv("P3D_TAP_INNER_MIN"); return e ? atoi(e) : 1024; }();      // (environment: A/B in the step)
-static int g_two_taps = 1;             // image-fed weight gradients of 64-input-channel multi-tap layers: two / three taps per column tile; p3d_fx_tune(9, 0): off, (9, 2): never three (A/B)
-static int g_conv_order = -1, g_wgrad_order = -1;      // -1: the built-in choice (fx_conv_order / fx_wgrad_order); 0 / 1 forced (p3d_fx_tune(7 / 8, v): A/B)
-// Which operand should the blocks an XCD runs at one time share?  An XCD's L2 holds 4 MB.  With the channel tile fastest an activation tile is fetched once and every
-// pixel tile streams the WHOLE weight image past the L2 (fine while that image stays in it); with the pixel tile fastest the ~96 resident blocks stream one
-// channel tile's weights together and each its own pixels.  Measured (profiles/r04_summary.md section 4): layer4 and the regressor fetched 3.7 - 28 x their algorithmic bytes.
-// MEASURED (tools/r04/r4_g.sh, profiles/r04_summary.md section 4): the pixel-tile-fastest order is 1 - 46 % SLOWER on every shape, layer4 and the regressor included (forward
-// 0.896 vs 0.845 ms): the bytes FETCH_SIZE counts beyond L2 come out of the 256 MB Infinity Cache at a rate these matrix-pipe-bound kernels do not feel, while losing
-// the shared activation tile costs L2 hits they do.  So the built-in choice stays 0 everywhere; the switches remain for the record (p3d_fx_tune(7 / 8, 1)).
-static int fx_conv_order(size_t wimg_bytes, int tiles_m, int tiles_n) {
-    (void)wimg_bytes; (void)tiles_m; (void)tiles_n;
-    return g_conv_order > 0 ? 1 : 0;
-}
+// (a tap change per K step costs more than their re-reads out of the Infinity Cache): 1024 takes the first and leaves the second.  The data gradient uses the same
+// threshold (its own at 512 / 256: 28.418 ms against 28.430, nothing; section 8b)
+constexpr int FX_TAP_INNER_MIN = 1024;
+// Block order of fx_conv_kernel / fx16_conv_kernel inside an XCD's run of logical ids: channel tile fastest, so that consecutive blocks share an activation tile and
+// every pixel tile streams the whole weight image past the L2.  The other order (pixel tile fastest: the ~96 resident blocks stream one channel tile's weights
+// together) was MEASURED (profiles/r04_summary.md section 4) 1 - 46 % SLOWER on every shape, layer4 and the regressor included (forward 0.896 vs 0.845 ms): the
+// bytes FETCH_SIZE counts beyond L2 (3.7 - 28 x the algorithmic bytes there) come out of the 256 MB Infinity Cache at a rate these matrix-pipe-bound kernels do not
+// feel, while losing the shared activation tile costs L2 hits they do.
 // The weight gradient of a WIDE multi-tap layer (>= 512 input channels) takes the tap-fastest order: the nine tap blocks of one (x tile, dy tile) pair then run side by side on
 // one XCD and the shifted views of the x tile are fetched once instead of once per tap -- FETCH_SIZE per launch 2.20 -> 0.80 GB for the 2048 -> 272 regressor, 254 -> 147 MB for
-// the 512 -> 512 3x3, at unchanged time (0.980 / 0.978 ms, 0.398 / 0.396; tools/r04/r4_w.sh).  Narrower layers keep order 0 (no traffic to win, +-2 % either way).
-static int fx_wgrad_order(const p3d_conv_desc* d) {
-    static const int env = [] { const char* e = getenv("P3D_WGRAD_ORDER"); return e ? atoi(e) : -1; }();      // 0 / 1: forced (A/B from the environment)
-    const int forced = g_wgrad_order >= 0 ? g_wgrad_order : env;
-    if (forced >= 0) return forced > 0 ? 1 : 0;
-    return (d->R * d->S > 1 && d->C >= 512) ? 1 : 0;
-}
-static int g_class_launches = 0;      // 1: one launch per parity class of a strided data gradient (the round-3 form; p3d_fx_tune(5, 1), A/B and tests)
-static int g_fx16 = -1;
-static int fx16_mode() {
-    if (g_fx16 < 0) { const char* e = getenv("P3D_FX16"); g_fx16 = e ? atoi(e) : 1; if (g_fx16 < 0 || g_fx16 > 2) g_fx16 = 1; }
-    return g_fx16;
-}
-// channel tile of the fx16 kernel for a launch (0: the launch stays on fx_conv_kernel): 16 x 16 sub-tiles allow 96- and 64-row tiles where 128 rows would be
-// mostly padding (the 272-channel regressor: 3 x 96 = 288 rows instead of 384; 64-channel layers: all four waves live)
+// the 512 -> 512 3x3, at unchanged time (0.980 / 0.978 ms, 0.398 / 0.396; profiles/r04_summary.md section 4).  Narrower layers keep order 0 (no traffic to win, +-2 % either way).
+static int fx_wgrad_order(const p3d_conv_desc* d) { return (d->R * d->S > 1 && d->C >= 512) ? 1 : 0; }
+static int g_class_launches = 0;      // 1: one launch per parity class of a strided data gradient (the round-3 form; p3d_fx_tune(5, 1), tests)
+// channel tile of the fx16 kernel (v_mfma_f32_16x16x32_bf16) for a launch (0: the launch stays on fx_conv_kernel): 16 x 16 sub-tiles allow 96- and 64-row tiles where
+// 128 rows would be mostly padding (the 272-channel regressor: 3 x 96 = 288 rows instead of 384; 64-channel layers: all four waves live).  At 128 rows the 16x16x32
+// form is 1-3 % SLOWER on the large layers (20 fragment reads per step against 12, and the chip holds no higher clock on it in these kernels: profiles/r04_summary.md
+// section 1), so those stay on the 32x32x16 kernel.
 static int fx16_bm(int M, bool img, int pro, int epi) {
-    const int mode = fx16_mode();
     if (epi == 5 || epi == 6 || epi == 7) epi = epi == 7 ? 0 : epi - 4;      // the masked epilogues run on the base instance with the factor pointer set
     if (epi == 8) epi = 0;                                                     // (inference: EPI 0's tiles)
-    if (!img || pro != 0 || (epi != 0 && epi != 1 && epi != 2) || mode == 0) return 0;
+    if (!img || pro != 0 || (epi != 0 && epi != 1 && epi != 2)) return 0;
     if (M <= 64) return 64;
-    if (ceil_div(M, 96) * 96 < ceil_div(M, 128) * 128) return 96;
-    return mode == 2 ? 128 : 0;
+    return ceil_div(M, 96) * 96 < ceil_div(M, 128) * 128 ? 96 : 0;
 }
 void fx_tune(int what, int value) {
-    if (what == 3) { g_pair_map = value; return; }      // 0: the two opening image passes of a downsample block as two launches (A/B, tests)
-    if (what == 5) { g_class_launches = value ? 1 : 0; return; }
-    if (what == 9) { g_two_taps = value < 0 ? 1 : value; return; }
-    if (what == 10) { g_tap_inner_min = value; return; }
-    if (what == 7) { g_conv_order = value; return; }
-    if (what == 8) { g_wgrad_order = value; return; }
-    if (what == 4) { g_fx16 = value < 0 || value > 2 ? 1 : value; return; }  // A/B of the two MFMA shapes in one process
-    (what == 0 ? g_force_wgrad_splits : what == 1 ? g_force_conv_splits : g_wgrad_target) = value;
+    switch (what) {
+        case 0: g_force_wgrad_splits = value; break;
+        case 1: g_force_conv_splits = value; break;
+        case 2: g_wgrad_target = value; break;
+        case 3: g_pair_map = value; break;                   // 0: the two opening image passes of a downsample block as two launches (tests)
+        case 5: g_class_launches = value ? 1 : 0; break;
+        default: break;                                      // (unknown code: ignored)
+    }
 }
 
 struct FxSplit { int splits, kchunk; };
@@ -1692,8 +1651,8 @@ static FxSplit fx_plan_split(int64_t tiles, int nk) {
     int64_t want;
     if (g_force_conv_splits > 0) want = g_force_conv_splits < nk ? g_force_conv_splits : nk;
     else {
-        static const int target = [] { const char* e = getenv("P3D_SPLITK_BLOCKS"); const int v = e ? atoi(e) : -1; return v >= 0 ? v : 768; }();      // (tuning aid; 0: never split)
-        if (tiles > 400 || nk < 64 || target == 0) return s;
+        constexpr int target = 768;      // blocks aimed at; 0 - 1024 swept in the step without a gain (profiles/r04_summary.md section 8b)
+        if (tiles > 400 || nk < 64) return s;
         want = ceil_div(target, tiles);
         if (want > nk / 32) want = nk / 32;
         if (want > 8) want = 8;
@@ -1918,10 +1877,9 @@ static void fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi,
     }
     // (the fx16 kernel applies p.emask at run time: the masked epilogues 5 / 6 / 7 are its 1 / 2 / 0 with the factor pointer set)
 #define P3D_FX16_CASE(BM, EPI) if (bm == BM && (epi == EPI || epi == (EPI == 0 ? 7 : EPI + 4))) { hipLaunchKernelGGL((fx16_conv_kernel<BM, EPI>), grid, dim3(256), 0, st, p); return; }
-    P3D_FX16_CASE(128, 0) P3D_FX16_CASE(128, 1) P3D_FX16_CASE(128, 2)
     P3D_FX16_CASE(96, 0) P3D_FX16_CASE(96, 1) P3D_FX16_CASE(96, 2)
     P3D_FX16_CASE(64, 0) P3D_FX16_CASE(64, 1) P3D_FX16_CASE(64, 2)
-    P3D_FX16_CASE(128, 8) P3D_FX16_CASE(96, 8) P3D_FX16_CASE(64, 8)
+    P3D_FX16_CASE(96, 8) P3D_FX16_CASE(64, 8)
 #undef P3D_FX16_CASE
 #define P3D_FX_CASE(AM, PRO, EPI) if (am == AM && pro == PRO && epi == EPI) { hipLaunchKernelGGL((fx_conv_kernel<AM, PRO, EPI>), grid, dim3(256), 0, st, p); return; }
     P3D_FX_CASE(0, 0, 0) P3D_FX_CASE(0, 0, 1) P3D_FX_CASE(0, 0, 2) P3D_FX_CASE(0, 4, 0) P3D_FX_CASE(0, 4, 4) P3D_FX_CASE(0, 4, 5)
@@ -1988,8 +1946,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     const FxSplit sp = fx_fwd_split(d);
     const int bm = fx16_bm(d->K, img, sp.splits > 1 ? 0 : pro, sp.splits > 1 ? 0 : epi);
     p.tiles_m = (int)ceil_div(d->K, bm ? bm : FX_BM);
-    p.order = fx_conv_order(fx_weight_image_bytes(d->K, d->C, RS, false), p.tiles_m, tiles_n);
-    p.tap_inner = img && RS > 1 && g_tap_inner_min > 0 && d->C >= g_tap_inner_min;
+    p.tap_inner = img && RS > 1 && d->C >= FX_TAP_INNER_MIN;
     if (sp.splits > 1) {
         p.kchunk = sp.kchunk; p.slab_stride = (size_t)d->N * d->K * d->Ho * d->Wo; p.Y = (float*)ws; p.bias = nullptr;
         const float* em = p.emask;
@@ -2042,9 +1999,7 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
         if (masked) { pro = img ? 0 : 4; epi = fuse->partial ? 6 : (img ? 7 : 4); p.pmask = fuse->pmask; p.emask = fuse->emask; }
     }
     const bool dsplit = d->stride == 1 && fx_dgrad_split(d).splits > 1;
-    static const int tap_inner_bwd = [] { const char* e = getenv("P3D_TAP_INNER_MIN_BWD"); return e ? atoi(e) : -1; }();      // (environment: the data gradient's own threshold, A/B in the step)
-    const int ti_min = tap_inner_bwd >= 0 ? tap_inner_bwd : g_tap_inner_min;
-    p.tap_inner = img && RS > 1 && ti_min > 0 && d->K >= ti_min;
+    p.tap_inner = img && RS > 1 && d->K >= FX_TAP_INNER_MIN;
     if (fuse && fuse->tail_c) {
         if (!(img && epi == 0 && pro == 0 && fx_dgrad_tail_applies(d) && fuse->tail_tab && fuse->tail_partial && (!fuse->tail_rc || fuse->tail_rtab))) {
             set_error("fx_conv_dgrad: the tail sums need an image-fed, dense, unsplit stride-1 data gradient without a BatchNorm epilogue (fx_dgrad_tail_applies)"); return P3D_EINVAL;
@@ -2060,7 +2015,6 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
         p.hmul = 1; p.hoff = d->pad; p.hstep = -d->dil; p.wmul = 1; p.woff = d->pad; p.wstep = -d->dil;
         const int tiles_n = (int)ceil_div(p.NP, FX_BN);
         const FxSplit sp = fx_dgrad_split(d);
-        p.order = fx_conv_order(fx_weight_image_bytes(d->K, d->C, RS, true), p.tiles_m, tiles_n);
         if (sp.splits > 1) {
             p.kchunk = sp.kchunk; p.slab_stride = (size_t)d->N * d->C * d->H * d->W; p.Y = (float*)ws;
             const float* em = p.emask;
@@ -2144,29 +2098,26 @@ bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d) { return d->stride
 // image-fed weight gradients of 64-input-channel multi-tap layers pack two taps into a column tile (fx_wgrad_kernel<.., TAPS 2>)
 // (returns the taps per column tile: 0 = the ordinary one-tap tiles, 2, or 3 when the output channels fit half an A image too)
 int fx_wgrad_two_taps(const p3d_conv_desc* d, bool images) {
-    static const int env = [] { const char* e = getenv("P3D_TWO_TAPS"); return e ? atoi(e) : 1; }();      // P3D_TWO_TAPS=0: one tap, =2: never three (A/B from the environment)
-    if (!g_two_taps || !env || !images || d->C != 64 || d->R * d->S <= 1 || (d->Wo & 15)) return 0;
-    return (g_two_taps == 1 && env == 1 && d->K <= 64) ? 3 : 2;
+    if (!images || d->C != 64 || d->R * d->S <= 1 || (d->Wo & 15)) return 0;
+    return d->K <= 64 ? 3 : 2;
 }
 int fx_wgrad_splits(const p3d_conv_desc* d, bool images) {
     const int tt = fx_wgrad_two_taps(d, images);
     const int64_t tiles = tt ? ceil_div(d->K, FX_BM) * ceil_div(d->R * d->S, tt) : ceil_div(d->K, FX_BM) * ceil_div(d->C, FX_BN) * d->R * d->S;
     const int64_t total = (int64_t)d->N * (d->Ho * d->Wo / FX_BK);
     int64_t target;
-    if (g_wgrad_target > 0) target = g_wgrad_target;          // (tuning aid: p3d_fx_tune, tools/split_sweep.py)
+    if (g_wgrad_target > 0) target = g_wgrad_target;          // (tuning aid: p3d_fx_tune(2, n), tools/split_sweep.py)
     else if (tiles >= 256) target = 1536;
     else switch ((int)tiles) {
         case 2: target = 384; break;
         case 4: target = 640; break;
-        case 5: target = 512; break;          // (two-tap column tiles of a 64 -> 64 3x3: tools/r04/r4_i.sh)
+        case 5: target = 512; break;          // (two-tap column tiles of a 64 -> 64 3x3: profiles/r04_summary.md section 6)
         case 8: case 32: case 36: target = 512; break;
         case 16: target = 256; break;
         case 128: target = 1024; break;
         case 144: target = 720; break;
         default: target = 768;              // (1, 9, 64 tiles; anything the sweep has not seen)
     }
-    static const int scale = [] { const char* e = getenv("P3D_WGRAD_SCALE"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 100; }();      // percent of the plan's block count (tuning aid)
-    target = target * scale / 100;
     int64_t splits = (2 * target + tiles) / (2 * tiles);                 // nearest
     if (splits > total / 32) splits = total / 32;                        // at least 32 K steps per block
     if (g_force_wgrad_splits > 0) splits = g_force_wgrad_splits < total ? g_force_wgrad_splits : total;
@@ -2342,7 +2293,7 @@ bool fx_stem_masked_applies(int K) { return fx16_bm(K, true, 0, 0) != 0; }      
 int32_t fx_stem_fwd(const void* x_img, const void* wimg, float* y, const float* mult, int N, int H, int W, int K, hipStream_t st) {
     FxConvParams p = fx_stem_params(N, H, W, K);
     if (mult) {
-        if (!fx_stem_masked_applies(K)) { set_error("fx_stem_fwd: the output factor needs the fx16 kernel (K <= 64 or a 96-row fit, P3D_FX16 != 0)"); return P3D_EINVAL; }
+        if (!fx_stem_masked_applies(K)) { set_error("fx_stem_fwd: the output factor needs the fx16 kernel (K <= 64 or a 96-row fit)"); return P3D_EINVAL; }
         p.emask = mult;
     }
     p.Ximg = (const unsigned char*)x_img; p.plane_bytes = (size_t)N * (H / 2) * (W / 2) * 32;

@@ -58,9 +58,9 @@ struct HGatherParams {
 // output and constants as hbn_bwd_reduce_kernel does).  EPI 2 / 3 need one pixel class (every block owns a full row of the partial table).
 // EPI 4: inference with a folded BatchNorm, y = fp16(relu?(acc * dscale + bias + res)) rounded once: the fp32 accumulators go through LDS in two passes of 64 channels
 // (EPI 1's 34 KB staging tile in the operand buffers holds 128 pixels x 64 fp32 channels), so the residual is read and the result written in 16-B runs.
-// PIPE: the K step in the order of the fp32 path's kernels -- the registers fetched during the previous step go to LDS behind the step's first MFMAs, then the loads of
+// The K step runs in the order of the fp32 path's kernels -- the registers fetched during the previous step go to LDS behind the step's first MFMAs, then the loads of
 // the step after next are issued, then the rest of the MFMAs run: a fetch has a whole step to arrive and the LDS stores complete under MFMAs instead of in front of the barrier.
-template <int BK, int EPI, bool PIPE>
+template <int BK, int EPI>
 __global__ __launch_bounds__(256) void hconv_gather_kernel(HGatherParams p) {
     constexpr int BM = 128, BN = 128;
     constexpr int CH = BK / 8;                 // 16-B chunks per tile row
@@ -157,16 +157,15 @@ __global__ __launch_bounds__(256) void hconv_gather_kernel(HGatherParams p) {
     // four SIMDs for this block -- would multiply zeros.  Narrow layout: every wave takes 32 of the 64 live rows (one row sub-tile) and its 64 columns.
     const bool narrow = p.M <= 64;
     const int rbase = narrow ? wm * 32 : wm * 64, na = narrow ? 1 : 2;
-    if (nk > 0) { fetch(); stage(0); if (PIPE && nk > 1) fetch(); }
+    if (nk > 0) { fetch(); stage(0); if (nk > 1) fetch(); }
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
-        if (!PIPE && kt + 1 < nk) fetch();
         const unsigned char* a_rd = As + (size_t)(buf * BM + rbase + fr) * ROWB + fh * 16;
         const unsigned char* b_rd = Bs + (size_t)(buf * BN + wn * 64 + fr) * ROWB + fh * 16;
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
-            if (PIPE && ks == 1) {
+            if (ks == 1) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (kt + 1 < nk) stage(buf ^ 1);
                 if (kt + 2 < nk) fetch();
@@ -185,7 +184,6 @@ __global__ __launch_bounds__(256) void hconv_gather_kernel(HGatherParams p) {
                     for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[a], bf[b], acc[a][b], 0, 0, 0);
                 }
         }
-        if (!PIPE && kt + 1 < nk) stage(buf ^ 1);
         __syncthreads();
     }
 
@@ -384,7 +382,6 @@ struct HWgradParams {
     int N, C, H, W, K, R, S, stride, pad, dil, Ho, Wo;
     int kchunk;               // pixels per split (multiple of 32)
     int tiles_m;
-    int tap_fast;             // column tiles walked tap-fastest (C % 128 == 0): the taps of one 128-channel chunk of x side by side (the fp32 path's fx_wgrad_order)
 };
 
 // byte offset of 16-B chunk `ch` (0..15) of row `row` in a [rows][128 halves] image that serves ds_read_b64_tr_b16 without
@@ -400,9 +397,7 @@ __global__ __launch_bounds__(256) void hconv_wgrad_kernel(HWgradParams p) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_m = bid % p.tiles_m;
-    int tile_n = bid / p.tiles_m;
-    if (p.tap_fast) { const int rs = p.R * p.S, tp = tile_n % rs, ct = tile_n / rs; tile_n = tp * (p.C >> 7) + ct; }
+    const int tile_m = bid % p.tiles_m, tile_n = bid / p.tiles_m;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int RSC = p.R * p.S * p.C, C8 = p.C >> 3, HoWo = p.Ho * p.Wo;
     const int ktot = p.N * HoWo;
@@ -479,7 +474,7 @@ __global__ __launch_bounds__(256) void hconv_wgrad_kernel(HWgradParams p) {
         return __builtin_bit_cast(h8, v);
     };
 
-    // (K step in the order of hconv_gather_kernel<.., PIPE>: the next step's stores and the loads of the step after it between the two halves of the step's MFMAs)
+    // (K step in the order of hconv_gather_kernel: the next step's stores and the loads of the step after it between the two halves of the step's MFMAs)
     if (nk > 0) { fetch(0); stage(0); if (nk > 1) fetch(1); }
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
@@ -704,13 +699,11 @@ static int32_t hvalidate(const p3d_conv_desc* d, const char* what) {
 
 // epi: 0 plain, 2 + BatchNorm statistics, 3 + BatchNorm-backward sums (p.partial etc. set), 4 inference epilogue (bias, residual, ReLU); a plain launch without
 // bias / factor / accumulate stores through LDS (EPI 1)
-static bool g_hstage = [] { const char* e = getenv("P3D_HALF_STAGED_STORE"); return !(e && atoi(e) == 0); }();      // P3D_HALF_STAGED_STORE=0: A/B
 static void launch_gather(const HGatherParams& p, int ncls, int max_cols, hipStream_t st, int epi = 0) {
     const int tiles_n = (int)ceil_div(max_cols, 128);
     dim3 grid((unsigned)(p.tiles_m * tiles_n), (unsigned)ncls);
-    static const bool pipe = [] { const char* e = getenv("P3D_HALF_PIPE"); return !(e && atoi(e) == 0); }();      // P3D_HALF_PIPE=0: A/B
-    const int e = epi >= 2 ? epi : (g_hstage && !p.bias && !(p.dscale && p.accumulate)) ? 1 : 0;      // (bias, and a factor on an accumulating launch, keep the single rounding of EPI 0)
-#define P3D_HG_CASE(E) if (e == E) { if (pipe) hipLaunchKernelGGL((hconv_gather_kernel<32, E, true>), grid, dim3(256), 0, st, p); else hipLaunchKernelGGL((hconv_gather_kernel<32, E, false>), grid, dim3(256), 0, st, p); return; }
+    const int e = epi >= 2 ? epi : (!p.bias && !(p.dscale && p.accumulate)) ? 1 : 0;      // (bias, and a factor on an accumulating launch, keep the single rounding of EPI 0)
+#define P3D_HG_CASE(E) if (e == E) { hipLaunchKernelGGL((hconv_gather_kernel<32, E>), grid, dim3(256), 0, st, p); return; }
     P3D_HG_CASE(0) P3D_HG_CASE(1) P3D_HG_CASE(2) P3D_HG_CASE(3) P3D_HG_CASE(4)
 #undef P3D_HG_CASE
 }
@@ -830,10 +823,10 @@ int32_t p3d_hconv2d_dgrad_sums(const p3d_conv_desc* d, const void* dy, const voi
 static void hwgrad_plan(const p3d_conv_desc* d, int* splits, int* kchunk) {
     const int64_t tiles = ceil_div(d->K, 128) * ceil_div((int64_t)d->R * d->S * d->C, 128);
     const int64_t ktot = (int64_t)d->N * d->Ho * d->Wo;
-    // blocks aimed at per layer.  Measured in the two-stream step (tools/r04/r4_n.sh, -half_acc ResNet-50 batch 64): 1536 -> 15.22 ms, 1024 -> 15.05, 768 -> 14.81, 512 -> 14.71,
+    // blocks aimed at per layer.  Measured in the two-stream step (profiles/r04_summary.md section 8, -half_acc ResNet-50 batch 64): 1536 -> 15.22 ms, 1024 -> 15.05, 768 -> 14.81, 512 -> 14.71,
     // 384 -> 14.64, 256 -> 15.26: every slab is 4 B per weight written and read again beside the launch stream's memory-bound passes, so the best count in the step is well
-    // below the one that fills the chip for the kernel alone (P3D_HWGRAD_BLOCKS: tuning aid)
-    static const int target = [] { const char* e = getenv("P3D_HWGRAD_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 384; }();
+    // below the one that fills the chip for the kernel alone
+    constexpr int target = 384;
     int64_t s = ceil_div(target, tiles);
     const int64_t smax = ceil_div(ktot, 32 * 8);
     if (s > smax) s = smax;
@@ -870,9 +863,8 @@ int32_t p3d_hconv2d_wgrad(const p3d_conv_desc* d, const void* dy, const void* x,
     p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.Ho = d->Ho; p.Wo = d->Wo;
     p.kchunk = kchunk;
     p.tiles_m = (int)ceil_div(d->K, 128);
-    // (P3D_HWGRAD_TAP_FAST=1: measured in the fp16 step -- 14.10 / 14.12 / 14.14 ms against 14.13 / 14.11 / 14.12, no difference, unlike the fp32 path's 6-B images -- so off)
-    static const int tap_fast_env = [] { const char* e = getenv("P3D_HWGRAD_TAP_FAST"); return e ? atoi(e) : 0; }();
-    p.tap_fast = (tap_fast_env > 0 && d->R * d->S > 1 && d->C % 128 == 0) ? 1 : 0;
+    // (column tiles stay channel-fastest: tap-fastest measured 14.10 / 14.12 / 14.14 ms against 14.13 / 14.11 / 14.12 in the fp16 step, no difference, unlike the fp32
+    // path's 6-B images -- profiles/r04_summary.md section 8b)
     const int tiles_n = (int)ceil_div((int64_t)d->R * d->S * d->C, 128);
     hipLaunchKernelGGL(hconv_wgrad_kernel, dim3((unsigned)(p.tiles_m * tiles_n), (unsigned)splits), dim3(256), 0, (hipStream_t)stream, p);
     if (int32_t e = check_launch("hconv2d_wgrad")) return e;

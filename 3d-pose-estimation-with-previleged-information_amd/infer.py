@@ -405,7 +405,7 @@ class FoldedNet(_Folded):
         (relu(maxpool(c mult) + b') = maxpool(relu(c mult + b')): both monotone per channel).  Returns (y, max-pooled mask_out)."""
         n, cin, h, w = x.shape
         L = lib()
-        if not (s.foldable and ops_block.MASKED_STEM and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_masked_supported(n, cin, h, w, s.k)
+        if not (s.foldable and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_masked_supported(n, cin, h, w, s.k)
                 and (h // 2) % 2 == 0 and (w // 2) % 4 == 0):
             from ._trunk import stem_tail
             c, veil = s.conv(x, veil)                       # today's path (odd sides: the reference's default -side_in 257)

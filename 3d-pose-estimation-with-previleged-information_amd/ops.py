@@ -75,9 +75,9 @@ def workspace(device, nbytes):
 # join_side_stream() orders the launch stream after everything issued there (before an all-reduce / the optimizer reads .grad).
 WGRAD_STREAM = os.environ.get('P3D_WGRAD_STREAM', '1') != '0'
 # -half_acc: the weight gradient of a network's FIRST layer (no data gradient behind it) is the last kernel of the backward pass: queued on the second stream it waits
-# behind the weight gradients still pending there while the launch stream has nothing left to do; on the launch stream it runs beside them (tools/r04/r4_t.sh: 14.04 / 14.03 ms
-# against 14.09 / 14.11; P3D_LAST_WGRAD_MAIN=0: A/B).  The fp32 step measured no difference (28.17 / 28.11 / 28.10 against 28.29 / 28.05 / 27.99) and keeps the second stream.
-LAST_WGRAD_ON_LAUNCH = os.environ.get('P3D_LAST_WGRAD_MAIN', '1') != '0'
+# behind the weight gradients still pending there while the launch stream has nothing left to do; on the launch stream it runs beside them (14.04 / 14.03 ms against
+# 14.09 / 14.11; ops_half's weight-gradient launch).  The fp32 step measured no difference (28.17 / 28.11 / 28.10 against 28.29 / 28.05 / 27.99; profiles/r04_summary.md
+# section 8b) and keeps the second stream.
 _side_streams = {}
 _side_workspaces = {}
 
@@ -94,8 +94,7 @@ def _second_workspace(device, nbytes):
     return ws
 
 
-SIDE_STREAM_KIND = os.environ.get('P3D_SIDE_STREAM', 'probe')       # probe | torch (a stream from PyTorch's pool) | low | normal | high (a fixed priority class)
-SIDE_STREAM_OVERLAPS = {}                                              # device -> what the probe found (None: not probed)
+SIDE_STREAM_OVERLAPS = {}                                              # device -> what the probe found
 
 
 def cu_mask_words(spec, total=256):
@@ -121,9 +120,6 @@ def masked_stream(device, spec):
     return torch.cuda.ExternalStream(handle.value, device=device)
 
 
-SIDE_STREAM_CUS = os.environ.get('P3D_SIDE_CUS', '')                  # e.g. '192': the weight-gradient stream may use 192 of the 256 compute units
-
-
 def _side_stream(device):
     """The weight-gradient stream.  HIP multiplexes the streams of one priority onto four hardware queues: a stream taken from PyTorch's pool landed on
     the launch stream's own queue whenever an RCCL communicator had been created first (rocprofv3: every kernel of the step on one queue), which costs
@@ -131,21 +127,11 @@ def _side_stream(device):
     p3d_stream_create_beside creates candidates until two spin kernels, one per stream, demonstrably run side by side."""
     st = _side_streams.get(device)
     if st is None:
-        if SIDE_STREAM_CUS:
-            st = masked_stream(device, SIDE_STREAM_CUS)
-            SIDE_STREAM_OVERLAPS[device] = None
-        elif SIDE_STREAM_KIND == 'torch':
-            st = torch.cuda.Stream(device=device)
-            SIDE_STREAM_OVERLAPS[device] = None
-        else:
-            handle, found = ctypes.c_void_p(), ctypes.c_int32(-1)
-            with torch.cuda.device(device):
-                if SIDE_STREAM_KIND == 'probe':
-                    check(lib().p3d_stream_create_beside(ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream), ctypes.byref(handle), ctypes.byref(found)), 'stream_create_beside')
-                else:
-                    check(lib().p3d_stream_create({'low': 1, 'normal': 0, 'high': -1}[SIDE_STREAM_KIND], ctypes.byref(handle)), 'stream_create')
-            st = torch.cuda.ExternalStream(handle.value, device=device)
-            SIDE_STREAM_OVERLAPS[device] = None if found.value < 0 else bool(found.value)
+        handle, found = ctypes.c_void_p(), ctypes.c_int32(0)
+        with torch.cuda.device(device):
+            check(lib().p3d_stream_create_beside(ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream), ctypes.byref(handle), ctypes.byref(found)), 'stream_create_beside')
+        st = torch.cuda.ExternalStream(handle.value, device=device)
+        SIDE_STREAM_OVERLAPS[device] = bool(found.value)
         _side_streams[device] = st
     return st
 
@@ -623,11 +609,8 @@ class StemTailFn(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, None, None
 
 
-STEM_TAIL = os.environ.get('P3D_STEM_TAIL', '1') != '0'        # A/B switch: 0 = BatchNorm + ReLU and the max pool of the stem as two nodes
-
-
 def stem_tail_usable(x, bn, pool):
-    if not (STEM_TAIL and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and bn.training and bn.affine and bn.track_running_stats and torch.is_grad_enabled()):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and bn.training and bn.affine and bn.track_running_stats and torch.is_grad_enabled()):
         return False
     one = lambda v: v[0] if isinstance(v, (tuple, list)) else v
     if (one(pool.kernel_size), one(pool.stride), one(pool.padding), one(pool.dilation)) != (3, 2, 1, 1) or pool.ceil_mode:

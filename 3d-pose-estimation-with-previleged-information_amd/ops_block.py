@@ -259,33 +259,11 @@ def _rebuild_stale_images(device):
         c.__dict__['_fx_images'] = (_image_key(c.weight), fwd, bwd)
 
 
-# P3D_IMAGES_EARLY=1: the optimizer step queues the rebuild of every weight image on the second stream right behind the Adam kernel, so that it runs beside the next
-# step's stem (whose own small image is not part of the batch) instead of on the launch stream in front of the first residual block.
-IMAGES_EARLY = os.environ.get('P3D_IMAGES_EARLY', '0') == '1'
-_images_event = {}
-
-
-def rebuild_images_early(device):
-    if not (IMAGES_EARLY and ops.WGRAD_STREAM and USE_WEIGHT_IMAGES) or torch.cuda.is_current_stream_capturing():
-        return
-    side = ops._side_stream(device)
-    side.wait_stream(torch.cuda.current_stream(device))            # the optimizer's kernels
-    with torch.cuda.stream(side):
-        _rebuild_stale_images(device)
-    ev = torch.cuda.Event()
-    ev.record(side)
-    _images_event[device] = ev
-
-
 def weight_images(conv):
     """(forward image, data-gradient image) of conv.weight as device byte tensors (p3d_fx_weight_images*), rebuilt when the weight has changed:
     in-place edits through torch bump weight._version; writes behind torch's back (the optimizer kernels, broadcasts into the flat buffer) bump ops.WEIGHT_EPOCH."""
     import weakref
     w = conv.weight
-    if _images_event:
-        ev = _images_event.pop(w.device, None)
-        if ev is not None:
-            torch.cuda.current_stream(w.device).wait_event(ev)
     cached = conv.__dict__.get('_fx_images')
     if cached is not None and cached[0] == _image_key(w):
         return cached[1], cached[2]
@@ -305,9 +283,6 @@ def weight_images(conv):
     _rebuild_stale_images(w.device)
     cached = conv.__dict__['_fx_images']
     return cached[1], cached[2]
-
-
-USE_WEIGHT_IMAGES = os.environ.get('P3D_WEIGHT_IMAGES', '1') != '0'
 
 
 PLAN_LIMIT = 3
@@ -374,15 +349,11 @@ def plan_for(block, x, masked=False):
     return plan
 
 
-# P3D_MASKED_BLOCKS=0: the partial-convolution blocks of the partial families stay on the per-layer path (one autograd node per conv / BatchNorm; A/B)
-MASKED_BLOCKS = os.environ.get('P3D_MASKED_BLOCKS', '1') != '0'
-
-
 def usable(block, x, veil=None):
     """The fused executor takes this call: fp32 block on the GPU, every BatchNorm computing batch statistics, supported shapes; dense, or (veil given) with
     partial convolutions in its main chain (partial_depthnet.py:62-75,140-157; the downsample branch is a dense conv there too)."""
     masked = veil is not None
-    if bool(block.partial) != masked or x.dtype != torch.float32 or not x.is_cuda or (masked and not MASKED_BLOCKS):
+    if bool(block.partial) != masked or x.dtype != torch.float32 or not x.is_cuda:
         return False
     if masked and not (veil.is_cuda and veil.dtype == torch.float32 and veil.dim() == 4 and veil.shape[1] == 1 and veil.shape[0] == x.shape[0] and veil.shape[2:] == x.shape[2:]):
         return False
@@ -431,8 +402,7 @@ class ResidualBlockFn(torch.autograd.Function):
         ctx.pix = pix
         for slot, conv, bn in layers:
             io.w[slot], io.c[slot] = conv.weight.data_ptr(), cs[slot].data_ptr()
-            if USE_WEIGHT_IMAGES:
-                io.wimg[slot] = weight_images(conv)[0].data_ptr()
+            io.wimg[slot] = weight_images(conv)[0].data_ptr()
             if slot in acts:
                 io.aimg[slot] = acts[slot].data_ptr()
             io.table[slot] = tables.data_ptr() + row * 32
@@ -513,8 +483,7 @@ class ResidualBlockFn(torch.autograd.Function):
         row = 0
         for slot, conv, bn in layers:
             io.w[slot], io.c[slot] = conv.weight.data_ptr(), cs[slot].data_ptr()
-            if USE_WEIGHT_IMAGES:
-                io.wimgT[slot] = weight_images(conv)[1].data_ptr()
+            io.wimgT[slot] = weight_images(conv)[1].data_ptr()
             if slot in acts:
                 io.aimg[slot] = acts[slot].data_ptr()
             io.table[slot] = tables.data_ptr() + row * 32
@@ -585,11 +554,8 @@ def residual_block(block, x, veil=None):
 # Multi-tap and strided convolutions gain most from operands that are split once instead of per channel tile and filter tap (profiles/r03_summary.md:
 # ResNet-50's 2048 -> 272 3x3 regressor 3.33 -> 2.78 ms per step over its three passes, image passes included); plain 1x1 layers do not repay the extra
 # pass, so they stay on ops.conv2d.
-IMAGE_CONVS = os.environ.get('P3D_IMAGE_CONVS', '1') != '0'
-
-
 def conv_takes_images(conv, x):
-    if not (IMAGE_CONVS and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and type(conv).__name__ == 'Conv2d'):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and type(conv).__name__ == 'Conv2d'):
         return False
     k = conv.kernel_size[0]
     if k < 2 or conv.in_channels < 64:
@@ -617,7 +583,7 @@ class ConvImagesFn(torch.autograd.Function):
         ctx.lease = _Lease(bufs)
         x_img = ops.act_image(x, out=bufs.tensor('x', 6 * x.numel()))
         y = torch.empty((d.N, d.K, d.Ho, d.Wo), dtype=torch.float32, device=x.device)
-        wimg = weight_images(conv)[0] if USE_WEIGHT_IMAGES else None
+        wimg = weight_images(conv)[0]
         ws = ops.workspace(x.device, L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 0))
         with ops._Timed('fwd', d):
             check(L.p3d_fx_conv_fwd_img(ctypes.byref(d), ops._p(x_img), ops._p(w), ops._p(wimg), ops._p(bias), ops._p(y), ops._p(ws), ws.numel(), ops._stream()),
@@ -644,7 +610,7 @@ class ConvImagesFn(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dy.device)
-            wimgT = weight_images(conv)[1] if USE_WEIGHT_IMAGES else None
+            wimgT = weight_images(conv)[1]
             ws = ops.workspace(dy.device, L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 1))
             with ops._Timed('dgrad', d):
                 check(L.p3d_fx_conv_dgrad_img(ctypes.byref(d), ops._p(dy_img), ops._p(w), ops._p(wimgT), ops._p(dx), ops._p(ws), ws.numel(), st), 'p3d_fx_conv_dgrad_img')
@@ -688,18 +654,14 @@ def conv2d_images(conv, x):
 # ---- the stem conv1 (7x7, stride 2, Cin = 3 or 1: depthnet.py:138) on the x3 kernels -------------------------------------------------------------------------
 def stem_takes_x3(conv, x, masked=False):
     """conv1 on the restated stem kernels?  masked: as a partial convolution (PartialConv stems of partial_depthnet / partial_fusionnet: per-pixel factors)."""
-    if not (IMAGE_CONVS and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and type(conv).__name__ == ('PartialConv' if masked else 'Conv2d') and conv.bias is None):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and type(conv).__name__ == ('PartialConv' if masked else 'Conv2d') and conv.bias is None):
         return False
     if (conv.kernel_size[0], _one(conv.stride), _one(conv.padding), _one(conv.dilation)) != (7, 2, 3, 1) or conv.in_channels > 4:
         return False
     n, c, h, w = x.shape
     if masked:
-        return MASKED_STEM and bool(lib().p3d_stem_masked_supported(n, c, h, w, conv.out_channels))
+        return bool(lib().p3d_stem_masked_supported(n, c, h, w, conv.out_channels))
     return bool(lib().p3d_stem_supported(n, c, h, w, conv.out_channels))
-
-
-# P3D_MASKED_STEM=0: the 1-channel partial-convolution stems stay on the fp32-MFMA kernel (the round-3 path; A/B)
-MASKED_STEM = os.environ.get('P3D_MASKED_STEM', '1') != '0'
 
 
 def stem_weight_image(conv):

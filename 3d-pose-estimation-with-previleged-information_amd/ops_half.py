@@ -206,7 +206,7 @@ class HConv2dFn(torch.autograd.Function):
             dw = torch.empty(wshape, dtype=torch.float32, device=x.device) if sink is None else sink
             d.accumulate = 0 if sink is None else 1
             nbytes = L.p3d_hconv2d_wgrad_workspace_bytes(ctypes.byref(d))
-            if ops.WGRAD_STREAM and sink is not None and not (ops.LAST_WGRAD_ON_LAUNCH and not ctx.needs_input_grad[0]):
+            if ops.WGRAD_STREAM and sink is not None and ctx.needs_input_grad[0]:      # (a network's first layer stays on the launch stream: see ops.WGRAD_STREAM)
                 side = ops._side_stream(x.device)
                 ops._queue_join()
                 side.wait_stream(torch.cuda.current_stream())
@@ -395,7 +395,6 @@ def relu(x):
 import os as _os
 
 HALF_BLOCKS = _os.environ.get('P3D_HALF_BLOCKS', '1') != '0'
-HALF_MASK = _os.environ.get('P3D_HALF_MASK', '1') != '0'          # the closing ReLU's mask bytes instead of the block output in backward (A/B)
 _vp = ctypes.c_void_p
 
 
@@ -482,12 +481,11 @@ class HResidualBlockFn(torch.autograd.Function):
         # the closing ReLU's mask as one byte per 8 outputs: backward reads it in place of `out` (p3d_hblock_fuse_sums(1); ignored otherwise)
         n, k, ho, wo = plan.out_shape
         out_mask = torch.empty(n * ho * wo * (k // 8), dtype=torch.uint8, device=dev)
-        if HALF_MASK:
-            io.out_mask = out_mask.data_ptr()
+        io.out_mask = out_mask.data_ptr()
         ws = workspace(dev, plan.main_bytes)
         check(lib().p3d_hblock_fwd(ctypes.byref(plan.desc), ctypes.byref(io), _p(ws), ws.numel(), _stream()), 'p3d_hblock_fwd')
         ctx.block, ctx.plan = block, plan
-        ctx.fused = HALF_MASK and bool(lib().p3d_hblock_fuse_sums(-1))
+        ctx.fused = bool(lib().p3d_hblock_fuse_sums(-1))
         ctx.saved = (cs, acts, coefs, out_mask)
         ctx.save_for_backward(x, out)
         return out

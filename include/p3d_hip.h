@@ -34,9 +34,6 @@ extern "C" {
 
 int32_t p3d_version(void);
 const char* p3d_last_error(void);
-/* A HIP stream of a priority class (-1 high, 0 normal, 1 low) on the current device; the weight-gradient stream of the host mirror is a LOW one (its own
- * hardware-queue pool: see csrc/p3d_api.hip).  No reference counterpart: the reference leaves streams to PyTorch. */
-int32_t p3d_stream_create(int32_t priority_class, void** stream);
 /* A second stream that is PROVEN to run beside `main_stream` (two 200-us spin kernels, one per stream, must take ~200 us, not ~400): see csrc/p3d_api.hip.
  * *overlaps = 1 if a candidate passed the probe, 0 if the returned stream shares the main stream's hardware queue after all. */
 int32_t p3d_stream_create_beside(void* main_stream, void** stream, int32_t* overlaps);
@@ -100,7 +97,13 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
  * (three-piece operand split, six piece products, fp32 accumulation; csrc/p3d_fx.hip): fp32-grade results, measured error <= the
  * fp32-MFMA kernel's.  p3d_x3_enable(0) (or P3D_X3=0 in the environment) keeps every layer on the v_mfma_f32_32x32x2_f32 kernels.  Returns the previous setting. */
 int32_t p3d_x3_enable(int32_t on);
-/* Tuning aid of tools/split_sweep.py: force the split count of the x3 weight-gradient (what = 0) or forward / data-gradient (what = 1) launches; value 0 restores the built-in plan. */
+/* Test and tuning hooks of the x3 path; value 0 restores the built-in behaviour unless noted.  Codes:
+ *   0  forced split count of the weight-gradient launches                  (tools/split_sweep.py, tests/test_kernels_gpu.py)
+ *   1  forced split count of the forward / data-gradient launches          (the same)
+ *   2  forced block target of the weight-gradient split plan               (tools/split_sweep.py)
+ *   3  0: the two opening image passes of a downsample block as two launches instead of the pair pass (default 1; tests/test_block_gpu.py)
+ *   5  1: one launch per parity class of a strided data gradient instead of one launch for all (tests/test_geometry_gpu.py)
+ * Any other code is ignored. */
 void p3d_fx_tune(int32_t what, int32_t value);
 /* How many conv launches took which path since the last reset: counts / flops [0..2] = forward, data gradient, weight gradient on the bf16-pipe kernels,
  * [3..5] = the same three on the fp32-MFMA kernels (algorithmic flops 2*N*K*Ho*Wo*C*R*S).  Host-side bookkeeping only. */
@@ -230,7 +233,7 @@ typedef struct p3d_hblock_io {
     void* out_mask;             /* or NULL: P * K_last / 8 bytes written by forward (bit = [out > 0]), read by backward in place of `out` (with p3d_hblock_fuse_sums(1)) */
 } p3d_hblock_io;
 int32_t p3d_hblock_workspace_bytes(const p3d_block_desc* b, size_t* main_bytes, size_t* side_bytes);
-/* BatchNorm sums of the block's layers from the conv epilogues (1, the default; P3D_HALF_FUSED=0 in the environment: 0) or from stand-alone passes (0: bit-identical to
+/* BatchNorm sums of the block's layers from the conv epilogues (1, the default) or from stand-alone passes (0: bit-identical to
  * the per-layer entry points); on < 0 queries.  Returns the previous setting. */
 int32_t p3d_hblock_fuse_sums(int32_t on);
 int32_t p3d_hblock_fwd(const p3d_block_desc* b, const p3d_hblock_io* io, void* workspace, size_t workspace_bytes, void* stream);

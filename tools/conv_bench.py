@@ -44,7 +44,7 @@ def main():
     ap.add_argument('--only', default='')
     ap.add_argument('--mode', default='all', help='all | fwd | dgrad | wgrad')
     ap.add_argument('--img', action='store_true', help='also time the image-fed instances (pre-split activation / gradient images, pre-built weight images: what the block executor launches)')
-    ap.add_argument('--tune', default='', help='p3d_fx_tune settings for this run, e.g. "7=1,8=0" (7: conv block order, 8: wgrad block order; -1 / unset = built-in choice)')
+    ap.add_argument('--tune', default='', help='p3d_fx_tune settings for this run, e.g. "1=4,5=1" (the codes of include/p3d_hip.h: 0 / 1 forced split counts, 2 wgrad block target, 3 pair pass, 5 per-class launches)')
     a = ap.parse_args()
     for kv in filter(None, a.tune.split(',')):
         what, value = kv.split('=')
