@@ -33,65 +33,53 @@ def _stream():
     return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()))
 
 
-_workspaces = {}
-
 # When a list, every conv launch is bracketed by a pair of events on the launch stream and
 # (kind, algorithmic_flops, start, end) is appended: bench.py's live per-kernel timing.
 PROFILE = None
 
 
 class _Timed:
-    def __init__(self, kind, d):
-        self.kind = kind
+    def __init__(self, kind, d, stream=None):
+        """stream: where the launch goes when that is not the current stream (the weight-gradient stream of _side_launch)."""
+        self.kind, self.stream = kind, stream
         self.flops = 2.0 * d.N * d.K * d.Ho * d.Wo * d.C * d.R * d.S
 
     def __enter__(self):
         if PROFILE is not None:
             self.start = torch.cuda.Event(enable_timing=True)
             self.end = torch.cuda.Event(enable_timing=True)
-            self.start.record()
+            self.start.record(self.stream)
         return self
 
     def __exit__(self, *exc):
         if PROFILE is not None:
-            self.end.record()
+            self.end.record(self.stream)
             PROFILE.append((self.kind, self.flops, self.start, self.end))
         return False
 
 
-
-def workspace(device, nbytes):
-    """Grow-only scratch buffer per device; ops on one stream are ordered, so it can be shared."""
-    ws = _workspaces.get(device)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
-        _workspaces[device] = ws
-    return ws
-
-
 # Weight-gradient kernels leave the critical path of backward (dy -> BN backward -> dgrad -> next layer): they only feed the
 # optimizer.  With P3D_WGRAD_STREAM != 0 they are launched on a second HIP stream, so the matrix-core-bound wgrad of layer i
-# overlaps the HBM-bound BN backward and the grid tails of layer i-1's kernels instead of queueing behind them.
+# overlaps the HBM-bound BN backward and the grid tails of layer i-1's kernels instead of queueing behind them (_side_launch).
 # join_side_stream() orders the launch stream after everything issued there (before an all-reduce / the optimizer reads .grad).
 WGRAD_STREAM = os.environ.get('P3D_WGRAD_STREAM', '1') != '0'
-# -half_acc: the weight gradient of a network's FIRST layer (no data gradient behind it) is the last kernel of the backward pass: queued on the second stream it waits
-# behind the weight gradients still pending there while the launch stream has nothing left to do; on the launch stream it runs beside them (14.04 / 14.03 ms against
-# 14.09 / 14.11; ops_half's weight-gradient launch).  The fp32 step measured no difference (28.17 / 28.11 / 28.10 against 28.29 / 28.05 / 27.99; profiles/r04_summary.md
-# section 8b) and keeps the second stream.
 _side_streams = {}
-_side_workspaces = {}
+_scratch = {}                                                          # (device, role) -> grow-only byte buffer
 
 
-_second_workspaces = {}
-
-
-def _second_workspace(device, nbytes):
-    """A second grow-only scratch buffer on the launch stream (the block executor's weight-gradient slabs when no second stream is used)."""
-    ws = _second_workspaces.get(device)
+def _scratch_buffer(device, nbytes, role):
+    """Grow-only scratch per device and role; ops on one stream are ordered, so they share it.  Roles: 'launch' (workspace()), 'second' (also on the launch stream:
+    the block executors' weight-gradient slabs when no second stream is used, beside the 'launch' scratch of the same call) and 'side', the weight-gradient
+    stream's, allocated with that stream current so that the allocator knows it as the owner."""
+    ws = _scratch.get((device, role))
     if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
-        _second_workspaces[device] = ws
+        with torch.cuda.stream(_side_stream(device) if role == 'side' else None):
+            ws = _scratch[(device, role)] = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
     return ws
+
+
+def workspace(device, nbytes):
+    return _scratch_buffer(device, nbytes, 'launch')
 
 
 SIDE_STREAM_OVERLAPS = {}                                              # device -> what the probe found
@@ -136,18 +124,7 @@ def _side_stream(device):
     return st
 
 
-def _side_workspace(device, nbytes):
-    ws = _side_workspaces.get(device)
-    if ws is None or ws.numel() < nbytes:
-        with torch.cuda.stream(_side_stream(device)):
-            ws = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
-        _side_workspaces[device] = ws
-    return ws
-
-
 _join_queued = False
-
-
 _event_ring, _event_next = [], [0]
 
 
@@ -179,10 +156,39 @@ def _queue_join():
         torch.autograd.Variable._execution_engine.queue_callback(join_side_stream)
 
 
+def _side_launch(device, wanted, nbytes, ready=None, block=False):
+    """Where a weight-gradient launch goes and what it may scribble on: (side, stream handle, scratch).  The ONE place that orders the two streams of backward.
+    wanted: the caller's own conditions; the launch leaves the launch stream only if WGRAD_STREAM (read now: bench.py assigns it between passes) holds too.
+    Callers pass `grads.direct and ...`: a gradient handed back to autograd is consumed on the launch stream, so only sink-bound ones may go aside.
+    On the second stream: the backward pass is told to join the streams when it ends, the stream is ordered behind `ready` (an event of _mark_ready()
+    recorded where the operands became final; None: the launch stream as of now) and the scratch is the second stream's own.  block=True is the call of a
+    block executor, which takes the second stream beside the launch stream and orders its launches there itself: no wait here, and handle None plus the second
+    launch-stream scratch (its call uses workspace() too) when everything stays on the launch stream.
+    Nothing here creates an event, allocates or synchronizes in steady state (a captured step runs through it).  side is None on the launch stream; hand it to
+    _Timed and, after the launch, to _side_launched."""
+    if not (WGRAD_STREAM and wanted):
+        return None, (None if block else _stream()), _scratch_buffer(device, nbytes, 'second' if block else 'launch')
+    side = _side_stream(device)
+    _queue_join()
+    if not block:
+        side.wait_event(_mark_ready() if ready is None else ready)
+    return side, ctypes.c_void_p(side.cuda_stream), _scratch_buffer(device, nbytes, 'side')
+
+
+def _side_launched(side, tensors=(), owned=None):
+    """After a launch placed by _side_launch: what the second stream still reads must outlive / stay untouched until it is done.  tensors: the allocator-owned
+    operands (autograd frees them while the kernel may be pending; None entries are skipped); owned: the module- or plan-owned buffer set among the operands,
+    whose next user orders itself behind the event recorded here (ops_block._free_set).  Call _GradOut.done() only after this."""
+    if side is not None:
+        for t in tensors:
+            if t is not None:
+                t.record_stream(side)
+        if owned is not None:
+            owned.mark_side(side)
+
+
 def _grad_sink(param):
-    """The preallocated .grad of a parameter owned by FlatAdam (flagged _p3d_direct_grad), or None.
-    Backward kernels accumulate straight into it (the buffer is zeroed once per step), so autograd's own
-    per-parameter add kernel and its temporary are skipped; the Function then returns None for that input."""
+    """The preallocated .grad of a parameter owned by FlatAdam (flagged _p3d_direct_grad), or None."""
     if param is not None and getattr(param, '_p3d_direct_grad', False) and param.grad is not None:
         return param.grad
     return None
@@ -192,6 +198,29 @@ def _grad_done(param):
     ready = getattr(param, '_p3d_grad_ready', None)       # set by dist.GradReducer: counts the bucket down
     if ready is not None:
         ready()
+
+
+class _GradOut:
+    """Where a backward writes the gradients of `params` (fp32 parameters, one for the per-parameter rule, several for all-or-nothing: the gamma / beta of a
+    BatchNorm, every parameter of a block) and what it returns to autograd for them.  If EVERY parameter has a FlatAdam sink (_grad_sink), `bufs` are those
+    and `direct` is set: the kernels accumulate straight into them (the buffer is zeroed once per step), so autograd's own per-parameter add kernel and its
+    temporary are skipped and done() returns None for each.  Otherwise `bufs` are fresh tensors, overwritten and returned.
+    done() also reports completion (under a process group dist.GradReducer may then queue an all-reduce on the second stream): call it LAST, after the launch
+    and after _side_launched, so that a buffer set's next user waits for the weight gradients and not for the collective behind them."""
+    __slots__ = ('params', 'direct', 'bufs')
+
+    def __init__(self, *params):
+        sinks = [_grad_sink(p) for p in params]
+        self.params = params
+        self.direct = all(s is not None for s in sinks)
+        self.bufs = sinks if self.direct else [torch.empty(p.shape, dtype=torch.float32, device=p.device) for p in params]
+
+    def done(self):
+        if not self.direct:
+            return tuple(self.bufs)
+        for p in self.params:
+            _grad_done(p)
+        return (None,) * len(self.params)
 
 
 def conv_out(h, k, stride, pad, dil):
@@ -317,44 +346,24 @@ class Conv2dFn(torch.autograd.Function):
             ws = workspace(x.device, L.p3d_conv2d_dgrad_workspace_bytes(ctypes.byref(d)))
             with _Timed('dgrad', d):
                 check(L.p3d_conv2d_dgrad(ctypes.byref(d), _p(dy), _p(w), _p(mult), _p(mask_in), _p(dx), _p(ws), ws.numel(), st), 'p3d_conv2d_dgrad')
-            d.accumulate = 0
             if _stash(join_put, dx):
                 dx = None                                     # the consumer returns it
         w_param, b_param = ctx.params
         if ctx.needs_input_grad[1]:
-            sink = _grad_sink(w_param)
-            dw = torch.empty_like(w) if sink is None else sink
-            d.accumulate = 0 if sink is None else 1
-            nbytes = L.p3d_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
-            if WGRAD_STREAM and sink is not None:
-                side = _side_stream(x.device)
-                _queue_join()
-                side.wait_event(dy_ready)                               # dy (and the zeroed gradient buffer) are ready
-                ws = _side_workspace(x.device, nbytes)
-                with torch.cuda.stream(side):
-                    with _Timed('wgrad', d):
-                        check(L.p3d_conv2d_wgrad(ctypes.byref(d), _p(dy), _p(x), _p(mult), _p(mask_in), _p(dw), _p(ws), ws.numel(), _stream()),
-                              'p3d_conv2d_wgrad')
-                for t in (dy, x, mult, mask_in):                        # freed by autograd while the side stream may still read them
-                    if t is not None:
-                        t.record_stream(side)
-            else:
-                ws = workspace(x.device, nbytes)
-                with _Timed('wgrad', d):
-                    check(L.p3d_conv2d_wgrad(ctypes.byref(d), _p(dy), _p(x), _p(mult), _p(mask_in), _p(dw), _p(ws), ws.numel(), st), 'p3d_conv2d_wgrad')
-            if sink is not None:
-                dw = None
-                _grad_done(w_param)
+            grads = _GradOut(w_param)
+            d.accumulate = int(grads.direct)
+            side, wst, ws = _side_launch(x.device, grads.direct, L.p3d_conv2d_wgrad_workspace_bytes(ctypes.byref(d)), dy_ready)    # behind dy (and the zeroed gradient buffer)
+            with _Timed('wgrad', d, side):
+                check(L.p3d_conv2d_wgrad(ctypes.byref(d), _p(dy), _p(x), _p(mult), _p(mask_in), _p(grads.bufs[0]), _p(ws), ws.numel(), wst), 'p3d_conv2d_wgrad')
+            _side_launched(side, (dy, x, mult, mask_in))
+            dw, = grads.done()
         if has_bias and ctx.needs_input_grad[2]:
-            sink = _grad_sink(b_param)
-            db = torch.empty(d.K, dtype=torch.float32, device=x.device) if sink is None else sink
+            grads = _GradOut(b_param)
             if mult is not None:      # PartialConv with bias: d out / d b = mask_out (partial_conv.py:48-51)
-                check(L.p3d_conv2d_bgrad_masked(_p(dy), _p(mult), d.N, d.K, d.Ho * d.Wo, _p(db), 0 if sink is None else 1, st), 'p3d_conv2d_bgrad_masked')
+                check(L.p3d_conv2d_bgrad_masked(_p(dy), _p(mult), d.N, d.K, d.Ho * d.Wo, _p(grads.bufs[0]), int(grads.direct), st), 'p3d_conv2d_bgrad_masked')
             else:
-                check(L.p3d_conv2d_bgrad(_p(dy), d.N, d.K, d.Ho * d.Wo, _p(db), 0 if sink is None else 1, st), 'p3d_conv2d_bgrad')
-            if sink is not None:
-                db = None
-                _grad_done(b_param)
+                check(L.p3d_conv2d_bgrad(_p(dy), d.N, d.K, d.Ho * d.Wo, _p(grads.bufs[0]), int(grads.direct), st), 'p3d_conv2d_bgrad')
+            db, = grads.done()
         return dx, dw, db, None, None, None, None, None, None, None
 
 
@@ -402,15 +411,12 @@ class ConvCat1x1Fn(torch.autograd.Function):
             dyy = torch.empty_like(y)
             check(L.p3d_conv2d_dgrad(ctypes.byref(d2), _p(dy), _p(w), None, None, _p(dyy), _p(wsd), wsd.numel(), st), 'p3d_conv2d_dgrad')
         if ctx.needs_input_grad[2]:
-            sink = _grad_sink(ctx.w_param)
-            dw = torch.empty_like(w) if sink is None else sink
+            grads = _GradOut(ctx.w_param)
             for d, inp in ((d1, x), (d2, y)):
-                d.accumulate = 0 if sink is None else 1
+                d.accumulate = int(grads.direct)
                 ws = workspace(x.device, L.p3d_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
-                check(L.p3d_conv2d_wgrad(ctypes.byref(d), _p(dy), _p(inp), None, None, _p(dw), _p(ws), ws.numel(), st), 'p3d_conv2d_wgrad')
-            if sink is not None:
-                dw = None
-                _grad_done(ctx.w_param)
+                check(L.p3d_conv2d_wgrad(ctypes.byref(d), _p(dy), _p(inp), None, None, _p(grads.bufs[0]), _p(ws), ws.numel(), st), 'p3d_conv2d_wgrad')
+            dw, = grads.done()
         return dx, dyy, dw
 
 
@@ -480,11 +486,9 @@ class BatchNormActFn(torch.autograd.Function):
         dres = None
         if has_res and ctx.needs_input_grad[5]:
             dres = torch.empty_like(x) if relu else dy      # without ReLU the residual gradient is dy itself
-        g_param, b_param = ctx.params
-        g_sink, b_sink = _grad_sink(g_param), _grad_sink(b_param)
-        direct = g_sink is not None and b_sink is not None
-        dgamma = g_sink if direct else torch.empty(c, dtype=torch.float32, device=x.device)
-        dbeta = b_sink if direct else torch.empty_like(dgamma)
+        grads = _GradOut(*ctx.params)
+        direct = grads.direct
+        dgamma, dbeta = grads.bufs
         ws = workspace(x.device, L.p3d_bn_workspace_bytes(n, c, h * w))
         dres_ptr = _p(dres) if (dres is not None and relu) else None
         if training:
@@ -493,10 +497,7 @@ class BatchNormActFn(torch.autograd.Function):
         else:
             check(L.p3d_bn_eval_bwd(_p(dy), _p(x), _p(y), _p(gamma), _p(s1), _p(s2), _p(dx), dres_ptr, _p(dgamma), _p(dbeta),
                                     n, c, h * w, eps, int(relu), int(direct), _p(ws), ws.numel(), st), 'p3d_bn_eval_bwd')
-        if direct:
-            dgamma = dbeta = None
-            _grad_done(g_param)
-            _grad_done(b_param)
+        dgamma, dbeta = grads.done()
         if dres is not None and relu and _stash(ctx.res_join, dres):    # (without ReLU dres aliases dy: never hand that out)
             dres = None
         return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None
@@ -594,18 +595,13 @@ class StemTailFn(torch.autograd.Function):
         dy = dy.contiguous()
         L, st = lib(), _stream()
         dx = torch.empty_like(x)
-        g_param, b_param = ctx.params
-        g_sink, b_sink = _grad_sink(g_param), _grad_sink(b_param)
-        direct = g_sink is not None and b_sink is not None
-        dgamma = g_sink if direct else torch.empty(c, dtype=torch.float32, device=x.device)
-        dbeta = b_sink if direct else torch.empty_like(dgamma)
+        grads = _GradOut(*ctx.params)
+        direct = grads.direct
+        dgamma, dbeta = grads.bufs
         ws = workspace(x.device, L.p3d_bn_workspace_bytes(n, c, h * w))
         check(L.p3d_stem_tail_bwd(_p(dy), _p(idx), _p(x), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(dx), _p(dgamma), _p(dbeta), n, c, h, w, int(direct),
                                   _p(ws), ws.numel(), st), 'p3d_stem_tail_bwd')
-        if direct:
-            dgamma = dbeta = None
-            _grad_done(g_param)
-            _grad_done(b_param)
+        dgamma, dbeta = grads.done()
         return dx, dgamma, dbeta, None, None, None, None
 
 

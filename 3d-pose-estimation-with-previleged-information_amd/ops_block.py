@@ -96,25 +96,39 @@ class _Plan:
         self.tail_bytes = int(lib().p3d_block_tail_partial_bytes(ctypes.byref(d))) if self.tail_ok else 0
         self.in_shape = tuple(x_shape)
 
-    def acquire(self, device):
-        """A free buffer set (or a new one).  Two are kept per plan (a block that runs twice before its backward: labelled + unlabelled batch of semi_train);
-        a third concurrent execution gets a set that dies with its autograd node."""
-        for b in self.sets:
-            if not b.held and b.device == device:
-                break
-        else:
-            b = _Buffers(self, device)
-            if len(self.sets) < 2:
-                self.sets.append(b)
-        if b.side_done is not None:     # the previous backward's weight gradients (second stream) read these buffers: order this stream behind them
-            torch.cuda.current_stream(device).wait_event(b.side_done)
-        return b
+
+def _free_set(sets, device, make):
+    """A buffer set of `sets` that no live autograd node holds, or a new one from make().  Two are kept per owner (a module that runs twice before its backward:
+    labelled + unlabelled batch of semi_train); a third concurrent execution gets a set that dies with its autograd node."""
+    for b in sets:
+        if not b.held and b.device == device:
+            break
+    else:
+        b = make()
+        if len(sets) < 2:
+            sets.append(b)
+    if b.side_done is not None:         # the previous backward's weight gradients (second stream) read these buffers: order this stream behind them
+        torch.cuda.current_stream(device).wait_event(b.side_done)
+    return b
+
+
+class _BufferSet:
+    """Device memory that a module or plan owns for ONE execution in flight: `held` while an autograd node uses it (_Lease), `side_done` the event behind the
+    last reader on the weight-gradient stream (ops._side_launched records it, _free_set waits on it, reset_side_events forgets it)."""
+
+    def __init__(self, device):
+        self.device, self.held, self.side_done = device, False, None
+
+    def mark_side(self, side):
+        if self.side_done is None:
+            self.side_done = torch.cuda.Event()
+        self.side_done.record(side)
 
 
 _spare_shapes = set()
 
 
-class _Buffers:
+class _Buffers(_BufferSet):
     """The device memory of ONE execution of a block, owned by its plan and used again by the next step: the conv outputs c_i, the activation images a_i and the
     BatchNorm tables (written by forward, read by backward), and the backward's own scratch (gradient images, the fp32 gradients between layers).  Taking these
     from the caching allocator per call cost more than its bookkeeping: tensors the weight-gradient stream reads must be `record_stream`ed, which makes their
@@ -122,7 +136,8 @@ class _Buffers:
     process, in the middle of the timed region (profiles/r03_summary.md section 8)."""
 
     def __init__(self, plan, device):
-        self.device, self.held, self.side_done, self.bwd = device, False, None, None
+        super().__init__(device)
+        self.bwd = None
         self.tail = None                # (partial scratch, sums [C][TAIL_ROWS][3] fp64): where a consumer block leaves this block's opening sums
         self.open_ready = None          # (data_ptr, _version) of the gradient tensor those sums were reduced over
         f32 = dict(dtype=torch.float32, device=device)
@@ -158,22 +173,18 @@ class _Buffers:
         return self.bwd
 
 
-class _OwnedBuffers:
+class _OwnedBuffers(_BufferSet):
     """Named byte buffers owned by one module for one execution in flight (the per-layer twins of _Buffers: the operand images of ConvImagesFn / StemConvFn)."""
 
     def __init__(self, device):
-        self.device, self.held, self.side_done, self.t = device, False, None, {}
+        super().__init__(device)
+        self.t = {}
 
     def tensor(self, name, nbytes):
         t = self.t.get(name)
         if t is None or t.numel() != nbytes:
             t = self.t[name] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return t
-
-    def mark_side(self, side):
-        if self.side_done is None:
-            self.side_done = torch.cuda.Event()
-        self.side_done.record(side)
 
 
 def _owned(module, key, device):
@@ -189,16 +200,7 @@ def _owned(module, key, device):
                     break
         sets = []
     cache[key] = sets
-    for b in sets:
-        if not b.held and b.device == device:
-            break
-    else:
-        b = _OwnedBuffers(device)
-        if len(sets) < 2:
-            sets.append(b)
-    if b.side_done is not None:
-        torch.cuda.current_stream(device).wait_event(b.side_done)
-    return b
+    return _free_set(sets, device, lambda: _OwnedBuffers(device))
 
 
 class _Lease:
@@ -376,7 +378,7 @@ class ResidualBlockFn(torch.autograd.Function):
         io.x = x.data_ptr()
         out = torch.empty(plan.out_shape, dtype=torch.float32, device=x.device)
         io.out = out.data_ptr()
-        bufs = plan.acquire(x.device)
+        bufs = _free_set(plan.sets, x.device, lambda: _Buffers(plan, x.device))
         lease = _Lease(bufs)
         bufs.open_ready = None
         # the block whose output this input is (residual_block tags its result): its buffers, for the tail sums of backward
@@ -442,9 +444,7 @@ class ResidualBlockFn(torch.autograd.Function):
         params = []
         for slot, conv, bn in layers:
             params += [(slot, 'dw', conv.weight), (slot, 'dgamma', bn.weight), (slot, 'dbeta', bn.bias)]
-        sinks = [ops._grad_sink(p) for _, _, p in params]
-        direct = all(s is not None for s in sinks)
-        grads = sinks if direct else [torch.empty_like(p) for _, _, p in params]
+        grads = ops._GradOut(*[p for _, _, p in params])
         io = BlockIO()
         io.x, io.out, io.dout = x.data_ptr(), out.data_ptr(), dout.data_ptr()
         if bufs.mask is not None:
@@ -489,7 +489,7 @@ class ResidualBlockFn(torch.autograd.Function):
             io.table[slot] = tables.data_ptr() + row * 32
             row += plan.shapes[slot][1]
             io.gamma[slot], io.beta[slot] = bn.weight.data_ptr(), bn.bias.data_ptr()
-        for (slot, kind, _), g in zip(params, grads):
+        for (slot, kind, _), g in zip(params, grads.bufs):
             getattr(io, kind)[slot] = g.data_ptr()
         dcimg, da, gbuf = bufs.backward_scratch(plan)
         if gbuf is None and not (d.has_downsample and bufs.mask is not None):
@@ -508,33 +508,17 @@ class ResidualBlockFn(torch.autograd.Function):
             else:
                 dx = gbuf                                   # identity shortcut: conv1's data gradient is added onto g in place
         desc = BlockDesc.from_buffer_copy(d)
-        desc.need_dx, desc.accumulate_grads = int(need_dx), int(direct)
+        desc.need_dx, desc.accumulate_grads = int(need_dx), int(grads.direct)
         ws = ops.workspace(x.device, plan.main_bytes)
-        two = ops.WGRAD_STREAM and direct and BLOCK_SIDE_STREAM
-        if two:
-            side = ops._side_stream(x.device)
-            ops._queue_join()
-            sws = ops._side_workspace(x.device, plan.side_bytes)
-            side_handle = _vp(side.cuda_stream)
-        else:
-            sws = ops._second_workspace(x.device, plan.side_bytes)
-            side_handle = None
+        side, side_handle, sws = ops._side_launch(x.device, grads.direct and BLOCK_SIDE_STREAM, plan.side_bytes, block=True)
         check(L.p3d_block_bwd(ctypes.byref(desc), ctypes.byref(io), ops._p(ws), ws.numel(), ops._p(sws), sws.numel(), ops._stream(), side_handle), 'p3d_block_bwd')
         if tail_for is not None and dx is not None:
             tail_for.open_ready = (dx.data_ptr(), dx._version)      # the producer's backward checks that this is what it receives
-        if two:
-            x.record_stream(side)          # the one allocator-owned tensor the second stream reads (first conv's and the downsample's weight gradients)
-            if ctx.pix is not None:
-                ctx.pix[0][0].record_stream(side)          # (and, for a masked block, conv 1's mask_in: its weight gradient multiplies x by it)
-            if bufs.side_done is None:
-                bufs.side_done = torch.cuda.Event()
-            bufs.side_done.record(side)    # the plan's buffers: their next user (plan.acquire) orders itself behind this
+        # the allocator-owned tensors the second stream reads: x (first conv's and the downsample's weight gradients) and, for a masked block, conv 1's mask_in (its
+        # weight gradient multiplies x by it); everything else is the plan's
+        ops._side_launched(side, (x, None if ctx.pix is None else ctx.pix[0][0]), bufs)
         del lease
-        if direct:
-            for _, _, p in params:
-                ops._grad_done(p)
-            return (dx, None, None) + (None,) * len(params)
-        return (dx, None, None) + tuple(grads)
+        return (dx, None, None) + grads.done()
 
 
 def residual_block(block, x, veil=None):
@@ -615,35 +599,17 @@ class ConvImagesFn(torch.autograd.Function):
             with ops._Timed('dgrad', d):
                 check(L.p3d_fx_conv_dgrad_img(ctypes.byref(d), ops._p(dy_img), ops._p(w), ops._p(wimgT), ops._p(dx), ops._p(ws), ws.numel(), st), 'p3d_fx_conv_dgrad_img')
         if ctx.needs_input_grad[2]:
-            sink = ops._grad_sink(w)
-            dw = torch.empty_like(w) if sink is None else sink
-            d.accumulate = 0 if sink is None else 1
-            nbytes = L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 2)
-            if ops.WGRAD_STREAM and sink is not None:
-                side = ops._side_stream(dy.device)
-                ops._queue_join()
-                side.wait_event(dy_ready)
-                sws = ops._side_workspace(dy.device, nbytes)
-                with torch.cuda.stream(side):
-                    with ops._Timed('wgrad', d):
-                        check(L.p3d_fx_conv_wgrad_img(ctypes.byref(d), ops._p(dy_img), None, ops._p(x_img), ops._p(dw), ops._p(sws), sws.numel(), ops._stream()),
-                              'p3d_fx_conv_wgrad_img')
-                bufs.mark_side(side)                        # both images are the module's own buffers: their next user orders itself behind this
-            else:
-                sws = ops.workspace(dy.device, nbytes)
-                with ops._Timed('wgrad', d):
-                    check(L.p3d_fx_conv_wgrad_img(ctypes.byref(d), ops._p(dy_img), None, ops._p(x_img), ops._p(dw), ops._p(sws), sws.numel(), st), 'p3d_fx_conv_wgrad_img')
-            d.accumulate = 0
-            if sink is not None:
-                dw = None
-                ops._grad_done(w)
+            grads = ops._GradOut(w)
+            d.accumulate = int(grads.direct)
+            side, wst, sws = ops._side_launch(dy.device, grads.direct, L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 2), dy_ready)
+            with ops._Timed('wgrad', d, side):
+                check(L.p3d_fx_conv_wgrad_img(ctypes.byref(d), ops._p(dy_img), None, ops._p(x_img), ops._p(grads.bufs[0]), ops._p(sws), sws.numel(), wst), 'p3d_fx_conv_wgrad_img')
+            ops._side_launched(side, owned=bufs)            # both images are the module's own buffers
+            dw, = grads.done()
         if bias is not None and ctx.needs_input_grad[3]:
-            sink = ops._grad_sink(bias)
-            db = torch.empty(d.K, dtype=torch.float32, device=dy.device) if sink is None else sink
-            check(L.p3d_conv2d_bgrad(ops._p(dy), d.N, d.K, d.Ho * d.Wo, ops._p(db), 0 if sink is None else 1, st), 'p3d_conv2d_bgrad')
-            if sink is not None:
-                db = None
-                ops._grad_done(bias)
+            grads = ops._GradOut(bias)
+            check(L.p3d_conv2d_bgrad(ops._p(dy), d.N, d.K, d.Ho * d.Wo, ops._p(grads.bufs[0]), int(grads.direct), st), 'p3d_conv2d_bgrad')
+            db, = grads.done()
         return dx, None, dw, db
 
 
@@ -721,28 +687,11 @@ class StemConvFn(torch.autograd.Function):
         if lease is None:
             raise P3DError('stem_conv: backward called a second time on the same graph; run the forward again')
         if ctx.needs_input_grad[2]:
-            sink = ops._grad_sink(w)
-            dw = torch.empty_like(w) if sink is None else sink
-            nbytes = L.p3d_stem_workspace_bytes(n, h, wd, k)
-            if ops.WGRAD_STREAM and sink is not None:
-                dy_ready = ops._mark_ready()
-                side = ops._side_stream(dy.device)
-                ops._queue_join()
-                side.wait_event(dy_ready)
-                sws = ops._side_workspace(dy.device, nbytes)
-                with torch.cuda.stream(side):
-                    check(L.p3d_stem_wgrad_masked(ops._p(dy), mp, ops._p(x_img), ops._p(dw), n, c, h, wd, k, 1, ops._p(sws), sws.numel(), ops._stream()), 'p3d_stem_wgrad')
-                dy.record_stream(side)                      # (allocator-owned: the stem BatchNorm's data gradient)
-                if mult is not None:
-                    mult.record_stream(side)
-                lease.bufs.mark_side(side)
-            else:
-                sws = ops.workspace(dy.device, nbytes)
-                check(L.p3d_stem_wgrad_masked(ops._p(dy), mp, ops._p(x_img), ops._p(dw), n, c, h, wd, k, 0 if sink is None else 1, ops._p(sws), sws.numel(), ops._stream()),
-                      'p3d_stem_wgrad')
-            if sink is not None:
-                dw = None
-                ops._grad_done(w)
+            grads = ops._GradOut(w)
+            side, wst, sws = ops._side_launch(dy.device, grads.direct, L.p3d_stem_workspace_bytes(n, h, wd, k))
+            check(L.p3d_stem_wgrad_masked(ops._p(dy), mp, ops._p(x_img), ops._p(grads.bufs[0]), n, c, h, wd, k, int(grads.direct), ops._p(sws), sws.numel(), wst), 'p3d_stem_wgrad')
+            ops._side_launched(side, (dy, mult), lease.bufs)                # (dy is allocator-owned: the stem BatchNorm's data gradient; the image is the module's)
+            dw, = grads.done()
         return None, None, dw, None, None
 
 

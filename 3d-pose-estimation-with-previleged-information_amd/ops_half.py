@@ -11,7 +11,7 @@ import torch
 
 from . import ops
 from ._lib import P3DError, check, lib
-from .ops import _desc, _grad_done, _grad_sink, _p, _stream, workspace
+from .ops import _GradOut, _desc, _p, _side_launch, _side_launched, _stream, workspace
 
 CL = torch.channels_last
 
@@ -198,41 +198,24 @@ class HConv2dFn(torch.autograd.Function):
                 dx = _empty(n, c, h, wd, x.device)
             with ops._Timed('dgrad', d):
                 check(L.p3d_hconv2d_dgrad(ctypes.byref(d), _p(dy), _p(images.crsk), _p(mask_in), _p(dx), st), 'p3d_hconv2d_dgrad')
-            d.accumulate = 0
             if ops._stash(join_put, dx):
                 dx = None
         if ctx.needs_input_grad[1]:
-            sink = _grad_sink(w_param)
-            dw = torch.empty(wshape, dtype=torch.float32, device=x.device) if sink is None else sink
-            d.accumulate = 0 if sink is None else 1
-            nbytes = L.p3d_hconv2d_wgrad_workspace_bytes(ctypes.byref(d))
-            if ops.WGRAD_STREAM and sink is not None and ctx.needs_input_grad[0]:      # (a network's first layer stays on the launch stream: see ops.WGRAD_STREAM)
-                side = ops._side_stream(x.device)
-                ops._queue_join()
-                side.wait_stream(torch.cuda.current_stream())
-                ws = ops._side_workspace(x.device, nbytes)
-                with torch.cuda.stream(side):
-                    with ops._Timed('wgrad', d):
-                        check(L.p3d_hconv2d_wgrad(ctypes.byref(d), _p(dy), _p(x), _p(mask_in), _p(dw), images.c_real, 1.0, _p(ws), ws.numel(), _stream()),
-                              'p3d_hconv2d_wgrad')
-                for t in (dy, x, mask_in):
-                    if t is not None:
-                        t.record_stream(side)
-            else:
-                ws = workspace(x.device, nbytes)
-                with ops._Timed('wgrad', d):
-                    check(L.p3d_hconv2d_wgrad(ctypes.byref(d), _p(dy), _p(x), _p(mask_in), _p(dw), images.c_real, 1.0, _p(ws), ws.numel(), st), 'p3d_hconv2d_wgrad')
-            d.accumulate = 0
-            if sink is not None:
-                dw = None
-                _grad_done(w_param)
+            grads = _GradOut(w_param)
+            d.accumulate = int(grads.direct)
+            # The weight gradient of a network's FIRST layer (no data gradient behind it) is the last kernel of the backward pass: queued on the second stream it waits
+            # behind the weight gradients still pending there while the launch stream has nothing left to do; on the launch stream it runs beside them (14.04 / 14.03 ms
+            # against 14.09 / 14.11).  (The fp32 step measured no difference, 28.17 / 28.11 / 28.10 against 28.29 / 28.05 / 27.99, profiles/r04_summary.md section 8b, and
+            # keeps the second stream.)  Every other layer goes aside, behind its data gradient.
+            side, wst, ws = _side_launch(x.device, grads.direct and ctx.needs_input_grad[0], L.p3d_hconv2d_wgrad_workspace_bytes(ctypes.byref(d)))
+            with ops._Timed('wgrad', d, side):
+                check(L.p3d_hconv2d_wgrad(ctypes.byref(d), _p(dy), _p(x), _p(mask_in), _p(grads.bufs[0]), images.c_real, 1.0, _p(ws), ws.numel(), wst), 'p3d_hconv2d_wgrad')
+            _side_launched(side, (dy, x, mask_in))
+            dw, = grads.done()
         if b_param is not None and ctx.needs_input_grad[2]:
-            sink = _grad_sink(b_param)
-            db = torch.empty(k, dtype=torch.float32, device=x.device) if sink is None else sink
-            check(L.p3d_hconv2d_bgrad(_p(dy), n * d.Ho * d.Wo, k, _p(db), 1.0, 0 if sink is None else 1, st), 'p3d_hconv2d_bgrad')
-            if sink is not None:
-                db = None
-                _grad_done(b_param)
+            grads = _GradOut(b_param)
+            check(L.p3d_hconv2d_bgrad(_p(dy), n * d.Ho * d.Wo, k, _p(grads.bufs[0]), 1.0, int(grads.direct), st), 'p3d_hconv2d_bgrad')
+            db, = grads.done()
         return dx, dw, db, None, None, None, None, None, None, None, None
 
 
@@ -284,19 +267,14 @@ class HBatchNormActFn(torch.autograd.Function):
         dres = None
         if has_res and ctx.needs_input_grad[5]:
             dres = _empty(n, c, h, w, x.device) if relu else dy
-        g_param, b_param = ctx.params
-        g_sink, b_sink = _grad_sink(g_param), _grad_sink(b_param)
-        direct = g_sink is not None and b_sink is not None
-        dgamma = g_sink if direct else torch.empty(c, dtype=torch.float32, device=x.device)
-        dbeta = b_sink if direct else torch.empty_like(dgamma)
+        grads = _GradOut(*ctx.params)
+        direct = grads.direct
+        dgamma, dbeta = grads.bufs
         ws = workspace(x.device, L.p3d_hbn_workspace_bytes(c))
         bwd = L.p3d_hbn_train_bwd if training else L.p3d_hbn_frozen_bwd
         check(bwd(_p(dy), _p(x), _p(y), _p(coef), _p(dx), _p(dres) if (dres is not None and relu) else None,
                   _p(dgamma), _p(dbeta), n * h * w, c, int(relu), int(direct), _p(ws), ws.numel(), st), 'p3d_hbn_train_bwd')
-        if direct:
-            dgamma = dbeta = None
-            _grad_done(g_param)
-            _grad_done(b_param)
+        dgamma, dbeta = grads.done()
         if dres is not None and relu and ops._stash(ctx.res_join, dres):     # (without ReLU dres aliases dy: never hand that out)
             dres = None
         return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None
@@ -507,9 +485,7 @@ class HResidualBlockFn(torch.autograd.Function):
         params = []
         for slot, conv, bn in plan.layers:
             params += [(slot, 'dw', conv.weight), (slot, 'dgamma', bn.weight), (slot, 'dbeta', bn.bias)]
-        sinks = [_grad_sink(p) for _, _, p in params]
-        direct = all(s_ is not None for s_ in sinks)
-        grads = sinks if direct else [torch.empty(p.shape, dtype=torch.float32, device=dev) for _, _, p in params]
+        grads = _GradOut(*[p for _, _, p in params])
         io = HBlockIO()
         io.x, io.out, io.dout = x.data_ptr(), out.data_ptr(), dout.data_ptr()
         if ctx.fused:                                      # (forward wrote the mask bytes only with the sums from the epilogues)
@@ -538,29 +514,15 @@ class HResidualBlockFn(torch.autograd.Function):
                 io.dx = dx.data_ptr()
             else:
                 dx = dres
-        for (slot, kind, _), g in zip(params, grads):
+        for (slot, kind, _), g in zip(params, grads.bufs):
             getattr(io, kind)[slot] = g.data_ptr()
         desc = ops_block.BlockDesc.from_buffer_copy(d)
-        desc.need_dx, desc.accumulate_grads = int(need_dx), int(direct)
+        desc.need_dx, desc.accumulate_grads = int(need_dx), int(grads.direct)
         ws = workspace(dev, plan.main_bytes)
-        two = ops.WGRAD_STREAM and direct
-        if two:
-            side = ops._side_stream(dev)
-            ops._queue_join()
-            sws = ops._side_workspace(dev, plan.side_bytes)
-            side_handle = _vp(side.cuda_stream)
-        else:
-            sws = ops._second_workspace(dev, plan.side_bytes)
-            side_handle = None
+        side, side_handle, sws = _side_launch(dev, grads.direct, plan.side_bytes, block=True)
         check(lib().p3d_hblock_bwd(ctypes.byref(desc), ctypes.byref(io), _p(ws), ws.numel(), _p(sws), sws.numel(), _stream(), side_handle), 'p3d_hblock_bwd')
-        if two:
-            for t in [x, dout] + list(acts.values()) + keep:        # freed by autograd while the second stream may still read them
-                t.record_stream(side)
-        if direct:
-            for _, _, p in params:
-                _grad_done(p)
-            return (dx, None) + (None,) * len(params)
-        return (dx, None) + tuple(grads)
+        _side_launched(side, [x, dout] + list(acts.values()) + keep)      # all of it allocator-owned: freed by autograd while the second stream may still read it
+        return (dx, None) + grads.done()
 
 
 def residual_block(block, x):

@@ -298,3 +298,52 @@ def test_rccl_overlap_verdict_fails_closed(pkg, monkeypatch):
     assert verdict({'NCCL_ALGO': 'Tree', 'P3D_RCCL_OVERLAP': '1'})[0]
     assert not verdict({'NCCL_ALGO': 'Ring', 'P3D_RCCL_OVERLAP': '0'})[0]
     monkeypatch.setattr(d, '_overlap_verdict', None)
+
+
+def test_gradient_sink_rules(pkg):
+    """ops._GradOut, the one place that decides where a backward writes a parameter gradient (it only looks at attributes, so CPU tensors do):
+    a parameter FlatAdam owns (_p3d_direct_grad and a .grad) yields that buffer, accumulate on, None back to autograd and exactly one
+    _p3d_grad_ready call; any other yields a fresh tensor that is returned and no call; a group with one unflagged member falls back to
+    fresh tensors for ALL members and calls nothing."""
+    ops = pkg.ops
+    calls = []
+
+    def param(shape, flagged):
+        p = torch.nn.Parameter(torch.zeros(shape))
+        p._p3d_grad_ready = lambda: calls.append(p)
+        if flagged:
+            p.grad = torch.zeros(shape)
+            p._p3d_direct_grad = True
+        return p
+
+    w = param((4, 3, 1, 1), True)
+    out = ops._GradOut(w)
+    assert out.direct is True and len(out.bufs) == 1 and out.bufs[0] is w.grad
+    assert not calls                                          # nothing is reported before done()
+    assert out.done() == (None,)
+    assert len(calls) == 1 and calls[0] is w
+
+    del calls[:]
+    plain = param((4, 3, 1, 1), False)
+    out = ops._GradOut(plain)
+    assert out.direct is False and out.bufs[0].shape == plain.shape and out.bufs[0].dtype == torch.float32
+    fresh = out.bufs[0]
+    ret = out.done()
+    assert len(ret) == 1 and ret[0] is fresh and not calls
+    flagged_without_grad = param((4,), False)
+    flagged_without_grad._p3d_direct_grad = True              # (FlatAdam has not attached its buffer: no sink)
+    assert ops._GradOut(flagged_without_grad).direct is False
+
+    gamma, beta = param((8,), True), param((8,), True)
+    out = ops._GradOut(gamma, beta)
+    assert out.direct is True and out.bufs[0] is gamma.grad and out.bufs[1] is beta.grad
+    assert out.done() == (None, None)
+    assert len(calls) == 2 and calls[0] is gamma and calls[1] is beta
+
+    del calls[:]
+    beta = param((8,), False)
+    out = ops._GradOut(gamma, beta)
+    assert out.direct is False
+    assert all(b is not gamma.grad and b.shape == (8,) for b in out.bufs) and out.bufs[0] is not out.bufs[1]
+    ret = out.done()
+    assert ret[0] is out.bufs[0] and ret[1] is out.bufs[1] and not calls
