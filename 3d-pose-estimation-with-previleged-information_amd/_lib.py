@@ -59,6 +59,9 @@ SIGNATURES = {
     'p3d_fx_conv_fwd_infer_supported': (_i32, [_desc, _i32]),
     'p3d_fx_conv_fwd_infer_workspace_bytes': (_sz, [_desc]),
     'p3d_fx_conv_fwd_infer': (_i32, [_desc, _ptr, _ptr, _ptr, _sz, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
+    'p3d_fx_conv_fwd_infer_any_supported': (_i32, [_desc]),
+    'p3d_fx_conv_fwd_infer_any_workspace_bytes': (_sz, [_desc]),
+    'p3d_fx_conv_fwd_infer_any': (_i32, [_desc, _ptr, _ptr, _sz, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
     'p3d_fx_conv_fwd_infer_masked_supported': (_i32, [_desc]),
     'p3d_fx_conv_fwd_infer_masked': (_i32, [_desc, _ptr, _ptr, _sz, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
     'p3d_stem_tail_infer': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),

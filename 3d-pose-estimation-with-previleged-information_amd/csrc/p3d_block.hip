@@ -974,6 +974,30 @@ int32_t p3d_fx_conv_fwd_infer(const p3d_conv_desc* d, const float* x, const void
     return fx_conv_fwd(d, x_img ? nullptr : x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
 }
 
+// The same at any map width (fx_conv_kernel's ragged instances <0, 0, 8, false, true>; split-K: the <0, 0, 0, false, true> slabs, then fx_reduce_any_kernel): fp32-fed only
+int32_t p3d_fx_conv_fwd_infer_any_supported(const p3d_conv_desc* d) {
+    return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate >= 0 && d->accumulate <= 1 && fx_fwd_any_applies(d, 32) ? 1 : 0;
+}
+size_t p3d_fx_conv_fwd_infer_any_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_fwd_any_workspace(d) : 0; }
+
+int32_t p3d_fx_conv_fwd_infer_any(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* res, int32_t relu,
+                                  float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    P3D_REQUIRE(d && x && wimg && y, "fx_conv_fwd_infer_any: null argument");
+    P3D_REQUIRE(p3d_fx_conv_fwd_infer_any_supported(d), "fx_conv_fwd_infer_any: shape outside the ragged x3 kernels (N=%d C=%d %dx%d K=%d R=%d stride=%d c_offset=%d "
+                "c_total=%d accumulate=%d)", d->N, d->C, d->H, d->W, d->K, d->R, d->stride, d->c_offset, d->c_total, d->accumulate);
+    P3D_REQUIRE(wimg_bytes == fx_weight_image_bytes(d->K, d->C, d->R * d->S, false), "fx_conv_fwd_infer_any: weight image of %zu B does not belong to K=%d C=%d RS=%d (%zu B)",
+                wimg_bytes, d->K, d->C, d->R * d->S, fx_weight_image_bytes(d->K, d->C, d->R * d->S, false));
+    // (of the base pointers only: inside the tensors the kernel picks 16-B or dword accesses by the address)
+    P3D_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(wimg) |
+                  reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "fx_conv_fwd_infer_any: operands must be 16-B aligned");
+    FxFuse f{};
+    f.wimg = wimg;
+    f.infer = 2; f.res = res; f.relu = relu ? 1 : 0;
+    ProfScope ps(0, d, (hipStream_t)stream);
+    fx_count(0, d);
+    return fx_conv_fwd(d, x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
+}
+
 // The same for a partial convolution (fx_conv_kernel<0, 4, 9>; split-K: the <0, 4, 0> slabs, then fx_reduce_kernel with the factor before b')
 int32_t p3d_fx_conv_fwd_infer_masked_supported(const p3d_conv_desc* d) {
     return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate == 0 && fx_fwd_masked_applies(d) ? 1 : 0;

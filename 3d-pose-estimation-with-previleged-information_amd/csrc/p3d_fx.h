@@ -80,7 +80,7 @@ struct FxFuse {
     const float* tail_c; const float* tail_tab; const float* tail_rc; const float* tail_rtab; const unsigned char* tail_mask; float* tail_partial;
     // FWD, inference (a conv with its eval-mode BatchNorm folded into the weight image and the bias): y = conv + bias (+ y when accumulating) (+ res) (then ReLU), on
     // the split-K path applied by the reduce pass after the slabs are summed
-    int infer;
+    int infer;              // 1; 2: on the ragged instances (any map width; fp32 operand, dense, no partial convolution)
     const float* res;
     int relu;
 };
@@ -104,6 +104,7 @@ int fx_set_enabled(int on);
 void fx_count(int kind, const p3d_conv_desc* d);
 void fx_stats(unsigned long long* counts, double* flops, int reset);
 bool fx_fwd_applies(const p3d_conv_desc* d, int min_m = 96);
+bool fx_fwd_any_applies(const p3d_conv_desc* d, int min_m = 96);       // the ragged forward: fx_fwd_applies without W % 4 == 0 and Wo % 4 == 0 (FxFuse::infer == 2)
 bool fx_dgrad_applies(const p3d_conv_desc* d, int min_m = 96);
 bool fx_wgrad_applies(const p3d_conv_desc* d, int min_m = 96);
 bool fx_dgrad_has_dead_classes(const p3d_conv_desc* d);
@@ -115,6 +116,7 @@ bool fx_fwd_masked_applies(const p3d_conv_desc* d);          // partial convolut
 bool fx_dgrad_masked_applies(const p3d_conv_desc* d);
 bool fx_wgrad_masked_applies(const p3d_conv_desc* d);
 size_t fx_fwd_workspace(const p3d_conv_desc* d);
+size_t fx_fwd_any_workspace(const p3d_conv_desc* d);
 size_t fx_dgrad_workspace(const p3d_conv_desc* d);
 int fx_partial_rows_fwd(const p3d_conv_desc* d);
 int fx_partial_rows_dgrad(const p3d_conv_desc* d);

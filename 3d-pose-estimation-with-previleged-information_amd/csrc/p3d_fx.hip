@@ -148,9 +148,14 @@ __device__ __forceinline__ FxConvParams fx_class_params(const FxConvParams& in) 
 }
 
 // TAPI (image-fed multi-tap launches of wide layers, FxConvParams::tap_inner): the K steps walk the taps innermost
-template <int AMODE, int PRO, int EPIX, bool TAPI = false>
+// RAG ("ragged", fx_conv_fwd with FxFuse::infer == 2): map widths that are not multiples of 4.  The GEMM column stays the flat pixel index, so a thread's four
+// consecutive pixels may straddle an output row or an image: their positions are derived per element when the tap changes, from the first pixel's (row, column,
+// image) kept across the K loop; every fetch is a dword load, and the dense store falls back to dword accesses wherever four pixels do not share an image or a
+// 16-B line.  fp32-fed forward only, epilogues 8 (inference) and 0 (split-K slabs).
+template <int AMODE, int PRO, int EPIX, bool TAPI = false, bool RAG = false>
 __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in) {
     static_assert(!TAPI || AMODE == 1, "the tap-inner K order is an image-fed instance");
+    static_assert(!RAG || (AMODE == 0 && PRO == 0 && (EPIX == 0 || EPIX == 8)), "the ragged instances are the fp32-fed forward with the plain / inference epilogue");
     // EPIX 5 / 6 / 7 = EPI 1 / 2 / 0 with the result first multiplied by emask[pixel] (a partial convolution inside the residual-block executor: the BatchNorm sums are
     // taken of the renormalised result); EPIX 4 = the per-layer partial convolution (factor, no sums); EPIX 8 = EPI 0 then (+ ep_res) (ReLU): inference with a folded
     // BatchNorm (the bias is the folded shift); EPIX 9 = EPIX 8 of a partial convolution: acc * emask[pixel] + bias (+ ep_res) (ReLU), the factor BEFORE the
@@ -215,6 +220,18 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) rXi[pc] = fx_rsrc(p.Ximg + pc * p.plane_bytes + (size_t)nfirst * p.Cred * HWi * 2, left);
     }
+    // RAG: the thread's FIRST pixel as (output row, output column, element offset of its image's reduction row trow); set_tap steps from it pixel by pixel through
+    // row ends and image ends, so the K loop carries three values instead of a position per element
+    // (derived here again rather than kept from the block above, which computes the same row and column: sharing them was tried and the register allocator then
+    // spills 92 B per lane instead of 64, profiles/eval_folded_anysize.md)
+    int rg_oh = 0, rg_ow = 0, rg_img = 0;
+    if constexpr (RAG) {
+        const int cc = col_ok ? col : 0;
+        const int pn = cc / OHW;
+        const int rem = cc - pn * OHW;
+        rg_oh = rem / p.OW; rg_ow = rem - rg_oh * p.OW;
+        rg_img = ((pn - nfirst) * p.Cred + trow) * HWi;
+    }
     const i32x4 rPM = fx_rsrc(PRO == 4 ? p.pmask + (size_t)nfirst * HWi : nullptr, PRO == 4 ? (size_t)(p.N - nfirst) * HWi * sizeof(float) : 0);
 
     // per-tap state of the activation gather (recomputed only when the tap changes)
@@ -232,6 +249,16 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
         const bool row_ok = col_ok && (unsigned)hi < (unsigned)p.Hi;
         if constexpr (AMODE != 0) {
             x_voff[0] = (row_ok && (unsigned)wi0 < (unsigned)p.Wi) ? (img_off + hi * p.Wi + wi0) * 32 + 16 * ph : FX_OOB;
+        } else if constexpr (RAG) {
+            const int dh = p.hoff + ir * p.hstep, dw = p.woff + wshift;         // wave-uniform: the tap's displacement
+            int oh = rg_oh, ow = rg_ow, im = rg_img;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int he = oh * p.hmul + dh, we = ow * p.wmul + dw;
+                const bool ok = col + e < p.NP && (unsigned)he < (unsigned)p.Hi && (unsigned)we < (unsigned)p.Wi;
+                x_voff[e] = ok ? (im + he * p.Wi + we) * 4 : FX_OOB;
+                if (++ow == p.OW) { ow = 0; if (++oh == p.OH) { oh = 0; im += p.Cred * HWi; } }      // the next flat pixel: next row, next image
+            }
         } else {
             x_vec = p.wmul == 1 && ((p.woff + wshift) & 3) == 0;        // wave-uniform: the four pixels are one aligned 16-B group, in or out together
             const int base = (img_off + hi * p.Wi + wi0) * 4;
@@ -269,7 +296,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int so = (f_k + 8 * i) * HWi * 4;             // wave-uniform: reduction chunk + this pass's 8-row step
-                if (x_vec) rx[i] = fx_buffer_load_f32x4(rX, x_voff[0], so, 0);
+                if (!RAG && x_vec) rx[i] = fx_buffer_load_f32x4(rX, x_voff[0], so, 0);
                 else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) rx[i][e] = fx_buffer_load_f32(rX, x_voff[e], so, 0);
@@ -531,6 +558,26 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                 f32x4 v = *reinterpret_cast<const f32x4*>(lds + row * EROW + q * 16);
                 const size_t at = ((size_t)n * p.M + m) * OHW + rem;
                 f32x4* dst = reinterpret_cast<f32x4*>(yout + at);
+                if constexpr (RAG) {
+                    // four pixels of one image on one 16-B line go out as below; anything else element by element, each with its own image and never beyond NP
+                    if (!(rem + 3 < OHW && (reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
+                        int ne = n, re = rem;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e, ++re) {
+                            if (c4 + e >= p.NP) break;
+                            while (re >= OHW) { re -= OHW; ++ne; }
+                            const size_t ae = ((size_t)ne * p.M + m) * OHW + re;
+                            float ve = v[e];
+                            if (accum) ve += yout[ae];
+                            if constexpr (EPIX == 8) {
+                                if (p.ep_res) ve += p.ep_res[ae];
+                                if (p.ep_relu) ve = fmaxf(ve, 0.f);
+                            }
+                            yout[ae] = ve;
+                        }
+                        continue;
+                    }
+                }
                 if (accum) {
                     f32x4 o4;
                     if (p.acc_src) {              // the summand comes from another tensor (through a ReLU's mask bytes): Y is written, never read
@@ -968,6 +1015,21 @@ __global__ __launch_bounds__(256) void fx_reduce_kernel(const float* __restrict_
             dst[0] = r1[0] + r1[1] + r1[2] + r1[3];
             dst[1] = r2[0] + r2[1] + r2[2] + r2[3];
         }
+    }
+}
+
+// The same sum for the ragged forward (fx_conv_kernel's RAG instances: OHW is no multiple of 4, so no channel row is 16-B aligned): one element per thread,
+// y (=|+=) sum over the slabs + bias (+ res) (then ReLU), in the order of the vector kernel.  total = N * M * OHW.
+__global__ __launch_bounds__(256) void fx_reduce_any_kernel(const float* __restrict__ slabs, float* __restrict__ y, const float* __restrict__ bias, int nsplit,
+                                                            size_t slab_stride, unsigned total, int M, int OHW, int accumulate, const float* __restrict__ res, int relu) {
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        float v = slabs[i];
+        for (int z = 1; z < nsplit; ++z) v += slabs[(size_t)z * slab_stride + i];
+        if (bias) v += bias[(i / (unsigned)OHW) % (unsigned)M];
+        if (accumulate) v += y[i];
+        if (res) v += res[i];
+        if (relu) v = fmaxf(v, 0.f);
+        y[i] = v;
     }
 }
 
@@ -1595,6 +1657,10 @@ static bool fx_common(const p3d_conv_desc* d) {
 bool fx_fwd_applies(const p3d_conv_desc* d, int min_m) {
     return fx_common(d) && d->C % FX_BK == 0 && d->C >= 32 && d->Wo % 4 == 0 && d->W % 4 == 0 && d->K >= min_m;
 }
+// the ragged forward (fx_conv_kernel's RAG instances): fx_fwd_applies without its two width clauses
+bool fx_fwd_any_applies(const p3d_conv_desc* d, int min_m) {
+    return fx_common(d) && d->C % FX_BK == 0 && d->C >= 32 && d->K >= min_m;
+}
 // dgrad: reduction channels K in steps of 16; the GEMM columns are the pixels of one stride^2 parity class of the input
 bool fx_dgrad_applies(const p3d_conv_desc* d, int min_m) {
     if (!(fx_common(d) && d->K % FX_BK == 0 && d->K >= 32 && d->C % 4 == 0 && d->C >= min_m && d->Wo % 4 == 0)) return false;
@@ -1686,6 +1752,12 @@ bool fx_wgrad_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && 
 size_t fx_fwd_workspace(const p3d_conv_desc* d) {
     const FxSplit s = fx_fwd_split(d);
     return align256(fx_weight_image_bytes(d->K, d->C, d->R * d->S, false)) + (s.splits > 1 ? (size_t)s.splits * d->N * d->K * d->Ho * d->Wo * sizeof(float) : 0);
+}
+// (ragged: each slab starts on a 16-B line)
+static size_t fx_any_slab_stride(const p3d_conv_desc* d) { return ((size_t)d->N * d->K * d->Ho * d->Wo + 3) & ~(size_t)3; }
+size_t fx_fwd_any_workspace(const p3d_conv_desc* d) {
+    const FxSplit s = fx_fwd_split(d);
+    return align256(fx_weight_image_bytes(d->K, d->C, d->R * d->S, false)) + (s.splits > 1 ? (size_t)s.splits * fx_any_slab_stride(d) * sizeof(float) : 0);
 }
 size_t fx_dgrad_workspace(const p3d_conv_desc* d) {
     const FxSplit s = fx_dgrad_split(d);
@@ -1908,6 +1980,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     const bool img = fuse && fuse->act_img;
     const bool masked = fuse && (fuse->pmask || fuse->emask);
     const bool infer = fuse && fuse->infer;
+    const bool rag = fuse && fuse->infer == 2;          // the ragged instances (p3d_fx_conv_fwd_infer_any): any map width
     const void* wimg = fuse ? fuse->wimg : nullptr;
     if (masked && (!fuse->emask || (bias && !infer) || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr))) {
         set_error("fx_conv_fwd: the partial-convolution instances take the output factor, the input factor exactly for an fp32 operand, and no bias"); return P3D_EINVAL;
@@ -1918,7 +1991,8 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     P3D_REQUIRE(!infer || (!fuse->partial && wimg && (!masked || (!img && !d->accumulate))),
                 "fx_conv_fwd: the inference epilogue takes a cached folded weight image, no other fusion, and a partial convolution only from an fp32 operand");
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
-    const size_t need = fx_fwd_workspace(d);
+    P3D_REQUIRE(!rag || (!img && !masked), "fx_conv_fwd: the ragged forward takes an fp32 operand and no partial convolution");
+    const size_t need = rag ? fx_fwd_any_workspace(d) : fx_fwd_workspace(d);
     if (need && (!workspace || workspace_bytes < need)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
     FxConvParams p{};
     p.X = x; p.Y = y; p.bias = bias;
@@ -1944,10 +2018,22 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     }
     const int tiles_n = (int)ceil_div(p.NP, FX_BN);
     const FxSplit sp = fx_fwd_split(d);
-    const int bm = fx16_bm(d->K, img, sp.splits > 1 ? 0 : pro, sp.splits > 1 ? 0 : epi);
+    const int bm = rag ? 0 : fx16_bm(d->K, img, sp.splits > 1 ? 0 : pro, sp.splits > 1 ? 0 : epi);
     p.tiles_m = (int)ceil_div(d->K, bm ? bm : FX_BM);
     p.tap_inner = img && RS > 1 && d->C >= FX_TAP_INNER_MIN;
-    if (sp.splits > 1) {
+    if (rag) {
+        const dim3 grid((unsigned)(p.tiles_m * tiles_n), (unsigned)sp.splits);
+        if (sp.splits > 1) {
+            p.kchunk = sp.kchunk; p.slab_stride = fx_any_slab_stride(d); p.Y = (float*)ws; p.bias = nullptr;
+            hipLaunchKernelGGL((fx_conv_kernel<0, 0, 0, false, true>), grid, dim3(256), 0, st, p);
+            prof_kernel_done(st);
+            const unsigned total = (unsigned)((size_t)d->N * d->K * d->Ho * d->Wo);          // (fx_common: below 2^31)
+            hipLaunchKernelGGL(fx_reduce_any_kernel, dim3((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096), dim3(256), 0, st, (const float*)ws, y, bias,
+                               sp.splits, p.slab_stride, total, d->K, d->Ho * d->Wo, d->accumulate, p.ep_res, p.ep_relu);
+        } else {
+            hipLaunchKernelGGL((fx_conv_kernel<0, 0, 8, false, true>), grid, dim3(256), 0, st, p);
+        }
+    } else if (sp.splits > 1) {
         p.kchunk = sp.kchunk; p.slab_stride = (size_t)d->N * d->K * d->Ho * d->Wo; p.Y = (float*)ws; p.bias = nullptr;
         const float* em = p.emask;
         p.emask = nullptr;             // (the slabs are raw partial products: the factor, like the sums, belongs to the reduce pass)

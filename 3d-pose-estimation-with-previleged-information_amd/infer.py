@@ -10,7 +10,9 @@ p3d_fx_conv_fwd_infer, whose epilogue adds b', the residual and the ReLU, and on
     ...optimizer step / new running statistics...
     net.refresh()                       # re-fold from the current parameters (one launch)
 
-A conv the x3 forward cannot take (odd sizes, fx_fwd_applies) goes through today's eval path for that layer (ops.conv_bn_eval).
+A conv the x3 forward cannot take (odd sizes, fx_fwd_applies) goes through today's eval path for that layer (ops.conv_bn_eval).  `fold(model,
+any_size=True)` sends such a dense conv to p3d_fx_conv_fwd_infer_any first, the same x3 arithmetic on the same folded image for map widths that are not
+multiples of 4 (the reference's default -side_in 257: 65, 33 and 17 wide maps); the stems and the partial layers at odd sides stay where they are.
 
 The partial-convolution layers of partial_depthnet (stem, layer1, layer2) and partial_fusionnet (conv2, layer5, layer6) fold as well: each conv runs on
 p3d_fx_conv_fwd_infer_masked (mask_in multiplied into the operand, y = relu?(conv * mult + b' + res), the factor before b'), each with its own
@@ -304,6 +306,10 @@ class FoldedNet(_Folded):
     as the image the stem kernels read."""
     WHO, HALF, Conv = 'infer.fold', False, _Conv
 
+    def __init__(self, model, any_size=False):
+        self.any_size = bool(any_size)
+        super().__init__(model)
+
     def _allocate(self, device):
         self.workspace = torch.empty(1 << 20, dtype=torch.uint8, device=device)
         super()._allocate(device)
@@ -345,17 +351,24 @@ class FoldedNet(_Folded):
     _out = _in
 
     def _conv(self, c, x, res=None, relu=False, out=None, accumulate=0):
-        """y = conv(x, w') + b' (+ out) (+ res) (then ReLU) on the folded image; None when the x3 forward cannot take the conv."""
+        """y = conv(x, w') + b' (+ out) (+ res) (then ReLU) on the folded image; None when the x3 forward cannot take the conv.  any_size: a conv
+        p3d_fx_conv_fwd_infer refuses is offered to p3d_fx_conv_fwd_infer_any (any map width) before that."""
         L = lib()
         d = c.desc(x, accumulate) if c.foldable else None
-        if d is None or not L.p3d_fx_conv_fwd_infer_supported(ctypes.byref(d), 0):
+        if d is None:
+            return None
+        if L.p3d_fx_conv_fwd_infer_supported(ctypes.byref(d), 0):
+            name, image = 'p3d_fx_conv_fwd_infer', (None,)      # (the entry's x_img argument: fed the fp32 tensor)
+        elif self.any_size and L.p3d_fx_conv_fwd_infer_any_supported(ctypes.byref(d)):
+            name, image = 'p3d_fx_conv_fwd_infer_any', ()
+        else:
             return None
         x = x.contiguous()
         y = out if out is not None else torch.empty((d.N, d.K, d.Ho, d.Wo), dtype=torch.float32, device=x.device)
-        ws = self._ws(L.p3d_fx_conv_fwd_infer_workspace_bytes(ctypes.byref(d)))
-        check(L.p3d_fx_conv_fwd_infer(ctypes.byref(d), ops._p(x), None, self._at(c.img_off), c.img_bytes,
-                                      self._at(c.bias_off) if c.bias_off is not None else None, ops._p(None if res is None else res.contiguous()),
-                                      int(bool(relu)), ops._p(y), ops._p(ws), ws.numel(), ops._stream()), 'p3d_fx_conv_fwd_infer')
+        ws = self._ws(getattr(L, name + '_workspace_bytes')(ctypes.byref(d)))
+        check(getattr(L, name)(ctypes.byref(d), ops._p(x), *image, self._at(c.img_off), c.img_bytes,
+                               self._at(c.bias_off) if c.bias_off is not None else None, ops._p(None if res is None else res.contiguous()),
+                               int(bool(relu)), ops._p(y), ops._p(ws), ws.numel(), ops._stream()), name)
         return y
 
     def _conv_bn(self, c, x, res=None, relu=False):
@@ -437,10 +450,13 @@ class FoldedNet(_Folded):
 
 class FoldedConv(FoldedNet):
     """One conv (no bias) + eval-mode BatchNorm, folded: FoldedConv(conv, bn)(x, res=None, relu=False) = relu(bn(conv(x)) + res).  For a PartialConv
-    the validity mask comes along: FoldedConv(pconv, bn)(x, res, relu, veil=mask_in) = (relu(bn(pconv(x, mask_in)[0]) + res), mask_out)."""
+    the validity mask comes along: FoldedConv(pconv, bn)(x, res, relu, veil=mask_in) = (relu(bn(pconv(x, mask_in)[0]) + res), mask_out).
+    any_size (default False: a map width p3d_fx_conv_fwd_infer refuses runs on ops.conv_bn_eval, the fp32-MFMA kernel, which tests rely on): offer such a
+    dense conv to p3d_fx_conv_fwd_infer_any first."""
     WHO = 'infer.FoldedConv'
 
-    def __init__(self, conv, bn):
+    def __init__(self, conv, bn, any_size=False):
+        self.any_size = bool(any_size)
         self.model, self.stems = torch.nn.ModuleList([conv, bn]), {}      # (model: what refresh() checks)
         self.conv = _Conv(conv, bn)
         self.convs = [self.conv]
@@ -453,9 +469,12 @@ class FoldedConv(FoldedNet):
             return self._pconv(self.conv, x, veil, res, relu) if self.conv.partial else self._conv_bn(self.conv, x, res, relu)
 
 
-def fold(model):
-    """FoldedNet of a network in eval mode (every BatchNorm frozen); raises P3DError for a BatchNorm in training mode or a -half_acc model."""
-    return FoldedNet(getattr(model, 'module', model))
+def fold(model, any_size=False):
+    """FoldedNet of a network in eval mode (every BatchNorm frozen); raises P3DError for a BatchNorm in training mode or a -half_acc model.
+    any_size: a dense conv whose map widths are not multiples of 4 (every layer behind the stem at -side_in 257) runs on p3d_fx_conv_fwd_infer_any
+    instead of the per-layer fallback.  The default stays False: without the keyword a refused layer lands on ops.conv_bn_eval (the fp32-MFMA
+    kernel) exactly as before, which is what the existing tests of the fallback count."""
+    return FoldedNet(getattr(model, 'module', model), any_size=any_size)
 
 
 # ---- -half_acc: BatchNorm folded into the fp16 convolutions ------------------------------------------------------------------------------

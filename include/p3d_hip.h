@@ -296,6 +296,16 @@ int32_t p3d_fx_conv_fwd_infer_supported(const p3d_conv_desc* d, int32_t image_fe
 size_t p3d_fx_conv_fwd_infer_workspace_bytes(const p3d_conv_desc* d);
 int32_t p3d_fx_conv_fwd_infer(const p3d_conv_desc* d, const float* x, const void* x_img, const void* wimg, size_t wimg_bytes, const float* bias, const float* res,
                               int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* The same at ANY map width (the reference's default -side_in 257: maps of 65, 33 and 17): y = conv(x, w') + b' (+ y when d->accumulate) (+ res) (then ReLU) on the
+ * "ragged" instances of the x3 forward, which take their four pixels element by element and store with 16-B or dword accesses as the address allows.  fp32 x only (no
+ * activation image); wimg is the same folded image (p3d_fx_fold_bn_images kind 0, the same byte-size check); only the BASE pointers x, y, res, wimg and workspace need
+ * 16-B alignment.  Split-K launches sum their slabs in a scalar pass with the same epilogue.  Workspace: p3d_fx_conv_fwd_infer_any_workspace_bytes.
+ * supported: p3d_fx_conv_fwd_infer_supported(d, 0) without its W % 4 == 0 and Wo % 4 == 0 (C % 16 == 0, C >= 32, K >= 32, odd square filter, stride <= 2, no channel
+ * window, accumulate 0 / 1, fewer than 2^31 elements per tensor); host only. */
+int32_t p3d_fx_conv_fwd_infer_any_supported(const p3d_conv_desc* d);
+size_t p3d_fx_conv_fwd_infer_any_workspace_bytes(const p3d_conv_desc* d);
+int32_t p3d_fx_conv_fwd_infer_any(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* res, int32_t relu,
+                                  float* y, void* workspace, size_t workspace_bytes, void* stream);
 /* The same for a PARTIAL convolution (partial_conv.py:32-57) with its BatchNorm folded: y = relu?(conv(x * mask_in, w') * mult + b' + res), the factor applied before
  * b' (an empty window, mult = 0, gives relu(b' + res), what the reference's BatchNorm makes of the 0 its partial conv writes there).  mask_in [N][1][H][W], mult
  * [N][1][Ho][Wo] (ops.mask_count); fp32 x only, 16-B aligned operands, wimg as above; bias / res may be NULL.  Workspace: p3d_fx_conv_fwd_infer_workspace_bytes.
