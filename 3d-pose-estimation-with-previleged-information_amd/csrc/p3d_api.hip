@@ -11,6 +11,15 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
+
+int32_t name_entry(const char* entry, int32_t rc) {
+    if (rc == P3D_EWORKSPACE) {
+        char old[sizeof(g_err)];
+        snprintf(old, sizeof(old), "%s", g_err);
+        snprintf(g_err, sizeof(g_err), "%s: %s", entry, old);
+    }
+    return rc;
+}
 }  // namespace p3d
 
 extern "C" {

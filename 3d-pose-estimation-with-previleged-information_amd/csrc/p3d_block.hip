@@ -913,7 +913,7 @@ int32_t p3d_fx_conv_fwd_img(const p3d_conv_desc* d, const void* x_img, const flo
     f.act_img = x_img; f.wimg = wimg;
     ProfScope ps(0, d, (hipStream_t)stream);
     fx_count(0, d);
-    return fx_conv_fwd(d, nullptr, w, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
+    return name_entry("fx_conv_fwd_img", fx_conv_fwd(d, nullptr, w, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
 }
 
 int32_t p3d_fx_conv_dgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
@@ -926,7 +926,7 @@ int32_t p3d_fx_conv_dgrad_img(const p3d_conv_desc* d, const void* dy_img, const 
     fx_count(1, d);
     if (fx_dgrad_has_dead_classes(d) && !d->accumulate)
         if (hipMemsetAsync(dx, 0, (size_t)d->N * d->C * d->H * d->W * sizeof(float), (hipStream_t)stream) != hipSuccess) { set_error("fx_conv_dgrad_img: memset failed"); return P3D_ELAUNCH; }
-    return fx_conv_dgrad(d, nullptr, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream);
+    return name_entry("fx_conv_dgrad_img", fx_conv_dgrad(d, nullptr, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream));
 }
 
 // x: the fp32 input, used when x_img is NULL (the block input of a residual block); otherwise ignored
@@ -971,7 +971,7 @@ int32_t p3d_fx_conv_fwd_infer(const p3d_conv_desc* d, const float* x, const void
     f.infer = 1; f.res = res; f.relu = relu ? 1 : 0;
     ProfScope ps(0, d, (hipStream_t)stream);
     fx_count(0, d);
-    return fx_conv_fwd(d, x_img ? nullptr : x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
+    return name_entry("fx_conv_fwd_infer", fx_conv_fwd(d, x_img ? nullptr : x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
 }
 
 // The same at any map width (fx_conv_kernel's ragged instances <0, 0, 8, false, true>; split-K: the <0, 0, 0, false, true> slabs, then fx_reduce_any_kernel): fp32-fed only
@@ -995,7 +995,7 @@ int32_t p3d_fx_conv_fwd_infer_any(const p3d_conv_desc* d, const float* x, const 
     f.infer = 2; f.res = res; f.relu = relu ? 1 : 0;
     ProfScope ps(0, d, (hipStream_t)stream);
     fx_count(0, d);
-    return fx_conv_fwd(d, x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
+    return name_entry("fx_conv_fwd_infer_any", fx_conv_fwd(d, x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
 }
 
 // The same for a partial convolution (fx_conv_kernel<0, 4, 9>; split-K: the <0, 4, 0> slabs, then fx_reduce_kernel with the factor before b')
@@ -1019,7 +1019,7 @@ int32_t p3d_fx_conv_fwd_infer_masked(const p3d_conv_desc* d, const float* x, con
     f.infer = 1; f.res = res; f.relu = relu ? 1 : 0;
     ProfScope ps(0, d, (hipStream_t)stream);
     fx_count(0, d);
-    return fx_conv_fwd(d, x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
+    return name_entry("fx_conv_fwd_infer_masked", fx_conv_fwd(d, x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
 }
 
 // The stem conv1 = Conv2d(Cin <= 4, K, 7, stride 2, padding 3) (depthnet.py:138) on the x3 kernels: a 4x4 stride-1 convolution over a space-to-depth image of the
@@ -1072,7 +1072,7 @@ int32_t p3d_stem_wgrad_masked(const float* dy, const float* mult, const void* x_
     const p3d_conv_desc d = stem_desc(N, Cin, H, W, K);
     ProfScope ps(2, &d, (hipStream_t)stream);
     fx_count(2, &d);
-    return fx_stem_wgrad(dy, mult, x_img, dw, N, Cin, H, W, K, accumulate, workspace, workspace_bytes, (hipStream_t)stream);
+    return name_entry(mult ? "stem_wgrad_masked" : "stem_wgrad", fx_stem_wgrad(dy, mult, x_img, dw, N, Cin, H, W, K, accumulate, workspace, workspace_bytes, (hipStream_t)stream));
 }
 
 // All weight images of a network in one launch.  jobs: device array of njobs records {const float* w; void* img_fwd; void* img_bwd; int32 K, C, RS, pad} (40 bytes each;

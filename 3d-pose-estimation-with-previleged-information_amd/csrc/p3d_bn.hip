@@ -498,8 +498,8 @@ static int32_t bn_bwd_common(const float* dy, const float* x, const float* y, co
 int32_t p3d_bn_train_bwd(const float* dy, const float* x, const float* y, const float* gamma, const float* beta, const float* save_mean,
                          const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta, int32_t N, int32_t C,
                          int32_t HW, int32_t relu, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-    return bn_bwd_common(dy, x, y, gamma, beta, save_mean, save_invstd, 0, 0.f, dx, dres, dgamma, dbeta, N, C, HW, relu, 1, accumulate, workspace,
-                         workspace_bytes, stream);
+    return name_entry("bn_train_bwd", bn_bwd_common(dy, x, y, gamma, beta, save_mean, save_invstd, 0, 0.f, dx, dres, dgamma, dbeta, N, C, HW, relu, 1, accumulate,
+                                                    workspace, workspace_bytes, stream));
 }
 
 int32_t p3d_bn_eval_fwd(const float* x, const float* res, const float* gamma, const float* beta, const float* running_mean,
@@ -518,8 +518,8 @@ int32_t p3d_bn_eval_fwd(const float* x, const float* res, const float* gamma, co
 int32_t p3d_bn_eval_bwd(const float* dy, const float* x, const float* y, const float* gamma, const float* running_mean,
                         const float* running_var, float* dx, float* dres, float* dgamma, float* dbeta, int32_t N, int32_t C,
                         int32_t HW, float eps, int32_t relu, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-    return bn_bwd_common(dy, x, y, gamma, nullptr, running_mean, running_var, 1, eps, dx, dres, dgamma, dbeta, N, C, HW, relu, 0, accumulate, workspace,
-                         workspace_bytes, stream);
+    return name_entry("bn_eval_bwd", bn_bwd_common(dy, x, y, gamma, nullptr, running_mean, running_var, 1, eps, dx, dres, dgamma, dbeta, N, C, HW, relu, 0, accumulate,
+                                                   workspace, workspace_bytes, stream));
 }
 
 int32_t p3d_stem_tail_supported(int32_t N, int32_t C, int32_t H, int32_t W) { return N > 0 && C > 0 && H >= 2 && W >= 4 && H % 2 == 0 && W % 4 == 0; }

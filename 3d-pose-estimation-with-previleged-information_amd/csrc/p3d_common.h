@@ -9,6 +9,8 @@
 namespace p3d {
 
 void set_error(const char* fmt, ...);
+// for an entry point that shares its launch path with others: a P3D_EWORKSPACE text written there gets the entry's own name in front ("entry: path: ...")
+int32_t name_entry(const char* entry, int32_t rc);
 
 inline int32_t check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -112,7 +112,7 @@ int32_t p3d_distill_fwd_bwd(const float* teach, const float* student, const floa
     P3D_REQUIRE(teach && student && atten && loss, "distill: null tensor");
     P3D_REQUIRE(B > 0 && C > 0 && HW > 0 && mode >= 0 && mode <= 2, "distill: bad shape/mode B=%d C=%d HW=%d mode=%d", B, C, HW, mode);
     if (!workspace || workspace_bytes < p3d_distill_workspace_bytes(B)) {
-        set_error("distill: workspace too small");
+        set_error("distill_fwd_bwd: workspace too small");
         return P3D_EWORKSPACE;
     }
     dim3 grid(B, DISTILL_SPLIT);

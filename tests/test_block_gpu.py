@@ -452,6 +452,7 @@ def opening_sums_case(pkg, consumer, h, w):
         assert ob.TAIL_STATS['opening_passes_skipped'] == before['opening_passes_skipped']
         for k in base2:
             assert (fused2[k] - base2[k]).abs().max().item() <= 2e-5 * base2[k].abs().max().item(), k
+    return dict(base=base, fused=fused)
 
 
 #                kind          inplanes planes stride dil  N  H   downsample

@@ -27,6 +27,9 @@ def test_alpha_schedule(pkg):
     assert tr.get_dist_weight(6) == 0.1 and tr.get_dist_weight(30) == 0.1
 
 
+DISTILL_TOL = 1e-5          # loss and student gradient of p3d_distill_fwd_bwd against the reference, relative (fp32 sums of a few thousand terms)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('mode', ['l2', 'sigmoid', 'bce'])
 def test_distill_loss_matches_reference(mode, pkg):
@@ -34,9 +37,9 @@ def test_distill_loss_matches_reference(mode, pkg):
     s = torch.from_numpy(g['s']).cuda().requires_grad_(True)
     weighted, raw = pkg.ops.distill_loss(torch.from_numpy(g['t']).cuda(), s, torch.from_numpy(g['a']).cuda(), mode, weight=1.0)
     weighted.backward()
-    assert float(raw) == pytest.approx(float(g[mode + '.loss']), rel=1e-5)
+    assert float(raw) == pytest.approx(float(g[mode + '.loss']), rel=DISTILL_TOL)
     ref = g[mode + '.ds']
-    assert np.abs(s.grad.cpu().numpy() - ref).max() < 1e-5 * max(np.abs(ref).max(), 1e-12)
+    assert np.abs(s.grad.cpu().numpy() - ref).max() < DISTILL_TOL * max(np.abs(ref).max(), 1e-12)
     # weight scales the gradient, not the reported loss
     s2 = torch.from_numpy(g['s']).cuda().requires_grad_(True)
     w2, raw2 = pkg.ops.distill_loss(torch.from_numpy(g['t']).cuda(), s2, torch.from_numpy(g['a']).cuda(), mode, weight=0.25, unit_grad=True)
