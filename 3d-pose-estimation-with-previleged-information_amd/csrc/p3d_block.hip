@@ -956,70 +956,54 @@ int32_t p3d_fx_conv_fwd_infer_supported(const p3d_conv_desc* d, int32_t image_fe
     return !image_fed || (d->C % 16 == 0 && (d->H * d->W) % 4 == 0) ? 1 : 0;
 }
 size_t p3d_fx_conv_fwd_infer_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_fwd_workspace(d) : 0; }
-
-int32_t p3d_fx_conv_fwd_infer(const p3d_conv_desc* d, const float* x, const void* x_img, const void* wimg, size_t wimg_bytes, const float* bias, const float* res,
-                              int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
-    P3D_REQUIRE(d && (x || x_img) && wimg && y, "fx_conv_fwd_infer: null argument");
-    P3D_REQUIRE(p3d_fx_conv_fwd_infer_supported(d, x_img != nullptr), "fx_conv_fwd_infer: shape outside the x3 kernels (N=%d C=%d %dx%d K=%d R=%d stride=%d c_offset=%d c_total=%d)",
-                d->N, d->C, d->H, d->W, d->K, d->R, d->stride, d->c_offset, d->c_total);
-    P3D_REQUIRE(wimg_bytes == fx_weight_image_bytes(d->K, d->C, d->R * d->S, false), "fx_conv_fwd_infer: weight image of %zu B does not belong to K=%d C=%d RS=%d (%zu B)",
-                wimg_bytes, d->K, d->C, d->R * d->S, fx_weight_image_bytes(d->K, d->C, d->R * d->S, false));
-    P3D_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(x_img) |
-                  reinterpret_cast<uintptr_t>(wimg) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "fx_conv_fwd_infer: operands must be 16-B aligned");
-    FxFuse f{};
-    f.act_img = x_img; f.wimg = wimg;
-    f.infer = 1; f.res = res; f.relu = relu ? 1 : 0;
-    ProfScope ps(0, d, (hipStream_t)stream);
-    fx_count(0, d);
-    return name_entry("fx_conv_fwd_infer", fx_conv_fwd(d, x_img ? nullptr : x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
-}
-
-// The same at any map width (fx_conv_kernel's ragged instances <0, 0, 8, false, true>; split-K: the <0, 0, 0, false, true> slabs, then fx_reduce_any_kernel): fp32-fed only
+// The same at any map width (fx_conv_kernel's ragged instances; split-K: their slabs, then fx_reduce_any_kernel): fp32-fed only
 int32_t p3d_fx_conv_fwd_infer_any_supported(const p3d_conv_desc* d) {
     return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate >= 0 && d->accumulate <= 1 && fx_fwd_any_applies(d, 32) ? 1 : 0;
 }
 size_t p3d_fx_conv_fwd_infer_any_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_fwd_any_workspace(d) : 0; }
-
-int32_t p3d_fx_conv_fwd_infer_any(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* res, int32_t relu,
-                                  float* y, void* workspace, size_t workspace_bytes, void* stream) {
-    P3D_REQUIRE(d && x && wimg && y, "fx_conv_fwd_infer_any: null argument");
-    P3D_REQUIRE(p3d_fx_conv_fwd_infer_any_supported(d), "fx_conv_fwd_infer_any: shape outside the ragged x3 kernels (N=%d C=%d %dx%d K=%d R=%d stride=%d c_offset=%d "
-                "c_total=%d accumulate=%d)", d->N, d->C, d->H, d->W, d->K, d->R, d->stride, d->c_offset, d->c_total, d->accumulate);
-    P3D_REQUIRE(wimg_bytes == fx_weight_image_bytes(d->K, d->C, d->R * d->S, false), "fx_conv_fwd_infer_any: weight image of %zu B does not belong to K=%d C=%d RS=%d (%zu B)",
-                wimg_bytes, d->K, d->C, d->R * d->S, fx_weight_image_bytes(d->K, d->C, d->R * d->S, false));
-    // (of the base pointers only: inside the tensors the kernel picks 16-B or dword accesses by the address)
-    P3D_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(wimg) |
-                  reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "fx_conv_fwd_infer_any: operands must be 16-B aligned");
-    FxFuse f{};
-    f.wimg = wimg;
-    f.infer = 2; f.res = res; f.relu = relu ? 1 : 0;
-    ProfScope ps(0, d, (hipStream_t)stream);
-    fx_count(0, d);
-    return name_entry("fx_conv_fwd_infer_any", fx_conv_fwd(d, x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
-}
-
-// The same for a partial convolution (fx_conv_kernel<0, 4, 9>; split-K: the <0, 4, 0> slabs, then fx_reduce_kernel with the factor before b')
+// The same for a partial convolution (FX_EPI_INFER_FACTOR; split-K: fx_reduce_kernel applies the factor before b')
 int32_t p3d_fx_conv_fwd_infer_masked_supported(const p3d_conv_desc* d) {
     return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate == 0 && fx_fwd_masked_applies(d) ? 1 : 0;
 }
 
-int32_t p3d_fx_conv_fwd_infer_masked(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* mask_in,
-                                     const float* mult, const float* res, int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
-    P3D_REQUIRE(d && x && wimg && mask_in && mult && y, "fx_conv_fwd_infer_masked: null argument");
-    P3D_REQUIRE(p3d_fx_conv_fwd_infer_masked_supported(d), "fx_conv_fwd_infer_masked: shape outside the masked x3 kernels (N=%d C=%d %dx%d K=%d R=%d stride=%d c_offset=%d "
-                "c_total=%d accumulate=%d)", d->N, d->C, d->H, d->W, d->K, d->R, d->stride, d->c_offset, d->c_total, d->accumulate);
-    P3D_REQUIRE(wimg_bytes == fx_weight_image_bytes(d->K, d->C, d->R * d->S, false), "fx_conv_fwd_infer_masked: weight image of %zu B does not belong to K=%d C=%d RS=%d (%zu B)",
-                wimg_bytes, d->K, d->C, d->R * d->S, fx_weight_image_bytes(d->K, d->C, d->R * d->S, false));
-    P3D_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(mask_in) |
-                  reinterpret_cast<uintptr_t>(mult) | reinterpret_cast<uintptr_t>(wimg) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
-                "fx_conv_fwd_infer_masked: operands must be 16-B aligned");
+// What the three inference entries share: the checks (every text opens with the entry's own name), the profile bracket, the path counter and the launch.
+// f says which entry this is: infer == 2 the ragged one, a pmask the masked one.  (Alignment, ragged: of the base pointers only; inside the tensors the kernel picks
+// 16-B or dword accesses by the address.)
+static FxFuse infer_fuse(int infer, const void* x_img, const void* wimg, const float* mask_in, const float* mult, const float* res, int32_t relu) {
     FxFuse f{};
-    f.wimg = wimg;
-    f.pmask = mask_in; f.emask = mult;
-    f.infer = 1; f.res = res; f.relu = relu ? 1 : 0;
+    f.infer = infer; f.act_img = x_img; f.wimg = wimg; f.pmask = mask_in; f.emask = mult; f.res = res; f.relu = relu ? 1 : 0; return f;
+}
+static int32_t fx_infer_entry(const char* name, bool args, const p3d_conv_desc* d, const float* x, size_t wimg_bytes, const float* bias, float* y, const FxFuse& f,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    P3D_REQUIRE(args, "%s: null argument", name);
+    const char* kind = f.infer == 2 ? "ragged " : f.pmask ? "masked " : "";
+    char acc[32] = "";
+    if (kind[0]) snprintf(acc, sizeof(acc), " accumulate=%d", d->accumulate);
+    P3D_REQUIRE(f.infer == 2 ? p3d_fx_conv_fwd_infer_any_supported(d) : f.pmask ? p3d_fx_conv_fwd_infer_masked_supported(d) : p3d_fx_conv_fwd_infer_supported(d, f.act_img != nullptr),
+                "%s: shape outside the %sx3 kernels (N=%d C=%d %dx%d K=%d R=%d stride=%d c_offset=%d c_total=%d%s)", name, kind, d->N, d->C, d->H, d->W, d->K, d->R, d->stride,
+                d->c_offset, d->c_total, acc);
+    const size_t want = fx_weight_image_bytes(d->K, d->C, d->R * d->S, false);
+    P3D_REQUIRE(wimg_bytes == want, "%s: weight image of %zu B does not belong to K=%d C=%d RS=%d (%zu B)", name, wimg_bytes, d->K, d->C, d->R * d->S, want);
+    auto u = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    P3D_REQUIRE(((u(x) | u(y) | u(f.res) | u(f.act_img) | u(f.pmask) | u(f.emask) | u(f.wimg) | u(workspace)) & 15) == 0, "%s: operands must be 16-B aligned", name);
     ProfScope ps(0, d, (hipStream_t)stream);
     fx_count(0, d);
-    return name_entry("fx_conv_fwd_infer_masked", fx_conv_fwd(d, x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
+    return name_entry(name, fx_conv_fwd(d, f.act_img ? nullptr : x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
+}
+int32_t p3d_fx_conv_fwd_infer(const p3d_conv_desc* d, const float* x, const void* x_img, const void* wimg, size_t wimg_bytes, const float* bias, const float* res,
+                              int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    return fx_infer_entry("fx_conv_fwd_infer", d && (x || x_img) && wimg && y, d, x, wimg_bytes, bias, y, infer_fuse(1, x_img, wimg, nullptr, nullptr, res, relu), workspace,
+                          workspace_bytes, stream);
+}
+int32_t p3d_fx_conv_fwd_infer_any(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* res, int32_t relu,
+                                  float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    return fx_infer_entry("fx_conv_fwd_infer_any", d && x && wimg && y, d, x, wimg_bytes, bias, y, infer_fuse(2, nullptr, wimg, nullptr, nullptr, res, relu), workspace,
+                          workspace_bytes, stream);
+}
+int32_t p3d_fx_conv_fwd_infer_masked(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* mask_in,
+                                     const float* mult, const float* res, int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    return fx_infer_entry("fx_conv_fwd_infer_masked", d && x && wimg && mask_in && mult && y, d, x, wimg_bytes, bias, y, infer_fuse(1, nullptr, wimg, mask_in, mult, res, relu),
+                          workspace, workspace_bytes, stream);
 }
 
 // The stem conv1 = Conv2d(Cin <= 4, K, 7, stride 2, padding 3) (depthnet.py:138) on the x3 kernels: a 4x4 stride-1 convolution over a space-to-depth image of the

@@ -86,6 +86,25 @@ struct FxFuse {
 };
 constexpr int FX_TAB = 8;   // floats per channel of a table
 
+// The epilogue of a forward / data-gradient launch: EPIX of fx_conv_kernel<AMODE, PRO, EPIX, TAPI, RAG> and EPI of fx16_conv_kernel<BM, EPI, TAPI> (plain ints: the values
+// are part of the kernels' mangled names, which the profiles and tools/ quote).  Every code stores the result (+ bias); the three functions below take a code apart.
+// Under split-K the slabs come from the FX_EPI_STORE instance and the rest of the epilogue is done by the pass that sums them (fx_reduce_kernel).
+enum : int {
+    FX_EPI_STORE = 0,
+    FX_EPI_STATS = 1,               // sums 1: per-(pixel tile, channel) partial sums of y, y^2 (the BatchNorm behind the conv)
+    FX_EPI_BWD_SUMS = 2,            // sums 2: of g, g * (c2 - mean), g = y * [c2 * sc + sh > 0] (the BatchNorm + ReLU in front of the conv whose input gradient this is; ep_c = c2, ep_tab its table)
+    FX_EPI_TAIL_SUMS = 3,           // sums 3: the opening sums of the producer block's backward pass (FxConvParams::tail_*), on the data gradient that writes a block's dx last
+    FX_EPI_FACTOR = 4,              // factor: the result times emask[pixel], in the register view; the per-layer partial convolution (fp32-fed, PRO 4)
+    FX_EPI_FACTOR_STATS = 5, FX_EPI_FACTOR_BWD_SUMS = 6, FX_EPI_FACTOR_IMG = 7,     // factor with sums 1 / sums 2 / image-fed: partial convolutions inside the residual-block
+                                    // executor, the sums taken of the renormalised result.  (fx16_conv_kernel reads the factor pointer at run time: fx16_epi)
+    FX_EPI_INFER = 8,               // inference tail: (+ ep_res) (ReLU), the bias being the shift b' of a folded BatchNorm
+    FX_EPI_INFER_FACTOR = 9,        // the same of a partial convolution: acc * emask[pixel] + b' (+ ep_res) (ReLU), the factor BEFORE the folded shift and in the staged store (an
+                                    // empty window, emask = 0, gives relu(b' + res): the reference's partial conv writes 0 there and the BatchNorm behind it maps 0 to b')
+};
+constexpr int fx_epi_sums(int epi) { return epi == FX_EPI_STATS || epi == FX_EPI_FACTOR_STATS ? 1 : epi == FX_EPI_BWD_SUMS || epi == FX_EPI_FACTOR_BWD_SUMS ? 2 : epi == FX_EPI_TAIL_SUMS ? 3 : 0; }
+constexpr bool fx_epi_factor(int epi) { return epi >= FX_EPI_FACTOR && epi <= FX_EPI_FACTOR_IMG; }
+constexpr bool fx_epi_infer(int epi) { return epi == FX_EPI_INFER || epi == FX_EPI_INFER_FACTOR; }
+
 // HIP-event bracket around one conv launch (p3d_block.hip keeps the records; no-op unless p3d_profile_enable(1))
 struct ProfScope {
     hipEvent_t a = nullptr, b = nullptr, m = nullptr;        // m: where the conv kernel itself ended, when slab / split-K sums follow inside the bracket

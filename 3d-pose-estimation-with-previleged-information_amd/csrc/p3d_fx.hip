@@ -132,9 +132,7 @@ __device__ __forceinline__ void fx_tr_frag_off(int lane, int cb, int (&off)[2]) 
 // AMODE 0: the activation operand is fp32 NCHW; a thread fetches four consecutive pixels of two reduction rows per K step and splits them ("tr" image).
 //          PRO 4 multiplies by pmask[pixel] first (partial convolution: one factor per pixel, all channels).
 // AMODE 1: the activation operand is a pre-split activation image; a thread copies one 16-B chunk (pixel, half of the 16 channels) per plane ("rc" image).
-// EPI: 0 store; 1 store + per-(pixel tile, channel) partial sums of y, y^2 (the BatchNorm behind the conv); 2 store + partial sums of g, g * (c2 - mean) with
-//      g = y * [c2 * sc + sh > 0] (the BatchNorm + ReLU in front of the conv whose input gradient this is; ep_c = c2 laid out like the output, ep_tab = its
-//      table); 4 store y * emask[pixel] (partial convolution).  Under split-K the epilogue work is done by fx_reduce_kernel instead.
+// EPIX: the epilogue, one of the FX_EPI_* codes (p3d_fx.h); below SUMS is the kind of partial sums it takes and EM whether it multiplies by emask[pixel] in registers.
 // the launch's parameters as block z sees them: a strided data gradient runs its parity classes as the z slices of one grid (the longest K loops first), each a dense
 // GEMM over the filter taps that reach the class
 __device__ __forceinline__ FxConvParams fx_class_params(const FxConvParams& in) {
@@ -155,20 +153,16 @@ __device__ __forceinline__ FxConvParams fx_class_params(const FxConvParams& in) 
 template <int AMODE, int PRO, int EPIX, bool TAPI = false, bool RAG = false>
 __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in) {
     static_assert(!TAPI || AMODE == 1, "the tap-inner K order is an image-fed instance");
-    static_assert(!RAG || (AMODE == 0 && PRO == 0 && (EPIX == 0 || EPIX == 8)), "the ragged instances are the fp32-fed forward with the plain / inference epilogue");
-    // EPIX 5 / 6 / 7 = EPI 1 / 2 / 0 with the result first multiplied by emask[pixel] (a partial convolution inside the residual-block executor: the BatchNorm sums are
-    // taken of the renormalised result); EPIX 4 = the per-layer partial convolution (factor, no sums); EPIX 8 = EPI 0 then (+ ep_res) (ReLU): inference with a folded
-    // BatchNorm (the bias is the folded shift); EPIX 9 = EPIX 8 of a partial convolution: acc * emask[pixel] + bias (+ ep_res) (ReLU), the factor BEFORE the
-    // folded shift (an empty window, emask = 0, gives relu(b' + res): the reference's partial conv writes 0 there and the BatchNorm behind it maps 0 to b')
-    constexpr int EPI = EPIX == 5 ? 1 : EPIX == 6 ? 2 : EPIX == 7 || EPIX == 8 || EPIX == 9 ? 0 : EPIX;
-    constexpr bool EM = EPIX == 4 || (EPIX >= 5 && EPIX <= 7);
+    static_assert(!RAG || (AMODE == 0 && PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER)), "the ragged instances are the fp32-fed forward with the plain / inference epilogue");
+    constexpr int SUMS = fx_epi_sums(EPIX);
+    constexpr bool EM = fx_epi_factor(EPIX);
     const FxConvParams p = fx_class_params(p_in);
     static_assert(AMODE == 0 || PRO == 0, "the partial-convolution factor is applied by the in-kernel split");
     // one shared array: two buffers of [3 pixel pieces][3 channel pieces]; after the K loop the result tile on its way out (33.8 KB) and, behind it, the
-    // per-channel sums of EPI 1 / 2
+    // per-channel sums of SUMS 1 / 2
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * 6 * FX_PIECE];
     constexpr int BUFB = 6 * FX_PIECE, CH0 = 3 * FX_PIECE;                             // bytes per buffer; offset of the channel (weight) pieces in a buffer
-    float (*const red)[2][128] = reinterpret_cast<float (*)[2][128]>(lds + 40960);     // EPI 1 / 2: [wave along pixels][sum kind][channel]
+    float (*const red)[2][128] = reinterpret_cast<float (*)[2][128]>(lds + 40960);     // SUMS 1 / 2: [wave along pixels][sum kind][channel]
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), wm = wave >> 1, wn = wave & 1;
     // XCD-aware remap (bijective): blocks b, b+8, ... share an XCD; give each XCD a contiguous run of logical ids (pixel tile outer, channel tile inner)
     int bid;
@@ -414,24 +408,24 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     const bool dense = split || (p.oxs == 1 && p.oys == 1 && p.oy0 == 0 && p.ox0 == 0 && p.YW == p.OW && p.YH == p.OH);
     float ssum[2] = {0.f, 0.f}, ssq[2] = {0.f, 0.f}, sthird[2] = {0.f, 0.f};
     float esc[2] = {0.f, 0.f}, esh[2] = {0.f, 0.f}, emean[2] = {0.f, 0.f};
-    if constexpr (EPI == 2) {
+    if constexpr (SUMS == 2) {
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             const int m = m0 + wm * 64 + b * 32 + fr;
             if (m < p.M) { esc[b] = p.ep_tab[8 * m]; esh[b] = p.ep_tab[8 * m + 1]; emean[b] = p.ep_tab[8 * m + 2]; }
         }
     }
-    if constexpr (EPI == 3) {             // emean: the mean of the producer's closing BatchNorm; esc: that of its downsample BatchNorm
+    if constexpr (SUMS == 3) {             // emean: the mean of the producer's closing BatchNorm; esc: that of its downsample BatchNorm
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             const int m = m0 + wm * 64 + b * 32 + fr;
             if (m < p.M) { emean[b] = p.tail_tab[8 * m + 2]; esc[b] = p.tail_rc ? p.tail_rtab[8 * m + 2] : 0.f; }
         }
     }
-    if constexpr (EPI == 3) {
+    if constexpr (SUMS == 3) {
         // The launch that writes a block's dx last (dense, unsplit, accumulating): the summand joins HERE, in the register view, so that v is the final gradient,
         // and the opening sums of the producer block's backward pass (g = v [producer's out > 0]; its closing and its downsample BatchNorm) are per-lane adds like
-        // EPI 2's.  Straight-line code: out-of-range lanes read element 0 and contribute nothing, optional operands are pointer selects, so no branch separates the
+        // SUMS 2's.  Straight-line code: out-of-range lanes read element 0 and contribute nothing, optional operands are pointer selects, so no branch separates the
         // loads and the compiler keeps several iterations' worth in flight (one memory round trip per iteration otherwise, which cost more than the pass saved).
         const float* src = p.acc_src ? p.acc_src : yout;                       // what is added to the result
         const unsigned char* amask = p.acc_mask ? p.acc_mask : p.tail_mask;    // (tail_mask: any readable bytes; forced to "all pass" below)
@@ -477,7 +471,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            if constexpr (EPI == 3) continue;
+            if constexpr (SUMS == 3) continue;
             const int c4 = n0 + wn * 64 + a * 32 + 8 * g + 4 * fh;         // first of this lane's 4 consecutive pixels
             if (c4 >= p.NP) continue;
             const int n = c4 / OHW, rem = c4 - n * OHW, oh = rem / p.OW, ow = rem - oh * p.OW;
@@ -486,7 +480,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                 const int m = m0 + wm * 64 + b * 32 + fr;
                 if (m >= p.M) continue;
                 f32x4 v = {acc[a][b][4 * g], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]};
-                if (!split && EPIX != 9) {        // (EPIX 9: factor and bias in the staged store below, where no accumulator is live)
+                if (!split && EPIX != FX_EPI_INFER_FACTOR) {        // (there: factor and bias in the staged store below, where no accumulator is live)
                     if (p.bias) { const float bb = p.bias[m]; v[0] += bb; v[1] += bb; v[2] += bb; v[3] += bb; }
                 }
                 if (dense) {
@@ -516,13 +510,13 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                         for (int e = 0; e < 4; ++e) dst[e * p.oxs] = p.accumulate ? dst[e * p.oxs] + v[e] : v[e];
                     }
                 }
-                if constexpr (EPI == 1) {
+                if constexpr (SUMS == 1) {
                     if (!split) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { ssum[b] += v[e]; ssq[b] = fmaf(v[e], v[e], ssq[b]); }
                     }
                 }
-                if constexpr (EPI == 2) {
+                if constexpr (SUMS == 2) {
                     if (!split) {
                         const f32x4 c2 = *reinterpret_cast<const f32x4*>(p.ep_c + ((size_t)n * p.M + m) * OHW + rem);
 #pragma unroll
@@ -537,7 +531,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     if (dense) {
         // (every wave left the K loop through its last barrier: the operand buffers are free)
         constexpr int EROW = 512 + 16;               // bytes per staged channel row: 128 pixels + one 16-B pad (staging stores of 8 consecutive rows hit 32 different banks)
-        const bool accum = EPI != 3 && !split && p.accumulate;      // (EPI 3 has added its summand in the register view above: its sums need the final value)
+        const bool accum = SUMS != 3 && !split && p.accumulate;      // (SUMS 3 has added its summand in the register view above: its sums need the final value)
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             if (b == 1) __syncthreads();             // round 0's rows have been read
@@ -569,7 +563,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                             const size_t ae = ((size_t)ne * p.M + m) * OHW + re;
                             float ve = v[e];
                             if (accum) ve += yout[ae];
-                            if constexpr (EPIX == 8) {
+                            if constexpr (fx_epi_infer(EPIX)) {
                                 if (p.ep_res) ve += p.ep_res[ae];
                                 if (p.ep_relu) ve = fmaxf(ve, 0.f);
                             }
@@ -590,12 +584,12 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                     } else o4 = *dst;
                     v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3];
                 }
-                if constexpr (EPIX == 9) {        // (fx_conv_fwd launches it dense, unsplit and without accumulate: one factor per pixel, the plane of image n)
+                if constexpr (EPIX == FX_EPI_INFER_FACTOR) {        // (fx_conv_fwd launches it dense, unsplit and without accumulate: one factor per pixel, the plane of image n)
                     const f32x4 em = *reinterpret_cast<const f32x4*>(p.emask + (size_t)n * OHW + rem);
                     const float bb = p.bias ? p.bias[m] : 0.f;
                     v[0] = v[0] * em[0] + bb; v[1] = v[1] * em[1] + bb; v[2] = v[2] * em[2] + bb; v[3] = v[3] * em[3] + bb;
                 }
-                if constexpr (EPIX == 8 || EPIX == 9) {
+                if constexpr (fx_epi_infer(EPIX)) {
                     if (p.ep_res) { const f32x4 r4 = *reinterpret_cast<const f32x4*>(p.ep_res + at); v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3]; }
                     if (p.ep_relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
                 }
@@ -603,7 +597,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
             }
         }
     }
-    if constexpr (EPI == 1 || EPI == 2) {
+    if constexpr (SUMS == 1 || SUMS == 2) {
         if (!split) {
             // the two half-waves hold different pixels of the same channels; then the two waves along the pixel axis
 #pragma unroll
@@ -620,7 +614,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
             }
         }
     }
-    if constexpr (EPI == 3) {
+    if constexpr (SUMS == 3) {
         // three sums per channel: [wave along pixels][kind][channel] behind the staged tile (3 KB at byte 40960 of the 48 KB array)
         float (*const red3)[3][128] = reinterpret_cast<float (*)[3][128]>(lds + 40960);
 #pragma unroll
@@ -654,6 +648,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
 template <int BM, int EPI, bool TAPI = false>
 __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_in) {
     const FxConvParams p = fx_class_params(p_in);
+    constexpr int SUMS = fx_epi_sums(EPI);
     static_assert(BM == 96 || BM == 64, "channel tile");
     constexpr int GA = 4, GB = BM / 32;                 // 16-pixel / 16-channel groups of a wave (2 x 2 waves; a wave: 64 pixels x BM / 2 channels)
     constexpr int WCH = BM / 2;
@@ -830,7 +825,7 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
 #pragma unroll
     for (int b = 0; b < GB; ++b) {
         ssum[b] = ssq[b] = esc[b] = esh[b] = emean[b] = 0.f;
-        if constexpr (EPI == 2) {
+        if constexpr (SUMS == 2) {
             const int m = m0 + wm * WCH + b * 16 + lc;
             if (m < p.M) { esc[b] = p.ep_tab[8 * m]; esh[b] = p.ep_tab[8 * m + 1]; emean[b] = p.ep_tab[8 * m + 2]; }
         }
@@ -870,13 +865,13 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
                     for (int e = 0; e < 4; ++e) dst[e * p.oxs] = p.accumulate ? dst[e * p.oxs] + v[e] : v[e];
                 }
             }
-            if constexpr (EPI == 1) {
+            if constexpr (SUMS == 1) {
                 if (!split) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { ssum[b] += v[e]; ssq[b] = fmaf(v[e], v[e], ssq[b]); }
                 }
             }
-            if constexpr (EPI == 2) {
+            if constexpr (SUMS == 2) {
                 if (!split) {
                     const f32x4 c2 = *reinterpret_cast<const f32x4*>(p.ep_c + ((size_t)n * p.M + m) * OHW + rem);
 #pragma unroll
@@ -929,7 +924,7 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
                     } else o4 = *dst;
                     v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3];
                 }
-                if constexpr (EPI == 8) {      // inference (fx_conv_kernel's EPIX 8)
+                if constexpr (fx_epi_infer(EPI)) {
                     if (p.ep_res) { const f32x4 r4 = *reinterpret_cast<const f32x4*>(p.ep_res + at); v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3]; }
                     if (p.ep_relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
                 }
@@ -937,7 +932,7 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
             }
         }
     }
-    if constexpr (EPI == 1 || EPI == 2) {
+    if constexpr (SUMS == 1 || SUMS == 2) {
         if (!split) {
             // the four 16-lane groups hold different pixels of the same channels; then the two waves along the pixel axis
 #pragma unroll
@@ -956,9 +951,9 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
     }
 }
 
-// y (=|+=) sum over the split-K slabs (+ bias); EPI as in fx_conv_kernel: per-(chunk, channel) partial sums.  One block per (channel m, image group):
+// y (=|+=) sum over the split-K slabs (+ bias); SUMS as in fx_conv_kernel (0 / 1 / 2): per-(chunk, channel) partial sums.  One block per (channel m, image group):
 // grid (M, ngroups), block z handles images n = z, z + ngroups, ...; the partial index is the group.
-template <int EPI>
+template <int SUMS>
 __global__ __launch_bounds__(256) void fx_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ y, const float* __restrict__ bias, int nsplit,
                                                         size_t slab_stride, int N, int M, int OHW, int accumulate, const float* __restrict__ ep_c,
                                                         const float* __restrict__ ep_tab, float* __restrict__ partial, const float* __restrict__ emask,
@@ -966,7 +961,7 @@ __global__ __launch_bounds__(256) void fx_reduce_kernel(const float* __restrict_
     const int m = blockIdx.x, grp = blockIdx.y, ngrp = gridDim.y;
     const float bb = bias ? bias[m] : 0.f;
     float esc = 0.f, esh = 0.f, emean = 0.f;
-    if constexpr (EPI == 2) { esc = ep_tab[8 * m]; esh = ep_tab[8 * m + 1]; emean = ep_tab[8 * m + 2]; }
+    if constexpr (SUMS == 2) { esc = ep_tab[8 * m]; esh = ep_tab[8 * m + 1]; emean = ep_tab[8 * m + 2]; }
     float s1 = 0.f, s2 = 0.f;
     const int q4 = OHW >> 2;
     for (int n = grp; n < N; n += ngrp) {
@@ -978,7 +973,7 @@ __global__ __launch_bounds__(256) void fx_reduce_kernel(const float* __restrict_
                 v[0] += u[0]; v[1] += u[1]; v[2] += u[2]; v[3] += u[3];
             }
             if (emask && bias) {
-                // folded partial convolution at inference (EPIX 9): the factor first, then b', so that an empty window (factor 0) gives b'.  Only this pairing takes
+                // folded partial convolution at inference (FX_EPI_INFER_FACTOR): the factor first, then b', so that an empty window (factor 0) gives b'.  Only this pairing takes
                 // the order: the training instances pass no bias with a factor, and their (v + 0) * em keeps the sign of a zero that v * em + 0 would not.
                 const f32x4 em = *reinterpret_cast<const f32x4*>(emask + (size_t)n * OHW + 4 * i);
                 v[0] = v[0] * em[0] + bb; v[1] = v[1] * em[1] + bb; v[2] = v[2] * em[2] + bb; v[3] = v[3] * em[3] + bb;
@@ -994,18 +989,18 @@ __global__ __launch_bounds__(256) void fx_reduce_kernel(const float* __restrict_
             if (res) { const f32x4 r4 = *reinterpret_cast<const f32x4*>(res + base + 4 * i); v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3]; }      // inference
             if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
             *dst = v;
-            if constexpr (EPI == 1) {
+            if constexpr (SUMS == 1) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { s1 += v[e]; s2 = fmaf(v[e], v[e], s2); }
             }
-            if constexpr (EPI == 2) {
+            if constexpr (SUMS == 2) {
                 const f32x4 c2 = *reinterpret_cast<const f32x4*>(ep_c + base + 4 * i);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { const float gg = fmaf(c2[e], esc, esh) > 0.f ? v[e] : 0.f; s1 += gg; s2 = fmaf(gg, c2[e] - emean, s2); }
             }
         }
     }
-    if constexpr (EPI != 0) {
+    if constexpr (SUMS != 0) {
         __shared__ float r1[4], r2[4];
         s1 = wave_sum(s1); s2 = wave_sum(s2);
         if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = s1; r2[threadIdx.x >> 6] = s2; }
@@ -1693,13 +1688,66 @@ static int g_class_launches = 0;      // 1: one launch per parity class of a str
 // 128 rows would be mostly padding (the 272-channel regressor: 3 x 96 = 288 rows instead of 384; 64-channel layers: all four waves live).  At 128 rows the 16x16x32
 // form is 1-3 % SLOWER on the large layers (20 fragment reads per step against 12, and the chip holds no higher clock on it in these kernels: profiles/r04_summary.md
 // section 1), so those stay on the 32x32x16 kernel.
+// The instance a code runs on there: the kernel applies p.emask at run time, so a factor code is the instance without the factor, with the pointer set; -1: none (the
+// tail sums and the two fp32-fed partial-convolution codes).  Image-fed launches only.
+constexpr int fx16_epi(int epi) {
+    if (fx_epi_sums(epi) == 3 || epi == FX_EPI_FACTOR || epi == FX_EPI_INFER_FACTOR) return -1;
+    return fx_epi_infer(epi) ? FX_EPI_INFER : fx_epi_sums(epi) == 1 ? FX_EPI_STATS : fx_epi_sums(epi) == 2 ? FX_EPI_BWD_SUMS : FX_EPI_STORE;
+}
 static int fx16_bm(int M, bool img, int pro, int epi) {
-    if (epi == 5 || epi == 6 || epi == 7) epi = epi == 7 ? 0 : epi - 4;      // the masked epilogues run on the base instance with the factor pointer set
-    if (epi == 8) epi = 0;                                                     // (inference: EPI 0's tiles)
-    if (!img || pro != 0 || (epi != 0 && epi != 1 && epi != 2)) return 0;
+    if (!img || pro != 0 || fx16_epi(epi) < 0) return 0;
     if (M <= 64) return 64;
     return ceil_div(M, 96) * 96 < ceil_div(M, 128) * 128 ? 96 : 0;
 }
+
+// What a call asks for -> the prologue and epilogue of its (unsplit) launch.  PRO 4: an fp32 operand of a partial convolution is multiplied by pmask in the kernel; an
+// image carries its factor already.
+struct FxSelect { int pro, epi; };
+constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool infer, bool tail) {
+    const int pro = masked && !img ? 4 : 0;
+    if (tail) return {pro, FX_EPI_TAIL_SUMS};
+    if (infer) return {pro, masked ? FX_EPI_INFER_FACTOR : FX_EPI_INFER};
+    if (masked) return {pro, sums ? (dgrad ? FX_EPI_FACTOR_BWD_SUMS : FX_EPI_FACTOR_STATS) : (img ? FX_EPI_FACTOR_IMG : FX_EPI_FACTOR)};
+    return {pro, sums ? (dgrad ? FX_EPI_BWD_SUMS : FX_EPI_STATS) : FX_EPI_STORE};
+}
+
+// Every compiled instance of the two convolution kernels, once: X(AMODE, PRO, EPIX, TAPI, RAG) of fx_conv_kernel, X(BM, EPI, TAPI) of fx16_conv_kernel.  The tap-inner
+// twins exist where the layers that want them land: 128-row tiles with the plain / BatchNorm epilogues, and the 96-row fx16 tile (the regressor).
+#define P3D_FX_CONV_INSTANCES(X)                                                                                                                              \
+    X(0, 0, FX_EPI_STORE, false, false) X(0, 0, FX_EPI_STATS, false, false) X(0, 0, FX_EPI_BWD_SUMS, false, false) X(0, 0, FX_EPI_INFER, false, false)        \
+    X(0, 4, FX_EPI_STORE, false, false) X(0, 4, FX_EPI_FACTOR, false, false) X(0, 4, FX_EPI_FACTOR_STATS, false, false) X(0, 4, FX_EPI_INFER_FACTOR, false, false) \
+    X(1, 0, FX_EPI_STORE, false, false) X(1, 0, FX_EPI_STATS, false, false) X(1, 0, FX_EPI_BWD_SUMS, false, false) X(1, 0, FX_EPI_TAIL_SUMS, false, false)    \
+    X(1, 0, FX_EPI_FACTOR_STATS, false, false) X(1, 0, FX_EPI_FACTOR_BWD_SUMS, false, false) X(1, 0, FX_EPI_FACTOR_IMG, false, false) X(1, 0, FX_EPI_INFER, false, false) \
+    X(1, 0, FX_EPI_STORE, true, false) X(1, 0, FX_EPI_STATS, true, false) X(1, 0, FX_EPI_BWD_SUMS, true, false) X(0, 0, FX_EPI_STORE, false, true) X(0, 0, FX_EPI_INFER, false, true)
+#define P3D_FX16_CONV_INSTANCES(X)                                                                                             \
+    X(96, FX_EPI_STORE, false) X(96, FX_EPI_STATS, false) X(96, FX_EPI_BWD_SUMS, false) X(96, FX_EPI_INFER, false)             \
+    X(64, FX_EPI_STORE, false) X(64, FX_EPI_STATS, false) X(64, FX_EPI_BWD_SUMS, false) X(64, FX_EPI_INFER, false)             \
+    X(96, FX_EPI_STORE, true) X(96, FX_EPI_STATS, true) X(96, FX_EPI_BWD_SUMS, true)
+// The instance of a launch (bm 0: fx_conv_kernel; 96 / 64: fx16_conv_kernel), or null.  A tap-inner twin is looked up by the code itself: a launch with the per-pixel
+// factor keeps the tap-outer order on either kernel.
+using FxKernel = void (*)(const FxConvParams);
+constexpr FxKernel fx_instance(int bm, bool img, int pro, int epi, bool tapi, bool rag) {
+    const int am = img ? 1 : 0, e = bm && !tapi ? fx16_epi(epi) : epi;
+#define P3D_X(AM, PRO, EPI, TAPI, RAG) if (bm == 0 && am == AM && pro == PRO && e == EPI && tapi == TAPI && rag == RAG) return fx_conv_kernel<AM, PRO, EPI, TAPI, RAG>;
+    P3D_FX_CONV_INSTANCES(P3D_X)
+#undef P3D_X
+#define P3D_X(BM, EPI, TAPI) if (bm == BM && am == 1 && pro == 0 && e == EPI && tapi == TAPI && !rag) return fx16_conv_kernel<BM, EPI, TAPI>;
+    P3D_FX16_CONV_INSTANCES(P3D_X)
+#undef P3D_X
+    return nullptr;
+}
+// everything fx_select can return for arguments that fx_conv_fwd / fx_conv_dgrad admit has its instances: on each tile the code can get, and for its split-K slabs
+constexpr bool fx_select_covered() {
+    for (int c = 0; c < 64; ++c) {
+        const bool dgrad = c & 1, img = c & 2, masked = c & 4, sums = c & 8, infer = c & 16, tail = c & 32;
+        if (dgrad ? (infer || (masked && !img && sums) || (tail && (!img || masked || sums))) : (tail || (infer && (sums || (masked && img))))) continue;
+        const FxSelect s = fx_select(dgrad, img, masked, sums, infer, tail);
+        if (!fx_instance(0, img, s.pro, s.epi, false, false) || !fx_instance(0, img, s.pro, FX_EPI_STORE, false, false)) return false;
+        if (img && s.pro == 0 && fx16_epi(s.epi) >= 0 && !(fx_instance(96, img, 0, s.epi, false, false) && fx_instance(64, img, 0, s.epi, false, false))) return false;
+    }
+    return fx_instance(0, false, 0, FX_EPI_INFER, false, true) && fx_instance(0, false, 0, FX_EPI_STORE, false, true);      // (the ragged forward: fp32-fed inference)
+}
+static_assert(fx_select_covered(), "fx_select returns a code without a compiled instance");
 void fx_tune(int what, int value) {
     switch (what) {
         case 0: g_force_wgrad_splits = value; break;
@@ -1711,66 +1759,55 @@ void fx_tune(int what, int value) {
     }
 }
 
-struct FxSplit { int splits, kchunk; };
-static FxSplit fx_plan_split(int64_t tiles, int nk) {
-    FxSplit s{1, 0};
-    int64_t want;
-    if (g_force_conv_splits > 0) want = g_force_conv_splits < nk ? g_force_conv_splits : nk;
-    else {
-        constexpr int target = 768;      // blocks aimed at; 0 - 1024 swept in the step without a gain (profiles/r04_summary.md section 8b)
-        if (tiles > 400 || nk < 64) return s;
-        want = ceil_div(target, tiles);
-        if (want > nk / 32) want = nk / 32;
-        if (want > 8) want = 8;
-    }
-    if (want < 2) return s;
-    s.kchunk = (int)ceil_div(nk, want);
-    s.splits = (int)ceil_div(nk, s.kchunk);
-    if (s.splits < 2) { s.splits = 1; s.kchunk = 0; }
-    return s;
-}
-
+// How one forward / data-gradient call is launched: what the workspace and partial-row queries report and what the launchers use
+struct FxPlan {
+    int splits, kchunk;         // split-K: slabs, and K steps per slab (1, 0: one launch writes the result)
+    int tiles_n;                // 128-pixel tiles of the GEMM's pixel grid (a strided data gradient: of one parity class)
+    size_t slab_stride;         // elements between two slabs
+    size_t slab_offset;         // bytes: the slabs lie behind the room for the weight image (built by the call unless the caller hands one in)
+    size_t workspace;           // bytes in all
+    int partial_rows;           // rows of the per-channel partial sums [rows][M][2]: pixel tiles, or under split-K the image groups of fx_reduce_kernel
+};
 size_t fx_weight_image_bytes(int K, int C, int RS, bool bwd) {
     const int rows = bwd ? C : K, red = bwd ? K : C;
     return (size_t)RS * ((rows + 127) / 128) * (red / FX_BK) * (3 * FX_PIECE);
 }
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-static FxSplit fx_fwd_split(const p3d_conv_desc* d) {
-    return fx_plan_split(ceil_div(d->K, FX_BM) * ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BN), d->R * d->S * (d->C / FX_BK));
-}
-static FxSplit fx_dgrad_split(const p3d_conv_desc* d) {
-    if (d->stride != 1) return FxSplit{1, 0};
-    return fx_plan_split(ceil_div(d->C, FX_BM) * ceil_div((int64_t)d->N * d->H * d->W, FX_BN), d->R * d->S * (d->K / FX_BK));
+// dgrad: rows = input channels, reduction = output channels, pixels = the input map; only stride 1 splits (a strided one writes its parity classes in place).
+// ragged (the forward at any map width): each slab starts on a 16-B line.
+static FxPlan fx_plan(const p3d_conv_desc* d, bool dgrad, bool ragged = false) {
+    const int rows = dgrad ? d->C : d->K, red = dgrad ? d->K : d->C, RS = d->R * d->S, nk = RS * (red / FX_BK);
+    const int64_t pixels = dgrad ? (int64_t)d->N * d->H * d->W : (int64_t)d->N * d->Ho * d->Wo;
+    FxPlan s{1};
+    s.tiles_n = (int)ceil_div(dgrad && d->stride > 1 ? (int64_t)d->N * (d->H / d->stride) * (d->W / d->stride) : pixels, FX_BN);
+    const int64_t tiles = ceil_div(rows, FX_BM) * s.tiles_n;
+    const bool may_split = !dgrad || d->stride == 1;
+    int64_t want = 1;
+    if (may_split && g_force_conv_splits > 0) want = g_force_conv_splits < nk ? g_force_conv_splits : nk;
+    else if (may_split && tiles <= 400 && nk >= 64) {
+        want = ceil_div(768, tiles);      // 768 blocks aimed at; 0 - 1024 swept in the step without a gain (profiles/r04_summary.md section 8b)
+        if (want > nk / 32) want = nk / 32;
+        if (want > 8) want = 8;
+    }
+    if (want >= 2) { s.kchunk = (int)ceil_div(nk, want); s.splits = (int)ceil_div(nk, s.kchunk); }
+    if (s.splits < 2) { s.splits = 1; s.kchunk = 0; }
+    s.slab_stride = ragged ? ((size_t)rows * pixels + 3) & ~(size_t)3 : (size_t)rows * pixels;
+    s.slab_offset = align256(fx_weight_image_bytes(d->K, d->C, RS, dgrad));
+    s.workspace = s.slab_offset + (s.splits > 1 ? (size_t)s.splits * s.slab_stride * sizeof(float) : 0);
+    s.partial_rows = s.splits > 1 ? (d->N < 16 ? d->N : 16) : (int)ceil_div(pixels, FX_BN);
+    return s;
 }
 // partial convolutions (PRO 4 / EPI 4 instances): 64-channel layers included (half-dead tiles), unsplit launches only
 static bool fx_masked_on() { static const bool on = [] { const char* e = getenv("P3D_FX_MASKED"); return !(e && atoi(e) == 0); }(); return on; }      // A/B switch
 bool fx_fwd_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_fwd_applies(d, 64); }
 bool fx_dgrad_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_dgrad_applies(d, 64); }
 bool fx_wgrad_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_wgrad_applies(d, 96); }
-// workspace of a call: room for the weight image (built by the call unless the caller hands one in) + the split-K slabs
-size_t fx_fwd_workspace(const p3d_conv_desc* d) {
-    const FxSplit s = fx_fwd_split(d);
-    return align256(fx_weight_image_bytes(d->K, d->C, d->R * d->S, false)) + (s.splits > 1 ? (size_t)s.splits * d->N * d->K * d->Ho * d->Wo * sizeof(float) : 0);
-}
-// (ragged: each slab starts on a 16-B line)
-static size_t fx_any_slab_stride(const p3d_conv_desc* d) { return ((size_t)d->N * d->K * d->Ho * d->Wo + 3) & ~(size_t)3; }
-size_t fx_fwd_any_workspace(const p3d_conv_desc* d) {
-    const FxSplit s = fx_fwd_split(d);
-    return align256(fx_weight_image_bytes(d->K, d->C, d->R * d->S, false)) + (s.splits > 1 ? (size_t)s.splits * fx_any_slab_stride(d) * sizeof(float) : 0);
-}
-size_t fx_dgrad_workspace(const p3d_conv_desc* d) {
-    const FxSplit s = fx_dgrad_split(d);
-    return align256(fx_weight_image_bytes(d->K, d->C, d->R * d->S, true)) + (s.splits > 1 ? (size_t)s.splits * d->N * d->C * d->H * d->W * sizeof(float) : 0);
-}
-int fx_partial_rows_fwd(const p3d_conv_desc* d) {
-    const FxSplit s = fx_fwd_split(d);
-    return s.splits > 1 ? (d->N < 16 ? d->N : 16) : (int)ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BN);
-}
-int fx_partial_rows_dgrad(const p3d_conv_desc* d) {
-    const FxSplit s = fx_dgrad_split(d);
-    return s.splits > 1 ? (d->N < 16 ? d->N : 16) : (int)ceil_div((int64_t)d->N * d->H * d->W, FX_BN);
-}
+size_t fx_fwd_workspace(const p3d_conv_desc* d) { return fx_plan(d, false).workspace; }
+size_t fx_fwd_any_workspace(const p3d_conv_desc* d) { return fx_plan(d, false, true).workspace; }
+size_t fx_dgrad_workspace(const p3d_conv_desc* d) { return fx_plan(d, true).workspace; }
+int fx_partial_rows_fwd(const p3d_conv_desc* d) { return fx_plan(d, false).partial_rows; }
+int fx_partial_rows_dgrad(const p3d_conv_desc* d) { return fx_plan(d, true).partial_rows; }
 
 // Pre-split weight images of one conv weight w [K][C][R*S] (fp32): blockIdx.y = 0 the forward image (rows = output channels, reduction = input channels),
 // 1 the data-gradient image (rows = input channels, reduction = output channels); a null image pointer skips that direction.  One thread per 16-B chunk
@@ -1936,39 +1973,36 @@ int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_f
     return check_launch("fx_build_weight_images");
 }
 
-static void fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi, int bm, dim3 grid, hipStream_t st) {
-    const int am = img ? 1 : 0;
+// the one place that launches a convolution kernel: the instance of (tile, operand, prologue, epilogue, K order, ragged), P3D_EINVAL if none was compiled
+static int32_t fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi, int bm, dim3 grid, hipStream_t st, bool rag = false) {
     FxConvParams p = p_in;
-    // the tap-inner instances exist where the layers that want them land: 128-row tiles with the plain / BatchNorm epilogues, and the 96-row fx16 tile (the regressor)
-    if (p.tap_inner && !((bm == 0 && am == 1 && pro == 0 && epi >= 0 && epi <= 2) || (bm == 96 && epi >= 0 && epi <= 2))) p.tap_inner = 0;
-    if (p.tap_inner) {
-#define P3D_FX_TAPI(EPI) if (bm == 0 && epi == EPI) { hipLaunchKernelGGL((fx_conv_kernel<1, 0, EPI, true>), grid, dim3(256), 0, st, p); return; } \
-                         if (bm == 96 && epi == EPI) { hipLaunchKernelGGL((fx16_conv_kernel<96, EPI, true>), grid, dim3(256), 0, st, p); return; }
-        P3D_FX_TAPI(0) P3D_FX_TAPI(1) P3D_FX_TAPI(2)
-#undef P3D_FX_TAPI
-    }
-    // (the fx16 kernel applies p.emask at run time: the masked epilogues 5 / 6 / 7 are its 1 / 2 / 0 with the factor pointer set)
-#define P3D_FX16_CASE(BM, EPI) if (bm == BM && (epi == EPI || epi == (EPI == 0 ? 7 : EPI + 4))) { hipLaunchKernelGGL((fx16_conv_kernel<BM, EPI>), grid, dim3(256), 0, st, p); return; }
-    P3D_FX16_CASE(96, 0) P3D_FX16_CASE(96, 1) P3D_FX16_CASE(96, 2)
-    P3D_FX16_CASE(64, 0) P3D_FX16_CASE(64, 1) P3D_FX16_CASE(64, 2)
-    P3D_FX16_CASE(96, 8) P3D_FX16_CASE(64, 8)
-#undef P3D_FX16_CASE
-#define P3D_FX_CASE(AM, PRO, EPI) if (am == AM && pro == PRO && epi == EPI) { hipLaunchKernelGGL((fx_conv_kernel<AM, PRO, EPI>), grid, dim3(256), 0, st, p); return; }
-    P3D_FX_CASE(0, 0, 0) P3D_FX_CASE(0, 0, 1) P3D_FX_CASE(0, 0, 2) P3D_FX_CASE(0, 4, 0) P3D_FX_CASE(0, 4, 4) P3D_FX_CASE(0, 4, 5)
-    P3D_FX_CASE(1, 0, 0) P3D_FX_CASE(1, 0, 1) P3D_FX_CASE(1, 0, 2) P3D_FX_CASE(1, 0, 3) P3D_FX_CASE(1, 0, 5) P3D_FX_CASE(1, 0, 6) P3D_FX_CASE(1, 0, 7)
-    P3D_FX_CASE(0, 0, 8) P3D_FX_CASE(1, 0, 8) P3D_FX_CASE(0, 4, 9)
-#undef P3D_FX_CASE
-    set_error("fx_launch_conv: no kernel instance for img=%d pro=%d epi=%d bm=%d", am, pro, epi, bm);
+    if (p.tap_inner && !fx_instance(bm, img, pro, epi, true, rag)) p.tap_inner = 0;
+    const FxKernel kernel = fx_instance(bm, img, pro, epi, p.tap_inner != 0, rag);
+    if (!kernel) { set_error("fx_launch_conv: no kernel instance for img=%d pro=%d epi=%d bm=%d", img ? 1 : 0, pro, epi, bm); return P3D_EINVAL; }
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, p);
+    return P3D_OK;
 }
 
-static void fx_launch_reduce(int epi, dim3 grid, hipStream_t st, const float* slabs, float* y, const float* bias, int nsplit, size_t slab_stride, int N, int M,
-                             int OHW, int accumulate, const float* ep_c, const float* ep_tab, float* partial, const float* emask, const float* res = nullptr,
-                             int relu = 0) {
-    if (epi == 5 || epi == 6 || epi == 7 || epi == 4 || epi == 8 || epi == 9) epi = epi == 5 ? 1 : epi == 6 ? 2 : 0;      // the masked epilogues: the base sums over the result times emask
+// A split-K call: the slabs (raw partial products, from the FX_EPI_STORE instance: bias, factor, sums and the inference tail belong to the pass that sums them), then
+// that pass, which writes p.Y.  p: the parameters of the unsplit launch.
+static int32_t fx_launch_split(FxConvParams p, const FxPlan& pl, bool img, int pro, int epi, int bm, float* slabs, hipStream_t st, bool rag = false) {
+    float* const y = p.Y;
+    const float* const bias = p.bias, * const em = p.emask;
+    const int OHW = p.OH * p.OW;
+    p.kchunk = pl.kchunk; p.slab_stride = pl.slab_stride; p.Y = slabs; p.bias = nullptr; p.emask = nullptr;
+    if (int32_t e = fx_launch_conv(p, img, pro == 4 ? 4 : 0, FX_EPI_STORE, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), (unsigned)pl.splits), st, rag)) return e;
     prof_kernel_done(st);
-    if (epi == 1) hipLaunchKernelGGL(fx_reduce_kernel<1>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask, res, relu);
-    else if (epi == 2) hipLaunchKernelGGL(fx_reduce_kernel<2>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask, res, relu);
-    else hipLaunchKernelGGL(fx_reduce_kernel<0>, grid, dim3(256), 0, st, slabs, y, bias, nsplit, slab_stride, N, M, OHW, accumulate, ep_c, ep_tab, partial, emask, res, relu);
+    if (rag) {
+        const unsigned total = (unsigned)((size_t)p.N * p.M * OHW);          // (fx_common: below 2^31)
+        hipLaunchKernelGGL(fx_reduce_any_kernel, dim3((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096), dim3(256), 0, st, (const float*)slabs, y, bias, pl.splits,
+                           pl.slab_stride, total, p.M, OHW, p.accumulate, p.ep_res, p.ep_relu);
+    } else {
+        const int sums = fx_epi_sums(epi);       // (of the result times the factor, where there is one)
+        auto* reduce = sums == 1 ? fx_reduce_kernel<1> : sums == 2 ? fx_reduce_kernel<2> : fx_reduce_kernel<0>;
+        hipLaunchKernelGGL(reduce, dim3((unsigned)p.M, (unsigned)pl.partial_rows), dim3(256), 0, st, (const float*)slabs, y, bias, pl.splits, pl.slab_stride, p.N, p.M, OHW,
+                           p.accumulate, p.ep_c, p.ep_tab, p.partial, em, p.ep_res, p.ep_relu);
+    }
+    return P3D_OK;
 }
 
 // y = conv(x, w) (+ bias); fuse may be null (plain convolution from fp32 x, the weight image built here)
@@ -1976,7 +2010,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
                     const FxFuse* fuse, hipStream_t st) {
     // partial convolution (partial_conv.py:45-53): y = conv(x * pmask) * emask.  An fp32 operand is multiplied by pmask before the in-kernel split (PRO 4); an image
     // operand carries its factor already (the pass that wrote it multiplied it in), so only emask is given.  With `partial` the BatchNorm statistics are taken of
-    // the renormalised result (the residual-block executor: epilogue 5).
+    // the renormalised result (the residual-block executor: FX_EPI_FACTOR_STATS).
     const bool img = fuse && fuse->act_img;
     const bool masked = fuse && (fuse->pmask || fuse->emask);
     const bool infer = fuse && fuse->infer;
@@ -1992,8 +2026,8 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
                 "fx_conv_fwd: the inference epilogue takes a cached folded weight image, no other fusion, and a partial convolution only from an fp32 operand");
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
     P3D_REQUIRE(!rag || (!img && !masked), "fx_conv_fwd: the ragged forward takes an fp32 operand and no partial convolution");
-    const size_t need = rag ? fx_fwd_any_workspace(d) : fx_fwd_workspace(d);
-    if (need && (!workspace || workspace_bytes < need)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
+    const FxPlan pl = fx_plan(d, false, rag);
+    if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     FxConvParams p{};
     p.X = x; p.Y = y; p.bias = bias;
     if (img) { p.Ximg = (const unsigned char*)fuse->act_img; p.plane_bytes = (size_t)d->N * d->C * d->H * d->W * 2; }
@@ -2008,41 +2042,15 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
         if (int32_t e = fx_build_weight_images(w, d->K, d->C, RS, ws, nullptr, st, d->c_total, d->c_offset)) return e;
         wimg = ws;
     }
-    ws += align256(fx_weight_image_bytes(d->K, d->C, RS, false));
     p.Wimg = (const unsigned char*)wimg;
-    int pro = 0, epi = 0;
-    if (fuse) {
-        if (fuse->partial) { epi = 1; p.partial = fuse->partial; }
-        if (masked) { pro = img ? 0 : 4; epi = fuse->partial ? 5 : (img ? 7 : 4); p.pmask = fuse->pmask; p.emask = fuse->emask; }
-        if (infer) { epi = masked ? 9 : 8; p.ep_res = fuse->res; p.ep_relu = fuse->relu; }      // (9: PRO 4 + the factor before b', fx_conv_kernel)
-    }
-    const int tiles_n = (int)ceil_div(p.NP, FX_BN);
-    const FxSplit sp = fx_fwd_split(d);
-    const int bm = rag ? 0 : fx16_bm(d->K, img, sp.splits > 1 ? 0 : pro, sp.splits > 1 ? 0 : epi);
+    const FxSelect sel = fx_select(false, img, masked, fuse && fuse->partial, infer, false);
+    if (fuse) { p.partial = fuse->partial; p.pmask = fuse->pmask; p.emask = fuse->emask; p.ep_res = fuse->res; p.ep_relu = fuse->relu; }      // (res / relu: inference only, above)
+    const bool split = pl.splits > 1;
+    const int bm = rag ? 0 : fx16_bm(d->K, img, split ? 0 : sel.pro, split ? FX_EPI_STORE : sel.epi);
     p.tiles_m = (int)ceil_div(d->K, bm ? bm : FX_BM);
     p.tap_inner = img && RS > 1 && d->C >= FX_TAP_INNER_MIN;
-    if (rag) {
-        const dim3 grid((unsigned)(p.tiles_m * tiles_n), (unsigned)sp.splits);
-        if (sp.splits > 1) {
-            p.kchunk = sp.kchunk; p.slab_stride = fx_any_slab_stride(d); p.Y = (float*)ws; p.bias = nullptr;
-            hipLaunchKernelGGL((fx_conv_kernel<0, 0, 0, false, true>), grid, dim3(256), 0, st, p);
-            prof_kernel_done(st);
-            const unsigned total = (unsigned)((size_t)d->N * d->K * d->Ho * d->Wo);          // (fx_common: below 2^31)
-            hipLaunchKernelGGL(fx_reduce_any_kernel, dim3((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096), dim3(256), 0, st, (const float*)ws, y, bias,
-                               sp.splits, p.slab_stride, total, d->K, d->Ho * d->Wo, d->accumulate, p.ep_res, p.ep_relu);
-        } else {
-            hipLaunchKernelGGL((fx_conv_kernel<0, 0, 8, false, true>), grid, dim3(256), 0, st, p);
-        }
-    } else if (sp.splits > 1) {
-        p.kchunk = sp.kchunk; p.slab_stride = (size_t)d->N * d->K * d->Ho * d->Wo; p.Y = (float*)ws; p.bias = nullptr;
-        const float* em = p.emask;
-        p.emask = nullptr;             // (the slabs are raw partial products: the factor, like the sums, belongs to the reduce pass)
-        fx_launch_conv(p, img, pro == 4 ? 4 : 0, 0, bm, dim3((unsigned)(p.tiles_m * tiles_n), (unsigned)sp.splits), st);
-        fx_launch_reduce(epi, dim3((unsigned)d->K, (unsigned)(d->N < 16 ? d->N : 16)), st, (const float*)ws, y, bias, sp.splits, p.slab_stride, d->N, d->K,
-                         d->Ho * d->Wo, d->accumulate, nullptr, nullptr, p.partial, em, p.ep_res, p.ep_relu);
-    } else {
-        fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1), st);
-    }
+    if (int32_t e = split ? fx_launch_split(p, pl, img, sel.pro, sel.epi, bm, (float*)(ws + pl.slab_offset), st, rag)
+                          : fx_launch_conv(p, img, sel.pro, sel.epi, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), 1), st, rag)) return e;
     return check_launch("fx_conv_fwd");
 }
 
@@ -2050,7 +2058,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
 int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, float* dx, void* workspace, size_t workspace_bytes, const FxFuse* fuse,
                       hipStream_t st) {
     // partial convolution: dx = dgrad(dy * pmask) * emask (pmask = mult of the output pixel, emask = mask_in of the input pixel).  As in fx_conv_fwd an image operand
-    // carries its factor; with `partial` the BatchNorm-backward sums are taken of the masked result (epilogue 6).
+    // carries its factor; with `partial` the BatchNorm-backward sums are taken of the masked result (FX_EPI_FACTOR_BWD_SUMS).
     const bool img = fuse && fuse->act_img;
     const bool masked = fuse && (fuse->pmask || fuse->emask);
     const void* wimg = fuse ? fuse->wimg : nullptr;
@@ -2059,8 +2067,8 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
     if (masked && (!fuse->emask || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr) || (!img && fuse->partial))) {
         set_error("fx_conv_dgrad: the partial-convolution instances take the result factor and the operand factor exactly for an fp32 operand"); return P3D_EINVAL;
     }
-    const size_t need = fx_dgrad_workspace(d);
-    if (need && (!workspace || workspace_bytes < need)) { set_error("fx_conv_dgrad: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
+    const FxPlan pl = fx_plan(d, true);
+    if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_dgrad: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     if (fuse && fuse->acc_src && !(d->accumulate && fx_dgrad_accumulates_from_source(d))) {
         set_error("fx_conv_dgrad: an accumulation source needs accumulate = 1, stride 1 and an unsplit launch"); return P3D_EINVAL;
     }
@@ -2077,49 +2085,36 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
         if (int32_t e = fx_build_weight_images(w, d->K, d->C, RS, nullptr, ws, st, d->c_total, d->c_offset)) return e;
         wimg = ws;
     }
-    ws += align256(fx_weight_image_bytes(d->K, d->C, RS, true));
     p.Wimg = (const unsigned char*)wimg;
-    int pro = 0, epi = 0;
-    if (fuse) {
-        if (fuse->partial) { epi = 2; p.partial = fuse->partial; p.ep_c = fuse->ep_c; p.ep_tab = fuse->ep_tab; }
-        if (masked) { pro = img ? 0 : 4; epi = fuse->partial ? 6 : (img ? 7 : 4); p.pmask = fuse->pmask; p.emask = fuse->emask; }
-    }
-    const bool dsplit = d->stride == 1 && fx_dgrad_split(d).splits > 1;
+    const bool sums = fuse && fuse->partial, tail = fuse && fuse->tail_c;
+    if (sums) { p.partial = fuse->partial; p.ep_c = fuse->ep_c; p.ep_tab = fuse->ep_tab; }
+    if (masked) { p.pmask = fuse->pmask; p.emask = fuse->emask; }
+    const bool split = pl.splits > 1;
     p.tap_inner = img && RS > 1 && d->K >= FX_TAP_INNER_MIN;
-    if (fuse && fuse->tail_c) {
-        if (!(img && epi == 0 && pro == 0 && fx_dgrad_tail_applies(d) && fuse->tail_tab && fuse->tail_partial && (!fuse->tail_rc || fuse->tail_rtab))) {
+    if (tail) {
+        if (!(img && !sums && !masked && fx_dgrad_tail_applies(d) && fuse->tail_tab && fuse->tail_partial && (!fuse->tail_rc || fuse->tail_rtab))) {
             set_error("fx_conv_dgrad: the tail sums need an image-fed, dense, unsplit stride-1 data gradient without a BatchNorm epilogue (fx_dgrad_tail_applies)"); return P3D_EINVAL;
         }
-        epi = 3;
         p.tail_c = fuse->tail_c; p.tail_tab = fuse->tail_tab; p.tail_rc = fuse->tail_rc; p.tail_rtab = fuse->tail_rtab; p.tail_mask = fuse->tail_mask; p.tail_partial = fuse->tail_partial;
     }
-    const int bm = fx16_bm(d->C, img, dsplit ? 0 : pro, dsplit ? 0 : epi);
+    const auto [pro, epi] = fx_select(true, img, masked, sums, false, tail);
+    const int bm = fx16_bm(d->C, img, split ? 0 : pro, split ? FX_EPI_STORE : epi);
     p.tiles_m = (int)ceil_div(d->C, bm ? bm : FX_BM);
     if (d->stride == 1) {
         p.OH = d->H; p.OW = d->W; p.NP = d->N * d->H * d->W; p.oy0 = 0; p.ox0 = 0; p.oys = 1; p.oxs = 1;
         p.nR = d->R; p.nS = d->S; p.ntap = RS; p.r0 = 0; p.rstep = 1; p.s0 = 0; p.sstep = 1;
         p.hmul = 1; p.hoff = d->pad; p.hstep = -d->dil; p.wmul = 1; p.woff = d->pad; p.wstep = -d->dil;
-        const int tiles_n = (int)ceil_div(p.NP, FX_BN);
-        const FxSplit sp = fx_dgrad_split(d);
-        if (sp.splits > 1) {
-            p.kchunk = sp.kchunk; p.slab_stride = (size_t)d->N * d->C * d->H * d->W; p.Y = (float*)ws;
-            const float* em = p.emask;
-            p.emask = nullptr;
-            fx_launch_conv(p, img, pro == 4 ? 4 : 0, 0, bm, dim3((unsigned)(p.tiles_m * tiles_n), (unsigned)sp.splits), st);
-            fx_launch_reduce(epi, dim3((unsigned)d->C, (unsigned)(d->N < 16 ? d->N : 16)), st, (const float*)ws, dx, nullptr, sp.splits, p.slab_stride, d->N, d->C,
-                             d->H * d->W, d->accumulate, p.ep_c, p.ep_tab, p.partial, em);
-        } else {
-            if (fuse && fuse->acc_src && d->accumulate) { p.acc_src = fuse->acc_src; p.acc_mask = fuse->acc_mask; }
-            fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1), st);
-        }
+        if (!split && fuse && fuse->acc_src && d->accumulate) { p.acc_src = fuse->acc_src; p.acc_mask = fuse->acc_mask; }
+        if (int32_t e = split ? fx_launch_split(p, pl, img, pro, epi, bm, (float*)(ws + pl.slab_offset), st)
+                              : fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), 1), st)) return e;
         return check_launch("fx_conv_dgrad");
     }
     // stride 2: input pixel (ph + 2 i, pw + 2 j) of class (ph, pw) gathers dy at (i + off0 - ir * offstep, ...) over the taps r = r0 + rstep * ir that reach it
-    if (epi != 0 && epi != 4 && epi != 7) { set_error("fx_conv_dgrad: the BatchNorm-backward epilogue is not available for strided data gradients"); return P3D_EINVAL; }
+    if (fx_epi_sums(epi) != 0) { set_error("fx_conv_dgrad: the BatchNorm-backward epilogue is not available for strided data gradients"); return P3D_EINVAL; }
     const int st2 = d->stride;
     p.OH = d->H / st2; p.OW = d->W / st2; p.NP = d->N * p.OH * p.OW; p.oys = st2; p.oxs = st2;
     p.hmul = 1; p.wmul = 1;
-    const int tiles_n = (int)ceil_div(p.NP, FX_BN);
+    const int tiles_n = pl.tiles_n;
     FxConvClass cls[4];
     int ncls = 0;
     for (int ph = 0; ph < st2; ++ph)
@@ -2134,7 +2129,7 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
             c.hoff = th >= 0 ? th / st2 : -((-th) / st2); c.hstep = -(c.rstep * d->dil) / st2;
             c.woff = tw >= 0 ? tw / st2 : -((-tw) / st2); c.wstep = -(c.sstep * d->dil) / st2;
             c.oy0 = ph; c.ox0 = pw;
-            if (g_class_launches) { fx_launch_conv(c, img, pro, epi, bm, dim3((unsigned)(c.tiles_m * tiles_n), 1), st); continue; }
+            if (g_class_launches) { if (int32_t e = fx_launch_conv(c, img, pro, epi, bm, dim3((unsigned)(c.tiles_m * tiles_n), 1), st)) return e; continue; }
             cls[ncls++] = FxConvClass{c.nR, c.nS, c.ntap, c.r0, c.rstep, c.s0, c.sstep, c.hoff, c.hstep, c.woff, c.wstep, c.oy0, c.ox0};
         }
     if (ncls > 0) {
@@ -2143,7 +2138,7 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
             for (int j = i; j > 0 && cls[j].ntap > cls[j - 1].ntap; --j) { const FxConvClass t = cls[j]; cls[j] = cls[j - 1]; cls[j - 1] = t; }
         p.ncls = ncls;
         for (int i = 0; i < ncls; ++i) p.cls[i] = cls[i];
-        fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1, (unsigned)ncls), st);
+        if (int32_t e = fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1, (unsigned)ncls), st)) return e;
     }
     return check_launch("fx_conv_dgrad");
 }
@@ -2151,7 +2146,7 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
 // The data gradient that writes a block's dx last can also reduce the opening sums of the producer block's backward pass (EPI 3 of fx_conv_kernel): dense rows
 // (stride 1), one launch (no split-K), channel tiles of 128 rows (the fx16 instances have no such epilogue), whole 16-B pixel groups
 bool fx_dgrad_tail_applies(const p3d_conv_desc* d) {
-    return fx_dgrad_applies(d, 96) && d->stride == 1 && fx_dgrad_split(d).splits == 1 && (d->H * d->W) % 4 == 0 && fx16_bm(d->C, true, 0, 0) == 0;
+    return fx_dgrad_applies(d, 96) && fx_dgrad_accumulates_from_source(d) && fx16_bm(d->C, true, 0, FX_EPI_STORE) == 0;
 }
 int fx_dgrad_tail_rows(const p3d_conv_desc* d) { return (int)ceil_div((int64_t)d->N * d->H * d->W, FX_BN); }
 // partial [rows][C][4] (fp32: sum g, sum g (c - mean), sum g (rc - rmean), 0) -> sums [C][out_rows][3] (fp64), row r of the output = rows r, r + out_rows, ... in order
@@ -2174,7 +2169,7 @@ int32_t fx_tail_fold(const float* partial, int rows, int C, double* sums, int ou
 // input pixels of a strided 1x1 that no tap reaches: fx_conv_dgrad leaves them untouched, so a caller that does not accumulate zero-fills dx first
 bool fx_dgrad_has_dead_classes(const p3d_conv_desc* d) { return d->stride > 1 && d->R == 1; }
 // the dense unsplit launch can take its summand from another tensor (FxFuse::acc_src / acc_mask)
-bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d) { return d->stride == 1 && fx_dgrad_split(d).splits == 1 && (d->H * d->W) % 4 == 0; }
+bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d) { return d->stride == 1 && fx_plan(d, true).splits == 1 && (d->H * d->W) % 4 == 0; }
 
 // How many slabs (splits of the pixel reduction) a weight gradient is cut into.  Measured on MI355X over the ResNet layer classes at batch 64 with
 // image operands (tools/split_sweep.py, profiles/r03_split_sweep.txt): the best block count depends on the tile count more than on anything else -- all
@@ -2375,7 +2370,7 @@ static FxConvParams fx_stem_params(int N, int H, int W, int K) {
 }
 
 // y [N][K][H/2][W/2] = conv1(x) from the space-to-depth image of x and the restated weight image
-bool fx_stem_masked_applies(int K) { return fx16_bm(K, true, 0, 0) != 0; }       // the per-pixel output factor lives in the fx16 kernel's epilogue
+bool fx_stem_masked_applies(int K) { return fx16_bm(K, true, 0, FX_EPI_STORE) != 0; }       // the per-pixel output factor lives in the fx16 kernel's epilogue
 int32_t fx_stem_fwd(const void* x_img, const void* wimg, float* y, const float* mult, int N, int H, int W, int K, hipStream_t st) {
     FxConvParams p = fx_stem_params(N, H, W, K);
     if (mult) {
@@ -2385,9 +2380,9 @@ int32_t fx_stem_fwd(const void* x_img, const void* wimg, float* y, const float* 
     p.Ximg = (const unsigned char*)x_img; p.plane_bytes = (size_t)N * (H / 2) * (W / 2) * 32;
     p.Wimg = (const unsigned char*)wimg; p.Y = y;
     const int tiles_n = (int)ceil_div(p.NP, FX_BN);
-    const int bm = fx16_bm(K, true, 0, 0);
+    const int bm = fx16_bm(K, true, 0, FX_EPI_STORE);
     if (bm) p.tiles_m = (int)ceil_div(K, bm);
-    fx_launch_conv(p, true, 0, 0, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1), st);
+    if (int32_t e = fx_launch_conv(p, true, 0, FX_EPI_STORE, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1), st)) return e;
     return check_launch("fx_stem_fwd");
 }
 
