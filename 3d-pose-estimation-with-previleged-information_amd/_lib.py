@@ -64,6 +64,13 @@ SIGNATURES = {
     'p3d_fx_conv_fwd_infer_any': (_i32, [_desc, _ptr, _ptr, _sz, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
     'p3d_fx_conv_fwd_infer_masked_supported': (_i32, [_desc]),
     'p3d_fx_conv_fwd_infer_masked': (_i32, [_desc, _ptr, _ptr, _sz, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
+    'p3d_fx_conv_fwd_infer_masked_any_supported': (_i32, [_desc]),
+    'p3d_fx_conv_fwd_infer_masked_any_workspace_bytes': (_sz, [_desc]),
+    'p3d_fx_conv_fwd_infer_masked_any': (_i32, [_desc, _ptr, _ptr, _sz, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
+    'p3d_stem_any_padded': (_i32, [_i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    'p3d_stem_any_supported': (_i32, [_i32] * 5),
+    'p3d_stem_image_any': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
+    'p3d_stem_tail_infer_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
     'p3d_stem_tail_infer': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
     'p3d_hblock_workspace_bytes': (_i32, [_ptr, _ptr, _ptr]),
     'p3d_hblock_fwd': (_i32, [_ptr, _ptr, _ptr, _sz, _ptr]),

@@ -965,9 +965,14 @@ size_t p3d_fx_conv_fwd_infer_any_workspace_bytes(const p3d_conv_desc* d) { retur
 int32_t p3d_fx_conv_fwd_infer_masked_supported(const p3d_conv_desc* d) {
     return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate == 0 && fx_fwd_masked_applies(d) ? 1 : 0;
 }
+// The partial convolution at any map width (the ragged PRO-4 instances, FX_EPI_INFER_FACTOR; split-K: their slabs, then fx_reduce_any_kernel with the factor before b')
+int32_t p3d_fx_conv_fwd_infer_masked_any_supported(const p3d_conv_desc* d) {
+    return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate == 0 && fx_fwd_masked_any_applies(d) ? 1 : 0;
+}
+size_t p3d_fx_conv_fwd_infer_masked_any_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_fwd_any_workspace(d) : 0; }
 
-// What the three inference entries share: the checks (every text opens with the entry's own name), the profile bracket, the path counter and the launch.
-// f says which entry this is: infer == 2 the ragged one, a pmask the masked one.  (Alignment, ragged: of the base pointers only; inside the tensors the kernel picks
+// What the four inference entries share: the checks (every text opens with the entry's own name), the profile bracket, the path counter and the launch.
+// f says which entry this is: infer == 2 a ragged one, a pmask a masked one.  (Alignment, ragged: of the base pointers only; inside the tensors the kernel picks
 // 16-B or dword accesses by the address.)
 static FxFuse infer_fuse(int infer, const void* x_img, const void* wimg, const float* mask_in, const float* mult, const float* res, int32_t relu) {
     FxFuse f{};
@@ -976,10 +981,10 @@ static FxFuse infer_fuse(int infer, const void* x_img, const void* wimg, const f
 static int32_t fx_infer_entry(const char* name, bool args, const p3d_conv_desc* d, const float* x, size_t wimg_bytes, const float* bias, float* y, const FxFuse& f,
                               void* workspace, size_t workspace_bytes, void* stream) {
     P3D_REQUIRE(args, "%s: null argument", name);
-    const char* kind = f.infer == 2 ? "ragged " : f.pmask ? "masked " : "";
+    const char* kind = f.infer == 2 ? (f.pmask ? "ragged masked " : "ragged ") : f.pmask ? "masked " : "";
     char acc[32] = "";
     if (kind[0]) snprintf(acc, sizeof(acc), " accumulate=%d", d->accumulate);
-    P3D_REQUIRE(f.infer == 2 ? p3d_fx_conv_fwd_infer_any_supported(d) : f.pmask ? p3d_fx_conv_fwd_infer_masked_supported(d) : p3d_fx_conv_fwd_infer_supported(d, f.act_img != nullptr),
+    P3D_REQUIRE(f.infer == 2 ? (f.pmask ? p3d_fx_conv_fwd_infer_masked_any_supported(d) : p3d_fx_conv_fwd_infer_any_supported(d)) : f.pmask ? p3d_fx_conv_fwd_infer_masked_supported(d) : p3d_fx_conv_fwd_infer_supported(d, f.act_img != nullptr),
                 "%s: shape outside the %sx3 kernels (N=%d C=%d %dx%d K=%d R=%d stride=%d c_offset=%d c_total=%d%s)", name, kind, d->N, d->C, d->H, d->W, d->K, d->R, d->stride,
                 d->c_offset, d->c_total, acc);
     const size_t want = fx_weight_image_bytes(d->K, d->C, d->R * d->S, false);
@@ -1003,6 +1008,11 @@ int32_t p3d_fx_conv_fwd_infer_any(const p3d_conv_desc* d, const float* x, const 
 int32_t p3d_fx_conv_fwd_infer_masked(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* mask_in,
                                      const float* mult, const float* res, int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
     return fx_infer_entry("fx_conv_fwd_infer_masked", d && x && wimg && mask_in && mult && y, d, x, wimg_bytes, bias, y, infer_fuse(1, nullptr, wimg, mask_in, mult, res, relu),
+                          workspace, workspace_bytes, stream);
+}
+int32_t p3d_fx_conv_fwd_infer_masked_any(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* mask_in,
+                                         const float* mult, const float* res, int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    return fx_infer_entry("fx_conv_fwd_infer_masked_any", d && x && wimg && mask_in && mult && y, d, x, wimg_bytes, bias, y, infer_fuse(2, nullptr, wimg, mask_in, mult, res, relu),
                           workspace, workspace_bytes, stream);
 }
 
@@ -1043,6 +1053,28 @@ int32_t p3d_stem_fwd_masked(const void* x_img, const void* wimg, float* y, const
     ProfScope ps(0, &d, (hipStream_t)stream);
     fx_count(0, &d);
     return fx_stem_fwd(x_img, wimg, y, mult, N, H, W, K, (hipStream_t)stream);
+}
+
+// The stem at ANY side >= 8 (odd crops: the reference's default -side_in 257): the input is zero-extended to (Hp, Wp) >= (H, W) that fx_stem_applies takes (the smallest Wp, then the smallest Hp for it) --
+// the added zeros are the conv's own padding, so rows < (H - 1) / 2 + 1 and columns < (W - 1) / 2 + 1 of the padded conv are exactly the conv of x -- and the tail reads
+// that prefix of the pitched result.  The conv itself is p3d_stem_fwd on the padded sides.
+int32_t p3d_stem_any_padded(int32_t H, int32_t W, int32_t* Hp, int32_t* Wp) {
+    if (H < 8 || W < 8 || H > (1 << 20) || W > (1 << 20)) return 0;
+    int32_t wp = (W + 7) & ~7, hp = (H + 1) & ~1;
+    while (((hp / 2) * (wp / 2)) % 16 != 0) hp += 2;       // (Wp / 2 is a multiple of 4: at most three steps)
+    if (Hp) *Hp = hp;
+    if (Wp) *Wp = wp;
+    return 1;
+}
+int32_t p3d_stem_any_supported(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t K) {
+    int32_t hp = 0, wp = 0;
+    return p3d_stem_any_padded(H, W, &hp, &wp) && fx_stem_applies(N, Cin, hp, wp, K) ? 1 : 0;
+}
+int32_t p3d_stem_image_any(const float* x, const float* mask_in, void* img, int32_t N, int32_t Cin, int32_t H, int32_t W, void* stream) {
+    int32_t hp = 0, wp = 0;
+    P3D_REQUIRE(x && img && N > 0 && Cin >= 1 && Cin <= 4 && p3d_stem_any_padded(H, W, &hp, &wp) && (int64_t)N * Cin * H * W < (1ll << 31), "stem_image_any: bad argument");
+    P3D_REQUIRE((reinterpret_cast<uintptr_t>(img) & 15) == 0, "stem_image_any: the image must be 16-B aligned");
+    return fx_stem_image_any(x, mask_in, img, N, Cin, H, W, hp, wp, (hipStream_t)stream);
 }
 
 int32_t p3d_stem_wgrad(const float* dy, const void* x_img, float* dw, int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t K, int32_t accumulate, void* workspace,

@@ -80,7 +80,7 @@ struct FxFuse {
     const float* tail_c; const float* tail_tab; const float* tail_rc; const float* tail_rtab; const unsigned char* tail_mask; float* tail_partial;
     // FWD, inference (a conv with its eval-mode BatchNorm folded into the weight image and the bias): y = conv + bias (+ y when accumulating) (+ res) (then ReLU), on
     // the split-K path applied by the reduce pass after the slabs are summed
-    int infer;              // 1; 2: on the ragged instances (any map width; fp32 operand, dense, no partial convolution)
+    int infer;              // 1; 2: on the ragged instances (any map width; fp32 operand, dense; a partial convolution with pmask and emask)
     const float* res;
     int relu;
 };
@@ -132,6 +132,7 @@ bool fx_dgrad_tail_applies(const p3d_conv_desc* d);                 // the image
 int fx_dgrad_tail_rows(const p3d_conv_desc* d);                     // rows of tail_partial [rows][C][4]
 int32_t fx_tail_fold(const float* partial, int rows, int C, double* sums, int out_rows, hipStream_t st);      // -> sums [C][out_rows][3]
 bool fx_fwd_masked_applies(const p3d_conv_desc* d);          // partial convolutions: the masked instances exist for unsplit launches without bias
+bool fx_fwd_masked_any_applies(const p3d_conv_desc* d);      // the same at any map width (the ragged PRO-4 instances, inference only)
 bool fx_dgrad_masked_applies(const p3d_conv_desc* d);
 bool fx_wgrad_masked_applies(const p3d_conv_desc* d);
 size_t fx_fwd_workspace(const p3d_conv_desc* d);
@@ -192,6 +193,8 @@ size_t fx_stem_image_bytes(int N, int H, int W);
 size_t fx_stem_weight_image_bytes(int K);
 size_t fx_stem_workspace(int N, int H, int W, int K);
 int32_t fx_stem_image(const float* x, const float* mask, void* img, int N, int Cin, int H, int W, hipStream_t st);      // mask: per-pixel factor of x [N][1][H][W], or null
+// the space-to-depth image of x zero-extended to (Hp, Wp) >= (H, W): dword fetches checked against the true sides, every pixel beyond them an exact zero
+int32_t fx_stem_image_any(const float* x, const float* mask, void* img, int N, int Cin, int H, int W, int Hp, int Wp, hipStream_t st);
 bool fx_stem_masked_applies(int K);
 int32_t fx_stem_weight_image(const float* w, int K, int Cin, void* wimg, void* workspace, hipStream_t st);
 // mult: per-pixel factor of the result (forward) / of dy (weight gradient), [N][1][H/2][W/2], or null -- the partial-convolution stem of the partial families

@@ -149,11 +149,13 @@ __device__ __forceinline__ FxConvParams fx_class_params(const FxConvParams& in) 
 // RAG ("ragged", fx_conv_fwd with FxFuse::infer == 2): map widths that are not multiples of 4.  The GEMM column stays the flat pixel index, so a thread's four
 // consecutive pixels may straddle an output row or an image: their positions are derived per element when the tap changes, from the first pixel's (row, column,
 // image) kept across the K loop; every fetch is a dword load, and the dense store falls back to dword accesses wherever four pixels do not share an image or a
-// 16-B line.  fp32-fed forward only, epilogues 8 (inference) and 0 (split-K slabs).
+// 16-B line.  fp32-fed forward only, epilogues 8 (inference) and 0 (split-K slabs); as a partial convolution (PRO 4) epilogues 9 and 0: the operand factor is fetched
+// per element at the same positions from the one-plane mask (its own image offset, stepped beside x's), the result factor per element in the staged store.
 template <int AMODE, int PRO, int EPIX, bool TAPI = false, bool RAG = false>
 __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in) {
     static_assert(!TAPI || AMODE == 1, "the tap-inner K order is an image-fed instance");
-    static_assert(!RAG || (AMODE == 0 && PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER)), "the ragged instances are the fp32-fed forward with the plain / inference epilogue");
+    static_assert(!RAG || (AMODE == 0 && ((PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER)) || (PRO == 4 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER_FACTOR)))),
+                  "the ragged instances are the fp32-fed forward with the plain / inference epilogue, dense or as a partial convolution");
     constexpr int SUMS = fx_epi_sums(EPIX);
     constexpr bool EM = fx_epi_factor(EPIX);
     const FxConvParams p = fx_class_params(p_in);
@@ -218,13 +220,17 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     // row ends and image ends, so the K loop carries three values instead of a position per element
     // (derived here again rather than kept from the block above, which computes the same row and column: sharing them was tried and the register allocator then
     // spills 92 B per lane instead of 64, profiles/eval_folded_anysize.md)
-    int rg_oh = 0, rg_ow = 0, rg_img = 0;
+    // PRO 4: a fourth, the offset of the image's mask plane (rPM is based at image nfirst like rX).  (Deriving all four from `col` again at every tap change, and
+    // making the second sub-tile's fragment offsets from the first's in every step, were tried to free registers: neither removes the loop's spill reloads,
+    // profiles/eval_folded_oddsides.md)
+    int rg_oh = 0, rg_ow = 0, rg_img = 0, rg_mimg = 0;
     if constexpr (RAG) {
         const int cc = col_ok ? col : 0;
         const int pn = cc / OHW;
         const int rem = cc - pn * OHW;
         rg_oh = rem / p.OW; rg_ow = rem - rg_oh * p.OW;
         rg_img = ((pn - nfirst) * p.Cred + trow) * HWi;
+        rg_mimg = (pn - nfirst) * HWi;
     }
     const i32x4 rPM = fx_rsrc(PRO == 4 ? p.pmask + (size_t)nfirst * HWi : nullptr, PRO == 4 ? (size_t)(p.N - nfirst) * HWi * sizeof(float) : 0);
 
@@ -246,12 +252,14 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
         } else if constexpr (RAG) {
             const int dh = p.hoff + ir * p.hstep, dw = p.woff + wshift;         // wave-uniform: the tap's displacement
             int oh = rg_oh, ow = rg_ow, im = rg_img;
+            int mim = rg_mimg;                                                  // PRO 4: the same walk over the one-plane mask (stride HWi per image)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int he = oh * p.hmul + dh, we = ow * p.wmul + dw;
                 const bool ok = col + e < p.NP && (unsigned)he < (unsigned)p.Hi && (unsigned)we < (unsigned)p.Wi;
                 x_voff[e] = ok ? (im + he * p.Wi + we) * 4 : FX_OOB;
-                if (++ow == p.OW) { ow = 0; if (++oh == p.OH) { oh = 0; im += p.Cred * HWi; } }      // the next flat pixel: next row, next image
+                if constexpr (PRO == 4) tmask[e] = fx_buffer_load_f32(rPM, ok ? (mim + he * p.Wi + we) * 4 : FX_OOB, 0, 0);
+                if (++ow == p.OW) { ow = 0; if (++oh == p.OH) { oh = 0; im += p.Cred * HWi; mim += HWi; } }      // the next flat pixel: next row, next image
             }
         } else {
             x_vec = p.wmul == 1 && ((p.woff + wshift) & 3) == 0;        // wave-uniform: the four pixels are one aligned 16-B group, in or out together
@@ -563,6 +571,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                             const size_t ae = ((size_t)ne * p.M + m) * OHW + re;
                             float ve = v[e];
                             if (accum) ve += yout[ae];
+                            if constexpr (EPIX == FX_EPI_INFER_FACTOR) ve = ve * p.emask[(size_t)ne * OHW + re] + (p.bias ? p.bias[m] : 0.f);      // this element's own image
                             if constexpr (fx_epi_infer(EPIX)) {
                                 if (p.ep_res) ve += p.ep_res[ae];
                                 if (p.ep_relu) ve = fmaxf(ve, 0.f);
@@ -585,7 +594,12 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                     v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3];
                 }
                 if constexpr (EPIX == FX_EPI_INFER_FACTOR) {        // (fx_conv_fwd launches it dense, unsplit and without accumulate: one factor per pixel, the plane of image n)
-                    const f32x4 em = *reinterpret_cast<const f32x4*>(p.emask + (size_t)n * OHW + rem);
+                    // (ragged: with OHW odd the factor's line n OHW + rem and y's ((n M + m) OHW + rem) are 16-B aligned at different times -- element by element)
+                    f32x4 em;
+                    if constexpr (RAG) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) em[e] = p.emask[(size_t)n * OHW + rem + e];
+                    } else em = *reinterpret_cast<const f32x4*>(p.emask + (size_t)n * OHW + rem);
                     const float bb = p.bias ? p.bias[m] : 0.f;
                     v[0] = v[0] * em[0] + bb; v[1] = v[1] * em[1] + bb; v[2] = v[2] * em[2] + bb; v[3] = v[3] * em[3] + bb;
                 }
@@ -1014,13 +1028,17 @@ __global__ __launch_bounds__(256) void fx_reduce_kernel(const float* __restrict_
 }
 
 // The same sum for the ragged forward (fx_conv_kernel's RAG instances: OHW is no multiple of 4, so no channel row is 16-B aligned): one element per thread,
-// y (=|+=) sum over the slabs + bias (+ res) (then ReLU), in the order of the vector kernel.  total = N * M * OHW.
+// y (=|+=) sum over the slabs (* emask) + bias (+ res) (then ReLU), in the order of the vector kernel.  total = N * M * OHW.
 __global__ __launch_bounds__(256) void fx_reduce_any_kernel(const float* __restrict__ slabs, float* __restrict__ y, const float* __restrict__ bias, int nsplit,
-                                                            size_t slab_stride, unsigned total, int M, int OHW, int accumulate, const float* __restrict__ res, int relu) {
+                                                            size_t slab_stride, unsigned total, int M, int OHW, int accumulate, const float* __restrict__ emask,
+                                                            const float* __restrict__ res, int relu) {
     for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
         float v = slabs[i];
         for (int z = 1; z < nsplit; ++z) v += slabs[(size_t)z * slab_stride + i];
-        if (bias) v += bias[(i / (unsigned)OHW) % (unsigned)M];
+        if (emask) {         // folded partial convolution: the factor [N][1][OH][OW] first, then b' (an empty window gives b'), as fx_reduce_kernel
+            const float em = emask[(size_t)(i / ((unsigned)M * (unsigned)OHW)) * OHW + i % (unsigned)OHW];
+            v = v * em + (bias ? bias[(i / (unsigned)OHW) % (unsigned)M] : 0.f);
+        } else if (bias) v += bias[(i / (unsigned)OHW) % (unsigned)M];
         if (accumulate) v += y[i];
         if (res) v += res[i];
         if (relu) v = fmaxf(v, 0.f);
@@ -1718,7 +1736,8 @@ constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool 
     X(0, 4, FX_EPI_STORE, false, false) X(0, 4, FX_EPI_FACTOR, false, false) X(0, 4, FX_EPI_FACTOR_STATS, false, false) X(0, 4, FX_EPI_INFER_FACTOR, false, false) \
     X(1, 0, FX_EPI_STORE, false, false) X(1, 0, FX_EPI_STATS, false, false) X(1, 0, FX_EPI_BWD_SUMS, false, false) X(1, 0, FX_EPI_TAIL_SUMS, false, false)    \
     X(1, 0, FX_EPI_FACTOR_STATS, false, false) X(1, 0, FX_EPI_FACTOR_BWD_SUMS, false, false) X(1, 0, FX_EPI_FACTOR_IMG, false, false) X(1, 0, FX_EPI_INFER, false, false) \
-    X(1, 0, FX_EPI_STORE, true, false) X(1, 0, FX_EPI_STATS, true, false) X(1, 0, FX_EPI_BWD_SUMS, true, false) X(0, 0, FX_EPI_STORE, false, true) X(0, 0, FX_EPI_INFER, false, true)
+    X(1, 0, FX_EPI_STORE, true, false) X(1, 0, FX_EPI_STATS, true, false) X(1, 0, FX_EPI_BWD_SUMS, true, false) X(0, 0, FX_EPI_STORE, false, true) X(0, 0, FX_EPI_INFER, false, true) \
+    X(0, 4, FX_EPI_INFER_FACTOR, false, true) X(0, 4, FX_EPI_STORE, false, true)
 #define P3D_FX16_CONV_INSTANCES(X)                                                                                             \
     X(96, FX_EPI_STORE, false) X(96, FX_EPI_STATS, false) X(96, FX_EPI_BWD_SUMS, false) X(96, FX_EPI_INFER, false)             \
     X(64, FX_EPI_STORE, false) X(64, FX_EPI_STATS, false) X(64, FX_EPI_BWD_SUMS, false) X(64, FX_EPI_INFER, false)             \
@@ -1745,7 +1764,8 @@ constexpr bool fx_select_covered() {
         if (!fx_instance(0, img, s.pro, s.epi, false, false) || !fx_instance(0, img, s.pro, FX_EPI_STORE, false, false)) return false;
         if (img && s.pro == 0 && fx16_epi(s.epi) >= 0 && !(fx_instance(96, img, 0, s.epi, false, false) && fx_instance(64, img, 0, s.epi, false, false))) return false;
     }
-    return fx_instance(0, false, 0, FX_EPI_INFER, false, true) && fx_instance(0, false, 0, FX_EPI_STORE, false, true);      // (the ragged forward: fp32-fed inference)
+    return fx_instance(0, false, 0, FX_EPI_INFER, false, true) && fx_instance(0, false, 0, FX_EPI_STORE, false, true) &&     // (the ragged forward: fp32-fed inference,
+           fx_instance(0, false, 4, FX_EPI_INFER_FACTOR, false, true) && fx_instance(0, false, 4, FX_EPI_STORE, false, true);    //  dense and as a partial convolution)
 }
 static_assert(fx_select_covered(), "fx_select returns a code without a compiled instance");
 void fx_tune(int what, int value) {
@@ -1801,6 +1821,7 @@ static FxPlan fx_plan(const p3d_conv_desc* d, bool dgrad, bool ragged = false) {
 // partial convolutions (PRO 4 / EPI 4 instances): 64-channel layers included (half-dead tiles), unsplit launches only
 static bool fx_masked_on() { static const bool on = [] { const char* e = getenv("P3D_FX_MASKED"); return !(e && atoi(e) == 0); }(); return on; }      // A/B switch
 bool fx_fwd_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_fwd_applies(d, 64); }
+bool fx_fwd_masked_any_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_fwd_any_applies(d, 64); }
 bool fx_dgrad_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_dgrad_applies(d, 64); }
 bool fx_wgrad_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_wgrad_applies(d, 96); }
 size_t fx_fwd_workspace(const p3d_conv_desc* d) { return fx_plan(d, false).workspace; }
@@ -1995,7 +2016,7 @@ static int32_t fx_launch_split(FxConvParams p, const FxPlan& pl, bool img, int p
     if (rag) {
         const unsigned total = (unsigned)((size_t)p.N * p.M * OHW);          // (fx_common: below 2^31)
         hipLaunchKernelGGL(fx_reduce_any_kernel, dim3((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096), dim3(256), 0, st, (const float*)slabs, y, bias, pl.splits,
-                           pl.slab_stride, total, p.M, OHW, p.accumulate, p.ep_res, p.ep_relu);
+                           pl.slab_stride, total, p.M, OHW, p.accumulate, em, p.ep_res, p.ep_relu);
     } else {
         const int sums = fx_epi_sums(epi);       // (of the result times the factor, where there is one)
         auto* reduce = sums == 1 ? fx_reduce_kernel<1> : sums == 2 ? fx_reduce_kernel<2> : fx_reduce_kernel<0>;
@@ -2014,7 +2035,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     const bool img = fuse && fuse->act_img;
     const bool masked = fuse && (fuse->pmask || fuse->emask);
     const bool infer = fuse && fuse->infer;
-    const bool rag = fuse && fuse->infer == 2;          // the ragged instances (p3d_fx_conv_fwd_infer_any): any map width
+    const bool rag = fuse && fuse->infer == 2;          // the ragged instances (p3d_fx_conv_fwd_infer_any, p3d_fx_conv_fwd_infer_masked_any): any map width
     const void* wimg = fuse ? fuse->wimg : nullptr;
     if (masked && (!fuse->emask || (bias && !infer) || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr))) {
         set_error("fx_conv_fwd: the partial-convolution instances take the output factor, the input factor exactly for an fp32 operand, and no bias"); return P3D_EINVAL;
@@ -2025,7 +2046,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     P3D_REQUIRE(!infer || (!fuse->partial && wimg && (!masked || (!img && !d->accumulate))),
                 "fx_conv_fwd: the inference epilogue takes a cached folded weight image, no other fusion, and a partial convolution only from an fp32 operand");
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
-    P3D_REQUIRE(!rag || (!img && !masked), "fx_conv_fwd: the ragged forward takes an fp32 operand and no partial convolution");
+    P3D_REQUIRE(!rag || !img, "fx_conv_fwd: the ragged forward takes an fp32 operand");
     const FxPlan pl = fx_plan(d, false, rag);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     FxConvParams p{};
@@ -2293,6 +2314,44 @@ __global__ __launch_bounds__(256) void fx_s2d_image_kernel(const float* __restri
     }
 }
 
+// The same image of x zero-extended to (Hp, Wp) (p3d_stem_image_any: odd sides).  One thread per pixel of the padded half-resolution grid; every source element is a
+// dword load checked against the true H and W (at odd W a row is only 4-B aligned), and what lies at or beyond them stays the exact zero v starts with, in all three planes.
+__global__ __launch_bounds__(256) void fx_s2d_image_any_kernel(const float* __restrict__ x, const float* __restrict__ mask, unsigned char* __restrict__ img, size_t plane_bytes, int N,
+                                                               int Cin, int H, int W, int H2, int W2) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)N * H2 * W2) return;
+    const int j2 = (int)(i % W2), i2 = (int)((i / W2) % H2), n = (int)(i / ((long long)W2 * H2));
+    float v[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) v[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int pi = 0; pi < 2; ++pi)
+#pragma unroll
+            for (int pj = 0; pj < 2; ++pj) {
+                const int h = 2 * i2 + pi, w = 2 * j2 + pj;
+                if (c < Cin && h < H && w < W) {
+                    float q = x[(((size_t)n * Cin + c) * H + h) * W + w];
+                    if (mask) {          // (one explicit scalar multiply per value, as in fx_s2d_image_kernel: no packed-fp32 instruction may be formed)
+                        const float mq = mask[((size_t)n * H + h) * W + w];
+                        asm("v_mul_f32 %0, %1, %2" : "=v"(q) : "v"(q), "v"(mq));
+                    }
+                    v[c * 4 + pi * 2 + pj] = q;
+                }
+            }
+    unsigned hp[8], mp[8], lp[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) fx_split2(v[2 * e], v[2 * e + 1], hp[e], mp[e], lp[e]);
+    unsigned char* dst = img + (size_t)i * 32;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        *reinterpret_cast<i32x4*>(dst + 16 * h) = i32x4{(int)hp[4 * h], (int)hp[4 * h + 1], (int)hp[4 * h + 2], (int)hp[4 * h + 3]};
+        *reinterpret_cast<i32x4*>(dst + plane_bytes + 16 * h) = i32x4{(int)mp[4 * h], (int)mp[4 * h + 1], (int)mp[4 * h + 2], (int)mp[4 * h + 3]};
+        *reinterpret_cast<i32x4*>(dst + 2 * plane_bytes + 16 * h) = i32x4{(int)lp[4 * h], (int)lp[4 * h + 1], (int)lp[4 * h + 2], (int)lp[4 * h + 3]};
+    }
+}
+
 // w [K][Cin][7][7] -> w' [K][16][4][4]
 __global__ __launch_bounds__(256) void fx_stem_weights_kernel(const float* __restrict__ w, float* __restrict__ w2, int K, int Cin) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -2350,6 +2409,12 @@ int32_t fx_stem_image(const float* x, const float* mask, void* img, int N, int C
     const long long total = (long long)N * (H / 2) * (W / 2);
     hipLaunchKernelGGL(fx_s2d_image_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, x, mask, (unsigned char*)img, (size_t)total * 32, N, Cin, H, W);
     return check_launch("fx_stem_image");
+}
+
+int32_t fx_stem_image_any(const float* x, const float* mask, void* img, int N, int Cin, int H, int W, int Hp, int Wp, hipStream_t st) {
+    const long long total = (long long)N * (Hp / 2) * (Wp / 2);
+    hipLaunchKernelGGL(fx_s2d_image_any_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, x, mask, (unsigned char*)img, (size_t)total * 32, N, Cin, H, W, Hp / 2, Wp / 2);
+    return check_launch("fx_stem_image_any");
 }
 
 // w [K][Cin][7][7] -> the forward weight image of the restated convolution (workspace: K * 256 floats)

@@ -127,6 +127,42 @@ __global__ __launch_bounds__(256) void stem_tail_infer_kernel(const float* __res
     }
 }
 
+// The same behind the stem at odd sides (p3d_stem_tail_infer_any): c is the conv of the zero-extended input, [NC][Hc][Wc] with Wc % 4 == 0, of which only rows < H and
+// columns < W are the stem's output (the pad columns hold real, non-zero conv results of the image edge and must not enter a window).  mult (optional, [N][1][H][W]
+// dense: the partial-convolution factor) is multiplied in BEFORE the max.  y [NC][Ho][Wo] has 4-B aligned rows at odd Wo: dword stores.
+__global__ __launch_bounds__(256) void stem_tail_infer_any_kernel(const float* __restrict__ x, const float* __restrict__ bias, const float* __restrict__ mult,
+                                                                  float* __restrict__ y, int C, int NC, int Hc, int Wc, int H, int W, int Ho, int Wo) {
+    const int J = (Wo + 1) / 2;                      // a thread: input columns 4 j .. 4 j + 3 (4 j <= W - 1 for every j < J), outputs 2 j and 2 j + 1
+    const size_t total = (size_t)NC * Ho * J;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int j = (int)(i % J);
+        const int ho = (int)((i / J) % Ho);
+        const size_t nc = i / ((size_t)J * Ho);
+        const float* src = x + nc * Hc * Wc;
+        const float* mrow = mult ? mult + (nc / C) * H * W : nullptr;
+        float b0 = -INFINITY, b1 = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int hi = 2 * ho - 1 + r;
+            if ((unsigned)hi >= (unsigned)H) continue;
+            const float4 q = *reinterpret_cast<const float4*>(src + (size_t)hi * Wc + 4 * j);
+            float v[5] = {j > 0 ? src[(size_t)hi * Wc + 4 * j - 1] : -INFINITY, q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int e = 0; e < 5; ++e) {
+                const int col = 4 * j - 1 + e;
+                if (col >= W) v[e] = -INFINITY;
+                else if (mrow && col >= 0) v[e] *= mrow[(size_t)hi * W + col];
+            }
+            b0 = fmaxf(b0, fmaxf(v[0], fmaxf(v[1], v[2])));
+            b1 = fmaxf(b1, fmaxf(v[2], fmaxf(v[3], v[4])));
+        }
+        const float bb = bias[nc % C];
+        float* dst = y + (nc * Ho + ho) * Wo + 2 * j;
+        dst[0] = fmaxf(b0 + bb, 0.f);
+        if (2 * j + 1 < Wo) dst[1] = fmaxf(b1 + bb, 0.f);
+    }
+}
+
 __global__ __launch_bounds__(256) void maxpool_bwd4_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ idx, float* __restrict__ dx,
                                                            int NC, int H, int W, int Ho, int Wo) {
     const int W4 = W / 4;
@@ -506,6 +542,18 @@ int32_t p3d_stem_tail_infer(const float* c, const float* bias, float* y, int32_t
     const unsigned blocks = (unsigned)(ceil_div(total4, 256) < 16384 ? ceil_div(total4, 256) : 16384);
     hipLaunchKernelGGL(stem_tail_infer_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c, bias, y, C, N * C, H, W, Ho, Wo);
     return check_launch("stem_tail_infer");
+}
+
+int32_t p3d_stem_tail_infer_any(const float* c, const float* bias, const float* mult, float* y, int32_t N, int32_t C, int32_t H, int32_t W, void* stream) {
+    int32_t hp = 0, wp = 0;
+    P3D_REQUIRE(c && bias && y && N > 0 && C > 0 && p3d_stem_any_padded(H, W, &hp, &wp), "stem_tail_infer_any: bad argument (N=%d C=%d %dx%d)", N, C, H, W);
+    P3D_REQUIRE(((uintptr_t)c & 15) == 0, "stem_tail_infer_any: c must be 16-B aligned");
+    const int Hc = hp / 2, Wc = wp / 2, Hv = (H - 1) / 2 + 1, Wv = (W - 1) / 2 + 1;      // the pitch of c; its valid rows and columns
+    const int Ho = (Hv - 1) / 2 + 1, Wo = (Wv - 1) / 2 + 1;
+    const int64_t total = (int64_t)N * C * Ho * ((Wo + 1) / 2);
+    const unsigned blocks = (unsigned)(ceil_div(total, 256) < 16384 ? ceil_div(total, 256) : 16384);
+    hipLaunchKernelGGL(stem_tail_infer_any_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c, bias, mult, y, C, N * C, Hc, Wc, Hv, Wv, Ho, Wo);
+    return check_launch("stem_tail_infer_any");
 }
 
 int32_t p3d_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int32_t NC, int32_t H, int32_t W, void* stream) {

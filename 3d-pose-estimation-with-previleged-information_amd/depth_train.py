@@ -428,7 +428,7 @@ class Trainer:
     def _fold(self, net):
         if infer.fp8_enabled():                              # (takes precedence over the other two switches)
             return infer.fold_fp8(net)
-        return infer.fold_half(net) if self.half_acc else infer.fold(net, any_size=True)      # (any_size: the default -side_in 257 stays on the x3 kernels)
+        return infer.fold_half(net) if self.half_acc else infer.fold(net, any_size=True, odd_sides=True)      # (the default -side_in 257 stays on the x3 kernels, stems and partial layers included)
 
     # ---- distillation: the "privileged information" training (depth_train.py:107-129,161-283,641-647,682-691) --------
     def set_teacher(self, teacher):

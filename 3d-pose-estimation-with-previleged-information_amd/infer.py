@@ -12,7 +12,11 @@ p3d_fx_conv_fwd_infer, whose epilogue adds b', the residual and the ReLU, and on
 
 A conv the x3 forward cannot take (odd sizes, fx_fwd_applies) goes through today's eval path for that layer (ops.conv_bn_eval).  `fold(model,
 any_size=True)` sends such a dense conv to p3d_fx_conv_fwd_infer_any first, the same x3 arithmetic on the same folded image for map widths that are not
-multiples of 4 (the reference's default -side_in 257: 65, 33 and 17 wide maps); the stems and the partial layers at odd sides stay where they are.
+multiples of 4 (the reference's default -side_in 257: 65, 33 and 17 wide maps).  `fold(model, any_size=True, odd_sides=True)` folds what that leaves at an odd
+crop as well: a partial conv the masked entry refuses goes to p3d_fx_conv_fwd_infer_masked_any (the ragged kernels with mask_in in the operand fetch and mult in
+the store), and a 7x7 stem p3d_stem_supported refuses runs on p3d_stem_image_any (the space-to-depth image of the input zero-extended to sides the stem
+kernel takes: 257 -> 264) + p3d_stem_fwd on the padded sides + p3d_stem_tail_infer_any (the max pool over the valid prefix of the pitched result, a masked
+stem's mult multiplied in before the max).  Without odd_sides those stay where they were, launch for launch.
 
 The partial-convolution layers of partial_depthnet (stem, layer1, layer2) and partial_fusionnet (conv2, layer5, layer6) fold as well: each conv runs on
 p3d_fx_conv_fwd_infer_masked (mask_in multiplied into the operand, y = relu?(conv * mult + b' + res), the factor before b'), each with its own
@@ -306,8 +310,9 @@ class FoldedNet(_Folded):
     as the image the stem kernels read."""
     WHO, HALF, Conv = 'infer.fold', False, _Conv
 
-    def __init__(self, model, any_size=False):
+    def __init__(self, model, any_size=False, odd_sides=False):
         self.any_size = bool(any_size)
+        self.odd_sides = bool(odd_sides) and self.any_size      # (acts only together with any_size)
         super().__init__(model)
 
     def _allocate(self, device):
@@ -379,10 +384,16 @@ class FoldedNet(_Folded):
 
     def _pconv(self, c, x, veil, res=None, relu=True):
         """A partial convolution (partial_conv.py) + its folded BatchNorm: y = relu?(conv(x * veil, w') * mult + b' + res), mult and mask_out from the box count
-        of veil (ops.mask_count); returns (y, mask_out).  A conv the masked entry cannot take runs as the module, then the eval-mode BatchNorm pass."""
+        of veil (ops.mask_count); returns (y, mask_out).  odd_sides: a conv the masked entry refuses is offered to p3d_fx_conv_fwd_infer_masked_any (any map
+        width).  A conv neither takes runs as the module, then the eval-mode BatchNorm pass."""
         L = lib()
         d = c.desc(x) if c.foldable else None
-        if d is None or not L.p3d_fx_conv_fwd_infer_masked_supported(ctypes.byref(d)):
+        name = None
+        if d is not None and L.p3d_fx_conv_fwd_infer_masked_supported(ctypes.byref(d)):
+            name, ws_name = 'p3d_fx_conv_fwd_infer_masked', 'p3d_fx_conv_fwd_infer_workspace_bytes'
+        elif d is not None and self.odd_sides and L.p3d_fx_conv_fwd_infer_masked_any_supported(ctypes.byref(d)):
+            name, ws_name = 'p3d_fx_conv_fwd_infer_masked_any', 'p3d_fx_conv_fwd_infer_masked_any_workspace_bytes'
+        if name is None:
             y, mask_out = c.conv(x, veil)
             return c.bn(y, res=res, relu=relu), mask_out
         if tuple(veil.shape) != (d.N, 1, d.H, d.W) or veil.dtype != torch.float32:
@@ -390,10 +401,35 @@ class FoldedNet(_Folded):
         mult, mask_out = ops.mask_count(veil, c.r, c.stride, c.pad, c.dil)
         x = x.contiguous()
         y = torch.empty((d.N, d.K, d.Ho, d.Wo), dtype=torch.float32, device=x.device)
-        ws = self._ws(L.p3d_fx_conv_fwd_infer_workspace_bytes(ctypes.byref(d)))
-        check(L.p3d_fx_conv_fwd_infer_masked(ctypes.byref(d), ops._p(x), self._at(c.img_off), c.img_bytes, self._at(c.bias_off), ops._p(veil.contiguous()),
-                                             ops._p(mult), ops._p(None if res is None else res.contiguous()), int(bool(relu)), ops._p(y), ops._p(ws), ws.numel(),
-                                             ops._stream()), 'p3d_fx_conv_fwd_infer_masked')
+        ws = self._ws(getattr(L, ws_name)(ctypes.byref(d)))
+        check(getattr(L, name)(ctypes.byref(d), ops._p(x), self._at(c.img_off), c.img_bytes, self._at(c.bias_off), ops._p(veil.contiguous()),
+                               ops._p(mult), ops._p(None if res is None else res.contiguous()), int(bool(relu)), ops._p(y), ops._p(ws), ws.numel(),
+                               ops._stream()), name)
+        return y, mask_out
+
+    def _stem_any(self, s, x, veil=None):
+        """The folded stem at sides p3d_stem_supported refuses (odd_sides): the space-to-depth image of x (* veil) zero-extended to the padded sides, the stem conv
+        on those (never with the output factor), then relu(maxpool(c * mult) + b') over the valid prefix of the pitched c.  None when the shape is outside it."""
+        n, cin, h, w = x.shape
+        L = lib()
+        if not (self.odd_sides and s.foldable and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_any_supported(n, cin, h, w, s.k)):
+            return None
+        hp, wp = ctypes.c_int32(), ctypes.c_int32()
+        L.p3d_stem_any_padded(h, w, ctypes.byref(hp), ctypes.byref(wp))
+        hp, wp = hp.value, wp.value
+        x = x.contiguous()
+        st = ops._stream()
+        mult = mask_out = None
+        if veil is not None:
+            veil = veil.contiguous()
+            mult, mask_out = ops.mask_count(veil, 7, 2, 3, 1)
+        x_img = torch.empty(L.p3d_stem_image_bytes(n, hp, wp), dtype=torch.uint8, device=x.device)
+        check(L.p3d_stem_image_any(ops._p(x), ops._p(veil), ops._p(x_img), n, cin, h, w, st), 'p3d_stem_image_any')
+        c = torch.empty((n, s.k, hp // 2, wp // 2), dtype=torch.float32, device=x.device)
+        check(L.p3d_stem_fwd(ops._p(x_img), self._at(s.img_off), ops._p(c), n, cin, hp, wp, s.k, st), 'p3d_stem_fwd')
+        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        y = torch.empty((n, s.k, (ho - 1) // 2 + 1, (wo - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+        check(L.p3d_stem_tail_infer_any(ops._p(c), self._at(s.bias_off), ops._p(mult), ops._p(y), n, s.k, h, w, st), 'p3d_stem_tail_infer_any')
         return y, mask_out
 
     def _stem(self, s, x):
@@ -401,6 +437,9 @@ class FoldedNet(_Folded):
         L = lib()
         if not (s.foldable and not s.masked and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_supported(n, cin, h, w, s.k)
                 and (h // 2) % 2 == 0 and (w // 2) % 4 == 0):
+            out = None if s.masked else self._stem_any(s, x)
+            if out is not None:
+                return out[0]
             from ._trunk import stem
             return stem(s.conv, s.bn, self.model.maxpool, x)
         x = x.contiguous()
@@ -420,8 +459,11 @@ class FoldedNet(_Folded):
         L = lib()
         if not (s.foldable and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_masked_supported(n, cin, h, w, s.k)
                 and (h // 2) % 2 == 0 and (w // 2) % 4 == 0):
+            out = self._stem_any(s, x, veil) if s.masked and veil.dtype == torch.float32 and tuple(veil.shape) == (n, 1, h, w) else None
+            if out is not None:
+                return out[0], self.model.maxpool(out[1])
             from ._trunk import stem_tail
-            c, veil = s.conv(x, veil)                       # today's path (odd sides: the reference's default -side_in 257)
+            c, veil = s.conv(x, veil)                       # today's path (odd sides without odd_sides)
             return stem_tail(s.bn, self.model.maxpool, c), self.model.maxpool(veil)
         x, veil = x.contiguous(), veil.contiguous()
         mult, mask_out = ops.mask_count(veil, 7, 2, 3, 1)
@@ -452,11 +494,12 @@ class FoldedConv(FoldedNet):
     """One conv (no bias) + eval-mode BatchNorm, folded: FoldedConv(conv, bn)(x, res=None, relu=False) = relu(bn(conv(x)) + res).  For a PartialConv
     the validity mask comes along: FoldedConv(pconv, bn)(x, res, relu, veil=mask_in) = (relu(bn(pconv(x, mask_in)[0]) + res), mask_out).
     any_size (default False: a map width p3d_fx_conv_fwd_infer refuses runs on ops.conv_bn_eval, the fp32-MFMA kernel, which tests rely on): offer such a
-    dense conv to p3d_fx_conv_fwd_infer_any first."""
+    dense conv to p3d_fx_conv_fwd_infer_any first; with odd_sides as well, a partial conv the masked entry refuses to p3d_fx_conv_fwd_infer_masked_any."""
     WHO = 'infer.FoldedConv'
 
-    def __init__(self, conv, bn, any_size=False):
+    def __init__(self, conv, bn, any_size=False, odd_sides=False):
         self.any_size = bool(any_size)
+        self.odd_sides = bool(odd_sides) and self.any_size
         self.model, self.stems = torch.nn.ModuleList([conv, bn]), {}      # (model: what refresh() checks)
         self.conv = _Conv(conv, bn)
         self.convs = [self.conv]
@@ -469,12 +512,14 @@ class FoldedConv(FoldedNet):
             return self._pconv(self.conv, x, veil, res, relu) if self.conv.partial else self._conv_bn(self.conv, x, res, relu)
 
 
-def fold(model, any_size=False):
+def fold(model, any_size=False, odd_sides=False):
     """FoldedNet of a network in eval mode (every BatchNorm frozen); raises P3DError for a BatchNorm in training mode or a -half_acc model.
     any_size: a dense conv whose map widths are not multiples of 4 (every layer behind the stem at -side_in 257) runs on p3d_fx_conv_fwd_infer_any
     instead of the per-layer fallback.  The default stays False: without the keyword a refused layer lands on ops.conv_bn_eval (the fp32-MFMA
-    kernel) exactly as before, which is what the existing tests of the fallback count."""
-    return FoldedNet(getattr(model, 'module', model), any_size=any_size)
+    kernel) exactly as before, which is what the existing tests of the fallback count.
+    odd_sides (acts only with any_size): the 7x7 stems at sides the stem kernel refuses run on the padded space-to-depth image and the pitched tail, and the
+    partial layers at odd map widths on p3d_fx_conv_fwd_infer_masked_any, so a partial network folds completely at 257 as it does at 256."""
+    return FoldedNet(getattr(model, 'module', model), any_size=any_size, odd_sides=odd_sides)
 
 
 # ---- -half_acc: BatchNorm folded into the fp16 convolutions ------------------------------------------------------------------------------

@@ -313,6 +313,16 @@ int32_t p3d_fx_conv_fwd_infer_any(const p3d_conv_desc* d, const float* x, const 
 int32_t p3d_fx_conv_fwd_infer_masked_supported(const p3d_conv_desc* d);
 int32_t p3d_fx_conv_fwd_infer_masked(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* mask_in,
                                      const float* mult, const float* res, int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* The partial convolution at ANY map width: p3d_fx_conv_fwd_infer_masked on the ragged instances (PRO 4: mask_in fetched element by element at the positions of x, from
+ * its one plane per image; mult applied per element in the store, each element with its own image; split-K: the scalar slab pass applies mult before b').  Same
+ * arguments and the same order factor, b', res, ReLU, so an empty window gives exactly relu(b' + res).  Only the BASE pointers need 16-B alignment.
+ * supported: p3d_fx_conv_fwd_infer_masked_supported without its W % 4 == 0 and Wo % 4 == 0 (C % 16 == 0, C >= 32, K >= 64, odd square filter, stride <= 2, no channel
+ * window, accumulate 0; 0 under P3D_FX_MASKED=0 and for a NULL d); host only.  Workspace: p3d_fx_conv_fwd_infer_masked_any_workspace_bytes (the weight image's room,
+ * then the split-K slabs, each on a 16-B line). */
+int32_t p3d_fx_conv_fwd_infer_masked_any_supported(const p3d_conv_desc* d);
+size_t p3d_fx_conv_fwd_infer_masked_any_workspace_bytes(const p3d_conv_desc* d);
+int32_t p3d_fx_conv_fwd_infer_masked_any(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* mask_in,
+                                         const float* mult, const float* res, int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream);
 /* Stem tail at inference behind p3d_stem_fwd on a folded stem image: y = maxpool3x3s2(relu(c + bias[channel])) = relu(maxpool(c) + bias) (both monotone per
  * channel), no argmax output.  c [N][C][H][W] (H, W even), y [N][C][H/2][W/2]. */
 int32_t p3d_stem_tail_infer(const float* c, const float* bias, float* y, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
@@ -334,6 +344,23 @@ int32_t p3d_stem_wgrad(const float* dy, const void* x_img, float* dw, int32_t N,
 int32_t p3d_stem_masked_supported(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t K);
 int32_t p3d_stem_image_masked(const float* x, const float* mask_in, void* img, int32_t N, int32_t Cin, int32_t H, int32_t W, void* stream);
 int32_t p3d_stem_fwd_masked(const void* x_img, const void* wimg, float* y, const float* mult, int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t K, void* stream);
+/* The folded stem at ANY sides H, W >= 8 (inference; the reference's default -side_in 257).  A 7x7 / stride 2 / pad 3 conv of the input zero-extended to (Hp, Wp) >=
+ * (H, W) equals, in its first (H - 1) / 2 + 1 rows and (W - 1) / 2 + 1 columns, the conv of the input itself: the added zeros are the conv's own padding.  So:
+ *   p3d_stem_any_padded(H, W, &Hp, &Wp)   the smallest Wp >= W with Wp % 8 == 0, then the smallest even Hp >= H with (Hp / 2) (Wp / 2) % 16 == 0 (a supported pair maps
+ *                                         to itself: 257 -> 264, 129 -> 136, 33 -> 40); returns 0 for a side below 8.  p3d_stem_any_supported: the padded pair passes
+ *                                         p3d_stem_supported.  Both host only.  Every size query (p3d_stem_image_bytes, ...) takes the PADDED sides.
+ *   p3d_stem_image_any(x, mask_in | NULL, img, N, Cin, H, W)   the space-to-depth image of the padded input (layout of p3d_stem_image at (Hp, Wp)); x and mask_in
+ *                                         [N][1][H][W] are fetched as dwords checked against the true H and W, every pixel at or beyond them is an exact zero.
+ *   p3d_stem_fwd(img, wimg, c, N, Cin, Hp, Wp, K)              the conv itself, called with the PADDED sides and never with the output factor: c [N][K][Hp/2][Wp/2]
+ *                                         (p3d_conv_path_stats counts one x3 forward with the flops of the padded conv: +4.7 % at 257).
+ *   p3d_stem_tail_infer_any(c, bias, mult | NULL, y, N, C, H, W)   y [N][C][Ho2][Wo2] = relu(maxpool3x3s2p1(c * mult) + bias), Ho = (H - 1) / 2 + 1, Ho2 = (Ho - 1) / 2 + 1
+ *                                         (H, W: the TRUE input sides; c is read at the pitch Hp/2 x Wp/2, only rows < Ho and columns < Wo enter a window -- the pad
+ *                                         columns hold real, non-zero conv outputs).  mult [N][1][Ho][Wo] dense (ops.mask_count) is multiplied in BEFORE the max: it
+ *                                         stands for the epilogue factor of p3d_stem_fwd_masked.  c 16-B aligned; y is stored as dwords. */
+int32_t p3d_stem_any_padded(int32_t H, int32_t W, int32_t* Hp, int32_t* Wp);
+int32_t p3d_stem_any_supported(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t K);
+int32_t p3d_stem_image_any(const float* x, const float* mask_in, void* img, int32_t N, int32_t Cin, int32_t H, int32_t W, void* stream);
+int32_t p3d_stem_tail_infer_any(const float* c, const float* bias, const float* mult, float* y, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
 int32_t p3d_stem_wgrad_masked(const float* dy, const float* mult, const void* x_img, float* dw, int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t K, int32_t accumulate,
                               void* workspace, size_t workspace_bytes, void* stream);
 

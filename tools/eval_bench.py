@@ -6,6 +6,9 @@ Legs, timed in the same process, alternating (device-synchronised, 10 warm-up + 
   folded    infer.fold(model): BatchNorm folded into the x3 convolutions (p3d_fx_conv_fwd_infer)
 --any-size adds, for a --side whose maps are not multiples of 4 wide (the reference's default 257):
   folded_any    infer.fold(model, any_size=True): the layers `folded` leaves on the per-layer fallback run on p3d_fx_conv_fwd_infer_any
+--odd-sides adds, at such a --side:
+  folded_odd    infer.fold(model, any_size=True, odd_sides=True): the 7x7 stems on the padded space-to-depth image (p3d_stem_image_any, p3d_stem_tail_infer_any) and
+                the partial layers on p3d_fx_conv_fwd_infer_masked_any as well (what Trainer._fold builds)
 --family partial_depthnet / partial_fusionnet times those networks (depth ~ U[0, 1) with values < 0.3 zeroed; partial_depthnet: -depth_only).
 --half replaces them with the -half_acc legs:
   half          today's fp16 eval forward: fp16 conv, then a stand-alone eval-mode BatchNorm (+ res + ReLU) pass per layer
@@ -43,6 +46,7 @@ ap.add_argument('--warmup', type=int, default=10)
 ap.add_argument('--iters', type=int, default=50)
 ap.add_argument('--rounds', type=int, default=3)
 ap.add_argument('--any-size', action='store_true', help='add the folded_any leg: infer.fold(model, any_size=True)')
+ap.add_argument('--odd-sides', action='store_true', help='add the folded_odd leg: infer.fold(model, any_size=True, odd_sides=True)')
 ap.add_argument('--separate', action='store_true')
 ap.add_argument('--distill', action='store_true')
 ap.add_argument('--half', action='store_true', help='-half_acc legs: half / half_folded')
@@ -155,6 +159,9 @@ else:
     if opt.any_size:
         folded_any = pkg.infer.fold(model, any_size=True)
         legs['folded_any'] = lambda: folded_any(*inputs)
+    if opt.odd_sides:
+        folded_odd = pkg.infer.fold(model, any_size=True, odd_sides=True)
+        legs['folded_odd'] = lambda: folded_odd(*inputs)
 if opt.separate:
     legs['separate'] = lambda: model(*inputs)
 if opt.only:
