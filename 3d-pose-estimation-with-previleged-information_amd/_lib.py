@@ -47,8 +47,6 @@ SIGNATURES = {
     'p3d_conv2d_bgrad': (_i32, [_ptr, _i32, _i32, _i32, _ptr, _i32, _ptr]),
     'p3d_conv2d_bgrad_masked': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _ptr, _i32, _ptr]),
     'p3d_block_supported': (_i32, [_ptr]),
-    'p3d_block_tail_supported': (_i32, [_ptr]),
-    'p3d_block_tail_partial_bytes': (ctypes.c_size_t, [_ptr]),
     'p3d_block_workspace_bytes': (_i32, [_ptr, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
     'p3d_block_fwd': (_i32, [_ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_block_bwd': (_i32, [_ptr, _ptr, _ptr, _sz, _ptr, _sz, _ptr, _ptr]),

@@ -502,24 +502,12 @@ int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
     return check_launch("block_fwd");
 }
 
-// Can this block's backward pass reduce its producer's opening sums (p3d_block_io.tail_*)?  The last writer of dx must be a dense stride-1 launch whose epilogue
-// sees the final value: conv 0's data gradient with an identity shortcut (dx = dgrad + g), the downsample conv's (dx += dgrad) otherwise.
-int32_t p3d_block_tail_supported(const p3d_block_desc* b) {
-    if (check_block(b) || b->masked) return 0;
-    if (b->has_downsample) return b->conv[3].stride == 1 && fx_dgrad_tail_applies(&b->conv[3]) ? 1 : 0;
-    return fx_dgrad_tail_applies(&b->conv[0]) && fx_dgrad_accumulates_from_source(&b->conv[0]) ? 1 : 0;
-}
-size_t p3d_block_tail_partial_bytes(const p3d_block_desc* b) {
-    if (!p3d_block_tail_supported(b)) return 0;
-    const p3d_conv_desc* d = &b->conv[b->has_downsample ? 3 : 0];
-    return (size_t)fx_dgrad_tail_rows(d) * d->C * 4 * sizeof(float);
-}
-
 // dout -> dx (+ every parameter gradient, accumulated into io->dw / dgamma / dbeta when b->accumulate_grads, else written).
 // side_stream may be null (everything on `stream`); otherwise the weight-gradient kernels run there, ordered by events behind the kernels that produce
 // their operands; the caller joins the two streams before it reads the gradients.
 int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* workspace, size_t workspace_bytes, void* side_workspace, size_t side_bytes,
                       void* stream, void* side_stream) {
+    static_assert(sizeof(p3d_block_io) == 592, "74 pointers (ops_block.BlockIO mirrors the struct)");
     if (int32_t e = check_block(b)) return e;
     P3D_REQUIRE(io && io->x && io->out && io->dout, "block_bwd: null tensor");
     // g = dout * [out > 0] never exists as a tensor when forward left mask bytes: the two opening image passes mask dout themselves, and with an identity
@@ -547,28 +535,17 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
     const p3d_conv_desc* dl = &b->conv[last];
     const int acc = b->accumulate_grads;
 
-    // 1. open: g = dout * [out > 0]; channel sums of the closing BN (and of the downsample BN) -- unless the block that consumed `out` left them already: the data
-    //    gradient that wrote dout reduced them in its epilogue (io->open_sums = that call's io->tail_sums), and this pass over dout and c is not needed at all
-    const bool sums_given = io->open_sums != nullptr && !g_in_memory;
-    const int split = sums_given ? P3D_TAIL_ROWS : close_split(dl->N, dl->K);
-    const void* open_partial = sums_given ? (const void*)io->open_sums : (const void*)partial;
+    // 1. open: g = dout * [out > 0]; channel sums of the closing BN (and of the downsample BN)
+    const int split = close_split(dl->N, dl->K);
     const float* g = (b->relu_out && g_in_memory) ? io->gbuf : io->dout;
     const unsigned char* gmask = g_in_memory ? nullptr : io->out_mask;
-    if (!sums_given)
-        hipLaunchKernelGGL(block_open_bwd_kernel, dim3(dl->K, split), dim3(256), 0, st, io->dout, (const float*)io->out, (const float*)io->c[last],
-                           (const float*)io->table[last], b->has_downsample ? (const float*)io->c[3] : (const float*)nullptr,
-                           b->has_downsample ? (const float*)io->table[3] : (const float*)nullptr, g_in_memory ? io->gbuf : (float*)nullptr, (double*)partial,
-                           (const unsigned char*)io->out_mask, dl->N, dl->K,
-                           dl->Ho * dl->Wo, b->relu_out);
+    hipLaunchKernelGGL(block_open_bwd_kernel, dim3(dl->K, split), dim3(256), 0, st, io->dout, (const float*)io->out, (const float*)io->c[last],
+                       (const float*)io->table[last], b->has_downsample ? (const float*)io->c[3] : (const float*)nullptr,
+                       b->has_downsample ? (const float*)io->table[3] : (const float*)nullptr, g_in_memory ? io->gbuf : (float*)nullptr, (double*)partial,
+                       (const unsigned char*)io->out_mask, dl->N, dl->K,
+                       dl->Ho * dl->Wo, b->relu_out);
     const double cnt_last = (double)dl->N * dl->Ho * dl->Wo;
     if (int32_t e = check_launch("block_bwd open")) return e;
-    // this block as a consumer: may the last writer of dx reduce the producer's opening sums?
-    const bool tail = b->need_dx && io->tail_c_last && io->tail_table_last && io->tail_partial && io->tail_sums && (!io->tail_c_ds || io->tail_table_ds) &&
-                      p3d_block_tail_supported(b);
-    auto set_tail = [&](FxFuse& f) {
-        f.tail_c = io->tail_c_last; f.tail_tab = io->tail_table_last; f.tail_rc = io->tail_c_ds; f.tail_rtab = io->tail_table_ds; f.tail_mask = io->tail_mask;
-        f.tail_partial = io->tail_partial;
-    };
 
     // 2. The gradient that enters conv i is the upstream gradient taken through BN i's backward map (masked by its ReLU, except the closing BN whose ReLU went
     //    into g already): d c_i = A g + B c_i + K, written ONCE, as the image both the weight gradient and the data gradient of conv i copy into LDS.  The
@@ -579,13 +556,12 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
     // partial convolutions: the gradient image of conv `slot` carries its renormalisation factor (d raw = d c * mult: partial_conv.py:53 and its autograd)
     for (int i = 0; b->masked && i < b->nconv; ++i) P3D_REQUIRE(io->pix_in[i] && io->pix_out[i], "block_bwd: null per-pixel factor of partial convolution %d", i);
     auto pixmul = [&](int slot) -> const float* { return (b->masked && slot != 3) ? io->pix_out[slot] : nullptr; };
-    auto bwd_map = [&](const float* gin, int slot, int masked, int kind, int rows, int which, double cnt, const unsigned char* front_mask = nullptr,
-                       const void* part = nullptr) -> int32_t {
+    auto bwd_map = [&](const float* gin, int slot, int masked, int kind, int rows, int which, double cnt, const unsigned char* front_mask = nullptr) -> int32_t {
         const p3d_conv_desc* dc = &b->conv[slot];
         P3D_REQUIRE(io->dcimg[slot], "block_bwd: null gradient image %d", slot);
         if (kind == 3 || rows <= FX_FIN_MAX_ROWS) {
             FxFinalize fin{};
-            fin.kind = kind; fin.partial = part ? part : partial; fin.rows = rows; fin.which = which; fin.count = cnt; fin.gamma = io->gamma[slot];
+            fin.kind = kind; fin.partial = partial; fin.rows = rows; fin.which = which; fin.count = cnt; fin.gamma = io->gamma[slot];
             fin.dgamma = io->dgamma[slot]; fin.dbeta = io->dbeta[slot]; fin.accumulate = acc; fin.table = io->table[slot];
             fin.gmask = front_mask;
             return fx_act_image(2, gin, io->c[slot], io->table[slot], masked, io->dcimg[slot], dc->N, dc->K, dc->Ho * dc->Wo, st, &fin, pixmul(slot));
@@ -615,14 +591,14 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
         // both images in one pass: g (dout and the mask bytes) is read once
         P3D_REQUIRE(io->dcimg[last] && io->dcimg[3], "block_bwd: null gradient image");
         FxFinalize fa{}, fb{};
-        fa.kind = 3; fa.partial = open_partial; fa.rows = split; fa.which = 0; fa.count = cnt_last; fa.gamma = io->gamma[last]; fa.dgamma = io->dgamma[last];
+        fa.kind = 3; fa.partial = partial; fa.rows = split; fa.which = 0; fa.count = cnt_last; fa.gamma = io->gamma[last]; fa.dgamma = io->dgamma[last];
         fa.dbeta = io->dbeta[last]; fa.accumulate = acc; fa.table = io->table[last];
         fb = fa; fb.which = 1; fb.gamma = io->gamma[3]; fb.dgamma = io->dgamma[3]; fb.dbeta = io->dbeta[3]; fb.table = io->table[3];
         if (int32_t e = fx_act_image_pair(g, gmask, io->c[last], io->c[3], io->dcimg[last], io->dcimg[3], &fa, &fb, dl->N, dl->K, dl->Ho * dl->Wo, st, pixmul(last))) return e;
     } else {
-        if (int32_t e = bwd_map(g, last, 0, 3, split, 0, cnt_last, gmask, open_partial)) return e;
+        if (int32_t e = bwd_map(g, last, 0, 3, split, 0, cnt_last, gmask)) return e;
         if (b->has_downsample)
-            if (int32_t e = bwd_map(g, 3, 0, 3, split, 1, cnt_last, gmask, open_partial)) return e;
+            if (int32_t e = bwd_map(g, 3, 0, 3, split, 1, cnt_last, gmask)) return e;
     }
     hipEvent_t ready = two ? mark_position(st) : nullptr;           // d c_last (and the downsample branch's gradient image) are complete
     const hipEvent_t ready_ds = ready;
@@ -669,15 +645,12 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
                 P3D_REQUIRE(io->gbuf, "block_bwd: null gradient buffer (dx of an identity shortcut)");
                 dx = io->gbuf; dd.accumulate = 1;
                 if (!g_in_memory) { f.acc_src = io->dout; f.acc_mask = io->out_mask; }      // gbuf is written here for the first time
-                if (tail) set_tail(f);                 // this launch writes the final dx: the producer block's opening sums ride in its epilogue
             }
             {
                 ProfScope ps(1, d, st);
                 fx_count(1, d);
                 if (int32_t e = fx_conv_dgrad(&dd, nullptr, io->w[0], dx, workspace, conv_ws, &f, st)) return e;
             }
-            if (tail && !b->has_downsample)
-                if (int32_t e = fx_tail_fold(io->tail_partial, fx_dgrad_tail_rows(d), d->C, io->tail_sums, P3D_TAIL_ROWS, st)) return e;
             }
             if (int32_t e = launch_wgrad(0, io->x, nullptr, d->R * d->S > 1, ready)) return e;
         }
@@ -691,14 +664,11 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
             f.act_img = io->dcimg[3];
             p3d_conv_desc dd = *d;
             dd.accumulate = 1;
-            if (tail) set_tail(f);                     // dx += dgrad: the final value of dx leaves this launch
             {
                 ProfScope ps(1, d, st);
                 fx_count(1, d);
                 if (int32_t e = fx_conv_dgrad(&dd, nullptr, io->w[3], io->dx, workspace, conv_ws, &f, st)) return e;
             }
-            if (tail)
-                if (int32_t e = fx_tail_fold(io->tail_partial, fx_dgrad_tail_rows(d), d->C, io->tail_sums, P3D_TAIL_ROWS, st)) return e;
         }
         if (int32_t e = launch_wgrad(3, io->x, nullptr, false, ready_ds)) return e;
     }

@@ -27,9 +27,6 @@ struct FxConvParams {
     const unsigned char* acc_mask;   //   masking by these bytes when given (bit e of byte i: element 4 i + e passes): Y = result + src * mask, Y itself is only written
     const float* ep_res;    // EPIX 8 (inference: conv + folded BatchNorm): residual added after bias and accumulation, laid out like Y, or null
     int ep_relu;            // EPIX 8: ReLU last
-    // EPI 3 (dense unsplit data gradient that writes a block's dx last): per (pixel tile, channel) partial sums of g, g (tail_c - mean), g (tail_rc - rmean) with
-    // g = Y * [tail_mask bit], Y the final value (after accumulation): the opening sums of the backward pass of the block that produced this block's input
-    const float* tail_c; const float* tail_tab; const float* tail_rc; const float* tail_rtab; const unsigned char* tail_mask; float* tail_partial;   // [tiles_n][M][4]
     size_t slab_stride;     // elements between two split-K slabs
     int N, Cred, Hi, Wi;
     int M, OH, OW, NP;      // the GEMM's pixel grid (for strided dgrad: one parity class of the input) and its size N * OH * OW
@@ -76,8 +73,6 @@ struct FxFuse {
     const void* wimg;       // FWD / DGRAD: pre-split weight image of this conv for this direction (fx_build_weight_images), or null: built into the workspace by the call
     const float* acc_src;   // DGRAD with d->accumulate, stride 1, unsplit (fx_dgrad_accumulates_from_source): dx = dgrad + acc_src * [acc_mask bit] instead of dx += dgrad
     const unsigned char* acc_mask;
-    // DGRAD (fx_dgrad_tail_applies): also reduce the opening sums of the producer block's backward pass over the final dx (FxConvParams::tail_*)
-    const float* tail_c; const float* tail_tab; const float* tail_rc; const float* tail_rtab; const unsigned char* tail_mask; float* tail_partial;
     // FWD, inference (a conv with its eval-mode BatchNorm folded into the weight image and the bias): y = conv + bias (+ y when accumulating) (+ res) (then ReLU), on
     // the split-K path applied by the reduce pass after the slabs are summed
     int infer;              // 1; 2: on the ragged instances (any map width; fp32 operand, dense; a partial convolution with pmask and emask)
@@ -93,7 +88,7 @@ enum : int {
     FX_EPI_STORE = 0,
     FX_EPI_STATS = 1,               // sums 1: per-(pixel tile, channel) partial sums of y, y^2 (the BatchNorm behind the conv)
     FX_EPI_BWD_SUMS = 2,            // sums 2: of g, g * (c2 - mean), g = y * [c2 * sc + sh > 0] (the BatchNorm + ReLU in front of the conv whose input gradient this is; ep_c = c2, ep_tab its table)
-    FX_EPI_TAIL_SUMS = 3,           // sums 3: the opening sums of the producer block's backward pass (FxConvParams::tail_*), on the data gradient that writes a block's dx last
+                                    // (3 is unused: it was the tail-sums epilogue, measured slower and removed; profiles/r04_summary.md §3.  The other codes keep their values)
     FX_EPI_FACTOR = 4,              // factor: the result times emask[pixel], in the register view; the per-layer partial convolution (fp32-fed, PRO 4)
     FX_EPI_FACTOR_STATS = 5, FX_EPI_FACTOR_BWD_SUMS = 6, FX_EPI_FACTOR_IMG = 7,     // factor with sums 1 / sums 2 / image-fed: partial convolutions inside the residual-block
                                     // executor, the sums taken of the renormalised result.  (fx16_conv_kernel reads the factor pointer at run time: fx16_epi)
@@ -101,7 +96,7 @@ enum : int {
     FX_EPI_INFER_FACTOR = 9,        // the same of a partial convolution: acc * emask[pixel] + b' (+ ep_res) (ReLU), the factor BEFORE the folded shift and in the staged store (an
                                     // empty window, emask = 0, gives relu(b' + res): the reference's partial conv writes 0 there and the BatchNorm behind it maps 0 to b')
 };
-constexpr int fx_epi_sums(int epi) { return epi == FX_EPI_STATS || epi == FX_EPI_FACTOR_STATS ? 1 : epi == FX_EPI_BWD_SUMS || epi == FX_EPI_FACTOR_BWD_SUMS ? 2 : epi == FX_EPI_TAIL_SUMS ? 3 : 0; }
+constexpr int fx_epi_sums(int epi) { return epi == FX_EPI_STATS || epi == FX_EPI_FACTOR_STATS ? 1 : epi == FX_EPI_BWD_SUMS || epi == FX_EPI_FACTOR_BWD_SUMS ? 2 : 0; }
 constexpr bool fx_epi_factor(int epi) { return epi >= FX_EPI_FACTOR && epi <= FX_EPI_FACTOR_IMG; }
 constexpr bool fx_epi_infer(int epi) { return epi == FX_EPI_INFER || epi == FX_EPI_INFER_FACTOR; }
 
@@ -128,9 +123,6 @@ bool fx_dgrad_applies(const p3d_conv_desc* d, int min_m = 96);
 bool fx_wgrad_applies(const p3d_conv_desc* d, int min_m = 96);
 bool fx_dgrad_has_dead_classes(const p3d_conv_desc* d);
 bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d);      // stride 1 and no split-K: FxFuse::acc_src is honoured
-bool fx_dgrad_tail_applies(const p3d_conv_desc* d);                 // the image-fed data gradient of d takes FxFuse::tail_* (dense, unsplit, 128-row channel tiles)
-int fx_dgrad_tail_rows(const p3d_conv_desc* d);                     // rows of tail_partial [rows][C][4]
-int32_t fx_tail_fold(const float* partial, int rows, int C, double* sums, int out_rows, hipStream_t st);      // -> sums [C][out_rows][3]
 bool fx_fwd_masked_applies(const p3d_conv_desc* d);          // partial convolutions: the masked instances exist for unsplit launches without bias
 bool fx_fwd_masked_any_applies(const p3d_conv_desc* d);      // the same at any map width (the ragged PRO-4 instances, inference only)
 bool fx_dgrad_masked_applies(const p3d_conv_desc* d);

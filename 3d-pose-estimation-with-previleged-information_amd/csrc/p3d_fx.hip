@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     const bool split = p.kchunk > 0;
     float* yout = p.Y + (split ? (size_t)blockIdx.y * p.slab_stride : 0);
     const bool dense = split || (p.oxs == 1 && p.oys == 1 && p.oy0 == 0 && p.ox0 == 0 && p.YW == p.OW && p.YH == p.OH);
-    float ssum[2] = {0.f, 0.f}, ssq[2] = {0.f, 0.f}, sthird[2] = {0.f, 0.f};
+    float ssum[2] = {0.f, 0.f}, ssq[2] = {0.f, 0.f};
     float esc[2] = {0.f, 0.f}, esh[2] = {0.f, 0.f}, emean[2] = {0.f, 0.f};
     if constexpr (SUMS == 2) {
 #pragma unroll
@@ -423,63 +423,10 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
             if (m < p.M) { esc[b] = p.ep_tab[8 * m]; esh[b] = p.ep_tab[8 * m + 1]; emean[b] = p.ep_tab[8 * m + 2]; }
         }
     }
-    if constexpr (SUMS == 3) {             // emean: the mean of the producer's closing BatchNorm; esc: that of its downsample BatchNorm
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int m = m0 + wm * 64 + b * 32 + fr;
-            if (m < p.M) { emean[b] = p.tail_tab[8 * m + 2]; esc[b] = p.tail_rc ? p.tail_rtab[8 * m + 2] : 0.f; }
-        }
-    }
-    if constexpr (SUMS == 3) {
-        // The launch that writes a block's dx last (dense, unsplit, accumulating): the summand joins HERE, in the register view, so that v is the final gradient,
-        // and the opening sums of the producer block's backward pass (g = v [producer's out > 0]; its closing and its downsample BatchNorm) are per-lane adds like
-        // SUMS 2's.  Straight-line code: out-of-range lanes read element 0 and contribute nothing, optional operands are pointer selects, so no branch separates the
-        // loads and the compiler keeps several iterations' worth in flight (one memory round trip per iteration otherwise, which cost more than the pass saved).
-        const float* src = p.acc_src ? p.acc_src : yout;                       // what is added to the result
-        const unsigned char* amask = p.acc_mask ? p.acc_mask : p.tail_mask;    // (tail_mask: any readable bytes; forced to "all pass" below)
-        const unsigned aforce = p.acc_mask ? 0u : 0xFu;
-        const float* rcp = p.tail_rc ? p.tail_rc : p.tail_c;                   // no downsample BatchNorm: the third sum is computed on the same lines and ignored
-        int dep = 0;
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c4 = n0 + wn * 64 + a * 32 + 8 * g + 4 * fh;
-                const int cc = (c4 < p.NP ? c4 : 0) + dep;          // (the whole index computation of a batch hangs on `dep`: it is not hoisted either)
-                const int n = cc / OHW, rem = cc - n * OHW;
-                const unsigned pix = (unsigned)n * (unsigned)p.M * (unsigned)OHW + (unsigned)rem;       // (fx_common: the tensor has fewer than 2^31 elements)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const int m = m0 + wm * 64 + b * 32 + fr;
-                    const bool ok = c4 < p.NP && m < p.M;
-                    const unsigned at = ok ? pix + (unsigned)m * (unsigned)OHW : 0u;
-                    const f32x4 o4 = *reinterpret_cast<const f32x4*>(src + at);
-                    const unsigned am = amask[at >> 2] | aforce;
-                    const unsigned mk = p.tail_mask[at >> 2];
-                    const f32x4 cl = *reinterpret_cast<const f32x4*>(p.tail_c + at);
-                    const f32x4 rc = *reinterpret_cast<const f32x4*>(rcp + at);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = acc[a][b][4 * g + e] + ((am >> e) & 1u ? o4[e] : 0.f);
-                        acc[a][b][4 * g + e] = v;
-                        const float gg = (ok && ((mk >> e) & 1u)) ? v : 0.f;
-                        ssum[b] += gg;
-                        ssq[b] = fmaf(gg, cl[e] - emean[b], ssq[b]);
-                        sthird[b] = fmaf(gg, rc[e] - esc[b], sthird[b]);
-                    }
-                }
-                // A batch = the two channel sub-tiles of one pixel group.  Left to itself the compiler hoists all sixteen iterations' loads (200 registers beside the
-                // 64 of the accumulator) and spills them straight to scratch; neither a scheduling barrier nor a memory clobber holds loads it has proven unclobbered.
-                // So the next batch's addresses are made to depend on this batch's sums: `dep` stays 0, which the compiler cannot know.
-                // (ALL the sums: with only the first pair the scheduler rushes that chain ahead and parks the operands of the other two in scratch)
-                if (g & 1) asm volatile("" : "+v"(dep) : "v"(ssum[0]), "v"(ssum[1]), "v"(ssq[0]), "v"(ssq[1]), "v"(sthird[0]), "v"(sthird[1]));
-            }
-    }
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            if constexpr (SUMS == 3) continue;
             const int c4 = n0 + wn * 64 + a * 32 + 8 * g + 4 * fh;         // first of this lane's 4 consecutive pixels
             if (c4 >= p.NP) continue;
             const int n = c4 / OHW, rem = c4 - n * OHW, oh = rem / p.OW, ow = rem - oh * p.OW;
@@ -539,7 +486,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     if (dense) {
         // (every wave left the K loop through its last barrier: the operand buffers are free)
         constexpr int EROW = 512 + 16;               // bytes per staged channel row: 128 pixels + one 16-B pad (staging stores of 8 consecutive rows hit 32 different banks)
-        const bool accum = SUMS != 3 && !split && p.accumulate;      // (SUMS 3 has added its summand in the register view above: its sums need the final value)
+        const bool accum = !split && p.accumulate;
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             if (b == 1) __syncthreads();             // round 0's rows have been read
@@ -627,21 +574,6 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                 dst[1] = red[0][1][t] + red[1][1][t];
             }
         }
-    }
-    if constexpr (SUMS == 3) {
-        // three sums per channel: [wave along pixels][kind][channel] behind the staged tile (3 KB at byte 40960 of the 48 KB array)
-        float (*const red3)[3][128] = reinterpret_cast<float (*)[3][128]>(lds + 40960);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            ssum[b] += __shfl_xor(ssum[b], 32, 64);
-            ssq[b] += __shfl_xor(ssq[b], 32, 64);
-            sthird[b] += __shfl_xor(sthird[b], 32, 64);
-            if (fh == 0) { const int ch = wm * 64 + b * 32 + fr; red3[wn][0][ch] = ssum[b]; red3[wn][1][ch] = ssq[b]; red3[wn][2][ch] = sthird[b]; }
-        }
-        __syncthreads();
-        if (t < 128 && m0 + t < p.M)
-            *reinterpret_cast<f32x4*>(p.tail_partial + ((size_t)tile_n * p.M + m0 + t) * 4) =
-                f32x4{red3[0][0][t] + red3[1][0][t], red3[0][1][t] + red3[1][1][t], red3[0][2][t] + red3[1][2][t], 0.f};
     }
 }
 
@@ -1707,9 +1639,9 @@ static int g_class_launches = 0;      // 1: one launch per parity class of a str
 // form is 1-3 % SLOWER on the large layers (20 fragment reads per step against 12, and the chip holds no higher clock on it in these kernels: profiles/r04_summary.md
 // section 1), so those stay on the 32x32x16 kernel.
 // The instance a code runs on there: the kernel applies p.emask at run time, so a factor code is the instance without the factor, with the pointer set; -1: none (the
-// tail sums and the two fp32-fed partial-convolution codes).  Image-fed launches only.
+// two fp32-fed partial-convolution codes).  Image-fed launches only.
 constexpr int fx16_epi(int epi) {
-    if (fx_epi_sums(epi) == 3 || epi == FX_EPI_FACTOR || epi == FX_EPI_INFER_FACTOR) return -1;
+    if (epi == FX_EPI_FACTOR || epi == FX_EPI_INFER_FACTOR) return -1;
     return fx_epi_infer(epi) ? FX_EPI_INFER : fx_epi_sums(epi) == 1 ? FX_EPI_STATS : fx_epi_sums(epi) == 2 ? FX_EPI_BWD_SUMS : FX_EPI_STORE;
 }
 static int fx16_bm(int M, bool img, int pro, int epi) {
@@ -1721,9 +1653,8 @@ static int fx16_bm(int M, bool img, int pro, int epi) {
 // What a call asks for -> the prologue and epilogue of its (unsplit) launch.  PRO 4: an fp32 operand of a partial convolution is multiplied by pmask in the kernel; an
 // image carries its factor already.
 struct FxSelect { int pro, epi; };
-constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool infer, bool tail) {
+constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool infer) {
     const int pro = masked && !img ? 4 : 0;
-    if (tail) return {pro, FX_EPI_TAIL_SUMS};
     if (infer) return {pro, masked ? FX_EPI_INFER_FACTOR : FX_EPI_INFER};
     if (masked) return {pro, sums ? (dgrad ? FX_EPI_FACTOR_BWD_SUMS : FX_EPI_FACTOR_STATS) : (img ? FX_EPI_FACTOR_IMG : FX_EPI_FACTOR)};
     return {pro, sums ? (dgrad ? FX_EPI_BWD_SUMS : FX_EPI_STATS) : FX_EPI_STORE};
@@ -1734,7 +1665,7 @@ constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool 
 #define P3D_FX_CONV_INSTANCES(X)                                                                                                                              \
     X(0, 0, FX_EPI_STORE, false, false) X(0, 0, FX_EPI_STATS, false, false) X(0, 0, FX_EPI_BWD_SUMS, false, false) X(0, 0, FX_EPI_INFER, false, false)        \
     X(0, 4, FX_EPI_STORE, false, false) X(0, 4, FX_EPI_FACTOR, false, false) X(0, 4, FX_EPI_FACTOR_STATS, false, false) X(0, 4, FX_EPI_INFER_FACTOR, false, false) \
-    X(1, 0, FX_EPI_STORE, false, false) X(1, 0, FX_EPI_STATS, false, false) X(1, 0, FX_EPI_BWD_SUMS, false, false) X(1, 0, FX_EPI_TAIL_SUMS, false, false)    \
+    X(1, 0, FX_EPI_STORE, false, false) X(1, 0, FX_EPI_STATS, false, false) X(1, 0, FX_EPI_BWD_SUMS, false, false)                                           \
     X(1, 0, FX_EPI_FACTOR_STATS, false, false) X(1, 0, FX_EPI_FACTOR_BWD_SUMS, false, false) X(1, 0, FX_EPI_FACTOR_IMG, false, false) X(1, 0, FX_EPI_INFER, false, false) \
     X(1, 0, FX_EPI_STORE, true, false) X(1, 0, FX_EPI_STATS, true, false) X(1, 0, FX_EPI_BWD_SUMS, true, false) X(0, 0, FX_EPI_STORE, false, true) X(0, 0, FX_EPI_INFER, false, true) \
     X(0, 4, FX_EPI_INFER_FACTOR, false, true) X(0, 4, FX_EPI_STORE, false, true)
@@ -1757,10 +1688,10 @@ constexpr FxKernel fx_instance(int bm, bool img, int pro, int epi, bool tapi, bo
 }
 // everything fx_select can return for arguments that fx_conv_fwd / fx_conv_dgrad admit has its instances: on each tile the code can get, and for its split-K slabs
 constexpr bool fx_select_covered() {
-    for (int c = 0; c < 64; ++c) {
-        const bool dgrad = c & 1, img = c & 2, masked = c & 4, sums = c & 8, infer = c & 16, tail = c & 32;
-        if (dgrad ? (infer || (masked && !img && sums) || (tail && (!img || masked || sums))) : (tail || (infer && (sums || (masked && img))))) continue;
-        const FxSelect s = fx_select(dgrad, img, masked, sums, infer, tail);
+    for (int c = 0; c < 32; ++c) {
+        const bool dgrad = c & 1, img = c & 2, masked = c & 4, sums = c & 8, infer = c & 16;
+        if (dgrad ? (infer || (masked && !img && sums)) : (infer && (sums || (masked && img)))) continue;
+        const FxSelect s = fx_select(dgrad, img, masked, sums, infer);
         if (!fx_instance(0, img, s.pro, s.epi, false, false) || !fx_instance(0, img, s.pro, FX_EPI_STORE, false, false)) return false;
         if (img && s.pro == 0 && fx16_epi(s.epi) >= 0 && !(fx_instance(96, img, 0, s.epi, false, false) && fx_instance(64, img, 0, s.epi, false, false))) return false;
     }
@@ -2064,7 +1995,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
         wimg = ws;
     }
     p.Wimg = (const unsigned char*)wimg;
-    const FxSelect sel = fx_select(false, img, masked, fuse && fuse->partial, infer, false);
+    const FxSelect sel = fx_select(false, img, masked, fuse && fuse->partial, infer);
     if (fuse) { p.partial = fuse->partial; p.pmask = fuse->pmask; p.emask = fuse->emask; p.ep_res = fuse->res; p.ep_relu = fuse->relu; }      // (res / relu: inference only, above)
     const bool split = pl.splits > 1;
     const int bm = rag ? 0 : fx16_bm(d->K, img, split ? 0 : sel.pro, split ? FX_EPI_STORE : sel.epi);
@@ -2107,18 +2038,12 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
         wimg = ws;
     }
     p.Wimg = (const unsigned char*)wimg;
-    const bool sums = fuse && fuse->partial, tail = fuse && fuse->tail_c;
+    const bool sums = fuse && fuse->partial;
     if (sums) { p.partial = fuse->partial; p.ep_c = fuse->ep_c; p.ep_tab = fuse->ep_tab; }
     if (masked) { p.pmask = fuse->pmask; p.emask = fuse->emask; }
     const bool split = pl.splits > 1;
     p.tap_inner = img && RS > 1 && d->K >= FX_TAP_INNER_MIN;
-    if (tail) {
-        if (!(img && !sums && !masked && fx_dgrad_tail_applies(d) && fuse->tail_tab && fuse->tail_partial && (!fuse->tail_rc || fuse->tail_rtab))) {
-            set_error("fx_conv_dgrad: the tail sums need an image-fed, dense, unsplit stride-1 data gradient without a BatchNorm epilogue (fx_dgrad_tail_applies)"); return P3D_EINVAL;
-        }
-        p.tail_c = fuse->tail_c; p.tail_tab = fuse->tail_tab; p.tail_rc = fuse->tail_rc; p.tail_rtab = fuse->tail_rtab; p.tail_mask = fuse->tail_mask; p.tail_partial = fuse->tail_partial;
-    }
-    const auto [pro, epi] = fx_select(true, img, masked, sums, false, tail);
+    const auto [pro, epi] = fx_select(true, img, masked, sums, false);
     const int bm = fx16_bm(d->C, img, split ? 0 : pro, split ? FX_EPI_STORE : epi);
     p.tiles_m = (int)ceil_div(d->C, bm ? bm : FX_BM);
     if (d->stride == 1) {
@@ -2162,29 +2087,6 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
         if (int32_t e = fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1, (unsigned)ncls), st)) return e;
     }
     return check_launch("fx_conv_dgrad");
-}
-
-// The data gradient that writes a block's dx last can also reduce the opening sums of the producer block's backward pass (EPI 3 of fx_conv_kernel): dense rows
-// (stride 1), one launch (no split-K), channel tiles of 128 rows (the fx16 instances have no such epilogue), whole 16-B pixel groups
-bool fx_dgrad_tail_applies(const p3d_conv_desc* d) {
-    return fx_dgrad_applies(d, 96) && fx_dgrad_accumulates_from_source(d) && fx16_bm(d->C, true, 0, FX_EPI_STORE) == 0;
-}
-int fx_dgrad_tail_rows(const p3d_conv_desc* d) { return (int)ceil_div((int64_t)d->N * d->H * d->W, FX_BN); }
-// partial [rows][C][4] (fp32: sum g, sum g (c - mean), sum g (rc - rmean), 0) -> sums [C][out_rows][3] (fp64), row r of the output = rows r, r + out_rows, ... in order
-__global__ __launch_bounds__(64) void fx_tail_fold_kernel(const float* __restrict__ partial, int rows, int C, double* __restrict__ sums, int out_rows) {
-    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y;
-    if (c >= C) return;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int i = r; i < rows; i += out_rows) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(partial + ((size_t)i * C + c) * 4);
-        s0 += v[0]; s1 += v[1]; s2 += v[2];
-    }
-    double* dst = sums + ((size_t)c * out_rows + r) * 3;
-    dst[0] = s0; dst[1] = s1; dst[2] = s2;
-}
-int32_t fx_tail_fold(const float* partial, int rows, int C, double* sums, int out_rows, hipStream_t st) {
-    hipLaunchKernelGGL(fx_tail_fold_kernel, dim3((unsigned)ceil_div(C, 64), (unsigned)out_rows), dim3(64), 0, st, partial, rows, C, sums, out_rows);
-    return check_launch("fx_tail_fold");
 }
 
 // input pixels of a strided 1x1 that no tap reaches: fx_conv_dgrad leaves them untouched, so a caller that does not accumulate zero-fills dx first

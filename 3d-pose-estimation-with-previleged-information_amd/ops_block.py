@@ -21,12 +21,6 @@ _vp = ctypes.c_void_p
 BLOCK_SIDE_STREAM = os.environ.get('P3D_BLOCK_SIDE', '1') != '0'
 # P3D_OUT_MASK=0: the backward pass reads the block's fp32 output for the closing ReLU's mask instead of the mask bytes forward leaves (p3d_block_io.out_mask = NULL)
 USE_OUT_MASK = os.environ.get('P3D_OUT_MASK', '1') != '0'
-# P3D_TAIL_SUMS=1 (opt-in, measured SLOWER: profiles/r04_summary.md section 3): a block takes the channel sums its backward pass opens with from the epilogue of the data
-# gradient that wrote dout (the consumer block's p3d_block_io.tail_*) instead of its own pass over dout (block_open_bwd).  13 of ResNet-50's 16 opening passes go away, but
-# the data gradient's epilogue then waits on uncoalesced reads of c_last / c_ds / the mask bytes: the step is 0.2 - 0.4 ms LONGER.  Kept tested, off by default.
-USE_TAIL_SUMS = os.environ.get('P3D_TAIL_SUMS', '0') == '1'
-TAIL_ROWS = 16                   # P3D_TAIL_ROWS
-TAIL_STATS = {'reduced': 0, 'opening_passes_skipped': 0}     # (tests: how often a consumer reduced its producer's sums / a producer found them valid)
 
 
 class BlockDesc(ctypes.Structure):
@@ -41,8 +35,7 @@ class BlockIO(ctypes.Structure):
     _fields_ = [('x', _vp), ('out', _vp), ('w', _vp * 4), ('wimg', _vp * 4), ('wimgT', _vp * 4), ('c', _vp * 4), ('aimg', _vp * 4), ('table', _vp * 4), ('gamma', _vp * 4), ('beta', _vp * 4),
                 ('running_mean', _vp * 4), ('running_var', _vp * 4), ('dout', _vp), ('gbuf', _vp), ('dcimg', _vp * 4), ('da', _vp * 4), ('dx', _vp), ('dw', _vp * 4),
                 ('dgamma', _vp * 4), ('dbeta', _vp * 4), ('out_mask', _vp),
-                ('tail_c_last', _vp), ('tail_table_last', _vp), ('tail_c_ds', _vp), ('tail_table_ds', _vp), ('tail_mask', _vp), ('tail_partial', _vp), ('tail_sums', _vp),
-                ('open_sums', _vp), ('pix_in', _vp * 4), ('pix_out', _vp * 4)]
+                ('pix_in', _vp * 4), ('pix_out', _vp * 4)]
 
 
 def _one(v):
@@ -91,10 +84,6 @@ class _Plan:
         self.table_rows = sum(ks)
         self.slots = [slot for slot, _, _ in _layers(block)]
         self.sets = []                  # _Buffers owned by this plan (see there)
-        # as a consumer: can this block's backward pass reduce the opening sums of the block that produced its input? (p3d_block_io.tail_*)
-        self.tail_ok = bool(self.ok and lib().p3d_block_tail_supported(ctypes.byref(d)))
-        self.tail_bytes = int(lib().p3d_block_tail_partial_bytes(ctypes.byref(d))) if self.tail_ok else 0
-        self.in_shape = tuple(x_shape)
 
 
 def _free_set(sets, device, make):
@@ -138,8 +127,6 @@ class _Buffers(_BufferSet):
     def __init__(self, plan, device):
         super().__init__(device)
         self.bwd = None
-        self.tail = None                # (partial scratch, sums [C][TAIL_ROWS][3] fp64): where a consumer block leaves this block's opening sums
-        self.open_ready = None          # (data_ptr, _version) of the gradient tensor those sums were reduced over
         f32 = dict(dtype=torch.float32, device=device)
         self.tables = torch.empty((plan.table_rows, 8), **f32)
         self.c = {slot: torch.empty(plan.shapes[slot], **f32) for slot in plan.slots}
@@ -155,12 +142,6 @@ class _Buffers(_BufferSet):
             _spare_shapes.add(key)
             spare = [torch.empty(plan.out_shape, **f32) for _ in range(3)]
             del spare
-
-    def tail_buffers(self, plan, nbytes):
-        if self.tail is None or self.tail[0].numel() < nbytes:
-            self.tail = (torch.empty(nbytes, dtype=torch.uint8, device=self.device),
-                         torch.empty((plan.out_shape[1], TAIL_ROWS, 3), dtype=torch.float64, device=self.device))
-        return self.tail
 
     def backward_scratch(self, plan):
         if self.bwd is None:
@@ -380,9 +361,6 @@ class ResidualBlockFn(torch.autograd.Function):
         io.out = out.data_ptr()
         bufs = _free_set(plan.sets, x.device, lambda: _Buffers(plan, x.device))
         lease = _Lease(bufs)
-        bufs.open_ready = None
-        # the block whose output this input is (residual_block tags its result): its buffers, for the tail sums of backward
-        ctx.producer = getattr(x, '_p3d_block_out', None) if (USE_TAIL_SUMS and plan.tail_ok) else None
         tables, cs, acts, row = bufs.tables, bufs.c, bufs.act, 0
         if bufs.mask is not None:
             io.out_mask = bufs.mask.data_ptr()
@@ -420,7 +398,6 @@ class ResidualBlockFn(torch.autograd.Function):
         ctx.block, ctx.plan = block, plan
         ctx.saved = (lease, bufs)                          # (a plain attribute: the plan's buffers are never inputs / outputs of another node)
         ctx.save_for_backward(x, out)
-        block.__dict__['_last_exec'] = (bufs, plan)        # residual_block() tags the returned tensor with it
         if veil is not None:
             ctx.mark_non_differentiable(veil_out)
             return out, veil_out
@@ -452,34 +429,6 @@ class ResidualBlockFn(torch.autograd.Function):
         if ctx.pix is not None:
             for slot, (v, mult) in ctx.pix.items():
                 io.pix_in[slot], io.pix_out[slot] = v.data_ptr(), mult.data_ptr()
-        # This block as the producer: the block that consumed `out` reduced the opening sums over the gradient it wrote -- valid if that very tensor arrives here
-        # untouched (another consumer's gradient would have been added by autograd: a new tensor, or an in-place add that bumps the version).
-        if bufs.open_ready is not None and bufs.open_ready == (dout.data_ptr(), dout._version) and bufs.tail is not None:
-            io.open_sums = bufs.tail[1].data_ptr()
-            TAIL_STATS['opening_passes_skipped'] += 1
-        bufs.open_ready = None
-        # This block as the consumer: hand the producer's tensors to the data gradient that writes dx last.
-        prod = ctx.producer
-        ctx.producer = None
-        tail_for = None
-        if prod is not None and need_dx:
-            pb, pp = prod
-            plast = pp.desc.nconv - 1
-            if pb.held and pp.out_shape == plan.in_shape and pb.device == x.device and (pb.mask is not None) == bool(pp.desc.relu_out):
-                prow = 0
-                ptab = {}
-                for slot in pp.slots:
-                    ptab[slot] = pb.tables.data_ptr() + prow * 32
-                    prow += pp.shapes[slot][1]
-                scratch, sums = pb.tail_buffers(pp, plan.tail_bytes)
-                io.tail_c_last, io.tail_table_last = pb.c[plast].data_ptr(), ptab[plast]
-                if pp.desc.has_downsample:
-                    io.tail_c_ds, io.tail_table_ds = pb.c[3].data_ptr(), ptab[3]
-                if pb.mask is not None:
-                    io.tail_mask = pb.mask.data_ptr()
-                io.tail_partial, io.tail_sums = scratch.data_ptr(), sums.data_ptr()
-                tail_for = pb
-                TAIL_STATS['reduced'] += 1
         row = 0
         for slot, conv, bn in layers:
             io.w[slot], io.c[slot] = conv.weight.data_ptr(), cs[slot].data_ptr()
@@ -512,8 +461,6 @@ class ResidualBlockFn(torch.autograd.Function):
         ws = ops.workspace(x.device, plan.main_bytes)
         side, side_handle, sws = ops._side_launch(x.device, grads.direct and BLOCK_SIDE_STREAM, plan.side_bytes, block=True)
         check(L.p3d_block_bwd(ctypes.byref(desc), ctypes.byref(io), ops._p(ws), ws.numel(), ops._p(sws), sws.numel(), ops._stream(), side_handle), 'p3d_block_bwd')
-        if tail_for is not None and dx is not None:
-            tail_for.open_ready = (dx.data_ptr(), dx._version)      # the producer's backward checks that this is what it receives
         # the allocator-owned tensors the second stream reads: x (first conv's and the downsample's weight gradients) and, for a masked block, conv 1's mask_in (its
         # weight gradient multiplies x by it); everything else is the plan's
         ops._side_launched(side, (x, None if ctx.pix is None else ctx.pix[0][0]), bufs)
@@ -526,12 +473,7 @@ def residual_block(block, x, veil=None):
     params = []
     for _, conv, bn in _layers(block):
         params += [conv.weight, bn.weight, bn.bias]
-    res = ResidualBlockFn.apply(x, block, veil, *params)
-    out = res[0] if veil is not None else res
-    last = block.__dict__.pop('_last_exec', None)
-    if last is not None and USE_TAIL_SUMS:
-        out._p3d_block_out = last        # a consumer block that receives THIS tensor object as its input may reduce our opening sums in its backward pass
-    return res
+    return ResidualBlockFn.apply(x, block, veil, *params)
 
 
 # ---- a single convolution on image operands (the 3x3 `regressor` behind layer4: depthnet.py:156,199) ------------------------------------------------------

@@ -183,12 +183,11 @@ def test_fused_block(pkg, blk, hw, n):
 
 @needs_blocks
 @pytest.mark.parametrize('hw', T.ASPECTS, ids=hw_id)
-def test_block_out_mask_tail_sums_and_masked_block(pkg, hw):
-    """out_mask bytes on / off (bit-identical), the producer / consumer pair of the opening sums, and one block of partial convolutions (stride 2, downsample)"""
+def test_block_out_mask_and_masked_block(pkg, hw):
+    """out_mask bytes on / off (bit-identical) and one block of partial convolutions (stride 2, downsample)"""
     h, w = hw
     tb.test_out_mask_bytes_equal_reading_the_output(pkg, ('bottleneck', 256, 128, 2, True, (3, 256, h, w), (3, 512, h // 2, w // 2)))
     tb.test_out_mask_bytes_equal_reading_the_output(pkg, ('basic', 128, 128, 1, False, (3, 128, h, w), (3, 128, h, w)))
-    tb.opening_sums_case(pkg, 'identity', h, w)
     tb.masked_block_case(pkg, 'bottleneck', 256, 128, 2, 1, 3, h, w, True)
 
 

@@ -347,3 +347,12 @@ def test_gradient_sink_rules(pkg):
     assert all(b is not gamma.grad and b.shape == (8,) for b in out.bufs) and out.bufs[0] is not out.bufs[1]
     ret = out.done()
     assert ret[0] is out.bufs[0] and ret[1] is out.bufs[1] and not calls
+
+
+def test_block_io_mirror_has_the_size_the_executor_asserts(pkg):
+    """ops_block.BlockIO mirrors struct p3d_block_io (include/p3d_hip.h): 74 pointers.  csrc/p3d_block.hip holds the same number in a static_assert, so a field
+    added on one side only fails either the build or this test instead of shifting every pointer behind it."""
+    import ctypes
+    assert ctypes.sizeof(pkg.ops_block.BlockIO) == 592 == 74 * ctypes.sizeof(ctypes.c_void_p)
+    with open(os.path.join(os.path.dirname(pkg.__file__), 'csrc', 'p3d_block.hip')) as f:
+        assert 'static_assert(sizeof(p3d_block_io) == 592,' in f.read()

@@ -18,8 +18,8 @@ Which test fences which entry point of include/p3d_hip.h (every one that takes a
   p3d_conv2d_fwd / _dgrad / _wgrad              test_fp32_conv, test_fp32_partial_conv, test_x3_conv, test_outputs_conv, test_outputs_conv_accumulate,
                                                 test_short_workspace_is_refused[conv2d_*], test_optional_workspace_may_be_missing
   p3d_conv2d_bn_eval_fwd                        test_conv_bn_eval, test_short_workspace_is_refused[conv2d_bn_eval_fwd]
-  p3d_block_fwd / _bwd (main and side workspace; aimg, dcimg, tables, out_mask: test_outputs_block; tail_partial, tail_sums: test_block_tail_sums; the weight images of
-  p3d_fx_weight_images_batched)                 test_block_executor, test_masked_block_executor, test_block_tail_sums, test_outputs_block, ...[block_fwd / block_bwd]
+  p3d_block_fwd / _bwd (main and side workspace; aimg, dcimg, tables, out_mask: test_outputs_block; the weight images of
+  p3d_fx_weight_images_batched)                 test_block_executor, test_masked_block_executor, test_outputs_block, ...[block_fwd / block_bwd]
   p3d_hblock_fwd / _bwd                         test_half_block_executor, test_half_training_step, ...[hblock_fwd / hblock_bwd]
   p3d_fx_weight_images, p3d_fx_fold_bn_images   test_outputs_weight_images_and_fold_kind0, test_outputs_fold_kind2, test_outputs_fold_kind3 (kind 1: test_folded_net)
   p3d_fx_act_image                              test_outputs_activation_image, test_image_fed_conv
@@ -369,34 +369,6 @@ def test_block_executor(pkg, fenced_scratch, case):
 def test_masked_block_executor(pkg, fenced_scratch, case):
     kind, inplanes, planes, stride, dil, n, h, with_ds = case
     fenced_then_plain(fenced_scratch, lambda: tb.masked_block_case(pkg, kind, inplanes, planes, stride, dil, n, h, h, with_ds), [(tb, 'rel'), (torch, 'equal')])
-
-
-@needs_blocks
-@pytest.mark.parametrize('consumer', _params(tb.test_opening_sums_from_the_consumer_blocks_epilogue))
-def test_block_tail_sums(pkg, fenced_outputs, fenced_scratch, consumer, monkeypatch):
-    """tail_partial and tail_sums, the opening sums a consumer block's data gradient leaves for its producer.  ops_block takes the two tables from torch.empty, not
-    from the scratch: under fenced_outputs they lie, poisoned, in fences of exactly p3d_block_tail_partial_bytes and C x P3D_TAIL_ROWS x 3 doubles -- asserted on
-    the tensors the producer's buffer sets hold when the case has run"""
-    ob, blocks, build = pkg.ops_block, [], tb.build
-
-    def keep(*a, **k):
-        blocks.append(build(*a, **k))
-        return blocks[-1]
-    monkeypatch.setattr(tb, 'build', keep)
-    fenced_then_plain(fenced_scratch, lambda: tb.opening_sums_case(pkg, consumer, 32, 32))
-    fenced_outputs.check()
-    tails = [(plan, bufs.tail) for blk in blocks for plan in blk.__dict__.get('_blk_plans', {}).values() for bufs in plan.sets if bufs.tail is not None]
-    if consumer == 'downsample_s2':                          # (a strided downsample consumer cannot leave the sums: opening_sums_case asserts that none were)
-        return
-    assert tails
-    # (the producer's buffer set keeps the tables; their size is the CONSUMER's query: it is that block's data gradient which fills them)
-    L = pkg._lib.lib()
-    asked = {L.p3d_block_tail_partial_bytes(ctypes.byref(plan.desc)) for blk in blocks for plan in blk.__dict__.get('_blk_plans', {}).values() if plan.tail_ok}
-    for plan, (partial, sums) in tails:
-        assert partial.numel() in asked and partial.numel() > 0 and partial.dtype == torch.uint8, (partial.numel(), asked)
-        assert tuple(sums.shape) == (plan.out_shape[1], ob.TAIL_ROWS, 3) and sums.dtype == torch.float64
-        for t in (partial, sums):
-            assert fenced_outputs.holds(t), 'a tail table outside the fences'
 
 
 def _hconv_op_case(pkg, case):
