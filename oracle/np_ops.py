@@ -496,6 +496,30 @@ def masked_loss(pred, target, valid, criterion='SmoothL1'):
     return float((per * mask).sum() / count), dper * mask / count
 
 
+# ---- feature distillation (depth_train.py:115-129) ---------------------------------------------------------------------------------
+def distill_fwd_bwd(t, s, a, mode):
+    """Trainer.distill in float64: teacher / student features t, s [B,C,H,W], attention a [B,1,H,W] -> (loss, d loss / d s).
+      'l2'      diff = (t - s) * a,                      loss = mean_b ||diff_b||_2
+      'sigmoid' diff = (sigmoid(t) - sigmoid(s)) * a,    loss = mean_b ||diff_b||_2
+      'bce'     F.binary_cross_entropy_with_logits(s, sigmoid(t)) with its default 'mean' reduction is a scalar, which the reference multiplies by the
+                attention map and sums per sample: loss = mean_all(bce) * mean_b(sum_hw a_b).
+    A sample whose norm is zero gets a zero gradient (the subgradient torch.linalg.norm's backward picks)."""
+    t, s, a = (np.asarray(v, np.float64) for v in (t, s, a))
+    b = s.shape[0]
+    sig = lambda x: 1.0 / (1.0 + np.exp(-x))
+    if mode == 'bce':
+        y = sig(t)
+        per = np.maximum(s, 0) - s * y + np.log1p(np.exp(-np.abs(s)))
+        att = a.reshape(b, -1).sum(1).mean()
+        return per.mean() * att, (sig(s) - y) * (att / s.size)
+    ss = sig(s)
+    diff = ((sig(t) - ss) if mode == 'sigmoid' else (t - s)) * a
+    norm = np.sqrt((diff.reshape(b, -1) ** 2).sum(1))
+    inv = np.divide(1.0, norm, out=np.zeros_like(norm), where=norm > 0).reshape(b, 1, 1, 1)
+    inner = ss * (1 - ss) if mode == 'sigmoid' else 1.0
+    return norm.mean(), -diff * a * inner * inv / b
+
+
 def softargmax2d(z, map_range):
     """mat_utils.to_heatmap + decode (mat_utils.py:32-56): softmax over H*W, expectation against linspace(0, 1, n) * map_range."""
     z = np.asarray(z, np.float64)
