@@ -31,6 +31,7 @@ constexpr int BLOCK_MIN_M = 64;
 // every convolution must be on the x3 kernels (there is no fp32 copy of a_i / d c_i for another kernel to read).  A main-chain convolution whose strided
 // data gradient leaves input pixels untouched (1x1, stride 2: fx_dgrad_has_dead_classes) is refused: its gradient buffer is not zero-filled here (the
 // reference's blocks put the stride on the 3x3; the strided 1x1 of a downsample branch ADDS onto a gradient that is already complete).
+static bool block_slot(const p3d_block_desc* b, int i) { return i < b->nconv || (i == 3 && b->has_downsample); }      // slots 0 .. nconv - 1: the main chain; 3: the downsample conv
 static bool block_conv_ok(const p3d_conv_desc* d, bool main_chain) {
     return fx_fwd_applies(d, BLOCK_MIN_M) && fx_dgrad_applies(d, BLOCK_MIN_M) && fx_wgrad_applies(d, BLOCK_MIN_M) && (d->Ho * d->Wo) % 4 == 0 &&
            (d->H * d->W) % 4 == 0 && d->C % 16 == 0 && d->K % 16 == 0 && !(main_chain && fx_dgrad_has_dead_classes(d));
@@ -361,17 +362,84 @@ static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // a partial convolution inside the executor: the per-pixel factors live in the conv kernels' epilogues (for a split-K launch: in the pass that sums the slabs)
 static bool masked_conv_ok(const p3d_conv_desc* d) { return fx_fwd_masked_applies(d) && fx_dgrad_masked_applies(d); }
 
+// The admission predicate of the executor (b non-null, nconv 2 or 3): 0 = every slot is taken; otherwise *slot is the first one refused, 1 = its shape is outside
+// the fused path, 2 = it is a partial convolution outside the masked instances
+static int block_refusal(const p3d_block_desc* b, int* slot) {
+    for (int i = 0; i < 4; ++i) {
+        if (!block_slot(b, i)) continue;
+        *slot = i;
+        if (!block_conv_ok(&b->conv[i], i < 3)) return 1;
+        if (b->masked && i != 3 && !masked_conv_ok(&b->conv[i])) return 2;
+    }
+    return 0;
+}
 static int32_t check_block(const p3d_block_desc* b) {
     P3D_REQUIRE(b != nullptr, "block: null descriptor");
     P3D_REQUIRE(b->nconv == 2 || b->nconv == 3, "block: nconv must be 2 (BasicBlock) or 3 (Bottleneck), got %d", b->nconv);
-    for (int i = 0; i < 4; ++i) {
-        if (i >= b->nconv && !(i == 3 && b->has_downsample)) continue;
-        const p3d_conv_desc* d = &b->conv[i];
-        P3D_REQUIRE(block_conv_ok(d, i < 3),
-                    "block: convolution %d (C=%d K=%d %dx%d stride %d, %dx%d input) is outside the fused path", i, d->C, d->K, d->R, d->S, d->stride, d->H, d->W);
-        P3D_REQUIRE(!b->masked || i == 3 || masked_conv_ok(d), "block: partial convolution %d is outside the masked instances of the x3 kernels", i);
-    }
+    int i = 0;
+    const int why = block_refusal(b, &i);
+    const p3d_conv_desc* d = &b->conv[i];
+    P3D_REQUIRE(why != 1, "block: convolution %d (C=%d K=%d %dx%d stride %d, %dx%d input) is outside the fused path", i, d->C, d->K, d->R, d->S, d->stride, d->H, d->W);
+    P3D_REQUIRE(why != 2, "block: partial convolution %d is outside the masked instances of the x3 kernels", i);
     return P3D_OK;
+}
+
+// The executor's two workspaces.  main (the launch stream's) = [conv scratch: weight images, split-K slabs | partial sums | the downsample conv's partial sums]: the
+// closing conv's and the downsample conv's sums live side by side until the closing pass has read both; side (the weight-gradient stream's) = slabs.
+struct BlockLayout { size_t conv_ws, part_bytes, main_bytes, side_bytes; };
+static BlockLayout block_layout(const p3d_block_desc* b) {
+    size_t mw = 0, sw = 0, part = 0;
+    auto atleast = [](size_t& m, size_t v) { if (v > m) m = v; };
+    for (int i = 0; i < 4; ++i) {
+        if (!block_slot(b, i)) continue;
+        const p3d_conv_desc* d = &b->conv[i];
+        atleast(mw, fx_fwd_workspace(d));
+        atleast(mw, fx_dgrad_workspace(d));
+        atleast(part, (size_t)fx_partial_rows_fwd(d) * d->K * 2 * sizeof(float));
+        atleast(part, (size_t)fx_partial_rows_dgrad(d) * d->C * 2 * sizeof(float));
+        atleast(part, (size_t)(d->K > d->C ? d->K : d->C) * CLOSE_MAX_SPLIT * 3 * sizeof(double));      // the opening pass's and bn_bwd_sums_kernel's fp64 sums
+        atleast(sw, fx_wgrad_workspace(d));
+    }
+    return BlockLayout{align256(mw), align256(part), align256(mw) + 2 * align256(part), align256(sw)};
+}
+
+// the constants of the BatchNorm behind conv `i`, as the finalize steps take them
+struct BlockBn { const float *gamma, *beta; float *running_mean, *running_var; float momentum, eps; float *dgamma, *dbeta, *table; };
+static BlockBn block_bn(const p3d_block_desc* b, const p3d_block_io* io, int i) {
+    return BlockBn{io->gamma[i], io->beta[i], io->running_mean[i], io->running_var[i], b->momentum[i], b->eps[i], io->dgamma[i], io->dbeta[i], io->table[i]};
+}
+
+// How a BatchNorm gets from partial sums to its constants, decided here for both directions: with few partial rows (the 32 x 32 and 16 x 16 stages, split-K launches) in
+// the prologue of the pass that consumes the constants; with many (layer1: 2048 pixel tiles) every block of that pass would sum all of them again, strided, in front
+// of its streaming loop (measured: the closing pass ran at 4.2 TB/s), and a finalize launch of its own costs less (round 4).
+// Forward: the CloseFin for the consumer's prologue, or, after a launch of bn_finalize_fwd_kernel, the same with rows = 0: read the table.
+static CloseFin finalize_fwd(const BlockBn& bn, const float* partial, int rows, int C, double count, hipStream_t st) {
+    if (rows > FX_FIN_MAX_ROWS) {
+        hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(fin_threads(rows)), 0, st, partial, rows, C, count, bn.gamma, bn.beta, bn.running_mean,
+                           bn.running_var, bn.momentum, bn.eps, bn.table);
+        rows = 0;
+    }
+    return CloseFin{partial, rows, bn.gamma, bn.beta, bn.running_mean, bn.running_var, bn.momentum, bn.eps, bn.table};
+}
+// the same step as fx_act_image takes it (an inner layer: the consumer is the image pass of a_i)
+static FxFinalize act_finalize(const CloseFin& f, double count) {
+    FxFinalize fin{};
+    fin.kind = 1; fin.partial = f.partial; fin.rows = f.rows; fin.count = count; fin.gamma = f.gamma; fin.beta = f.beta;
+    fin.running_mean = f.running_mean; fin.running_var = f.running_var; fin.momentum = f.momentum; fin.eps = f.eps; fin.table = f.table;
+    return fin;
+}
+// Backward: the FxFinalize for the prologue of the image pass of d c (fp64 sums of the opening pass, kind 3, always; fp32 sums of a data gradient's epilogue, kind 2,
+// when the rows are few), or, after a launch of bn_finalize_bwd_kernel, one of kind 0: read the table.
+static FxFinalize finalize_bwd(const BlockBn& bn, int kind, const void* partial, int rows, int which, int C, double count, int accumulate, hipStream_t st) {
+    FxFinalize fin{};
+    if (kind == 3 || rows <= FX_FIN_MAX_ROWS) {
+        fin.kind = kind; fin.partial = partial; fin.rows = rows; fin.which = which; fin.count = count; fin.gamma = bn.gamma;
+        fin.dgamma = bn.dgamma; fin.dbeta = bn.dbeta; fin.accumulate = accumulate; fin.table = bn.table;
+    } else {
+        hipLaunchKernelGGL(bn_finalize_bwd_kernel<false>, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(fin_threads(rows)), 0, st, partial, rows, C, count, 0, bn.gamma, bn.dgamma,
+                           bn.dbeta, accumulate, bn.table);
+    }
+    return fin;
 }
 
 }  // namespace p3d
@@ -381,68 +449,30 @@ using namespace p3d;
 extern "C" {
 
 int32_t p3d_block_supported(const p3d_block_desc* b) {
-    if (!fx_enabled() || !b || !(b->nconv == 2 || b->nconv == 3)) return 0;
-    for (int i = 0; i < 4; ++i) {
-        if (i >= b->nconv && !(i == 3 && b->has_downsample)) continue;
-        const p3d_conv_desc* d = &b->conv[i];
-        if (!block_conv_ok(d, i < 3)) return 0;
-        if (b->masked && i != 3 && !masked_conv_ok(d)) return 0;
-    }
-    return 1;
+    int slot = 0;
+    return fx_enabled() && b && (b->nconv == 2 || b->nconv == 3) && block_refusal(b, &slot) == 0 ? 1 : 0;
 }
 
-// main = workspace of the launch stream (weight images, split-K slabs, partial sums), side = workspace of the weight-gradient stream (slabs)
 int32_t p3d_block_workspace_bytes(const p3d_block_desc* b, size_t* main_bytes, size_t* side_bytes) {
     if (int32_t e = check_block(b)) return e;
-    size_t mw = 0, sw = 0, part = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (i >= b->nconv && !(i == 3 && b->has_downsample)) continue;
-        const p3d_conv_desc* d = &b->conv[i];
-        size_t a = fx_fwd_workspace(d), g = fx_dgrad_workspace(d);
-        if (g > a) a = g;
-        if (a > mw) mw = a;
-        size_t rows = (size_t)fx_partial_rows_fwd(d) * d->K, r2 = (size_t)fx_partial_rows_dgrad(d) * d->C;
-        if (r2 > rows) rows = r2;
-        if (rows * 2 * sizeof(float) > part) part = rows * 2 * sizeof(float);
-        const size_t open = (size_t)d->K * CLOSE_MAX_SPLIT * 3 * sizeof(double), open2 = (size_t)d->C * CLOSE_MAX_SPLIT * 3 * sizeof(double);
-        if (open > part) part = open;
-        if (open2 > part) part = open2;
-        const int ns = fx_wgrad_splits(d, false) > fx_wgrad_splits(d, true) ? fx_wgrad_splits(d, false) : fx_wgrad_splits(d, true);
-        const size_t slabs = (size_t)ns * d->K * d->C * d->R * d->S * sizeof(float);
-        if (slabs > sw) sw = slabs;
-    }
-    if (main_bytes) *main_bytes = align256(mw) + 2 * align256(part);          // (two partial-sum regions: the closing conv's and the downsample conv's live side by side)
-    if (side_bytes) *side_bytes = align256(sw);
+    const BlockLayout lay = block_layout(b);
+    if (main_bytes) *main_bytes = lay.main_bytes;
+    if (side_bytes) *side_bytes = lay.side_bytes;
     return P3D_OK;
 }
 
 int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* workspace, size_t workspace_bytes, void* stream) {
     if (int32_t e = check_block(b)) return e;
     P3D_REQUIRE(io && io->x && io->out, "block_fwd: null tensor");
-    size_t need = 0;
-    p3d_block_workspace_bytes(b, &need, nullptr);
-    if (!workspace || workspace_bytes < need) { set_error("block_fwd: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
+    const BlockLayout lay = block_layout(b);
+    if (!workspace || workspace_bytes < lay.main_bytes) { set_error("block_fwd: workspace %zu B < required %zu B", workspace_bytes, lay.main_bytes); return P3D_EWORKSPACE; }
     hipStream_t st = (hipStream_t)stream;
-    size_t conv_ws = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (i >= b->nconv && !(i == 3 && b->has_downsample)) continue;
-        size_t a = fx_fwd_workspace(&b->conv[i]), g = fx_dgrad_workspace(&b->conv[i]);
-        if (g > a) a = g;
-        if (a > conv_ws) conv_ws = a;
-    }
-    conv_ws = align256(conv_ws);
-    float* partial = (float*)((char*)workspace + conv_ws);
-    size_t part_bytes = 0;
-    {
-        size_t need_main = 0;
-        p3d_block_workspace_bytes(b, &need_main, nullptr);
-        part_bytes = (need_main - conv_ws) / 2;
-    }
-    float* partial2 = (float*)((char*)partial + part_bytes);          // the downsample conv's partial sums
+    float* partial = (float*)((char*)workspace + lay.conv_ws);
+    float* partial2 = (float*)((char*)partial + lay.part_bytes);      // the downsample conv's partial sums
     const int last = b->nconv - 1;
     for (int i = 0; i < 4; ++i) {
         const bool ds = i == 3;
-        if (i >= b->nconv && !(ds && b->has_downsample)) continue;
+        if (!block_slot(b, i)) continue;
         const p3d_conv_desc* d = &b->conv[i];
         P3D_REQUIRE(io->w[i] && io->c[i] && io->table[i] && io->gamma[i] && io->beta[i], "block_fwd: null tensor of conv %d", i);
         const bool from_x = ds || i == 0;          // the block input arrives as fp32 (split in the kernel); everything produced inside the block as an image
@@ -460,46 +490,179 @@ int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
         {
             ProfScope ps(0, d, st);
             fx_count(0, d);
-            if (int32_t e = fx_conv_fwd(d, from_x ? io->x : nullptr, io->w[i], nullptr, io->c[i], workspace, conv_ws, &f, st)) return e;
+            if (int32_t e = fx_conv_fwd(d, from_x ? io->x : nullptr, io->w[i], nullptr, io->c[i], workspace, lay.conv_ws, &f, st)) return e;
         }
         if (ds || i == last) continue;               // the closing pass finalizes these two BatchNorm layers itself
-        // a_i = relu(bn_i(c_i)), written once, as the image the next convolution (and, in backward, its weight gradient) copies into LDS.  With few partial rows
-        // (the 32 x 32 and 16 x 16 stages, split-K launches) the statistics are finalized in that pass's prologue; otherwise by a launch of its own.
+        // a_i = relu(bn_i(c_i)), written once, as the image the next convolution (and, in backward, its weight gradient) copies into LDS
         P3D_REQUIRE(io->aimg[i], "block_fwd: null activation image %d", i);
-        const int rows = fx_partial_rows_fwd(d);
         const double cnt = (double)d->N * d->Ho * d->Wo;
-        if (rows <= FX_FIN_MAX_ROWS) {
-            FxFinalize fin{};
-            fin.kind = 1; fin.partial = partial; fin.rows = rows; fin.count = cnt; fin.gamma = io->gamma[i]; fin.beta = io->beta[i];
-            fin.running_mean = io->running_mean[i]; fin.running_var = io->running_var[i]; fin.momentum = b->momentum[i]; fin.eps = b->eps[i]; fin.table = io->table[i];
-            if (int32_t e = fx_act_image(1, io->c[i], nullptr, io->table[i], 0, io->aimg[i], d->N, d->K, d->Ho * d->Wo, st, &fin, mk ? io->pix_in[i + 1] : nullptr)) return e;
-        } else {
-            hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3((unsigned)ceil_div(d->K, FIN_CH)), dim3(fin_threads(rows)), 0, st, (const float*)partial, rows, d->K, cnt, io->gamma[i],
-                               io->beta[i], io->running_mean[i], io->running_var[i], b->momentum[i], b->eps[i], io->table[i]);
-            if (int32_t e = fx_act_image(1, io->c[i], nullptr, io->table[i], 0, io->aimg[i], d->N, d->K, d->Ho * d->Wo, st, nullptr, mk ? io->pix_in[i + 1] : nullptr)) return e;
-        }
+        const CloseFin cf = finalize_fwd(block_bn(b, io, i), partial, fx_partial_rows_fwd(d), d->K, cnt, st);
+        const FxFinalize fin = act_finalize(cf, cnt);
+        if (int32_t e = fx_act_image(1, io->c[i], nullptr, io->table[i], 0, io->aimg[i], d->N, d->K, d->Ho * d->Wo, st, cf.rows ? &fin : nullptr, mk ? io->pix_in[i + 1] : nullptr)) return e;
     }
     const p3d_conv_desc* dl = &b->conv[last];
     const int HW = dl->Ho * dl->Wo;
-    CloseFin cf{partial, fx_partial_rows_fwd(dl), io->gamma[last], io->beta[last], io->running_mean[last], io->running_var[last], b->momentum[last], b->eps[last], io->table[last]};
-    CloseFin rf{};
-    if (b->has_downsample)
-        rf = CloseFin{partial2, fx_partial_rows_fwd(&b->conv[3]), io->gamma[3], io->beta[3], io->running_mean[3], io->running_var[3], b->momentum[3], b->eps[3], io->table[3]};
-    // With many partial rows (layer1: 2048 pixel tiles) the closing pass's blocks -- one per (channel, image group) -- would each sum all of them again, strided, in front
-    // of their streaming loop (measured: the pass ran at 4.2 TB/s); a finalize launch of its own then costs less (round 4).  rows = 0 tells the pass to read the table.
     const double cnt_close = (double)dl->N * HW;
-    for (CloseFin* f : {&cf, &rf}) {
-        if (f->partial && f->rows > FX_FIN_MAX_ROWS) {
-            const int slot = f == &cf ? last : 3;
-            hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3((unsigned)ceil_div(dl->K, FIN_CH)), dim3(fin_threads(f->rows)), 0, st, (const float*)f->partial, f->rows, dl->K, cnt_close,
-                               io->gamma[slot], io->beta[slot], io->running_mean[slot], io->running_var[slot], b->momentum[slot], b->eps[slot], io->table[slot]);
-            f->rows = 0;
-        }
-    }
+    const CloseFin cf = finalize_fwd(block_bn(b, io, last), partial, fx_partial_rows_fwd(dl), dl->K, cnt_close, st);
+    const CloseFin rf = b->has_downsample ? finalize_fwd(block_bn(b, io, 3), partial2, fx_partial_rows_fwd(&b->conv[3]), dl->K, cnt_close, st) : CloseFin{};
     hipLaunchKernelGGL(block_close_fwd_kernel, dim3(dl->K, close_split(dl->N, dl->K)), dim3(256), 0, st, (const float*)io->c[last], cf,
-                       b->has_downsample ? (const float*)io->c[3] : io->x, rf, io->out, b->relu_out ? io->out_mask : (unsigned char*)nullptr, dl->N, dl->K, HW, b->relu_out,
-                       (double)dl->N * HW);
+                       b->has_downsample ? (const float*)io->c[3] : io->x, rf, io->out, b->relu_out ? io->out_mask : (unsigned char*)nullptr, dl->N, dl->K, HW, b->relu_out, cnt_close);
     return check_launch("block_fwd");
+}
+
+// ---- backward: four stages over one context ------------------------------------------------------------------------------------------------------
+// Streams: a weight gradient runs on the second stream behind an event of the launch stream; it reads dcimg[i] and aimg[i - 1] / x, none of which the launch
+// stream writes again inside this call, so the launch stream never waits for the second one here.
+struct BwdCtx {
+    const p3d_block_desc* b;
+    const p3d_block_io* io;
+    void* ws; size_t conv_ws;       // the launch stream's workspace: conv scratch
+    void* partial;                  //   and the partial sums behind it
+    float* side_ws;                 // the weight-gradient stream's slabs
+    hipStream_t st, ss;
+    bool two;                       // ss is a stream of its own
+    int acc, last;
+    // g = dout * [out > 0] never exists as a tensor when forward left mask bytes: the two opening image passes mask dout themselves, and with an identity
+    // shortcut the first convolution's data gradient adds the masked dout in its epilogue (dx = dgrad + dout * mask) instead of accumulating into a copy of g
+    bool g_in_memory;
+    const float* g;                 // the gradient behind the closing ReLU: gbuf, or dout to be masked by
+    const unsigned char* gmask;     //   these bytes (null: g is masked already)
+};
+
+// partial convolutions: the gradient image of conv `slot` carries its renormalisation factor (d raw = d c * mult: partial_conv.py:53 and its autograd)
+static const float* bwd_pixmul(const BwdCtx& x, int slot) { return (x.b->masked && slot != 3) ? x.io->pix_out[slot] : nullptr; }
+
+// The gradient that enters conv `slot` is the upstream gradient taken through its BatchNorm's backward map (masked by its ReLU, except the closing BN whose ReLU
+// went into g already): d c = A g + B c + K, written ONCE, as the image both the weight gradient and the data gradient of the conv copy into LDS.  The constants
+// come from channel sums (the opening pass's for the closing and the downsample BatchNorm, the downstream data gradient's epilogue for the others): finalize_bwd.
+static int32_t bwd_map(const BwdCtx& x, const float* gin, int slot, int masked, int kind, int rows, int which, double cnt, const unsigned char* front_mask = nullptr) {
+    const p3d_block_io* io = x.io;
+    const p3d_conv_desc* dc = &x.b->conv[slot];
+    P3D_REQUIRE(io->dcimg[slot], "block_bwd: null gradient image %d", slot);
+    FxFinalize fin = finalize_bwd(block_bn(x.b, io, slot), kind, x.partial, rows, which, dc->K, cnt, x.acc, x.st);
+    fin.gmask = front_mask;
+    return fx_act_image(2, gin, io->c[slot], io->table[slot], masked, io->dcimg[slot], dc->N, dc->K, dc->Ho * dc->Wo, x.st, fin.kind ? &fin : nullptr, bwd_pixmul(x, slot));
+}
+
+// `ready`: the launch stream's position when the gradient image of this convolution was complete (the data gradient of the same layer has been queued on
+// the launch stream since: it is the critical path and gets to the GPU first; the weight gradient only feeds the optimizer)
+static int32_t launch_wgrad(const BwdCtx& x, int slot, const float* xin, const void* ximg, bool tapm, hipEvent_t ready) {
+    const p3d_conv_desc* d = &x.b->conv[slot];
+    if (x.two && (!ready || hipStreamWaitEvent(x.ss, ready, 0) != hipSuccess)) { set_error("block_bwd: event failure"); return P3D_ELAUNCH; }
+    ProfScope ps(2, d, x.ss);
+    fx_count(2, d);
+    FxFuse fw{};
+    fw.dy_img = x.io->dcimg[slot]; fw.x_img = ximg;
+    if (x.b->masked && slot != 3 && !ximg) fw.emask = x.io->pix_in[slot];      // the block input is fp32: x * mask_in in the kernel's split (an image carries it)
+    const int splits = fx_wgrad_splits(d, ximg != nullptr);
+    if (int32_t e = fx_conv_wgrad_slabs(d, nullptr, xin, x.side_ws, splits, &fw, x.ss)) return e;
+    p3d_conv_desc dw_desc = *d;
+    dw_desc.accumulate = x.acc;
+    return wgrad_finish(&dw_desc, x.side_ws, splits, tapm, x.io->dw[slot], x.ss);
+}
+
+static int32_t bwd_dgrad(const BwdCtx& x, int slot, const p3d_conv_desc* dd, float* dx, const FxFuse* f) {
+    ProfScope ps(1, &x.b->conv[slot], x.st);
+    fx_count(1, &x.b->conv[slot]);
+    return fx_conv_dgrad(dd, nullptr, x.io->w[slot], dx, x.ws, x.conv_ws, f, x.st);
+}
+
+// 1. open: g = dout * [out > 0]; channel sums of the closing BN (and of the downsample BN)
+static int32_t bwd_open(const BwdCtx& x) {
+    const p3d_block_desc* b = x.b;
+    const p3d_block_io* io = x.io;
+    const p3d_conv_desc* dl = &b->conv[x.last];
+    hipLaunchKernelGGL(block_open_bwd_kernel, dim3(dl->K, close_split(dl->N, dl->K)), dim3(256), 0, x.st, io->dout, (const float*)io->out, (const float*)io->c[x.last],
+                       (const float*)io->table[x.last], b->has_downsample ? (const float*)io->c[3] : (const float*)nullptr,
+                       b->has_downsample ? (const float*)io->table[3] : (const float*)nullptr, x.g_in_memory ? io->gbuf : (float*)nullptr, (double*)x.partial,
+                       (const unsigned char*)io->out_mask, dl->N, dl->K, dl->Ho * dl->Wo, b->relu_out);
+    return check_launch("block_bwd open");
+}
+
+// 2. the two maps fed by the opening pass's sums (its partial buffer is overwritten by the first data gradient of the chain): closing BatchNorm, downsample BatchNorm
+static int32_t bwd_open_images(const BwdCtx& x) {
+    const p3d_block_desc* b = x.b;
+    const p3d_block_io* io = x.io;
+    const int last = x.last;
+    const p3d_conv_desc* dl = &b->conv[last];
+    const int split = close_split(dl->N, dl->K);
+    const double cnt = (double)dl->N * dl->Ho * dl->Wo;
+    for (int i = 0; b->masked && i < b->nconv; ++i) P3D_REQUIRE(io->pix_in[i] && io->pix_out[i], "block_bwd: null per-pixel factor of partial convolution %d", i);
+    if (b->has_downsample && fx_pair_map_enabled()) {
+        // both images in one pass: g (dout and the mask bytes) is read once
+        P3D_REQUIRE(io->dcimg[last] && io->dcimg[3], "block_bwd: null gradient image");
+        const FxFinalize fa = finalize_bwd(block_bn(b, io, last), 3, x.partial, split, 0, dl->K, cnt, x.acc, x.st);
+        const FxFinalize fb = finalize_bwd(block_bn(b, io, 3), 3, x.partial, split, 1, dl->K, cnt, x.acc, x.st);
+        return fx_act_image_pair(x.g, x.gmask, io->c[last], io->c[3], io->dcimg[last], io->dcimg[3], &fa, &fb, dl->N, dl->K, dl->Ho * dl->Wo, x.st, bwd_pixmul(x, last));
+    }
+    if (int32_t e = bwd_map(x, x.g, last, 0, 3, split, 0, cnt, x.gmask)) return e;
+    return b->has_downsample ? bwd_map(x, x.g, 3, 0, 3, split, 1, cnt, x.gmask) : P3D_OK;
+}
+
+// 3. the main chain, last convolution first.  Per layer the data gradient first (the chain the next layer waits for), then the weight gradient of the same layer on
+//    the second stream, then the image of d c_{i-1}.  `ready`: the launch stream's position when d c_last was complete.
+static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
+    const p3d_block_desc* b = x.b;
+    const p3d_block_io* io = x.io;
+    for (int i = x.last; i >= 0; --i) {
+        const p3d_conv_desc* d = &b->conv[i];
+        if (i > 0) P3D_REQUIRE(io->aimg[i - 1], "block_bwd: null activation image %d", i - 1);
+        FxFuse f{};
+        f.wimg = io->wimgT[i];
+        f.act_img = io->dcimg[i];
+        p3d_conv_desc dd = *d;
+        if (i > 0) {
+            const p3d_conv_desc* dp = &b->conv[i - 1];                       // producer of this conv's input
+            const bool epi = d->stride == 1;
+            if (epi) { f.partial = (float*)x.partial; f.ep_c = io->c[i - 1]; f.ep_tab = io->table[i - 1]; }
+            if (b->masked) f.emask = io->pix_in[i];            // dx = dgrad(d raw) * mask_in: the gradient w.r.t. a_{i-1}, of which the BatchNorm-backward sums are taken
+            dd.accumulate = 0;
+            P3D_REQUIRE(io->da[i - 1], "block_bwd: null gradient buffer %d", i - 1);
+            if (int32_t e = bwd_dgrad(x, i, &dd, io->da[i - 1], &f)) return e;
+            if (int32_t e = launch_wgrad(x, i, nullptr, io->aimg[i - 1], d->R * d->S > 1, ready)) return e;
+            const double cnt = (double)dp->N * dp->Ho * dp->Wo;
+            if (epi) {
+                if (int32_t e = bwd_map(x, io->da[i - 1], i - 1, 1, 2, fx_partial_rows_dgrad(d), 0, cnt)) return e;
+            } else {
+                // a strided data gradient takes no sums in its epilogue: a pass of their own
+                const int sp = close_split(dp->N, dp->K);
+                hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(dp->K, sp), dim3(256), 0, x.st, (const float*)io->da[i - 1], (const float*)io->c[i - 1],
+                                   (const float*)io->table[i - 1], (double*)x.partial, dp->N, dp->K, dp->Ho * dp->Wo);
+                if (int32_t e = bwd_map(x, io->da[i - 1], i - 1, 1, 3, sp, 0, cnt)) return e;
+            }
+            ready = x.two ? mark_position(x.st) : nullptr;                  // d c_{i-1} is complete
+            continue;
+        }
+        if (b->need_dx) {
+            // block input: identity shortcut -> the gradient joins g's own buffer in place (dx = g + dgrad); downsample shortcut -> dx is written here and
+            // the downsample conv's dgrad adds to it in the last stage.  No weight-gradient kernel reads g (they read the images), so the launch stream does not wait.
+            float* dx;
+            if (b->masked) f.emask = io->pix_in[0];
+            if (b->has_downsample) { dx = io->dx; dd.accumulate = 0; }
+            else {
+                P3D_REQUIRE(b->relu_out, "block_bwd: an identity shortcut without the closing ReLU would overwrite the caller's gradient (not a reference block)");
+                P3D_REQUIRE(io->gbuf, "block_bwd: null gradient buffer (dx of an identity shortcut)");
+                dx = io->gbuf; dd.accumulate = 1;
+                if (!x.g_in_memory) { f.acc_src = io->dout; f.acc_mask = io->out_mask; }      // gbuf is written here for the first time
+            }
+            if (int32_t e = bwd_dgrad(x, 0, &dd, dx, &f)) return e;
+        }
+        if (int32_t e = launch_wgrad(x, 0, io->x, nullptr, d->R * d->S > 1, ready)) return e;
+    }
+    return P3D_OK;
+}
+
+// 4. downsample branch: data gradient added onto dx, weight gradient (its gradient image was written with the closing BatchNorm's: `ready` is the chain's first event)
+static int32_t bwd_downsample(const BwdCtx& x, hipEvent_t ready) {
+    if (x.b->need_dx) {
+        FxFuse f{};
+        f.wimg = x.io->wimgT[3];
+        f.act_img = x.io->dcimg[3];
+        p3d_conv_desc dd = x.b->conv[3];
+        dd.accumulate = 1;
+        if (int32_t e = bwd_dgrad(x, 3, &dd, x.io->dx, &f)) return e;
+    }
+    return launch_wgrad(x, 3, x.io->x, nullptr, false, ready);
 }
 
 // dout -> dx (+ every parameter gradient, accumulated into io->dw / dgamma / dbeta when b->accumulate_grads, else written).
@@ -510,173 +673,32 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
     static_assert(sizeof(p3d_block_io) == 592, "74 pointers (ops_block.BlockIO mirrors the struct)");
     if (int32_t e = check_block(b)) return e;
     P3D_REQUIRE(io && io->x && io->out && io->dout, "block_bwd: null tensor");
-    // g = dout * [out > 0] never exists as a tensor when forward left mask bytes: the two opening image passes mask dout themselves, and with an identity
-    // shortcut the first convolution's data gradient adds the masked dout in its epilogue (dx = dgrad + dout * mask) instead of accumulating into a copy of g
-    const bool g_in_memory = !(b->relu_out && io->out_mask && (b->has_downsample || !b->need_dx || fx_dgrad_accumulates_from_source(&b->conv[0])));
-    P3D_REQUIRE(!g_in_memory || !b->relu_out || io->gbuf, "block_bwd: null gradient buffer");
-    size_t need = 0, need_side = 0;
-    p3d_block_workspace_bytes(b, &need, &need_side);
-    if (!workspace || workspace_bytes < need || !side_workspace || side_bytes < need_side) {
-        set_error("block_bwd: workspaces %zu / %zu B < required %zu / %zu B", workspace_bytes, side_bytes, need, need_side);
+    BwdCtx x{};
+    x.b = b; x.io = io;
+    x.g_in_memory = !(b->relu_out && io->out_mask && (b->has_downsample || !b->need_dx || fx_dgrad_accumulates_from_source(&b->conv[0])));
+    P3D_REQUIRE(!x.g_in_memory || !b->relu_out || io->gbuf, "block_bwd: null gradient buffer");
+    const BlockLayout lay = block_layout(b);
+    if (!workspace || workspace_bytes < lay.main_bytes || !side_workspace || side_bytes < lay.side_bytes) {
+        set_error("block_bwd: workspaces %zu / %zu B < required %zu / %zu B", workspace_bytes, side_bytes, lay.main_bytes, lay.side_bytes);
         return P3D_EWORKSPACE;
     }
-    hipStream_t st = (hipStream_t)stream, ss = side_stream ? (hipStream_t)side_stream : st;
-    const bool two = ss != st;
-    size_t conv_ws = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (i >= b->nconv && !(i == 3 && b->has_downsample)) continue;
-        size_t a = fx_fwd_workspace(&b->conv[i]), g = fx_dgrad_workspace(&b->conv[i]);
-        if (g > a) a = g;
-        if (a > conv_ws) conv_ws = a;
-    }
-    conv_ws = align256(conv_ws);
-    void* partial = (char*)workspace + conv_ws;
-    const int last = b->nconv - 1;
-    const p3d_conv_desc* dl = &b->conv[last];
-    const int acc = b->accumulate_grads;
+    x.ws = workspace; x.conv_ws = lay.conv_ws; x.partial = (char*)workspace + lay.conv_ws; x.side_ws = (float*)side_workspace;
+    x.st = (hipStream_t)stream; x.ss = side_stream ? (hipStream_t)side_stream : x.st;
+    x.two = x.ss != x.st;
+    x.acc = b->accumulate_grads; x.last = b->nconv - 1;
+    x.g = (b->relu_out && x.g_in_memory) ? io->gbuf : io->dout;
+    x.gmask = x.g_in_memory ? nullptr : io->out_mask;
 
-    // 1. open: g = dout * [out > 0]; channel sums of the closing BN (and of the downsample BN)
-    const int split = close_split(dl->N, dl->K);
-    const float* g = (b->relu_out && g_in_memory) ? io->gbuf : io->dout;
-    const unsigned char* gmask = g_in_memory ? nullptr : io->out_mask;
-    hipLaunchKernelGGL(block_open_bwd_kernel, dim3(dl->K, split), dim3(256), 0, st, io->dout, (const float*)io->out, (const float*)io->c[last],
-                       (const float*)io->table[last], b->has_downsample ? (const float*)io->c[3] : (const float*)nullptr,
-                       b->has_downsample ? (const float*)io->table[3] : (const float*)nullptr, g_in_memory ? io->gbuf : (float*)nullptr, (double*)partial,
-                       (const unsigned char*)io->out_mask, dl->N, dl->K,
-                       dl->Ho * dl->Wo, b->relu_out);
-    const double cnt_last = (double)dl->N * dl->Ho * dl->Wo;
-    if (int32_t e = check_launch("block_bwd open")) return e;
-
-    // 2. The gradient that enters conv i is the upstream gradient taken through BN i's backward map (masked by its ReLU, except the closing BN whose ReLU went
-    //    into g already): d c_i = A g + B c_i + K, written ONCE, as the image both the weight gradient and the data gradient of conv i copy into LDS.  The
-    //    constants come from channel sums (the opening pass's for the closing and the downsample BatchNorm, the downstream data gradient's epilogue for the
-    //    others), finalized in the image pass's own prologue when the partial rows are few, by a launch of their own otherwise.
-    //    Streams: a weight gradient runs on the second stream behind an event of the launch stream; it reads dcimg[i] and aimg[i - 1] / x, none of which the
-    //    launch stream writes again inside this call, so the launch stream never waits for the second one here.
-    // partial convolutions: the gradient image of conv `slot` carries its renormalisation factor (d raw = d c * mult: partial_conv.py:53 and its autograd)
-    for (int i = 0; b->masked && i < b->nconv; ++i) P3D_REQUIRE(io->pix_in[i] && io->pix_out[i], "block_bwd: null per-pixel factor of partial convolution %d", i);
-    auto pixmul = [&](int slot) -> const float* { return (b->masked && slot != 3) ? io->pix_out[slot] : nullptr; };
-    auto bwd_map = [&](const float* gin, int slot, int masked, int kind, int rows, int which, double cnt, const unsigned char* front_mask = nullptr) -> int32_t {
-        const p3d_conv_desc* dc = &b->conv[slot];
-        P3D_REQUIRE(io->dcimg[slot], "block_bwd: null gradient image %d", slot);
-        if (kind == 3 || rows <= FX_FIN_MAX_ROWS) {
-            FxFinalize fin{};
-            fin.kind = kind; fin.partial = partial; fin.rows = rows; fin.which = which; fin.count = cnt; fin.gamma = io->gamma[slot];
-            fin.dgamma = io->dgamma[slot]; fin.dbeta = io->dbeta[slot]; fin.accumulate = acc; fin.table = io->table[slot];
-            fin.gmask = front_mask;
-            return fx_act_image(2, gin, io->c[slot], io->table[slot], masked, io->dcimg[slot], dc->N, dc->K, dc->Ho * dc->Wo, st, &fin, pixmul(slot));
-        }
-        hipLaunchKernelGGL(bn_finalize_bwd_kernel<false>, dim3((unsigned)ceil_div(dc->K, FIN_CH)), dim3(fin_threads(rows)), 0, st, (const void*)partial, rows, dc->K, cnt, 0,
-                           io->gamma[slot], io->dgamma[slot], io->dbeta[slot], acc, io->table[slot]);
-        return fx_act_image(2, gin, io->c[slot], io->table[slot], masked, io->dcimg[slot], dc->N, dc->K, dc->Ho * dc->Wo, st, nullptr, pixmul(slot));
-    };
-    // `ready`: the launch stream's position when the gradient image of this convolution was complete (the data gradient of the same layer has been queued on
-    // the launch stream since: it is the critical path and gets to the GPU first; the weight gradient only feeds the optimizer)
-    auto launch_wgrad = [&](int slot, const float* xin, const void* ximg, bool tapm, hipEvent_t ready) -> int32_t {
-        const p3d_conv_desc* d = &b->conv[slot];
-        if (two && (!ready || hipStreamWaitEvent(ss, ready, 0) != hipSuccess)) { set_error("block_bwd: event failure"); return P3D_ELAUNCH; }
-        ProfScope ps(2, d, ss);
-        fx_count(2, d);
-        FxFuse fw{};
-        fw.dy_img = io->dcimg[slot]; fw.x_img = ximg;
-        if (b->masked && slot != 3 && !ximg) fw.emask = io->pix_in[slot];      // the block input is fp32: x * mask_in in the kernel's split (an image carries it)
-        const int splits = fx_wgrad_splits(d, ximg != nullptr);
-        if (int32_t e = fx_conv_wgrad_slabs(d, nullptr, xin, (float*)side_workspace, splits, &fw, ss)) return e;
-        p3d_conv_desc dw_desc = *d;
-        dw_desc.accumulate = acc;
-        return wgrad_finish(&dw_desc, (float*)side_workspace, splits, tapm, io->dw[slot], ss);
-    };
-    // the two maps fed by the opening pass's sums (its partial buffer is overwritten by the first data gradient below): closing BatchNorm, downsample BatchNorm
-    if (b->has_downsample && fx_pair_map_enabled()) {
-        // both images in one pass: g (dout and the mask bytes) is read once
-        P3D_REQUIRE(io->dcimg[last] && io->dcimg[3], "block_bwd: null gradient image");
-        FxFinalize fa{}, fb{};
-        fa.kind = 3; fa.partial = partial; fa.rows = split; fa.which = 0; fa.count = cnt_last; fa.gamma = io->gamma[last]; fa.dgamma = io->dgamma[last];
-        fa.dbeta = io->dbeta[last]; fa.accumulate = acc; fa.table = io->table[last];
-        fb = fa; fb.which = 1; fb.gamma = io->gamma[3]; fb.dgamma = io->dgamma[3]; fb.dbeta = io->dbeta[3]; fb.table = io->table[3];
-        if (int32_t e = fx_act_image_pair(g, gmask, io->c[last], io->c[3], io->dcimg[last], io->dcimg[3], &fa, &fb, dl->N, dl->K, dl->Ho * dl->Wo, st, pixmul(last))) return e;
-    } else {
-        if (int32_t e = bwd_map(g, last, 0, 3, split, 0, cnt_last, gmask)) return e;
-        if (b->has_downsample)
-            if (int32_t e = bwd_map(g, 3, 0, 3, split, 1, cnt_last, gmask)) return e;
-    }
-    hipEvent_t ready = two ? mark_position(st) : nullptr;           // d c_last (and the downsample branch's gradient image) are complete
-    const hipEvent_t ready_ds = ready;
-    for (int i = last; i >= 0; --i) {
-        const p3d_conv_desc* d = &b->conv[i];
-        if (i > 0) P3D_REQUIRE(io->aimg[i - 1], "block_bwd: null activation image %d", i - 1);
-        // data gradient first (the chain the next layer waits for), then the weight gradient of the same layer on the second stream
-        FxFuse f{};
-        f.wimg = io->wimgT[i];
-        f.act_img = io->dcimg[i];
-        p3d_conv_desc dd = *d;
-        if (i > 0) {
-            const p3d_conv_desc* dp = &b->conv[i - 1];                       // producer of this conv's input
-            const bool epi = d->stride == 1;
-            if (epi) { f.partial = (float*)partial; f.ep_c = io->c[i - 1]; f.ep_tab = io->table[i - 1]; }
-            if (b->masked) f.emask = io->pix_in[i];            // dx = dgrad(d raw) * mask_in: the gradient w.r.t. a_{i-1}, of which the BatchNorm-backward sums are taken
-            dd.accumulate = 0;
-            P3D_REQUIRE(io->da[i - 1], "block_bwd: null gradient buffer %d", i - 1);
-            {
-                ProfScope ps(1, d, st);
-                fx_count(1, d);
-                if (int32_t e = fx_conv_dgrad(&dd, nullptr, io->w[i], io->da[i - 1], workspace, conv_ws, &f, st)) return e;
-            }
-            if (int32_t e = launch_wgrad(i, nullptr, io->aimg[i - 1], d->R * d->S > 1, ready)) return e;
-            const double cnt = (double)dp->N * dp->Ho * dp->Wo;
-            if (epi) {
-                if (int32_t e = bwd_map(io->da[i - 1], i - 1, 1, 2, fx_partial_rows_dgrad(d), 0, cnt)) return e;
-            } else {
-                const int sp = close_split(dp->N, dp->K);
-                hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(dp->K, sp), dim3(256), 0, st, (const float*)io->da[i - 1], (const float*)io->c[i - 1],
-                                   (const float*)io->table[i - 1], (double*)partial, dp->N, dp->K, dp->Ho * dp->Wo);
-                if (int32_t e = bwd_map(io->da[i - 1], i - 1, 1, 3, sp, 0, cnt)) return e;
-            }
-            ready = two ? mark_position(st) : nullptr;                      // d c_{i-1} is complete
-        } else {
-            if (b->need_dx) {
-            // block input: identity shortcut -> the gradient joins g's own buffer in place (dx = g + dgrad); downsample shortcut -> dx is written here and
-            // the downsample conv's dgrad adds to it below.  No weight-gradient kernel reads g (they read the images), so the launch stream does not wait.
-            float* dx;
-            if (b->masked) f.emask = io->pix_in[0];
-            if (b->has_downsample) { dx = io->dx; dd.accumulate = 0; }
-            else {
-                P3D_REQUIRE(b->relu_out, "block_bwd: an identity shortcut without the closing ReLU would overwrite the caller's gradient (not a reference block)");
-                P3D_REQUIRE(io->gbuf, "block_bwd: null gradient buffer (dx of an identity shortcut)");
-                dx = io->gbuf; dd.accumulate = 1;
-                if (!g_in_memory) { f.acc_src = io->dout; f.acc_mask = io->out_mask; }      // gbuf is written here for the first time
-            }
-            {
-                ProfScope ps(1, d, st);
-                fx_count(1, d);
-                if (int32_t e = fx_conv_dgrad(&dd, nullptr, io->w[0], dx, workspace, conv_ws, &f, st)) return e;
-            }
-            }
-            if (int32_t e = launch_wgrad(0, io->x, nullptr, d->R * d->S > 1, ready)) return e;
-        }
-    }
-    // 3. downsample branch: data gradient added onto dx, weight gradient (its gradient image was written with the closing BatchNorm's)
-    if (b->has_downsample) {
-        const p3d_conv_desc* d = &b->conv[3];
-        if (b->need_dx) {
-            FxFuse f{};
-            f.wimg = io->wimgT[3];
-            f.act_img = io->dcimg[3];
-            p3d_conv_desc dd = *d;
-            dd.accumulate = 1;
-            {
-                ProfScope ps(1, d, st);
-                fx_count(1, d);
-                if (int32_t e = fx_conv_dgrad(&dd, nullptr, io->w[3], io->dx, workspace, conv_ws, &f, st)) return e;
-            }
-        }
-        if (int32_t e = launch_wgrad(3, io->x, nullptr, false, ready_ds)) return e;
-    }
+    if (int32_t e = bwd_open(x)) return e;
+    if (int32_t e = bwd_open_images(x)) return e;
+    const hipEvent_t ready = x.two ? mark_position(x.st) : nullptr;       // d c_last (and the downsample branch's gradient image) are complete
+    if (int32_t e = bwd_chain(x, ready)) return e;
+    if (b->has_downsample)
+        if (int32_t e = bwd_downsample(x, ready)) return e;
     return check_launch("block_bwd");
 }
 
 // ---- the same block on the fp16 NHWC kernels (-half_acc): host-side fusion of the per-layer entry points into one call per block and direction -------------------
-static bool hblock_slot(const p3d_block_desc* b, int i) { return i < b->nconv || (i == 3 && b->has_downsample); }
 // BatchNorm sums in the conv epilogues (p3d_hconv2d_fwd_stats / p3d_hconv2d_dgrad_sums); p3d_hblock_fuse_sums(0): the stand-alone statistics / reduce passes (the
 // configuration in which the executor is bit-identical to the per-layer path)
 static int g_hblock_fused = 1;
@@ -699,7 +721,7 @@ int32_t p3d_hblock_workspace_bytes(const p3d_block_desc* b, size_t* main_bytes, 
     P3D_REQUIRE(b && (b->nconv == 2 || b->nconv == 3), "hblock: nconv must be 2 or 3");
     size_t mw = 0, sw = 0;
     for (int i = 0; i < 4; ++i) {
-        if (!hblock_slot(b, i)) continue;
+        if (!block_slot(b, i)) continue;
         const int kc = b->conv[i].K > b->conv[i].C ? b->conv[i].K : b->conv[i].C;
         const size_t a = hblock_rows(&b->conv[i]) * kc * 2 * sizeof(float) + (size_t)kc * 4 * sizeof(float), w = p3d_hconv2d_wgrad_workspace_bytes(&b->conv[i]);
         if (a > mw) mw = a;
@@ -714,7 +736,7 @@ int32_t p3d_hblock_fwd(const p3d_block_desc* b, const p3d_hblock_io* io, void* w
     P3D_REQUIRE(b && io && io->x && io->out && (b->nconv == 2 || b->nconv == 3), "hblock_fwd: bad argument");
     const int last = b->nconv - 1;
     for (int i = 0; i < 4; ++i)
-        if (hblock_slot(b, i)) P3D_REQUIRE(io->w_krsc[i] && io->c[i] && io->coef[i] && io->gamma[i] && io->beta[i] && (i == last || io->a[i]), "hblock_fwd: null tensor of conv %d", i);
+        if (block_slot(b, i)) P3D_REQUIRE(io->w_krsc[i] && io->c[i] && io->coef[i] && io->gamma[i] && io->beta[i] && (i == last || io->a[i]), "hblock_fwd: null tensor of conv %d", i);
     hipStream_t st = (hipStream_t)stream;
     const bool fused = hblock_fused();
     {
@@ -756,7 +778,7 @@ int32_t p3d_hblock_bwd(const p3d_block_desc* b, const p3d_hblock_io* io, void* w
     P3D_REQUIRE(b->relu_out, "hblock_bwd: blocks without the closing ReLU stay on the per-layer path");
     const int last = b->nconv - 1;
     for (int i = 0; i < 4; ++i)
-        if (hblock_slot(b, i)) P3D_REQUIRE(io->c[i] && io->coef[i] && io->dc[i] && io->dw[i] && io->dgamma[i] && io->dbeta[i] && (i == 0 || i == 3 || io->w_crsk[i]) && (i == last || i == 3 || io->da[i]),
+        if (block_slot(b, i)) P3D_REQUIRE(io->c[i] && io->coef[i] && io->dc[i] && io->dw[i] && io->dgamma[i] && io->dbeta[i] && (i == 0 || i == 3 || io->w_crsk[i]) && (i == last || i == 3 || io->da[i]),
                                            "hblock_bwd: null tensor of conv %d", i);
     P3D_REQUIRE(io->da[3] && (!b->need_dx || !b->has_downsample || (io->dx && io->w_crsk[0] && io->w_crsk[3])) && (!b->need_dx || b->has_downsample || io->w_crsk[0]), "hblock_bwd: null gradient buffer");
     hipStream_t st = (hipStream_t)stream, ss = side_stream ? (hipStream_t)side_stream : st;
@@ -865,8 +887,7 @@ size_t p3d_fx_conv_img_workspace_bytes(const p3d_conv_desc* d, int32_t pass) {
     if (!d) return 0;
     if (pass == 0) return fx_fwd_workspace(d);
     if (pass == 1) return fx_dgrad_workspace(d);
-    const int ns = fx_wgrad_splits(d, false) > fx_wgrad_splits(d, true) ? fx_wgrad_splits(d, false) : fx_wgrad_splits(d, true);
-    return (size_t)ns * d->K * d->C * d->R * d->S * sizeof(float);
+    return fx_wgrad_workspace(d);
 }
 
 // bit 0 / 1 / 2: the forward / data-gradient / weight-gradient pass of this convolution can run on image operands

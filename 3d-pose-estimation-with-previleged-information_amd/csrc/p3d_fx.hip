@@ -1760,6 +1760,10 @@ size_t fx_fwd_any_workspace(const p3d_conv_desc* d) { return fx_plan(d, false, t
 size_t fx_dgrad_workspace(const p3d_conv_desc* d) { return fx_plan(d, true).workspace; }
 int fx_partial_rows_fwd(const p3d_conv_desc* d) { return fx_plan(d, false).partial_rows; }
 int fx_partial_rows_dgrad(const p3d_conv_desc* d) { return fx_plan(d, true).partial_rows; }
+size_t fx_wgrad_workspace(const p3d_conv_desc* d) {
+    const int a = fx_wgrad_splits(d, false), b = fx_wgrad_splits(d, true);
+    return (size_t)(a > b ? a : b) * d->K * d->C * d->R * d->S * sizeof(float);
+}
 
 // Pre-split weight images of one conv weight w [K][C][R*S] (fp32): blockIdx.y = 0 the forward image (rows = output channels, reduction = input channels),
 // 1 the data-gradient image (rows = input channels, reduction = output channels); a null image pointer skips that direction.  One thread per 16-B chunk

@@ -80,9 +80,12 @@ class _Plan:
             m, s = ctypes.c_size_t(), ctypes.c_size_t()
             check(lib().p3d_block_workspace_bytes(ctypes.byref(d), ctypes.byref(m), ctypes.byref(s)), 'p3d_block_workspace_bytes')
             self.main_bytes, self.side_bytes = m.value, s.value
-        ks = [self.shapes[slot][1] for slot, _, _ in _layers(block)]
-        self.table_rows = sum(ks)
         self.slots = [slot for slot, _, _ in _layers(block)]
+        # one table for the block's BatchNorm layers, [K_slot][8] floats each, in slot order
+        self.table_offset, self.table_rows = {}, 0
+        for slot in self.slots:
+            self.table_offset[slot] = self.table_rows * 32
+            self.table_rows += self.shapes[slot][1]
         self.sets = []                  # _Buffers owned by this plan (see there)
 
 
@@ -347,6 +350,21 @@ def usable(block, x, veil=None):
     return plan_for(block, x, masked).ok
 
 
+def _fill_io(io, plan, bufs, layers, images_index):
+    """What both directions hand to the executor per slot: weights, their images for this direction (weight_images()[images_index]: 0 forward -> wimg,
+    1 data gradient -> wimgT), the plan-owned conv outputs, activation images and tables, and the BatchNorm's affine parameters."""
+    wimg = io.wimgT if images_index else io.wimg
+    for slot, conv, bn in layers:
+        io.w[slot], io.c[slot] = conv.weight.data_ptr(), bufs.c[slot].data_ptr()
+        wimg[slot] = weight_images(conv)[images_index].data_ptr()
+        if slot in bufs.act:
+            io.aimg[slot] = bufs.act[slot].data_ptr()
+        io.table[slot] = bufs.tables.data_ptr() + plan.table_offset[slot]
+        io.gamma[slot], io.beta[slot] = bn.weight.data_ptr(), bn.bias.data_ptr()
+    if bufs.mask is not None:
+        io.out_mask = bufs.mask.data_ptr()
+
+
 class ResidualBlockFn(torch.autograd.Function):
 
     @staticmethod
@@ -361,9 +379,6 @@ class ResidualBlockFn(torch.autograd.Function):
         io.out = out.data_ptr()
         bufs = _free_set(plan.sets, x.device, lambda: _Buffers(plan, x.device))
         lease = _Lease(bufs)
-        tables, cs, acts, row = bufs.tables, bufs.c, bufs.act, 0
-        if bufs.mask is not None:
-            io.out_mask = bufs.mask.data_ptr()
         # partial convolutions: the veil chain of the block (partial_conv.py:35-43, one tiny box-sum kernel per conv) gives every conv its two per-pixel factors
         pix = None
         veil_out = None
@@ -380,14 +395,8 @@ class ResidualBlockFn(torch.autograd.Function):
                     v = v_next
             veil_out = v
         ctx.pix = pix
-        for slot, conv, bn in layers:
-            io.w[slot], io.c[slot] = conv.weight.data_ptr(), cs[slot].data_ptr()
-            io.wimg[slot] = weight_images(conv)[0].data_ptr()
-            if slot in acts:
-                io.aimg[slot] = acts[slot].data_ptr()
-            io.table[slot] = tables.data_ptr() + row * 32
-            row += plan.shapes[slot][1]
-            io.gamma[slot], io.beta[slot] = bn.weight.data_ptr(), bn.bias.data_ptr()
+        _fill_io(io, plan, bufs, layers, 0)
+        for slot, _, bn in layers:
             io.running_mean[slot], io.running_var[slot] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
             if getattr(bn, '_ticked', False):             # counted by the network's pre-hook (_trunk._tick_batchnorm)
                 bn._ticked = False
@@ -412,7 +421,6 @@ class ResidualBlockFn(torch.autograd.Function):
                            'releases its saved activations after the first backward; run the forward again')
         lease, bufs = ctx.saved
         ctx.saved = None
-        cs, tables, acts = bufs.c, bufs.tables, bufs.act
         layers = _layers(block)
         L = lib()
         dout = dout.contiguous()
@@ -424,20 +432,10 @@ class ResidualBlockFn(torch.autograd.Function):
         grads = ops._GradOut(*[p for _, _, p in params])
         io = BlockIO()
         io.x, io.out, io.dout = x.data_ptr(), out.data_ptr(), dout.data_ptr()
-        if bufs.mask is not None:
-            io.out_mask = bufs.mask.data_ptr()
         if ctx.pix is not None:
             for slot, (v, mult) in ctx.pix.items():
                 io.pix_in[slot], io.pix_out[slot] = v.data_ptr(), mult.data_ptr()
-        row = 0
-        for slot, conv, bn in layers:
-            io.w[slot], io.c[slot] = conv.weight.data_ptr(), cs[slot].data_ptr()
-            io.wimgT[slot] = weight_images(conv)[1].data_ptr()
-            if slot in acts:
-                io.aimg[slot] = acts[slot].data_ptr()
-            io.table[slot] = tables.data_ptr() + row * 32
-            row += plan.shapes[slot][1]
-            io.gamma[slot], io.beta[slot] = bn.weight.data_ptr(), bn.bias.data_ptr()
+        _fill_io(io, plan, bufs, layers, 1)
         for (slot, kind, _), g in zip(params, grads.bufs):
             getattr(io, kind)[slot] = g.data_ptr()
         dcimg, da, gbuf = bufs.backward_scratch(plan)

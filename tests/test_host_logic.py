@@ -356,3 +356,35 @@ def test_block_io_mirror_has_the_size_the_executor_asserts(pkg):
     assert ctypes.sizeof(pkg.ops_block.BlockIO) == 592 == 74 * ctypes.sizeof(ctypes.c_void_p)
     with open(os.path.join(os.path.dirname(pkg.__file__), 'csrc', 'p3d_block.hip')) as f:
         assert 'static_assert(sizeof(p3d_block_io) == 592,' in f.read()
+
+
+def test_block_admission_and_workspace_queries_agree(pkg):
+    """One admission predicate and one workspace layout behind the block executor's queries (csrc/p3d_block.hip: block_refusal, block_layout): over the block kinds
+    of tests/geometry_table.py on its maps, dense and masked, p3d_block_supported says 1 exactly when p3d_block_workspace_bytes answers P3D_OK; both workspaces are
+    whole 256-byte units; and the side workspace holds the weight-gradient slabs p3d_fx_conv_img_workspace_bytes(d, 2) asks for, for every convolution of the block
+    (fx_wgrad_workspace is the one formula behind both)."""
+    import ctypes
+    import geometry_table as T
+    from test_geometry_host import _block
+    L = pkg._lib.lib()
+    verdicts = set()
+    for kind, inplanes, planes, stride, dil, with_ds in T.BLOCKS:
+        block = _block(pkg, kind, inplanes, planes, stride, dil, with_ds)
+        for h, w in T.BLOCK_MAPS:
+            for n in (1, 3):
+                for masked in (0, 1):
+                    plan = pkg.ops_block._Plan(block, (n, inplanes, h, w), masked=bool(masked))
+                    d = plan.desc
+                    assert d.masked == masked
+                    main, side = ctypes.c_size_t(), ctypes.c_size_t()
+                    supported = L.p3d_block_supported(ctypes.byref(d))
+                    rc = L.p3d_block_workspace_bytes(ctypes.byref(d), ctypes.byref(main), ctypes.byref(side))
+                    case = (kind, inplanes, planes, stride, dil, h, w, n, masked)
+                    assert supported in (0, 1) and (supported == 1) == (rc == 0), case
+                    verdicts.add(supported)
+                    if not supported:
+                        continue
+                    assert main.value > 0 and main.value % 256 == 0 and side.value > 0 and side.value % 256 == 0, case
+                    for slot in plan.slots:
+                        assert L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d.conv[slot]), 2) <= side.value, case + (slot,)
+    assert verdicts == {0, 1}                   # the table reaches both answers

@@ -357,11 +357,19 @@ def _smallest_per_geometry(cases):
 BLOCK_IDS = lambda c: '%s_c%d_p%d_s%d_d%d_n%d_h%d%s' % (c[0], c[1], c[2], c[3], c[4], c[5], c[6], '_ds' if c[7] else '')
 
 
+# The split-K layout of the main workspace (the slabs lie inside the conv scratch, the partial rows are image groups), which the built-in plan never reaches on the
+# small cases: an identity and a downsample block under forced forward / data-gradient splits.  (Masked blocks have unsplit instances only.)
+SPLITK_BLOCKS = _rows(tb.CASES, [('bottleneck', 512, 128, 1, 1, 4, 16, False), ('bottleneck', 128, 128, 1, 1, 3, 32, True)])
+EXECUTOR_CASES = [c + (None,) for c in _smallest_per_geometry(tb.CASES)] + [c + ((1, splits),) for c in SPLITK_BLOCKS for splits in (2, 3)]
+
+
 @needs_blocks
-@pytest.mark.parametrize('case', _smallest_per_geometry(tb.CASES), ids=BLOCK_IDS)
+@pytest.mark.parametrize('case', EXECUTOR_CASES, ids=lambda c: BLOCK_IDS(c) + ('_tune%d_%d' % c[8] if c[8] else ''))
 def test_block_executor(pkg, fenced_scratch, case):
     """p3d_block_fwd / p3d_block_bwd on their main and side workspaces, and the per-layer path beside them"""
-    fenced_then_plain(fenced_scratch, lambda: tb.fused_block_case(pkg, *case), [(tb, 'rel'), (tb, 'rel2')])
+    hook = case[8]
+    with (_tune(pkg, *hook) if hook else contextlib.nullcontext()):
+        fenced_then_plain(fenced_scratch, lambda: tb.fused_block_case(pkg, *case[:8]), [(tb, 'rel'), (tb, 'rel2')])
 
 
 @needs_blocks
