@@ -130,6 +130,10 @@ SIGNATURES = {
     'p3d_probe_hw_ids': (_i32, [ctypes.c_void_p, ctypes.c_void_p, _i32, _i32]),
     'p3d_stream_destroy': (_i32, [ctypes.c_void_p]),
     'p3d_x3_enable': (_i32, [_i32]),
+    'p3d_x3_any_enable': (_i32, [_i32]),
+    'p3d_conv2d_fwd_any_supported': (_i32, [_desc]),
+    'p3d_conv2d_dgrad_any_supported': (_i32, [_desc]),
+    'p3d_conv2d_wgrad_any_supported': (_i32, [_desc]),
     'p3d_fx_tune': (None, [_i32, _i32]),
     'p3d_conv_path_stats': (None, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), _i32]),
     'p3d_reproject_crops': (_i32, [_ptr, _i32, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _ptr]),

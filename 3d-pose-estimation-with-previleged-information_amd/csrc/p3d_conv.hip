@@ -1166,11 +1166,22 @@ static FwdPlan plan_fwd(const p3d_conv_desc* d, bool masked, bool allow_split) {
     return pl;
 }
 
+// p3d_x3_any_enable: what the ragged instances take from the per-layer entries -- a dense convolution with whole weights (no channel window) that the aligned predicate
+// of the pass refuses.  The *_any_ok forms do not look at the switch (the public p3d_conv2d_*_any_supported queries).
+static bool whole_weight(const p3d_conv_desc* d) { return d->c_offset == 0 && d->c_total == d->C; }
+static bool fwd_any_ok(const p3d_conv_desc* d) { return whole_weight(d) && fx_fwd_any_applies(d); }
+static bool dgrad_any_ok(const p3d_conv_desc* d) { return whole_weight(d) && fx_dgrad_any_applies(d); }
+static bool wgrad_any_ok(const p3d_conv_desc* d) { return whole_weight(d) && fx_wgrad_any_applies(d); }
+static bool fwd_ragged(const p3d_conv_desc* d) { return fx_any_enabled() && !fx_fwd_applies(d) && fwd_any_ok(d); }
+static bool dgrad_ragged(const p3d_conv_desc* d) { return fx_any_enabled() && !fx_dgrad_applies(d) && dgrad_any_ok(d); }
+static bool wgrad_ragged(const p3d_conv_desc* d) { return fx_any_enabled() && !fx_wgrad_applies(d) && wgrad_any_ok(d); }
+
 size_t p3d_conv2d_fwd_workspace_bytes(const p3d_conv_desc* d) {
     if (validate(d)) return 0;
     const FwdPlan pl = plan_fwd(d, false, true);
     const size_t base = weight_image_bytes(d) + (pl.splits > 1 ? (size_t)pl.splits * d->N * d->K * d->Ho * d->Wo * sizeof(float) : 0);
-    const size_t fx = (fx_fwd_applies(d) || fx_fwd_masked_applies(d)) ? fx_fwd_workspace(d) : 0;
+    size_t fx = (fx_fwd_applies(d) || fx_fwd_masked_applies(d)) ? fx_fwd_workspace(d) : 0;
+    if (fwd_ragged(d) && fx_fwd_any_workspace(d) > fx) fx = fx_fwd_any_workspace(d);
     return base > fx ? base : fx;
 }
 
@@ -1183,6 +1194,13 @@ static int32_t conv2d_fwd_impl(const p3d_conv_desc* d, const float* x, const flo
         ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0) {
         fx_count(0, d);          // exact fp32 on the bf16 matrix pipe (p3d_fx.hip), the default path of the dense layers
         return fx_conv_fwd(d, x, w, bias, y, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+    }
+    if (!mask_in && !mult && !ep_scale && !ep_res && !ep_relu && fwd_ragged(d) && workspace_bytes >= fx_fwd_any_workspace(d) &&
+        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0) {
+        fx_count(0, d);          // the same arithmetic at a map width that is no multiple of 4: the ragged instances (p3d_x3_any_enable)
+        FxFuse f{};
+        f.ragged = 1;
+        return fx_conv_fwd(d, x, w, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
     }
     if (mask_in && mult && !bias && !ep_scale && !ep_res && !ep_relu && fx_enabled() && fx_fwd_masked_applies(d) && workspace_bytes >= fx_fwd_workspace(d) &&
         ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(workspace) |
@@ -1291,7 +1309,8 @@ size_t p3d_conv2d_dgrad_workspace_bytes(const p3d_conv_desc* d) {
     if (d->stride == 1) {
         const FwdPlan pl = plan_dgrad1(d, false);
         const size_t base = weight_image_bytes(d) + (pl.splits > 1 ? (size_t)pl.splits * d->N * d->C * d->H * d->W * sizeof(float) : 0);
-        const size_t fx = (fx_dgrad_applies(d) || fx_dgrad_masked_applies(d)) ? fx_dgrad_workspace(d) : 0;
+        size_t fx = (fx_dgrad_applies(d) || fx_dgrad_masked_applies(d)) ? fx_dgrad_workspace(d) : 0;
+        if (dgrad_ragged(d) && fx_dgrad_any_workspace(d) > fx) fx = fx_dgrad_any_workspace(d);
         return base > fx ? base : fx;
     }
     const size_t hc = (size_t)ceil_div(d->H, d->stride), wc = (size_t)ceil_div(d->W, d->stride);
@@ -1311,6 +1330,13 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
         if (fx_dgrad_has_dead_classes(d) && !d->accumulate)          // input pixels no tap reaches (1x1, stride 2) must read zero
             (void)hipMemsetAsync(dx, 0, (size_t)d->N * d->C * d->H * d->W * sizeof(float), (hipStream_t)stream);
         return fx_conv_dgrad(d, dy, w, dx, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+    }
+    if (!mask_in && !mult && dgrad_ragged(d) && workspace_bytes >= fx_dgrad_any_workspace(d) &&
+        ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0) {
+        fx_count(1, d);          // stride 1 at any map width: the ragged forward instances over dy (p3d_x3_any_enable)
+        FxFuse f{};
+        f.ragged = 1;
+        return fx_conv_dgrad(d, dy, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream);
     }
     if (mask_in && mult && fx_enabled() && fx_dgrad_masked_applies(d) && workspace_bytes >= fx_dgrad_workspace(d) &&
         ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(workspace) |
@@ -1396,6 +1422,7 @@ size_t p3d_conv2d_wgrad_workspace_bytes(const p3d_conv_desc* d) {
     const WgradPlan a = plan_wgrad(d, false), b = plan_wgrad(d, true);
     int splits = a.splits > b.splits ? a.splits : b.splits;
     if (fx_wgrad_applies(d) && fx_wgrad_splits(d) > splits) splits = fx_wgrad_splits(d);
+    if (wgrad_ragged(d) && fx_wgrad_splits(d, false, true) > splits) splits = fx_wgrad_splits(d, false, true);
     return (size_t)splits * d->K * d->C * d->R * d->S * sizeof(float);
 }
 
@@ -1409,8 +1436,10 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
     const bool fxm = mask_in && mult && fx_enabled() && fx_wgrad_masked_applies(d) &&
                      ((reinterpret_cast<uintptr_t>(mask_in) | reinterpret_cast<uintptr_t>(mult)) & 15) == 0;          // partial convolution: dy * mult, x * mask_in in the fetch
     const bool fx = (!masked || fxm) && fx_wgrad_applies(d) && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0;
-    if (fx) { pl.splits = fx_wgrad_splits(d); pl.tapm = d->R * d->S > 1; }      // slabs [split][k][tap][c]: the tap-major columns of wgrad_reduce_tapm_kernel
-    fx_count(fx ? 2 : 5, d);
+    // any map width (p3d_x3_any_enable): the same slabs from fx_wgrad_any_kernel
+    const bool fxr = !fx && !masked && wgrad_ragged(d) && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0;
+    if (fx || fxr) { pl.splits = fx_wgrad_splits(d, false, fxr); pl.tapm = d->R * d->S > 1; }      // slabs [split][k][tap][c]: the tap-major columns of wgrad_reduce_tapm_kernel
+    fx_count(fx || fxr ? 2 : 5, d);
     const size_t need = (size_t)pl.splits * d->K * d->C * d->R * d->S * sizeof(float);
     if (!workspace || workspace_bytes < need) {
         set_error("conv2d_wgrad: workspace %zu B < required %zu B", workspace_bytes, need);
@@ -1437,12 +1466,22 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
         f.pmask = mult; f.emask = mask_in;
         if (int32_t e = fx_conv_wgrad_slabs(d, dy, x, (float*)workspace, pl.splits, masked ? &f : nullptr, (hipStream_t)stream)) return e;
     }
+    else if (fxr) {
+        FxFuse f{};
+        f.ragged = 1;
+        if (int32_t e = fx_conv_wgrad_slabs(d, dy, x, (float*)workspace, pl.splits, &f, (hipStream_t)stream)) return e;
+    }
     else launch_igemm<MODE_WGRAD>(pl.cfg, pl.tapm, masked, p, pl.splits, (hipStream_t)stream, wv);
     if (int32_t e = check_launch("conv2d_wgrad")) return e;
     return wgrad_finish(d, (float*)workspace, pl.splits, pl.tapm, dw, (hipStream_t)stream);
 }
 
 int32_t p3d_x3_enable(int32_t on) { return fx_set_enabled(on); }
+int32_t p3d_x3_any_enable(int32_t on) { return fx_set_any_enabled(on); }
+// what the ragged instances admit, whatever the switch says
+int32_t p3d_conv2d_fwd_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && fwd_any_ok(d) ? 1 : 0; }
+int32_t p3d_conv2d_dgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && dgrad_any_ok(d) ? 1 : 0; }
+int32_t p3d_conv2d_wgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && wgrad_any_ok(d) ? 1 : 0; }
 void p3d_fx_tune(int32_t what, int32_t value) { fx_tune(what, value); }
 
 void p3d_conv_path_stats(uint64_t* counts, double* flops, int32_t reset) {

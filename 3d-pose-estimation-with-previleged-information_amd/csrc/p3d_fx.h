@@ -78,6 +78,8 @@ struct FxFuse {
     int infer;              // 1; 2: on the ragged instances (any map width; fp32 operand, dense; a partial convolution with pmask and emask)
     const float* res;
     int relu;
+    int ragged;             // 1: FWD / DGRAD (stride 1) on the ragged instances with the plain epilogue, WGRAD on fx_wgrad_any_kernel: dense fp32-fed training launches at any
+                            // map width (p3d_x3_any_enable); no other field set
 };
 constexpr int FX_TAB = 8;   // floats per channel of a table
 
@@ -115,12 +117,16 @@ void prof_kernel_done(hipStream_t st);
 bool fx_enabled();
 void fx_tune(int what, int value);
 int fx_set_enabled(int on);
+bool fx_any_enabled();                  // p3d_x3_any_enable / P3D_X3_ANY=1 (default off): the per-layer training entries use the ragged instances where the aligned predicates refuse
+int fx_set_any_enabled(int on);
 void fx_count(int kind, const p3d_conv_desc* d);
 void fx_stats(unsigned long long* counts, double* flops, int reset);
 bool fx_fwd_applies(const p3d_conv_desc* d, int min_m = 96);
 bool fx_fwd_any_applies(const p3d_conv_desc* d, int min_m = 96);       // the ragged forward: fx_fwd_applies without W % 4 == 0 and Wo % 4 == 0 (FxFuse::infer == 2)
 bool fx_dgrad_applies(const p3d_conv_desc* d, int min_m = 96);
 bool fx_wgrad_applies(const p3d_conv_desc* d, int min_m = 96);
+bool fx_dgrad_any_applies(const p3d_conv_desc* d, int min_m = 96);     // the ragged data gradient: stride 1, without Wo % 4 == 0 and W % 4 == 0 (FxFuse::ragged)
+bool fx_wgrad_any_applies(const p3d_conv_desc* d, int min_m = 96);     // the ragged weight gradient: without (Ho Wo) % 16 == 0, Wo % 4 == 0 and W % 4 == 0 (FxFuse::ragged)
 bool fx_dgrad_has_dead_classes(const p3d_conv_desc* d);
 bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d);      // stride 1 and no split-K: FxFuse::acc_src is honoured
 bool fx_fwd_masked_applies(const p3d_conv_desc* d);          // partial convolutions: the masked instances exist for unsplit launches without bias
@@ -130,9 +136,10 @@ bool fx_wgrad_masked_applies(const p3d_conv_desc* d);
 size_t fx_fwd_workspace(const p3d_conv_desc* d);
 size_t fx_fwd_any_workspace(const p3d_conv_desc* d);
 size_t fx_dgrad_workspace(const p3d_conv_desc* d);
+size_t fx_dgrad_any_workspace(const p3d_conv_desc* d);
 int fx_partial_rows_fwd(const p3d_conv_desc* d);
 int fx_partial_rows_dgrad(const p3d_conv_desc* d);
-int fx_wgrad_splits(const p3d_conv_desc* d, bool images = false);      // images: dy AND x arrive as images (the slab count of fx_wgrad_two_taps layers differs)
+int fx_wgrad_splits(const p3d_conv_desc* d, bool images = false, bool ragged = false);      // images: dy AND x arrive as images (the slab count of fx_wgrad_two_taps layers differs)
 size_t fx_wgrad_workspace(const p3d_conv_desc* d);       // slab bytes for the larger of the two split counts (fp32- or image-fed x): what a caller reserves before it knows which
 int fx_wgrad_two_taps(const p3d_conv_desc* d, bool images);      // taps per column tile: 0 (one-tap tiles), 2 or 3
 int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, const float* bias, float* y, void* workspace, size_t workspace_bytes,

@@ -1285,6 +1285,176 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
         }
 }
 
+// The ragged weight gradient (p3d_x3_any_enable): fx_wgrad_kernel<false, false, false> -- both operands fp32 NCHW, unmasked, one tap per block -- without
+// OHW % 16 == 0, OW % 4 == 0 and Wi % 4 == 0.  The reduction index stays the flat pixel n OHW + oh OW + ow in K steps of 16 (the columns of the ragged forward), slabs cut it
+// at multiples of 16, so a step may straddle two images, a thread's four pixels an output row or an image, and the last step of the last slab may run beyond N OHW.
+// A thread keeps its FIRST pixel as (output row, output column, flat index, element offsets of its rows in dy's and x's image); every fetch steps four pixels from it
+// through row ends and image ends (the walk of fx_conv_kernel's RAG set_tap) into eight independent byte offsets, each with the out-of-range bit for padding and for
+// pixels at or beyond N OHW -- those contribute exact zero through BOTH operands, and the resources keep the tensors' exact sizes -- then moves 16 pixels on
+// (16 = di images + dr rows + dc columns, one conditional carry each: no division and no loop in the K loop).  Every fetch is a dword load: with OHW odd a channel's run of
+// dy is only 4-B aligned.  LDS images, the pixel permutation of the stores, block order, partial tiles and the slab layout are fx_wgrad_kernel's.
+// (A kernel of its own rather than a fifth template axis of fx_wgrad_kernel: none of that kernel's image-fed / masked / multi-tap branches applies, and its
+// instances keep their symbols and their code.)
+__global__ __launch_bounds__(256, 3) void fx_wgrad_any_kernel(const FxWgradParams p) {
+    __shared__ __attribute__((aligned(16))) unsigned char As[2 * 3 * FX_PIECE];
+    __shared__ __attribute__((aligned(16))) unsigned char Bs[2 * 3 * FX_PIECE];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
+    int bx, by, bz;              // the XCD block order of fx_wgrad_kernel
+    {
+        const int gx = gridDim.x, gy = gridDim.y, nwg = gx * gy * gridDim.z;
+        const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+        const int q = nwg >> 3, r = nwg & 7, xcd = lin & 7, idx = lin >> 3;
+        const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        if (p.order == 0) {
+            bx = bid % gx;
+            const int rest = bid / gx;
+            by = rest % gy;
+            bz = rest / gy;
+        } else {
+            const int nt = p.R * p.S;
+            const int tp = bid % nt;
+            int rest = bid / nt;
+            by = rest % gy; rest /= gy;
+            bx = rest % gx;
+            bz = (rest / gx) * nt + tp;
+        }
+    }
+    const int m0 = by * FX_BM, n0 = bx * FX_BN;
+    const int ntaps = p.R * p.S;
+    const int split = bz / ntaps, tap = bz - split * ntaps;
+    const int tr = tap / p.S, ts = tap - tr * p.S;
+    const int dh = tr * p.dil - p.pad, dw = ts * p.dil - p.pad;             // input coordinate = output coordinate * stride + (dh, dw)
+    const int OHW = p.OH * p.OW, HWi = p.Hi * p.Wi, NP = p.N * OHW;
+    const int total = (NP + FX_BK - 1) / FX_BK;                              // the last K step may hold fewer than 16 pixels
+    const int s0 = split * p.spb, s1 = (s0 + p.spb < total) ? s0 + p.spb : total;
+    const int nk = s1 > s0 ? s1 - s0 : 0;                                    // (a slab beyond the range writes zeros)
+    const int row = t >> 2, kq = t & 3;                                      // rows row, row + 64 of the tile, pixels 4 kq .. 4 kq + 3 of the step
+    const int a_bad[2] = {m0 + row < p.K ? 0 : FX_OOB, m0 + row + 64 < p.K ? 0 : FX_OOB}, b_bad[2] = {n0 + row < p.C ? 0 : FX_OOB, n0 + row + 64 < p.C ? 0 : FX_OOB};
+    const i32x4 rA = fx_rsrc(p.DY, (size_t)p.N * p.K * OHW * sizeof(float));
+    const i32x4 rB = fx_rsrc(p.X, (size_t)p.N * p.C * HWi * sizeof(float));
+    const int a_so = 64 * OHW * 4, b_so = 64 * HWi * 4;                      // the second row (wave-uniform; the per-pixel image offsets live in the thread's offsets)
+    const int a_nimg = p.K * OHW, b_nimg = p.C * HWi;                        // elements per image
+    const int di = FX_BK / OHW, dr = (FX_BK - di * OHW) / p.OW, dc = FX_BK - di * OHW - dr * p.OW;
+    int f_q = s0 * FX_BK + 4 * kq, f_oh, f_ow, f_a, f_b;
+    {
+        const int qc = f_q < NP ? f_q : 0;               // (a thread that starts beyond the end stays beyond it: its position is never used)
+        const int n = qc / OHW, rem = qc - n * OHW;
+        f_oh = rem / p.OW; f_ow = rem - f_oh * p.OW;
+        f_a = (n * p.K + m0 + row) * OHW; f_b = (n * p.C + n0 + row) * HWi;
+    }
+    f32x4 ra[2], rb[2];
+    auto fetch = [&]() {
+        int a_voff[4], b_voff[4];
+        int oh = f_oh, ow = f_ow, ia = f_a, ib = f_b;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool ok = f_q + e < NP;
+            const int hi = oh * p.stride + dh, wi = ow * p.stride + dw;
+            a_voff[e] = ok ? (ia + oh * p.OW + ow) * 4 : FX_OOB;
+            b_voff[e] = (ok && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi) ? (ib + hi * p.Wi + wi) * 4 : FX_OOB;
+            if (++ow == p.OW) { ow = 0; if (++oh == p.OH) { oh = 0; ia += a_nimg; ib += b_nimg; } }      // the next flat pixel: next row, next image
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                ra[i][e] = fx_buffer_load_f32(rA, a_voff[e] | a_bad[i], i * a_so, 0);
+                rb[i][e] = fx_buffer_load_f32(rB, b_voff[e] | b_bad[i], i * b_so, 0);
+            }
+        // the thread's first pixel of the next K step
+        f_q += FX_BK;
+        f_ow += dc;
+        if (f_ow >= p.OW) { f_ow -= p.OW; ++f_oh; }
+        f_oh += dr;
+        int carry = di;
+        if (f_oh >= p.OH) { f_oh -= p.OH; ++carry; }
+        f_a += carry * a_nimg; f_b += carry * b_nimg;
+    };
+    const int st_off[2] = {fx_rc_off(row, kq >> 1) + 8 * (kq & 1), fx_rc_off(row + 64, kq >> 1) + 8 * (kq & 1)};
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            fx_split_store(As + buf * 3 * FX_PIECE + st_off[i], ra[i]);
+            fx_split_store(Bs + buf * 3 * FX_PIECE + st_off[i], rb[i]);
+        }
+    };
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    const int fr = lane & 31, fh = lane >> 5;
+    int rd_a[2], rd_b[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        rd_a[a] = fx_rc_off(wm * 64 + a * 32 + fr, fh);
+        rd_b[a] = fx_rc_off(wn * 64 + a * 32 + fr, fh);
+    }
+    const int live_a = fx_live_subtiles(m0 + wm * 64, p.K), live_b = fx_live_subtiles(n0 + wn * 64, p.C);
+    if (nk > 0) { fetch(); stage(0); if (nk > 1) fetch(); }       // the software pipeline of fx_wgrad_kernel
+    __syncthreads();
+    auto kloop = [&](auto nat, auto nbt) {
+        constexpr int NA = decltype(nat)::value, NB = decltype(nbt)::value;
+        constexpr bool LIVE = NA > 0 && NB > 0;
+        auto step = [&](int kt, auto st, auto fe) {
+            const int buf = kt & 1;
+            bf8 af[3][2], bf[3][2];
+            auto read_a = [&](int pc) {
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+                    if (a < NA) af[pc][a] = *reinterpret_cast<const bf8*>(As + (buf * 3 + pc) * FX_PIECE + rd_a[a]);
+            };
+            auto read_b = [&](int pc) {
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+                    if (a < NB) bf[pc][a] = *reinterpret_cast<const bf8*>(Bs + (buf * 3 + pc) * FX_PIECE + rd_b[a]);
+            };
+            if constexpr (LIVE) {
+                read_a(2); read_b(0); read_a(0); read_b(2);
+                __builtin_amdgcn_sched_barrier(0);
+                P3D_FX_PRODUCTS_RANGE(acc, af, bf, NA, NB, 0, 1)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if constexpr (decltype(st)::value) stage(buf ^ 1);
+            if constexpr (decltype(fe)::value) fetch();
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (LIVE) {
+                read_a(1); read_b(1);
+                P3D_FX_PRODUCTS_RANGE(acc, af, bf, NA, NB, 1, 6)
+            }
+            __syncthreads();
+        };
+        int kt = 0;
+        for (; kt + 2 < nk; ++kt) step(kt, std::true_type{}, std::true_type{});
+        if (kt + 1 < nk) { step(kt, std::true_type{}, std::false_type{}); ++kt; }
+        if (kt < nk) step(kt, std::false_type{}, std::false_type{});
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    if (live_a == 0 || live_b == 0) kloop(I0{}, I0{});
+    else if (live_a == 2 && live_b == 2) kloop(I2{}, I2{});
+    else if (live_a == 1 && live_b == 2) kloop(I1{}, I2{});
+    else if (live_a == 2 && live_b == 1) kloop(I2{}, I1{});
+    else kloop(I1{}, I1{});
+    // C/D layout: col = lane & 31 (input channel c, contiguous in the slab), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (output channel k)
+    float* out = p.slabs + (size_t)split * p.K * p.C * ntaps;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int c = n0 + wn * 64 + b * 32 + fr;
+            if (c >= p.C) continue;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int k = m0 + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                if (k < p.K) out[((size_t)k * ntaps + tap) * p.C + c] = acc[a][b][r];
+            }
+        }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // Activation images: fp32 NCHW [N][C][HW] -> three bf16 planes [N][C/16][HW][16], optionally through the BatchNorm + ReLU of the forward pass (MODE 1) or
 // the BatchNorm-backward map (MODE 2) of the layer the tensor belongs to (depthnet.py:98-116: out = relu(bn(conv(x))) and its autograd).
@@ -1576,6 +1746,13 @@ bool fx_enabled() {
     return g_fx == 1;
 }
 int fx_set_enabled(int on) { const int before = fx_enabled() ? 1 : 0; g_fx = on ? 1 : 0; return before; }
+// p3d_x3_any_enable: the per-layer training entries (p3d_conv2d_fwd / _dgrad / _wgrad) offer dense convolutions the aligned predicates refuse to the ragged instances
+static int g_fx_any = -1;
+bool fx_any_enabled() {
+    if (g_fx_any < 0) { const char* e = getenv("P3D_X3_ANY"); g_fx_any = (e && atoi(e) == 1) ? 1 : 0; }      // default OFF
+    return g_fx_any == 1;
+}
+int fx_set_any_enabled(int on) { const int before = fx_any_enabled() ? 1 : 0; g_fx_any = on ? 1 : 0; return before; }
 
 // coverage counters (launches routed here vs to the fp32-MFMA kernel), read by bench.py so that no fallback goes uncounted
 static std::mutex g_fx_count_mu;
@@ -1615,6 +1792,16 @@ bool fx_dgrad_applies(const p3d_conv_desc* d, int min_m) {
 bool fx_wgrad_applies(const p3d_conv_desc* d, int min_m) {
     if ((int64_t)d->N * d->C * d->H * d->W >= (1ll << 29) || (int64_t)d->N * d->K * d->Ho * d->Wo >= (1ll << 29)) return false;      // 32-bit byte offsets into whole tensors
     return fx_common(d) && d->K >= min_m && d->C >= min_m && (d->Ho * d->Wo) % FX_BK == 0 && d->Wo % 4 == 0 && d->W % 4 == 0 && (d->R == 1 || d->C % 64 == 0);
+}
+// the ragged data gradient (the ragged forward instances over dy): fx_dgrad_applies' stride-1 branch without its two width clauses.  (Stride 2: the parity classes of an
+// odd map differ in size -- the fp32-MFMA kernel keeps those)
+bool fx_dgrad_any_applies(const p3d_conv_desc* d, int min_m) {
+    return fx_common(d) && d->K % FX_BK == 0 && d->K >= 32 && d->C % 4 == 0 && d->C >= min_m && d->stride == 1;
+}
+// the ragged weight gradient (fx_wgrad_any_kernel): fx_wgrad_applies without OHW % 16 == 0, Wo % 4 == 0 and W % 4 == 0
+bool fx_wgrad_any_applies(const p3d_conv_desc* d, int min_m) {
+    if ((int64_t)d->N * d->C * d->H * d->W >= (1ll << 29) || (int64_t)d->N * d->K * d->Ho * d->Wo >= (1ll << 29)) return false;
+    return fx_common(d) && d->K >= min_m && d->C >= min_m && (d->R == 1 || d->C % 64 == 0);
 }
 
 // p3d_fx_tune(0 / 1 / 2, n): forced split counts (weight gradient, forward / data gradient) and a forced weight-gradient block target; 0 = the built-in plan
@@ -1758,6 +1945,7 @@ bool fx_wgrad_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && 
 size_t fx_fwd_workspace(const p3d_conv_desc* d) { return fx_plan(d, false).workspace; }
 size_t fx_fwd_any_workspace(const p3d_conv_desc* d) { return fx_plan(d, false, true).workspace; }
 size_t fx_dgrad_workspace(const p3d_conv_desc* d) { return fx_plan(d, true).workspace; }
+size_t fx_dgrad_any_workspace(const p3d_conv_desc* d) { return fx_plan(d, true, true).workspace; }
 int fx_partial_rows_fwd(const p3d_conv_desc* d) { return fx_plan(d, false).partial_rows; }
 int fx_partial_rows_dgrad(const p3d_conv_desc* d) { return fx_plan(d, true).partial_rows; }
 size_t fx_wgrad_workspace(const p3d_conv_desc* d) {
@@ -1970,7 +2158,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     const bool img = fuse && fuse->act_img;
     const bool masked = fuse && (fuse->pmask || fuse->emask);
     const bool infer = fuse && fuse->infer;
-    const bool rag = fuse && fuse->infer == 2;          // the ragged instances (p3d_fx_conv_fwd_infer_any, p3d_fx_conv_fwd_infer_masked_any): any map width
+    const bool rag = fuse && (fuse->infer == 2 || fuse->ragged);          // the ragged instances (p3d_fx_conv_fwd_infer_any, p3d_fx_conv_fwd_infer_masked_any; training under p3d_x3_any_enable): any map width
     const void* wimg = fuse ? fuse->wimg : nullptr;
     if (masked && (!fuse->emask || (bias && !infer) || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr))) {
         set_error("fx_conv_fwd: the partial-convolution instances take the output factor, the input factor exactly for an fp32 operand, and no bias"); return P3D_EINVAL;
@@ -1982,6 +2170,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
                 "fx_conv_fwd: the inference epilogue takes a cached folded weight image, no other fusion, and a partial convolution only from an fp32 operand");
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
     P3D_REQUIRE(!rag || !img, "fx_conv_fwd: the ragged forward takes an fp32 operand");
+    P3D_REQUIRE(!(fuse && fuse->ragged) || (!infer && !masked && !fuse->partial), "fx_conv_fwd: the ragged training forward is the plain dense convolution");
     const FxPlan pl = fx_plan(d, false, rag);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     FxConvParams p{};
@@ -2023,7 +2212,9 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
     if (masked && (!fuse->emask || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr) || (!img && fuse->partial))) {
         set_error("fx_conv_dgrad: the partial-convolution instances take the result factor and the operand factor exactly for an fp32 operand"); return P3D_EINVAL;
     }
-    const FxPlan pl = fx_plan(d, true);
+    const bool rag = fuse && fuse->ragged;          // the ragged forward instances over dy (p3d_x3_any_enable): any map width, stride 1, dense, fp32-fed
+    P3D_REQUIRE(!rag || (d->stride == 1 && !img && !masked && !fuse->partial && !fuse->acc_src), "fx_conv_dgrad: the ragged data gradient is the plain dense stride-1 one");
+    const FxPlan pl = fx_plan(d, true, rag);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_dgrad: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     if (fuse && fuse->acc_src && !(d->accumulate && fx_dgrad_accumulates_from_source(d))) {
         set_error("fx_conv_dgrad: an accumulation source needs accumulate = 1, stride 1 and an unsplit launch"); return P3D_EINVAL;
@@ -2048,15 +2239,15 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
     const bool split = pl.splits > 1;
     p.tap_inner = img && RS > 1 && d->K >= FX_TAP_INNER_MIN;
     const auto [pro, epi] = fx_select(true, img, masked, sums, false);
-    const int bm = fx16_bm(d->C, img, split ? 0 : pro, split ? FX_EPI_STORE : epi);
+    const int bm = rag ? 0 : fx16_bm(d->C, img, split ? 0 : pro, split ? FX_EPI_STORE : epi);
     p.tiles_m = (int)ceil_div(d->C, bm ? bm : FX_BM);
     if (d->stride == 1) {
         p.OH = d->H; p.OW = d->W; p.NP = d->N * d->H * d->W; p.oy0 = 0; p.ox0 = 0; p.oys = 1; p.oxs = 1;
         p.nR = d->R; p.nS = d->S; p.ntap = RS; p.r0 = 0; p.rstep = 1; p.s0 = 0; p.sstep = 1;
         p.hmul = 1; p.hoff = d->pad; p.hstep = -d->dil; p.wmul = 1; p.woff = d->pad; p.wstep = -d->dil;
         if (!split && fuse && fuse->acc_src && d->accumulate) { p.acc_src = fuse->acc_src; p.acc_mask = fuse->acc_mask; }
-        if (int32_t e = split ? fx_launch_split(p, pl, img, pro, epi, bm, (float*)(ws + pl.slab_offset), st)
-                              : fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), 1), st)) return e;
+        if (int32_t e = split ? fx_launch_split(p, pl, img, pro, epi, bm, (float*)(ws + pl.slab_offset), st, rag)
+                              : fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), 1), st, rag)) return e;
         return check_launch("fx_conv_dgrad");
     }
     // stride 2: input pixel (ph + 2 i, pw + 2 j) of class (ph, pw) gathers dy at (i + off0 - ir * offstep, ...) over the taps r = r0 + rstep * ir that reach it
@@ -2109,10 +2300,14 @@ int fx_wgrad_two_taps(const p3d_conv_desc* d, bool images) {
     if (!images || d->C != 64 || d->R * d->S <= 1 || (d->Wo & 15)) return 0;
     return d->K <= 64 ? 3 : 2;
 }
-int fx_wgrad_splits(const p3d_conv_desc* d, bool images) {
+// ragged (fx_wgrad_any_kernel): the K steps are those of the flat pixel index, ceil(N Ho Wo / 16), and a block keeps at least 8 of them instead of 32 -- the floor of the
+// fp32-MFMA plan (plan_wgrad, p3d_conv.hip).  A slab is one chain of 6 dependent fp32 accumulations per K step; at the small batches where the floor binds, 32 steps leave a
+// whole reduction in one or two slabs on a handful of blocks, and its rounding error at several times that of the fp32-MFMA kernel, which sums many short slabs
+// (profiles/train_anysize.md).  At batch 64 the floor binds for one class only (four tiles at 33 x 33).
+int fx_wgrad_splits(const p3d_conv_desc* d, bool images, bool ragged) {
     const int tt = fx_wgrad_two_taps(d, images);
     const int64_t tiles = tt ? ceil_div(d->K, FX_BM) * ceil_div(d->R * d->S, tt) : ceil_div(d->K, FX_BM) * ceil_div(d->C, FX_BN) * d->R * d->S;
-    const int64_t total = (int64_t)d->N * (d->Ho * d->Wo / FX_BK);
+    const int64_t total = ragged ? ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BK) : (int64_t)d->N * (d->Ho * d->Wo / FX_BK);
     int64_t target;
     if (g_wgrad_target > 0) target = g_wgrad_target;          // (tuning aid: p3d_fx_tune(2, n), tools/split_sweep.py)
     else if (tiles >= 256) target = 1536;
@@ -2127,7 +2322,8 @@ int fx_wgrad_splits(const p3d_conv_desc* d, bool images) {
         default: target = 768;              // (1, 9, 64 tiles; anything the sweep has not seen)
     }
     int64_t splits = (2 * target + tiles) / (2 * tiles);                 // nearest
-    if (splits > total / 32) splits = total / 32;                        // at least 32 K steps per block
+    const int min_steps = ragged ? 8 : 32;
+    if (splits > total / min_steps) splits = total / min_steps;          // at least 32 K steps per block (ragged: 8)
     if (g_force_wgrad_splits > 0) splits = g_force_wgrad_splits < total ? g_force_wgrad_splits : total;
     if (splits < 1) splits = 1;
     const int64_t spb = ceil_div(total, splits);
@@ -2143,6 +2339,13 @@ int32_t fx_conv_wgrad_slabs(const p3d_conv_desc* d, const float* dy, const float
     p.nsplit = splits;
     p.spb = (int)ceil_div((int64_t)d->N * (d->Ho * d->Wo / FX_BK), splits);
     p.order = fx_wgrad_order(d);
+    if (fuse && fuse->ragged) {          // any map width: K steps over the flat pixel index, the last one partial (fx_wgrad_any_kernel)
+        if (fuse->dy_img || fuse->x_img || fuse->pmask || fuse->emask) { set_error("fx_conv_wgrad: the ragged weight gradient takes fp32 operands and no factor"); return P3D_EINVAL; }
+        p.spb = (int)ceil_div(ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BK), splits);
+        hipLaunchKernelGGL(fx_wgrad_any_kernel, dim3((unsigned)ceil_div(d->C, FX_BN), (unsigned)ceil_div(d->K, FX_BM), (unsigned)(splits * d->R * d->S)), dim3(256), 0, st, p);
+        prof_kernel_done(st);
+        return check_launch("fx_conv_wgrad");
+    }
     bool aimg = false, bimg = false, masked = false;
     if (fuse) {
         if (fuse->dy_img) { aimg = true; p.DYimg = (const unsigned char*)fuse->dy_img; p.dy_plane = (size_t)d->N * d->K * d->Ho * d->Wo * 2; }

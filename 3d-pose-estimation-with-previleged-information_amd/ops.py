@@ -910,6 +910,13 @@ def set_x3(on):
     return bool(lib().p3d_x3_enable(int(bool(on))))
 
 
+def x3_any(on):
+    """Opt-in, OFF by default (P3D_X3_ANY=1 turns it on): the per-layer training path (Conv2dFn: forward, stride-1 data gradient, weight gradient) runs dense
+    convolutions on the x3 kernels at map widths that are no multiples of 4 -- the 65 / 33 / 17 maps of the default 257 crop -- instead of the fp32-MFMA
+    kernels.  Returns the previous setting."""
+    return bool(lib().p3d_x3_any_enable(int(bool(on))))
+
+
 X3_EPOCH = 0
 WEIGHT_EPOCH = 0          # bumped whenever parameters are written behind torch's back (FlatAdam's kernels, broadcasts into / restores of flat_p): cached per-weight derivatives (ops_block.weight_images) are stale
 

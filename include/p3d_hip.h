@@ -97,6 +97,17 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
  * (three-piece operand split, six piece products, fp32 accumulation; csrc/p3d_fx.hip): fp32-grade results, measured error <= the
  * fp32-MFMA kernel's.  p3d_x3_enable(0) (or P3D_X3=0 in the environment) keeps every layer on the v_mfma_f32_32x32x2_f32 kernels.  Returns the previous setting. */
 int32_t p3d_x3_enable(int32_t on);
+/* Opt-in (default OFF; P3D_X3_ANY=1 in the environment turns it on): p3d_conv2d_fwd, p3d_conv2d_dgrad (stride 1) and p3d_conv2d_wgrad run a dense convolution with a
+ * whole weight tensor that the aligned predicates refuse only for its map width (W, Wo no multiples of 4; Ho * Wo no multiple of 16: the 65 / 33 / 17 maps of the
+ * reference's default 257 crop) on the ragged x3 instances instead of the fp32-MFMA kernels ("Training at any map width").  While it is on the
+ * three workspace queries report the larger of the two plans.  Aligned shapes, partial convolutions and strided data gradients are launched exactly as with the switch
+ * off.  Returns the previous setting.
+ * p3d_conv2d_*_any_supported: 1 where the ragged instances of that pass admit the convolution (whatever the switch says; they admit aligned shapes too, which the
+ * entries keep on the aligned instances), 0 otherwise -- a channel window, a strided data gradient, channel counts outside the x3 rules. */
+int32_t p3d_x3_any_enable(int32_t on);
+int32_t p3d_conv2d_fwd_any_supported(const p3d_conv_desc* d);
+int32_t p3d_conv2d_dgrad_any_supported(const p3d_conv_desc* d);
+int32_t p3d_conv2d_wgrad_any_supported(const p3d_conv_desc* d);
 /* Test and tuning hooks of the x3 path; value 0 restores the built-in behaviour unless noted.  Codes:
  *   0  forced split count of the weight-gradient launches                  (tools/split_sweep.py, tests/test_kernels_gpu.py)
  *   1  forced split count of the forward / data-gradient launches          (the same)

@@ -1,0 +1,179 @@
+#!/usr/bin/env python3
+"""Training at the default 257^2 crop with ops.x3_any on and off: ResNet-50 depthnet, stride 16, batch 64 (profiles/train_anysize.md).
+
+  --classes   per conv class of the trunk at its odd map (65 / 33 / 17): p3d_conv2d_fwd, p3d_conv2d_dgrad and p3d_conv2d_wgrad timed with device events, the switch
+              on and off alternating within one process, --rounds rounds of --iters launches each.  One line per class and pass: median ms [min .. max] of both legs,
+              which kernel family each leg ran on (the library's launch counters), the ratio; then the sums weighted by the layers per class.
+  --step      the whole training step at --side (default 257): legs `off` and `on` alternating, --rounds rounds of --iters steps after --warmup, median [min .. max]
+              ms per step of each leg, the launch counts per step and pass of both legs, and the verdict: `on` wins when its median is below `off`'s by more than the
+              two legs' combined spread (max - min).  On a build without ops.x3_any (the parent commit) only the `off` leg runs.
+GPU box only."""
+import argparse
+import ctypes
+import importlib
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+pkg = importlib.import_module('3d-pose-estimation-with-previleged-information_amd')
+ops = pkg.ops
+PASSES = ('fwd', 'dgrad', 'wgrad')
+
+# Cin, odd map, Cout, k, stride, dilation, layers of the class   (the dense convs behind the stem: tools/anysize_bench.py's table at the odd maps)
+R50 = [(64, 65, 64, 1, 1, 1, 1), (64, 65, 64, 3, 1, 1, 3), (64, 65, 256, 1, 1, 1, 4), (256, 65, 64, 1, 1, 1, 2),
+       (256, 65, 128, 1, 1, 1, 1), (128, 65, 128, 3, 2, 1, 1), (128, 33, 512, 1, 1, 1, 4), (256, 65, 512, 1, 2, 1, 1),
+       (512, 33, 128, 1, 1, 1, 3), (128, 33, 128, 3, 1, 1, 3), (512, 33, 256, 1, 1, 1, 1), (256, 33, 256, 3, 2, 1, 1),
+       (256, 17, 1024, 1, 1, 1, 6), (512, 33, 1024, 1, 2, 1, 1), (1024, 17, 256, 1, 1, 1, 5), (256, 17, 256, 3, 1, 1, 5),
+       (1024, 17, 512, 1, 1, 1, 1), (512, 17, 512, 3, 1, 2, 1), (512, 17, 2048, 1, 1, 1, 3), (1024, 17, 2048, 1, 1, 1, 1),
+       (2048, 17, 512, 1, 1, 1, 2), (512, 17, 512, 3, 1, 1, 2), (2048, 17, 272, 3, 1, 1, 1)]
+
+
+def switch(on):
+    if hasattr(ops, 'x3_any'):
+        ops.x3_any(on)
+    elif on:
+        raise SystemExit('this build has no ops.x3_any')
+
+
+def timed(fn, iters):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def med(v):
+    v = sorted(v)
+    return v[len(v) // 2], v[0], v[-1]
+
+
+def family(stats, name):
+    return 'x3' if stats['x3'][name][0] else 'fp32'
+
+
+def classes(a):
+    L = pkg._lib.lib()
+    total = {(p, leg): 0.0 for p in PASSES for leg in ('off', 'on')}
+    for (c, h, k, ks, st, dil, cnt) in sorted(R50, key=lambda r: -r[0] * r[2] * r[3] ** 2 * ((r[1] // r[4] + 1) ** 2) * r[6]):
+        tag = 'c%d h%d k%d %dx%d s%d d%d x%d' % (c, h, k, ks, ks, st, dil, cnt)
+        if a.only and a.only not in tag:
+            continue
+        torch.manual_seed(c + k)
+        pad = dil * (ks - 1) // 2
+        x = torch.randn(a.batch, c, h, h, device='cuda')
+        w = torch.randn(k, c, ks, ks, device='cuda') / (c * ks * ks) ** 0.5
+        d = ops._desc(x.shape, w.shape, st, pad, dil)
+        dy = torch.randn(a.batch, k, d.Ho, d.Wo, device='cuda')
+        y, dx, dw = torch.empty_like(dy), torch.empty_like(x), torch.empty_like(w)
+        b = ctypes.byref(d)
+        switch(True)                                             # (the larger plan: one workspace serves both legs)
+        ws = torch.empty(max(L.p3d_conv2d_fwd_workspace_bytes(b), L.p3d_conv2d_dgrad_workspace_bytes(b), L.p3d_conv2d_wgrad_workspace_bytes(b), 16), dtype=torch.uint8, device='cuda')
+        switch(False)
+        P, stream = ops._p, ops._stream()
+        calls = {'fwd': lambda: L.p3d_conv2d_fwd(b, P(x), P(w), None, None, None, P(y), P(ws), ws.numel(), stream),
+                 'dgrad': lambda: L.p3d_conv2d_dgrad(b, P(dy), P(w), None, None, P(dx), P(ws), ws.numel(), stream),
+                 'wgrad': lambda: L.p3d_conv2d_wgrad(b, P(dy), P(x), None, None, P(dw), P(ws), ws.numel(), stream)}
+        gf = 2.0 * a.batch * k * c * ks * ks * d.Ho * d.Wo / 1e9
+        for name, fn in calls.items():
+            ms, ran = {'off': [], 'on': []}, {}
+            for leg in ('off', 'on'):
+                switch(leg == 'on')
+                ops.conv_path_stats(reset=True)
+                for _ in range(3):
+                    assert fn() == 0, pkg._lib.lib().p3d_last_error()
+                ran[leg] = family(ops.conv_path_stats(reset=True), name)
+            for _ in range(a.rounds):
+                for leg in ('off', 'on'):
+                    switch(leg == 'on')
+                    ms[leg].append(timed(fn, a.iters))
+            switch(False)
+            assert ran['off'] == 'fp32', (tag, name, ran)
+            m0, m1 = med(ms['off']), med(ms['on'])
+            print('%-28s %-5s %7.2f GF | off %-4s %.3f [%.3f..%.3f] ms %5.1f TF | on %-4s %.3f [%.3f..%.3f] ms %5.1f TF | on/off %.2f' % (
+                (tag, name, gf, ran['off']) + m0 + (gf / m0[0], ran['on']) + m1 + (gf / m1[0], m1[0] / m0[0])), flush=True)
+            total[(name, 'off')] += m0[0] * cnt
+            total[(name, 'on')] += m1[0] * cnt
+    for name in PASSES:
+        print('sum over the classes x their layer counts, %-5s: off %.2f ms  on %.2f ms' % (name, total[(name, 'off')], total[(name, 'on')]))
+    print('all three passes: off %.2f ms  on %.2f ms' % (sum(total[(p, 'off')] for p in PASSES), sum(total[(p, 'on')] for p in PASSES)))
+
+
+def step(a):
+    flags = ['-model', a.model, '-suffix', 'bench', '-data_name', 'h36m', '-save_path', '/tmp/p3d_bench', '-criterion', 'SmoothL1', '-num_joints', '17', '-side_in', str(a.side),
+             '-stride', '16', '-depth', '16', '-depth_range', '1000', '-loss_div', '10', '-learn_rate', '5e-5', '-weight_decay', '4e-5', '-grad_norm', '5']
+    args = pkg.opts.parse(flags)
+    torch.manual_seed(0)
+    model, _ = pkg.depth_main.create_model(args)
+    model = model.cuda().train()
+    trainer = pkg.depth_train.Trainer(args, model, pkg.utils.get_info())
+    trainer.verbose = False
+    trainer.adapt_learn_rate(1)
+    batches = []
+    for i in range(3):
+        c, d, tc, tv = pkg.synth.make_batch(a.batch, side=a.side, rank=0, step=i)
+        batches.append((torch.from_numpy(c).cuda(), None, torch.from_numpy(tc).cuda(), torch.from_numpy(tv).cuda()))
+    legs = ('off', 'on') if hasattr(ops, 'x3_any') and not a.off_only else ('off',)
+
+    def run(n):
+        for i in range(n):
+            trainer.train_step(*batches[i % 3])
+        ops.join_side_stream()
+
+    ms, counts = {leg: [] for leg in legs}, {}
+    for leg in legs:
+        switch(leg == 'on')
+        run(a.warmup)
+        torch.cuda.synchronize()
+        ops.conv_path_stats(reset=True)
+        run(1)
+        torch.cuda.synchronize()
+        st = ops.conv_path_stats(reset=True)
+        counts[leg] = {fam: {p: st[fam][p][0] for p in PASSES} for fam in ('x3', 'fp32')}
+    for r in range(a.rounds):
+        for leg in legs:
+            switch(leg == 'on')
+            run(2)
+            torch.cuda.synchronize()
+            ms[leg].append(timed(lambda: run(a.iters), 1) / a.iters)
+            print('round %d %-3s %.3f ms/step' % (r, leg, ms[leg][-1]), flush=True)
+    switch(False)
+    out = {'side': a.side, 'batch': a.batch, 'model': a.model, 'launches_per_step': counts}
+    for leg in legs:
+        m = med(ms[leg])
+        out[leg] = {'median_ms': round(m[0], 3), 'min_ms': round(m[1], 3), 'max_ms': round(m[2], 3)}
+    if len(legs) == 2:
+        spread = (out['off']['max_ms'] - out['off']['min_ms']) + (out['on']['max_ms'] - out['on']['min_ms'])
+        out['gain_ms'] = round(out['off']['median_ms'] - out['on']['median_ms'], 3)
+        out['combined_spread_ms'] = round(spread, 3)
+        out['on_wins'] = bool(out['gain_ms'] > spread)
+    print(json.dumps(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--classes', action='store_true')
+    ap.add_argument('--step', action='store_true')
+    ap.add_argument('--off-only', action='store_true', help='--step: the off leg alone')
+    ap.add_argument('--batch', type=int, default=64)
+    ap.add_argument('--side', type=int, default=257)
+    ap.add_argument('--model', default='resnet50')
+    ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--only', default='')
+    a = ap.parse_args()
+    if a.classes:
+        classes(a)
+    if a.step:
+        step(a)
+
+
+if __name__ == '__main__':
+    main()
