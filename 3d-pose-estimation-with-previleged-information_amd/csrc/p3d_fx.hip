@@ -413,7 +413,51 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     // and their c2 operand) is done first, in place in the accumulator.
     const bool split = p.kchunk > 0;
     float* yout = p.Y + (split ? (size_t)blockIdx.y * p.slab_stride : 0);
-    const bool dense = split || (p.oxs == 1 && p.oys == 1 && p.oy0 == 0 && p.ox0 == 0 && p.YW == p.OW && p.YH == p.OH);
+    // (the forward-only epilogues -- statistics of y, the inference tails -- are never a parity class: their instances carry no strided path; nor do the ragged
+    // ones, which fx_conv_fwd / fx_conv_dgrad launch dense only)
+    constexpr bool FWD_ONLY = SUMS == 1 || fx_epi_infer(EPIX);
+    const bool dense = FWD_ONLY || split || (p.oxs == 1 && p.oys == 1 && p.oy0 == 0 && p.ox0 == 0 && p.YW == p.OW && p.YH == p.OH);
+    if constexpr (!FWD_ONLY && !RAG) {
+        if (!dense) {
+            // A parity class of a strided data gradient stores straight from the accumulator view and is done: four dwords oxs apart per lane and channel, read first
+            // under `accumulate`.  It has this loop to itself, so that the dense epilogue below carries none of it (with the two in one loop every dense launch
+            // paid for it: profiles/strided_paths.md).  No sums here: fx_conv_dgrad refuses the BatchNorm-backward epilogue at a stride.
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int c4 = n0 + wn * 64 + a * 32 + 8 * g + 4 * fh;
+                    if (c4 >= p.NP) continue;
+                    const int n = c4 / OHW, rem = c4 - n * OHW, oh = rem / p.OW, ow = rem - oh * p.OW;
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        const int m = m0 + wm * 64 + b * 32 + fr;
+                        if (m >= p.M) continue;
+                        f32x4 v = {acc[a][b][4 * g], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]};
+                        if (p.bias) { const float bb = p.bias[m]; v[0] += bb; v[1] += bb; v[2] += bb; v[3] += bb; }
+                        float* dst = yout + (((size_t)n * p.M + m) * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow * p.oxs;
+                        if (p.oxs == 1) {
+                            if constexpr (EM) {
+                                const f32x4 em = *reinterpret_cast<const f32x4*>(p.emask + ((size_t)n * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow);
+                                v[0] *= em[0]; v[1] *= em[1]; v[2] *= em[2]; v[3] *= em[3];
+                            }
+                            f32x4* d4 = reinterpret_cast<f32x4*>(dst);
+                            if (p.accumulate) { const f32x4 o4 = *d4; v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3]; }
+                            *d4 = v;
+                        } else {
+                            if constexpr (EM) {
+                                const float* em = p.emask + ((size_t)n * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow * p.oxs;
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) v[e] *= em[e * p.oxs];
+                            }
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) dst[e * p.oxs] = p.accumulate ? dst[e * p.oxs] + v[e] : v[e];
+                        }
+                    }
+                }
+            return;
+        }
+    }
     float ssum[2] = {0.f, 0.f}, ssq[2] = {0.f, 0.f};
     float esc[2] = {0.f, 0.f}, esh[2] = {0.f, 0.f}, emean[2] = {0.f, 0.f};
     if constexpr (SUMS == 2) {
@@ -438,33 +482,12 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                 if (!split && EPIX != FX_EPI_INFER_FACTOR) {        // (there: factor and bias in the staged store below, where no accumulator is live)
                     if (p.bias) { const float bb = p.bias[m]; v[0] += bb; v[1] += bb; v[2] += bb; v[3] += bb; }
                 }
-                if (dense) {
-                    if constexpr (EM) {           // partial convolution: the result times the per-pixel factor (before it joins an existing gradient)
-                        const f32x4 em = *reinterpret_cast<const f32x4*>(p.emask + ((size_t)n * p.YH + oh) * p.YW + ow);
-                        v[0] *= em[0]; v[1] *= em[1]; v[2] *= em[2]; v[3] *= em[3];
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[a][b][4 * g + e] = v[e];
-                } else {
-                    float* dst = yout + (((size_t)n * p.M + m) * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow * p.oxs;
-                    if (p.oxs == 1) {
-                        if constexpr (EM) {
-                            const f32x4 em = *reinterpret_cast<const f32x4*>(p.emask + ((size_t)n * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow);
-                            v[0] *= em[0]; v[1] *= em[1]; v[2] *= em[2]; v[3] *= em[3];
-                        }
-                        f32x4* d4 = reinterpret_cast<f32x4*>(dst);
-                        if (p.accumulate) { const f32x4 o4 = *d4; v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3]; }
-                        *d4 = v;
-                    } else {
-                        if constexpr (EM) {
-                            const float* em = p.emask + ((size_t)n * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow * p.oxs;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] *= em[e * p.oxs];
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) dst[e * p.oxs] = p.accumulate ? dst[e * p.oxs] + v[e] : v[e];
-                    }
+                if constexpr (EM) {               // partial convolution: the result times the per-pixel factor (before it joins an existing gradient)
+                    const f32x4 em = *reinterpret_cast<const f32x4*>(p.emask + ((size_t)n * p.YH + oh) * p.YW + ow);
+                    v[0] *= em[0]; v[1] *= em[1]; v[2] *= em[2]; v[3] *= em[3];
                 }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[a][b][4 * g + e] = v[e];
                 if constexpr (SUMS == 1) {
                     if (!split) {
 #pragma unroll
@@ -483,7 +506,19 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                 }
             }
         }
-    if (dense) {
+    if constexpr (SUMS == 1 || SUMS == 2) {
+        if (!split) {
+            // the two half-waves hold different pixels of the same channels; the two waves along the pixel axis meet in LDS behind the staging tile (the sums
+            // leave the registers here, in front of the staged store: its barriers also order these writes before the reads at the end)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                ssum[b] += __shfl_xor(ssum[b], 32, 64);
+                ssq[b] += __shfl_xor(ssq[b], 32, 64);
+                if (fh == 0) { red[wn][0][wm * 64 + b * 32 + fr] = ssum[b]; red[wn][1][wm * 64 + b * 32 + fr] = ssq[b]; }
+            }
+        }
+    }
+    {
         // (every wave left the K loop through its last barrier: the operand buffers are free)
         constexpr int EROW = 512 + 16;               // bytes per staged channel row: 128 pixels + one 16-B pad (staging stores of 8 consecutive rows hit 32 different banks)
         const bool accum = !split && p.accumulate;
@@ -560,14 +595,6 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     }
     if constexpr (SUMS == 1 || SUMS == 2) {
         if (!split) {
-            // the two half-waves hold different pixels of the same channels; then the two waves along the pixel axis
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                ssum[b] += __shfl_xor(ssum[b], 32, 64);
-                ssq[b] += __shfl_xor(ssq[b], 32, 64);
-                if (fh == 0) { red[wn][0][wm * 64 + b * 32 + fr] = ssum[b]; red[wn][1][wm * 64 + b * 32 + fr] = ssq[b]; }
-            }
-            __syncthreads();
             if (t < 128 && m0 + t < p.M) {
                 float* dst = p.partial + ((size_t)tile_n * p.M + m0 + t) * 2;
                 dst[0] = red[0][0][t] + red[1][0][t];
@@ -764,53 +791,75 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
     else if (GB > 3 && live_b == 3) kloop(std::integral_constant<int, (GB > 3 ? 3 : 0)>{});
 
     // ---- epilogue: lane = output channel (16 b + lc of the wave's), acc[a][b][e] = pixel 16 a + 4 lq + e of the wave's 64 ----
+    // (the lane's indices derived afresh from an opaque copy of the thread index: shared with the prologue's they stay live across the K loop; two VGPRs fewer on
+    // every instance of this kernel, profiles/strided_paths.md section 1)
+    int et = t;
+    asm volatile("" : "+v"(et));
+    const int elc = et & 15, elq = (et & 63) >> 4;
     const bool split = p.kchunk > 0;
     float* yout = p.Y + (split ? (size_t)blockIdx.y * p.slab_stride : 0);
-    const bool dense = split || (p.oxs == 1 && p.oys == 1 && p.oy0 == 0 && p.ox0 == 0 && p.YW == p.OW && p.YH == p.OH);
+    constexpr bool FWD_ONLY = SUMS == 1 || fx_epi_infer(EPI);        // (see fx_conv_kernel)
+    const bool dense = FWD_ONLY || split || (p.oxs == 1 && p.oys == 1 && p.oy0 == 0 && p.ox0 == 0 && p.YW == p.OW && p.YH == p.OH);
+    if constexpr (!FWD_ONLY) {
+        if (!dense) {
+            // a parity class of a strided data gradient: straight from the accumulator view, in a loop of its own (see fx_conv_kernel)
+#pragma unroll
+            for (int a = 0; a < GA; ++a) {
+                const int c4 = n0 + wn * 64 + a * 16 + 4 * elq;
+                if (c4 >= p.NP) continue;
+                const int n = c4 / OHW, rem = c4 - n * OHW, oh = rem / p.OW, ow = rem - oh * p.OW;
+#pragma unroll
+                for (int b = 0; b < GB; ++b) {
+                    const int m = m0 + wm * WCH + b * 16 + elc;
+                    if (m >= p.M) continue;
+                    f32x4 v = acc[a][b];
+                    if (p.bias) { const float bb = p.bias[m]; v[0] += bb; v[1] += bb; v[2] += bb; v[3] += bb; }
+                    float* dst = yout + (((size_t)n * p.M + m) * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow * p.oxs;
+                    if (p.emask) {              // (of a partial convolution: the factor of the input pixels this class writes)
+                        const float* em = p.emask + ((size_t)n * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow * p.oxs;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] *= em[e * p.oxs];
+                    }
+                    if (p.oxs == 1) {
+                        f32x4* d4 = reinterpret_cast<f32x4*>(dst);
+                        if (p.accumulate) { const f32x4 o4 = *d4; v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3]; }
+                        *d4 = v;
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) dst[e * p.oxs] = p.accumulate ? dst[e * p.oxs] + v[e] : v[e];
+                    }
+                }
+            }
+            return;
+        }
+    }
     float ssum[GB], ssq[GB], esc[GB], esh[GB], emean[GB];
 #pragma unroll
     for (int b = 0; b < GB; ++b) {
         ssum[b] = ssq[b] = esc[b] = esh[b] = emean[b] = 0.f;
         if constexpr (SUMS == 2) {
-            const int m = m0 + wm * WCH + b * 16 + lc;
+            const int m = m0 + wm * WCH + b * 16 + elc;
             if (m < p.M) { esc[b] = p.ep_tab[8 * m]; esh[b] = p.ep_tab[8 * m + 1]; emean[b] = p.ep_tab[8 * m + 2]; }
         }
     }
 #pragma unroll
     for (int a = 0; a < GA; ++a) {
-        const int c4 = n0 + wn * 64 + a * 16 + 4 * lq;
+        const int c4 = n0 + wn * 64 + a * 16 + 4 * elq;
         if (c4 >= p.NP) continue;
         const int n = c4 / OHW, rem = c4 - n * OHW, oh = rem / p.OW, ow = rem - oh * p.OW;
 #pragma unroll
         for (int b = 0; b < GB; ++b) {
-            const int m = m0 + wm * WCH + b * 16 + lc;
+            const int m = m0 + wm * WCH + b * 16 + elc;
             if (m >= p.M) continue;
             f32x4 v = acc[a][b];
             if (!split) {
                 if (p.bias) { const float bb = p.bias[m]; v[0] += bb; v[1] += bb; v[2] += bb; v[3] += bb; }
             }
-            if (dense) {
-                if (p.emask && !split) {        // partial convolution: the result times the per-pixel renormalisation factor (before any statistics are taken of it)
-                    const f32x4 em = *reinterpret_cast<const f32x4*>(p.emask + ((size_t)n * p.YH + oh) * p.YW + ow);
-                    v[0] *= em[0]; v[1] *= em[1]; v[2] *= em[2]; v[3] *= em[3];
-                }
-                acc[a][b] = v;
-            } else {
-                float* dst = yout + (((size_t)n * p.M + m) * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow * p.oxs;
-                if (p.emask) {              // (a strided data gradient of a partial convolution: the factor of the input pixels this class writes)
-                    const float* em = p.emask + ((size_t)n * p.YH + p.oy0 + oh * p.oys) * p.YW + p.ox0 + ow * p.oxs;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] *= em[e * p.oxs];
-                }
-                if (p.oxs == 1) {
-                    f32x4* d4 = reinterpret_cast<f32x4*>(dst);
-                    if (p.accumulate) { const f32x4 o4 = *d4; v[0] += o4[0]; v[1] += o4[1]; v[2] += o4[2]; v[3] += o4[3]; }
-                    *d4 = v;
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) dst[e * p.oxs] = p.accumulate ? dst[e * p.oxs] + v[e] : v[e];
-                }
+            if (p.emask && !split) {            // partial convolution: the result times the per-pixel renormalisation factor (before any statistics are taken of it)
+                const f32x4 em = *reinterpret_cast<const f32x4*>(p.emask + ((size_t)n * p.YH + oh) * p.YW + ow);
+                v[0] *= em[0]; v[1] *= em[1]; v[2] *= em[2]; v[3] *= em[3];
             }
+            acc[a][b] = v;
             if constexpr (SUMS == 1) {
                 if (!split) {
 #pragma unroll
@@ -829,7 +878,19 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
             }
         }
     }
-    if (dense) {
+    if constexpr (SUMS == 1 || SUMS == 2) {
+        if (!split) {
+            // the four 16-lane groups hold different pixels of the same channels; the two waves along the pixel axis meet in LDS behind the staging tile (in
+            // front of the staged store, whose barriers order these writes before the reads at the end: see fx_conv_kernel)
+#pragma unroll
+            for (int b = 0; b < GB; ++b) {
+                ssum[b] += __shfl_xor(ssum[b], 16, 64); ssq[b] += __shfl_xor(ssq[b], 16, 64);
+                ssum[b] += __shfl_xor(ssum[b], 32, 64); ssq[b] += __shfl_xor(ssq[b], 32, 64);
+                if (elq == 0) { red[wn][0][wm * WCH + b * 16 + elc] = ssum[b]; red[wn][1][wm * WCH + b * 16 + elc] = ssq[b]; }
+            }
+        }
+    }
+    {
         // through a [64 channels][128 pixels] staging tile, 32 channels of each wave row per round (see fx_conv_kernel)
         constexpr int EROW = 512 + 16;
         constexpr int ROUNDS = (GB + 1) / 2;
@@ -843,13 +904,13 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
                 if (b < GB) {
 #pragma unroll
                     for (int a = 0; a < GA; ++a)
-                        *reinterpret_cast<f32x4*>(lds + (wm * 32 + b2 * 16 + lc) * EROW + (wn * 64 + a * 16 + 4 * lq) * 4) = acc[a][b < GB ? b : 0];
+                        *reinterpret_cast<f32x4*>(lds + (wm * 32 + b2 * 16 + elc) * EROW + (wn * 64 + a * 16 + 4 * elq) * 4) = acc[a][b < GB ? b : 0];
                 }
             }
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const int id = t + 256 * i, row = id >> 5, q = id & 31;
+                const int id = et + 256 * i, row = id >> 5, q = id & 31;
                 const int within = r * 32 + (row & 31);
                 const int m = m0 + (row >> 5) * WCH + within;
                 const int c4 = n0 + 4 * q;
@@ -880,18 +941,10 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
     }
     if constexpr (SUMS == 1 || SUMS == 2) {
         if (!split) {
-            // the four 16-lane groups hold different pixels of the same channels; then the two waves along the pixel axis
-#pragma unroll
-            for (int b = 0; b < GB; ++b) {
-                ssum[b] += __shfl_xor(ssum[b], 16, 64); ssq[b] += __shfl_xor(ssq[b], 16, 64);
-                ssum[b] += __shfl_xor(ssum[b], 32, 64); ssq[b] += __shfl_xor(ssq[b], 32, 64);
-                if (lq == 0) { red[wn][0][wm * WCH + b * 16 + lc] = ssum[b]; red[wn][1][wm * WCH + b * 16 + lc] = ssq[b]; }
-            }
-            __syncthreads();
-            if (t < BM && m0 + t < p.M) {
-                float* dst = p.partial + ((size_t)tile_n * p.M + m0 + t) * 2;
-                dst[0] = red[0][0][t] + red[1][0][t];
-                dst[1] = red[0][1][t] + red[1][1][t];
+            if (et < BM && m0 + et < p.M) {
+                float* dst = p.partial + ((size_t)tile_n * p.M + m0 + et) * 2;
+                dst[0] = red[0][0][et] + red[1][0][et];
+                dst[1] = red[0][1][et] + red[1][1][et];
             }
         }
     }
@@ -2120,6 +2173,9 @@ int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_f
 // the one place that launches a convolution kernel: the instance of (tile, operand, prologue, epilogue, K order, ragged), P3D_EINVAL if none was compiled
 static int32_t fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi, int bm, dim3 grid, hipStream_t st, bool rag = false) {
     FxConvParams p = p_in;
+    // only the STORE and backward instances of the aligned kernels hold the strided store: a parity class on any other would be written at dense addresses
+    P3D_REQUIRE(!(rag || fx_epi_sums(epi) == 1 || fx_epi_infer(epi)) || (p.oxs == 1 && p.oys == 1 && p.oy0 == 0 && p.ox0 == 0 && p.YW == p.OW && p.YH == p.OH && p.ncls == 0),
+                "fx_launch_conv: a strided result on a dense-only instance (rag=%d epi=%d)", rag ? 1 : 0, epi);
     if (p.tap_inner && !fx_instance(bm, img, pro, epi, true, rag)) p.tap_inner = 0;
     const FxKernel kernel = fx_instance(bm, img, pro, epi, p.tap_inner != 0, rag);
     if (!kernel) { set_error("fx_launch_conv: no kernel instance for img=%d pro=%d epi=%d bm=%d", img ? 1 : 0, pro, epi, bm); return P3D_EINVAL; }
