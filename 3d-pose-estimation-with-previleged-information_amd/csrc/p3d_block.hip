@@ -33,7 +33,7 @@ constexpr int BLOCK_MIN_M = 64;
 // reference's blocks put the stride on the 3x3; the strided 1x1 of a downsample branch ADDS onto a gradient that is already complete).
 static bool block_slot(const p3d_block_desc* b, int i) { return i < b->nconv || (i == 3 && b->has_downsample); }      // slots 0 .. nconv - 1: the main chain; 3: the downsample conv
 static bool block_conv_ok(const p3d_conv_desc* d, bool main_chain) {
-    return fx_fwd_applies(d, BLOCK_MIN_M) && fx_dgrad_applies(d, BLOCK_MIN_M) && fx_wgrad_applies(d, BLOCK_MIN_M) && (d->Ho * d->Wo) % 4 == 0 &&
+    return fx_applies(FX_FWD, d, BLOCK_MIN_M) && fx_applies(FX_DGRAD, d, BLOCK_MIN_M) && fx_applies(FX_WGRAD, d, BLOCK_MIN_M) && (d->Ho * d->Wo) % 4 == 0 &&
            (d->H * d->W) % 4 == 0 && d->C % 16 == 0 && d->K % 16 == 0 && !(main_chain && fx_dgrad_has_dead_classes(d));
 }
 
@@ -360,7 +360,7 @@ ProfScope::~ProfScope() {
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // a partial convolution inside the executor: the per-pixel factors live in the conv kernels' epilogues (for a split-K launch: in the pass that sums the slabs)
-static bool masked_conv_ok(const p3d_conv_desc* d) { return fx_fwd_masked_applies(d) && fx_dgrad_masked_applies(d); }
+static bool masked_conv_ok(const p3d_conv_desc* d) { return fx_masked_applies(FX_FWD, d) && fx_masked_applies(FX_DGRAD, d); }
 
 // The admission predicate of the executor (b non-null, nconv 2 or 3): 0 = every slot is taken; otherwise *slot is the first one refused, 1 = its shape is outside
 // the fused path, 2 = it is a partial convolution outside the masked instances
@@ -393,12 +393,12 @@ static BlockLayout block_layout(const p3d_block_desc* b) {
     for (int i = 0; i < 4; ++i) {
         if (!block_slot(b, i)) continue;
         const p3d_conv_desc* d = &b->conv[i];
-        atleast(mw, fx_fwd_workspace(d));
-        atleast(mw, fx_dgrad_workspace(d));
-        atleast(part, (size_t)fx_partial_rows_fwd(d) * d->K * 2 * sizeof(float));
-        atleast(part, (size_t)fx_partial_rows_dgrad(d) * d->C * 2 * sizeof(float));
+        atleast(mw, fx_workspace(FX_FWD, d));
+        atleast(mw, fx_workspace(FX_DGRAD, d));
+        atleast(part, (size_t)fx_partial_rows(FX_FWD, d) * d->K * 2 * sizeof(float));
+        atleast(part, (size_t)fx_partial_rows(FX_DGRAD, d) * d->C * 2 * sizeof(float));
         atleast(part, (size_t)(d->K > d->C ? d->K : d->C) * CLOSE_MAX_SPLIT * 3 * sizeof(double));      // the opening pass's and bn_bwd_sums_kernel's fp64 sums
-        atleast(sw, fx_wgrad_workspace(d));
+        atleast(sw, fx_workspace(FX_WGRAD, d));
     }
     return BlockLayout{align256(mw), align256(part), align256(mw) + 2 * align256(part), align256(sw)};
 }
@@ -496,15 +496,15 @@ int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
         // a_i = relu(bn_i(c_i)), written once, as the image the next convolution (and, in backward, its weight gradient) copies into LDS
         P3D_REQUIRE(io->aimg[i], "block_fwd: null activation image %d", i);
         const double cnt = (double)d->N * d->Ho * d->Wo;
-        const CloseFin cf = finalize_fwd(block_bn(b, io, i), partial, fx_partial_rows_fwd(d), d->K, cnt, st);
+        const CloseFin cf = finalize_fwd(block_bn(b, io, i), partial, fx_partial_rows(FX_FWD, d), d->K, cnt, st);
         const FxFinalize fin = act_finalize(cf, cnt);
         if (int32_t e = fx_act_image(1, io->c[i], nullptr, io->table[i], 0, io->aimg[i], d->N, d->K, d->Ho * d->Wo, st, cf.rows ? &fin : nullptr, mk ? io->pix_in[i + 1] : nullptr)) return e;
     }
     const p3d_conv_desc* dl = &b->conv[last];
     const int HW = dl->Ho * dl->Wo;
     const double cnt_close = (double)dl->N * HW;
-    const CloseFin cf = finalize_fwd(block_bn(b, io, last), partial, fx_partial_rows_fwd(dl), dl->K, cnt_close, st);
-    const CloseFin rf = b->has_downsample ? finalize_fwd(block_bn(b, io, 3), partial2, fx_partial_rows_fwd(&b->conv[3]), dl->K, cnt_close, st) : CloseFin{};
+    const CloseFin cf = finalize_fwd(block_bn(b, io, last), partial, fx_partial_rows(FX_FWD, dl), dl->K, cnt_close, st);
+    const CloseFin rf = b->has_downsample ? finalize_fwd(block_bn(b, io, 3), partial2, fx_partial_rows(FX_FWD, &b->conv[3]), dl->K, cnt_close, st) : CloseFin{};
     hipLaunchKernelGGL(block_close_fwd_kernel, dim3(dl->K, close_split(dl->N, dl->K)), dim3(256), 0, st, (const float*)io->c[last], cf,
                        b->has_downsample ? (const float*)io->c[3] : io->x, rf, io->out, b->relu_out ? io->out_mask : (unsigned char*)nullptr, dl->N, dl->K, HW, b->relu_out, cnt_close);
     return check_launch("block_fwd");
@@ -622,7 +622,7 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
             if (int32_t e = launch_wgrad(x, i, nullptr, io->aimg[i - 1], d->R * d->S > 1, ready)) return e;
             const double cnt = (double)dp->N * dp->Ho * dp->Wo;
             if (epi) {
-                if (int32_t e = bwd_map(x, io->da[i - 1], i - 1, 1, 2, fx_partial_rows_dgrad(d), 0, cnt)) return e;
+                if (int32_t e = bwd_map(x, io->da[i - 1], i - 1, 1, 2, fx_partial_rows(FX_DGRAD, d), 0, cnt)) return e;
             } else {
                 // a strided data gradient takes no sums in its epilogue: a pass of their own
                 const int sp = close_split(dp->N, dp->K);
@@ -885,21 +885,19 @@ int32_t p3d_fx_act_image(int32_t mode, const float* x, const float* x2, const fl
 // x_img / dy_img: p3d_fx_act_image of the fp32 tensor p3d_conv2d_* would take; wimg: the matching p3d_fx_weight_images image, or NULL (built into the workspace).
 size_t p3d_fx_conv_img_workspace_bytes(const p3d_conv_desc* d, int32_t pass) {
     if (!d) return 0;
-    if (pass == 0) return fx_fwd_workspace(d);
-    if (pass == 1) return fx_dgrad_workspace(d);
-    return fx_wgrad_workspace(d);
+    return fx_workspace(pass == 0 ? FX_FWD : pass == 1 ? FX_DGRAD : FX_WGRAD, d);
 }
 
 // bit 0 / 1 / 2: the forward / data-gradient / weight-gradient pass of this convolution can run on image operands
 int32_t p3d_fx_conv_img_supported(const p3d_conv_desc* d) {
     if (!d || !fx_enabled() || d->C % 16 != 0 || d->K % 16 != 0 || (d->H * d->W) % 4 != 0 || (d->Ho * d->Wo) % 4 != 0) return 0;
-    return (fx_fwd_applies(d, 32) ? 1 : 0) | (fx_dgrad_applies(d, 32) ? 2 : 0) | (fx_wgrad_applies(d, 32) ? 4 : 0);
+    return (fx_applies(FX_FWD, d, 32) ? 1 : 0) | (fx_applies(FX_DGRAD, d, 32) ? 2 : 0) | (fx_applies(FX_WGRAD, d, 32) ? 4 : 0);
 }
 
 int32_t p3d_fx_conv_fwd_img(const p3d_conv_desc* d, const void* x_img, const float* w, const void* wimg, const float* bias, float* y, void* workspace,
                             size_t workspace_bytes, void* stream) {
     P3D_REQUIRE(d && x_img && w && y, "fx_conv_fwd_img: null argument");
-    P3D_REQUIRE(fx_fwd_applies(d, 32) && d->C % 16 == 0 && (d->H * d->W) % 4 == 0, "fx_conv_fwd_img: shape outside the x3 kernels");
+    P3D_REQUIRE(fx_applies(FX_FWD, d, 32) && d->C % 16 == 0 && (d->H * d->W) % 4 == 0, "fx_conv_fwd_img: shape outside the x3 kernels");
     FxFuse f{};
     f.act_img = x_img; f.wimg = wimg;
     ProfScope ps(0, d, (hipStream_t)stream);
@@ -910,13 +908,12 @@ int32_t p3d_fx_conv_fwd_img(const p3d_conv_desc* d, const void* x_img, const flo
 int32_t p3d_fx_conv_dgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
                               void* stream) {
     P3D_REQUIRE(d && dy_img && w && dx, "fx_conv_dgrad_img: null argument");
-    P3D_REQUIRE(fx_dgrad_applies(d, 32) && d->K % 16 == 0 && (d->Ho * d->Wo) % 4 == 0, "fx_conv_dgrad_img: shape outside the x3 kernels");
+    P3D_REQUIRE(fx_applies(FX_DGRAD, d, 32) && d->K % 16 == 0 && (d->Ho * d->Wo) % 4 == 0, "fx_conv_dgrad_img: shape outside the x3 kernels");
     FxFuse f{};
     f.act_img = dy_img; f.wimg = wimgT;
     ProfScope ps(1, d, (hipStream_t)stream);
     fx_count(1, d);
-    if (fx_dgrad_has_dead_classes(d) && !d->accumulate)
-        if (hipMemsetAsync(dx, 0, (size_t)d->N * d->C * d->H * d->W * sizeof(float), (hipStream_t)stream) != hipSuccess) { set_error("fx_conv_dgrad_img: memset failed"); return P3D_ELAUNCH; }
+    if (int32_t e = fx_dgrad_zero_dead_classes(d, dx, (hipStream_t)stream)) return e;
     return name_entry("fx_conv_dgrad_img", fx_conv_dgrad(d, nullptr, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream));
 }
 
@@ -924,7 +921,7 @@ int32_t p3d_fx_conv_dgrad_img(const p3d_conv_desc* d, const void* dy_img, const 
 int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
                               void* stream) {
     P3D_REQUIRE(d && dy_img && (x || x_img) && dw, "fx_conv_wgrad_img: null argument");
-    P3D_REQUIRE(fx_wgrad_applies(d, 32) && d->K % 16 == 0 && (!x_img || d->C % 16 == 0), "fx_conv_wgrad_img: shape outside the x3 kernels");
+    P3D_REQUIRE(fx_applies(FX_WGRAD, d, 32) && d->K % 16 == 0 && (!x_img || d->C % 16 == 0), "fx_conv_wgrad_img: shape outside the x3 kernels");
     const int splits = fx_wgrad_splits(d, x_img != nullptr);
     const size_t need = (size_t)splits * d->K * d->C * d->R * d->S * sizeof(float);
     if (!workspace || workspace_bytes < need) { set_error("fx_conv_wgrad_img: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
@@ -943,67 +940,66 @@ int32_t p3d_fx_fold_bn_images(const void* jobs, int32_t njobs, int32_t blocks, v
 }
 
 int32_t p3d_fx_conv_fwd_infer_supported(const p3d_conv_desc* d, int32_t image_fed) {
-    if (!d || d->c_offset != 0 || d->c_total != d->C || d->accumulate < 0 || d->accumulate > 1 || !fx_fwd_applies(d, 32)) return 0;
+    if (!d || d->c_offset != 0 || d->c_total != d->C || d->accumulate < 0 || d->accumulate > 1 || !fx_applies(FX_FWD, d, 32)) return 0;
     return !image_fed || (d->C % 16 == 0 && (d->H * d->W) % 4 == 0) ? 1 : 0;
 }
-size_t p3d_fx_conv_fwd_infer_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_fwd_workspace(d) : 0; }
+size_t p3d_fx_conv_fwd_infer_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_workspace(FX_FWD, d) : 0; }
 // The same at any map width (fx_conv_kernel's ragged instances; split-K: their slabs, then fx_reduce_any_kernel): fp32-fed only
 int32_t p3d_fx_conv_fwd_infer_any_supported(const p3d_conv_desc* d) {
-    return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate >= 0 && d->accumulate <= 1 && fx_fwd_any_applies(d, 32) ? 1 : 0;
+    return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate >= 0 && d->accumulate <= 1 && fx_applies(FX_FWD, d, 32, true) ? 1 : 0;
 }
-size_t p3d_fx_conv_fwd_infer_any_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_fwd_any_workspace(d) : 0; }
+size_t p3d_fx_conv_fwd_infer_any_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_workspace(FX_FWD, d, true) : 0; }
 // The same for a partial convolution (FX_EPI_INFER_FACTOR; split-K: fx_reduce_kernel applies the factor before b')
 int32_t p3d_fx_conv_fwd_infer_masked_supported(const p3d_conv_desc* d) {
-    return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate == 0 && fx_fwd_masked_applies(d) ? 1 : 0;
+    return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate == 0 && fx_masked_applies(FX_FWD, d) ? 1 : 0;
 }
 // The partial convolution at any map width (the ragged PRO-4 instances, FX_EPI_INFER_FACTOR; split-K: their slabs, then fx_reduce_any_kernel with the factor before b')
 int32_t p3d_fx_conv_fwd_infer_masked_any_supported(const p3d_conv_desc* d) {
-    return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate == 0 && fx_fwd_masked_any_applies(d) ? 1 : 0;
+    return d && d->c_offset == 0 && d->c_total == d->C && d->accumulate == 0 && fx_masked_applies(FX_FWD, d, true) ? 1 : 0;
 }
-size_t p3d_fx_conv_fwd_infer_masked_any_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_fwd_any_workspace(d) : 0; }
+size_t p3d_fx_conv_fwd_infer_masked_any_workspace_bytes(const p3d_conv_desc* d) { return d ? fx_workspace(FX_FWD, d, true) : 0; }
 
 // What the four inference entries share: the checks (every text opens with the entry's own name), the profile bracket, the path counter and the launch.
-// f says which entry this is: infer == 2 a ragged one, a pmask a masked one.  (Alignment, ragged: of the base pointers only; inside the tensors the kernel picks
+// f says which entry this is: `ragged` a ragged one, a pmask a masked one.  (Alignment, ragged: of the base pointers only; inside the tensors the kernel picks
 // 16-B or dword accesses by the address.)
-static FxFuse infer_fuse(int infer, const void* x_img, const void* wimg, const float* mask_in, const float* mult, const float* res, int32_t relu) {
+static FxFuse infer_fuse(bool ragged, const void* x_img, const void* wimg, const float* mask_in, const float* mult, const float* res, int32_t relu) {
     FxFuse f{};
-    f.infer = infer; f.act_img = x_img; f.wimg = wimg; f.pmask = mask_in; f.emask = mult; f.res = res; f.relu = relu ? 1 : 0; return f;
+    f.infer = 1; f.ragged = ragged ? 1 : 0; f.act_img = x_img; f.wimg = wimg; f.pmask = mask_in; f.emask = mult; f.res = res; f.relu = relu ? 1 : 0; return f;
 }
 static int32_t fx_infer_entry(const char* name, bool args, const p3d_conv_desc* d, const float* x, size_t wimg_bytes, const float* bias, float* y, const FxFuse& f,
                               void* workspace, size_t workspace_bytes, void* stream) {
     P3D_REQUIRE(args, "%s: null argument", name);
-    const char* kind = f.infer == 2 ? (f.pmask ? "ragged masked " : "ragged ") : f.pmask ? "masked " : "";
+    const char* kind = f.ragged ? (f.pmask ? "ragged masked " : "ragged ") : f.pmask ? "masked " : "";
     char acc[32] = "";
     if (kind[0]) snprintf(acc, sizeof(acc), " accumulate=%d", d->accumulate);
-    P3D_REQUIRE(f.infer == 2 ? (f.pmask ? p3d_fx_conv_fwd_infer_masked_any_supported(d) : p3d_fx_conv_fwd_infer_any_supported(d)) : f.pmask ? p3d_fx_conv_fwd_infer_masked_supported(d) : p3d_fx_conv_fwd_infer_supported(d, f.act_img != nullptr),
+    P3D_REQUIRE(f.ragged ? (f.pmask ? p3d_fx_conv_fwd_infer_masked_any_supported(d) : p3d_fx_conv_fwd_infer_any_supported(d)) : f.pmask ? p3d_fx_conv_fwd_infer_masked_supported(d) : p3d_fx_conv_fwd_infer_supported(d, f.act_img != nullptr),
                 "%s: shape outside the %sx3 kernels (N=%d C=%d %dx%d K=%d R=%d stride=%d c_offset=%d c_total=%d%s)", name, kind, d->N, d->C, d->H, d->W, d->K, d->R, d->stride,
                 d->c_offset, d->c_total, acc);
     const size_t want = fx_weight_image_bytes(d->K, d->C, d->R * d->S, false);
     P3D_REQUIRE(wimg_bytes == want, "%s: weight image of %zu B does not belong to K=%d C=%d RS=%d (%zu B)", name, wimg_bytes, d->K, d->C, d->R * d->S, want);
-    auto u = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-    P3D_REQUIRE(((u(x) | u(y) | u(f.res) | u(f.act_img) | u(f.pmask) | u(f.emask) | u(f.wimg) | u(workspace)) & 15) == 0, "%s: operands must be 16-B aligned", name);
+    P3D_REQUIRE(aligned16(x, y, f.res, f.act_img, f.pmask, f.emask, f.wimg, workspace), "%s: operands must be 16-B aligned", name);
     ProfScope ps(0, d, (hipStream_t)stream);
     fx_count(0, d);
     return name_entry(name, fx_conv_fwd(d, f.act_img ? nullptr : x, nullptr, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
 }
 int32_t p3d_fx_conv_fwd_infer(const p3d_conv_desc* d, const float* x, const void* x_img, const void* wimg, size_t wimg_bytes, const float* bias, const float* res,
                               int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
-    return fx_infer_entry("fx_conv_fwd_infer", d && (x || x_img) && wimg && y, d, x, wimg_bytes, bias, y, infer_fuse(1, x_img, wimg, nullptr, nullptr, res, relu), workspace,
+    return fx_infer_entry("fx_conv_fwd_infer", d && (x || x_img) && wimg && y, d, x, wimg_bytes, bias, y, infer_fuse(false, x_img, wimg, nullptr, nullptr, res, relu), workspace,
                           workspace_bytes, stream);
 }
 int32_t p3d_fx_conv_fwd_infer_any(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* res, int32_t relu,
                                   float* y, void* workspace, size_t workspace_bytes, void* stream) {
-    return fx_infer_entry("fx_conv_fwd_infer_any", d && x && wimg && y, d, x, wimg_bytes, bias, y, infer_fuse(2, nullptr, wimg, nullptr, nullptr, res, relu), workspace,
+    return fx_infer_entry("fx_conv_fwd_infer_any", d && x && wimg && y, d, x, wimg_bytes, bias, y, infer_fuse(true, nullptr, wimg, nullptr, nullptr, res, relu), workspace,
                           workspace_bytes, stream);
 }
 int32_t p3d_fx_conv_fwd_infer_masked(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* mask_in,
                                      const float* mult, const float* res, int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
-    return fx_infer_entry("fx_conv_fwd_infer_masked", d && x && wimg && mask_in && mult && y, d, x, wimg_bytes, bias, y, infer_fuse(1, nullptr, wimg, mask_in, mult, res, relu),
+    return fx_infer_entry("fx_conv_fwd_infer_masked", d && x && wimg && mask_in && mult && y, d, x, wimg_bytes, bias, y, infer_fuse(false, nullptr, wimg, mask_in, mult, res, relu),
                           workspace, workspace_bytes, stream);
 }
 int32_t p3d_fx_conv_fwd_infer_masked_any(const p3d_conv_desc* d, const float* x, const void* wimg, size_t wimg_bytes, const float* bias, const float* mask_in,
                                          const float* mult, const float* res, int32_t relu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
-    return fx_infer_entry("fx_conv_fwd_infer_masked_any", d && x && wimg && mask_in && mult && y, d, x, wimg_bytes, bias, y, infer_fuse(2, nullptr, wimg, mask_in, mult, res, relu),
+    return fx_infer_entry("fx_conv_fwd_infer_masked_any", d && x && wimg && mask_in && mult && y, d, x, wimg_bytes, bias, y, infer_fuse(true, nullptr, wimg, mask_in, mult, res, relu),
                           workspace, workspace_bytes, stream);
 }
 

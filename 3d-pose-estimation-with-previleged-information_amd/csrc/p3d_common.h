@@ -48,6 +48,29 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// every pointer on a 16-B line (NULL counts as aligned)
+template <typename... P> inline bool aligned16(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }
+
+// Taps r in [0,R) with (par + pad - r*dil) % stride == 0 form an arithmetic progression r0 + step*ir; the output
+// coordinate they read is ho = i + off0 - ir*offstep for the class-grid row i (hi = par + stride*i).  The parity classes of a strided data gradient, one axis at a
+// time: the fp32-MFMA kernel (p3d_conv.hip) and the x3 kernels (fx_conv_dgrad, p3d_fx.hip: hoff = off0, hstep = -offstep) take theirs from here.
+inline void fill_class(int par, int R, int stride, int pad, int dil, int* r0, int* step, int* n, int* off0, int* offstep) {
+    *r0 = 0; *step = 1; *n = 0; *off0 = 0; *offstep = 0;
+    int first = -1, second = -1;
+    for (int r = 0; r < R; ++r) {
+        const int t = par + pad - r * dil;
+        if (((t % stride) + stride) % stride != 0) continue;
+        if (first < 0) first = r;
+        else if (second < 0) second = r;
+        ++*n;
+    }
+    if (first < 0) return;
+    *r0 = first;
+    *step = second < 0 ? 1 : second - first;
+    const int t0 = par + pad - first * dil;                 // divisible by stride
+    *off0 = t0 >= 0 ? t0 / stride : -((-t0) / stride);
+    *offstep = (*step * dil) / stride;                        // (step*dil) is a multiple of stride by construction
+}
 
 // MXFP8 (OCP MX v1.0, e4m3fn elements, 32-element blocks) -- the one rule of the fold (p3d_fx.hip kind 3) and the fp8 convolution (p3d_f8conv.hip):
 // e = floor(log2(amax)) from the exponent bits, scale byte E8M0 = clamp(e - 8 + 127, 0, 254) (8: the exponent of 448), X = 2^(byte - 127),

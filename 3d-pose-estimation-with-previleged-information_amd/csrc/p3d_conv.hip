@@ -1040,26 +1040,6 @@ static WgradPlan plan_wgrad(const p3d_conv_desc* d, bool masked) {
     return {cfg, tapm, (int)splits, (int)kchunk};
 }
 
-// Taps r in [0,R) with (par + pad - r*dil) % stride == 0 form an arithmetic progression r0 + step*ir; the output
-// coordinate they read is ho = i + off0 - ir*offstep for the class-grid row i (hi = par + stride*i).
-static void fill_class(int par, int R, int stride, int pad, int dil, int* r0, int* step, int* n, int* off0, int* offstep) {
-    *r0 = 0; *step = 1; *n = 0; *off0 = 0; *offstep = 0;
-    int first = -1, second = -1;
-    for (int r = 0; r < R; ++r) {
-        const int t = par + pad - r * dil;
-        if (((t % stride) + stride) % stride != 0) continue;
-        if (first < 0) first = r;
-        else if (second < 0) second = r;
-        ++*n;
-    }
-    if (first < 0) return;
-    *r0 = first;
-    *step = second < 0 ? 1 : second - first;
-    const int t0 = par + pad - first * dil;                 // divisible by stride
-    *off0 = t0 >= 0 ? t0 / stride : -((-t0) / stride);
-    *offstep = (*step * dil) / stride;                        // (step*dil) is a multiple of stride by construction
-}
-
 }  // namespace p3d
 
 namespace p3d {
@@ -1077,7 +1057,7 @@ int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm,
                                nslab, ldw, woff, d->accumulate);
             return check_launch("conv2d_wgrad reduce16 tapm");
         }
-        if (!(tapm && d->R * d->S > 1) && ldw == Ncols && woff == 0 && (tot & 3) == 0 && ((reinterpret_cast<uintptr_t>(dw) | reinterpret_cast<uintptr_t>(slabs)) & 15) == 0) {
+        if (!(tapm && d->R * d->S > 1) && ldw == Ncols && woff == 0 && (tot & 3) == 0 && aligned16(dw, slabs)) {
             const size_t n4 = tot >> 2;
             const int64_t nb = ceil_div((int64_t)n4, 16);
             hipLaunchKernelGGL(wgrad_reduce16_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, st, (const float*)slabs, dw, n4, nslab, d->accumulate);
@@ -1135,53 +1115,80 @@ static void use_weight_image(IgemmParams& p, const p3d_conv_desc* d, const float
     p.a_bytes = (size_t)d->K * d->C * d->R * d->S * sizeof(float);
 }
 
-struct FwdPlan { int cfg; bool tapm; int splits; int kchunk; };
-
-static FwdPlan plan_fwd(const p3d_conv_desc* d, bool masked, bool allow_split) {
-    FwdPlan pl;
-    const int M = d->K, Ncols = d->N * d->Ho * d->Wo;
-    pl.tapm = d->C >= 16;
-    pl.cfg = pick_cfg(M, Ncols, 1);
-    pl.splits = 1; pl.kchunk = 0;
-    if (!allow_split || masked || !pl.tapm) return pl;
+// The fp32-MFMA split-K plan of a forward (rows = K, columns = N Ho Wo, reduction = C) or a stride-1 data gradient (rows = C, columns = N H W, reduction = K): a launch of
+// <= 400 long-K blocks leaves CUs with 1 or 2 blocks and no tail to even them out (the 256 -> 256 3x3 at 16x16: 256 blocks x 144 K-steps), so the K steps are cut
+// into up to 8 slabs of at least 32, 768 blocks aimed at.
+struct SplitPlan { int cfg, splits, kchunk; };
+static SplitPlan plan_splitk(int rows, int cols, int red, int taps, bool may_split) {
+    const SplitPlan unsplit{pick_cfg(rows, cols, 1), 1, 0};
+    if (!may_split) return unsplit;
     // candidate: the tile with the least padded work if the grid had no tail; if that leaves <= 400 long blocks, split K
     int cfgA = 0;
     double best = 1e300;
     for (int i = 0; i < 6; ++i) {
-        const double cost = (double)ceil_div(M, kCfgs[i].bm) * kCfgs[i].bm * ceil_div(Ncols, kCfgs[i].bn) * kCfgs[i].bn / kCfgs[i].eff;
+        const double cost = (double)ceil_div(rows, kCfgs[i].bm) * kCfgs[i].bm * ceil_div(cols, kCfgs[i].bn) * kCfgs[i].bn / kCfgs[i].eff;
         if (cost < best * 0.999) { best = cost; cfgA = i; }
     }
-    const int64_t blocksA = ceil_div(M, kCfgs[cfgA].bm) * ceil_div(Ncols, kCfgs[cfgA].bn);
-    if (blocksA > 400) return pl;
-    const int cpad = (int)ceil_div(d->C, kCfgs[cfgA].bk) * kCfgs[cfgA].bk;
-    const int nk = d->R * d->S * (cpad / kCfgs[cfgA].bk);
+    const int64_t blocksA = ceil_div(rows, kCfgs[cfgA].bm) * ceil_div(cols, kCfgs[cfgA].bn);
+    if (blocksA > 400) return unsplit;
+    const int nk = taps * (int)ceil_div(red, kCfgs[cfgA].bk);
     int64_t splits = ceil_div(768, blocksA);
     if (splits > nk / 32) splits = nk / 32;
     if (splits > 8) splits = 8;
-    if (splits < 2) return pl;
-    pl.cfg = cfgA;
-    pl.kchunk = (int)ceil_div(nk, splits);
-    pl.splits = (int)ceil_div(nk, pl.kchunk);
-    if (pl.splits < 2) { pl.splits = 1; pl.kchunk = 0; pl.cfg = pick_cfg(M, Ncols, 1); }
-    return pl;
+    if (splits < 2) return unsplit;
+    const int kchunk = (int)ceil_div(nk, splits);
+    if (ceil_div(nk, kchunk) < 2) return unsplit;
+    return {cfgA, (int)ceil_div(nk, kchunk), kchunk};
 }
+// (the forward splits only tap-major launches, C >= 16, and neither pass a partial convolution)
+static SplitPlan plan_fwd(const p3d_conv_desc* d, bool may_split) { return plan_splitk(d->K, d->N * d->Ho * d->Wo, d->C, d->R * d->S, may_split && d->C >= 16); }
+static SplitPlan plan_dgrad1(const p3d_conv_desc* d, bool may_split) { return plan_splitk(d->C, d->N * d->H * d->W, d->K, d->R * d->S, may_split); }
 
-// p3d_x3_any_enable: what the ragged instances take from the per-layer entries -- a dense convolution with whole weights (no channel window) that the aligned predicate
-// of the pass refuses.  The *_any_ok forms do not look at the switch (the public p3d_conv2d_*_any_supported queries).
+// The kernel family one call of p3d_conv2d_fwd / _dgrad / _wgrad lands on, and the workspace that family needs: decided here for the three entries and, with
+// "aligned pointers, unlimited workspace", for their workspace queries, so that a query covers whatever its entry picks.
+//   X3         dense, the aligned predicate of the pass admits;
+//   X3_RAGGED  dense, it refuses for the map width alone, p3d_x3_any_enable is on and the weights are whole (no channel window): the instances for any map width;
+//   X3_MASKED  partial convolution (both factors given; one alone stays on fp32-MFMA) within the masked instances, which take no bias -- written with fx_enabled()
+//              beside the predicate, as the entries always had it (the predicate implies it);
+//   FP32_MFMA  everything else: an eval epilogue (the x3 entries of p3d_block.hip have their own), an operand off a 16-B line, a refused shape.
+// A forward or data gradient whose workspace is too small for its x3 family quietly runs on fp32-MFMA instead.  The weight gradient does NOT look at workspace_bytes
+// here: it stays on x3 and its entry fails with P3D_EWORKSPACE (both paths need slabs; the x3 plan usually the larger).
+struct ConvRoute { enum Family { FP32_MFMA, X3, X3_RAGGED, X3_MASKED } family; size_t x3_bytes; };
 static bool whole_weight(const p3d_conv_desc* d) { return d->c_offset == 0 && d->c_total == d->C; }
-static bool fwd_any_ok(const p3d_conv_desc* d) { return whole_weight(d) && fx_fwd_any_applies(d); }
-static bool dgrad_any_ok(const p3d_conv_desc* d) { return whole_weight(d) && fx_dgrad_any_applies(d); }
-static bool wgrad_any_ok(const p3d_conv_desc* d) { return whole_weight(d) && fx_wgrad_any_applies(d); }
-static bool fwd_ragged(const p3d_conv_desc* d) { return fx_any_enabled() && !fx_fwd_applies(d) && fwd_any_ok(d); }
-static bool dgrad_ragged(const p3d_conv_desc* d) { return fx_any_enabled() && !fx_dgrad_applies(d) && dgrad_any_ok(d); }
-static bool wgrad_ragged(const p3d_conv_desc* d) { return fx_any_enabled() && !fx_wgrad_applies(d) && wgrad_any_ok(d); }
+static bool any_ok(FxPass pass, const p3d_conv_desc* d) { return whole_weight(d) && fx_applies(pass, d, 96, true); }      // (the public p3d_conv2d_*_any_supported: not the switch)
+static ConvRoute conv_route(FxPass pass, const p3d_conv_desc* d, int masks /* factors given: 0, 1, 2 */, bool eval_epilogue, bool bias, bool aligned, size_t workspace_bytes) {
+    ConvRoute r{ConvRoute::FP32_MFMA, 0};
+    if (eval_epilogue || !aligned || masks == 1) return r;
+    if (masks) { if (!bias && fx_enabled() && fx_masked_applies(pass, d)) r.family = ConvRoute::X3_MASKED; }
+    else if (fx_applies(pass, d)) r.family = ConvRoute::X3;
+    else if (fx_any_enabled() && any_ok(pass, d)) r.family = ConvRoute::X3_RAGGED;
+    if (r.family == ConvRoute::FP32_MFMA) return r;
+    const bool ragged = r.family == ConvRoute::X3_RAGGED;
+    r.x3_bytes = pass == FX_WGRAD ? (size_t)fx_wgrad_splits(d, false, ragged) * d->K * d->C * d->R * d->S * sizeof(float) : fx_workspace(pass, d, ragged);
+    if (pass != FX_WGRAD && workspace_bytes < r.x3_bytes) return ConvRoute{ConvRoute::FP32_MFMA, 0};
+    return r;
+}
+// what a query reserves for the x3 families: the larger of the dense and the masked route
+static size_t x3_query_bytes(FxPass pass, const p3d_conv_desc* d) {
+    const size_t dense = conv_route(pass, d, 0, false, false, true, SIZE_MAX).x3_bytes, masked = conv_route(pass, d, 2, false, false, true, SIZE_MAX).x3_bytes;
+    return dense > masked ? dense : masked;
+}
+// the FxFuse of a routed call (pmask: the operand's factor, emask: the result's; the weight gradient: dy's and x's)
+static FxFuse route_fuse(const ConvRoute& r, const float* pmask, const float* emask) {
+    FxFuse f{};
+    switch (r.family) {
+        case ConvRoute::X3_RAGGED: f.ragged = 1; break;                          // the same arithmetic at a map width that is no multiple of 4
+        case ConvRoute::X3_MASKED: f.pmask = pmask; f.emask = emask; break;      // the operand times pmask in the fetch, the result times emask in the epilogue
+        default: break;                                                          // X3: exact fp32 on the bf16 matrix pipe (p3d_fx.hip), the default path of the dense layers
+    }
+    return f;
+}
 
 size_t p3d_conv2d_fwd_workspace_bytes(const p3d_conv_desc* d) {
     if (validate(d)) return 0;
-    const FwdPlan pl = plan_fwd(d, false, true);
+    const SplitPlan pl = plan_fwd(d, true);
     const size_t base = weight_image_bytes(d) + (pl.splits > 1 ? (size_t)pl.splits * d->N * d->K * d->Ho * d->Wo * sizeof(float) : 0);
-    size_t fx = (fx_fwd_applies(d) || fx_fwd_masked_applies(d)) ? fx_fwd_workspace(d) : 0;
-    if (fwd_ragged(d) && fx_fwd_any_workspace(d) > fx) fx = fx_fwd_any_workspace(d);
+    const size_t fx = x3_query_bytes(FX_FWD, d);
     return base > fx ? base : fx;
 }
 
@@ -1190,25 +1197,12 @@ static int32_t conv2d_fwd_impl(const p3d_conv_desc* d, const float* x, const flo
                                const float* ep_res, int ep_relu) {
     if (int32_t e = validate(d)) return e;
     P3D_REQUIRE(x && w && y, "conv2d_fwd: null tensor");
-    if (!mask_in && !mult && !ep_scale && !ep_res && !ep_relu && fx_fwd_applies(d) && workspace_bytes >= fx_fwd_workspace(d) &&
-        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0) {
-        fx_count(0, d);          // exact fp32 on the bf16 matrix pipe (p3d_fx.hip), the default path of the dense layers
-        return fx_conv_fwd(d, x, w, bias, y, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
-    }
-    if (!mask_in && !mult && !ep_scale && !ep_res && !ep_relu && fwd_ragged(d) && workspace_bytes >= fx_fwd_any_workspace(d) &&
-        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0) {
-        fx_count(0, d);          // the same arithmetic at a map width that is no multiple of 4: the ragged instances (p3d_x3_any_enable)
-        FxFuse f{};
-        f.ragged = 1;
+    const ConvRoute route = conv_route(FX_FWD, d, (mask_in != nullptr) + (mult != nullptr), ep_scale || ep_res || ep_relu, bias != nullptr,
+                                       aligned16(x, w, y, workspace, mask_in, mult), workspace_bytes);
+    if (route.family != ConvRoute::FP32_MFMA) {
+        fx_count(0, d);
+        const FxFuse f = route_fuse(route, mask_in, mult);
         return fx_conv_fwd(d, x, w, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
-    }
-    if (mask_in && mult && !bias && !ep_scale && !ep_res && !ep_relu && fx_enabled() && fx_fwd_masked_applies(d) && workspace_bytes >= fx_fwd_workspace(d) &&
-        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(workspace) |
-          reinterpret_cast<uintptr_t>(mask_in) | reinterpret_cast<uintptr_t>(mult)) & 15) == 0) {
-        fx_count(0, d);          // partial convolution on the same kernels: x * mask_in in the operand fetch, * mult in the epilogue
-        FxFuse f{};
-        f.pmask = mask_in; f.emask = mult;
-        return fx_conv_fwd(d, x, w, nullptr, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
     }
     fx_count(3, d);
     IgemmParams p = base_params(d);
@@ -1216,14 +1210,15 @@ static int32_t conv2d_fwd_impl(const p3d_conv_desc* d, const float* x, const flo
     p.ep_scale = ep_scale; p.ep_shift = ep_shift; p.ep_res = ep_res; p.ep_relu = ep_relu;
     p.M = d->K; p.Ncols = d->N * d->Ho * d->Wo; p.Kd = d->C * d->R * d->S;
     const bool masked = mask_in || mult;
-    FwdPlan pl = plan_fwd(d, masked, true);
+    const bool tapm = d->C >= 16;
+    SplitPlan pl = plan_fwd(d, !masked);
     const size_t ysize = (size_t)d->N * d->K * d->Ho * d->Wo;
     const size_t wimg = weight_image_bytes(d);
-    if (wimg && pl.tapm && workspace && workspace_bytes >= wimg) {      // tap-major weight image at the head of the workspace
+    if (wimg && tapm && workspace && workspace_bytes >= wimg) {      // tap-major weight image at the head of the workspace
         use_weight_image(p, d, w, (float*)workspace, (hipStream_t)stream);
         workspace = (char*)workspace + wimg; workspace_bytes -= wimg;
     }
-    if (pl.splits > 1 && (!workspace || workspace_bytes < pl.splits * ysize * sizeof(float))) pl = plan_fwd(d, masked, false);   // no scratch: unsplit
+    if (pl.splits > 1 && (!workspace || workspace_bytes < pl.splits * ysize * sizeof(float))) pl = plan_fwd(d, false);   // no scratch: unsplit
     p.cpad = (int)ceil_div(d->C, kCfgs[pl.cfg].bk) * kCfgs[pl.cfg].bk;
     if (pl.splits > 1) {
         p.Cout = (float*)workspace; p.bias = nullptr; p.accumulate = 0; p.ep_scale = nullptr;      // the epilogue runs in the reduce pass
@@ -1235,7 +1230,7 @@ static int32_t conv2d_fwd_impl(const p3d_conv_desc* d, const float* x, const flo
                            d->Ho * d->Wo, pl.splits, d->accumulate, ep_scale, ep_shift, ep_res, ep_relu);
         return check_launch("conv2d_fwd reduce");
     }
-    launch_igemm<MODE_FWD>(pl.cfg, pl.tapm, masked, p, 1, (hipStream_t)stream);
+    launch_igemm<MODE_FWD>(pl.cfg, tapm, masked, p, 1, (hipStream_t)stream);
     return check_launch("conv2d_fwd");
 }
 
@@ -1275,47 +1270,16 @@ int32_t p3d_conv2d_bn_eval_fwd(const p3d_conv_desc* d, const float* x, const flo
     return conv2d_fwd_impl(d, x, w, nullptr, nullptr, nullptr, y, (char*)workspace + head, workspace_bytes - head, stream, coef, coef + d->K, res, relu);
 }
 
-// stride-1 dgrad split-K, same reasoning as the forward one (few long blocks: 256 -> 256 3x3 at 16x16 is 256 blocks x 144 K-steps)
-static FwdPlan plan_dgrad1(const p3d_conv_desc* d, bool masked) {
-    FwdPlan pl;
-    const int M = d->C, Ncols = d->N * d->H * d->W;
-    pl.tapm = true;
-    pl.cfg = pick_cfg(M, Ncols, 1);
-    pl.splits = 1; pl.kchunk = 0;
-    if (masked) return pl;
-    int cfgA = 0;
-    double best = 1e300;
-    for (int i = 0; i < 6; ++i) {
-        const double cost = (double)ceil_div(M, kCfgs[i].bm) * kCfgs[i].bm * ceil_div(Ncols, kCfgs[i].bn) * kCfgs[i].bn / kCfgs[i].eff;
-        if (cost < best * 0.999) { best = cost; cfgA = i; }
-    }
-    const int64_t blocksA = ceil_div(M, kCfgs[cfgA].bm) * ceil_div(Ncols, kCfgs[cfgA].bn);
-    if (blocksA > 400) return pl;
-    const int cpad = (int)ceil_div(d->K, kCfgs[cfgA].bk) * kCfgs[cfgA].bk;
-    const int nk = d->R * d->S * (cpad / kCfgs[cfgA].bk);
-    int64_t splits = ceil_div(768, blocksA);
-    if (splits > nk / 32) splits = nk / 32;
-    if (splits > 8) splits = 8;
-    if (splits < 2) return pl;
-    pl.cfg = cfgA;
-    pl.kchunk = (int)ceil_div(nk, splits);
-    pl.splits = (int)ceil_div(nk, pl.kchunk);
-    if (pl.splits < 2) { pl.splits = 1; pl.kchunk = 0; pl.cfg = pick_cfg(M, Ncols, 1); }
-    return pl;
-}
-
 size_t p3d_conv2d_dgrad_workspace_bytes(const p3d_conv_desc* d) {
     if (validate(d)) return 0;
+    const size_t fx = x3_query_bytes(FX_DGRAD, d);
     if (d->stride == 1) {
-        const FwdPlan pl = plan_dgrad1(d, false);
+        const SplitPlan pl = plan_dgrad1(d, true);
         const size_t base = weight_image_bytes(d) + (pl.splits > 1 ? (size_t)pl.splits * d->N * d->C * d->H * d->W * sizeof(float) : 0);
-        size_t fx = (fx_dgrad_applies(d) || fx_dgrad_masked_applies(d)) ? fx_dgrad_workspace(d) : 0;
-        if (dgrad_ragged(d) && fx_dgrad_any_workspace(d) > fx) fx = fx_dgrad_any_workspace(d);
         return base > fx ? base : fx;
     }
     const size_t hc = (size_t)ceil_div(d->H, d->stride), wc = (size_t)ceil_div(d->W, d->stride);
     const size_t staged = (size_t)d->stride * d->stride * d->N * d->C * hc * wc * sizeof(float);
-    const size_t fx = (fx_dgrad_applies(d) || fx_dgrad_masked_applies(d)) ? fx_dgrad_workspace(d) : 0;
     return staged > fx ? staged : fx;
 }
 
@@ -1324,28 +1288,11 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
     if (int32_t e = validate(d)) return e;
     P3D_REQUIRE(dy && w && dx, "conv2d_dgrad: null tensor");
     ProfScope ps(1, d, (hipStream_t)stream);
-    if (!mask_in && !mult && fx_dgrad_applies(d) && workspace_bytes >= fx_dgrad_workspace(d) &&
-        ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0) {
+    const ConvRoute route = conv_route(FX_DGRAD, d, (mask_in != nullptr) + (mult != nullptr), false, false, aligned16(dy, w, dx, workspace, mask_in, mult), workspace_bytes);
+    if (route.family != ConvRoute::FP32_MFMA) {
         fx_count(1, d);
-        if (fx_dgrad_has_dead_classes(d) && !d->accumulate)          // input pixels no tap reaches (1x1, stride 2) must read zero
-            (void)hipMemsetAsync(dx, 0, (size_t)d->N * d->C * d->H * d->W * sizeof(float), (hipStream_t)stream);
-        return fx_conv_dgrad(d, dy, w, dx, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
-    }
-    if (!mask_in && !mult && dgrad_ragged(d) && workspace_bytes >= fx_dgrad_any_workspace(d) &&
-        ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0) {
-        fx_count(1, d);          // stride 1 at any map width: the ragged forward instances over dy (p3d_x3_any_enable)
-        FxFuse f{};
-        f.ragged = 1;
-        return fx_conv_dgrad(d, dy, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream);
-    }
-    if (mask_in && mult && fx_enabled() && fx_dgrad_masked_applies(d) && workspace_bytes >= fx_dgrad_workspace(d) &&
-        ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(workspace) |
-          reinterpret_cast<uintptr_t>(mask_in) | reinterpret_cast<uintptr_t>(mult)) & 15) == 0) {
-        fx_count(1, d);          // partial convolution: dy * mult in the operand fetch, * mask_in in the epilogue
-        if (fx_dgrad_has_dead_classes(d) && !d->accumulate)
-            (void)hipMemsetAsync(dx, 0, (size_t)d->N * d->C * d->H * d->W * sizeof(float), (hipStream_t)stream);
-        FxFuse f{};
-        f.pmask = mult; f.emask = mask_in;
+        if (int32_t e = fx_dgrad_zero_dead_classes(d, dx, (hipStream_t)stream)) return e;      // input pixels no tap reaches (1x1, stride 2) must read zero
+        const FxFuse f = route_fuse(route, mult, mask_in);
         return fx_conv_dgrad(d, dy, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream);
     }
     fx_count(4, d);
@@ -1369,7 +1316,7 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
     const int cfg = pick_cfg(p.M, p.Ncols, nlive > 0 ? nlive : 1);     // classes no tap reaches exit at once
     p.cpad = (int)ceil_div(d->K, kCfgs[cfg].bk) * kCfgs[cfg].bk;
     if (st == 1) {
-        const FwdPlan pl = plan_dgrad1(d, masked);
+        const SplitPlan pl = plan_dgrad1(d, !masked);
         const size_t xsize = (size_t)d->N * d->C * d->H * d->W;
         const size_t wimg = weight_image_bytes(d);
         if (wimg && workspace && workspace_bytes >= wimg) {
@@ -1404,7 +1351,7 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
     launch_igemm<MODE_DGRAD>(cfg, true, masked && mult != nullptr, p, p.ncls, (hipStream_t)stream);
     if (int32_t e = check_launch("conv2d_dgrad")) return e;
     const int64_t total = (int64_t)d->N * d->C * d->H * d->W;
-    if (st == 2 && d->W % 4 == 0 && ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(mask_in)) & 15) == 0) {
+    if (st == 2 && d->W % 4 == 0 && aligned16(dx, workspace, mask_in)) {
         const unsigned blocks4 = (unsigned)(ceil_div(total / 4, 256) < 8192 ? ceil_div(total / 4, 256) : 8192);
         hipLaunchKernelGGL(dgrad_interleave2_kernel, dim3(blocks4), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dx, mask_in,
                            d->N * d->C, d->C, d->H, d->W, p.cls_stride, live, d->accumulate);
@@ -1420,10 +1367,9 @@ size_t p3d_conv2d_wgrad_workspace_bytes(const p3d_conv_desc* d) {
     if (validate(d)) return 0;
     // the larger of the masked / unmasked plans, so one query serves both
     const WgradPlan a = plan_wgrad(d, false), b = plan_wgrad(d, true);
-    int splits = a.splits > b.splits ? a.splits : b.splits;
-    if (fx_wgrad_applies(d) && fx_wgrad_splits(d) > splits) splits = fx_wgrad_splits(d);
-    if (wgrad_ragged(d) && fx_wgrad_splits(d, false, true) > splits) splits = fx_wgrad_splits(d, false, true);
-    return (size_t)splits * d->K * d->C * d->R * d->S * sizeof(float);
+    const int splits = a.splits > b.splits ? a.splits : b.splits;
+    const size_t base = (size_t)splits * d->K * d->C * d->R * d->S * sizeof(float), fx = x3_query_bytes(FX_WGRAD, d);
+    return base > fx ? base : fx;
 }
 
 int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x, const float* mult,
@@ -1433,13 +1379,11 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
     ProfScope ps(2, d, (hipStream_t)stream);
     const bool masked = mask_in || mult;
     WgradPlan pl = plan_wgrad(d, masked);
-    const bool fxm = mask_in && mult && fx_enabled() && fx_wgrad_masked_applies(d) &&
-                     ((reinterpret_cast<uintptr_t>(mask_in) | reinterpret_cast<uintptr_t>(mult)) & 15) == 0;          // partial convolution: dy * mult, x * mask_in in the fetch
-    const bool fx = (!masked || fxm) && fx_wgrad_applies(d) && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0;
-    // any map width (p3d_x3_any_enable): the same slabs from fx_wgrad_any_kernel
-    const bool fxr = !fx && !masked && wgrad_ragged(d) && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0;
-    if (fx || fxr) { pl.splits = fx_wgrad_splits(d, false, fxr); pl.tapm = d->R * d->S > 1; }      // slabs [split][k][tap][c]: the tap-major columns of wgrad_reduce_tapm_kernel
-    fx_count(fx || fxr ? 2 : 5, d);
+    // (a short workspace does not move the route: see conv_route)
+    const ConvRoute route = conv_route(FX_WGRAD, d, (mask_in != nullptr) + (mult != nullptr), false, false, aligned16(dy, x, workspace, mask_in, mult), workspace_bytes);
+    const bool fx = route.family != ConvRoute::FP32_MFMA;
+    if (fx) { pl.splits = fx_wgrad_splits(d, false, route.family == ConvRoute::X3_RAGGED); pl.tapm = d->R * d->S > 1; }      // slabs [split][k][tap][c]: the tap-major columns of wgrad_reduce_tapm_kernel
+    fx_count(fx ? 2 : 5, d);
     const size_t need = (size_t)pl.splits * d->K * d->C * d->R * d->S * sizeof(float);
     if (!workspace || workspace_bytes < need) {
         set_error("conv2d_wgrad: workspace %zu B < required %zu B", workspace_bytes, need);
@@ -1456,19 +1400,12 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
     p.kchunk = pl.kchunk;
     p.cpad = d->C;
     int wv = 0;
-    const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };     // NULL counts as aligned
-    if ((d->Ho * d->Wo) % 4 == 0 && al16(dy) && al16(mult)) {
+    if ((d->Ho * d->Wo) % 4 == 0 && aligned16(dy, mult)) {
         wv = 1;
-        if (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0 && al16(x) && al16(mask_in)) wv = 2;
+        if (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0 && aligned16(x, mask_in)) wv = 2;
     }
     if (fx) {
-        FxFuse f{};
-        f.pmask = mult; f.emask = mask_in;
-        if (int32_t e = fx_conv_wgrad_slabs(d, dy, x, (float*)workspace, pl.splits, masked ? &f : nullptr, (hipStream_t)stream)) return e;
-    }
-    else if (fxr) {
-        FxFuse f{};
-        f.ragged = 1;
+        const FxFuse f = route_fuse(route, mult, mask_in);
         if (int32_t e = fx_conv_wgrad_slabs(d, dy, x, (float*)workspace, pl.splits, &f, (hipStream_t)stream)) return e;
     }
     else launch_igemm<MODE_WGRAD>(pl.cfg, pl.tapm, masked, p, pl.splits, (hipStream_t)stream, wv);
@@ -1479,9 +1416,9 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
 int32_t p3d_x3_enable(int32_t on) { return fx_set_enabled(on); }
 int32_t p3d_x3_any_enable(int32_t on) { return fx_set_any_enabled(on); }
 // what the ragged instances admit, whatever the switch says
-int32_t p3d_conv2d_fwd_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && fwd_any_ok(d) ? 1 : 0; }
-int32_t p3d_conv2d_dgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && dgrad_any_ok(d) ? 1 : 0; }
-int32_t p3d_conv2d_wgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && wgrad_any_ok(d) ? 1 : 0; }
+int32_t p3d_conv2d_fwd_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && any_ok(FX_FWD, d) ? 1 : 0; }
+int32_t p3d_conv2d_dgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && any_ok(FX_DGRAD, d) ? 1 : 0; }
+int32_t p3d_conv2d_wgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && any_ok(FX_WGRAD, d) ? 1 : 0; }
 void p3d_fx_tune(int32_t what, int32_t value) { fx_tune(what, value); }
 
 void p3d_conv_path_stats(uint64_t* counts, double* flops, int32_t reset) {

@@ -75,11 +75,12 @@ struct FxFuse {
     const unsigned char* acc_mask;
     // FWD, inference (a conv with its eval-mode BatchNorm folded into the weight image and the bias): y = conv + bias (+ y when accumulating) (+ res) (then ReLU), on
     // the split-K path applied by the reduce pass after the slabs are summed
-    int infer;              // 1; 2: on the ragged instances (any map width; fp32 operand, dense; a partial convolution with pmask and emask)
+    int infer;              // 0 / 1
     const float* res;
     int relu;
-    int ragged;             // 1: FWD / DGRAD (stride 1) on the ragged instances with the plain epilogue, WGRAD on fx_wgrad_any_kernel: dense fp32-fed training launches at any
-                            // map width (p3d_x3_any_enable); no other field set
+    int ragged;             // 1: the ragged instances (any map width), for inference and training alike; fp32 operands only.  With `infer`: dense, or a partial convolution
+                            // with pmask and emask.  Without: FWD / DGRAD (stride 1) with the plain epilogue, WGRAD on fx_wgrad_any_kernel -- dense fp32-fed training
+                            // launches (p3d_x3_any_enable), no other field set
 };
 constexpr int FX_TAB = 8;   // floats per channel of a table
 
@@ -121,26 +122,20 @@ bool fx_any_enabled();                  // p3d_x3_any_enable / P3D_X3_ANY=1 (def
 int fx_set_any_enabled(int on);
 void fx_count(int kind, const p3d_conv_desc* d);
 void fx_stats(unsigned long long* counts, double* flops, int reset);
-bool fx_fwd_applies(const p3d_conv_desc* d, int min_m = 96);
-bool fx_fwd_any_applies(const p3d_conv_desc* d, int min_m = 96);       // the ragged forward: fx_fwd_applies without W % 4 == 0 and Wo % 4 == 0 (FxFuse::infer == 2)
-bool fx_dgrad_applies(const p3d_conv_desc* d, int min_m = 96);
-bool fx_wgrad_applies(const p3d_conv_desc* d, int min_m = 96);
-bool fx_dgrad_any_applies(const p3d_conv_desc* d, int min_m = 96);     // the ragged data gradient: stride 1, without Wo % 4 == 0 and W % 4 == 0 (FxFuse::ragged)
-bool fx_wgrad_any_applies(const p3d_conv_desc* d, int min_m = 96);     // the ragged weight gradient: without (Ho Wo) % 16 == 0, Wo % 4 == 0 and W % 4 == 0 (FxFuse::ragged)
+// Which convolutions the x3 kernels take, per pass: one rule each (p3d_fx.hip).  min_m: the least channel count of the result's tile rows the caller finds worth it (96:
+// the per-layer entries; 64: the block executor; 32: image-fed and inference callers).  ragged: the instances that take any map width -- the same rule without its
+// width / alignment clauses (forward: W % 4, Wo % 4; data gradient: those, and stride 1 only; weight gradient: (Ho Wo) % 16, Wo % 4, W % 4), so it cannot drift
+// from the aligned one.
+enum FxPass { FX_FWD, FX_DGRAD, FX_WGRAD };
+bool fx_applies(FxPass pass, const p3d_conv_desc* d, int min_m = 96, bool ragged = false);
+bool fx_masked_applies(FxPass pass, const p3d_conv_desc* d, bool ragged = false);      // partial convolutions: the masked instances exist for unsplit launches without bias (ragged: forward, inference only)
+size_t fx_workspace(FxPass pass, const p3d_conv_desc* d, bool ragged = false);         // FX_FWD / FX_DGRAD: weight image + split-K slabs of the call's plan; FX_WGRAD: slabs for the larger of the two
+                                                                                       // split counts (fp32- or image-fed x), what a caller reserves before it knows which
+int fx_partial_rows(FxPass pass, const p3d_conv_desc* d);                              // FX_FWD / FX_DGRAD: rows of the per-channel partial sums of a launch with a sums epilogue
 bool fx_dgrad_has_dead_classes(const p3d_conv_desc* d);
+int32_t fx_dgrad_zero_dead_classes(const p3d_conv_desc* d, float* dx, hipStream_t st);      // zero-fills dx when the call does not accumulate and leaves such pixels untouched
 bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d);      // stride 1 and no split-K: FxFuse::acc_src is honoured
-bool fx_fwd_masked_applies(const p3d_conv_desc* d);          // partial convolutions: the masked instances exist for unsplit launches without bias
-bool fx_fwd_masked_any_applies(const p3d_conv_desc* d);      // the same at any map width (the ragged PRO-4 instances, inference only)
-bool fx_dgrad_masked_applies(const p3d_conv_desc* d);
-bool fx_wgrad_masked_applies(const p3d_conv_desc* d);
-size_t fx_fwd_workspace(const p3d_conv_desc* d);
-size_t fx_fwd_any_workspace(const p3d_conv_desc* d);
-size_t fx_dgrad_workspace(const p3d_conv_desc* d);
-size_t fx_dgrad_any_workspace(const p3d_conv_desc* d);
-int fx_partial_rows_fwd(const p3d_conv_desc* d);
-int fx_partial_rows_dgrad(const p3d_conv_desc* d);
 int fx_wgrad_splits(const p3d_conv_desc* d, bool images = false, bool ragged = false);      // images: dy AND x arrive as images (the slab count of fx_wgrad_two_taps layers differs)
-size_t fx_wgrad_workspace(const p3d_conv_desc* d);       // slab bytes for the larger of the two split counts (fp32- or image-fed x): what a caller reserves before it knows which
 int fx_wgrad_two_taps(const p3d_conv_desc* d, bool images);      // taps per column tile: 0 (one-tap tiles), 2 or 3
 int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, const float* bias, float* y, void* workspace, size_t workspace_bytes,
                     const FxFuse* fuse, hipStream_t st);

@@ -146,7 +146,7 @@ __device__ __forceinline__ FxConvParams fx_class_params(const FxConvParams& in) 
 }
 
 // TAPI (image-fed multi-tap launches of wide layers, FxConvParams::tap_inner): the K steps walk the taps innermost
-// RAG ("ragged", fx_conv_fwd with FxFuse::infer == 2): map widths that are not multiples of 4.  The GEMM column stays the flat pixel index, so a thread's four
+// RAG ("ragged", fx_conv_fwd with FxFuse::ragged): map widths that are not multiples of 4.  The GEMM column stays the flat pixel index, so a thread's four
 // consecutive pixels may straddle an output row or an image: their positions are derived per element when the tap changes, from the first pixel's (row, column,
 // image) kept across the K loop; every fetch is a dword load, and the dense store falls back to dword accesses wherever four pixels do not share an image or a
 // 16-B line.  fp32-fed forward only, epilogues 8 (inference) and 0 (split-K slabs); as a partial convolution (PRO 4) epilogues 9 and 0: the operand factor is fetched
@@ -1110,7 +1110,7 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
     const int a3_dh = (a3_tap / p.S) * p.dil - p.pad, a3_dw = (a3_tap - (a3_tap / p.S) * p.S) * p.dil - p.pad;
     const bool a3_ok = a3_tap < p.R * p.S;
     // Buffer-load fetch (see fx_conv_kernel): per-thread byte offsets with the out-of-range bit for rows beyond the tensor / padding pixels, the image and
-    // pixel position of the K step in a wave-uniform scalar offset.  (fx_wgrad_applies bounds every tensor below 2^29 elements.)
+    // pixel position of the K step in a wave-uniform scalar offset.  (fx_applies(FX_WGRAD) bounds every tensor below 2^29 elements.)
     i32x4 rA, rB, rAi[3], rBi[3];
     if constexpr (AIMG) {
 #pragma unroll
@@ -1828,33 +1828,24 @@ static bool fx_common(const p3d_conv_desc* d) {
            (int64_t)d->N * d->C * d->H * d->W < (1ll << 31) && (int64_t)d->N * d->K * d->Ho * d->Wo < (1ll << 31) &&
            (int64_t)(d->K + 127) * (d->C + 127) * d->R * d->S * 6 < (1ll << 31);          // (32-bit byte offsets into the weight images)
 }
-// forward: reduction channels C in steps of 16, four consecutive output pixels in one row, a reasonably filled channel tile
-bool fx_fwd_applies(const p3d_conv_desc* d, int min_m) {
-    return fx_common(d) && d->C % FX_BK == 0 && d->C >= 32 && d->Wo % 4 == 0 && d->W % 4 == 0 && d->K >= min_m;
-}
-// the ragged forward (fx_conv_kernel's RAG instances): fx_fwd_applies without its two width clauses
-bool fx_fwd_any_applies(const p3d_conv_desc* d, int min_m) {
-    return fx_common(d) && d->C % FX_BK == 0 && d->C >= 32 && d->K >= min_m;
-}
-// dgrad: reduction channels K in steps of 16; the GEMM columns are the pixels of one stride^2 parity class of the input
-bool fx_dgrad_applies(const p3d_conv_desc* d, int min_m) {
-    if (!(fx_common(d) && d->K % FX_BK == 0 && d->K >= 32 && d->C % 4 == 0 && d->C >= min_m && d->Wo % 4 == 0)) return false;
-    if (d->stride == 1) return d->W % 4 == 0;
-    return d->H % 2 == 0 && d->W % 8 == 0 && d->pad == d->dil * (d->R - 1) / 2 && (d->R == 1 || d->dil == 1);      // stride 2: classes of equal size
-}
-bool fx_wgrad_applies(const p3d_conv_desc* d, int min_m) {
-    if ((int64_t)d->N * d->C * d->H * d->W >= (1ll << 29) || (int64_t)d->N * d->K * d->Ho * d->Wo >= (1ll << 29)) return false;      // 32-bit byte offsets into whole tensors
-    return fx_common(d) && d->K >= min_m && d->C >= min_m && (d->Ho * d->Wo) % FX_BK == 0 && d->Wo % 4 == 0 && d->W % 4 == 0 && (d->R == 1 || d->C % 64 == 0);
-}
-// the ragged data gradient (the ragged forward instances over dy): fx_dgrad_applies' stride-1 branch without its two width clauses.  (Stride 2: the parity classes of an
-// odd map differ in size -- the fp32-MFMA kernel keeps those)
-bool fx_dgrad_any_applies(const p3d_conv_desc* d, int min_m) {
-    return fx_common(d) && d->K % FX_BK == 0 && d->K >= 32 && d->C % 4 == 0 && d->C >= min_m && d->stride == 1;
-}
-// the ragged weight gradient (fx_wgrad_any_kernel): fx_wgrad_applies without OHW % 16 == 0, Wo % 4 == 0 and W % 4 == 0
-bool fx_wgrad_any_applies(const p3d_conv_desc* d, int min_m) {
-    if ((int64_t)d->N * d->C * d->H * d->W >= (1ll << 29) || (int64_t)d->N * d->K * d->Ho * d->Wo >= (1ll << 29)) return false;
-    return fx_common(d) && d->K >= min_m && d->C >= min_m && (d->R == 1 || d->C % 64 == 0);
+// The shape rule of each pass, written once.  `ragged`: the instances that take any map width (fx_conv_kernel's RAG instances, fx_wgrad_any_kernel) -- the same rule
+// with its width / alignment clauses switched off, and for the data gradient "stride 1 only" switched on (the parity classes of an odd map differ in size: the
+// fp32-MFMA kernel keeps those).
+bool fx_applies(FxPass pass, const p3d_conv_desc* d, int min_m, bool ragged) {
+    if (!fx_common(d)) return false;
+    const bool widths = ragged || (d->W % 4 == 0 && d->Wo % 4 == 0);      // four consecutive pixels of one row per 16-B access
+    switch (pass) {
+        case FX_FWD:          // reduction channels C in steps of 16, a reasonably filled channel tile
+            return widths && d->C % FX_BK == 0 && d->C >= 32 && d->K >= min_m;
+        case FX_DGRAD:        // reduction channels K in steps of 16; the GEMM columns are the pixels of one stride^2 parity class of the input
+            if (!(widths && d->K % FX_BK == 0 && d->K >= 32 && d->C % 4 == 0 && d->C >= min_m)) return false;
+            if (d->stride == 1) return true;
+            return !ragged && d->H % 2 == 0 && d->W % 8 == 0 && d->pad == d->dil * (d->R - 1) / 2 && (d->R == 1 || d->dil == 1);      // stride 2: classes of equal size
+        case FX_WGRAD:        // the reduction runs over pixels in steps of 16; 32-bit byte offsets into whole tensors
+            if ((int64_t)d->N * d->C * d->H * d->W >= (1ll << 29) || (int64_t)d->N * d->K * d->Ho * d->Wo >= (1ll << 29)) return false;
+            return (ragged || (widths && (d->Ho * d->Wo) % FX_BK == 0)) && d->K >= min_m && d->C >= min_m && (d->R == 1 || d->C % 64 == 0);
+    }
+    return false;
 }
 
 // p3d_fx_tune(0 / 1 / 2, n): forced split counts (weight gradient, forward / data gradient) and a forced weight-gradient block target; 0 = the built-in plan
@@ -1989,22 +1980,19 @@ static FxPlan fx_plan(const p3d_conv_desc* d, bool dgrad, bool ragged = false) {
     s.partial_rows = s.splits > 1 ? (d->N < 16 ? d->N : 16) : (int)ceil_div(pixels, FX_BN);
     return s;
 }
-// partial convolutions (PRO 4 / EPI 4 instances): 64-channel layers included (half-dead tiles), unsplit launches only
-static bool fx_masked_on() { static const bool on = [] { const char* e = getenv("P3D_FX_MASKED"); return !(e && atoi(e) == 0); }(); return on; }      // A/B switch
-bool fx_fwd_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_fwd_applies(d, 64); }
-bool fx_fwd_masked_any_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_fwd_any_applies(d, 64); }
-bool fx_dgrad_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_dgrad_applies(d, 64); }
-bool fx_wgrad_masked_applies(const p3d_conv_desc* d) { return fx_masked_on() && fx_wgrad_applies(d, 96); }
-size_t fx_fwd_workspace(const p3d_conv_desc* d) { return fx_plan(d, false).workspace; }
-size_t fx_fwd_any_workspace(const p3d_conv_desc* d) { return fx_plan(d, false, true).workspace; }
-size_t fx_dgrad_workspace(const p3d_conv_desc* d) { return fx_plan(d, true).workspace; }
-size_t fx_dgrad_any_workspace(const p3d_conv_desc* d) { return fx_plan(d, true, true).workspace; }
-int fx_partial_rows_fwd(const p3d_conv_desc* d) { return fx_plan(d, false).partial_rows; }
-int fx_partial_rows_dgrad(const p3d_conv_desc* d) { return fx_plan(d, true).partial_rows; }
-size_t fx_wgrad_workspace(const p3d_conv_desc* d) {
-    const int a = fx_wgrad_splits(d, false), b = fx_wgrad_splits(d, true);
+// partial convolutions (PRO 4 / EPI 4 instances): 64-channel layers included (half-dead tiles), unsplit launches only.  P3D_FX_MASKED=0: A/B switch
+bool fx_masked_applies(FxPass pass, const p3d_conv_desc* d, bool ragged) {
+    static const bool on = [] { const char* e = getenv("P3D_FX_MASKED"); return !(e && atoi(e) == 0); }();
+    static const int min_m[3] = {64, 64, 96};          // FX_FWD, FX_DGRAD, FX_WGRAD
+    return on && fx_applies(pass, d, min_m[pass], ragged);
+}
+// FX_WGRAD: slab bytes for the larger of the two split counts (fp32- or image-fed x): what a caller reserves before it knows which
+size_t fx_workspace(FxPass pass, const p3d_conv_desc* d, bool ragged) {
+    if (pass != FX_WGRAD) return fx_plan(d, pass == FX_DGRAD, ragged).workspace;
+    const int a = fx_wgrad_splits(d, false, ragged), b = ragged ? 0 : fx_wgrad_splits(d, true);
     return (size_t)(a > b ? a : b) * d->K * d->C * d->R * d->S * sizeof(float);
 }
+int fx_partial_rows(FxPass pass, const p3d_conv_desc* d) { return fx_plan(d, pass == FX_DGRAD).partial_rows; }
 
 // Pre-split weight images of one conv weight w [K][C][R*S] (fp32): blockIdx.y = 0 the forward image (rows = output channels, reduction = input channels),
 // 1 the data-gradient image (rows = input channels, reduction = output channels); a null image pointer skips that direction.  One thread per 16-B chunk
@@ -2214,7 +2202,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     const bool img = fuse && fuse->act_img;
     const bool masked = fuse && (fuse->pmask || fuse->emask);
     const bool infer = fuse && fuse->infer;
-    const bool rag = fuse && (fuse->infer == 2 || fuse->ragged);          // the ragged instances (p3d_fx_conv_fwd_infer_any, p3d_fx_conv_fwd_infer_masked_any; training under p3d_x3_any_enable): any map width
+    const bool rag = fuse && fuse->ragged;          // the ragged instances (p3d_fx_conv_fwd_infer_any, p3d_fx_conv_fwd_infer_masked_any; training under p3d_x3_any_enable): any map width
     const void* wimg = fuse ? fuse->wimg : nullptr;
     if (masked && (!fuse->emask || (bias && !infer) || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr))) {
         set_error("fx_conv_fwd: the partial-convolution instances take the output factor, the input factor exactly for an fp32 operand, and no bias"); return P3D_EINVAL;
@@ -2226,7 +2214,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
                 "fx_conv_fwd: the inference epilogue takes a cached folded weight image, no other fusion, and a partial convolution only from an fp32 operand");
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
     P3D_REQUIRE(!rag || !img, "fx_conv_fwd: the ragged forward takes an fp32 operand");
-    P3D_REQUIRE(!(fuse && fuse->ragged) || (!infer && !masked && !fuse->partial), "fx_conv_fwd: the ragged training forward is the plain dense convolution");
+    P3D_REQUIRE(!(rag && !infer) || (!masked && !fuse->partial), "fx_conv_fwd: the ragged training forward is the plain dense convolution");
     const FxPlan pl = fx_plan(d, false, rag);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     FxConvParams p{};
@@ -2314,17 +2302,19 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
     const int tiles_n = pl.tiles_n;
     FxConvClass cls[4];
     int ncls = 0;
+    struct { int r0, step, n, off0, offstep; } ax[2][2];      // fill_class per axis (rows, columns) and parity: the taps r0 + step * i, i < n
+    for (int par = 0; par < st2; ++par) {
+        fill_class(par, d->R, st2, d->pad, d->dil, &ax[0][par].r0, &ax[0][par].step, &ax[0][par].n, &ax[0][par].off0, &ax[0][par].offstep);
+        fill_class(par, d->S, st2, d->pad, d->dil, &ax[1][par].r0, &ax[1][par].step, &ax[1][par].n, &ax[1][par].off0, &ax[1][par].offstep);
+    }
     for (int ph = 0; ph < st2; ++ph)
         for (int pw = 0; pw < st2; ++pw) {
-            int nr = 0, ns = 0, r0 = -1, r1 = -1, q0 = -1, q1 = -1;
-            for (int r = 0; r < d->R; ++r) { const int tt = ph + d->pad - r * d->dil; if (((tt % st2) + st2) % st2 == 0) { if (r0 < 0) r0 = r; else if (r1 < 0) r1 = r; ++nr; } }
-            for (int s = 0; s < d->S; ++s) { const int tt = pw + d->pad - s * d->dil; if (((tt % st2) + st2) % st2 == 0) { if (q0 < 0) q0 = s; else if (q1 < 0) q1 = s; ++ns; } }
-            if (nr == 0 || ns == 0) continue;      // a class no tap reaches keeps what dx held: see fx_dgrad_has_dead_classes
+            const auto &ty = ax[0][ph], &tx = ax[1][pw];
+            if (ty.n == 0 || tx.n == 0) continue;      // a class no tap reaches keeps what dx held: see fx_dgrad_has_dead_classes
             FxConvParams c = p;
-            c.nR = nr; c.nS = ns; c.ntap = nr * ns; c.r0 = r0; c.rstep = r1 < 0 ? 1 : r1 - r0; c.s0 = q0; c.sstep = q1 < 0 ? 1 : q1 - q0;
-            const int th = ph + d->pad - r0 * d->dil, tw = pw + d->pad - q0 * d->dil;       // divisible by the stride
-            c.hoff = th >= 0 ? th / st2 : -((-th) / st2); c.hstep = -(c.rstep * d->dil) / st2;
-            c.woff = tw >= 0 ? tw / st2 : -((-tw) / st2); c.wstep = -(c.sstep * d->dil) / st2;
+            c.nR = ty.n; c.nS = tx.n; c.ntap = ty.n * tx.n; c.r0 = ty.r0; c.rstep = ty.step; c.s0 = tx.r0; c.sstep = tx.step;
+            c.hoff = ty.off0; c.hstep = -ty.offstep;
+            c.woff = tx.off0; c.wstep = -tx.offstep;
             c.oy0 = ph; c.ox0 = pw;
             if (g_class_launches) { if (int32_t e = fx_launch_conv(c, img, pro, epi, bm, dim3((unsigned)(c.tiles_m * tiles_n), 1), st)) return e; continue; }
             cls[ncls++] = FxConvClass{c.nR, c.nS, c.ntap, c.r0, c.rstep, c.s0, c.sstep, c.hoff, c.hstep, c.woff, c.wstep, c.oy0, c.ox0};
@@ -2342,6 +2332,12 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
 
 // input pixels of a strided 1x1 that no tap reaches: fx_conv_dgrad leaves them untouched, so a caller that does not accumulate zero-fills dx first
 bool fx_dgrad_has_dead_classes(const p3d_conv_desc* d) { return d->stride > 1 && d->R == 1; }
+// ... which is this: every caller of fx_conv_dgrad that hands out dx as a whole result runs it first
+int32_t fx_dgrad_zero_dead_classes(const p3d_conv_desc* d, float* dx, hipStream_t st) {
+    if (!fx_dgrad_has_dead_classes(d) || d->accumulate) return P3D_OK;
+    if (hipMemsetAsync(dx, 0, (size_t)d->N * d->C * d->H * d->W * sizeof(float), st) != hipSuccess) { set_error("fx_conv_dgrad: zero fill of dx failed"); return P3D_ELAUNCH; }
+    return P3D_OK;
+}
 // the dense unsplit launch can take its summand from another tensor (FxFuse::acc_src / acc_mask)
 bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d) { return d->stride == 1 && fx_plan(d, true).splits == 1 && (d->H * d->W) % 4 == 0; }
 

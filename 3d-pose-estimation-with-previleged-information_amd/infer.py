@@ -10,7 +10,7 @@ p3d_fx_conv_fwd_infer, whose epilogue adds b', the residual and the ReLU, and on
     ...optimizer step / new running statistics...
     net.refresh()                       # re-fold from the current parameters (one launch)
 
-A conv the x3 forward cannot take (odd sizes, fx_fwd_applies) goes through today's eval path for that layer (ops.conv_bn_eval).  `fold(model,
+A conv the x3 forward cannot take (odd sizes, fx_applies(FX_FWD)) goes through today's eval path for that layer (ops.conv_bn_eval).  `fold(model,
 any_size=True)` sends such a dense conv to p3d_fx_conv_fwd_infer_any first, the same x3 arithmetic on the same folded image for map widths that are not
 multiples of 4 (the reference's default -side_in 257: 65, 33 and 17 wide maps).  `fold(model, any_size=True, odd_sides=True)` folds what that leaves at an odd
 crop as well: a partial conv the masked entry refuses goes to p3d_fx_conv_fwd_infer_masked_any (the ragged kernels with mask_in in the operand fetch and mult in

@@ -362,7 +362,7 @@ def test_block_admission_and_workspace_queries_agree(pkg):
     """One admission predicate and one workspace layout behind the block executor's queries (csrc/p3d_block.hip: block_refusal, block_layout): over the block kinds
     of tests/geometry_table.py on its maps, dense and masked, p3d_block_supported says 1 exactly when p3d_block_workspace_bytes answers P3D_OK; both workspaces are
     whole 256-byte units; and the side workspace holds the weight-gradient slabs p3d_fx_conv_img_workspace_bytes(d, 2) asks for, for every convolution of the block
-    (fx_wgrad_workspace is the one formula behind both)."""
+    (fx_workspace(FX_WGRAD, d) is the one formula behind both)."""
     import ctypes
     import geometry_table as T
     from test_geometry_host import _block

@@ -594,7 +594,7 @@ def x3_case(pkg, n, c, k, h, w, r, stride, pad, dil, with_bias, seed=None):
 
 
 def _x3_covers(n, c, k, h, r, stride, dil):
-    """What fx_fwd_applies / fx_dgrad_applies / fx_wgrad_applies (csrc/p3d_fx.hip) say for the square, same-padded shapes above, written out: the launch
+    """What fx_applies(FX_FWD / FX_DGRAD / FX_WGRAD, d) (csrc/p3d_fx.hip) says for the square, same-padded shapes above, written out: the launch
     counters x3_case reads must agree with it (a counter that stopped counting would otherwise pass for "not covered")."""
     ho = (h - 1) // stride + 1
     fwd = c % 16 == 0 and c >= 32 and ho % 4 == 0 and h % 4 == 0 and k >= 96
