@@ -136,6 +136,7 @@ SIGNATURES = {
     'p3d_conv2d_wgrad_any_supported': (_i32, [_desc]),
     'p3d_fx_tune': (None, [_i32, _i32]),
     'p3d_conv_path_stats': (None, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), _i32]),
+    'p3d_conv_last_fp32_launch': (None, [ctypes.POINTER(_i32)]),
     'p3d_reproject_crops': (_i32, [_ptr, _i32, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _ptr]),
     'p3d_enhance_depth': (_i32, [_ptr, _ptr, _i64, _f32, _i32, _ptr]),
     'p3d_normalize_rgb': (_i32, [_ptr, _i32, _i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _ptr]),

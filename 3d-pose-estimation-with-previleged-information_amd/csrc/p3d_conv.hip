@@ -32,6 +32,7 @@
 #include "p3d_common.h"
 #include "p3d_fx.h"
 #include <stdlib.h>
+#include <mutex>
 
 namespace p3d {
 
@@ -937,6 +938,25 @@ static IgemmParams base_params(const p3d_conv_desc* d) {
     return p;
 }
 
+// ---- what the last call launched (p3d_conv_last_fp32_launch) ---------------------------------------------
+// Host bookkeeping like fx_count: each of the four entries clears the record first, launch_igemm and the finishing launches write the values they launch with
+// (wgrad_finish, which the x3 and block paths share, hands its bits to the caller; only the fp32 branch of p3d_conv2d_wgrad records them).
+enum { LAST_PASS = 0, LAST_TILE, LAST_TAPM, LAST_MASKED, LAST_WV, LAST_GRID_X, LAST_GRID_Y, LAST_Y_MEANS, LAST_WEIGHT_IMAGE, LAST_FINISH, LAST_EVAL, LAST_NO_ROOM,
+       LAST_FIELDS = P3D_FP32_LAUNCH_FIELDS };
+enum { Y_ONE = 0, Y_SLABS = 1, Y_CLASSES = 2 };
+enum { FIN_FWD_REDUCE = 1, FIN_INTERLEAVE = 2, FIN_INTERLEAVE2 = 4, FIN_WGRAD_REDUCE = 8, FIN_WGRAD_REDUCE_TAPM = 16, FIN_WGRAD_REDUCE16 = 32,
+       FIN_WGRAD_REDUCE16_TAPM = 64, FIN_SLAB_FOLD = 128 };
+enum { NO_ROOM_SLABS = 1, NO_ROOM_WEIGHT_IMAGE = 2 };
+static std::mutex g_last_mu;
+static int32_t g_last[LAST_FIELDS] = {-1};
+static void last_clear(int eval) {
+    std::lock_guard<std::mutex> lock(g_last_mu);
+    for (int i = 0; i < LAST_FIELDS; ++i) g_last[i] = 0;
+    g_last[LAST_PASS] = -1; g_last[LAST_TILE] = -1; g_last[LAST_EVAL] = eval;
+}
+static void last_set(int field, int value) { std::lock_guard<std::mutex> lock(g_last_mu); g_last[field] = value; }
+static void last_or(int field, int bits) { std::lock_guard<std::mutex> lock(g_last_mu); g_last[field] |= bits; }
+
 // ---- tile configurations --------------------------------------------------------------------------------
 struct TileCfg { int bm, bn, bk; double eff; };
 //                               128x128           64x256            96x128            64x128            128x64            64x64
@@ -999,6 +1019,11 @@ template <int MODE>
 static void launch_igemm(int cfg, bool tapm, bool masked, IgemmParams& p, int ny, hipStream_t st, int wv = 0) {
     p.tiles_m = (int)ceil_div(p.M, kCfgs[cfg].bm);
     dim3 grid((unsigned)(p.tiles_m * ceil_div(p.Ncols, kCfgs[cfg].bn)), (unsigned)ny);
+    {
+        std::lock_guard<std::mutex> lock(g_last_mu);
+        g_last[LAST_PASS] = MODE; g_last[LAST_TILE] = cfg < 5 ? cfg : 5; g_last[LAST_TAPM] = tapm; g_last[LAST_MASKED] = masked; g_last[LAST_WV] = wv;
+        g_last[LAST_GRID_X] = (int32_t)grid.x; g_last[LAST_GRID_Y] = ny;
+    }
     switch (cfg) {
         case 0: launch_variant<MODE, 128, 128, 2, 2, 16>(tapm, masked, wv, grid, st, p); break;
         case 1: launch_variant<MODE, 64, 256, 1, 4, 16>(tapm, masked, wv, grid, st, p); break;
@@ -1045,7 +1070,9 @@ static WgradPlan plan_wgrad(const p3d_conv_desc* d, bool masked) {
 namespace p3d {
 // second half of every weight-gradient call: deep splits are folded to <= 16 slabs by a chip-filling grid, then one pass sums them into dw
 // (tap-major slabs [k][tap][c] are transposed to the weight's [k][c][tap] order on the way)
-int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm, float* dw, hipStream_t st) {
+int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm, float* dw, hipStream_t st, int32_t* launched) {
+    int32_t none = 0;
+    if (!launched) launched = &none;          // (the FIN_ bits of the kernels launched below, for the caller that keeps the launch record)
     const int M = d->K, Ncols = d->C * d->R * d->S;
     const int ldw = d->c_total * d->R * d->S, woff = d->c_offset * d->R * d->S;
     if (nslab > 16) {
@@ -1055,18 +1082,21 @@ int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm,
             const int RS = d->R * d->S;
             hipLaunchKernelGGL(wgrad_reduce16_tapm_kernel, dim3(d->K, d->C / 16), dim3(256), (size_t)(17 * RS * 16) * sizeof(float), st, (const float*)slabs, dw, M, d->C, RS,
                                nslab, ldw, woff, d->accumulate);
+            *launched |= FIN_WGRAD_REDUCE16_TAPM;
             return check_launch("conv2d_wgrad reduce16 tapm");
         }
         if (!(tapm && d->R * d->S > 1) && ldw == Ncols && woff == 0 && (tot & 3) == 0 && aligned16(dw, slabs)) {
             const size_t n4 = tot >> 2;
             const int64_t nb = ceil_div((int64_t)n4, 16);
             hipLaunchKernelGGL(wgrad_reduce16_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, st, (const float*)slabs, dw, n4, nslab, d->accumulate);
+            *launched |= FIN_WGRAD_REDUCE16;
             return check_launch("conv2d_wgrad reduce16");
         }
         const size_t total = (size_t)M * Ncols;
         const int G = 16;
         const int64_t bx = ceil_div((int64_t)ceil_div((int64_t)total, 4), 256);
         hipLaunchKernelGGL(slab_fold_kernel, dim3((unsigned)(bx < 256 ? bx : 256), G), dim3(256), 0, st, slabs, total, nslab, G);
+        *launched |= FIN_SLAB_FOLD;
         if (int32_t e = check_launch("conv2d_wgrad fold")) return e;
         nslab = G;
     }
@@ -1074,10 +1104,12 @@ int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm,
         const int RS = d->R * d->S;
         hipLaunchKernelGGL(wgrad_reduce_tapm_kernel, dim3(d->K, d->C / REDUCE_CH), dim3(256), RS * REDUCE_CH * sizeof(float), st, (const float*)slabs, dw, M, d->C, RS,
                            nslab, ldw, woff, d->accumulate);
+        *launched |= FIN_WGRAD_REDUCE_TAPM;
     } else {
         const size_t total = (size_t)M * Ncols;
         const unsigned blocks = (unsigned)(ceil_div((int64_t)total, 256) < 2048 ? ceil_div((int64_t)total, 256) : 2048);
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)slabs, dw, M, Ncols, nslab, ldw, woff, d->accumulate);
+        *launched |= FIN_WGRAD_REDUCE;
     }
     return check_launch("conv2d_wgrad reduce");
 }
@@ -1195,6 +1227,7 @@ size_t p3d_conv2d_fwd_workspace_bytes(const p3d_conv_desc* d) {
 static int32_t conv2d_fwd_impl(const p3d_conv_desc* d, const float* x, const float* w, const float* bias, const float* mask_in, const float* mult,
                                float* y, void* workspace, size_t workspace_bytes, void* stream, const float* ep_scale, const float* ep_shift,
                                const float* ep_res, int ep_relu) {
+    last_clear(ep_scale != nullptr);
     if (int32_t e = validate(d)) return e;
     P3D_REQUIRE(x && w && y, "conv2d_fwd: null tensor");
     const ConvRoute route = conv_route(FX_FWD, d, (mask_in != nullptr) + (mult != nullptr), ep_scale || ep_res || ep_relu, bias != nullptr,
@@ -1217,17 +1250,20 @@ static int32_t conv2d_fwd_impl(const p3d_conv_desc* d, const float* x, const flo
     if (wimg && tapm && workspace && workspace_bytes >= wimg) {      // tap-major weight image at the head of the workspace
         use_weight_image(p, d, w, (float*)workspace, (hipStream_t)stream);
         workspace = (char*)workspace + wimg; workspace_bytes -= wimg;
-    }
-    if (pl.splits > 1 && (!workspace || workspace_bytes < pl.splits * ysize * sizeof(float))) pl = plan_fwd(d, false);   // no scratch: unsplit
+        last_set(LAST_WEIGHT_IMAGE, 1);
+    } else if (wimg && tapm) last_or(LAST_NO_ROOM, NO_ROOM_WEIGHT_IMAGE);
+    if (pl.splits > 1 && (!workspace || workspace_bytes < pl.splits * ysize * sizeof(float))) { pl = plan_fwd(d, false); last_or(LAST_NO_ROOM, NO_ROOM_SLABS); }   // no scratch: unsplit
     p.cpad = (int)ceil_div(d->C, kCfgs[pl.cfg].bk) * kCfgs[pl.cfg].bk;
     if (pl.splits > 1) {
         p.Cout = (float*)workspace; p.bias = nullptr; p.accumulate = 0; p.ep_scale = nullptr;      // the epilogue runs in the reduce pass
         p.kchunk = pl.kchunk; p.cls_stride = ysize;
         launch_igemm<MODE_FWD>(pl.cfg, true, false, p, pl.splits, (hipStream_t)stream);
+        last_set(LAST_Y_MEANS, Y_SLABS);
         if (int32_t e = check_launch("conv2d_fwd")) return e;
         const unsigned blocks = (unsigned)(ceil_div((int64_t)ysize, 1024) < 4096 ? ceil_div((int64_t)ysize, 1024) : 4096);
         hipLaunchKernelGGL(fwd_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, y, bias, ysize, d->K,
                            d->Ho * d->Wo, pl.splits, d->accumulate, ep_scale, ep_shift, ep_res, ep_relu);
+        last_or(LAST_FINISH, FIN_FWD_REDUCE);
         return check_launch("conv2d_fwd reduce");
     }
     launch_igemm<MODE_FWD>(pl.cfg, tapm, masked, p, 1, (hipStream_t)stream);
@@ -1236,6 +1272,7 @@ static int32_t conv2d_fwd_impl(const p3d_conv_desc* d, const float* x, const flo
 
 int32_t p3d_conv2d_fwd(const p3d_conv_desc* d, const float* x, const float* w, const float* bias,
                        const float* mask_in, const float* mult, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    last_clear(0);
     if (!d) { set_error("conv: null descriptor"); return P3D_EINVAL; }
     ProfScope ps(0, d, (hipStream_t)stream);
     return conv2d_fwd_impl(d, x, w, bias, mask_in, mult, y, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, 0);
@@ -1259,6 +1296,7 @@ size_t p3d_conv2d_bn_eval_fwd_workspace_bytes(const p3d_conv_desc* d) {
 int32_t p3d_conv2d_bn_eval_fwd(const p3d_conv_desc* d, const float* x, const float* w, const float* gamma, const float* beta,
                                const float* running_mean, const float* running_var, float eps, const float* res, int32_t relu, float* y,
                                void* workspace, size_t workspace_bytes, void* stream) {
+    last_clear(1);
     if (int32_t e = validate(d)) return e;
     P3D_REQUIRE(gamma && beta && running_mean && running_var, "conv2d_bn_eval_fwd: null BatchNorm tensor");
     P3D_REQUIRE(!d->accumulate, "conv2d_bn_eval_fwd: accumulate is not meaningful with a fused activation");
@@ -1285,6 +1323,7 @@ size_t p3d_conv2d_dgrad_workspace_bytes(const p3d_conv_desc* d) {
 
 int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, const float* mult,
                          const float* mask_in, float* dx, void* workspace, size_t workspace_bytes, void* stream) {
+    last_clear(0);
     if (int32_t e = validate(d)) return e;
     P3D_REQUIRE(dy && w && dx, "conv2d_dgrad: null tensor");
     ProfScope ps(1, d, (hipStream_t)stream);
@@ -1322,17 +1361,21 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
         if (wimg && workspace && workspace_bytes >= wimg) {
             use_weight_image(p, d, w, (float*)workspace, (hipStream_t)stream);
             workspace = (char*)workspace + wimg; workspace_bytes -= wimg;
-        }
+            last_set(LAST_WEIGHT_IMAGE, 1);
+        } else if (wimg) last_or(LAST_NO_ROOM, NO_ROOM_WEIGHT_IMAGE);
         if (pl.splits > 1 && workspace && workspace_bytes >= pl.splits * xsize * sizeof(float)) {
             p.cpad = (int)ceil_div(d->K, kCfgs[pl.cfg].bk) * kCfgs[pl.cfg].bk;
             p.Cout = (float*)workspace; p.accumulate = 0; p.kchunk = pl.kchunk; p.cls_stride = xsize;
             launch_igemm<MODE_DGRAD>(pl.cfg, true, false, p, pl.splits, (hipStream_t)stream);
+            last_set(LAST_Y_MEANS, Y_SLABS);
             if (int32_t e = check_launch("conv2d_dgrad")) return e;
             const unsigned rb = (unsigned)(ceil_div((int64_t)xsize, 1024) < 4096 ? ceil_div((int64_t)xsize, 1024) : 4096);
             hipLaunchKernelGGL(fwd_reduce_kernel, dim3(rb), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dx, (const float*)nullptr, xsize,
                                d->C, d->H * d->W, pl.splits, d->accumulate);
+            last_or(LAST_FINISH, FIN_FWD_REDUCE);
             return check_launch("conv2d_dgrad reduce");
         }
+        if (pl.splits > 1) last_or(LAST_NO_ROOM, NO_ROOM_SLABS);
         launch_igemm<MODE_DGRAD>(cfg, true, masked, p, 1, (hipStream_t)stream);
         return check_launch("conv2d_dgrad");
     }
@@ -1349,17 +1392,20 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
     p.mask_in = nullptr;
     p.accumulate = 0;
     launch_igemm<MODE_DGRAD>(cfg, true, masked && mult != nullptr, p, p.ncls, (hipStream_t)stream);
+    last_set(LAST_Y_MEANS, Y_CLASSES);
     if (int32_t e = check_launch("conv2d_dgrad")) return e;
     const int64_t total = (int64_t)d->N * d->C * d->H * d->W;
     if (st == 2 && d->W % 4 == 0 && aligned16(dx, workspace, mask_in)) {
         const unsigned blocks4 = (unsigned)(ceil_div(total / 4, 256) < 8192 ? ceil_div(total / 4, 256) : 8192);
         hipLaunchKernelGGL(dgrad_interleave2_kernel, dim3(blocks4), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dx, mask_in,
                            d->N * d->C, d->C, d->H, d->W, p.cls_stride, live, d->accumulate);
+        last_or(LAST_FINISH, FIN_INTERLEAVE2);
         return check_launch("conv2d_dgrad interleave");
     }
     const unsigned blocks = (unsigned)(ceil_div(total, 256) < 8192 ? ceil_div(total, 256) : 8192);
     hipLaunchKernelGGL(dgrad_interleave_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dx, mask_in,
                        d->N * d->C, d->C, d->H, d->W, st, p.cls_stride, live, d->accumulate);
+    last_or(LAST_FINISH, FIN_INTERLEAVE);
     return check_launch("conv2d_dgrad interleave");
 }
 
@@ -1374,6 +1420,7 @@ size_t p3d_conv2d_wgrad_workspace_bytes(const p3d_conv_desc* d) {
 
 int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x, const float* mult,
                          const float* mask_in, float* dw, void* workspace, size_t workspace_bytes, void* stream) {
+    last_clear(0);
     if (int32_t e = validate(d)) return e;
     P3D_REQUIRE(dy && x && dw, "conv2d_wgrad: null tensor");
     ProfScope ps(2, d, (hipStream_t)stream);
@@ -1408,9 +1455,12 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
         const FxFuse f = route_fuse(route, mult, mask_in);
         if (int32_t e = fx_conv_wgrad_slabs(d, dy, x, (float*)workspace, pl.splits, &f, (hipStream_t)stream)) return e;
     }
-    else launch_igemm<MODE_WGRAD>(pl.cfg, pl.tapm, masked, p, pl.splits, (hipStream_t)stream, wv);
+    else { launch_igemm<MODE_WGRAD>(pl.cfg, pl.tapm, masked, p, pl.splits, (hipStream_t)stream, wv); last_set(LAST_Y_MEANS, Y_SLABS); }
     if (int32_t e = check_launch("conv2d_wgrad")) return e;
-    return wgrad_finish(d, (float*)workspace, pl.splits, pl.tapm, dw, (hipStream_t)stream);
+    int32_t finish = 0;
+    const int32_t e = wgrad_finish(d, (float*)workspace, pl.splits, pl.tapm, dw, (hipStream_t)stream, &finish);
+    if (!fx) last_or(LAST_FINISH, finish);
+    return e;
 }
 
 int32_t p3d_x3_enable(int32_t on) { return fx_set_enabled(on); }
@@ -1420,6 +1470,12 @@ int32_t p3d_conv2d_fwd_any_supported(const p3d_conv_desc* d) { return d && !vali
 int32_t p3d_conv2d_dgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && any_ok(FX_DGRAD, d) ? 1 : 0; }
 int32_t p3d_conv2d_wgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && any_ok(FX_WGRAD, d) ? 1 : 0; }
 void p3d_fx_tune(int32_t what, int32_t value) { fx_tune(what, value); }
+
+void p3d_conv_last_fp32_launch(int32_t* out) {
+    if (!out) return;
+    std::lock_guard<std::mutex> lock(g_last_mu);
+    for (int i = 0; i < LAST_FIELDS; ++i) out[i] = g_last[i];
+}
 
 void p3d_conv_path_stats(uint64_t* counts, double* flops, int32_t reset) {
     unsigned long long c[6];

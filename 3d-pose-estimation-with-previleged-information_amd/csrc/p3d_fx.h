@@ -141,8 +141,9 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
                     const FxFuse* fuse, hipStream_t st);
 int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, float* dx, void* workspace, size_t workspace_bytes, const FxFuse* fuse,
                       hipStream_t st);
-// p3d_conv.hip: fold the split slabs and write (or add) the weight gradient in the weight's own [K][C][R][S] layout
-int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm, float* dw, hipStream_t st);
+// p3d_conv.hip: fold the split slabs and write (or add) the weight gradient in the weight's own [K][C][R][S] layout; `launched`, when given, receives which kernels
+// ran, as the finishing bits of p3d_conv_last_fp32_launch
+int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm, float* dw, hipStream_t st, int32_t* launched = nullptr);
 size_t fx_weight_image_bytes(int K, int C, int RS, bool bwd);
 int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_fwd, void* img_bwd, hipStream_t st, int ctot = 0, int coff = 0);      // ctot > 0: a window of C input channels at coff
 int32_t fx_build_weight_images_batched(const void* jobs, int njobs, int blocks, hipStream_t st);      // jobs: device array of {w, fwd, bwd, K, C, RS, pad} (40 B each)

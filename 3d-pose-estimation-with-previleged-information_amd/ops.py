@@ -990,6 +990,19 @@ def conv_path_stats(reset=False):
                 fp32={n: (int(counts[3 + i]), float(flops[3 + i])) for i, n in enumerate(names)})
 
 
+# the record of p3d_conv_last_fp32_launch: include/p3d_hip.h and the enum of csrc/p3d_conv.hip define the layout; tests/test_fp32_mfma_instances_host.py holds these to them
+LAST_FP32_FIELDS = ('pass_', 'tile', 'tapm', 'masked', 'wv', 'grid_x', 'grid_y', 'y_means', 'weight_image', 'finish', 'eval', 'no_room')
+LAST_FP32_LEN = 16          # P3D_FP32_LAUNCH_FIELDS
+
+
+def conv_last_fp32_launch():
+    """What the last per-layer convolution call launched on the fp32-MFMA kernels (p3d_conv_last_fp32_launch): dict of LAST_FP32_FIELDS, pass_ -1 when it
+    launched nothing there."""
+    out = (ctypes.c_int32 * LAST_FP32_LEN)()
+    lib().p3d_conv_last_fp32_launch(out)
+    return {n: int(out[i]) for i, n in enumerate(LAST_FP32_FIELDS)}
+
+
 def reproject_crops(frames, params20, out_hw, round_u8=True):
     """Batch of cameralib.reproject_image calls (cameralib.py:378-443): frames [B,Hs,Ws,C] uint8 / fp32 as decoded, params20 [B,20] fp32
     (cameralib.reproject_params) -> [B,C,Ho,Wo] fp32."""

@@ -119,6 +119,20 @@ void p3d_fx_tune(int32_t what, int32_t value);
 /* How many conv launches took which path since the last reset: counts / flops [0..2] = forward, data gradient, weight gradient on the bf16-pipe kernels,
  * [3..5] = the same three on the fp32-MFMA kernels (algorithmic flops 2*N*K*Ho*Wo*C*R*S).  Host-side bookkeeping only. */
 void p3d_conv_path_stats(uint64_t* counts, double* flops, int32_t reset);
+/* What the last p3d_conv2d_fwd / _bn_eval_fwd / _dgrad / _wgrad call of the process launched on the fp32-MFMA family, written where the launches are made.
+ * Host-side bookkeeping only.  out[P3D_FP32_LAUNCH_FIELDS]:
+ *   [0] pass: 0 forward, 1 data gradient, 2 weight gradient, -1: the call launched no igemm_kernel (it ran on the x3 kernels, or was refused); every entry
+ *       clears the record before anything else, and calls of other entries (the block executor) never write to it, so with pass -1 all but [10] is 0 / -1
+ *   [1] tile 0..5 = 128x128, 64x256, 96x128, 64x128, 128x64, 64x64 (-1 with pass -1)     [2] TAPM     [3] MASKED     [4] WV  -- the kernel's template arguments
+ *   [5] grid.x   [6] grid.y   [7] what grid.y counts: 0 nothing (1), 1 K slabs, 2 parity classes of a strided data gradient
+ *   [8] 1: the operand A was the tap-major weight image at the head of the workspace
+ *   [9] the finishing kernels that followed, as bits: 1 fwd_reduce, 2 dgrad_interleave, 4 dgrad_interleave2, 8 wgrad_reduce, 16 wgrad_reduce_tapm,
+ *       32 wgrad_reduce16, 64 wgrad_reduce16_tapm, 128 slab_fold (then with 8 or 16)
+ *   [10] 1: the call came through p3d_conv2d_bn_eval_fwd
+ *   [11] what the plan wanted and the workspace had no room for, as bits: 1 the split-K slabs (the launch is unsplit), 2 the weight image
+ *   [12..15] 0 */
+#define P3D_FP32_LAUNCH_FIELDS 16
+void p3d_conv_last_fp32_launch(int32_t* out);
 /* db[k] (=|+=) sum_{n,h,w} dy[n,k,h,w]  (bias gradient of the regressor conv, depthnet.py:156). */
 int32_t p3d_conv2d_bgrad(const float* dy, int32_t N, int32_t K, int32_t HW, float* db, int32_t accumulate, void* stream);
 /* bias gradient of a PartialConv with bias (partial_conv.py:48-51: out = ((raw - b) * mult + b) * mask_out, so d out / d b = mask_out):
