@@ -733,6 +733,7 @@ static int32_t hconv_fwd_impl(const p3d_conv_desc* d, const void* x, const void*
                               float* partial, void* stream) {
     if (int32_t e = hvalidate(d, "hconv2d_fwd")) return e;
     P3D_REQUIRE(x && w_krsc && y, "hconv2d_fwd: null tensor");
+    P3D_REQUIRE(!d->accumulate, "hconv2d_fwd: accumulate is not supported");      // (hfwd_params carries no such field: y would be overwritten; no caller sets it)
     HGatherParams p = hfwd_params(d, x, w_krsc, bias, mask_in, mult, y);
     p.partial = partial;
     launch_gather(p, 1, d->N * d->Ho * d->Wo, (hipStream_t)stream, partial ? 2 : 0);

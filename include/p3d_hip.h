@@ -59,7 +59,7 @@ typedef struct p3d_conv_desc {
     int32_t stride, pad, dil;
     int32_t Ho, Wo;
     int32_t c_total, c_offset;
-    int32_t accumulate;   /* fwd: y += result; dgrad: dx += result; wgrad: dw += result */
+    int32_t accumulate;   /* fwd: y += result (fp16 forward: must be 0); dgrad: dx += result; wgrad: dw += result */
     int32_t reserved;
 } p3d_conv_desc;
 
@@ -561,7 +561,8 @@ int32_t p3d_normalize_rgb(float* img, int32_t B, int32_t HW, const float* mean3,
  * ------------------------------------------------------------------------------------------ */
 /* Partial conv (partial_conv.py:32-57): mask_in [N][H][W] fp32 {0,1} drops masked input pixels in the operand fetch, mult [N][Ho][Wo]
  * scales the result; both may be NULL.  Backward: the caller scales dy by mult once (p3d_hscale_pixels) and passes that tensor to
- * dgrad (mask_in then multiplies dx) and wgrad (mask_in masks x). */
+ * dgrad (mask_in then multiplies dx) and wgrad (mask_in masks x).
+ * d->accumulate, fp16 forward: must be 0 (p3d_hconv2d_fwd, p3d_hconv2d_fwd_stats and p3d_hconv2d_fwd_infer refuse anything else). */
 int32_t p3d_hconv2d_fwd(const p3d_conv_desc* d, const void* x_nhwc, const void* w_krsc, const float* bias, const float* mask_in,
                         const float* mult, void* y_nhwc, void* stream);
 int32_t p3d_hscale_pixels(const void* src_nhwc, const float* scale, void* dst_nhwc, int64_t P, int32_t C, void* stream);
