@@ -146,6 +146,9 @@ SIGNATURES = {
     'p3d_f8conv2d_fwd_infer_supported': (_i32, [_desc]),
     'p3d_f8conv2d_weight_bytes': (_sz, [_i32, _i32, _i32]),
     'p3d_f8conv2d_fwd_infer': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr]),
+    'p3d_f8act_bytes': (_sz, [_i64, _i32]),
+    'p3d_f8conv2d_fwd_infer_mx_supported': (_i32, [_desc, _i32, _i32]),
+    'p3d_f8conv2d_fwd_infer_mx': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _ptr]),
     'p3d_hscale_pixels': (_i32, [_ptr, _ptr, _ptr, _i64, _i32, _ptr]),
     'p3d_hconv2d_dgrad': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr]),
     'p3d_hblock_fuse_sums': (_i32, [_i32]),

@@ -407,7 +407,7 @@ class Trainer:
             ops_block.release_buffers(self.model)
         if self._folding():                                  # P3D_FOLDED_EVAL=1 / -half_acc with P3D_FOLDED_EVAL_HALF=1: BatchNorm folded into the convolutions
             net = getattr(self.model, 'module', self.model)
-            key = '_folded_fp8_model' if infer.fp8_enabled() else ('_folded_half_model' if self.half_acc else '_folded_model')
+            key = ('_folded_fp8_resident_model' if infer.fp8_resident_enabled() else '_folded_fp8_model') if infer.fp8_enabled() else ('_folded_half_model' if self.half_acc else '_folded_model')
             folded = self.__dict__.get(key)
             if folded is None or folded.model is not net:
                 folded = self.__dict__[key] = self._fold(net)
@@ -427,6 +427,8 @@ class Trainer:
 
     def _fold(self, net):
         if infer.fp8_enabled():                              # (takes precedence over the other two switches)
+            if infer.fp8_resident_enabled():                 # P3D_FOLDED_EVAL_FP8_RESIDENT=1: the same bits, MXFP8 activations between the fp8 convs
+                return infer.fold_fp8(net, resident=True)
             return infer.fold_fp8(net)
         return infer.fold_half(net) if self.half_acc else infer.fold(net, any_size=True, odd_sides=True)      # (the default -side_in 257 stays on the x3 kernels, stems and partial layers included)
 

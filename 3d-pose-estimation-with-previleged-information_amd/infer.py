@@ -32,6 +32,9 @@ forward has no BatchNorm pass at all.
 layers and the Fusion 1x1 that p3d_f8conv2d_fwd_infer accepts folds to a kind-3 MXFP8 image (e4m3 elements, one E8M0 scale per 32 input channels of a
 tap) and runs on that entry point, which quantizes its fp16 input by the same rule while staging it; the stems and the heads stay on the fp16 folded conv
 (the usual first / last layer rule), and so does a conv the entry point refuses.  One fold launch writes the kind-3 and the kind-2 images together.
+`fold_fp8(model, resident=True)` gives the same outputs bit for bit, with the activations between fp8 convs kept as MXFP8 tensors: a conv quantizes its
+result once, in its epilogue (p3d_f8conv2d_fwd_infer_mx), and the next conv copies the bytes in place of quantizing them per tap and row tile; the results
+inside a block's chain exist as MXFP8 only (resident_forms).
 
 All three share the plan (stems, blocks, fusion, heads), the fold launch and the walk over the network (_Folded); FoldedNet, HalfFoldedNet and
 Fp8FoldedNet supply the per-layer primitives.  Two A/B switches were measured and removed, because each only selected a slower path: leaving the partial stem
@@ -299,10 +302,13 @@ class _Folded:
         if 'conv2' in self.stems:
             x = self._fusion(x, self._branch('conv2', ('layer5', 'layer6'), y))
         a = self._layer('layer3', x)
-        n = self._layer('layer4', ops.relu(a) if self.skip_relu else a)
+        n = self._layer('layer4', self._relu(a) if self.skip_relu else a)
         if self.family == 'resnet':
             return tuple(self._head(c, n) for c in self.heads if c is not None)
-        return self._head(self.heads[0], ops.relu(n) if self.skip_relu else n), (a if self.early_dist else n)
+        return self._head(self.heads[0], self._relu(n) if self.skip_relu else n), (a if self.early_dist else n)
+
+    def _relu(self, x):
+        return ops.relu(x)
 
 
 class FoldedNet(_Folded):
@@ -668,7 +674,101 @@ class Fp8FoldedNet(HalfFoldedNet):
         return y
 
 
-def fold_fp8(model):
+# ---- the same, with the activations between fp8 convs kept in MXFP8 ---------------------------------------------------------------------------
+class _Act:
+    """An activation of the resident walk: the fp16 NHWC tensor (h), the MXFP8 activation tensor (mx: uint8, p3d_f8act_bytes of them, include/p3d_hip.h), or
+    both; shape is its NCHW shape."""
+    __slots__ = ('shape', 'h', 'mx')
+
+    def __init__(self, shape, h=None, mx=None):
+        self.shape, self.h, self.mx = tuple(shape), h, mx
+
+    @staticmethod
+    def of(x):
+        return x if isinstance(x, _Act) else _Act(x.shape, x)
+
+
+def _mx_supported(d, x_is_mx, y_mx):
+    """p3d_f8conv2d_fwd_infer_mx_supported (host only)"""
+    return bool(lib().p3d_f8conv2d_fwd_infer_mx_supported(ctypes.byref(d), int(bool(x_is_mx)), int(bool(y_mx))))
+
+
+def resident_forms(chain, i, d, x_is_mx=True):
+    """(fp16, mx): the forms in which conv i of a block's chain writes its result under fold_fp8(resident=True); d is its descriptor at the input it gets.
+    Needs no device.  The block's output (the chain's last conv; the Fusion 1x1 is a chain of one) is written in both forms: it is the next block's input
+    and its residual, a feature map, or what an fp16 head reads.  An interior result has one reader, the next conv of the chain: it is written as MX only
+    when that conv is an fp8 conv whose entry point accepts it as MX, and as fp16 otherwise.  An fp16 conv, and an fp8 conv the entry point refuses an MX
+    result (K % 32 != 0), write fp16 as they do without resident."""
+    c = chain[i]
+    if not isinstance(c, _F8Conv) or not _mx_supported(d, x_is_mx, 1):
+        return True, False
+    if i == len(chain) - 1:
+        return True, True
+    nxt = chain[i + 1]
+    if isinstance(nxt, _F8Conv) and _mx_supported(nxt.desc(_Act((d.N, d.K, d.Ho, d.Wo))), 1, 0):
+        return False, True
+    return True, False
+
+
+class Fp8ResidentNet(Fp8FoldedNet):
+    """Fp8FoldedNet whose fp8 convs hand each other MXFP8 activation tensors (p3d_f8conv2d_fwd_infer_mx): a conv quantizes its result once, in its
+    epilogue, and its readers copy the bytes.  Bit-equal to Fp8FoldedNet, since the block a producer writes is the block the reader would have made from
+    the fp16 value.  The walk carries _Act objects; what comes from an fp16 kernel (the pool behind a stem, ops.relu under skip_relu, the concat) is fp16
+    only, and the stems, the heads and the per-layer fallback always find an fp16 tensor (resident_forms)."""
+
+    def _conv_act(self, c, x, forms, res=None, relu=False, mask_in=None, mult=None):
+        """_conv_bn on an _Act, the result in `forms` (fp16, mx); the MX input is read when there is one."""
+        if isinstance(c, _F8Conv):
+            L, d = lib(), c.desc(x)
+            if _mx_supported(d, x.mx is not None, forms[1]):
+                dev = (x.h if x.mx is None else x.mx).device
+                y = ops_half._empty(d.N, d.K, d.Ho, d.Wo, dev) if forms[0] else None
+                ymx = torch.empty(L.p3d_f8act_bytes(d.N * d.Ho * d.Wo, d.K), dtype=torch.uint8, device=dev) if forms[1] else None
+                check(L.p3d_f8conv2d_fwd_infer_mx(ctypes.byref(d), ops._p(x.h) if x.mx is None else None, ops._p(x.mx), self._at(c.img_off), self._at(c.bias_off),
+                                                  ops._p(mask_in), ops._p(mult), ops._p(res), int(bool(relu)), ops._p(y), ops._p(ymx), ops._stream()),
+                      'p3d_f8conv2d_fwd_infer_mx')
+                return _Act((d.N, d.K, d.Ho, d.Wo), y, ymx)
+        return _Act.of(self._conv_bn(c, x.h, res, relu, mask_in, mult))      # an fp16 conv, or the per-layer fallback
+
+    def _layer(self, name, x, veil=None):
+        x = _Act.of(x)
+        for plan in self.blocks[name]:
+            blk, chain = plan['block'], plan['chain']
+            res = x.h if plan['ds'] is None else self._conv_act(plan['ds'], x, (True, False)).h
+            out, last = x, len(chain) - 1
+            for i, c in enumerate(chain):
+                forms = resident_forms(chain, i, c.desc(out), out.mx is not None)
+                if blk.partial:
+                    mult, mask_out = ops.mask_count(veil, c.r, c.stride, c.pad, c.dil)
+                    out, veil = self._conv_act(c, out, forms, res if i == last else None, True, veil.contiguous(), mult), mask_out
+                else:
+                    out = self._conv_act(c, out, forms, res if i == last else None, i < last or not blk.skip_relu)
+            x = out
+        return x if veil is None else (x, veil)
+
+    def _fusion(self, x, y):
+        cat = _Act.of(ops_half.concat(x.h, y.h))
+        return self._conv_act(self.fusion, cat, resident_forms([self.fusion], 0, self.fusion.desc(cat), False), relu=True)
+
+    def _relu(self, x):
+        return _Act.of(ops.relu(x.h))
+
+    def _head(self, c, x):
+        return super()._head(c, x.h)
+
+    @staticmethod
+    def _out(x):
+        return HalfFoldedNet._out(x.h if isinstance(x, _Act) else x)
+
+
+def fp8_resident_enabled():
+    """P3D_FOLDED_EVAL_FP8_RESIDENT=1, which acts only together with P3D_FOLDED_EVAL_FP8=1: the fp8 fold keeps its activations in MXFP8 between the
+    fp8 convs (fold_fp8(model, resident=True))."""
+    return fp8_enabled() and os.environ.get('P3D_FOLDED_EVAL_FP8_RESIDENT', '0') == '1'
+
+
+def fold_fp8(model, resident=False):
     """Fp8FoldedNet of a network in eval mode (fp32 or -half_acc): fp32 (or fp16) NCHW input, fp32 NCHW outputs.  Raises P3DError for a BatchNorm in
-    training mode or parameters that are not fp32 on the HIP device."""
-    return Fp8FoldedNet(getattr(model, 'module', model))
+    training mode or parameters that are not fp32 on the HIP device.  resident=True: an Fp8ResidentNet, the same outputs bit for bit with the activations
+    between fp8 convs kept as MXFP8 tensors (profiles/eval_folded_fp8_resident.md)."""
+    return (Fp8ResidentNet if resident else Fp8FoldedNet)(getattr(model, 'module', model))

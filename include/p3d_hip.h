@@ -583,6 +583,23 @@ int32_t p3d_f8conv2d_fwd_infer_supported(const p3d_conv_desc* d);
 size_t p3d_f8conv2d_weight_bytes(int32_t K, int32_t C, int32_t RS);
 int32_t p3d_f8conv2d_fwd_infer(const p3d_conv_desc* d, const void* x_nhwc, const void* w_mx, const float* bias, const float* mask_in, const float* mult,
                                const void* res_nhwc, int32_t relu, void* y_nhwc, void* stream);
+/* The MXFP8 activation tensor (infer.fold_fp8(model, resident=True)): what one fp8 convolution writes and the next reads, so that an activation is quantized
+ * once, by its producer, and not by every tap and row tile of its consumer.  For an NHWC activation [N][H][W][C] with C % 32 == 0, ONE allocation of
+ * p3d_f8act_bytes(N * H * W, C) bytes holds
+ *   e4m3fn elements  [N * H * W][C]        at byte 0, then
+ *   E8M0 scale bytes [N * H * W][C / 32]   at byte N * H * W * C (the scales follow the elements, as in the kind-3 weight image).
+ * A block is 32 consecutive channels of one pixel.  The rule is the one p3d_f8conv2d_fwd_infer applies to its fp16 input: e = floor(log2(amax)), scale byte
+ * e - 8 + 127, element = e4m3fn(RNE(clamp(v / 2^(e - 8), -448, 448))); an all-zero block has scale byte 0 (and elements +-0).  So the block a producer writes
+ * is bit for bit the block the consumer would have made from the stored fp16 value.
+ * p3d_f8act_bytes: pixels * C + pixels * C / 32; 0 for C % 32 != 0 or a non-positive argument.
+ * p3d_f8conv2d_fwd_infer_mx is p3d_f8conv2d_fwd_infer with either form on either side.  Exactly one of x_nhwc (fp16) / x_mx must be given, and at least one
+ * of y_nhwc (fp16) / y_mx; both results hold the same values, y_mx the quantized fp16 result.  mask_in with x_mx zeroes the masked pixels' blocks (elements
+ * and scale byte), which equals quantizing x * mask_in.  With fp16 on both sides it runs the kernel instance of p3d_f8conv2d_fwd_infer.
+ * supported (host only): p3d_f8conv2d_fwd_infer_supported, and K % 32 == 0 when y_mx is set, and the MX tensors inside the 2 GiB buffer window. */
+size_t p3d_f8act_bytes(int64_t pixels, int32_t C);
+int32_t p3d_f8conv2d_fwd_infer_mx_supported(const p3d_conv_desc* d, int32_t x_is_mx, int32_t y_mx);
+int32_t p3d_f8conv2d_fwd_infer_mx(const p3d_conv_desc* d, const void* x_nhwc, const void* x_mx, const void* w_mx, const float* bias, const float* mask_in,
+                                  const float* mult, const void* res_nhwc, int32_t relu, void* y_nhwc, void* y_mx, void* stream);
 /* d->accumulate != 0: dx += result (joins the gradient another consumer of the same input already wrote) */
 int32_t p3d_hconv2d_dgrad(const p3d_conv_desc* d, const void* dy_nhwc, const void* w_crsk, const float* mask_in, void* dx_nhwc, void* stream);
 /* A convolution whose epilogue also leaves the channel sums of the BatchNorm next to it (round 4; what the fp32 path's EPI 1 / 2 do), so that the BatchNorm costs no

@@ -15,6 +15,7 @@ Legs, timed in the same process, alternating (device-synchronised, 10 warm-up + 
   half_folded   infer.fold_half(model): BatchNorm folded into the fp16 convolutions (p3d_hconv2d_fwd_infer)
 --fp8 (with --half) adds the block-scaled FP8 leg:
   fp8_folded    infer.fold_fp8(model): MXFP8 convolutions between fp16 folded stems and heads (p3d_f8conv2d_fwd_infer)
+  fp8_resident  infer.fold_fp8(model, resident=True): the same bits, MXFP8 activation tensors between the fp8 convs (p3d_f8conv2d_fwd_infer_mx)
   and --distill then times the fp8 teacher (P3D_FOLDED_EVAL_FP8=1) beside the fp16 folded one; --deviation prints the relative L2 deviation of z and the
   feature map of the fp8 net against the fp32 eval forward and fold_half (depthnet and fusionnet, seeded synthetic weights and inputs).
 --separate adds the round-1 leg with stand-alone BatchNorm passes; --distill also times one distill_step with and without the folded teacher
@@ -52,7 +53,7 @@ ap.add_argument('--distill', action='store_true')
 ap.add_argument('--half', action='store_true', help='-half_acc legs: half / half_folded')
 ap.add_argument('--fp8', action='store_true', help='with --half (required): the fp8_folded leg (infer.fold_fp8), and an fp8 teacher under --distill')
 ap.add_argument('--deviation', action='store_true', help='with --fp8: relative L2 deviation of the fp8 net (not timed)')
-ap.add_argument('--only', default=None, help='time one leg only (profiling runs)')
+ap.add_argument('--only', default=None, help='time these legs only, comma-separated (one leg: profiling runs)')
 ap.add_argument('--test-loop', action='store_true', help='time Trainer.test: host metrics against P3D_DEVICE_EVAL=1, fp32 and fp16 folded')
 ap.add_argument('--test-batches', type=int, default=50)
 ap.add_argument('--family', default='depthnet', choices=['depthnet', 'partial_depthnet', 'partial_fusionnet'])
@@ -106,7 +107,7 @@ def test_loop():
         legs['host_' + prec] = loop
         legs['device_' + prec] = lambda loop=loop: loop(switch='1')
     if opt.only:
-        legs = {opt.only: legs[opt.only]}
+        legs = {k: legs[k] for k in opt.only.split(',')}
     times, records = {k: [] for k in legs}, {}
     for r in range(opt.rounds):
         for name, fn in legs.items():
@@ -153,6 +154,8 @@ if opt.half:
     if opt.fp8:
         f8folded = pkg.infer.fold_fp8(model)
         legs['fp8_folded'] = lambda: f8folded(*inputs)
+        f8resident = pkg.infer.fold_fp8(model, resident=True)
+        legs['fp8_resident'] = lambda: f8resident(*inputs)
 else:
     folded = pkg.infer.fold(model)
     legs = {'fused': lambda: model(*inputs), 'folded': lambda: folded(*inputs)}
@@ -165,7 +168,7 @@ else:
 if opt.separate:
     legs['separate'] = lambda: model(*inputs)
 if opt.only:
-    legs = {opt.only: legs[opt.only]}
+    legs = {k: legs[k] for k in opt.only.split(',')}
 
 
 def run(name, fn):

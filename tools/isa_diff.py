@@ -3,7 +3,7 @@
     python tools/isa_diff.py parent.s new.s [--map OLD=NEW ...]
 
 Kernels are matched by mangled name; --map renames a parent symbol first (an instance whose template list grew a defaulted parameter).  A body is the text
-between the kernel's label and its .Lfunc_end, comments stripped, the kernel's own symbol replaced and local label numbers dropped; the .amdhsa_ descriptor block
+between the kernel's label and its .Lfunc_end, comments and section directives stripped, the kernel's own symbol replaced and local label numbers dropped; the .amdhsa_ descriptor block
 is compared too.  Prints the counts, every kernel that differs or exists in one file only, and the resource lines of the new-only kernels."""
 import re
 import sys
@@ -21,7 +21,8 @@ def kernels(path):
         body = re.sub(r';.*', '', body)
         body = body.replace(name, 'KERNEL')
         body = re.sub(r'\.L[A-Za-z_]*\d+(_\d+)?', '.L', body)
-        body = '\n'.join(l.strip() for l in body.splitlines() if l.strip())
+        # (a kernel that became a template instance moves from .text to a comdat section of its own: where the code is placed, not what it is)
+        body = '\n'.join(l.strip() for l in body.splitlines() if l.strip() and not re.match(r'\s*\.(text|section)\b', l))
         out[name] = (body, desc.group(1))
     return out
 
