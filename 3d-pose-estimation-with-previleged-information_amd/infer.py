@@ -36,8 +36,8 @@ tap) and runs on that entry point, which quantizes its fp16 input by the same ru
 result once, in its epilogue (p3d_f8conv2d_fwd_infer_mx), and the next conv copies the bytes in place of quantizing them per tap and row tile; the results
 inside a block's chain exist as MXFP8 only (resident_forms).
 
-All three share the plan (stems, blocks, fusion, heads), the fold launch and the walk over the network (_Folded); FoldedNet, HalfFoldedNet and
-Fp8FoldedNet supply the per-layer primitives.  Two A/B switches were measured and removed, because each only selected a slower path: leaving the partial stem
+All four share the plan (stems, blocks, fusion, heads), the fold launch and the walk over the network (_Folded); FoldedNet, HalfFoldedNet,
+Fp8FoldedNet and Fp8ResidentNet supply the per-layer primitives.  Two A/B switches were measured and removed, because each only selected a slower path: leaving the partial stem
 and layers on the model's own modules (9.80 against 8.90 ms for R50 partial_depthnet, 13.10 against 12.22 ms for partial_fusionnet,
 profiles/eval_folded_partial.md), and feeding the 64-channel layers as an activation image (2.7 % slower, profiles/eval_folded.md).
 """
@@ -202,9 +202,11 @@ class _HConv:
 class _Folded:
     """model.eval()'s forward with every BatchNorm folded into its convolution.  Holds the plan (stems, blocks, fusion, heads) and one device buffer
     with every folded image and b', filled by one fold launch; parameters and running statistics are read at fold / refresh() time only (the
-    per-layer fallbacks read them live).  A subclass supplies the precision: its conv type (Conv), how a stem and the Fusion 1x1 fold, and the
-    primitives the walk calls (_in, _out, _stem, _stem_masked, _conv_bn, _pconv, _fusion, _head).  WHO names it in a refusal, HALF marks the
-    -half_acc fold."""
+    per-layer fallbacks read them live).  The walk (_forward, _branch, _layer) is written here only and treats the activation it carries as opaque.  A
+    subclass supplies the precision: its conv type (Conv), how a stem and the Fusion 1x1 fold, and the per-layer primitives the walk calls: _in, _out,
+    _stem, _stem_masked, _fusion, _head, _relu (given here) and, for a conv of a residual block, _chain_conv, which as given here runs _conv_bn (dense) or
+    _pconv (partial); a net whose result depends on the conv's place in its chain replaces _chain_conv itself (Fp8ResidentNet).  WHO names it in a
+    refusal, HALF marks the -half_acc fold."""
 
     def __init__(self, model):
         self.model = model
@@ -269,17 +271,23 @@ class _Folded:
 
     # ---- forward ---------------------------------------------------------------------------------------------------
     def _layer(self, name, x, veil=None):
+        """The residual blocks of a layer, and the one statement of the block rule: the shortcut is the input or its downsample conv, it enters the last conv of
+        the chain, every conv has a ReLU but the closing one of a skip_relu block, and a partial block threads the validity mask through its chain."""
         for plan in self.blocks[name]:
-            blk = plan['block']
-            res = x if plan['ds'] is None else self._conv_bn(plan['ds'], x)
-            out, last = x, len(plan['chain']) - 1
-            for i, c in enumerate(plan['chain']):
-                if blk.partial:                             # (the closing ReLU of a partial block is unconditional: _trunk.py forward_partial)
-                    out, veil = self._pconv(c, out, veil, res if i == last else None)
-                else:
-                    out = self._conv_bn(c, out, res if i == last else None, relu=i < last or not blk.skip_relu)
+            blk, chain = plan['block'], plan['chain']
+            res = x if plan['ds'] is None else self._chain_conv(plan['ds'], x)[0]
+            out, last = x, len(chain) - 1
+            for i, c in enumerate(chain):
+                relu = blk.partial or i < last or not blk.skip_relu      # (the closing ReLU of a partial block is unconditional: _trunk.py forward_partial)
+                out, mask_out = self._chain_conv(c, out, res if i == last else None, relu, veil if blk.partial else None, chain, i)
+                veil = mask_out if blk.partial else veil
             x = out
         return x if veil is None else (x, veil)
+
+    def _chain_conv(self, c, x, res=None, relu=False, veil=None, chain=None, i=0):
+        """Conv c of a residual block on the activation x -> (y, mask_out): a partial conv comes with its validity mask (veil), a dense one with none
+        (mask_out None).  c is chain[i] (chain None: the downsample shortcut), which only a net whose result depends on its reader looks at."""
+        return (self._conv_bn(c, x, res, relu), None) if veil is None else self._pconv(c, x, veil, res, relu)
 
     def _branch(self, stem, layers, x):
         """A stem and its two layers.  A PartialConv stem starts the validity mask x != 0, which its layers carry (the last mask_out feeds nothing)."""
@@ -309,6 +317,15 @@ class _Folded:
 
     def _relu(self, x):
         return ops.relu(x)
+
+
+# The fp32 x3 inference entries in the order a conv is offered to them, dense (False) and masked (True): the entry (its support query is the name +
+# '_supported'), what that query takes behind the descriptor and the entry between x and the weight image (p3d_fx_conv_fwd_infer alone: fed the fp32
+# tensor, no activation image), the workspace query, and the FoldedNet keyword that enables the entry (None: always).
+_X3 = {False: (('p3d_fx_conv_fwd_infer', (0,), (None,), 'p3d_fx_conv_fwd_infer_workspace_bytes', None),
+               ('p3d_fx_conv_fwd_infer_any', (), (), 'p3d_fx_conv_fwd_infer_any_workspace_bytes', 'any_size')),
+       True: (('p3d_fx_conv_fwd_infer_masked', (), (), 'p3d_fx_conv_fwd_infer_workspace_bytes', None),
+              ('p3d_fx_conv_fwd_infer_masked_any', (), (), 'p3d_fx_conv_fwd_infer_masked_any_workspace_bytes', 'odd_sides'))}
 
 
 class FoldedNet(_Folded):
@@ -361,26 +378,31 @@ class FoldedNet(_Folded):
 
     _out = _in
 
-    def _conv(self, c, x, res=None, relu=False, out=None, accumulate=0):
-        """y = conv(x, w') + b' (+ out) (+ res) (then ReLU) on the folded image; None when the x3 forward cannot take the conv.  any_size: a conv
-        p3d_fx_conv_fwd_infer refuses is offered to p3d_fx_conv_fwd_infer_any (any map width) before that."""
-        L = lib()
-        d = c.desc(x, accumulate) if c.foldable else None
-        if d is None:
+    def _conv(self, c, x, res=None, relu=False, out=None, accumulate=0, veil=None):
+        """y = conv(x, w') + b' (+ out) (+ res) (then ReLU) on the folded image, on the first entry of _X3 that takes the conv; None when none does.  With
+        a veil, the partial convolution y = relu?(conv(x * veil, w') * mult + b' + res), mult and mask_out from the box count of veil (ops.mask_count);
+        returns (y, mask_out)."""
+        if not c.foldable:
             return None
-        if L.p3d_fx_conv_fwd_infer_supported(ctypes.byref(d), 0):
-            name, image = 'p3d_fx_conv_fwd_infer', (None,)      # (the entry's x_img argument: fed the fp32 tensor)
-        elif self.any_size and L.p3d_fx_conv_fwd_infer_any_supported(ctypes.byref(d)):
-            name, image = 'p3d_fx_conv_fwd_infer_any', ()
+        L, d = lib(), c.desc(x, accumulate)
+        for name, fed, image, ws_name, keyword in _X3[veil is not None]:
+            if (keyword is None or getattr(self, keyword)) and getattr(L, name + '_supported')(ctypes.byref(d), *fed):
+                break
         else:
             return None
+        mask = ()
+        if veil is not None:
+            if tuple(veil.shape) != (d.N, 1, d.H, d.W) or veil.dtype != torch.float32:
+                raise P3DError('infer: the validity mask of a partial conv must be fp32 [N, 1, H, W] like its input, got %s %s' % (tuple(veil.shape), veil.dtype))
+            mult, mask_out = ops.mask_count(veil, c.r, c.stride, c.pad, c.dil)
+            veil = veil.contiguous()
+            mask = ops._p(veil), ops._p(mult)
         x = x.contiguous()
         y = out if out is not None else torch.empty((d.N, d.K, d.Ho, d.Wo), dtype=torch.float32, device=x.device)
-        ws = self._ws(getattr(L, name + '_workspace_bytes')(ctypes.byref(d)))
-        check(getattr(L, name)(ctypes.byref(d), ops._p(x), *image, self._at(c.img_off), c.img_bytes,
-                               self._at(c.bias_off) if c.bias_off is not None else None, ops._p(None if res is None else res.contiguous()),
-                               int(bool(relu)), ops._p(y), ops._p(ws), ws.numel(), ops._stream()), name)
-        return y
+        ws = self._ws(getattr(L, ws_name)(ctypes.byref(d)))
+        check(getattr(L, name)(ctypes.byref(d), ops._p(x), *image, self._at(c.img_off), c.img_bytes, self._at(c.bias_off) if c.bias_off is not None else None,
+                               *mask, ops._p(None if res is None else res.contiguous()), int(bool(relu)), ops._p(y), ops._p(ws), ws.numel(), ops._stream()), name)
+        return y if veil is None else (y, mask_out)
 
     def _conv_bn(self, c, x, res=None, relu=False):
         y = self._conv(c, x, res, relu)
@@ -389,98 +411,77 @@ class FoldedNet(_Folded):
         return y
 
     def _pconv(self, c, x, veil, res=None, relu=True):
-        """A partial convolution (partial_conv.py) + its folded BatchNorm: y = relu?(conv(x * veil, w') * mult + b' + res), mult and mask_out from the box count
-        of veil (ops.mask_count); returns (y, mask_out).  odd_sides: a conv the masked entry refuses is offered to p3d_fx_conv_fwd_infer_masked_any (any map
-        width).  A conv neither takes runs as the module, then the eval-mode BatchNorm pass."""
-        L = lib()
-        d = c.desc(x) if c.foldable else None
-        name = None
-        if d is not None and L.p3d_fx_conv_fwd_infer_masked_supported(ctypes.byref(d)):
-            name, ws_name = 'p3d_fx_conv_fwd_infer_masked', 'p3d_fx_conv_fwd_infer_workspace_bytes'
-        elif d is not None and self.odd_sides and L.p3d_fx_conv_fwd_infer_masked_any_supported(ctypes.byref(d)):
-            name, ws_name = 'p3d_fx_conv_fwd_infer_masked_any', 'p3d_fx_conv_fwd_infer_masked_any_workspace_bytes'
-        if name is None:
+        """A partial convolution (partial_conv.py) + its folded BatchNorm -> (y, mask_out).  A conv no masked entry takes runs as the module, then the
+        eval-mode BatchNorm pass."""
+        out = self._conv(c, x, res, relu, veil=veil)
+        if out is None:
             y, mask_out = c.conv(x, veil)
-            return c.bn(y, res=res, relu=relu), mask_out
-        if tuple(veil.shape) != (d.N, 1, d.H, d.W) or veil.dtype != torch.float32:
-            raise P3DError('infer: the validity mask of a partial conv must be fp32 [N, 1, H, W] like its input, got %s %s' % (tuple(veil.shape), veil.dtype))
-        mult, mask_out = ops.mask_count(veil, c.r, c.stride, c.pad, c.dil)
-        x = x.contiguous()
-        y = torch.empty((d.N, d.K, d.Ho, d.Wo), dtype=torch.float32, device=x.device)
-        ws = self._ws(getattr(L, ws_name)(ctypes.byref(d)))
-        check(getattr(L, name)(ctypes.byref(d), ops._p(x), self._at(c.img_off), c.img_bytes, self._at(c.bias_off), ops._p(veil.contiguous()),
-                               ops._p(mult), ops._p(None if res is None else res.contiguous()), int(bool(relu)), ops._p(y), ops._p(ws), ws.numel(),
-                               ops._stream()), name)
-        return y, mask_out
+            out = c.bn(y, res=res, relu=relu), mask_out
+        return out
 
-    def _stem_any(self, s, x, veil=None):
-        """The folded stem at sides p3d_stem_supported refuses (odd_sides): the space-to-depth image of x (* veil) zero-extended to the padded sides, the stem conv
-        on those (never with the output factor), then relu(maxpool(c * mult) + b') over the valid prefix of the pitched c.  None when the shape is outside it."""
+    def _stem_x3(self, s, x, veil=None, padded=False):
+        """The restated 7x7 stem + BatchNorm + ReLU + max pool -> (y, mask_out), mask_out (not pooled) None without a veil; None when the shape is outside it.
+        With a veil it is the PartialConv stem (partial_depthnet.py:177), conv(x * veil) * mult with mult and mask_out from ops.mask_count.  Aligned sides: the
+        space-to-depth image of x (* veil), the stem conv with mult in its epilogue, then relu(maxpool(.) + b') (= maxpool(relu(. + b')): both monotone per
+        channel).  padded (odd_sides), for sides p3d_stem_supported refuses: the image zero-extended to the padded sides, the stem conv on those (never with
+        the output factor), then relu(maxpool(c * mult) + b') over the valid prefix of the pitched c."""
         n, cin, h, w = x.shape
         L = lib()
-        if not (self.odd_sides and s.foldable and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_any_supported(n, cin, h, w, s.k)):
+        if padded:
+            query, fits = L.p3d_stem_any_supported, self.odd_sides
+        else:
+            query, fits = (L.p3d_stem_supported if veil is None else L.p3d_stem_masked_supported), (h // 2) % 2 == 0 and (w // 2) % 4 == 0
+        if not (fits and s.foldable and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and query(n, cin, h, w, s.k)
+                and (veil is None or (veil.dtype == torch.float32 and tuple(veil.shape) == (n, 1, h, w)))):
             return None
-        hp, wp = ctypes.c_int32(), ctypes.c_int32()
-        L.p3d_stem_any_padded(h, w, ctypes.byref(hp), ctypes.byref(wp))
-        hp, wp = hp.value, wp.value
-        x = x.contiguous()
-        st = ops._stream()
+        hp, wp = h, w
+        if padded:
+            hp, wp = ctypes.c_int32(), ctypes.c_int32()
+            L.p3d_stem_any_padded(h, w, ctypes.byref(hp), ctypes.byref(wp))
+            hp, wp = hp.value, wp.value
+        x, st = x.contiguous(), ops._stream()
         mult = mask_out = None
         if veil is not None:
             veil = veil.contiguous()
             mult, mask_out = ops.mask_count(veil, 7, 2, 3, 1)
         x_img = torch.empty(L.p3d_stem_image_bytes(n, hp, wp), dtype=torch.uint8, device=x.device)
-        check(L.p3d_stem_image_any(ops._p(x), ops._p(veil), ops._p(x_img), n, cin, h, w, st), 'p3d_stem_image_any')
+        if padded:
+            check(L.p3d_stem_image_any(ops._p(x), ops._p(veil), ops._p(x_img), n, cin, h, w, st), 'p3d_stem_image_any')
+        elif veil is None:
+            check(L.p3d_stem_image(ops._p(x), ops._p(x_img), n, cin, h, w, st), 'p3d_stem_image')
+        else:
+            check(L.p3d_stem_image_masked(ops._p(x), ops._p(veil), ops._p(x_img), n, cin, h, w, st), 'p3d_stem_image_masked')
         c = torch.empty((n, s.k, hp // 2, wp // 2), dtype=torch.float32, device=x.device)
-        check(L.p3d_stem_fwd(ops._p(x_img), self._at(s.img_off), ops._p(c), n, cin, hp, wp, s.k, st), 'p3d_stem_fwd')
+        if padded or veil is None:
+            check(L.p3d_stem_fwd(ops._p(x_img), self._at(s.img_off), ops._p(c), n, cin, hp, wp, s.k, st), 'p3d_stem_fwd')
+        else:
+            check(L.p3d_stem_fwd_masked(ops._p(x_img), self._at(s.img_off), ops._p(c), ops._p(mult), n, cin, h, w, s.k, st), 'p3d_stem_fwd_masked')
         ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         y = torch.empty((n, s.k, (ho - 1) // 2 + 1, (wo - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-        check(L.p3d_stem_tail_infer_any(ops._p(c), self._at(s.bias_off), ops._p(mult), ops._p(y), n, s.k, h, w, st), 'p3d_stem_tail_infer_any')
+        if padded:
+            check(L.p3d_stem_tail_infer_any(ops._p(c), self._at(s.bias_off), ops._p(mult), ops._p(y), n, s.k, h, w, st), 'p3d_stem_tail_infer_any')
+        else:
+            check(L.p3d_stem_tail_infer(ops._p(c), self._at(s.bias_off), ops._p(y), n, s.k, ho, wo, st), 'p3d_stem_tail_infer')
         return y, mask_out
 
-    def _stem(self, s, x):
-        n, cin, h, w = x.shape
-        L = lib()
-        if not (s.foldable and not s.masked and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_supported(n, cin, h, w, s.k)
-                and (h // 2) % 2 == 0 and (w // 2) % 4 == 0):
-            out = None if s.masked else self._stem_any(s, x)
-            if out is not None:
-                return out[0]
-            from ._trunk import stem
-            return stem(s.conv, s.bn, self.model.maxpool, x)
-        x = x.contiguous()
-        st = ops._stream()
-        x_img = torch.empty(L.p3d_stem_image_bytes(n, h, w), dtype=torch.uint8, device=x.device)
-        check(L.p3d_stem_image(ops._p(x), ops._p(x_img), n, cin, h, w, st), 'p3d_stem_image')
-        c = torch.empty((n, s.k, h // 2, w // 2), dtype=torch.float32, device=x.device)
-        check(L.p3d_stem_fwd(ops._p(x_img), self._at(s.img_off), ops._p(c), n, cin, h, w, s.k, st), 'p3d_stem_fwd')
-        y = torch.empty((n, s.k, h // 4, w // 4), dtype=torch.float32, device=x.device)
-        check(L.p3d_stem_tail_infer(ops._p(c), self._at(s.bias_off), ops._p(y), n, s.k, h // 2, w // 2, st), 'p3d_stem_tail_infer')
-        return y
+    def _stem_any(self, s, x, veil=None):
+        return self._stem_x3(s, x, veil, padded=True)
 
-    def _stem_masked(self, s, x, veil):
-        """The PartialConv stem + BatchNorm + ReLU + max pool (partial_depthnet.py:177): conv(x * veil) * mult on the restated stem, then relu(maxpool(.) + b')
-        (relu(maxpool(c mult) + b') = maxpool(relu(c mult + b')): both monotone per channel).  Returns (y, max-pooled mask_out)."""
-        n, cin, h, w = x.shape
-        L = lib()
-        if not (s.foldable and x.is_cuda and x.dtype == torch.float32 and cin == s.cin and L.p3d_stem_masked_supported(n, cin, h, w, s.k)
-                and (h // 2) % 2 == 0 and (w // 2) % 4 == 0):
-            out = self._stem_any(s, x, veil) if s.masked and veil.dtype == torch.float32 and tuple(veil.shape) == (n, 1, h, w) else None
-            if out is not None:
-                return out[0], self.model.maxpool(out[1])
-            from ._trunk import stem_tail
-            c, veil = s.conv(x, veil)                       # today's path (odd sides without odd_sides)
-            return stem_tail(s.bn, self.model.maxpool, c), self.model.maxpool(veil)
-        x, veil = x.contiguous(), veil.contiguous()
-        mult, mask_out = ops.mask_count(veil, 7, 2, 3, 1)
-        st = ops._stream()
-        x_img = torch.empty(L.p3d_stem_image_bytes(n, h, w), dtype=torch.uint8, device=x.device)
-        check(L.p3d_stem_image_masked(ops._p(x), ops._p(veil), ops._p(x_img), n, cin, h, w, st), 'p3d_stem_image_masked')
-        c = torch.empty((n, s.k, h // 2, w // 2), dtype=torch.float32, device=x.device)
-        check(L.p3d_stem_fwd_masked(ops._p(x_img), self._at(s.img_off), ops._p(c), ops._p(mult), n, cin, h, w, s.k, st), 'p3d_stem_fwd_masked')
-        y = torch.empty((n, s.k, h // 4, w // 4), dtype=torch.float32, device=x.device)
-        check(L.p3d_stem_tail_infer(ops._p(c), self._at(s.bias_off), ops._p(y), n, s.k, h // 2, w // 2, st), 'p3d_stem_tail_infer')
-        return y, self.model.maxpool(mask_out)
+    def _stem(self, s, x, veil=None):
+        """The stem of a branch -> y, with a veil (a PartialConv stem) -> (y, max-pooled mask_out): the aligned restated stem, else the padded one, else the
+        model's own modules (odd sides without odd_sides)."""
+        out = None
+        if s.masked == (veil is not None):
+            out = self._stem_x3(s, x, veil) or self._stem_x3(s, x, veil, padded=True)
+        if out is not None:
+            return out[0] if veil is None else (out[0], self.model.maxpool(out[1]))
+        from ._trunk import stem, stem_tail
+        if veil is None:
+            return stem(s.conv, s.bn, self.model.maxpool, x)
+        c, veil = s.conv(x, veil)
+        return stem_tail(s.bn, self.model.maxpool, c), self.model.maxpool(veil)
+
+    _stem_masked = _stem
 
     def _fusion(self, x, y):
         a, b = self.fusion
@@ -632,10 +633,28 @@ class _F8Conv(_HConv):
         return j
 
 
+class _Act:
+    """An activation of an fp8 net: the fp16 NHWC tensor (h), the MXFP8 activation tensor (mx: uint8, p3d_f8act_bytes of them, include/p3d_hip.h), or
+    both; shape is its NCHW shape."""
+    __slots__ = ('shape', 'h', 'mx')
+
+    def __init__(self, shape, h=None, mx=None):
+        self.shape, self.h, self.mx = tuple(shape), h, mx
+
+    @staticmethod
+    def of(x):
+        return x if isinstance(x, _Act) else _Act(x.shape, x)
+
+
+def _mx_supported(d, x_is_mx, y_mx):
+    """p3d_f8conv2d_fwd_infer_mx_supported (host only)"""
+    return bool(lib().p3d_f8conv2d_fwd_infer_mx_supported(ctypes.byref(d), int(bool(x_is_mx)), int(bool(y_mx))))
+
+
 class Fp8FoldedNet(HalfFoldedNet):
     """The -half_acc folded network with the convs between the stems and the heads on p3d_f8conv2d_fwd_infer (MXFP8 weights and activations, fp32
     accumulation, fp16 NHWC in and out).  Takes the same inputs and gives the same outputs as HalfFoldedNet, from fp32 master parameters."""
-    WHO = 'infer.fold_fp8'
+    WHO, MX_ENTRY = 'infer.fold_fp8', False
 
     def Conv(self, conv, bn):
         """_F8Conv when the fp8 entry point takes the conv's shape (queried on a nominal 1 x C x 64 x 64 input), else the fp16 folded _HConv."""
@@ -662,37 +681,31 @@ class Fp8FoldedNet(HalfFoldedNet):
     def _conv_bn(self, c, x, res=None, relu=False, mask_in=None, mult=None):
         """y = fp16(relu?(conv(q(x * mask_in), w') * mult + b' + res)) on the MXFP8 image; an fp16 conv, as HalfFoldedNet; an fp8 conv the entry point
         refuses at this input runs as HalfFoldedNet's per-layer fallback (the unfolded fp16 conv, then the eval-mode BatchNorm pass)."""
+        return self._conv_act(c, _Act.of(x), (True, False), res, relu, mask_in, mult).h
+
+    def _conv_act(self, c, x, forms, res=None, relu=False, mask_in=None, mult=None):
+        """_conv_bn on an _Act, the result an _Act in `forms` (fp16, mx), and the one place an fp8 conv is launched.  Here every activation is fp16 and the
+        entry is p3d_f8conv2d_fwd_infer; under MX_ENTRY (Fp8ResidentNet) it is p3d_f8conv2d_fwd_infer_mx, which reads the MX input when there is one.  The
+        support query is the MX entry's for both: for fp16 in and out it asks what p3d_f8conv2d_fwd_infer_supported asks."""
         if not isinstance(c, _F8Conv):
-            return super()._conv_bn(c, x, res, relu, mask_in, mult)
-        L = lib()
-        d = c.desc(x)
-        if not L.p3d_f8conv2d_fwd_infer_supported(ctypes.byref(d)):
-            return self._unfolded(c, x, res, relu, mask_in, mult)
-        y = ops_half._empty(d.N, d.K, d.Ho, d.Wo, x.device)
-        check(L.p3d_f8conv2d_fwd_infer(ctypes.byref(d), ops._p(x), self._at(c.img_off), self._at(c.bias_off), ops._p(mask_in), ops._p(mult),
-                                       ops._p(res), int(bool(relu)), ops._p(y), ops._stream()), 'p3d_f8conv2d_fwd_infer')
-        return y
+            return _Act.of(HalfFoldedNet._conv_bn(self, c, x.h, res, relu, mask_in, mult))
+        L, d = lib(), c.desc(x)
+        if not _mx_supported(d, x.mx is not None, forms[1]):
+            return _Act.of(self._unfolded(c, x.h, res, relu, mask_in, mult))
+        dev = (x.h if x.mx is None else x.mx).device
+        y = ops_half._empty(d.N, d.K, d.Ho, d.Wo, dev) if forms[0] else None
+        ymx = torch.empty(L.p3d_f8act_bytes(d.N * d.Ho * d.Wo, d.K), dtype=torch.uint8, device=dev) if forms[1] else None
+        tail = ops._p(mask_in), ops._p(mult), ops._p(res), int(bool(relu)), ops._p(y)
+        if self.MX_ENTRY:
+            check(L.p3d_f8conv2d_fwd_infer_mx(ctypes.byref(d), ops._p(x.h) if x.mx is None else None, ops._p(x.mx), self._at(c.img_off), self._at(c.bias_off),
+                                              *tail, ops._p(ymx), ops._stream()), 'p3d_f8conv2d_fwd_infer_mx')
+        else:
+            check(L.p3d_f8conv2d_fwd_infer(ctypes.byref(d), ops._p(x.h), self._at(c.img_off), self._at(c.bias_off), *tail, ops._stream()),
+                  'p3d_f8conv2d_fwd_infer')
+        return _Act((d.N, d.K, d.Ho, d.Wo), y, ymx)
 
 
 # ---- the same, with the activations between fp8 convs kept in MXFP8 ---------------------------------------------------------------------------
-class _Act:
-    """An activation of the resident walk: the fp16 NHWC tensor (h), the MXFP8 activation tensor (mx: uint8, p3d_f8act_bytes of them, include/p3d_hip.h), or
-    both; shape is its NCHW shape."""
-    __slots__ = ('shape', 'h', 'mx')
-
-    def __init__(self, shape, h=None, mx=None):
-        self.shape, self.h, self.mx = tuple(shape), h, mx
-
-    @staticmethod
-    def of(x):
-        return x if isinstance(x, _Act) else _Act(x.shape, x)
-
-
-def _mx_supported(d, x_is_mx, y_mx):
-    """p3d_f8conv2d_fwd_infer_mx_supported (host only)"""
-    return bool(lib().p3d_f8conv2d_fwd_infer_mx_supported(ctypes.byref(d), int(bool(x_is_mx)), int(bool(y_mx))))
-
-
 def resident_forms(chain, i, d, x_is_mx=True):
     """(fp16, mx): the forms in which conv i of a block's chain writes its result under fold_fp8(resident=True); d is its descriptor at the input it gets.
     Needs no device.  The block's output (the chain's last conv; the Fusion 1x1 is a chain of one) is written in both forms: it is the next block's input
@@ -715,40 +728,22 @@ class Fp8ResidentNet(Fp8FoldedNet):
     epilogue, and its readers copy the bytes.  Bit-equal to Fp8FoldedNet, since the block a producer writes is the block the reader would have made from
     the fp16 value.  The walk carries _Act objects; what comes from an fp16 kernel (the pool behind a stem, ops.relu under skip_relu, the concat) is fp16
     only, and the stems, the heads and the per-layer fallback always find an fp16 tensor (resident_forms)."""
+    MX_ENTRY = True
 
-    def _conv_act(self, c, x, forms, res=None, relu=False, mask_in=None, mult=None):
-        """_conv_bn on an _Act, the result in `forms` (fp16, mx); the MX input is read when there is one."""
-        if isinstance(c, _F8Conv):
-            L, d = lib(), c.desc(x)
-            if _mx_supported(d, x.mx is not None, forms[1]):
-                dev = (x.h if x.mx is None else x.mx).device
-                y = ops_half._empty(d.N, d.K, d.Ho, d.Wo, dev) if forms[0] else None
-                ymx = torch.empty(L.p3d_f8act_bytes(d.N * d.Ho * d.Wo, d.K), dtype=torch.uint8, device=dev) if forms[1] else None
-                check(L.p3d_f8conv2d_fwd_infer_mx(ctypes.byref(d), ops._p(x.h) if x.mx is None else None, ops._p(x.mx), self._at(c.img_off), self._at(c.bias_off),
-                                                  ops._p(mask_in), ops._p(mult), ops._p(res), int(bool(relu)), ops._p(y), ops._p(ymx), ops._stream()),
-                      'p3d_f8conv2d_fwd_infer_mx')
-                return _Act((d.N, d.K, d.Ho, d.Wo), y, ymx)
-        return _Act.of(self._conv_bn(c, x.h, res, relu, mask_in, mult))      # an fp16 conv, or the per-layer fallback
+    def _chain_conv(self, c, x, res=None, relu=False, veil=None, chain=None, i=0):
+        """The result in the forms its readers take (resident_forms); the downsample shortcut's only reader is a residual operand, which is fp16."""
+        forms = (True, False) if chain is None else resident_forms(chain, i, c.desc(x), x.mx is not None)
+        mask_in = mult = mask_out = None
+        if veil is not None:
+            mult, mask_out = ops.mask_count(veil, c.r, c.stride, c.pad, c.dil)
+            mask_in = veil.contiguous()
+        return self._conv_act(c, x, forms, None if res is None else res.h, relu, mask_in, mult), mask_out
 
-    def _layer(self, name, x, veil=None):
-        x = _Act.of(x)
-        for plan in self.blocks[name]:
-            blk, chain = plan['block'], plan['chain']
-            res = x.h if plan['ds'] is None else self._conv_act(plan['ds'], x, (True, False)).h
-            out, last = x, len(chain) - 1
-            for i, c in enumerate(chain):
-                forms = resident_forms(chain, i, c.desc(out), out.mx is not None)
-                if blk.partial:
-                    mult, mask_out = ops.mask_count(veil, c.r, c.stride, c.pad, c.dil)
-                    out, veil = self._conv_act(c, out, forms, res if i == last else None, True, veil.contiguous(), mult), mask_out
-                else:
-                    out = self._conv_act(c, out, forms, res if i == last else None, i < last or not blk.skip_relu)
-            x = out
-        return x if veil is None else (x, veil)
+    def _pool(self, x):
+        return _Act.of(super()._pool(x))
 
     def _fusion(self, x, y):
-        cat = _Act.of(ops_half.concat(x.h, y.h))
-        return self._conv_act(self.fusion, cat, resident_forms([self.fusion], 0, self.fusion.desc(cat), False), relu=True)
+        return self._chain_conv(self.fusion, _Act.of(ops_half.concat(x.h, y.h)), relu=True, chain=[self.fusion])[0]
 
     def _relu(self, x):
         return _Act.of(ops.relu(x.h))

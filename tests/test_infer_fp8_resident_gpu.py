@@ -218,6 +218,19 @@ def test_resident_network_bit_equal_to_fold_fp8(pkg, monkeypatch, family, model,
         assert sum(1 for _, _, y16, _ in calls['new'] if y16 is None) == interior
 
 
+def test_resident_skip_relu_bit_equal_to_fold_fp8(pkg):
+    """-skip_relu: the closing conv of layer3 and of layer4 without its ReLU (the feature map has negative values), ops.relu behind each, whose result is
+    fp16 only, so layer4 opens on an fp16 input"""
+    net, args = _net(pkg, 'depthnet', 'resnet18', '-skip_relu', side=64, seed=1)
+    assert net.skip_relu and net.layer3[-1].skip_relu and net.layer4[-1].skip_relu and not net.layer4[0].skip_relu
+    x, _ = _inputs('depthnet', args, 2, 64)
+    want = pkg.infer.fold_fp8(net)(x)
+    got = pkg.infer.fold_fp8(net, resident=True)(x)
+    assert float(want[1].min()) < 0
+    for g, w in zip(got, want):
+        assert g.dtype == w.dtype and torch.isfinite(w).all() and torch.equal(g, w)
+
+
 # ---- 7. refresh, Trainer -------------------------------------------------------------------------------------------------------------------
 def test_resident_refresh_after_optimizer_step(pkg):
     net, _ = _net(pkg, 'depthnet', 'resnet18', side=128)
