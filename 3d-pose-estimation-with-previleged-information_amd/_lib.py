@@ -134,6 +134,10 @@ SIGNATURES = {
     'p3d_conv2d_fwd_any_supported': (_i32, [_desc]),
     'p3d_conv2d_dgrad_any_supported': (_i32, [_desc]),
     'p3d_conv2d_wgrad_any_supported': (_i32, [_desc]),
+    'p3d_x3_any_partial_enable': (_i32, [_i32]),
+    'p3d_conv2d_fwd_masked_any_supported': (_i32, [_desc]),
+    'p3d_conv2d_dgrad_masked_any_supported': (_i32, [_desc]),
+    'p3d_conv2d_wgrad_masked_any_supported': (_i32, [_desc]),
     'p3d_fx_tune': (None, [_i32, _i32]),
     'p3d_conv_path_stats': (None, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), _i32]),
     'p3d_conv_last_fp32_launch': (None, [ctypes.POINTER(_i32)]),

@@ -1182,20 +1182,26 @@ static SplitPlan plan_dgrad1(const p3d_conv_desc* d, bool may_split) { return pl
 //   X3_RAGGED  dense, it refuses for the map width alone, p3d_x3_any_enable is on and the weights are whole (no channel window): the instances for any map width;
 //   X3_MASKED  partial convolution (both factors given; one alone stays on fp32-MFMA) within the masked instances, which take no bias -- written with fx_enabled()
 //              beside the predicate, as the entries always had it (the predicate implies it);
+//   X3_MASKED_RAGGED  partial convolution the masked predicate refuses for the map width alone, p3d_x3_any_partial_enable is on, no bias and whole weights: the masked
+//              instances for any map width (the data gradient: stride 1 only).  Independent of p3d_x3_any_enable;
 //   FP32_MFMA  everything else: an eval epilogue (the x3 entries of p3d_block.hip have their own), an operand off a 16-B line, a refused shape.
 // A forward or data gradient whose workspace is too small for its x3 family quietly runs on fp32-MFMA instead.  The weight gradient does NOT look at workspace_bytes
 // here: it stays on x3 and its entry fails with P3D_EWORKSPACE (both paths need slabs; the x3 plan usually the larger).
-struct ConvRoute { enum Family { FP32_MFMA, X3, X3_RAGGED, X3_MASKED } family; size_t x3_bytes; };
+struct ConvRoute { enum Family { FP32_MFMA, X3, X3_RAGGED, X3_MASKED, X3_MASKED_RAGGED } family; size_t x3_bytes; };
 static bool whole_weight(const p3d_conv_desc* d) { return d->c_offset == 0 && d->c_total == d->C; }
 static bool any_ok(FxPass pass, const p3d_conv_desc* d) { return whole_weight(d) && fx_applies(pass, d, 96, true); }      // (the public p3d_conv2d_*_any_supported: not the switch)
+static bool masked_any_ok(FxPass pass, const p3d_conv_desc* d) { return whole_weight(d) && fx_masked_applies(pass, d, true); }      // (p3d_conv2d_*_masked_any_supported)
 static ConvRoute conv_route(FxPass pass, const p3d_conv_desc* d, int masks /* factors given: 0, 1, 2 */, bool eval_epilogue, bool bias, bool aligned, size_t workspace_bytes) {
     ConvRoute r{ConvRoute::FP32_MFMA, 0};
     if (eval_epilogue || !aligned || masks == 1) return r;
-    if (masks) { if (!bias && fx_enabled() && fx_masked_applies(pass, d)) r.family = ConvRoute::X3_MASKED; }
+    if (masks) {
+        if (!bias && fx_enabled() && fx_masked_applies(pass, d)) r.family = ConvRoute::X3_MASKED;
+        else if (!bias && fx_enabled() && fx_any_partial_enabled() && masked_any_ok(pass, d)) r.family = ConvRoute::X3_MASKED_RAGGED;
+    }
     else if (fx_applies(pass, d)) r.family = ConvRoute::X3;
     else if (fx_any_enabled() && any_ok(pass, d)) r.family = ConvRoute::X3_RAGGED;
     if (r.family == ConvRoute::FP32_MFMA) return r;
-    const bool ragged = r.family == ConvRoute::X3_RAGGED;
+    const bool ragged = r.family == ConvRoute::X3_RAGGED || r.family == ConvRoute::X3_MASKED_RAGGED;
     r.x3_bytes = pass == FX_WGRAD ? (size_t)fx_wgrad_splits(d, false, ragged) * d->K * d->C * d->R * d->S * sizeof(float) : fx_workspace(pass, d, ragged);
     if (pass != FX_WGRAD && workspace_bytes < r.x3_bytes) return ConvRoute{ConvRoute::FP32_MFMA, 0};
     return r;
@@ -1211,6 +1217,7 @@ static FxFuse route_fuse(const ConvRoute& r, const float* pmask, const float* em
     switch (r.family) {
         case ConvRoute::X3_RAGGED: f.ragged = 1; break;                          // the same arithmetic at a map width that is no multiple of 4
         case ConvRoute::X3_MASKED: f.pmask = pmask; f.emask = emask; break;      // the operand times pmask in the fetch, the result times emask in the epilogue
+        case ConvRoute::X3_MASKED_RAGGED: f.ragged = 1; f.pmask = pmask; f.emask = emask; break;      // both
         default: break;                                                          // X3: exact fp32 on the bf16 matrix pipe (p3d_fx.hip), the default path of the dense layers
     }
     return f;
@@ -1429,7 +1436,7 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
     // (a short workspace does not move the route: see conv_route)
     const ConvRoute route = conv_route(FX_WGRAD, d, (mask_in != nullptr) + (mult != nullptr), false, false, aligned16(dy, x, workspace, mask_in, mult), workspace_bytes);
     const bool fx = route.family != ConvRoute::FP32_MFMA;
-    if (fx) { pl.splits = fx_wgrad_splits(d, false, route.family == ConvRoute::X3_RAGGED); pl.tapm = d->R * d->S > 1; }      // slabs [split][k][tap][c]: the tap-major columns of wgrad_reduce_tapm_kernel
+    if (fx) { pl.splits = fx_wgrad_splits(d, false, route.family == ConvRoute::X3_RAGGED || route.family == ConvRoute::X3_MASKED_RAGGED); pl.tapm = d->R * d->S > 1; }      // slabs [split][k][tap][c]: the tap-major columns of wgrad_reduce_tapm_kernel
     fx_count(fx ? 2 : 5, d);
     const size_t need = (size_t)pl.splits * d->K * d->C * d->R * d->S * sizeof(float);
     if (!workspace || workspace_bytes < need) {
@@ -1469,6 +1476,11 @@ int32_t p3d_x3_any_enable(int32_t on) { return fx_set_any_enabled(on); }
 int32_t p3d_conv2d_fwd_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && any_ok(FX_FWD, d) ? 1 : 0; }
 int32_t p3d_conv2d_dgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && any_ok(FX_DGRAD, d) ? 1 : 0; }
 int32_t p3d_conv2d_wgrad_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && any_ok(FX_WGRAD, d) ? 1 : 0; }
+int32_t p3d_x3_any_partial_enable(int32_t on) { return fx_set_any_partial_enabled(on); }
+// what the masked ragged instances admit (a partial convolution with both factors and no bias), whatever the switch says
+int32_t p3d_conv2d_fwd_masked_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && masked_any_ok(FX_FWD, d) ? 1 : 0; }
+int32_t p3d_conv2d_dgrad_masked_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && masked_any_ok(FX_DGRAD, d) ? 1 : 0; }
+int32_t p3d_conv2d_wgrad_masked_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && masked_any_ok(FX_WGRAD, d) ? 1 : 0; }
 void p3d_fx_tune(int32_t what, int32_t value) { fx_tune(what, value); }
 
 void p3d_conv_last_fp32_launch(int32_t* out) {

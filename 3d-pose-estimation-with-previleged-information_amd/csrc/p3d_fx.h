@@ -80,7 +80,8 @@ struct FxFuse {
     int relu;
     int ragged;             // 1: the ragged instances (any map width), for inference and training alike; fp32 operands only.  With `infer`: dense, or a partial convolution
                             // with pmask and emask.  Without: FWD / DGRAD (stride 1) with the plain epilogue, WGRAD on fx_wgrad_any_kernel -- dense fp32-fed training
-                            // launches (p3d_x3_any_enable), no other field set
+                            // launches (p3d_x3_any_enable), no other field set; or the same three as a partial convolution (p3d_x3_any_partial_enable): pmask AND
+                            // emask set, nothing else -- the factor epilogue, fx_wgrad_any_masked_kernel
 };
 constexpr int FX_TAB = 8;   // floats per channel of a table
 
@@ -120,6 +121,8 @@ void fx_tune(int what, int value);
 int fx_set_enabled(int on);
 bool fx_any_enabled();                  // p3d_x3_any_enable / P3D_X3_ANY=1 (default off): the per-layer training entries use the ragged instances where the aligned predicates refuse
 int fx_set_any_enabled(int on);
+bool fx_any_partial_enabled();          // p3d_x3_any_partial_enable / P3D_X3_ANY_PARTIAL=1 (default off): the same for partial convolutions (both factors), independent of the dense switch
+int fx_set_any_partial_enabled(int on);
 void fx_count(int kind, const p3d_conv_desc* d);
 void fx_stats(unsigned long long* counts, double* flops, int reset);
 // Which convolutions the x3 kernels take, per pass: one rule each (p3d_fx.hip).  min_m: the least channel count of the result's tile rows the caller finds worth it (96:
@@ -128,7 +131,7 @@ void fx_stats(unsigned long long* counts, double* flops, int reset);
 // from the aligned one.
 enum FxPass { FX_FWD, FX_DGRAD, FX_WGRAD };
 bool fx_applies(FxPass pass, const p3d_conv_desc* d, int min_m = 96, bool ragged = false);
-bool fx_masked_applies(FxPass pass, const p3d_conv_desc* d, bool ragged = false);      // partial convolutions: the masked instances exist for unsplit launches without bias (ragged: forward, inference only)
+bool fx_masked_applies(FxPass pass, const p3d_conv_desc* d, bool ragged = false);      // partial convolutions: the masked instances take no bias (ragged: all three passes -- inference and, under p3d_x3_any_partial_enable, training; the data gradient stride 1 only)
 size_t fx_workspace(FxPass pass, const p3d_conv_desc* d, bool ragged = false);         // FX_FWD / FX_DGRAD: weight image + split-K slabs of the call's plan; FX_WGRAD: slabs for the larger of the two
                                                                                        // split counts (fp32- or image-fed x), what a caller reserves before it knows which
 int fx_partial_rows(FxPass pass, const p3d_conv_desc* d);                              // FX_FWD / FX_DGRAD: rows of the per-channel partial sums of a launch with a sums epilogue

@@ -149,15 +149,18 @@ __device__ __forceinline__ FxConvParams fx_class_params(const FxConvParams& in) 
 // RAG ("ragged", fx_conv_fwd with FxFuse::ragged): map widths that are not multiples of 4.  The GEMM column stays the flat pixel index, so a thread's four
 // consecutive pixels may straddle an output row or an image: their positions are derived per element when the tap changes, from the first pixel's (row, column,
 // image) kept across the K loop; every fetch is a dword load, and the dense store falls back to dword accesses wherever four pixels do not share an image or a
-// 16-B line.  fp32-fed forward only, epilogues 8 (inference) and 0 (split-K slabs); as a partial convolution (PRO 4) epilogues 9 and 0: the operand factor is fetched
-// per element at the same positions from the one-plane mask (its own image offset, stepped beside x's), the result factor per element in the staged store.
+// 16-B line.  fp32-fed forward only, epilogues 8 (inference) and 0 (split-K slabs, the dense training launches); as a partial convolution (PRO 4) epilogues 9
+// (inference), 4 (training, p3d_x3_any_partial_enable) and 0: the operand factor is fetched per element at the same positions from the one-plane mask (its own image
+// offset, stepped beside x's), the result factor per element in the staged store -- for epilogue 4 BEFORE the accumulate read, so an empty window leaves exactly what
+// the result held.
 template <int AMODE, int PRO, int EPIX, bool TAPI = false, bool RAG = false>
 __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in) {
     static_assert(!TAPI || AMODE == 1, "the tap-inner K order is an image-fed instance");
-    static_assert(!RAG || (AMODE == 0 && ((PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER)) || (PRO == 4 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER_FACTOR)))),
+    static_assert(!RAG || (AMODE == 0 && ((PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER)) || (PRO == 4 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER_FACTOR || EPIX == FX_EPI_FACTOR)))),
                   "the ragged instances are the fp32-fed forward with the plain / inference epilogue, dense or as a partial convolution");
     constexpr int SUMS = fx_epi_sums(EPIX);
-    constexpr bool EM = fx_epi_factor(EPIX);
+    constexpr bool EM = fx_epi_factor(EPIX) && !RAG;          // (ragged: four pixels of the register view may lie in two images or end beyond the factor -- the staged store applies it)
+    constexpr bool EM_RAG = RAG && EPIX == FX_EPI_FACTOR;
     const FxConvParams p = fx_class_params(p_in);
     static_assert(AMODE == 0 || PRO == 0, "the partial-convolution factor is applied by the in-kernel split");
     // one shared array: two buffers of [3 pixel pieces][3 channel pieces]; after the K loop the result tile on its way out (33.8 KB) and, behind it, the
@@ -552,6 +555,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                             while (re >= OHW) { re -= OHW; ++ne; }
                             const size_t ae = ((size_t)ne * p.M + m) * OHW + re;
                             float ve = v[e];
+                            if constexpr (EM_RAG) ve *= p.emask[(size_t)ne * OHW + re];        // the factor first, then what the result held
                             if (accum) ve += yout[ae];
                             if constexpr (EPIX == FX_EPI_INFER_FACTOR) ve = ve * p.emask[(size_t)ne * OHW + re] + (p.bias ? p.bias[m] : 0.f);      // this element's own image
                             if constexpr (fx_epi_infer(EPIX)) {
@@ -562,6 +566,10 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                         }
                         continue;
                     }
+                }
+                if constexpr (EM_RAG) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] *= p.emask[(size_t)n * OHW + rem + e];
                 }
                 if (accum) {
                     f32x4 o4;
@@ -1348,165 +1356,21 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
 // dy is only 4-B aligned.  LDS images, the pixel permutation of the stores, block order, partial tiles and the slab layout are fx_wgrad_kernel's.
 // (A kernel of its own rather than a fifth template axis of fx_wgrad_kernel: none of that kernel's image-fed / masked / multi-tap branches applies, and its
 // instances keep their symbols and their code.)
-__global__ __launch_bounds__(256, 3) void fx_wgrad_any_kernel(const FxWgradParams p) {
-    __shared__ __attribute__((aligned(16))) unsigned char As[2 * 3 * FX_PIECE];
-    __shared__ __attribute__((aligned(16))) unsigned char Bs[2 * 3 * FX_PIECE];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
-    int bx, by, bz;              // the XCD block order of fx_wgrad_kernel
-    {
-        const int gx = gridDim.x, gy = gridDim.y, nwg = gx * gy * gridDim.z;
-        const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-        const int q = nwg >> 3, r = nwg & 7, xcd = lin & 7, idx = lin >> 3;
-        const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        if (p.order == 0) {
-            bx = bid % gx;
-            const int rest = bid / gx;
-            by = rest % gy;
-            bz = rest / gy;
-        } else {
-            const int nt = p.R * p.S;
-            const int tp = bid % nt;
-            int rest = bid / nt;
-            by = rest % gy; rest /= gy;
-            bx = rest % gx;
-            bz = (rest / gx) * nt + tp;
-        }
-    }
-    const int m0 = by * FX_BM, n0 = bx * FX_BN;
-    const int ntaps = p.R * p.S;
-    const int split = bz / ntaps, tap = bz - split * ntaps;
-    const int tr = tap / p.S, ts = tap - tr * p.S;
-    const int dh = tr * p.dil - p.pad, dw = ts * p.dil - p.pad;             // input coordinate = output coordinate * stride + (dh, dw)
-    const int OHW = p.OH * p.OW, HWi = p.Hi * p.Wi, NP = p.N * OHW;
-    const int total = (NP + FX_BK - 1) / FX_BK;                              // the last K step may hold fewer than 16 pixels
-    const int s0 = split * p.spb, s1 = (s0 + p.spb < total) ? s0 + p.spb : total;
-    const int nk = s1 > s0 ? s1 - s0 : 0;                                    // (a slab beyond the range writes zeros)
-    const int row = t >> 2, kq = t & 3;                                      // rows row, row + 64 of the tile, pixels 4 kq .. 4 kq + 3 of the step
-    const int a_bad[2] = {m0 + row < p.K ? 0 : FX_OOB, m0 + row + 64 < p.K ? 0 : FX_OOB}, b_bad[2] = {n0 + row < p.C ? 0 : FX_OOB, n0 + row + 64 < p.C ? 0 : FX_OOB};
-    const i32x4 rA = fx_rsrc(p.DY, (size_t)p.N * p.K * OHW * sizeof(float));
-    const i32x4 rB = fx_rsrc(p.X, (size_t)p.N * p.C * HWi * sizeof(float));
-    const int a_so = 64 * OHW * 4, b_so = 64 * HWi * 4;                      // the second row (wave-uniform; the per-pixel image offsets live in the thread's offsets)
-    const int a_nimg = p.K * OHW, b_nimg = p.C * HWi;                        // elements per image
-    const int di = FX_BK / OHW, dr = (FX_BK - di * OHW) / p.OW, dc = FX_BK - di * OHW - dr * p.OW;
-    int f_q = s0 * FX_BK + 4 * kq, f_oh, f_ow, f_a, f_b;
-    {
-        const int qc = f_q < NP ? f_q : 0;               // (a thread that starts beyond the end stays beyond it: its position is never used)
-        const int n = qc / OHW, rem = qc - n * OHW;
-        f_oh = rem / p.OW; f_ow = rem - f_oh * p.OW;
-        f_a = (n * p.K + m0 + row) * OHW; f_b = (n * p.C + n0 + row) * HWi;
-    }
-    f32x4 ra[2], rb[2];
-    auto fetch = [&]() {
-        int a_voff[4], b_voff[4];
-        int oh = f_oh, ow = f_ow, ia = f_a, ib = f_b;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool ok = f_q + e < NP;
-            const int hi = oh * p.stride + dh, wi = ow * p.stride + dw;
-            a_voff[e] = ok ? (ia + oh * p.OW + ow) * 4 : FX_OOB;
-            b_voff[e] = (ok && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi) ? (ib + hi * p.Wi + wi) * 4 : FX_OOB;
-            if (++ow == p.OW) { ow = 0; if (++oh == p.OH) { oh = 0; ia += a_nimg; ib += b_nimg; } }      // the next flat pixel: next row, next image
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                ra[i][e] = fx_buffer_load_f32(rA, a_voff[e] | a_bad[i], i * a_so, 0);
-                rb[i][e] = fx_buffer_load_f32(rB, b_voff[e] | b_bad[i], i * b_so, 0);
-            }
-        // the thread's first pixel of the next K step
-        f_q += FX_BK;
-        f_ow += dc;
-        if (f_ow >= p.OW) { f_ow -= p.OW; ++f_oh; }
-        f_oh += dr;
-        int carry = di;
-        if (f_oh >= p.OH) { f_oh -= p.OH; ++carry; }
-        f_a += carry * a_nimg; f_b += carry * b_nimg;
-    };
-    const int st_off[2] = {fx_rc_off(row, kq >> 1) + 8 * (kq & 1), fx_rc_off(row + 64, kq >> 1) + 8 * (kq & 1)};
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            fx_split_store(As + buf * 3 * FX_PIECE + st_off[i], ra[i]);
-            fx_split_store(Bs + buf * 3 * FX_PIECE + st_off[i], rb[i]);
-        }
-    };
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    const int fr = lane & 31, fh = lane >> 5;
-    int rd_a[2], rd_b[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        rd_a[a] = fx_rc_off(wm * 64 + a * 32 + fr, fh);
-        rd_b[a] = fx_rc_off(wn * 64 + a * 32 + fr, fh);
-    }
-    const int live_a = fx_live_subtiles(m0 + wm * 64, p.K), live_b = fx_live_subtiles(n0 + wn * 64, p.C);
-    if (nk > 0) { fetch(); stage(0); if (nk > 1) fetch(); }       // the software pipeline of fx_wgrad_kernel
-    __syncthreads();
-    auto kloop = [&](auto nat, auto nbt) {
-        constexpr int NA = decltype(nat)::value, NB = decltype(nbt)::value;
-        constexpr bool LIVE = NA > 0 && NB > 0;
-        auto step = [&](int kt, auto st, auto fe) {
-            const int buf = kt & 1;
-            bf8 af[3][2], bf[3][2];
-            auto read_a = [&](int pc) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-                    if (a < NA) af[pc][a] = *reinterpret_cast<const bf8*>(As + (buf * 3 + pc) * FX_PIECE + rd_a[a]);
-            };
-            auto read_b = [&](int pc) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-                    if (a < NB) bf[pc][a] = *reinterpret_cast<const bf8*>(Bs + (buf * 3 + pc) * FX_PIECE + rd_b[a]);
-            };
-            if constexpr (LIVE) {
-                read_a(2); read_b(0); read_a(0); read_b(2);
-                __builtin_amdgcn_sched_barrier(0);
-                P3D_FX_PRODUCTS_RANGE(acc, af, bf, NA, NB, 0, 1)
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if constexpr (decltype(st)::value) stage(buf ^ 1);
-            if constexpr (decltype(fe)::value) fetch();
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (LIVE) {
-                read_a(1); read_b(1);
-                P3D_FX_PRODUCTS_RANGE(acc, af, bf, NA, NB, 1, 6)
-            }
-            __syncthreads();
-        };
-        int kt = 0;
-        for (; kt + 2 < nk; ++kt) step(kt, std::true_type{}, std::true_type{});
-        if (kt + 1 < nk) { step(kt, std::true_type{}, std::false_type{}); ++kt; }
-        if (kt < nk) step(kt, std::false_type{}, std::false_type{});
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    if (live_a == 0 || live_b == 0) kloop(I0{}, I0{});
-    else if (live_a == 2 && live_b == 2) kloop(I2{}, I2{});
-    else if (live_a == 1 && live_b == 2) kloop(I1{}, I2{});
-    else if (live_a == 2 && live_b == 1) kloop(I2{}, I1{});
-    else kloop(I1{}, I1{});
-    // C/D layout: col = lane & 31 (input channel c, contiguous in the slab), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (output channel k)
-    float* out = p.slabs + (size_t)split * p.K * p.C * ntaps;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int c = n0 + wn * 64 + b * 32 + fr;
-            if (c >= p.C) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int k = m0 + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                if (k < p.K) out[((size_t)k * ntaps + tap) * p.C + c] = acc[a][b][r];
-            }
-        }
-}
+// MASKED (p3d_x3_any_partial_enable: the weight gradient of a partial convolution, dw = wgrad(dy * amask, x * bmask)): the factors are fetched in the same walk, one
+// dword per pixel and operand whatever the row.  amask has one plane per image, so the factor of flat pixel q is element q; bmask's sits at the x offset without
+// the channel row, its image offset carried beside x's.  A factor's offset has the out-of-range bit exactly where its operand's has, and the factor resources keep
+// their exact sizes, so a pixel beyond N OHW or a padding tap is 0 * 0.  The products are taken before the three-piece split, as in fx_wgrad_kernel<.., MASKED>.
+// (One text, p3d_fx_wgrad_any.h, read once per kernel rather than a kernel template or a shared body: the unmasked kernel keeps its symbol and its code.)
+#define P3D_FX_WGRAD_ANY_KERNEL fx_wgrad_any_kernel
+#define P3D_FX_WGRAD_ANY_MASKED false
+#include "p3d_fx_wgrad_any.h"
+#undef P3D_FX_WGRAD_ANY_KERNEL
+#undef P3D_FX_WGRAD_ANY_MASKED
+#define P3D_FX_WGRAD_ANY_KERNEL fx_wgrad_any_masked_kernel
+#define P3D_FX_WGRAD_ANY_MASKED true
+#include "p3d_fx_wgrad_any.h"
+#undef P3D_FX_WGRAD_ANY_KERNEL
+#undef P3D_FX_WGRAD_ANY_MASKED
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // Activation images: fp32 NCHW [N][C][HW] -> three bf16 planes [N][C/16][HW][16], optionally through the BatchNorm + ReLU of the forward pass (MODE 1) or
@@ -1806,6 +1670,13 @@ bool fx_any_enabled() {
     return g_fx_any == 1;
 }
 int fx_set_any_enabled(int on) { const int before = fx_any_enabled() ? 1 : 0; g_fx_any = on ? 1 : 0; return before; }
+// p3d_x3_any_partial_enable: the same offer for partial convolutions (both factors given) the aligned masked predicate refuses.  A switch of its own: neither looks at the other
+static int g_fx_any_partial = -1;
+bool fx_any_partial_enabled() {
+    if (g_fx_any_partial < 0) { const char* e = getenv("P3D_X3_ANY_PARTIAL"); g_fx_any_partial = (e && atoi(e) == 1) ? 1 : 0; }      // default OFF
+    return g_fx_any_partial == 1;
+}
+int fx_set_any_partial_enabled(int on) { const int before = fx_any_partial_enabled() ? 1 : 0; g_fx_any_partial = on ? 1 : 0; return before; }
 
 // coverage counters (launches routed here vs to the fp32-MFMA kernel), read by bench.py so that no fallback goes uncounted
 static std::mutex g_fx_count_mu;
@@ -1899,7 +1770,7 @@ constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool 
     X(1, 0, FX_EPI_STORE, false, false) X(1, 0, FX_EPI_STATS, false, false) X(1, 0, FX_EPI_BWD_SUMS, false, false)                                           \
     X(1, 0, FX_EPI_FACTOR_STATS, false, false) X(1, 0, FX_EPI_FACTOR_BWD_SUMS, false, false) X(1, 0, FX_EPI_FACTOR_IMG, false, false) X(1, 0, FX_EPI_INFER, false, false) \
     X(1, 0, FX_EPI_STORE, true, false) X(1, 0, FX_EPI_STATS, true, false) X(1, 0, FX_EPI_BWD_SUMS, true, false) X(0, 0, FX_EPI_STORE, false, true) X(0, 0, FX_EPI_INFER, false, true) \
-    X(0, 4, FX_EPI_INFER_FACTOR, false, true) X(0, 4, FX_EPI_STORE, false, true)
+    X(0, 4, FX_EPI_INFER_FACTOR, false, true) X(0, 4, FX_EPI_STORE, false, true) X(0, 4, FX_EPI_FACTOR, false, true)
 #define P3D_FX16_CONV_INSTANCES(X)                                                                                             \
     X(96, FX_EPI_STORE, false) X(96, FX_EPI_STATS, false) X(96, FX_EPI_BWD_SUMS, false) X(96, FX_EPI_INFER, false)             \
     X(64, FX_EPI_STORE, false) X(64, FX_EPI_STATS, false) X(64, FX_EPI_BWD_SUMS, false) X(64, FX_EPI_INFER, false)             \
@@ -1927,7 +1798,9 @@ constexpr bool fx_select_covered() {
         if (img && s.pro == 0 && fx16_epi(s.epi) >= 0 && !(fx_instance(96, img, 0, s.epi, false, false) && fx_instance(64, img, 0, s.epi, false, false))) return false;
     }
     return fx_instance(0, false, 0, FX_EPI_INFER, false, true) && fx_instance(0, false, 0, FX_EPI_STORE, false, true) &&     // (the ragged forward: fp32-fed inference,
-           fx_instance(0, false, 4, FX_EPI_INFER_FACTOR, false, true) && fx_instance(0, false, 4, FX_EPI_STORE, false, true);    //  dense and as a partial convolution)
+           fx_instance(0, false, 4, FX_EPI_INFER_FACTOR, false, true) && fx_instance(0, false, 4, FX_EPI_STORE, false, true) &&  //  dense and as a partial convolution;
+           fx_instance(0, false, fx_select(false, false, true, false, false).pro, fx_select(false, false, true, false, false).epi, false, true) &&      //  training: the partial
+           fx_instance(0, false, fx_select(true, false, true, false, false).pro, fx_select(true, false, true, false, false).epi, false, true);          //  convolution's two passes)
 }
 static_assert(fx_select_covered(), "fx_select returns a code without a compiled instance");
 void fx_tune(int what, int value) {
@@ -1980,7 +1853,8 @@ static FxPlan fx_plan(const p3d_conv_desc* d, bool dgrad, bool ragged = false) {
     s.partial_rows = s.splits > 1 ? (d->N < 16 ? d->N : 16) : (int)ceil_div(pixels, FX_BN);
     return s;
 }
-// partial convolutions (PRO 4 / EPI 4 instances): 64-channel layers included (half-dead tiles), unsplit launches only.  P3D_FX_MASKED=0: A/B switch
+// partial convolutions (PRO 4 / EPI 4 instances): 64-channel layers included (half-dead tiles).  P3D_FX_MASKED=0: A/B switch.  ragged: the pass's one rule at the same
+// thresholds without its width clauses (the data gradient: stride 1 only) -- the masked ragged instances, fx_wgrad_any_masked_kernel
 bool fx_masked_applies(FxPass pass, const p3d_conv_desc* d, bool ragged) {
     static const bool on = [] { const char* e = getenv("P3D_FX_MASKED"); return !(e && atoi(e) == 0); }();
     static const int min_m[3] = {64, 64, 96};          // FX_FWD, FX_DGRAD, FX_WGRAD
@@ -2202,7 +2076,8 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     const bool img = fuse && fuse->act_img;
     const bool masked = fuse && (fuse->pmask || fuse->emask);
     const bool infer = fuse && fuse->infer;
-    const bool rag = fuse && fuse->ragged;          // the ragged instances (p3d_fx_conv_fwd_infer_any, p3d_fx_conv_fwd_infer_masked_any; training under p3d_x3_any_enable): any map width
+    const bool rag = fuse && fuse->ragged;          // the ragged instances (p3d_fx_conv_fwd_infer_any, p3d_fx_conv_fwd_infer_masked_any; training under p3d_x3_any_enable, partial
+                                                    // convolutions under p3d_x3_any_partial_enable): any map width
     const void* wimg = fuse ? fuse->wimg : nullptr;
     if (masked && (!fuse->emask || (bias && !infer) || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr))) {
         set_error("fx_conv_fwd: the partial-convolution instances take the output factor, the input factor exactly for an fp32 operand, and no bias"); return P3D_EINVAL;
@@ -2214,7 +2089,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
                 "fx_conv_fwd: the inference epilogue takes a cached folded weight image, no other fusion, and a partial convolution only from an fp32 operand");
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
     P3D_REQUIRE(!rag || !img, "fx_conv_fwd: the ragged forward takes an fp32 operand");
-    P3D_REQUIRE(!(rag && !infer) || (!masked && !fuse->partial), "fx_conv_fwd: the ragged training forward is the plain dense convolution");
+    P3D_REQUIRE(!(rag && !infer) || !fuse->partial, "fx_conv_fwd: the ragged training forward takes no statistics");
     const FxPlan pl = fx_plan(d, false, rag);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     FxConvParams p{};
@@ -2256,8 +2131,8 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
     if (masked && (!fuse->emask || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr) || (!img && fuse->partial))) {
         set_error("fx_conv_dgrad: the partial-convolution instances take the result factor and the operand factor exactly for an fp32 operand"); return P3D_EINVAL;
     }
-    const bool rag = fuse && fuse->ragged;          // the ragged forward instances over dy (p3d_x3_any_enable): any map width, stride 1, dense, fp32-fed
-    P3D_REQUIRE(!rag || (d->stride == 1 && !img && !masked && !fuse->partial && !fuse->acc_src), "fx_conv_dgrad: the ragged data gradient is the plain dense stride-1 one");
+    const bool rag = fuse && fuse->ragged;          // the ragged forward instances over dy (p3d_x3_any_enable; masked: p3d_x3_any_partial_enable): any map width, stride 1, fp32-fed
+    P3D_REQUIRE(!rag || (d->stride == 1 && !img && !fuse->partial && !fuse->acc_src), "fx_conv_dgrad: the ragged data gradient is the stride-1 one, dense or masked, without sums");
     const FxPlan pl = fx_plan(d, true, rag);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_dgrad: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     if (fuse && fuse->acc_src && !(d->accumulate && fx_dgrad_accumulates_from_source(d))) {
@@ -2392,9 +2267,14 @@ int32_t fx_conv_wgrad_slabs(const p3d_conv_desc* d, const float* dy, const float
     p.spb = (int)ceil_div((int64_t)d->N * (d->Ho * d->Wo / FX_BK), splits);
     p.order = fx_wgrad_order(d);
     if (fuse && fuse->ragged) {          // any map width: K steps over the flat pixel index, the last one partial (fx_wgrad_any_kernel)
-        if (fuse->dy_img || fuse->x_img || fuse->pmask || fuse->emask) { set_error("fx_conv_wgrad: the ragged weight gradient takes fp32 operands and no factor"); return P3D_EINVAL; }
+        if (fuse->dy_img || fuse->x_img || (fuse->pmask != nullptr) != (fuse->emask != nullptr)) {
+            set_error("fx_conv_wgrad: the ragged weight gradient takes fp32 operands and both factors of a partial convolution or neither"); return P3D_EINVAL;
+        }
+        p.amask = fuse->pmask; p.bmask = fuse->emask;
         p.spb = (int)ceil_div(ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BK), splits);
-        hipLaunchKernelGGL(fx_wgrad_any_kernel, dim3((unsigned)ceil_div(d->C, FX_BN), (unsigned)ceil_div(d->K, FX_BM), (unsigned)(splits * d->R * d->S)), dim3(256), 0, st, p);
+        const dim3 grid((unsigned)ceil_div(d->C, FX_BN), (unsigned)ceil_div(d->K, FX_BM), (unsigned)(splits * d->R * d->S));
+        if (fuse->pmask) hipLaunchKernelGGL(fx_wgrad_any_masked_kernel, grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(fx_wgrad_any_kernel, grid, dim3(256), 0, st, p);
         prof_kernel_done(st);
         return check_launch("fx_conv_wgrad");
     }

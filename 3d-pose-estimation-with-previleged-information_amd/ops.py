@@ -917,6 +917,13 @@ def x3_any(on):
     return bool(lib().p3d_x3_any_enable(int(bool(on))))
 
 
+def x3_any_partial(on):
+    """Opt-in, OFF by default (P3D_X3_ANY_PARTIAL=1 turns it on), independent of x3_any: the per-layer training path runs PARTIAL convolutions (PartialConv without
+    a bias: both factors given) on the masked x3 kernels at map widths that are no multiples of 4 -- forward, stride-1 data gradient and weight gradient of the
+    partial families' layer1 / layer2 at the default 257 crop -- instead of the fp32-MFMA kernels.  Returns the previous setting."""
+    return bool(lib().p3d_x3_any_partial_enable(int(bool(on))))
+
+
 X3_EPOCH = 0
 WEIGHT_EPOCH = 0          # bumped whenever parameters are written behind torch's back (FlatAdam's kernels, broadcasts into / restores of flat_p): cached per-weight derivatives (ops_block.weight_images) are stale
 

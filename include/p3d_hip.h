@@ -108,6 +108,20 @@ int32_t p3d_x3_any_enable(int32_t on);
 int32_t p3d_conv2d_fwd_any_supported(const p3d_conv_desc* d);
 int32_t p3d_conv2d_dgrad_any_supported(const p3d_conv_desc* d);
 int32_t p3d_conv2d_wgrad_any_supported(const p3d_conv_desc* d);
+/* Opt-in, a switch of its own (default OFF; P3D_X3_ANY_PARTIAL=1 in the environment turns it on; independent of p3d_x3_any_enable): the same for PARTIAL convolutions.
+ * p3d_conv2d_fwd, p3d_conv2d_dgrad (stride 1) and p3d_conv2d_wgrad, called with BOTH factors (mask_in and mult), no bias and a whole weight tensor, run a convolution that
+ * the aligned masked instances refuse only for its map width on the masked ragged x3 instances instead of the fp32-MFMA kernels: y = conv(x * mask_in) * mult,
+ * dx (+)= dgrad(dy * mult) * mask_in (the factor before the accumulate read: where mask_in is 0 an accumulating call leaves dx bit for bit), dw = wgrad(dy * mult,
+ * x * mask_in).  While it is on the three workspace queries report the larger of the plans.  As for the dense switch, a forward or data gradient whose workspace is too
+ * small, or an operand off a 16-B line, quietly runs on fp32-MFMA; a weight gradient whose workspace is too small fails with P3D_EWORKSPACE.  A call with one factor, a
+ * bias, a channel window or a strided data gradient, every dense call and every aligned shape are launched exactly as with the switch off.  Returns the previous setting.
+ * p3d_conv2d_*_masked_any_supported: 1 where the masked ragged instances of that pass admit the convolution (whatever the switch says; aligned shapes too, which the
+ * entries keep on the aligned masked instances), 0 otherwise.  The rules are the dense ones at the masked thresholds: 64 result channels for the forward and the
+ * data gradient, 96 on both sides for the weight gradient. */
+int32_t p3d_x3_any_partial_enable(int32_t on);
+int32_t p3d_conv2d_fwd_masked_any_supported(const p3d_conv_desc* d);
+int32_t p3d_conv2d_dgrad_masked_any_supported(const p3d_conv_desc* d);
+int32_t p3d_conv2d_wgrad_masked_any_supported(const p3d_conv_desc* d);
 /* Test and tuning hooks of the x3 path; value 0 restores the built-in behaviour unless noted.  Codes:
  *   0  forced split count of the weight-gradient launches                  (tools/split_sweep.py, tests/test_kernels_gpu.py)
  *   1  forced split count of the forward / data-gradient launches          (the same)

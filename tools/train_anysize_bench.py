@@ -7,6 +7,10 @@
   --step      the whole training step at --side (default 257): legs `off` and `on` alternating, --rounds rounds of --iters steps after --warmup, median [min .. max]
               ms per step of each leg, the launch counts per step and pass of both legs, and the verdict: `on` wins when its median is below `off`'s by more than the
               two legs' combined spread (max - min).  On a build without ops.x3_any (the parent commit) only the `off` leg runs.
+  --family    depthnet (default: the above), partial_depthnet or partial_fusionnet (profiles/train_anysize_partial.md).  For the partial families --step runs three
+              legs -- `off`, `any` (ops.x3_any) and `both` (ops.x3_any and ops.x3_any_partial) -- and `both` wins when it beats `any` by more than their combined
+              spread; --classes times the masked convolutions of layer1 / layer2 (both factors, no bias) on the fp32-MFMA masked kernels, on the masked ragged
+              x3 instances, and the dense convolution of the same shape on the dense ragged instances.
 GPU box only."""
 import argparse
 import ctypes
@@ -32,11 +36,25 @@ R50 = [(64, 65, 64, 1, 1, 1, 1), (64, 65, 64, 3, 1, 1, 3), (64, 65, 256, 1, 1, 1
        (2048, 17, 512, 1, 1, 1, 2), (512, 17, 512, 3, 1, 1, 2), (2048, 17, 272, 3, 1, 1, 1)]
 
 
-def switch(on):
+# the PartialConvs of ResNet-50's layer1 / layer2 (partial_depthnet, partial_fusionnet: the shortcuts are dense), same columns
+R50_PARTIAL = [(64, 65, 64, 1, 1, 1, 1), (64, 65, 64, 3, 1, 1, 3), (64, 65, 256, 1, 1, 1, 3), (256, 65, 64, 1, 1, 1, 2),
+               (256, 65, 128, 1, 1, 1, 1), (128, 65, 128, 3, 2, 1, 1), (128, 33, 512, 1, 1, 1, 4), (512, 33, 128, 1, 1, 1, 3), (128, 33, 128, 3, 1, 1, 3)]
+FAMILY_FLAGS = {'depthnet': [], 'partial_depthnet': ['-depth_only', '-partial_conv'], 'partial_fusionnet': ['-do_fusion', '-partial_conv']}
+
+
+def switch(on, partial=False):
     if hasattr(ops, 'x3_any'):
         ops.x3_any(on)
     elif on:
         raise SystemExit('this build has no ops.x3_any')
+    if hasattr(ops, 'x3_any_partial'):
+        ops.x3_any_partial(partial)
+    elif partial:
+        raise SystemExit('this build has no ops.x3_any_partial')
+
+
+def switch_leg(leg):
+    switch(leg in ('on', 'any', 'both'), leg == 'both')
 
 
 def timed(fn, iters):
@@ -105,9 +123,68 @@ def classes(a):
     print('all three passes: off %.2f ms  on %.2f ms' % (sum(total[(p, 'off')] for p in PASSES), sum(total[(p, 'on')] for p in PASSES)))
 
 
+def classes_partial(a):
+    """the masked classes: leg `fp32` (the switch off), `x3` (ops.x3_any_partial on), `dense` (the same shape without factors under ops.x3_any)"""
+    L = pkg._lib.lib()
+    legs = ('fp32', 'x3', 'dense')
+    total = {(p, leg): 0.0 for p in PASSES for leg in legs}
+    for (c, h, k, ks, st, dil, cnt) in sorted(R50_PARTIAL, key=lambda r: -r[0] * r[2] * r[3] ** 2 * ((r[1] // r[4] + 1) ** 2) * r[6]):
+        tag = 'c%d h%d k%d %dx%d s%d d%d x%d' % (c, h, k, ks, ks, st, dil, cnt)
+        if a.only and a.only not in tag:
+            continue
+        torch.manual_seed(c + k)
+        pad = dil * (ks - 1) // 2
+        x = torch.randn(a.batch, c, h, h, device='cuda')
+        w = torch.randn(k, c, ks, ks, device='cuda') / (c * ks * ks) ** 0.5
+        m = (torch.rand(a.batch, 1, h, h, device='cuda') >= 0.3).float()
+        mult, _ = ops.mask_count(m, ks, st, pad, dil)
+        d = ops._desc(x.shape, w.shape, st, pad, dil)
+        dy = torch.randn(a.batch, k, d.Ho, d.Wo, device='cuda')
+        y, dx, dw = torch.empty_like(dy), torch.empty_like(x), torch.empty_like(w)
+        b = ctypes.byref(d)
+        switch(True, True)                                       # (the largest plan: one workspace serves every leg)
+        ws = torch.empty(max(L.p3d_conv2d_fwd_workspace_bytes(b), L.p3d_conv2d_dgrad_workspace_bytes(b), L.p3d_conv2d_wgrad_workspace_bytes(b), 16), dtype=torch.uint8, device='cuda')
+        switch(False)
+        P, stream = ops._p, ops._stream()
+
+        def calls(masked):
+            mi, mu = (P(m), P(mult)) if masked else (None, None)
+            return {'fwd': lambda: L.p3d_conv2d_fwd(b, P(x), P(w), None, mi, mu, P(y), P(ws), ws.numel(), stream),
+                    'dgrad': lambda: L.p3d_conv2d_dgrad(b, P(dy), P(w), mu, mi, P(dx), P(ws), ws.numel(), stream),
+                    'wgrad': lambda: L.p3d_conv2d_wgrad(b, P(dy), P(x), mu, mi, P(dw), P(ws), ws.numel(), stream)}
+
+        def set_leg(leg):
+            switch(leg == 'dense', leg == 'x3')
+
+        gf = 2.0 * a.batch * k * c * ks * ks * d.Ho * d.Wo / 1e9
+        for name in PASSES:
+            fns = {leg: calls(leg != 'dense')[name] for leg in legs}
+            ms, ran = {leg: [] for leg in legs}, {}
+            for leg in legs:
+                set_leg(leg)
+                ops.conv_path_stats(reset=True)
+                for _ in range(3):
+                    assert fns[leg]() == 0, pkg._lib.lib().p3d_last_error()
+                ran[leg] = family(ops.conv_path_stats(reset=True), name)
+            for _ in range(a.rounds):
+                for leg in legs:
+                    set_leg(leg)
+                    ms[leg].append(timed(fns[leg], a.iters))
+            switch(False)
+            assert ran['fp32'] == 'fp32', (tag, name, ran)
+            m0, m1, m2 = med(ms['fp32']), med(ms['x3']), med(ms['dense'])
+            print('%-28s %-5s %7.2f GF | masked off %-4s %.3f [%.3f..%.3f] ms | masked on %-4s %.3f [%.3f..%.3f] ms | dense %-4s %.3f [%.3f..%.3f] ms | on/off %.2f  on/dense %.2f' % (
+                (tag, name, gf, ran['fp32']) + m0 + (ran['x3'],) + m1 + (ran['dense'],) + m2 + (m1[0] / m0[0], m1[0] / m2[0])), flush=True)
+            for leg, mm in zip(legs, (m0, m1, m2)):
+                total[(name, leg)] += mm[0] * cnt
+    for name in PASSES:
+        print('sum over the classes x their layer counts, %-5s: masked off %.2f ms  masked on %.2f ms  dense %.2f ms' % ((name,) + tuple(total[(name, leg)] for leg in legs)))
+    print('all three passes: masked off %.2f ms  masked on %.2f ms  dense %.2f ms' % tuple(sum(total[(p, leg)] for p in PASSES) for leg in legs))
+
+
 def step(a):
     flags = ['-model', a.model, '-suffix', 'bench', '-data_name', 'h36m', '-save_path', '/tmp/p3d_bench', '-criterion', 'SmoothL1', '-num_joints', '17', '-side_in', str(a.side),
-             '-stride', '16', '-depth', '16', '-depth_range', '1000', '-loss_div', '10', '-learn_rate', '5e-5', '-weight_decay', '4e-5', '-grad_norm', '5']
+             '-stride', '16', '-depth', '16', '-depth_range', '1000', '-loss_div', '10', '-learn_rate', '5e-5', '-weight_decay', '4e-5', '-grad_norm', '5'] + FAMILY_FLAGS[a.family]
     args = pkg.opts.parse(flags)
     torch.manual_seed(0)
     model, _ = pkg.depth_main.create_model(args)
@@ -118,8 +195,10 @@ def step(a):
     batches = []
     for i in range(3):
         c, d, tc, tv = pkg.synth.make_batch(a.batch, side=a.side, rank=0, step=i)
-        batches.append((torch.from_numpy(c).cuda(), None, torch.from_numpy(tc).cuda(), torch.from_numpy(tv).cuda()))
+        batches.append((torch.from_numpy(c).cuda(), None if a.family == 'depthnet' else torch.from_numpy(d).cuda(), torch.from_numpy(tc).cuda(), torch.from_numpy(tv).cuda()))
     legs = ('off', 'on') if hasattr(ops, 'x3_any') and not a.off_only else ('off',)
+    if a.family != 'depthnet' and len(legs) == 2:
+        legs = ('off', 'any', 'both') if hasattr(ops, 'x3_any_partial') else ('off', 'any')
 
     def run(n):
         for i in range(n):
@@ -128,7 +207,7 @@ def step(a):
 
     ms, counts = {leg: [] for leg in legs}, {}
     for leg in legs:
-        switch(leg == 'on')
+        switch_leg(leg)
         run(a.warmup)
         torch.cuda.synchronize()
         ops.conv_path_stats(reset=True)
@@ -138,17 +217,24 @@ def step(a):
         counts[leg] = {fam: {p: st[fam][p][0] for p in PASSES} for fam in ('x3', 'fp32')}
     for r in range(a.rounds):
         for leg in legs:
-            switch(leg == 'on')
+            switch_leg(leg)
             run(2)
             torch.cuda.synchronize()
             ms[leg].append(timed(lambda: run(a.iters), 1) / a.iters)
             print('round %d %-3s %.3f ms/step' % (r, leg, ms[leg][-1]), flush=True)
     switch(False)
     out = {'side': a.side, 'batch': a.batch, 'model': a.model, 'launches_per_step': counts}
+    if a.family != 'depthnet':
+        out['family'] = a.family
     for leg in legs:
         m = med(ms[leg])
         out[leg] = {'median_ms': round(m[0], 3), 'min_ms': round(m[1], 3), 'max_ms': round(m[2], 3)}
-    if len(legs) == 2:
+    if legs == ('off', 'any', 'both'):
+        spread = (out['any']['max_ms'] - out['any']['min_ms']) + (out['both']['max_ms'] - out['both']['min_ms'])
+        out['gain_ms'] = round(out['any']['median_ms'] - out['both']['median_ms'], 3)
+        out['combined_spread_ms'] = round(spread, 3)
+        out['both_wins'] = bool(out['gain_ms'] > spread)
+    elif legs == ('off', 'on'):
         spread = (out['off']['max_ms'] - out['off']['min_ms']) + (out['on']['max_ms'] - out['on']['min_ms'])
         out['gain_ms'] = round(out['off']['median_ms'] - out['on']['median_ms'], 3)
         out['combined_spread_ms'] = round(spread, 3)
@@ -168,9 +254,10 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--only', default='')
+    ap.add_argument('--family', default='depthnet', choices=sorted(FAMILY_FLAGS))
     a = ap.parse_args()
     if a.classes:
-        classes(a)
+        (classes if a.family == 'depthnet' else classes_partial)(a)
     if a.step:
         step(a)
 
