@@ -80,6 +80,13 @@ SIGNATURES = {
     'p3d_fx_conv_fwd_img': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_fx_conv_dgrad_img': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_fx_conv_wgrad_img': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    'p3d_x3_any_images_enable': (_i32, [_i32]),
+    'p3d_fx_conv_img_any_supported': (_i32, [_ptr]),
+    'p3d_fx_conv_img_any_workspace_bytes': (_sz, [_ptr, _i32]),
+    'p3d_fx_act_image_any': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _ptr]),
+    'p3d_fx_conv_fwd_img_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    'p3d_fx_conv_dgrad_img_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    'p3d_fx_conv_wgrad_img_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_stem_supported': (_i32, [_i32] * 5),
     'p3d_stem_image_bytes': (_sz, [_i32] * 3),
     'p3d_stem_weight_image_bytes': (_sz, [_i32]),

@@ -933,6 +933,78 @@ int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const 
     return wgrad_finish(d, (float*)workspace, splits, d->R * d->S > 1, dw, (hipStream_t)stream);
 }
 
+// The same three passes at any map width (include/p3d_hip.h): the ragged image-fed instances of fx_conv_kernel and fx_wgrad_any_img_kernel.  Dense convolutions with
+// whole weights only, no fp32 fallback for an operand; for the shapes p3d_fx_conv_img_supported refuses, correct at the ones it admits too.
+int32_t p3d_x3_any_images_enable(int32_t on) { return fx_set_any_images_enabled(on); }
+
+static int32_t img_any_bits(const p3d_conv_desc* d) {
+    if (!d || d->N <= 0 || d->C <= 0 || d->K <= 0 || d->H <= 0 || d->W <= 0 || d->R <= 0 || d->S <= 0 || d->stride < 1 || d->dil < 1 || d->pad < 0) return 0;
+    // (the kernels take the geometry from the descriptor: the output sides must be the derived ones)
+    if (d->Ho <= 0 || d->Wo <= 0 || d->Ho != (d->H + 2 * d->pad - d->dil * (d->R - 1) - 1) / d->stride + 1 || d->Wo != (d->W + 2 * d->pad - d->dil * (d->S - 1) - 1) / d->stride + 1) return 0;
+    if (d->C % 16 != 0 || d->K % 16 != 0 || d->Ho * d->Wo < 16 || d->c_offset != 0 || d->c_total != d->C) return 0;
+    return (fx_applies(FX_FWD, d, 96, true) ? 1 : 0) | (d->stride == 1 && fx_applies(FX_DGRAD, d, 96, true) ? 2 : 0) | (fx_applies(FX_WGRAD, d, 96, true) ? 4 : 0);
+}
+int32_t p3d_fx_conv_img_any_supported(const p3d_conv_desc* d) { return img_any_bits(d); }
+
+size_t p3d_fx_conv_img_any_workspace_bytes(const p3d_conv_desc* d, int32_t pass) {
+    if (!d) return 0;
+    return fx_workspace(pass == 0 ? FX_FWD : pass == 1 ? FX_DGRAD : FX_WGRAD, d, true);
+}
+
+int32_t p3d_fx_act_image_any(const float* x, void* img, int32_t N, int32_t C, int32_t HW, void* stream) {
+    return fx_act_image_any(x, img, N, C, HW, (hipStream_t)stream);
+}
+
+int32_t p3d_fx_conv_fwd_img_any(const p3d_conv_desc* d, const void* x_img, const float* w, const void* wimg, const float* bias, float* y, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    P3D_REQUIRE(d && x_img && w && y, "fx_conv_fwd_img_any: null argument");
+    P3D_REQUIRE(img_any_bits(d) & 1, "fx_conv_fwd_img_any: shape outside the ragged image-fed kernels");
+    P3D_REQUIRE(d->accumulate == 0 || d->accumulate == 1, "fx_conv_fwd_img_any: accumulate must be 0 or 1");
+    P3D_REQUIRE(aligned16(x_img, wimg, y, workspace), "fx_conv_fwd_img_any: the image, the weight image, y and the workspace must be 16-B aligned");
+    const size_t need = fx_workspace(FX_FWD, d, true);
+    if (need && (!workspace || workspace_bytes < need)) { set_error("fx_conv_fwd_img_any: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
+    FxFuse f{};
+    f.act_img = x_img; f.wimg = wimg; f.ragged = 1;
+    ProfScope ps(0, d, (hipStream_t)stream);
+    fx_count(0, d);
+    return name_entry("fx_conv_fwd_img_any", fx_conv_fwd(d, nullptr, w, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
+}
+
+int32_t p3d_fx_conv_dgrad_img_any(const p3d_conv_desc* d, const void* dy_img, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    P3D_REQUIRE(d && dy_img && w && dx, "fx_conv_dgrad_img_any: null argument");
+    P3D_REQUIRE(img_any_bits(d) & 2, "fx_conv_dgrad_img_any: shape outside the ragged image-fed kernels (stride 1 only)");
+    P3D_REQUIRE(d->accumulate == 0 || d->accumulate == 1, "fx_conv_dgrad_img_any: accumulate must be 0 or 1");
+    P3D_REQUIRE(aligned16(dy_img, wimgT, dx, workspace), "fx_conv_dgrad_img_any: the image, the weight image, dx and the workspace must be 16-B aligned");
+    const size_t need = fx_workspace(FX_DGRAD, d, true);
+    if (need && (!workspace || workspace_bytes < need)) { set_error("fx_conv_dgrad_img_any: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
+    FxFuse f{};
+    f.act_img = dy_img; f.wimg = wimgT; f.ragged = 1;
+    ProfScope ps(1, d, (hipStream_t)stream);
+    fx_count(1, d);
+    return name_entry("fx_conv_dgrad_img_any", fx_conv_dgrad(d, nullptr, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream));
+}
+
+// x: ignored (the signature of p3d_fx_conv_wgrad_img; there is no fp32 fallback here)
+int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    (void)x;
+    P3D_REQUIRE(d && dy_img && x_img && dw, "fx_conv_wgrad_img_any: null argument (both images are required)");
+    P3D_REQUIRE(img_any_bits(d) & 4, "fx_conv_wgrad_img_any: shape outside the ragged image-fed kernels");
+    P3D_REQUIRE(d->accumulate == 0 || d->accumulate == 1, "fx_conv_wgrad_img_any: accumulate must be 0 or 1");
+    // (dw may sit anywhere on a 4-B line -- a view into a flat gradient buffer: wgrad_finish picks its accesses by the address)
+    P3D_REQUIRE(aligned16(dy_img, x_img, workspace) && (reinterpret_cast<uintptr_t>(dw) & 3) == 0, "fx_conv_wgrad_img_any: the images and the workspace must be 16-B aligned");
+    const int splits = fx_wgrad_splits(d, true, true);
+    const size_t need = (size_t)splits * d->K * d->C * d->R * d->S * sizeof(float);
+    if (!workspace || workspace_bytes < need) { set_error("fx_conv_wgrad_img_any: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
+    FxFuse f{};
+    f.dy_img = dy_img; f.x_img = x_img; f.ragged = 1;
+    ProfScope ps(2, d, (hipStream_t)stream);
+    fx_count(2, d);
+    if (int32_t e = name_entry("fx_conv_wgrad_img_any", fx_conv_wgrad_slabs(d, nullptr, nullptr, (float*)workspace, splits, &f, (hipStream_t)stream))) return e;
+    return name_entry("fx_conv_wgrad_img_any", wgrad_finish(d, (float*)workspace, splits, d->R * d->S > 1, dw, (hipStream_t)stream));
+}
+
 // Inference with folded BatchNorm (include/p3d_hip.h): the fold of a whole network in one launch, and the forward on the folded images with the inference epilogue.
 int32_t p3d_fx_fold_bn_images(const void* jobs, int32_t njobs, int32_t blocks, void* stream) {
     P3D_REQUIRE(jobs && njobs > 0 && blocks > 0, "fold_bn_images: bad argument");

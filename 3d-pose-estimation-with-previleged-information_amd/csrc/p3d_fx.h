@@ -78,7 +78,8 @@ struct FxFuse {
     int infer;              // 0 / 1
     const float* res;
     int relu;
-    int ragged;             // 1: the ragged instances (any map width), for inference and training alike; fp32 operands only.  With `infer`: dense, or a partial convolution
+    int ragged;             // 1: the ragged instances (any map width), for inference and training alike; fp32 operands, or (dense training launches only, nothing else set:
+                            // p3d_fx_conv_*_img_any) act_img for FWD / DGRAD (stride 1) and dy_img AND x_img for WGRAD (fx_wgrad_any_img_kernel).  With `infer`: dense, or a partial convolution
                             // with pmask and emask.  Without: FWD / DGRAD (stride 1) with the plain epilogue, WGRAD on fx_wgrad_any_kernel -- dense fp32-fed training
                             // launches (p3d_x3_any_enable), no other field set; or the same three as a partial convolution (p3d_x3_any_partial_enable): pmask AND
                             // emask set, nothing else -- the factor epilogue, fx_wgrad_any_masked_kernel
@@ -123,6 +124,8 @@ bool fx_any_enabled();                  // p3d_x3_any_enable / P3D_X3_ANY=1 (def
 int fx_set_any_enabled(int on);
 bool fx_any_partial_enabled();          // p3d_x3_any_partial_enable / P3D_X3_ANY_PARTIAL=1 (default off): the same for partial convolutions (both factors), independent of the dense switch
 int fx_set_any_partial_enabled(int on);
+bool fx_any_images_enabled();           // p3d_x3_any_images_enable / P3D_X3_ANY_IMAGES=1 (default off): image-feeding callers (ops_block.ConvImagesFn) use the ragged image-fed entries where the aligned query refuses; kept for them, read by no entry point
+int fx_set_any_images_enabled(int on);
 void fx_count(int kind, const p3d_conv_desc* d);
 void fx_stats(unsigned long long* counts, double* flops, int reset);
 // Which convolutions the x3 kernels take, per pass: one rule each (p3d_fx.hip).  min_m: the least channel count of the result's tile rows the caller finds worth it (96:
@@ -185,6 +188,8 @@ int32_t fx_act_image_pair(const float* x, const unsigned char* gmask, const floa
                           int N, int C, int HW, hipStream_t st, const float* pixmul_a = nullptr);
 int32_t fx_act_image(int mode, const float* x, const float* x2, const float* table, int masked, void* img, int N, int C, int HW, hipStream_t st,
                      const FxFinalize* fin = nullptr, const float* pixmul = nullptr);
+// mode 0 at any HW (the same bytes; x read with dword loads where a row is not 16-B aligned, the last pixel group of an image partial)
+int32_t fx_act_image_any(const float* x, void* img, int N, int C, int HW, hipStream_t st);
 
 // The 7x7 stride-2 stem (Cin = 1..4) as a 4x4 stride-1 convolution over a space-to-depth image of the input (p3d_fx.hip)
 bool fx_stem_applies(int N, int Cin, int H, int W, int K);

@@ -153,11 +153,14 @@ __device__ __forceinline__ FxConvParams fx_class_params(const FxConvParams& in) 
 // (inference), 4 (training, p3d_x3_any_partial_enable) and 0: the operand factor is fetched per element at the same positions from the one-plane mask (its own image
 // offset, stepped beside x's), the result factor per element in the staged store -- for epilogue 4 BEFORE the accumulate read, so an empty window leaves exactly what
 // the result held.
+// Image-fed (AMODE 1, p3d_x3_any_images_enable), epilogue 0 only, either K order: the operand side is the AMODE 1 fetch as it is -- one pixel's 32-B row per thread, its
+// position from the flat column, so nothing there knows of four-pixel groups -- and the result side the staged store above.
 template <int AMODE, int PRO, int EPIX, bool TAPI = false, bool RAG = false>
 __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in) {
     static_assert(!TAPI || AMODE == 1, "the tap-inner K order is an image-fed instance");
-    static_assert(!RAG || (AMODE == 0 && ((PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER)) || (PRO == 4 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER_FACTOR || EPIX == FX_EPI_FACTOR)))),
-                  "the ragged instances are the fp32-fed forward with the plain / inference epilogue, dense or as a partial convolution");
+    static_assert(!RAG || (AMODE == 1 && PRO == 0 && EPIX == FX_EPI_STORE) ||
+                      (AMODE == 0 && ((PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER)) || (PRO == 4 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER_FACTOR || EPIX == FX_EPI_FACTOR)))),
+                  "the ragged instances are the fp32-fed forward with the plain / inference epilogue, dense or as a partial convolution, and the image-fed forward with the plain one");
     constexpr int SUMS = fx_epi_sums(EPIX);
     constexpr bool EM = fx_epi_factor(EPIX) && !RAG;          // (ragged: four pixels of the register view may lie in two images or end beyond the factor -- the staged store applies it)
     constexpr bool EM_RAG = RAG && EPIX == FX_EPI_FACTOR;
@@ -1372,6 +1375,171 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
 #undef P3D_FX_WGRAD_ANY_KERNEL
 #undef P3D_FX_WGRAD_ANY_MASKED
 
+// The image-fed ragged weight gradient (p3d_x3_any_images_enable): fx_wgrad_kernel<true, true, false> -- both operands activation images, one tap per block -- over
+// the K steps of fx_wgrad_any_kernel: 16 consecutive values of the flat pixel index n OHW + oh OW + ow, the last step partial, a step free to span a row end or an image
+// end.  An image operand is per pixel already: a thread copies ONE pixel's 16-B chunk (8 channels of one of the tile's eight channel groups) per plane, operand and
+// step, no split and no four-pixel walk.  It keeps its pixel as (image, output row, output column) and moves
+// 16 pixels on per step with one conditional carry per level (16 = di images + dr rows + dc columns; OHW >= 16, so di <= 1: p3d_fx_conv_img_any_supported refuses
+// smaller maps) -- no division in the loop.  A pixel at or beyond N OHW, or one whose tap falls into the padding, carries the out-of-range bit on BOTH operands: 0 * 0,
+// whatever the other operand holds, and the resources keep the images' exact sizes.  The LDS "tr" images, the pixel permutation of the chunk stores, the XCD block
+// order, the partial tiles and the slab layout are fx_wgrad_kernel's.  (A kernel of its own, like fx_wgrad_any_kernel: that kernel's instances keep their code.)
+__global__ __launch_bounds__(256, 3) void fx_wgrad_any_img_kernel(const FxWgradParams p) {
+    __shared__ __attribute__((aligned(16))) unsigned char As[2 * 3 * FX_PIECE];
+    __shared__ __attribute__((aligned(16))) unsigned char Bs[2 * 3 * FX_PIECE];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
+    int bx, by, bz;              // the XCD block order of fx_wgrad_kernel
+    {
+        const int gx = gridDim.x, gy = gridDim.y, nwg = gx * gy * gridDim.z;
+        const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+        const int q = nwg >> 3, r = nwg & 7, xcd = lin & 7, idx = lin >> 3;
+        const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        if (p.order == 0) {
+            bx = bid % gx;
+            const int rest = bid / gx;
+            by = rest % gy;
+            bz = rest / gy;
+        } else {
+            const int nt = p.R * p.S;
+            const int tp = bid % nt;
+            int rest = bid / nt;
+            by = rest % gy; rest /= gy;
+            bx = rest % gx;
+            bz = (rest / gx) * nt + tp;
+        }
+    }
+    const int m0 = by * FX_BM, n0 = bx * FX_BN;
+    const int ntaps = p.R * p.S;
+    const int split = bz / ntaps, tap = bz - split * ntaps;
+    const int tr = tap / p.S, ts = tap - tr * p.S;
+    const int dh = tr * p.dil - p.pad, dw = ts * p.dil - p.pad;             // input coordinate = output coordinate * stride + (dh, dw)
+    const int OHW = p.OH * p.OW, HWi = p.Hi * p.Wi, NP = p.N * OHW;
+    const int total = (NP + FX_BK - 1) / FX_BK;                              // the last K step may hold fewer than 16 pixels
+    const int s0 = split * p.spb, s1 = (s0 + p.spb < total) ? s0 + p.spb : total;
+    const int nk = s1 > s0 ? s1 - s0 : 0;                                    // (a slab beyond the range writes zeros)
+    // pixel ipix of the step (bits permuted as in fx_wgrad_kernel), channel group icg of the tile's eight, 16-B half ih of the group's 32-B row
+    const int ih = t & 1, ipix = ((t >> 1) & 1) | (((t >> 3) & 3) << 1) | (((t >> 2) & 1) << 3), icg = t >> 5;
+    const int KG = p.K >> 4, CG = p.C >> 4;
+    const int a_cg = (m0 >> 4) + icg, b_cg = (n0 >> 4) + icg;
+    // the thread's chunk inside an image (fx_applies(FX_WGRAD): tensors below 2^29 elements, so every byte offset stays below 2^30); a channel group beyond the tensor
+    // carries the out-of-range bit here, and an offset added to it keeps the bit
+    const int a_base = a_cg < KG ? a_cg * OHW * 32 + 16 * ih : FX_OOB, b_base = b_cg < CG ? b_cg * HWi * 32 + 16 * ih : FX_OOB;
+    i32x4 rAi[3], rBi[3];
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) {
+        rAi[pc] = fx_rsrc(p.DYimg + pc * p.dy_plane, (size_t)p.N * p.K * OHW * 2);
+        rBi[pc] = fx_rsrc(p.Ximg + pc * p.x_plane, (size_t)p.N * p.C * HWi * 2);
+    }
+    const int a_nimg = KG * OHW, b_nimg = CG * HWi;                          // 32-B rows per image
+    const int di = FX_BK / OHW, dr = (FX_BK - di * OHW) / p.OW, dc = FX_BK - di * OHW - dr * p.OW;
+    // the thread's pixel as (image, output row, output column): a pixel at or beyond N OHW is one of image N or later, and a thread that starts there stays there
+    int f_n, f_oh, f_ow;
+    {
+        const int q0 = s0 * FX_BK + ipix;
+        f_n = q0 < NP ? q0 / OHW : p.N;
+        const int rem = q0 < NP ? q0 - f_n * OHW : 0;
+        f_oh = rem / p.OW; f_ow = rem - f_oh * p.OW;
+    }
+    i32x4 rai[3], rbi[3];
+    auto fetch = [&]() {
+        const int hi = f_oh * p.stride + dh, wi = f_ow * p.stride + dw;
+        const bool ok = f_n < p.N && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi;
+        const int a_voff = ok ? (f_n * a_nimg + f_oh * p.OW + f_ow) * 32 + a_base : FX_OOB;
+        const int b_voff = ok ? (f_n * b_nimg + hi * p.Wi + wi) * 32 + b_base : FX_OOB;
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) rai[pc] = fx_buffer_load_i32x4(rAi[pc], a_voff, 0, 0);
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) rbi[pc] = fx_buffer_load_i32x4(rBi[pc], b_voff, 0, 0);
+        // the thread's pixel of the next K step
+        f_ow += dc;
+        if (f_ow >= p.OW) { f_ow -= p.OW; ++f_oh; }
+        f_oh += dr;
+        f_n += di;
+        if (f_oh >= p.OH) { f_oh -= p.OH; ++f_n; }
+    };
+    const int st_img = fx_tr_off(ipix, 2 * icg + ih);
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<i32x4*>(As + (buf * 3 + pc) * FX_PIECE + st_img) = rai[pc];
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<i32x4*>(Bs + (buf * 3 + pc) * FX_PIECE + st_img) = rbi[pc];
+    };
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    const int fr = lane & 31, fh = lane >> 5;
+    int rd_a[2][2], rd_b[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        fx_tr_frag_off(lane, wm * 64 + a * 32, rd_a[a]);
+        fx_tr_frag_off(lane, wn * 64 + a * 32, rd_b[a]);
+    }
+    const int live_a = fx_live_subtiles(m0 + wm * 64, p.K), live_b = fx_live_subtiles(n0 + wn * 64, p.C);
+    if (nk > 0) { fetch(); stage(0); if (nk > 1) fetch(); }       // the software pipeline of fx_wgrad_kernel
+    __syncthreads();
+    auto kloop = [&](auto nat, auto nbt) {
+        constexpr int NA = decltype(nat)::value, NB = decltype(nbt)::value;
+        constexpr bool LIVE = NA > 0 && NB > 0;
+        auto step = [&](int kt, auto st, auto fe) {
+            const int buf = kt & 1;
+            bf8 af[3][2], bf[3][2];
+            auto read_a = [&](int pc) {
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+                    if (a < NA) af[pc][a] = fx_tr_read(As + (buf * 3 + pc) * FX_PIECE, rd_a[a]);
+            };
+            auto read_b = [&](int pc) {
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+                    if (a < NB) bf[pc][a] = fx_tr_read(Bs + (buf * 3 + pc) * FX_PIECE, rd_b[a]);
+            };
+            if constexpr (LIVE) {
+                read_a(2); read_b(0); read_a(0); read_b(2);
+                __builtin_amdgcn_sched_barrier(0);
+                P3D_FX_PRODUCTS_RANGE(acc, af, bf, NA, NB, 0, 1)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if constexpr (decltype(st)::value) stage(buf ^ 1);
+            if constexpr (decltype(fe)::value) fetch();
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (LIVE) {
+                read_a(1); read_b(1);
+                P3D_FX_PRODUCTS_RANGE(acc, af, bf, NA, NB, 1, 6)
+            }
+            __syncthreads();
+        };
+        int kt = 0;
+        for (; kt + 2 < nk; ++kt) step(kt, std::true_type{}, std::true_type{});
+        if (kt + 1 < nk) { step(kt, std::true_type{}, std::false_type{}); ++kt; }
+        if (kt < nk) step(kt, std::false_type{}, std::false_type{});
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    if (live_a == 0 || live_b == 0) kloop(I0{}, I0{});
+    else if (live_a == 2 && live_b == 2) kloop(I2{}, I2{});
+    else if (live_a == 1 && live_b == 2) kloop(I1{}, I2{});
+    else if (live_a == 2 && live_b == 1) kloop(I2{}, I1{});
+    else kloop(I1{}, I1{});
+    // C/D layout: col = lane & 31 (input channel c, contiguous in the slab), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (output channel k)
+    float* out = p.slabs + (size_t)split * p.K * p.C * ntaps;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int c = n0 + wn * 64 + b * 32 + fr;
+            if (c >= p.C) continue;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int k = m0 + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                if (k < p.K) out[((size_t)k * ntaps + tap) * p.C + c] = acc[a][b][r];
+            }
+        }
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // Activation images: fp32 NCHW [N][C][HW] -> three bf16 planes [N][C/16][HW][16], optionally through the BatchNorm + ReLU of the forward pass (MODE 1) or
 // the BatchNorm-backward map (MODE 2) of the layer the tensor belongs to (depthnet.py:98-116: out = relu(bn(conv(x))) and its autograd).
@@ -1654,6 +1822,53 @@ int32_t fx_act_image(int mode, const float* x, const float* x2, const float* tab
     return check_launch("fx_act_image");
 }
 
+// The mode-0 image at any HW (p3d_fx_act_image_any): the bytes and the layout of fx_act_image_kernel<0>, without HW % 4 == 0.  A thread owns the four-pixel group
+// 4 g .. 4 g + 3 of ONE image (the last group of an image holds HW - 4 g < 4 pixels when HW is no multiple of 4) and eight channels.  With HW odd a channel row of x is
+// only 4-B aligned: a row's group is one 16-B load where it is whole and its address allows, dword loads otherwise, none at or beyond the image's HW pixels -- so
+// nothing is read beyond N C HW floats.  The 32-B pixel rows of the image are aligned whatever HW is: the stores keep their 16-B form, one row per pixel the group holds.
+// grid (ceil(N * ceil(HW / 4) * 2 / 256), C / 16)
+__global__ __launch_bounds__(256) void fx_act_image_any_kernel(const float* __restrict__ X, unsigned char* __restrict__ img, size_t plane_bytes, int N, int C, int HW) {
+    const int cg = blockIdx.y, t = threadIdx.x, ih = t & 1;
+    const int q4 = (HW + 3) >> 2;
+    const long long quad = ((long long)blockIdx.x * 256 + t) >> 1;
+    if (quad >= (long long)N * q4) return;
+    const int n = (int)(quad / q4), pq = (int)(quad - (long long)n * q4);
+    const int left = HW - 4 * pq;                  // pixels of this group: 4, or 1 .. 3 in the last group of an image
+    const size_t in0 = ((size_t)n * C + cg * 16 + 8 * ih) * HW + 4 * pq;
+    f32x4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float* src = X + in0 + (size_t)j * HW;
+        if (left >= 4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) v[j] = *reinterpret_cast<const f32x4*>(src);
+        else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[j][e] = e < left ? src[e] : 0.f;
+        }
+    }
+    unsigned char* dst = img + (((size_t)n * (C >> 4) + cg) * HW + 4 * pq) * 32 + 16 * ih;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (e >= left) continue;
+        unsigned hp[4], mp[4], lp[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) fx_split2(v[2 * jj][e], v[2 * jj + 1][e], hp[jj], mp[jj], lp[jj]);
+        *reinterpret_cast<i32x4*>(dst + 32 * e) = i32x4{(int)hp[0], (int)hp[1], (int)hp[2], (int)hp[3]};
+        *reinterpret_cast<i32x4*>(dst + plane_bytes + 32 * e) = i32x4{(int)mp[0], (int)mp[1], (int)mp[2], (int)mp[3]};
+        *reinterpret_cast<i32x4*>(dst + 2 * plane_bytes + 32 * e) = i32x4{(int)lp[0], (int)lp[1], (int)lp[2], (int)lp[3]};
+    }
+}
+
+int32_t fx_act_image_any(const float* x, void* img, int N, int C, int HW, hipStream_t st) {
+    if (!x || !img || N <= 0 || C <= 0 || (C & 15) || HW <= 0 || (reinterpret_cast<uintptr_t>(img) & 15) || (reinterpret_cast<uintptr_t>(x) & 3) ||
+        (int64_t)N * C * HW >= (1ll << 31)) {
+        set_error("fx_act_image_any: bad argument (N=%d C=%d HW=%d; C %% 16 == 0 and a 16-B aligned image are required)", N, C, HW); return P3D_EINVAL;
+    }
+    const size_t plane = (size_t)N * C * HW * 2;
+    const dim3 grid((unsigned)ceil_div((int64_t)N * ((HW + 3) >> 2) * 2, 256), (unsigned)(C >> 4));
+    hipLaunchKernelGGL(fx_act_image_any_kernel, grid, dim3(256), 0, st, x, (unsigned char*)img, plane, N, C, HW);
+    return check_launch("fx_act_image_any");
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -1677,6 +1892,14 @@ bool fx_any_partial_enabled() {
     return g_fx_any_partial == 1;
 }
 int fx_set_any_partial_enabled(int on) { const int before = fx_any_partial_enabled() ? 1 : 0; g_fx_any_partial = on ? 1 : 0; return before; }
+// p3d_x3_any_images_enable: callers that feed convolutions pre-split images (ops_block.ConvImagesFn) offer the ones the aligned image-fed predicate refuses to the ragged
+// image-fed instances (p3d_fx_conv_*_img_any).  The library only keeps the setting: no entry point looks at it, and neither of the other two switches does
+static int g_fx_any_images = -1;
+bool fx_any_images_enabled() {
+    if (g_fx_any_images < 0) { const char* e = getenv("P3D_X3_ANY_IMAGES"); g_fx_any_images = (e && atoi(e) == 1) ? 1 : 0; }      // default OFF
+    return g_fx_any_images == 1;
+}
+int fx_set_any_images_enabled(int on) { const int before = fx_any_images_enabled() ? 1 : 0; g_fx_any_images = on ? 1 : 0; return before; }
 
 // coverage counters (launches routed here vs to the fp32-MFMA kernel), read by bench.py so that no fallback goes uncounted
 static std::mutex g_fx_count_mu;
@@ -1770,7 +1993,8 @@ constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool 
     X(1, 0, FX_EPI_STORE, false, false) X(1, 0, FX_EPI_STATS, false, false) X(1, 0, FX_EPI_BWD_SUMS, false, false)                                           \
     X(1, 0, FX_EPI_FACTOR_STATS, false, false) X(1, 0, FX_EPI_FACTOR_BWD_SUMS, false, false) X(1, 0, FX_EPI_FACTOR_IMG, false, false) X(1, 0, FX_EPI_INFER, false, false) \
     X(1, 0, FX_EPI_STORE, true, false) X(1, 0, FX_EPI_STATS, true, false) X(1, 0, FX_EPI_BWD_SUMS, true, false) X(0, 0, FX_EPI_STORE, false, true) X(0, 0, FX_EPI_INFER, false, true) \
-    X(0, 4, FX_EPI_INFER_FACTOR, false, true) X(0, 4, FX_EPI_STORE, false, true) X(0, 4, FX_EPI_FACTOR, false, true)
+    X(0, 4, FX_EPI_INFER_FACTOR, false, true) X(0, 4, FX_EPI_STORE, false, true) X(0, 4, FX_EPI_FACTOR, false, true)                                             \
+    X(1, 0, FX_EPI_STORE, false, true) X(1, 0, FX_EPI_STORE, true, true)
 #define P3D_FX16_CONV_INSTANCES(X)                                                                                             \
     X(96, FX_EPI_STORE, false) X(96, FX_EPI_STATS, false) X(96, FX_EPI_BWD_SUMS, false) X(96, FX_EPI_INFER, false)             \
     X(64, FX_EPI_STORE, false) X(64, FX_EPI_STATS, false) X(64, FX_EPI_BWD_SUMS, false) X(64, FX_EPI_INFER, false)             \
@@ -1800,7 +2024,9 @@ constexpr bool fx_select_covered() {
     return fx_instance(0, false, 0, FX_EPI_INFER, false, true) && fx_instance(0, false, 0, FX_EPI_STORE, false, true) &&     // (the ragged forward: fp32-fed inference,
            fx_instance(0, false, 4, FX_EPI_INFER_FACTOR, false, true) && fx_instance(0, false, 4, FX_EPI_STORE, false, true) &&  //  dense and as a partial convolution;
            fx_instance(0, false, fx_select(false, false, true, false, false).pro, fx_select(false, false, true, false, false).epi, false, true) &&      //  training: the partial
-           fx_instance(0, false, fx_select(true, false, true, false, false).pro, fx_select(true, false, true, false, false).epi, false, true);          //  convolution's two passes)
+           fx_instance(0, false, fx_select(true, false, true, false, false).pro, fx_select(true, false, true, false, false).epi, false, true) &&        //  convolution's two passes;
+           fx_instance(0, true, fx_select(false, true, false, false, false).pro, fx_select(false, true, false, false, false).epi, false, true) &&       //  the image-fed dense one,
+           fx_instance(0, true, fx_select(true, true, false, false, false).pro, fx_select(true, true, false, false, false).epi, true, true);            //  either K order)
 }
 static_assert(fx_select_covered(), "fx_select returns a code without a compiled instance");
 void fx_tune(int what, int value) {
@@ -1863,7 +2089,7 @@ bool fx_masked_applies(FxPass pass, const p3d_conv_desc* d, bool ragged) {
 // FX_WGRAD: slab bytes for the larger of the two split counts (fp32- or image-fed x): what a caller reserves before it knows which
 size_t fx_workspace(FxPass pass, const p3d_conv_desc* d, bool ragged) {
     if (pass != FX_WGRAD) return fx_plan(d, pass == FX_DGRAD, ragged).workspace;
-    const int a = fx_wgrad_splits(d, false, ragged), b = ragged ? 0 : fx_wgrad_splits(d, true);
+    const int a = fx_wgrad_splits(d, false, ragged), b = fx_wgrad_splits(d, true, ragged);
     return (size_t)(a > b ? a : b) * d->K * d->C * d->R * d->S * sizeof(float);
 }
 int fx_partial_rows(FxPass pass, const p3d_conv_desc* d) { return fx_plan(d, pass == FX_DGRAD).partial_rows; }
@@ -2088,7 +2314,7 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     P3D_REQUIRE(!infer || (!fuse->partial && wimg && (!masked || (!img && !d->accumulate))),
                 "fx_conv_fwd: the inference epilogue takes a cached folded weight image, no other fusion, and a partial convolution only from an fp32 operand");
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
-    P3D_REQUIRE(!rag || !img, "fx_conv_fwd: the ragged forward takes an fp32 operand");
+    P3D_REQUIRE(!(rag && img) || (!infer && !masked), "fx_conv_fwd: the ragged forward takes an image operand only as the dense training launch");
     P3D_REQUIRE(!(rag && !infer) || !fuse->partial, "fx_conv_fwd: the ragged training forward takes no statistics");
     const FxPlan pl = fx_plan(d, false, rag);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
@@ -2132,7 +2358,8 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
         set_error("fx_conv_dgrad: the partial-convolution instances take the result factor and the operand factor exactly for an fp32 operand"); return P3D_EINVAL;
     }
     const bool rag = fuse && fuse->ragged;          // the ragged forward instances over dy (p3d_x3_any_enable; masked: p3d_x3_any_partial_enable): any map width, stride 1, fp32-fed
-    P3D_REQUIRE(!rag || (d->stride == 1 && !img && !fuse->partial && !fuse->acc_src), "fx_conv_dgrad: the ragged data gradient is the stride-1 one, dense or masked, without sums");
+    P3D_REQUIRE(!rag || (d->stride == 1 && !(img && masked) && !fuse->partial && !fuse->acc_src),
+                "fx_conv_dgrad: the ragged data gradient is the stride-1 one, dense (fp32- or image-fed) or masked (fp32-fed), without sums");
     const FxPlan pl = fx_plan(d, true, rag);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_dgrad: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     if (fuse && fuse->acc_src && !(d->accumulate && fx_dgrad_accumulates_from_source(d))) {
@@ -2232,7 +2459,7 @@ int fx_wgrad_two_taps(const p3d_conv_desc* d, bool images) {
 // whole reduction in one or two slabs on a handful of blocks, and its rounding error at several times that of the fp32-MFMA kernel, which sums many short slabs
 // (profiles/train_anysize.md).  At batch 64 the floor binds for one class only (four tiles at 33 x 33).
 int fx_wgrad_splits(const p3d_conv_desc* d, bool images, bool ragged) {
-    const int tt = fx_wgrad_two_taps(d, images);
+    const int tt = ragged ? 0 : fx_wgrad_two_taps(d, images);          // (the ragged kernels, image-fed or not, run one tap per block: one plan for both)
     const int64_t tiles = tt ? ceil_div(d->K, FX_BM) * ceil_div(d->R * d->S, tt) : ceil_div(d->K, FX_BM) * ceil_div(d->C, FX_BN) * d->R * d->S;
     const int64_t total = ragged ? ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BK) : (int64_t)d->N * (d->Ho * d->Wo / FX_BK);
     int64_t target;
@@ -2267,13 +2494,20 @@ int32_t fx_conv_wgrad_slabs(const p3d_conv_desc* d, const float* dy, const float
     p.spb = (int)ceil_div((int64_t)d->N * (d->Ho * d->Wo / FX_BK), splits);
     p.order = fx_wgrad_order(d);
     if (fuse && fuse->ragged) {          // any map width: K steps over the flat pixel index, the last one partial (fx_wgrad_any_kernel)
-        if (fuse->dy_img || fuse->x_img || (fuse->pmask != nullptr) != (fuse->emask != nullptr)) {
-            set_error("fx_conv_wgrad: the ragged weight gradient takes fp32 operands and both factors of a partial convolution or neither"); return P3D_EINVAL;
+        const bool imgs = fuse->dy_img && fuse->x_img;          // both operands as activation images (fx_wgrad_any_img_kernel), or both fp32
+        if ((fuse->dy_img != nullptr) != (fuse->x_img != nullptr) || (fuse->pmask != nullptr) != (fuse->emask != nullptr) || (imgs && fuse->pmask) ||
+            (imgs && ((d->K & 15) || (d->C & 15) || d->Ho * d->Wo < FX_BK))) {
+            set_error("fx_conv_wgrad: the ragged weight gradient takes fp32 operands (with both factors of a partial convolution or neither) or two images (channel counts in "
+                      "steps of 16, maps of at least 16 pixels, no factors)"); return P3D_EINVAL;
         }
         p.amask = fuse->pmask; p.bmask = fuse->emask;
         p.spb = (int)ceil_div(ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BK), splits);
         const dim3 grid((unsigned)ceil_div(d->C, FX_BN), (unsigned)ceil_div(d->K, FX_BM), (unsigned)(splits * d->R * d->S));
-        if (fuse->pmask) hipLaunchKernelGGL(fx_wgrad_any_masked_kernel, grid, dim3(256), 0, st, p);
+        if (imgs) {
+            p.DYimg = (const unsigned char*)fuse->dy_img; p.dy_plane = (size_t)d->N * d->K * d->Ho * d->Wo * 2;
+            p.Ximg = (const unsigned char*)fuse->x_img; p.x_plane = (size_t)d->N * d->C * d->H * d->W * 2;
+            hipLaunchKernelGGL(fx_wgrad_any_img_kernel, grid, dim3(256), 0, st, p);
+        } else if (fuse->pmask) hipLaunchKernelGGL(fx_wgrad_any_masked_kernel, grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL(fx_wgrad_any_kernel, grid, dim3(256), 0, st, p);
         prof_kernel_done(st);
         return check_launch("fx_conv_wgrad");

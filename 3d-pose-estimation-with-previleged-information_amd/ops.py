@@ -924,6 +924,25 @@ def x3_any_partial(on):
     return bool(lib().p3d_x3_any_partial_enable(int(bool(on))))
 
 
+def x3_any_images(on):
+    """Opt-in, OFF by default (P3D_X3_ANY_IMAGES=1 turns it on), independent of x3_any and x3_any_partial: multi-tap convolutions that travel as pre-split images
+    (ops_block.ConvImagesFn: nn.Conv2d called without a join, 64 input channels or more -- the regressor and the stride-1 3x3 layers of the per-layer path) do so at
+    map sizes the aligned image-fed kernels refuse too -- the 129 / 65 / 33 / 17 maps of the default 257 crop -- on the ragged image-fed instances
+    (p3d_fx_conv_*_img_any) instead of going to ops.conv2d.  Returns the previous setting."""
+    global X3_EPOCH
+    X3_EPOCH += 1                       # (ops_block.conv_takes_images caches its answer per shape and epoch)
+    return bool(lib().p3d_x3_any_images_enable(int(bool(on))))
+
+
+def x3_any_images_enabled():
+    """The setting of x3_any_images, left as it is.  (The library keeps it -- P3D_X3_ANY_IMAGES and direct calls of p3d_x3_any_images_enable count -- and its one
+    entry returns the previous setting, so it is read by setting and restoring; ops_block.conv_takes_images asks once per shape and epoch.)"""
+    L = lib()
+    on = L.p3d_x3_any_images_enable(0)
+    L.p3d_x3_any_images_enable(on)
+    return bool(on)
+
+
 X3_EPOCH = 0
 WEIGHT_EPOCH = 0          # bumped whenever parameters are written behind torch's back (FlatAdam's kernels, broadcasts into / restores of flat_p): cached per-weight derivatives (ops_block.weight_images) are stale
 
@@ -937,14 +956,20 @@ def weights_changed():
 
 def act_image(x, mode=0, x2=None, table=None, masked=False, out=None):
     """Pre-split activation image of a fp32 NCHW tensor (p3d_fx_act_image): uint8 tensor of 6 bytes per element = three bf16 planes [N][C/16][H*W][16].
-    mode 0: x; 1: relu(x * sc + sh); 2: A * (masked ? x * [x2 * sc + sh > 0] : x) + B * x2 + K, constants per channel from `table` [C][8]."""
+    mode 0: x; 1: relu(x * sc + sh); 2: A * (masked ? x * [x2 * sc + sh > 0] : x) + B * x2 + K, constants per channel from `table` [C][8].
+    H * W no multiple of 4: mode 0 only (p3d_fx_act_image_any: the same bytes at any map size)."""
     _need_gpu(x)
     x = x.contiguous()
     n, c, h, w = x.shape
+    if (h * w) % 4 != 0 and mode != 0:
+        raise P3DError('act_image: mode %d needs H * W in steps of 4 (%d x %d); only the plain image (mode 0) exists at any map size' % (mode, h, w))
     nbytes = lib().p3d_fx_act_image_bytes(n, c, h * w)
     img = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if out is None else out
     if img.numel() != nbytes or img.dtype != torch.uint8 or not img.is_contiguous():
         raise P3DError('act_image: `out` must be a contiguous uint8 tensor of %d bytes' % nbytes)
+    if (h * w) % 4 != 0:
+        check(lib().p3d_fx_act_image_any(_p(x), _p(img), n, c, h * w, _stream()), 'p3d_fx_act_image_any')
+        return img
     check(lib().p3d_fx_act_image(mode, _p(x), None if x2 is None else _p(x2.contiguous()), None if table is None else _p(table.contiguous()), int(bool(masked)),
                                  _p(img), n, c, h * w, _stream()), 'p3d_fx_act_image')
     return img

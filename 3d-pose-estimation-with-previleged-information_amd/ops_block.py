@@ -478,6 +478,16 @@ def residual_block(block, x, veil=None):
 # Multi-tap and strided convolutions gain most from operands that are split once instead of per channel tile and filter tap (profiles/r03_summary.md:
 # ResNet-50's 2048 -> 272 3x3 regressor 3.33 -> 2.78 ms per step over its three passes, image passes included); plain 1x1 layers do not repay the extra
 # pass, so they stay on ops.conv2d.
+# At maps the aligned image-fed kernels refuse (H * W or Ho * Wo no multiple of 4: the default 257 crop) the same holds under ops.x3_any_images(True), on the ragged image-fed
+# entries, for the convolutions p3d_fx_conv_img_any_supported admits in all three passes: dense, stride 1, 96 channels or more on both sides.
+def _img_entries(L, d):
+    """The image-fed entry points and the workspace query of this convolution: (forward, data gradient, weight gradient, workspace bytes, their names) -- the aligned
+    ones where p3d_fx_conv_img_supported admits all three passes, else the ragged ones.  The one place that decides it, per call."""
+    if L.p3d_fx_conv_img_supported(ctypes.byref(d)) == 7:
+        return L.p3d_fx_conv_fwd_img, L.p3d_fx_conv_dgrad_img, L.p3d_fx_conv_wgrad_img, L.p3d_fx_conv_img_workspace_bytes, 'p3d_fx_conv_%s_img'
+    return L.p3d_fx_conv_fwd_img_any, L.p3d_fx_conv_dgrad_img_any, L.p3d_fx_conv_wgrad_img_any, L.p3d_fx_conv_img_any_workspace_bytes, 'p3d_fx_conv_%s_img_any'
+
+
 def conv_takes_images(conv, x):
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and type(conv).__name__ == 'Conv2d'):
         return False
@@ -489,13 +499,17 @@ def conv_takes_images(conv, x):
     ok = cache.get(key)
     if ok is None:
         d = ops._desc(x.shape, conv.weight.shape, _one(conv.stride), _one(conv.padding), _one(conv.dilation))
-        ok = cache[key] = lib().p3d_fx_conv_img_supported(ctypes.byref(d)) == 7
+        ok = lib().p3d_fx_conv_img_supported(ctypes.byref(d)) == 7
+        if not ok and ops.x3_any_images_enabled():
+            ok = lib().p3d_fx_conv_img_any_supported(ctypes.byref(d)) == 7
+        cache[key] = ok
     return ok
 
 
 class ConvImagesFn(torch.autograd.Function):
     """conv(x, w) + bias with x, dy (and w) travelling as pre-split images: forward = image pass of x + p3d_fx_conv_fwd_img; backward = image pass of dy +
-    p3d_fx_conv_dgrad_img on the launch stream + p3d_fx_conv_wgrad_img (dy image, the x image kept from forward) on the weight-gradient stream."""
+    p3d_fx_conv_dgrad_img on the launch stream + p3d_fx_conv_wgrad_img (dy image, the x image kept from forward) on the weight-gradient stream.  A convolution the
+    aligned entries refuse for its map size runs the same three steps on their _img_any twins (_img_entries)."""
 
     @staticmethod
     def forward(ctx, x, conv, w, bias):
@@ -508,10 +522,11 @@ class ConvImagesFn(torch.autograd.Function):
         x_img = ops.act_image(x, out=bufs.tensor('x', 6 * x.numel()))
         y = torch.empty((d.N, d.K, d.Ho, d.Wo), dtype=torch.float32, device=x.device)
         wimg = weight_images(conv)[0]
-        ws = ops.workspace(x.device, L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 0))
+        ctx.entries = _img_entries(L, d)          # (decided once per call: backward runs the same set)
+        fwd, _, _, ws_bytes, name = ctx.entries
+        ws = ops.workspace(x.device, ws_bytes(ctypes.byref(d), 0))
         with ops._Timed('fwd', d):
-            check(L.p3d_fx_conv_fwd_img(ctypes.byref(d), ops._p(x_img), ops._p(w), ops._p(wimg), ops._p(bias), ops._p(y), ops._p(ws), ws.numel(), ops._stream()),
-                  'p3d_fx_conv_fwd_img')
+            check(fwd(ctypes.byref(d), ops._p(x_img), ops._p(w), ops._p(wimg), ops._p(bias), ops._p(y), ops._p(ws), ws.numel(), ops._stream()), name % 'fwd')
         ctx.conv, ctx.cfg, ctx.x_shape = conv, (stride, pad, dil), tuple(x.shape)
         ctx.save_for_backward(x_img)
         return y
@@ -525,6 +540,7 @@ class ConvImagesFn(torch.autograd.Function):
         L, st = lib(), ops._stream()
         dy = dy.contiguous()
         d = ops._desc(ctx.x_shape, w.shape, stride, pad, dil)
+        _, dgrad, wgrad, ws_bytes, name = ctx.entries
         lease, ctx.lease = ctx.lease, None
         if lease is None:
             raise P3DError('conv2d_images: backward called a second time on the same graph; run the forward again')
@@ -535,15 +551,15 @@ class ConvImagesFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=dy.device)
             wimgT = weight_images(conv)[1]
-            ws = ops.workspace(dy.device, L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 1))
+            ws = ops.workspace(dy.device, ws_bytes(ctypes.byref(d), 1))
             with ops._Timed('dgrad', d):
-                check(L.p3d_fx_conv_dgrad_img(ctypes.byref(d), ops._p(dy_img), ops._p(w), ops._p(wimgT), ops._p(dx), ops._p(ws), ws.numel(), st), 'p3d_fx_conv_dgrad_img')
+                check(dgrad(ctypes.byref(d), ops._p(dy_img), ops._p(w), ops._p(wimgT), ops._p(dx), ops._p(ws), ws.numel(), st), name % 'dgrad')
         if ctx.needs_input_grad[2]:
             grads = ops._GradOut(w)
             d.accumulate = int(grads.direct)
-            side, wst, sws = ops._side_launch(dy.device, grads.direct, L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 2), dy_ready)
+            side, wst, sws = ops._side_launch(dy.device, grads.direct, ws_bytes(ctypes.byref(d), 2), dy_ready)
             with ops._Timed('wgrad', d, side):
-                check(L.p3d_fx_conv_wgrad_img(ctypes.byref(d), ops._p(dy_img), None, ops._p(x_img), ops._p(grads.bufs[0]), ops._p(sws), sws.numel(), wst), 'p3d_fx_conv_wgrad_img')
+                check(wgrad(ctypes.byref(d), ops._p(dy_img), None, ops._p(x_img), ops._p(grads.bufs[0]), ops._p(sws), sws.numel(), wst), name % 'wgrad')
             ops._side_launched(side, owned=bufs)            # both images are the module's own buffers
             dw, = grads.done()
         if bias is not None and ctx.needs_input_grad[3]:

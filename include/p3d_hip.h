@@ -286,6 +286,28 @@ int32_t p3d_fx_conv_dgrad_img(const p3d_conv_desc* d, const void* dy_img, const 
                               void* stream);
 int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
                               void* stream);
+/* The same at any map width (the 129 / 65 / 33 / 17 maps of the reference's default 257 crop): mode-0 activation images of tensors whose H * W is no multiple of 4, and
+ * the three passes of a DENSE convolution with a whole weight tensor on them -- the ragged image-fed instances of the x3 kernels ("Image operands
+ * at any map width").
+ * p3d_fx_act_image_any: mode 0 only; the bytes, layout and size (p3d_fx_act_image_bytes) of p3d_fx_act_image at any HW; C % 16 == 0, img 16-B aligned.
+ * p3d_fx_conv_img_any_supported: bit 0 / 1 / 2 as p3d_fx_conv_img_supported -- what the ragged image-fed instances admit, whatever any switch says: each pass's rule at the
+ * per-layer thresholds (96 result channels; the weight gradient 96 on both sides), C % 16 == 0, K % 16 == 0, Ho * Wo >= 16, no channel window, the data gradient at stride 1
+ * only.  They admit aligned shapes too (and are correct there); those belong on the entries above.
+ * p3d_fx_conv_{fwd,dgrad,wgrad}_img_any: the signatures of their _img siblings.  No fp32 operand: the weight gradient needs BOTH images (x is ignored).  Each checks its
+ * bit, its workspace (p3d_fx_conv_img_any_workspace_bytes; P3D_EWORKSPACE when short) and the 16-B alignment of its base pointers, and counts as an x3 launch.
+ * p3d_x3_any_images_enable (default OFF; P3D_X3_ANY_IMAGES=1 in the environment turns it on; independent of p3d_x3_any_enable and p3d_x3_any_partial_enable): the
+ * setting callers that feed images consult (ops_block.ConvImagesFn routes a convolution the aligned query refuses to these entries while it is on).  No entry point of the
+ * library looks at it: p3d_conv2d_*, the block executor and the entries above launch what they launch without it.  Returns the previous setting. */
+int32_t p3d_x3_any_images_enable(int32_t on);
+int32_t p3d_fx_conv_img_any_supported(const p3d_conv_desc* d);
+size_t p3d_fx_conv_img_any_workspace_bytes(const p3d_conv_desc* d, int32_t pass);
+int32_t p3d_fx_act_image_any(const float* x, void* img, int32_t N, int32_t C, int32_t HW, void* stream);
+int32_t p3d_fx_conv_fwd_img_any(const p3d_conv_desc* d, const void* x_img, const float* w, const void* wimg, const float* bias, float* y, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int32_t p3d_fx_conv_dgrad_img_any(const p3d_conv_desc* d, const void* dy_img, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
+                                  void* stream);
 
 /* Inference with eval-mode BatchNorm folded into the convolutions (infer.py): s = gamma / sqrt(var + eps), w' = w * s, b' = beta - mean * s (+ s * conv bias).
  * p3d_fx_fold_bn_images: ONE launch for a table of jobs (device array of p3d_fold_job); per job kind 0 writes the forward weight image of w' over the input

@@ -11,6 +11,11 @@
               legs -- `off`, `any` (ops.x3_any) and `both` (ops.x3_any and ops.x3_any_partial) -- and `both` wins when it beats `any` by more than their combined
               spread; --classes times the masked convolutions of layer1 / layer2 (both factors, no bias) on the fp32-MFMA masked kernels, on the masked ragged
               x3 instances, and the dense convolution of the same shape on the dense ragged instances.
+  --images    (depthnet; profiles/train_anysize_images.md) the image-fed ragged path, ops.x3_any_images.  With --classes: every stride-1 3x3 class with 96 channels or more
+              on both sides, leg `any` (p3d_conv2d_* under ops.x3_any: the fp32-fed ragged instances) against leg `img` (p3d_fx_conv_*_img_any on activation images and
+              cached weight images, as ops_block.ConvImagesFn calls them), each pass alone, the image passes of x and dy on lines of their own and inside a per-layer
+              total.  With --step: legs `any` (ops.x3_any alone) and `images` (ops.x3_any and ops.x3_any_images) alternating; `images` wins when it beats `any` by more
+              than their combined spread.  (The `any` leg of a build without ops.x3_any_images: --step without --images, whose `on` leg it is.)
 GPU box only."""
 import argparse
 import ctypes
@@ -54,7 +59,11 @@ def switch(on, partial=False):
 
 
 def switch_leg(leg):
-    switch(leg in ('on', 'any', 'both'), leg == 'both')
+    switch(leg in ('on', 'any', 'both', 'images'), leg == 'both')
+    if hasattr(ops, 'x3_any_images'):
+        ops.x3_any_images(leg == 'images')
+    elif leg == 'images':
+        raise SystemExit('this build has no ops.x3_any_images')
 
 
 def timed(fn, iters):
@@ -182,6 +191,67 @@ def classes_partial(a):
     print('all three passes: masked off %.2f ms  masked on %.2f ms  dense %.2f ms' % tuple(sum(total[(p, leg)] for p in PASSES) for leg in legs))
 
 
+def classes_images(a):
+    """the classes ops_block.ConvImagesFn takes at the odd maps under ops.x3_any_images: leg `any` (fp32-fed ragged, per-layer entries) against leg `img`"""
+    L = pkg._lib.lib()
+    legs = ('any', 'img')
+    rows = ('fwd', 'dgrad', 'wgrad', 'img x', 'img dy')
+    total = {(r, leg): 0.0 for r in rows for leg in legs}
+    P, stream = ops._p, ops._stream()
+    for (c, h, k, ks, st, dil, cnt) in sorted(R50, key=lambda r: -r[0] * r[2] * r[3] ** 2 * ((r[1] // r[4] + 1) ** 2) * r[6]):
+        tag = 'c%d h%d k%d %dx%d s%d d%d x%d' % (c, h, k, ks, ks, st, dil, cnt)
+        if ks < 2 or st != 1 or min(c, k) < 96 or (a.only and a.only not in tag):
+            continue
+        torch.manual_seed(c + k)
+        pad = dil * (ks - 1) // 2
+        conv = pkg.nn.Conv2d(c, k, ks, stride=st, padding=pad, dilation=dil, bias=False).cuda()
+        w = conv.weight.detach()
+        x = torch.randn(a.batch, c, h, h, device='cuda')
+        d = ops._desc(x.shape, w.shape, st, pad, dil)
+        b = ctypes.byref(d)
+        assert L.p3d_fx_conv_img_supported(b) == 0 and L.p3d_fx_conv_img_any_supported(b) == 7, tag
+        dy = torch.randn(a.batch, k, d.Ho, d.Wo, device='cuda')
+        y, dx, dw = torch.empty_like(dy), torch.empty_like(x), torch.empty_like(w)
+        switch(True)
+        ws = torch.empty(max([L.p3d_conv2d_fwd_workspace_bytes(b), L.p3d_conv2d_dgrad_workspace_bytes(b), L.p3d_conv2d_wgrad_workspace_bytes(b), 16] +
+                             [L.p3d_fx_conv_img_any_workspace_bytes(b, i) for i in range(3)]), dtype=torch.uint8, device='cuda')
+        wf, wb = pkg.ops_block.weight_images(conv)
+        x_img, dy_img = ops.act_image(x), ops.act_image(dy)
+        calls = {('fwd', 'any'): lambda: L.p3d_conv2d_fwd(b, P(x), P(w), None, None, None, P(y), P(ws), ws.numel(), stream),
+                 ('dgrad', 'any'): lambda: L.p3d_conv2d_dgrad(b, P(dy), P(w), None, None, P(dx), P(ws), ws.numel(), stream),
+                 ('wgrad', 'any'): lambda: L.p3d_conv2d_wgrad(b, P(dy), P(x), None, None, P(dw), P(ws), ws.numel(), stream),
+                 ('fwd', 'img'): lambda: L.p3d_fx_conv_fwd_img_any(b, P(x_img), P(w), P(wf), None, P(y), P(ws), ws.numel(), stream),
+                 ('dgrad', 'img'): lambda: L.p3d_fx_conv_dgrad_img_any(b, P(dy_img), P(w), P(wb), P(dx), P(ws), ws.numel(), stream),
+                 ('wgrad', 'img'): lambda: L.p3d_fx_conv_wgrad_img_any(b, P(dy_img), None, P(x_img), P(dw), P(ws), ws.numel(), stream),
+                 ('img x', 'img'): lambda: L.p3d_fx_act_image_any(P(x), P(x_img), a.batch, c, h * h, stream),
+                 ('img dy', 'img'): lambda: L.p3d_fx_act_image_any(P(dy), P(dy_img), a.batch, k, d.Ho * d.Wo, stream)}
+        gf = 2.0 * a.batch * k * c * ks * ks * d.Ho * d.Wo / 1e9
+        layer = {leg: 0.0 for leg in legs}
+        for row in rows:
+            ms = {leg: [] for leg in legs if (row, leg) in calls}
+            for leg in ms:
+                ops.conv_path_stats(reset=True)
+                for _ in range(3):
+                    assert calls[(row, leg)]() == 0, L.p3d_last_error()
+                if row in PASSES:
+                    assert family(ops.conv_path_stats(reset=True), row) == 'x3', (tag, row, leg)
+            for _ in range(a.rounds):
+                for leg in ms:
+                    ms[leg].append(timed(calls[(row, leg)], a.iters))
+            m = {leg: med(v) for leg, v in ms.items()}
+            text = ' | '.join('%s %.3f [%.3f..%.3f] ms' % ((leg,) + m[leg]) for leg in m)
+            ratio = ' | img/any %.2f' % (m['img'][0] / m['any'][0]) if 'any' in m else ''
+            print('%-28s %-6s %7.2f GF | %s%s' % (tag, row, gf if row in PASSES else 0.0, text, ratio), flush=True)
+            for leg in m:
+                layer[leg] += m[leg][0]
+                total[(row, leg)] += m[leg][0] * cnt
+        print('%-28s layer  any %.3f ms  img %.3f ms (image passes included)  img/any %.2f' % (tag, layer['any'], layer['img'], layer['img'] / layer['any']), flush=True)
+        switch(False)
+    for row in rows:
+        print('sum over the classes x their layer counts, %-6s: any %.2f ms  img %.2f ms' % (row, total[(row, 'any')], total[(row, 'img')]))
+    print('all passes: any %.2f ms  img %.2f ms' % (sum(total[(r, 'any')] for r in rows), sum(total[(r, 'img')] for r in rows)))
+
+
 def step(a):
     flags = ['-model', a.model, '-suffix', 'bench', '-data_name', 'h36m', '-save_path', '/tmp/p3d_bench', '-criterion', 'SmoothL1', '-num_joints', '17', '-side_in', str(a.side),
              '-stride', '16', '-depth', '16', '-depth_range', '1000', '-loss_div', '10', '-learn_rate', '5e-5', '-weight_decay', '4e-5', '-grad_norm', '5'] + FAMILY_FLAGS[a.family]
@@ -199,6 +269,8 @@ def step(a):
     legs = ('off', 'on') if hasattr(ops, 'x3_any') and not a.off_only else ('off',)
     if a.family != 'depthnet' and len(legs) == 2:
         legs = ('off', 'any', 'both') if hasattr(ops, 'x3_any_partial') else ('off', 'any')
+    if a.images:
+        legs = ('any', 'images')
 
     def run(n):
         for i in range(n):
@@ -234,6 +306,11 @@ def step(a):
         out['gain_ms'] = round(out['any']['median_ms'] - out['both']['median_ms'], 3)
         out['combined_spread_ms'] = round(spread, 3)
         out['both_wins'] = bool(out['gain_ms'] > spread)
+    elif legs == ('any', 'images'):
+        spread = (out['any']['max_ms'] - out['any']['min_ms']) + (out['images']['max_ms'] - out['images']['min_ms'])
+        out['gain_ms'] = round(out['any']['median_ms'] - out['images']['median_ms'], 3)
+        out['combined_spread_ms'] = round(spread, 3)
+        out['images_wins'] = bool(out['gain_ms'] > spread)
     elif legs == ('off', 'on'):
         spread = (out['off']['max_ms'] - out['off']['min_ms']) + (out['on']['max_ms'] - out['on']['min_ms'])
         out['gain_ms'] = round(out['off']['median_ms'] - out['on']['median_ms'], 3)
@@ -254,10 +331,13 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--only', default='')
+    ap.add_argument('--images', action='store_true', help='the image-fed ragged path (ops.x3_any_images): see above')
     ap.add_argument('--family', default='depthnet', choices=sorted(FAMILY_FLAGS))
     a = ap.parse_args()
+    if a.images and a.family != 'depthnet':
+        raise SystemExit('--images measures the dense family')
     if a.classes:
-        (classes if a.family == 'depthnet' else classes_partial)(a)
+        (classes_images if a.images else classes if a.family == 'depthnet' else classes_partial)(a)
     if a.step:
         step(a)
 
