@@ -109,6 +109,9 @@ SIGNATURES = {
     'p3d_bn_train_bwd': (_i32, [_ptr] * 11 + [_i32, _i32, _i32, _i32, _i32, _ptr, _sz, _ptr]),
     'p3d_bn_eval_fwd': (_i32, [_ptr] * 7 + [_i32, _i32, _i32, _f32, _i32, _ptr]),
     'p3d_bn_eval_bwd': (_i32, [_ptr] * 10 + [_i32, _i32, _i32, _f32, _i32, _i32, _ptr, _sz, _ptr]),
+    'p3d_frozen_grad_mask_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'p3d_frozen_grad_mask': (_i32, [_ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr, _sz, _ptr]),
+    'p3d_frozen_wgrad_finish': (_i32, [_ptr] * 5 + [_f32, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr]),
     'p3d_relu_fwd': (_i32, [_ptr, _ptr, _i64, _ptr]),
     'p3d_relu_bwd': (_i32, [_ptr, _ptr, _ptr, _i64, _ptr]),
     'p3d_maxpool3x3s2_fwd': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr]),

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 import os
 
-from . import ops, ops_block, ops_half
+from . import ops, ops_block, ops_frozen, ops_half
 from .nn import BatchNorm2d, Conv2d, MaxPool2d, Sequential
 from .partial_conv import PartialConv
 
@@ -58,11 +58,13 @@ class _ResidualBlock(nn.Module):
         self.skip_relu = skip_relu
         self.partial = partial
 
-    def _shortcut(self, x, join):
+    def _shortcut(self, x, join, fold=False):
         """Returns (res, res_join): with a downsample branch its conv hands its input gradient to `join`; an identity shortcut lets
-        the closing BN hand over the residual gradient instead."""
+        the closing BN hand over the residual gradient instead.  fold (the dense blocks): a downsample pair ops_frozen.admits is one folded node."""
         if self.downsample is None:
             return x, join
+        if fold and ops_frozen.admits(x, self.downsample[0], self.downsample[1]):
+            return ops_frozen.conv_bn(x, self.downsample[0], self.downsample[1], join_put=join), None
         return self.downsample[1](self.downsample[0](x, join_put=join)), None
 
     def forward(self, x):
@@ -79,12 +81,20 @@ class _ResidualBlock(nn.Module):
         out = x
         last = len(self._chain) - 1
         for i, (cname, bname) in enumerate(self._chain):
-            out = getattr(self, cname)(out, join_take=join) if i == 0 else getattr(self, cname)(out)
+            conv, bn = getattr(self, cname), getattr(self, bname)
+            if ops.FROZEN_FOLD and ops_frozen.admits(out, conv, bn):      # a frozen BatchNorm folded into its conv: one node, no BatchNorm pass (ops_frozen.py)
+                if i < last:
+                    out = ops_frozen.conv_bn(out, conv, bn, relu=True, join_take=join if i == 0 else None)
+                else:
+                    res, res_join = self._shortcut(x, join, fold=True)
+                    out = ops_frozen.conv_bn(out, conv, bn, res=res, relu=not self.skip_relu, join_take=join if i == 0 else None, res_join=res_join)
+                continue
+            out = conv(out, join_take=join) if i == 0 else conv(out)
             if i < last:
-                out = getattr(self, bname)(out, relu=True)
+                out = bn(out, relu=True)
             else:
-                res, res_join = self._shortcut(x, join)
-                out = getattr(self, bname)(out, res=res, relu=not self.skip_relu, res_join=res_join)
+                res, res_join = self._shortcut(x, join, fold=True)
+                out = bn(out, res=res, relu=not self.skip_relu, res_join=res_join)
         return out
 
     def _forward_inference(self, x):
@@ -157,12 +167,19 @@ def _tick_batchnorm(module, inputs):
             m._ticked = True
 
 
+def _frozen_fold(module, inputs):
+    """Forward pre-hook of the whole network: under ops.frozen_fold the plan of its frozen conv + BatchNorm pairs is made, and folded again when stale, once here."""
+    if ops.FROZEN_FOLD:
+        ops_frozen.prepare(module)
+
+
 class TrunkBase(nn.Module):
     """Holds `inplanes` bookkeeping and the stage factory shared by every family."""
 
     def __init__(self):
         super().__init__()
         self.register_forward_pre_hook(_tick_batchnorm)
+        self.register_forward_pre_hook(_frozen_fold)
 
     # -half_acc (depth_train.py:73-83): the Trainer sets `_p3d_half`; the network then runs on NHWC fp16 activations between
     # these two conversions, parameters stay fp32 masters with fp16 weight images beside them (ops_half.refresh_weights).

@@ -25,6 +25,7 @@ class GraphedStep:
         if trainer.world != 1 or trainer.reducer.active:
             raise RuntimeError('GraphedStep: whole-step capture is single-process only')
         self.trainer = trainer
+        self._refuse_frozen_fold()
         self.warmup = warmup
         self.graph = None
         self.static = None
@@ -32,8 +33,17 @@ class GraphedStep:
         self._lr = None
         self._shapes = None
 
+    def _refuse_frozen_fold(self):
+        """Under ops.frozen_fold a frozen BatchNorm trains on a fold that is made again from the host whenever the weights have changed (ops_frozen.FrozenFold):
+        a replayed graph would keep training on the fold of the capture.  Refuse rather than capture it."""
+        from . import ops_frozen
+        if ops.FROZEN_FOLD and ops_frozen.has_frozen(self.trainer.model):
+            raise ops.P3DError('GraphedStep: ops.frozen_fold is on and the model has a frozen (eval-mode) BatchNorm; the fold is refreshed from the host and '
+                               'cannot be captured.  Turn the switch off (ops.frozen_fold(False)) for whole-step capture')
+
     def _capture(self, batch):
         tr = self.trainer
+        self._refuse_frozen_fold()
         self.static = tuple(None if t is None else t.clone() for t in batch)
         run = self._run
         if self.graph is not None:

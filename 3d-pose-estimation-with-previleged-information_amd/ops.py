@@ -252,13 +252,17 @@ class GradJoin:
     normally, and a producer that runs AFTER the consumer (or whose consumer needs no input gradient) sees `taken` and returns its
     gradient to autograd like any other Function, so the shortcut gradient is never dropped.  A gradient that was stashed but never
     picked up (the consumer's backward did not run at all) is an error: the first stash of a pass queues an engine callback that
-    raises P3DError when the pass ends (`check_joins`), whoever called .backward()."""
-    __slots__ = ('buf', 'taken', '__weakref__')
+    raises P3DError when the pass ends (`check_joins`), whoever called .backward().
+    `after`: an event the producer may leave beside `buf` when a kernel on the second stream still reads the stashed buffer (ops_frozen.FrozenConvBnFn, whose
+    stashed gradient is also its weight gradient's operand); the consumer orders its stream behind it before it writes (`_take`).  Only the fp32 consumers
+    (Conv2dFn, FrozenConvBnFn) go through `_take`; the fp16 path (ops_half) reads `buf` itself, and no producer there or for it ever leaves an event."""
+    __slots__ = ('buf', 'taken', 'after', '__weakref__')
     _live = None
 
     def __init__(self):
         self.buf = None
         self.taken = False
+        self.after = None             # an event the consumer's stream waits for before it writes `buf` (a reader of the stashed buffer on the second stream)
         if GradJoin._live is None:
             import weakref
             GradJoin._live = weakref.WeakSet()
@@ -279,21 +283,36 @@ def check_joins():
     n = pending_joins()
     if n:
         for j in GradJoin._live:
-            j.buf = None
+            j.buf = j.after = None
         raise P3DError('%d shortcut gradient(s) were produced but never joined (ops.GradJoin): the backward pass did not reach the first '
                        'convolution of a residual block' % n)
 
 
-def _stash(join, grad):
-    """Producer side of a GradJoin: True if `grad` was handed to the join (return None to autograd), False if the consumer has already run."""
+def _stash(join, grad, after=None):
+    """Producer side of a GradJoin: True if `grad` was handed to the join (return None to autograd), False if the consumer has already run.
+    after: an event behind the producer's own readers of `grad` on the second stream (ops_frozen: the stashed gradient is also its weight gradient's operand);
+    the consumer accumulates into the buffer only behind it (_take)."""
     global _join_check_queued
     if join is None or join.taken:
         return False
     join.buf = grad
+    join.after = after
     if not _join_check_queued:
         _join_check_queued = True
         torch.autograd.Variable._execution_engine.queue_callback(check_joins)
     return True
+
+
+def _take(join, x):
+    """Consumer side of a GradJoin whose slot is filled: the stashed gradient, checked against the block input x it is a gradient of, with the slot emptied and
+    the launch stream ordered behind the producer's `after` event when it left one."""
+    joined = join.buf
+    if joined.shape != x.shape or joined.dtype != x.dtype:
+        raise P3DError('GradJoin: the shortcut gradient %s does not match the block input %s' % (tuple(joined.shape), tuple(x.shape)))
+    if join.after is not None:
+        torch.cuda.current_stream(x.device).wait_event(join.after)
+    join.buf = join.after = None
+    return joined
 
 
 class Conv2dFn(torch.autograd.Function):
@@ -335,11 +354,8 @@ class Conv2dFn(torch.autograd.Function):
         if join_take is not None:
             join_take.taken = True                            # producers that run later return their gradient to autograd themselves
         if ctx.needs_input_grad[0]:
-            joined = join_take.buf if join_take is not None else None
-            if joined is not None:
-                if joined.shape != x.shape or joined.dtype != x.dtype:
-                    raise P3DError('GradJoin: the shortcut gradient %s does not match the block input %s' % (tuple(joined.shape), tuple(x.shape)))
-                dx, join_take.buf = joined, None              # accumulate onto the shortcut's gradient: no separate add pass
+            if join_take is not None and join_take.buf is not None:
+                dx = _take(join_take, x)                      # accumulate onto the shortcut's gradient: no separate add pass
                 d.accumulate = 1
             else:
                 dx = torch.empty_like(x)
@@ -941,6 +957,18 @@ def x3_any_images_enabled():
     on = L.p3d_x3_any_images_enable(0)
     L.p3d_x3_any_images_enable(on)
     return bool(on)
+
+
+FROZEN_FOLD = os.environ.get('P3D_FROZEN_FOLD', '0') == '1'
+
+
+def frozen_fold(on):
+    """Opt-in, OFF by default (P3D_FROZEN_FOLD=1 turns it on): a dense conv + BatchNorm pair of a residual block whose BatchNorm is frozen (eval mode, the
+    reference's -do_freeze) trains on the folded convolution -- one x3 inference forward with b', the residual and the ReLU in its epilogue, no BatchNorm pass
+    in either direction and no conv output kept (ops_frozen.py).  Returns the previous setting."""
+    global FROZEN_FOLD
+    previous, FROZEN_FOLD = FROZEN_FOLD, bool(on)
+    return previous
 
 
 X3_EPOCH = 0

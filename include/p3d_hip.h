@@ -446,6 +446,22 @@ int32_t p3d_bn_eval_bwd(const float* dy, const float* x, const float* y, const f
                         float* dgamma, float* dbeta, int32_t N, int32_t C, int32_t HW, float eps, int32_t relu, int32_t accumulate,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Training through a frozen BatchNorm folded into its convolution (ops_frozen.py; csrc/p3d_frozen.hip): with s = gamma / sqrtf(var + eps), w' = w * s,
+ * b' = beta - mean * s the layer is y = relu?(conv(x, w') + b' (+ res)), and its backward is g = dy * [y > 0] (g = dy without a ReLU), dres = g,
+ * dx = dgrad(g, w'), raw = wgrad(x, g), dw = s * raw, dbeta[k] = sum g[k], dgamma[k] = (<w[k], raw[k]> - mean[k] * dbeta[k]) / sqrtf(var[k] + eps).
+ * p3d_frozen_grad_mask: dy, y, g are [N][K][HW] fp32.  With y: g = dy where y > 0, else +0.  y == NULL (then g == NULL too): nothing is written, dy is g.
+ * Either way sums[k] = sum over n and p of g[n][k][p] (overwritten).  16-B accesses where a channel row's address allows them (all three base pointers on 16-B
+ * lines), dwords elsewhere; no element beyond N * K * HW is touched.  The sums are accumulated in fp64 in a fixed order -- per-block partials in the workspace,
+ * then one ordered sum per channel -- without atomics: bitwise reproducible.  Workspace: p3d_frozen_grad_mask_workspace_bytes, on an 8-B line.
+ * p3d_frozen_wgrad_finish: raw, w, dw are [K][CRS]; dw = s * raw with s the very expression of the fold (p3d_fx_fold_bn_images), dgamma and dbeta as above from
+ * sums = p3d_frozen_grad_mask's; the inner product is accumulated in fp64 in a fixed order, one block per output channel.  accumulate != 0: all three are added
+ * onto what is there.  dw must not be raw. */
+size_t p3d_frozen_grad_mask_workspace_bytes(int32_t N, int32_t K, int32_t HW);
+int32_t p3d_frozen_grad_mask(const float* dy, const float* y, float* g, float* sums, int32_t N, int32_t K, int32_t HW, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int32_t p3d_frozen_wgrad_finish(const float* raw, const float* w, const float* gamma, const float* mean, const float* var, float eps, const float* sums,
+                                float* dw, float* dgamma, float* dbeta, int32_t K, int32_t CRS, int32_t accumulate, void* stream);
+
 /* standalone F.relu (skip_relu variants, depthnet.py:197-198) */
 int32_t p3d_relu_fwd(const float* x, float* y, int64_t n, void* stream);
 int32_t p3d_relu_bwd(const float* dy, const float* y, float* dx, int64_t n, void* stream);
