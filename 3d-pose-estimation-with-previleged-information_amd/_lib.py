@@ -80,6 +80,13 @@ SIGNATURES = {
     'p3d_fx_conv_fwd_img': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_fx_conv_dgrad_img': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_fx_conv_wgrad_img': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    'p3d_fx_row_image_bytes': (_sz, [_i32, _i32, _i32]),
+    'p3d_fx_row_image': (_i32, [_i32, _ptr, _ptr, _ptr, _i32, _ptr, _i32, _i32, _i32, _ptr]),
+    'p3d_fx_conv_fwd_rows': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    'p3d_fx_conv_dgrad_rows': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    'p3d_fx_conv_wgrad_rows': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    'p3d_block_image_bytes': (_sz, [_ptr, _i32, _i32, _i32]),
+    'p3d_fx_open_images': (_i32, [_i32, _ptr, _ptr, _ptr, _i32, ctypes.c_double] + [_ptr] * 12 + [_i32, _i32, _i32, _ptr]),
     'p3d_x3_any_images_enable': (_i32, [_i32]),
     'p3d_fx_conv_img_any_supported': (_i32, [_ptr]),
     'p3d_fx_conv_img_any_workspace_bytes': (_sz, [_ptr, _i32]),

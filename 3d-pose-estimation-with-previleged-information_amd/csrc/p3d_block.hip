@@ -5,9 +5,11 @@
 // input) done here: one call instead of ~12 per direction.
 //
 // Tensors produced inside the block and consumed only by convolutions -- a_i = relu(bn_i(c_i)) and d c_i = the BatchNorm-backward map of the incoming
-// gradient -- exist only as pre-split activation images (fx_act_image: three bf16 planes, hi + mid + lo == the fp32 value): the pass that applies the
-// BatchNorm map writes them once (6 B per element instead of 4), and the two or three kernels that read them stage them into LDS with 16-B copies
-// instead of splitting every value again per channel tile and filter tap.  The block input x and the gradients that leave a data gradient stay fp32.
+// gradient -- exist only as activation images (fx_act_image), channel-blocked rows [N][C/16][HW][16] in which every filter tap and stride of the two or three
+// kernels that read them lands on an aligned row.  Dense blocks: fp32 row images, 4 B per element, written once by the pass that applies the BatchNorm map and
+// cut into the three bf16 pieces by the row-fed kernel instances on the way into LDS.  Masked blocks (and every block under p3d_fx_tune(6, 1)): three
+// pre-split bf16 planes, hi + mid + lo == the fp32 value, 6 B per element, staged with plain 16-B copies.  block_row_images() decides.  The block input x and
+// the gradients that leave a data gradient stay fp32.
 //
 // HBM passes that are BatchNorm's own, per block: forward, per inner layer the image pass (reads c_i, writes the image of a_i) and one pass that closes
 // the block (out = act(bn(c_last) + shortcut)); backward, one pass that opens it (g = dout * [out > 0] plus the channel sums of the closing BN and of
@@ -384,6 +386,10 @@ static int32_t check_block(const p3d_block_desc* b) {
     return P3D_OK;
 }
 
+// The form of a block's activation images a_i and gradient images d c_i: fp32 row images (4 B per element; the row-fed kernel instances cut the pieces themselves) for
+// dense blocks, three bf16 planes (6 B) for masked blocks -- the partial-convolution instances are plane-fed -- and for every block under p3d_fx_tune(6, 1)
+static bool block_row_images(const p3d_block_desc* b) { return !b->masked && fx_block_row_images(); }
+
 // The executor's two workspaces.  main (the launch stream's) = [conv scratch: weight images, split-K slabs | partial sums | the downsample conv's partial sums]: the
 // closing conv's and the downsample conv's sums live side by side until the closing pass has read both; side (the weight-gradient stream's) = slabs.
 struct BlockLayout { size_t conv_ws, part_bytes, main_bytes, side_bytes; };
@@ -453,6 +459,11 @@ int32_t p3d_block_supported(const p3d_block_desc* b) {
     return fx_enabled() && b && (b->nconv == 2 || b->nconv == 3) && block_refusal(b, &slot) == 0 ? 1 : 0;
 }
 
+size_t p3d_block_image_bytes(const p3d_block_desc* b, int32_t N, int32_t C, int32_t HW) {
+    if (!b || N <= 0 || C <= 0 || HW <= 0) return 0;
+    return block_row_images(b) ? fx_row_image_bytes(N, C, HW) : fx_act_image_bytes(N, C, HW);
+}
+
 int32_t p3d_block_workspace_bytes(const p3d_block_desc* b, size_t* main_bytes, size_t* side_bytes) {
     if (int32_t e = check_block(b)) return e;
     const BlockLayout lay = block_layout(b);
@@ -470,6 +481,7 @@ int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
     float* partial = (float*)((char*)workspace + lay.conv_ws);
     float* partial2 = (float*)((char*)partial + lay.part_bytes);      // the downsample conv's partial sums
     const int last = b->nconv - 1;
+    const bool rows = block_row_images(b);
     for (int i = 0; i < 4; ++i) {
         const bool ds = i == 3;
         if (!block_slot(b, i)) continue;
@@ -479,6 +491,7 @@ int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
         if (!from_x) P3D_REQUIRE(io->aimg[i - 1], "block_fwd: null activation image %d", i - 1);
         FxFuse f{};
         f.act_img = from_x ? nullptr : io->aimg[i - 1];
+        f.rows = !from_x && rows;
         f.partial = ds ? partial2 : partial;
         f.wimg = io->wimg[i];
         const bool mk = b->masked && !ds;
@@ -498,7 +511,7 @@ int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
         const double cnt = (double)d->N * d->Ho * d->Wo;
         const CloseFin cf = finalize_fwd(block_bn(b, io, i), partial, fx_partial_rows(FX_FWD, d), d->K, cnt, st);
         const FxFinalize fin = act_finalize(cf, cnt);
-        if (int32_t e = fx_act_image(1, io->c[i], nullptr, io->table[i], 0, io->aimg[i], d->N, d->K, d->Ho * d->Wo, st, cf.rows ? &fin : nullptr, mk ? io->pix_in[i + 1] : nullptr)) return e;
+        if (int32_t e = fx_act_image(1, io->c[i], nullptr, io->table[i], 0, io->aimg[i], d->N, d->K, d->Ho * d->Wo, st, cf.rows ? &fin : nullptr, mk ? io->pix_in[i + 1] : nullptr, rows)) return e;
     }
     const p3d_conv_desc* dl = &b->conv[last];
     const int HW = dl->Ho * dl->Wo;
@@ -521,6 +534,7 @@ struct BwdCtx {
     float* side_ws;                 // the weight-gradient stream's slabs
     hipStream_t st, ss;
     bool two;                       // ss is a stream of its own
+    bool rows;                      // aimg / dcimg are fp32 row images (block_row_images)
     int acc, last;
     // g = dout * [out > 0] never exists as a tensor when forward left mask bytes: the two opening image passes mask dout themselves, and with an identity
     // shortcut the first convolution's data gradient adds the masked dout in its epilogue (dx = dgrad + dout * mask) instead of accumulating into a copy of g
@@ -541,7 +555,7 @@ static int32_t bwd_map(const BwdCtx& x, const float* gin, int slot, int masked, 
     P3D_REQUIRE(io->dcimg[slot], "block_bwd: null gradient image %d", slot);
     FxFinalize fin = finalize_bwd(block_bn(x.b, io, slot), kind, x.partial, rows, which, dc->K, cnt, x.acc, x.st);
     fin.gmask = front_mask;
-    return fx_act_image(2, gin, io->c[slot], io->table[slot], masked, io->dcimg[slot], dc->N, dc->K, dc->Ho * dc->Wo, x.st, fin.kind ? &fin : nullptr, bwd_pixmul(x, slot));
+    return fx_act_image(2, gin, io->c[slot], io->table[slot], masked, io->dcimg[slot], dc->N, dc->K, dc->Ho * dc->Wo, x.st, fin.kind ? &fin : nullptr, bwd_pixmul(x, slot), x.rows);
 }
 
 // `ready`: the launch stream's position when the gradient image of this convolution was complete (the data gradient of the same layer has been queued on
@@ -552,7 +566,7 @@ static int32_t launch_wgrad(const BwdCtx& x, int slot, const float* xin, const v
     ProfScope ps(2, d, x.ss);
     fx_count(2, d);
     FxFuse fw{};
-    fw.dy_img = x.io->dcimg[slot]; fw.x_img = ximg;
+    fw.dy_img = x.io->dcimg[slot]; fw.x_img = ximg; fw.rows = x.rows;
     if (x.b->masked && slot != 3 && !ximg) fw.emask = x.io->pix_in[slot];      // the block input is fp32: x * mask_in in the kernel's split (an image carries it)
     const int splits = fx_wgrad_splits(d, ximg != nullptr);
     if (int32_t e = fx_conv_wgrad_slabs(d, nullptr, xin, x.side_ws, splits, &fw, x.ss)) return e;
@@ -593,7 +607,7 @@ static int32_t bwd_open_images(const BwdCtx& x) {
         P3D_REQUIRE(io->dcimg[last] && io->dcimg[3], "block_bwd: null gradient image");
         const FxFinalize fa = finalize_bwd(block_bn(b, io, last), 3, x.partial, split, 0, dl->K, cnt, x.acc, x.st);
         const FxFinalize fb = finalize_bwd(block_bn(b, io, 3), 3, x.partial, split, 1, dl->K, cnt, x.acc, x.st);
-        return fx_act_image_pair(x.g, x.gmask, io->c[last], io->c[3], io->dcimg[last], io->dcimg[3], &fa, &fb, dl->N, dl->K, dl->Ho * dl->Wo, x.st, bwd_pixmul(x, last));
+        return fx_act_image_pair(x.g, x.gmask, io->c[last], io->c[3], io->dcimg[last], io->dcimg[3], &fa, &fb, dl->N, dl->K, dl->Ho * dl->Wo, x.st, bwd_pixmul(x, last), x.rows);
     }
     if (int32_t e = bwd_map(x, x.g, last, 0, 3, split, 0, cnt, x.gmask)) return e;
     return b->has_downsample ? bwd_map(x, x.g, 3, 0, 3, split, 1, cnt, x.gmask) : P3D_OK;
@@ -609,7 +623,7 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
         if (i > 0) P3D_REQUIRE(io->aimg[i - 1], "block_bwd: null activation image %d", i - 1);
         FxFuse f{};
         f.wimg = io->wimgT[i];
-        f.act_img = io->dcimg[i];
+        f.act_img = io->dcimg[i]; f.rows = x.rows;
         p3d_conv_desc dd = *d;
         if (i > 0) {
             const p3d_conv_desc* dp = &b->conv[i - 1];                       // producer of this conv's input
@@ -657,7 +671,7 @@ static int32_t bwd_downsample(const BwdCtx& x, hipEvent_t ready) {
     if (x.b->need_dx) {
         FxFuse f{};
         f.wimg = x.io->wimgT[3];
-        f.act_img = x.io->dcimg[3];
+        f.act_img = x.io->dcimg[3]; f.rows = x.rows;
         p3d_conv_desc dd = x.b->conv[3];
         dd.accumulate = 1;
         if (int32_t e = bwd_dgrad(x, 3, &dd, x.io->dx, &f)) return e;
@@ -685,7 +699,7 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
     x.ws = workspace; x.conv_ws = lay.conv_ws; x.partial = (char*)workspace + lay.conv_ws; x.side_ws = (float*)side_workspace;
     x.st = (hipStream_t)stream; x.ss = side_stream ? (hipStream_t)side_stream : x.st;
     x.two = x.ss != x.st;
-    x.acc = b->accumulate_grads; x.last = b->nconv - 1;
+    x.acc = b->accumulate_grads; x.last = b->nconv - 1; x.rows = block_row_images(b);
     x.g = (b->relu_out && x.g_in_memory) ? io->gbuf : io->dout;
     x.gmask = x.g_in_memory ? nullptr : io->out_mask;
 
@@ -881,6 +895,34 @@ int32_t p3d_fx_act_image(int32_t mode, const float* x, const float* x2, const fl
     return fx_act_image(mode, x, x2, table, masked, img, N, C, HW, (hipStream_t)stream);
 }
 
+// Row images: the same tensor, same channel-blocked rows, holding the fp32 value itself ([N][C/16][HW][16] floats); modes as p3d_fx_act_image
+size_t p3d_fx_row_image_bytes(int32_t N, int32_t C, int32_t HW) { return (N > 0 && C > 0 && HW > 0) ? fx_row_image_bytes(N, C, HW) : 0; }
+
+int32_t p3d_fx_row_image(int32_t mode, const float* x, const float* x2, const float* table, int32_t masked, void* img, int32_t N, int32_t C, int32_t HW, void* stream) {
+    return fx_act_image(mode, x, x2, table, masked, img, N, C, HW, (hipStream_t)stream, nullptr, nullptr, true);
+}
+
+// The image passes that open a block's backward pass, alone (tests): d c = A g + B c + K with g = x masked by `gmask` (bit e of byte i: element 4 i + e passes; may be
+// null) and the constants finalized in the pass's prologue from fp64 partial sums [C][nrows][3] = (sum g, sum g (c_a - mean_a), sum g (c_b - mean_b)) -- FxFinalize kind 3.
+// c_b null: the mode-2 pass for side a.  c_b given: both images in ONE pass (fx_act_image_pair).  table_*: the layers' [C][8] tables (mean, invstd read); d gamma / d beta
+// are written.  rows: 0 three-plane images, 1 fp32 row images.
+int32_t p3d_fx_open_images(int32_t rows, const float* x, const unsigned char* gmask, const double* partial, int32_t nrows, double count, const float* c_a, const float* table_a,
+                           const float* gamma_a, float* dgamma_a, float* dbeta_a, void* img_a, const float* c_b, const float* table_b, const float* gamma_b, float* dgamma_b,
+                           float* dbeta_b, void* img_b, int32_t N, int32_t C, int32_t HW, void* stream) {
+    P3D_REQUIRE(x && partial && nrows > 0 && count > 0 && c_a && table_a && gamma_a && dgamma_a && dbeta_a && img_a, "fx_open_images: null argument");
+    P3D_REQUIRE(!c_b || (table_b && gamma_b && dgamma_b && dbeta_b && img_b), "fx_open_images: null argument of the second image");
+    auto fin = [&](int which, const float* gamma, float* dgamma, float* dbeta, const float* table) {
+        FxFinalize f{};
+        f.kind = 3; f.partial = partial; f.rows = nrows; f.which = which; f.count = count; f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.table = const_cast<float*>(table);
+        f.gmask = gmask;
+        return f;
+    };
+    const FxFinalize fa = fin(0, gamma_a, dgamma_a, dbeta_a, table_a);
+    if (!c_b) return fx_act_image(2, x, c_a, table_a, 0, img_a, N, C, HW, (hipStream_t)stream, &fa, nullptr, rows != 0);
+    const FxFinalize fb = fin(1, gamma_b, dgamma_b, dbeta_b, table_b);
+    return fx_act_image_pair(x, gmask, c_a, c_b, img_a, img_b, &fa, &fb, N, C, HW, (hipStream_t)stream, nullptr, rows != 0);
+}
+
 // The three passes of a convolution with image operands (what p3d_block_* launches inside a block), for callers that hold images of their own.
 // x_img / dy_img: p3d_fx_act_image of the fp32 tensor p3d_conv2d_* would take; wimg: the matching p3d_fx_weight_images image, or NULL (built into the workspace).
 size_t p3d_fx_conv_img_workspace_bytes(const p3d_conv_desc* d, int32_t pass) {
@@ -894,43 +936,67 @@ int32_t p3d_fx_conv_img_supported(const p3d_conv_desc* d) {
     return (fx_applies(FX_FWD, d, 32) ? 1 : 0) | (fx_applies(FX_DGRAD, d, 32) ? 2 : 0) | (fx_applies(FX_WGRAD, d, 32) ? 4 : 0);
 }
 
-int32_t p3d_fx_conv_fwd_img(const p3d_conv_desc* d, const void* x_img, const float* w, const void* wimg, const float* bias, float* y, void* workspace,
+static int32_t conv_fwd_img(const char* name, bool rows, const p3d_conv_desc* d, const void* x_img, const float* w, const void* wimg, const float* bias, float* y, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    P3D_REQUIRE(d && x_img && w && y, "fx_conv_fwd_img: null argument");
-    P3D_REQUIRE(fx_applies(FX_FWD, d, 32) && d->C % 16 == 0 && (d->H * d->W) % 4 == 0, "fx_conv_fwd_img: shape outside the x3 kernels");
+    P3D_REQUIRE(d && x_img && w && y, "%s: null argument", name);
+    P3D_REQUIRE(fx_applies(FX_FWD, d, 32) && d->C % 16 == 0 && (d->H * d->W) % 4 == 0, "%s: shape outside the x3 kernels", name);
     FxFuse f{};
-    f.act_img = x_img; f.wimg = wimg;
+    f.act_img = x_img; f.wimg = wimg; f.rows = rows;
     ProfScope ps(0, d, (hipStream_t)stream);
     fx_count(0, d);
-    return name_entry("fx_conv_fwd_img", fx_conv_fwd(d, nullptr, w, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
+    return name_entry(name, fx_conv_fwd(d, nullptr, w, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream));
+}
+int32_t p3d_fx_conv_fwd_img(const p3d_conv_desc* d, const void* x_img, const float* w, const void* wimg, const float* bias, float* y, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    return conv_fwd_img("fx_conv_fwd_img", false, d, x_img, w, wimg, bias, y, workspace, workspace_bytes, stream);
+}
+int32_t p3d_fx_conv_fwd_rows(const p3d_conv_desc* d, const void* x_rows, const float* w, const void* wimg, const float* bias, float* y, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    return conv_fwd_img("fx_conv_fwd_rows", true, d, x_rows, w, wimg, bias, y, workspace, workspace_bytes, stream);
 }
 
-int32_t p3d_fx_conv_dgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
-                              void* stream) {
-    P3D_REQUIRE(d && dy_img && w && dx, "fx_conv_dgrad_img: null argument");
-    P3D_REQUIRE(fx_applies(FX_DGRAD, d, 32) && d->K % 16 == 0 && (d->Ho * d->Wo) % 4 == 0, "fx_conv_dgrad_img: shape outside the x3 kernels");
+static int32_t conv_dgrad_img(const char* name, bool rows, const p3d_conv_desc* d, const void* dy_img, const float* w, const void* wimgT, float* dx, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    P3D_REQUIRE(d && dy_img && w && dx, "%s: null argument", name);
+    P3D_REQUIRE(fx_applies(FX_DGRAD, d, 32) && d->K % 16 == 0 && (d->Ho * d->Wo) % 4 == 0, "%s: shape outside the x3 kernels", name);
     FxFuse f{};
-    f.act_img = dy_img; f.wimg = wimgT;
+    f.act_img = dy_img; f.wimg = wimgT; f.rows = rows;
     ProfScope ps(1, d, (hipStream_t)stream);
     fx_count(1, d);
     if (int32_t e = fx_dgrad_zero_dead_classes(d, dx, (hipStream_t)stream)) return e;
-    return name_entry("fx_conv_dgrad_img", fx_conv_dgrad(d, nullptr, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream));
+    return name_entry(name, fx_conv_dgrad(d, nullptr, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream));
+}
+int32_t p3d_fx_conv_dgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    return conv_dgrad_img("fx_conv_dgrad_img", false, d, dy_img, w, wimgT, dx, workspace, workspace_bytes, stream);
+}
+int32_t p3d_fx_conv_dgrad_rows(const p3d_conv_desc* d, const void* dy_rows, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    return conv_dgrad_img("fx_conv_dgrad_rows", true, d, dy_rows, w, wimgT, dx, workspace, workspace_bytes, stream);
 }
 
 // x: the fp32 input, used when x_img is NULL (the block input of a residual block); otherwise ignored
-int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
-                              void* stream) {
-    P3D_REQUIRE(d && dy_img && (x || x_img) && dw, "fx_conv_wgrad_img: null argument");
-    P3D_REQUIRE(fx_applies(FX_WGRAD, d, 32) && d->K % 16 == 0 && (!x_img || d->C % 16 == 0), "fx_conv_wgrad_img: shape outside the x3 kernels");
+static int32_t conv_wgrad_img(const char* name, bool rows, const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    P3D_REQUIRE(d && dy_img && (x || x_img) && dw, "%s: null argument", name);
+    P3D_REQUIRE(fx_applies(FX_WGRAD, d, 32) && d->K % 16 == 0 && (!x_img || d->C % 16 == 0), "%s: shape outside the x3 kernels", name);
     const int splits = fx_wgrad_splits(d, x_img != nullptr);
     const size_t need = (size_t)splits * d->K * d->C * d->R * d->S * sizeof(float);
-    if (!workspace || workspace_bytes < need) { set_error("fx_conv_wgrad_img: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
+    if (!workspace || workspace_bytes < need) { set_error("%s: workspace %zu B < required %zu B", name, workspace_bytes, need); return P3D_EWORKSPACE; }
     FxFuse f{};
-    f.dy_img = dy_img; f.x_img = x_img;
+    f.dy_img = dy_img; f.x_img = x_img; f.rows = rows;
     ProfScope ps(2, d, (hipStream_t)stream);
     fx_count(2, d);
     if (int32_t e = fx_conv_wgrad_slabs(d, nullptr, x, (float*)workspace, splits, &f, (hipStream_t)stream)) return e;
     return wgrad_finish(d, (float*)workspace, splits, d->R * d->S > 1, dw, (hipStream_t)stream);
+}
+int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    return conv_wgrad_img("fx_conv_wgrad_img", false, d, dy_img, x, x_img, dw, workspace, workspace_bytes, stream);
+}
+int32_t p3d_fx_conv_wgrad_rows(const p3d_conv_desc* d, const void* dy_rows, const float* x, const void* x_rows, float* dw, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    return conv_wgrad_img("fx_conv_wgrad_rows", true, d, dy_rows, x, x_rows, dw, workspace, workspace_bytes, stream);
 }
 
 // The same three passes at any map width (include/p3d_hip.h): the ragged image-fed instances of fx_conv_kernel and fx_wgrad_any_img_kernel.  Dense convolutions with

@@ -78,6 +78,8 @@ struct FxFuse {
     int infer;              // 0 / 1
     const float* res;
     int relu;
+    int rows;               // 1: act_img / dy_img / x_img are fp32 ROW images (fx_row_image: [N][C/16][HW][16] floats, 4 B per element) that the kernel cuts into the three
+                            // pieces itself -- dense aligned training launches only (no factor, not ragged, not inference): what the block executor keeps a_i and d c_i as
     int ragged;             // 1: the ragged instances (any map width), for inference and training alike; fp32 operands, or (dense training launches only, nothing else set:
                             // p3d_fx_conv_*_img_any) act_img for FWD / DGRAD (stride 1) and dy_img AND x_img for WGRAD (fx_wgrad_any_img_kernel).  With `infer`: dense, or a partial convolution
                             // with pmask and emask.  Without: FWD / DGRAD (stride 1) with the plain epilogue, WGRAD on fx_wgrad_any_kernel -- dense fp32-fed training
@@ -182,12 +184,16 @@ struct FxFinalize {
 };
 constexpr int FX_FIN_MAX_ROWS = 512;
 size_t fx_act_image_bytes(int64_t N, int64_t C, int64_t HW);
+// Row images: the same channel-blocked rows holding the fp32 value itself, [N][C/16][HW][16] floats; `rows` below writes one instead of the three planes (same modes,
+// finalize prologue, mask bytes and pixmul).  fx_block_row_images: the format the block executor keeps a_i / d c_i of DENSE blocks in (p3d_fx_tune(6, 1): planes)
+size_t fx_row_image_bytes(int64_t N, int64_t C, int64_t HW);
+bool fx_block_row_images();
 bool fx_pair_map_enabled();
 // pixmul (optional, [N][HW]): the image holds the tensor times this per-pixel factor (partial convolutions inside the block executor)
 int32_t fx_act_image_pair(const float* x, const unsigned char* gmask, const float* c_a, const float* c_b, void* img_a, void* img_b, const FxFinalize* fa, const FxFinalize* fb,
-                          int N, int C, int HW, hipStream_t st, const float* pixmul_a = nullptr);
+                          int N, int C, int HW, hipStream_t st, const float* pixmul_a = nullptr, bool rows = false);
 int32_t fx_act_image(int mode, const float* x, const float* x2, const float* table, int masked, void* img, int N, int C, int HW, hipStream_t st,
-                     const FxFinalize* fin = nullptr, const float* pixmul = nullptr);
+                     const FxFinalize* fin = nullptr, const float* pixmul = nullptr, bool rows = false);
 // mode 0 at any HW (the same bytes; x read with dword loads where a row is not 16-B aligned, the last pixel group of an image partial)
 int32_t fx_act_image_any(const float* x, void* img, int N, int C, int HW, hipStream_t st);
 

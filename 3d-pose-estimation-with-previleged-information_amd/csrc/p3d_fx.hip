@@ -12,6 +12,8 @@
 // executor where it applies BatchNorm + ReLU or the BatchNorm-backward map anyway), into an "activation image": three bf16 planes laid out
 // [n][channel / 16][h][w][16 channels], so that any (pixel, 16-channel K step) is one 32-B row per plane whatever the filter tap, stride or dilation.
 // A kernel fed by images does no arithmetic on its operands: 16-B copies into LDS, fragment reads, MFMAs.
+// Row images (ROWS instances, the dense residual blocks): the same rows holding the fp32 value itself, [n][channel / 16][h][w][16] floats -- 4 B per element written and
+// read instead of 6.  The layout is what makes the fetch cheap; the split is done by the consumer between its fetch registers and LDS (fx_split_row8), under MFMAs.
 //
 // GEMM view (the pixel index is the contiguous one of the fp32 tensors):
 //   FWD    y [n][m][oh][ow]  = sum_tap sum_c  W[m][c][tap] * x [n][c][oh*s - pad + r*dil][ow*s - pad + q*dil]
@@ -64,6 +66,19 @@ __device__ __forceinline__ void fx_split_store(unsigned char* base, const f32x4 
     *reinterpret_cast<u32x2*>(base) = u32x2{hp[0], hp[1]};
     *reinterpret_cast<u32x2*>(base + FX_PIECE) = u32x2{mp[0], mp[1]};
     *reinterpret_cast<u32x2*>(base + 2 * FX_PIECE) = u32x2{lp[0], lp[1]};
+}
+// Row images (ROWS instances): half a 64-B row of an fp32 row image -- eight consecutive channels of one pixel, fetched as two 16-B groups -- cut into the three
+// 16-B chunks the same position of a three-plane activation image holds: the channel pairs and the function are those of fx_act_image_kernel, so the chunks are
+// bit for bit what that pass would have stored
+__device__ __forceinline__ void fx_split_row8(const f32x4 a, const f32x4 b, i32x4 (&out)[3]) {
+    unsigned hp[4], mp[4], lp[4];
+    fx_split2(a[0], a[1], hp[0], mp[0], lp[0]);
+    fx_split2(a[2], a[3], hp[1], mp[1], lp[1]);
+    fx_split2(b[0], b[1], hp[2], mp[2], lp[2]);
+    fx_split2(b[2], b[3], hp[3], mp[3], lp[3]);
+    out[0] = i32x4{(int)hp[0], (int)hp[1], (int)hp[2], (int)hp[3]};
+    out[1] = i32x4{(int)mp[0], (int)mp[1], (int)mp[2], (int)mp[3]};
+    out[2] = i32x4{(int)lp[0], (int)lp[1], (int)lp[2], (int)lp[3]};
 }
 
 // LDS images of one piece of one operand tile:
@@ -155,9 +170,12 @@ __device__ __forceinline__ FxConvParams fx_class_params(const FxConvParams& in) 
 // the result held.
 // Image-fed (AMODE 1, p3d_x3_any_images_enable), epilogue 0 only, either K order: the operand side is the AMODE 1 fetch as it is -- one pixel's 32-B row per thread, its
 // position from the flat column, so nothing there knows of four-pixel groups -- and the result side the staged store above.
-template <int AMODE, int PRO, int EPIX, bool TAPI = false, bool RAG = false>
+// ROWS (image-fed, the dense block executor's launches): the activation operand is an fp32 row image [N][Cred/16][Hi][Wi][16] (fx_row_image); a thread fetches its half of a
+// pixel's 64-B row (two 16-B loads instead of three plane loads) and cuts it into the three pieces on the way from registers to LDS: same stores, same LDS image.
+template <int AMODE, int PRO, int EPIX, bool TAPI = false, bool RAG = false, bool ROWS = false>
 __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in) {
     static_assert(!TAPI || AMODE == 1, "the tap-inner K order is an image-fed instance");
+    static_assert(!ROWS || (AMODE == 1 && !RAG), "row images feed the aligned image-fed instances");
     static_assert(!RAG || (AMODE == 1 && PRO == 0 && EPIX == FX_EPI_STORE) ||
                       (AMODE == 0 && ((PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER)) || (PRO == 4 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER_FACTOR || EPIX == FX_EPI_FACTOR)))),
                   "the ragged instances are the fp32-fed forward with the plain / inference epilogue, dense or as a partial convolution, and the image-fed forward with the plain one");
@@ -217,6 +235,8 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
     i32x4 rX, rXi[3];
     if constexpr (AMODE == 0) {
         rX = fx_rsrc(p.X + (size_t)nfirst * p.Cred * HWi, (size_t)(p.N - nfirst) * p.Cred * HWi * sizeof(float));
+    } else if constexpr (ROWS) {
+        rXi[0] = fx_rsrc(p.Ximg + (size_t)nfirst * p.Cred * HWi * 4, (size_t)(p.N - nfirst) * p.Cred * HWi * 4);
     } else {
         const size_t left = (size_t)(p.N - nfirst) * p.Cred * HWi * 2;
 #pragma unroll
@@ -254,7 +274,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
         const int hi = hbase + ir * p.hstep, wshift = is * p.wstep, wi0 = wbase + wshift;
         const bool row_ok = col_ok && (unsigned)hi < (unsigned)p.Hi;
         if constexpr (AMODE != 0) {
-            x_voff[0] = (row_ok && (unsigned)wi0 < (unsigned)p.Wi) ? (img_off + hi * p.Wi + wi0) * 32 + 16 * ph : FX_OOB;
+            x_voff[0] = (row_ok && (unsigned)wi0 < (unsigned)p.Wi) ? (img_off + hi * p.Wi + wi0) * (ROWS ? 64 : 32) + (ROWS ? 32 : 16) * ph : FX_OOB;
         } else if constexpr (RAG) {
             const int dh = p.hoff + ir * p.hstep, dw = p.woff + wshift;         // wave-uniform: the tap's displacement
             int oh = rg_oh, ow = rg_ow, im = rg_img;
@@ -286,7 +306,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
         }
     };
 
-    f32x4 rx[2];
+    f32x4 rx[2];                                   // (ROWS: the thread's 32 B of the pixel's row)
     i32x4 rwi[3], rxi[3];                          // this thread's three 16-B chunks of the K step's weight image / activation image
     f32x4 smask = {1.f, 1.f, 1.f, 1.f};            // PRO 4: per-pixel factor of the fetched K step
     auto fetch = [&]() {
@@ -296,7 +316,11 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
 #pragma unroll
             for (int j = 0; j < 3; ++j) rwi[j] = fx_buffer_load_i32x4(rW, w_voff[j], so, 0);
         }
-        if constexpr (AMODE != 0) {
+        if constexpr (ROWS) {
+            const int so = (f_k >> 4) * HWi * 64;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) rx[i] = fx_buffer_load_f32x4(rXi[0], x_voff[0], so + 16 * i, 0);
+        } else if constexpr (AMODE != 0) {
             const int so = (f_k >> 4) * HWi * 32;                  // wave-uniform: the K step's channel group
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) rxi[pc] = fx_buffer_load_i32x4(rXi[pc], x_voff[0], so, 0);
@@ -327,6 +351,7 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
 #pragma unroll
         for (int j = 0; j < 3; ++j) *reinterpret_cast<i32x4*>(cb + 16 * (t + 256 * j)) = rwi[j];
         if constexpr (AMODE != 0) {
+            if constexpr (ROWS) fx_split_row8(rx[0], rx[1], rxi);
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<i32x4*>(pb + pc * FX_PIECE + st_p1) = rxi[pc];
         } else {
@@ -629,7 +654,8 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
 // by fetching, for LDS position 16 t, the chunk that belongs there.
 // In the accumulator a lane is output channel (lane & 15) of a 16-channel group and holds four consecutive pixels 4 (lane >> 4) .. + 3 of a 16-pixel group.
 // ------------------------------------------------------------------------------------------------------------------------------------------
-template <int BM, int EPI, bool TAPI = false>
+// ROWS: the activation operand is an fp32 row image, cut into pieces between the fetch registers and LDS (see fx_conv_kernel)
+template <int BM, int EPI, bool TAPI = false, bool ROWS = false>
 __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_in) {
     const FxConvParams p = fx_class_params(p_in);
     constexpr int SUMS = fx_epi_sums(EPI);
@@ -690,7 +716,9 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
         img_off = (pn - nfirst) * csteps * HWi;
     }
     i32x4 rXi[3];
-    {
+    if constexpr (ROWS) {
+        rXi[0] = fx_rsrc(p.Ximg + (size_t)nfirst * p.Cred * HWi * 4, (size_t)(p.N - nfirst) * p.Cred * HWi * 4);
+    } else {
         const size_t left = (size_t)(p.N - nfirst) * p.Cred * HWi * 2;
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) rXi[pc] = fx_rsrc(p.Ximg + pc * p.plane_bytes + (size_t)nfirst * p.Cred * HWi * 2, left);
@@ -703,9 +731,10 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
         w_tapoff = wtap * tiles128 * csteps * (3 * FX_PIECE);
         const int hi = hbase + ir * p.hstep, wi0 = wbase + is * p.wstep;
         const bool ok = col_ok && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi0 < (unsigned)p.Wi;
-        x_voff = ok ? (img_off + hi * p.Wi + wi0) * 32 + 16 * ph : FX_OOB;
+        x_voff = ok ? (img_off + hi * p.Wi + wi0) * (ROWS ? 64 : 32) + (ROWS ? 32 : 16) * ph : FX_OOB;
     };
     i32x4 rwi[3], rxi[3];
+    f32x4 rxr[2];                   // ROWS: the thread's 32 B of the pixel's row
     auto fetch = [&]() {
         if (f_tap != cur_tap) { asm volatile("" ::: "memory"); set_tap(f_tap); }
         {
@@ -713,7 +742,11 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
 #pragma unroll
             for (int j = 0; j < WCHUNKS; ++j) rwi[j] = fx_buffer_load_i32x4(rW, w_voff[j], so, 0);
         }
-        {
+        if constexpr (ROWS) {
+            const int so = (f_k >> 4) * HWi * 64;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) rxr[i] = fx_buffer_load_f32x4(rXi[0], x_voff, so + 16 * i, 0);
+        } else {
             const int so = (f_k >> 4) * HWi * 32;
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) rxi[pc] = fx_buffer_load_i32x4(rXi[pc], x_voff, so, 0);
@@ -729,6 +762,7 @@ __global__ __launch_bounds__(256, 3) void fx16_conv_kernel(const FxConvParams p_
 #pragma unroll
         for (int j = 0; j < WCHUNKS; ++j)
             if (j + 1 < WCHUNKS || w_last) *reinterpret_cast<i32x4*>(pb + w_lds[j]) = rwi[j];
+        if constexpr (ROWS) fx_split_row8(rxr[0], rxr[1], rxi);
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<i32x4*>(pb + pc * PIECE_P + 16 * t) = rxi[pc];
     };
@@ -1058,8 +1092,11 @@ __global__ __launch_bounds__(256) void fx_reduce_any_kernel(const float* __restr
 // weight block per tap no longer leaves three of the four waves without work (both column waves live).  grid (ceil(taps / 2), K tiles, splits); slabs as ever.
 // TAPS 3 (the same with at most 64 OUTPUT channels too -- every 3x3 of ResNet-50's layer1 and ResNet-18's): dy fills half of the A image, the other half carries a third tap of
 // x, and three of the four waves multiply dy by one tap each (one block = one filter row of a 3x3).  grid (ceil(taps / 3), 1, splits).
-template <bool AIMG, bool BIMG, bool MASKED, int TAPS = 0>
+// ROWS: every image operand is an fp32 row image [N][C/16][HW][16]; the thread's chunk (one pixel, eight channels) is 32 B of the pixel's 64-B row, fetched as two 16-B
+// groups and cut into the three pieces between the fetch registers and the "tr" image (fx_split_row8): the same stores to the same addresses.
+template <bool AIMG, bool BIMG, bool MASKED, int TAPS = 0, bool ROWS = false>
 __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p) {
+    static_assert(!ROWS || (AIMG && !MASKED && TAPS != 1), "row images feed the dense image-fed instances (not the stem's)");
     static_assert(TAPS < 2 || (AIMG && BIMG && !MASKED), "the multi-tap column tiles are image-fed instances");
     static_assert(!MASKED || !AIMG || !BIMG, "the partial-convolution factors are applied by the in-kernel split of an fp32 operand (an image carries its factor already)");
     static_assert(!TAPS || BIMG, "tap-major columns come from an image operand");
@@ -1123,11 +1160,14 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
     // Buffer-load fetch (see fx_conv_kernel): per-thread byte offsets with the out-of-range bit for rows beyond the tensor / padding pixels, the image and
     // pixel position of the K step in a wave-uniform scalar offset.  (fx_applies(FX_WGRAD) bounds every tensor below 2^29 elements.)
     i32x4 rA, rB, rAi[3], rBi[3];
-    if constexpr (AIMG) {
+    constexpr int RB = ROWS ? 64 : 32, RH = ROWS ? 32 : 16;          // bytes of a pixel's row of 16 channels in an image (plane), and of a thread's half of it
+    if constexpr (AIMG && ROWS) rAi[0] = fx_rsrc(p.DYimg, (size_t)p.N * p.K * OHW * 4);
+    else if constexpr (AIMG) {
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) rAi[pc] = fx_rsrc(p.DYimg + pc * p.dy_plane, (size_t)p.N * p.K * OHW * 2);
     } else rA = fx_rsrc(p.DY, (size_t)p.N * p.K * OHW * sizeof(float));
-    if constexpr (BIMG) {
+    if constexpr (BIMG && ROWS) rBi[0] = fx_rsrc(p.Ximg, (size_t)p.N * p.C * HWi * 4);
+    else if constexpr (BIMG) {
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) rBi[pc] = fx_rsrc(p.Ximg + pc * p.x_plane, (size_t)p.N * (TAPS == 1 ? 16 : p.C) * HWi * 2);
     } else rB = fx_rsrc(p.X, (size_t)p.N * p.C * HWi * sizeof(float));
@@ -1136,11 +1176,11 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
     int a_voff[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) a_voff[i] = a_ok[i] ? ((m0 + row + 64 * i) * OHW + 4 * kq) * 4 : FX_OOB;
-    const int ai_voff = ai_ok ? (a_cg * OHW + ipix) * 32 + 16 * ih : FX_OOB;
+    const int ai_voff = ai_ok ? (a_cg * OHW + ipix) * RB + RH * ih : FX_OOB;
     const bool simple = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0;      // 1x1: the input pixel IS the output pixel
     const bool vec = p.stride == 1 && (dw & 3) == 0;        // uniform: the four input pixels are one aligned 16-B group, in or out together
     const int b_row = (n0 + row) * HWi;
-    f32x4 ra[2], rb[2];
+    f32x4 ra[2], rb[2];          // (ROWS: an image operand's 32 B of the pixel's row)
     i32x4 rai[3], rbi[3];
     f32x4 ram, rbm;              // MASKED: the per-pixel factors of the fetched K step (one value per pixel, whatever the row)
     int b_voff[4] = {FX_OOB, FX_OOB, FX_OOB, FX_OOB};
@@ -1155,14 +1195,24 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
                 int hi, wi;
                 if (rowwise) { hi = f_oh * p.stride + a3_dh; wi = (f_ow + ipix) * p.stride + a3_dw; }
                 else { const int q = f_p + ipix, oh = q / p.OW, ow = q - oh * p.OW; hi = oh * p.stride + a3_dh; wi = ow * p.stride + a3_dw; }
-                const int voff = (a3_ok && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi) ? ((icg & 3) * HWi + hi * p.Wi + wi) * 32 + 16 * ih : FX_OOB;
-                const int x_so = f_img * CG * HWi * 32;
+                const int voff = (a3_ok && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi) ? ((icg & 3) * HWi + hi * p.Wi + wi) * RB + RH * ih : FX_OOB;
+                const int x_so = f_img * CG * HWi * RB;
+                if constexpr (ROWS) {
 #pragma unroll
-                for (int pc = 0; pc < 3; ++pc) rai[pc] = fx_buffer_load_i32x4(rBi[pc], voff, x_so, 0);
+                    for (int i = 0; i < 2; ++i) ra[i] = fx_buffer_load_f32x4(rBi[0], voff, x_so + 16 * i, 0);
+                } else {
+#pragma unroll
+                    for (int pc = 0; pc < 3; ++pc) rai[pc] = fx_buffer_load_i32x4(rBi[pc], voff, x_so, 0);
+                }
             } else {
-                const int a_so = (f_img * KG * OHW + f_p) * 32;
+                const int a_so = (f_img * KG * OHW + f_p) * RB;
+                if constexpr (ROWS) {
 #pragma unroll
-                for (int pc = 0; pc < 3; ++pc) rai[pc] = fx_buffer_load_i32x4(rAi[pc], ai_voff, a_so, 0);
+                    for (int i = 0; i < 2; ++i) ra[i] = fx_buffer_load_f32x4(rAi[0], ai_voff, a_so + 16 * i, 0);
+                } else {
+#pragma unroll
+                    for (int pc = 0; pc < 3; ++pc) rai[pc] = fx_buffer_load_i32x4(rAi[pc], ai_voff, a_so, 0);
+                }
             }
         } else {
             const int a_so = (f_img * p.K * OHW + f_p) * 4;
@@ -1172,17 +1222,22 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
         }
         // operand B (x at this block's filter tap)
         if constexpr (BIMG) {
-            int b_so = f_img * CG * HWi * 32, voff;
-            if (!TAPS && simple) { b_so += f_p * 32; voff = bi_ok ? (b_cg * HWi + ipix) * 32 + 16 * ih : FX_OOB; }
+            int b_so = f_img * CG * HWi * RB, voff;
+            if (!TAPS && simple) { b_so += f_p * RB; voff = bi_ok ? (b_cg * HWi + ipix) * RB + RH * ih : FX_OOB; }
             else {
                 int hi, wi;
                 const int tdh = TAPS ? t_dh : dh, tdw = TAPS ? t_dw : dw;
                 if (rowwise) { hi = f_oh * p.stride + tdh; wi = (f_ow + ipix) * p.stride + tdw; }        // the step's 16 pixels lie in output row f_oh (a scalar)
                 else { const int q = f_p + ipix, oh = q / p.OW, ow = q - oh * p.OW; hi = oh * p.stride + tdh; wi = ow * p.stride + tdw; }
-                voff = (bi_ok && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi) ? (b_cg * HWi + hi * p.Wi + wi) * 32 + 16 * ih : FX_OOB;
+                voff = (bi_ok && (unsigned)hi < (unsigned)p.Hi && (unsigned)wi < (unsigned)p.Wi) ? (b_cg * HWi + hi * p.Wi + wi) * RB + RH * ih : FX_OOB;
             }
+            if constexpr (ROWS) {
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) rbi[pc] = fx_buffer_load_i32x4(rBi[pc], voff, b_so, 0);
+                for (int i = 0; i < 2; ++i) rb[i] = fx_buffer_load_f32x4(rBi[0], voff, b_so + 16 * i, 0);
+            } else {
+#pragma unroll
+                for (int pc = 0; pc < 3; ++pc) rbi[pc] = fx_buffer_load_i32x4(rBi[pc], voff, b_so, 0);
+            }
         } else {
             int b_so = f_img * p.C * HWi * 4;
             if (simple) {
@@ -1230,6 +1285,7 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
         unsigned char* ab = As + buf * 3 * FX_PIECE;
         unsigned char* bb = Bs + buf * 3 * FX_PIECE;
         if constexpr (AIMG) {
+            if constexpr (ROWS) fx_split_row8(ra[0], ra[1], rai);
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<i32x4*>(ab + pc * FX_PIECE + st_img) = rai[pc];
         } else {
@@ -1244,6 +1300,7 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_kernel(const FxWgradParams p)
             }
         }
         if constexpr (BIMG) {
+            if constexpr (ROWS) fx_split_row8(rb[0], rb[1], rbi);
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<i32x4*>(bb + pc * FX_PIECE + st_img) = rbi[pc];
         } else {
@@ -1547,10 +1604,18 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_any_img_kernel(const FxWgradP
 // contiguous) and writes twelve 16-B chunks; the partner lane (ih) owns the other eight channels of the same pixels, so a lane pair writes 32-B rows.
 // grid (ceil(N * HW / 4 * 2 / 256), C / 16)
 // ------------------------------------------------------------------------------------------------------------------------------------------
-template <int MODE>
+// ROWS: the same values stored unsplit, as an fp32 row image [N][C/16][HW][16] -- a thread writes its eight channels of a pixel as two 16-B
+// groups, a lane pair a whole 64-B row; the row-fed instances of the convolution kernels cut them into the three pieces themselves (fx_split_row8).
+// (MODEX = MODE, or FX_IMG_ROWS + MODE for a row image: one int, so the plane instances keep the names fx_act_image_kernel<0 / 1 / 2> the profiles quote; the row
+// instances are <4 / 5 / 6> and ignore plane_bytes)
+constexpr int FX_IMG_ROWS = 4;
+template <int MODEX>
 __global__ __launch_bounds__(256) void fx_act_image_kernel(const float* __restrict__ X, const float* __restrict__ X2, const float* __restrict__ tab,
                                                            unsigned char* __restrict__ img, size_t plane_bytes, int N, int C, int HW, int masked, const FxFinalize fin,
                                                            const float* __restrict__ pixmul) {
+    constexpr int MODE = MODEX % FX_IMG_ROWS;
+    constexpr bool ROWS = MODEX >= FX_IMG_ROWS;
+    static_assert(MODE <= 2 && MODEX < 2 * FX_IMG_ROWS, "modes 0, 1, 2 in either format");
     __shared__ float cst[16][FX_TAB];
     __shared__ double fred[2][16][16];
     const int cg = blockIdx.y, t = threadIdx.x;
@@ -1673,15 +1738,24 @@ __global__ __launch_bounds__(256) void fx_act_image_kernel(const float* __restri
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[j][e] *= f[e];
     }
-    unsigned char* dst = img + (((size_t)n * (C >> 4) + cg) * HW + 4 * pq) * 32 + 16 * ih;
+    if constexpr (ROWS) {
+        unsigned char* dst = img + (((size_t)n * (C >> 4) + cg) * HW + 4 * pq) * 64 + 32 * ih;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        unsigned hp[4], mp[4], lp[4];
+        for (int e = 0; e < 4; ++e) {
+            *reinterpret_cast<f32x4*>(dst + 64 * e) = f32x4{v[0][e], v[1][e], v[2][e], v[3][e]};
+            *reinterpret_cast<f32x4*>(dst + 64 * e + 16) = f32x4{v[4][e], v[5][e], v[6][e], v[7][e]};
+        }
+    } else {
+        unsigned char* dst = img + (((size_t)n * (C >> 4) + cg) * HW + 4 * pq) * 32 + 16 * ih;
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) fx_split2(v[2 * jj][e], v[2 * jj + 1][e], hp[jj], mp[jj], lp[jj]);
-        *reinterpret_cast<i32x4*>(dst + 32 * e) = i32x4{(int)hp[0], (int)hp[1], (int)hp[2], (int)hp[3]};
-        *reinterpret_cast<i32x4*>(dst + plane_bytes + 32 * e) = i32x4{(int)mp[0], (int)mp[1], (int)mp[2], (int)mp[3]};
-        *reinterpret_cast<i32x4*>(dst + 2 * plane_bytes + 32 * e) = i32x4{(int)lp[0], (int)lp[1], (int)lp[2], (int)lp[3]};
+        for (int e = 0; e < 4; ++e) {
+            unsigned hp[4], mp[4], lp[4];
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) fx_split2(v[2 * jj][e], v[2 * jj + 1][e], hp[jj], mp[jj], lp[jj]);
+            *reinterpret_cast<i32x4*>(dst + 32 * e) = i32x4{(int)hp[0], (int)hp[1], (int)hp[2], (int)hp[3]};
+            *reinterpret_cast<i32x4*>(dst + plane_bytes + 32 * e) = i32x4{(int)mp[0], (int)mp[1], (int)mp[2], (int)mp[3]};
+            *reinterpret_cast<i32x4*>(dst + 2 * plane_bytes + 32 * e) = i32x4{(int)lp[0], (int)lp[1], (int)lp[2], (int)lp[3]};
+        }
     }
 }
 
@@ -1690,6 +1764,7 @@ __global__ __launch_bounds__(256) void fx_act_image_kernel(const float* __restri
 // partials [C][rows][3] of block_open_bwd: sum g, sum g (c_last - mean), sum g (c_ds - mean_ds)); every value by the expressions, and the partial rows in the order, of
 // fx_act_image_kernel<2>, so the images are bit-identical to two separate passes (p3d_fx_tune(3, 0) switches back: tests/test_block_gpu.py).
 struct FxPairSide { const float* c; unsigned char* img; const float* gamma; float* dgamma; float* dbeta; const float* table; const float* pixmul; };
+template <bool ROWS = false>          // ROWS: both images as fp32 row images (plane_bytes ignored)
 __global__ __launch_bounds__(256) void fx_act_image_pair_kernel(const float* __restrict__ X, const unsigned char* __restrict__ gmask, const FxPairSide a, const FxPairSide b,
                                                                 const double* __restrict__ partial, int rows, double count, int accumulate, size_t plane_bytes,
                                                                 int N, int C, int HW) {
@@ -1772,15 +1847,24 @@ __global__ __launch_bounds__(256) void fx_act_image_pair_kernel(const float* __r
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[j][e] *= f[e];
         }
-        unsigned char* dst = q.img + (((size_t)n * (C >> 4) + cg) * HW + 4 * pq) * 32 + 16 * ih;
+        if constexpr (ROWS) {         // the fp32 row image (fx_act_image_kernel)
+            unsigned char* dst = q.img + (((size_t)n * (C >> 4) + cg) * HW + 4 * pq) * 64 + 32 * ih;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            unsigned hp[4], mp[4], lp[4];
+            for (int e = 0; e < 4; ++e) {
+                *reinterpret_cast<f32x4*>(dst + 64 * e) = f32x4{v[0][e], v[1][e], v[2][e], v[3][e]};
+                *reinterpret_cast<f32x4*>(dst + 64 * e + 16) = f32x4{v[4][e], v[5][e], v[6][e], v[7][e]};
+            }
+        } else {
+            unsigned char* dst = q.img + (((size_t)n * (C >> 4) + cg) * HW + 4 * pq) * 32 + 16 * ih;
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) fx_split2(v[2 * jj][e], v[2 * jj + 1][e], hp[jj], mp[jj], lp[jj]);
-            *reinterpret_cast<i32x4*>(dst + 32 * e) = i32x4{(int)hp[0], (int)hp[1], (int)hp[2], (int)hp[3]};
-            *reinterpret_cast<i32x4*>(dst + plane_bytes + 32 * e) = i32x4{(int)mp[0], (int)mp[1], (int)mp[2], (int)mp[3]};
-            *reinterpret_cast<i32x4*>(dst + 2 * plane_bytes + 32 * e) = i32x4{(int)lp[0], (int)lp[1], (int)lp[2], (int)lp[3]};
+            for (int e = 0; e < 4; ++e) {
+                unsigned hp[4], mp[4], lp[4];
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) fx_split2(v[2 * jj][e], v[2 * jj + 1][e], hp[jj], mp[jj], lp[jj]);
+                *reinterpret_cast<i32x4*>(dst + 32 * e) = i32x4{(int)hp[0], (int)hp[1], (int)hp[2], (int)hp[3]};
+                *reinterpret_cast<i32x4*>(dst + plane_bytes + 32 * e) = i32x4{(int)mp[0], (int)mp[1], (int)mp[2], (int)mp[3]};
+                *reinterpret_cast<i32x4*>(dst + 2 * plane_bytes + 32 * e) = i32x4{(int)lp[0], (int)lp[1], (int)lp[2], (int)lp[3]};
+            }
         }
     }
 }
@@ -1788,22 +1872,26 @@ __global__ __launch_bounds__(256) void fx_act_image_pair_kernel(const float* __r
 static int g_pair_map = 1;
 bool fx_pair_map_enabled() { return g_pair_map != 0; }
 int32_t fx_act_image_pair(const float* x, const unsigned char* gmask, const float* c_a, const float* c_b, void* img_a, void* img_b, const FxFinalize* fa, const FxFinalize* fb,
-                          int N, int C, int HW, hipStream_t st, const float* pixmul_a) {
+                          int N, int C, int HW, hipStream_t st, const float* pixmul_a, bool rows) {
     if (!x || !c_a || !c_b || !img_a || !img_b || !fa || !fb || fa->kind != 3 || fb->kind != 3 || fa->partial != fb->partial || fa->rows != fb->rows || fa->which != 0 ||
         fb->which != 1 || N <= 0 || C <= 0 || (C & 15) || HW <= 0 || (HW & 3)) {
         set_error("fx_act_image_pair: bad argument"); return P3D_EINVAL;
     }
     const FxPairSide a{c_a, (unsigned char*)img_a, fa->gamma, fa->dgamma, fa->dbeta, fa->table, pixmul_a}, b{c_b, (unsigned char*)img_b, fb->gamma, fb->dgamma, fb->dbeta, fb->table, nullptr};
     const dim3 grid((unsigned)ceil_div((int64_t)N * (HW >> 2) * 2, 256), (unsigned)(C >> 4));
-    hipLaunchKernelGGL(fx_act_image_pair_kernel, grid, dim3(256), 0, st, x, gmask, a, b, (const double*)fa->partial, fa->rows, fa->count, fa->accumulate,
-                       (size_t)N * C * HW * 2, N, C, HW);
+    auto* kernel = rows ? fx_act_image_pair_kernel<true> : fx_act_image_pair_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, x, gmask, a, b, (const double*)fa->partial, fa->rows, fa->count, fa->accumulate, (size_t)N * C * HW * 2, N, C, HW);
     return check_launch("fx_act_image_pair");
 }
 
 size_t fx_act_image_bytes(int64_t N, int64_t C, int64_t HW) { return (size_t)(3 * N * C * HW * 2); }
+size_t fx_row_image_bytes(int64_t N, int64_t C, int64_t HW) { return (size_t)(N * C * HW * 4); }
+// 1: the block executor keeps a_i and d c_i of dense blocks as three-plane images, as before the row images (p3d_fx_tune(6, 1): the A/B, tests/test_row_images_gpu.py)
+static int g_plane_images = 0;
+bool fx_block_row_images() { return g_plane_images == 0; }
 
 int32_t fx_act_image(int mode, const float* x, const float* x2, const float* table, int masked, void* img, int N, int C, int HW, hipStream_t st,
-                     const FxFinalize* fin, const float* pixmul) {
+                     const FxFinalize* fin, const float* pixmul, bool rows) {
     if (!x || !img || N <= 0 || C <= 0 || (C & 15) || HW <= 0 || (HW & 3) || (mode != 0 && !table && !fin) || (mode == 2 && !x2) || mode < 0 || mode > 2) {
         set_error("fx_act_image: bad argument (N=%d C=%d HW=%d mode=%d; C %% 16 == 0 and HW %% 4 == 0 are required)", N, C, HW, mode); return P3D_EINVAL;
     }
@@ -1816,6 +1904,12 @@ int32_t fx_act_image(int mode, const float* x, const float* x2, const float* tab
     }
     const size_t plane = (size_t)N * C * HW * 2;
     const dim3 grid((unsigned)ceil_div((int64_t)N * (HW >> 2) * 2, 256), (unsigned)(C >> 4));
+    if (rows) {
+        if (mode == 0) hipLaunchKernelGGL(fx_act_image_kernel<FX_IMG_ROWS + 0>, grid, dim3(256), 0, st, x, x2, table, (unsigned char*)img, plane, N, C, HW, masked, f, pixmul);
+        else if (mode == 1) hipLaunchKernelGGL(fx_act_image_kernel<FX_IMG_ROWS + 1>, grid, dim3(256), 0, st, x, x2, table, (unsigned char*)img, plane, N, C, HW, masked, f, pixmul);
+        else hipLaunchKernelGGL(fx_act_image_kernel<FX_IMG_ROWS + 2>, grid, dim3(256), 0, st, x, x2, table, (unsigned char*)img, plane, N, C, HW, masked, f, pixmul);
+        return check_launch("fx_row_image");
+    }
     if (mode == 0) hipLaunchKernelGGL(fx_act_image_kernel<0>, grid, dim3(256), 0, st, x, x2, table, (unsigned char*)img, plane, N, C, HW, masked, f, pixmul);
     else if (mode == 1) hipLaunchKernelGGL(fx_act_image_kernel<1>, grid, dim3(256), 0, st, x, x2, table, (unsigned char*)img, plane, N, C, HW, masked, f, pixmul);
     else hipLaunchKernelGGL(fx_act_image_kernel<2>, grid, dim3(256), 0, st, x, x2, table, (unsigned char*)img, plane, N, C, HW, masked, f, pixmul);
@@ -1985,29 +2079,37 @@ constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool 
     return {pro, sums ? (dgrad ? FX_EPI_BWD_SUMS : FX_EPI_STATS) : FX_EPI_STORE};
 }
 
-// Every compiled instance of the two convolution kernels, once: X(AMODE, PRO, EPIX, TAPI, RAG) of fx_conv_kernel, X(BM, EPI, TAPI) of fx16_conv_kernel.  The tap-inner
+// Every compiled instance of the two convolution kernels, once: X(AMODE, PRO, EPIX, TAPI, RAG, ROWS) of fx_conv_kernel, X(BM, EPI, TAPI, ROWS) of fx16_conv_kernel.  The
+// row-fed (ROWS) instances are those the dense block executor launches: the plain epilogue (its split-K slabs too) and the two BatchNorm ones, either K order, every tile.
+// (A block's image-fed 3x3 is planes -> planes, so the tap-inner 96-row BatchNorm twins <96, STATS | BWD_SUMS, true, true> are reached by no block today: they are there so
+// that a launch gets the same K order -- the same bits -- in both formats, like their plane-fed twins.)  The tap-inner
 // twins exist where the layers that want them land: 128-row tiles with the plain / BatchNorm epilogues, and the 96-row fx16 tile (the regressor).
 #define P3D_FX_CONV_INSTANCES(X)                                                                                                                              \
-    X(0, 0, FX_EPI_STORE, false, false) X(0, 0, FX_EPI_STATS, false, false) X(0, 0, FX_EPI_BWD_SUMS, false, false) X(0, 0, FX_EPI_INFER, false, false)        \
-    X(0, 4, FX_EPI_STORE, false, false) X(0, 4, FX_EPI_FACTOR, false, false) X(0, 4, FX_EPI_FACTOR_STATS, false, false) X(0, 4, FX_EPI_INFER_FACTOR, false, false) \
-    X(1, 0, FX_EPI_STORE, false, false) X(1, 0, FX_EPI_STATS, false, false) X(1, 0, FX_EPI_BWD_SUMS, false, false)                                           \
-    X(1, 0, FX_EPI_FACTOR_STATS, false, false) X(1, 0, FX_EPI_FACTOR_BWD_SUMS, false, false) X(1, 0, FX_EPI_FACTOR_IMG, false, false) X(1, 0, FX_EPI_INFER, false, false) \
-    X(1, 0, FX_EPI_STORE, true, false) X(1, 0, FX_EPI_STATS, true, false) X(1, 0, FX_EPI_BWD_SUMS, true, false) X(0, 0, FX_EPI_STORE, false, true) X(0, 0, FX_EPI_INFER, false, true) \
-    X(0, 4, FX_EPI_INFER_FACTOR, false, true) X(0, 4, FX_EPI_STORE, false, true) X(0, 4, FX_EPI_FACTOR, false, true)                                             \
-    X(1, 0, FX_EPI_STORE, false, true) X(1, 0, FX_EPI_STORE, true, true)
+    X(0, 0, FX_EPI_STORE, false, false, false) X(0, 0, FX_EPI_STATS, false, false, false) X(0, 0, FX_EPI_BWD_SUMS, false, false, false) X(0, 0, FX_EPI_INFER, false, false, false)        \
+    X(0, 4, FX_EPI_STORE, false, false, false) X(0, 4, FX_EPI_FACTOR, false, false, false) X(0, 4, FX_EPI_FACTOR_STATS, false, false, false) X(0, 4, FX_EPI_INFER_FACTOR, false, false, false) \
+    X(1, 0, FX_EPI_STORE, false, false, false) X(1, 0, FX_EPI_STATS, false, false, false) X(1, 0, FX_EPI_BWD_SUMS, false, false, false)                                           \
+    X(1, 0, FX_EPI_FACTOR_STATS, false, false, false) X(1, 0, FX_EPI_FACTOR_BWD_SUMS, false, false, false) X(1, 0, FX_EPI_FACTOR_IMG, false, false, false) X(1, 0, FX_EPI_INFER, false, false, false) \
+    X(1, 0, FX_EPI_STORE, true, false, false) X(1, 0, FX_EPI_STATS, true, false, false) X(1, 0, FX_EPI_BWD_SUMS, true, false, false) X(0, 0, FX_EPI_STORE, false, true, false) X(0, 0, FX_EPI_INFER, false, true, false) \
+    X(0, 4, FX_EPI_INFER_FACTOR, false, true, false) X(0, 4, FX_EPI_STORE, false, true, false) X(0, 4, FX_EPI_FACTOR, false, true, false)                                             \
+    X(1, 0, FX_EPI_STORE, false, true, false) X(1, 0, FX_EPI_STORE, true, true, false)                                                                      \
+    X(1, 0, FX_EPI_STORE, false, false, true) X(1, 0, FX_EPI_STATS, false, false, true) X(1, 0, FX_EPI_BWD_SUMS, false, false, true)                        \
+    X(1, 0, FX_EPI_STORE, true, false, true) X(1, 0, FX_EPI_STATS, true, false, true) X(1, 0, FX_EPI_BWD_SUMS, true, false, true)
 #define P3D_FX16_CONV_INSTANCES(X)                                                                                             \
-    X(96, FX_EPI_STORE, false) X(96, FX_EPI_STATS, false) X(96, FX_EPI_BWD_SUMS, false) X(96, FX_EPI_INFER, false)             \
-    X(64, FX_EPI_STORE, false) X(64, FX_EPI_STATS, false) X(64, FX_EPI_BWD_SUMS, false) X(64, FX_EPI_INFER, false)             \
-    X(96, FX_EPI_STORE, true) X(96, FX_EPI_STATS, true) X(96, FX_EPI_BWD_SUMS, true)
+    X(96, FX_EPI_STORE, false, false) X(96, FX_EPI_STATS, false, false) X(96, FX_EPI_BWD_SUMS, false, false) X(96, FX_EPI_INFER, false, false)             \
+    X(64, FX_EPI_STORE, false, false) X(64, FX_EPI_STATS, false, false) X(64, FX_EPI_BWD_SUMS, false, false) X(64, FX_EPI_INFER, false, false)             \
+    X(96, FX_EPI_STORE, true, false) X(96, FX_EPI_STATS, true, false) X(96, FX_EPI_BWD_SUMS, true, false)                       \
+    X(96, FX_EPI_STORE, false, true) X(96, FX_EPI_STATS, false, true) X(96, FX_EPI_BWD_SUMS, false, true)                       \
+    X(64, FX_EPI_STORE, false, true) X(64, FX_EPI_STATS, false, true) X(64, FX_EPI_BWD_SUMS, false, true)                       \
+    X(96, FX_EPI_STORE, true, true) X(96, FX_EPI_STATS, true, true) X(96, FX_EPI_BWD_SUMS, true, true)
 // The instance of a launch (bm 0: fx_conv_kernel; 96 / 64: fx16_conv_kernel), or null.  A tap-inner twin is looked up by the code itself: a launch with the per-pixel
 // factor keeps the tap-outer order on either kernel.
 using FxKernel = void (*)(const FxConvParams);
-constexpr FxKernel fx_instance(int bm, bool img, int pro, int epi, bool tapi, bool rag) {
+constexpr FxKernel fx_instance(int bm, bool img, int pro, int epi, bool tapi, bool rag, bool rows = false) {
     const int am = img ? 1 : 0, e = bm && !tapi ? fx16_epi(epi) : epi;
-#define P3D_X(AM, PRO, EPI, TAPI, RAG) if (bm == 0 && am == AM && pro == PRO && e == EPI && tapi == TAPI && rag == RAG) return fx_conv_kernel<AM, PRO, EPI, TAPI, RAG>;
+#define P3D_X(AM, PRO, EPI, TAPI, RAG, ROWS) if (bm == 0 && am == AM && pro == PRO && e == EPI && tapi == TAPI && rag == RAG && rows == ROWS) return fx_conv_kernel<AM, PRO, EPI, TAPI, RAG, ROWS>;
     P3D_FX_CONV_INSTANCES(P3D_X)
 #undef P3D_X
-#define P3D_X(BM, EPI, TAPI) if (bm == BM && am == 1 && pro == 0 && e == EPI && tapi == TAPI && !rag) return fx16_conv_kernel<BM, EPI, TAPI>;
+#define P3D_X(BM, EPI, TAPI, ROWS) if (bm == BM && am == 1 && pro == 0 && e == EPI && tapi == TAPI && !rag && rows == ROWS) return fx16_conv_kernel<BM, EPI, TAPI, ROWS>;
     P3D_FX16_CONV_INSTANCES(P3D_X)
 #undef P3D_X
     return nullptr;
@@ -2020,6 +2122,13 @@ constexpr bool fx_select_covered() {
         const FxSelect s = fx_select(dgrad, img, masked, sums, infer);
         if (!fx_instance(0, img, s.pro, s.epi, false, false) || !fx_instance(0, img, s.pro, FX_EPI_STORE, false, false)) return false;
         if (img && s.pro == 0 && fx16_epi(s.epi) >= 0 && !(fx_instance(96, img, 0, s.epi, false, false) && fx_instance(64, img, 0, s.epi, false, false))) return false;
+    }
+    // row images: the dense image-fed codes of training, on every tile and in either K order where the plane-fed code has a tap-inner twin
+    for (int c = 0; c < 4; ++c) {
+        const FxSelect s = fx_select(c & 1, true, false, c & 2, false);
+        const int bms[3] = {0, 96, 64};
+        for (int bm : bms)
+            if (!fx_instance(bm, true, s.pro, s.epi, false, false, true) || (bm != 64 && !fx_instance(bm, true, s.pro, s.epi, true, false, true))) return false;
     }
     return fx_instance(0, false, 0, FX_EPI_INFER, false, true) && fx_instance(0, false, 0, FX_EPI_STORE, false, true) &&     // (the ragged forward: fp32-fed inference,
            fx_instance(0, false, 4, FX_EPI_INFER_FACTOR, false, true) && fx_instance(0, false, 4, FX_EPI_STORE, false, true) &&  //  dense and as a partial convolution;
@@ -2036,6 +2145,7 @@ void fx_tune(int what, int value) {
         case 2: g_wgrad_target = value; break;
         case 3: g_pair_map = value; break;                   // 0: the two opening image passes of a downsample block as two launches (tests)
         case 5: g_class_launches = value ? 1 : 0; break;
+        case 6: g_plane_images = value ? 1 : 0; break;
         default: break;                                      // (unknown code: ignored)
     }
 }
@@ -2259,26 +2369,26 @@ int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_f
 }
 
 // the one place that launches a convolution kernel: the instance of (tile, operand, prologue, epilogue, K order, ragged), P3D_EINVAL if none was compiled
-static int32_t fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi, int bm, dim3 grid, hipStream_t st, bool rag = false) {
+static int32_t fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi, int bm, dim3 grid, hipStream_t st, bool rag = false, bool rows = false) {
     FxConvParams p = p_in;
     // only the STORE and backward instances of the aligned kernels hold the strided store: a parity class on any other would be written at dense addresses
     P3D_REQUIRE(!(rag || fx_epi_sums(epi) == 1 || fx_epi_infer(epi)) || (p.oxs == 1 && p.oys == 1 && p.oy0 == 0 && p.ox0 == 0 && p.YW == p.OW && p.YH == p.OH && p.ncls == 0),
                 "fx_launch_conv: a strided result on a dense-only instance (rag=%d epi=%d)", rag ? 1 : 0, epi);
-    if (p.tap_inner && !fx_instance(bm, img, pro, epi, true, rag)) p.tap_inner = 0;
-    const FxKernel kernel = fx_instance(bm, img, pro, epi, p.tap_inner != 0, rag);
-    if (!kernel) { set_error("fx_launch_conv: no kernel instance for img=%d pro=%d epi=%d bm=%d", img ? 1 : 0, pro, epi, bm); return P3D_EINVAL; }
+    if (p.tap_inner && !fx_instance(bm, img, pro, epi, true, rag, rows)) p.tap_inner = 0;
+    const FxKernel kernel = fx_instance(bm, img, pro, epi, p.tap_inner != 0, rag, rows);
+    if (!kernel) { set_error("fx_launch_conv: no kernel instance for img=%d pro=%d epi=%d bm=%d rows=%d", img ? 1 : 0, pro, epi, bm, rows ? 1 : 0); return P3D_EINVAL; }
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, p);
     return P3D_OK;
 }
 
 // A split-K call: the slabs (raw partial products, from the FX_EPI_STORE instance: bias, factor, sums and the inference tail belong to the pass that sums them), then
 // that pass, which writes p.Y.  p: the parameters of the unsplit launch.
-static int32_t fx_launch_split(FxConvParams p, const FxPlan& pl, bool img, int pro, int epi, int bm, float* slabs, hipStream_t st, bool rag = false) {
+static int32_t fx_launch_split(FxConvParams p, const FxPlan& pl, bool img, int pro, int epi, int bm, float* slabs, hipStream_t st, bool rag = false, bool rows = false) {
     float* const y = p.Y;
     const float* const bias = p.bias, * const em = p.emask;
     const int OHW = p.OH * p.OW;
     p.kchunk = pl.kchunk; p.slab_stride = pl.slab_stride; p.Y = slabs; p.bias = nullptr; p.emask = nullptr;
-    if (int32_t e = fx_launch_conv(p, img, pro == 4 ? 4 : 0, FX_EPI_STORE, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), (unsigned)pl.splits), st, rag)) return e;
+    if (int32_t e = fx_launch_conv(p, img, pro == 4 ? 4 : 0, FX_EPI_STORE, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), (unsigned)pl.splits), st, rag, rows)) return e;
     prof_kernel_done(st);
     if (rag) {
         const unsigned total = (unsigned)((size_t)p.N * p.M * OHW);          // (fx_common: below 2^31)
@@ -2305,6 +2415,8 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     const bool rag = fuse && fuse->ragged;          // the ragged instances (p3d_fx_conv_fwd_infer_any, p3d_fx_conv_fwd_infer_masked_any; training under p3d_x3_any_enable, partial
                                                     // convolutions under p3d_x3_any_partial_enable): any map width
     const void* wimg = fuse ? fuse->wimg : nullptr;
+    const bool rows = fuse && fuse->rows;           // act_img is an fp32 row image (fx_row_image_bytes)
+    P3D_REQUIRE(!rows || (img && !masked && !infer && !rag), "fx_conv_fwd: a row image feeds the dense aligned training launches only");
     if (masked && (!fuse->emask || (bias && !infer) || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr))) {
         set_error("fx_conv_fwd: the partial-convolution instances take the output factor, the input factor exactly for an fp32 operand, and no bias"); return P3D_EINVAL;
     }
@@ -2339,8 +2451,8 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     const int bm = rag ? 0 : fx16_bm(d->K, img, split ? 0 : sel.pro, split ? FX_EPI_STORE : sel.epi);
     p.tiles_m = (int)ceil_div(d->K, bm ? bm : FX_BM);
     p.tap_inner = img && RS > 1 && d->C >= FX_TAP_INNER_MIN;
-    if (int32_t e = split ? fx_launch_split(p, pl, img, sel.pro, sel.epi, bm, (float*)(ws + pl.slab_offset), st, rag)
-                          : fx_launch_conv(p, img, sel.pro, sel.epi, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), 1), st, rag)) return e;
+    if (int32_t e = split ? fx_launch_split(p, pl, img, sel.pro, sel.epi, bm, (float*)(ws + pl.slab_offset), st, rag, rows)
+                          : fx_launch_conv(p, img, sel.pro, sel.epi, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), 1), st, rag, rows)) return e;
     return check_launch("fx_conv_fwd");
 }
 
@@ -2357,6 +2469,8 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
     if (masked && (!fuse->emask || (img ? fuse->pmask != nullptr : fuse->pmask == nullptr) || (!img && fuse->partial))) {
         set_error("fx_conv_dgrad: the partial-convolution instances take the result factor and the operand factor exactly for an fp32 operand"); return P3D_EINVAL;
     }
+    const bool rows = fuse && fuse->rows;           // act_img is an fp32 row image
+    P3D_REQUIRE(!rows || (img && !masked && !(fuse && fuse->ragged)), "fx_conv_dgrad: a row image feeds the dense aligned launches only");
     const bool rag = fuse && fuse->ragged;          // the ragged forward instances over dy (p3d_x3_any_enable; masked: p3d_x3_any_partial_enable): any map width, stride 1, fp32-fed
     P3D_REQUIRE(!rag || (d->stride == 1 && !(img && masked) && !fuse->partial && !fuse->acc_src),
                 "fx_conv_dgrad: the ragged data gradient is the stride-1 one, dense (fp32- or image-fed) or masked (fp32-fed), without sums");
@@ -2392,8 +2506,8 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
         p.nR = d->R; p.nS = d->S; p.ntap = RS; p.r0 = 0; p.rstep = 1; p.s0 = 0; p.sstep = 1;
         p.hmul = 1; p.hoff = d->pad; p.hstep = -d->dil; p.wmul = 1; p.woff = d->pad; p.wstep = -d->dil;
         if (!split && fuse && fuse->acc_src && d->accumulate) { p.acc_src = fuse->acc_src; p.acc_mask = fuse->acc_mask; }
-        if (int32_t e = split ? fx_launch_split(p, pl, img, pro, epi, bm, (float*)(ws + pl.slab_offset), st, rag)
-                              : fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), 1), st, rag)) return e;
+        if (int32_t e = split ? fx_launch_split(p, pl, img, pro, epi, bm, (float*)(ws + pl.slab_offset), st, rag, rows)
+                              : fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), 1), st, rag, rows)) return e;
         return check_launch("fx_conv_dgrad");
     }
     // stride 2: input pixel (ph + 2 i, pw + 2 j) of class (ph, pw) gathers dy at (i + off0 - ir * offstep, ...) over the taps r = r0 + rstep * ir that reach it
@@ -2418,7 +2532,7 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
             c.hoff = ty.off0; c.hstep = -ty.offstep;
             c.woff = tx.off0; c.wstep = -tx.offstep;
             c.oy0 = ph; c.ox0 = pw;
-            if (g_class_launches) { if (int32_t e = fx_launch_conv(c, img, pro, epi, bm, dim3((unsigned)(c.tiles_m * tiles_n), 1), st)) return e; continue; }
+            if (g_class_launches) { if (int32_t e = fx_launch_conv(c, img, pro, epi, bm, dim3((unsigned)(c.tiles_m * tiles_n), 1), st, false, rows)) return e; continue; }
             cls[ncls++] = FxConvClass{c.nR, c.nS, c.ntap, c.r0, c.rstep, c.s0, c.sstep, c.hoff, c.hstep, c.woff, c.wstep, c.oy0, c.ox0};
         }
     if (ncls > 0) {
@@ -2427,7 +2541,7 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
             for (int j = i; j > 0 && cls[j].ntap > cls[j - 1].ntap; --j) { const FxConvClass t = cls[j]; cls[j] = cls[j - 1]; cls[j - 1] = t; }
         p.ncls = ncls;
         for (int i = 0; i < ncls; ++i) p.cls[i] = cls[i];
-        if (int32_t e = fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1, (unsigned)ncls), st)) return e;
+        if (int32_t e = fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1, (unsigned)ncls), st, false, rows)) return e;
     }
     return check_launch("fx_conv_dgrad");
 }
@@ -2524,18 +2638,24 @@ int32_t fx_conv_wgrad_slabs(const p3d_conv_desc* d, const float* dy, const float
             masked = true; p.amask = fuse->pmask; p.bmask = fuse->emask;
         }
     }
+    const bool rows = fuse && fuse->rows;           // the image operands are fp32 row images
+    if (rows && (!aimg || masked)) { set_error("fx_conv_wgrad: row images feed the dense image-fed instances only"); return P3D_EINVAL; }
     if ((aimg && (d->K & 15)) || (bimg && (d->C & 15)) || (bimg && !aimg)) { set_error("fx_conv_wgrad: image operands need channel counts in steps of 16 (and a dy image beside an x image)"); return P3D_EINVAL; }
     const dim3 grid((unsigned)ceil_div(d->C, FX_BN), (unsigned)ceil_div(d->K, FX_BM), (unsigned)(splits * d->R * d->S));
     if (const int tt = fx_wgrad_two_taps(d, aimg && bimg && !masked)) {
         const dim3 tg((unsigned)ceil_div(d->R * d->S, tt), (unsigned)ceil_div(d->K, FX_BM), (unsigned)splits);
-        if (tt == 3) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 3>), tg, dim3(256), 0, st, p);
+        if (tt == 3 && rows) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 3, true>), tg, dim3(256), 0, st, p);
+        else if (tt == 3) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 3>), tg, dim3(256), 0, st, p);
+        else if (rows) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 2, true>), tg, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 2>), tg, dim3(256), 0, st, p);
         prof_kernel_done(st);
         return check_launch("fx_conv_wgrad");
     }
     if (masked && aimg) hipLaunchKernelGGL((fx_wgrad_kernel<true, false, true>), grid, dim3(256), 0, st, p);
     else if (masked) hipLaunchKernelGGL((fx_wgrad_kernel<false, false, true>), grid, dim3(256), 0, st, p);
+    else if (aimg && bimg && rows) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 0, true>), grid, dim3(256), 0, st, p);
     else if (aimg && bimg) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false>), grid, dim3(256), 0, st, p);
+    else if (aimg && rows) hipLaunchKernelGGL((fx_wgrad_kernel<true, false, false, 0, true>), grid, dim3(256), 0, st, p);
     else if (aimg) hipLaunchKernelGGL((fx_wgrad_kernel<true, false, false>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((fx_wgrad_kernel<false, false, false>), grid, dim3(256), 0, st, p);
     prof_kernel_done(st);

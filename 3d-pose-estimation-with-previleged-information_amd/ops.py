@@ -1003,26 +1003,66 @@ def act_image(x, mode=0, x2=None, table=None, masked=False, out=None):
     return img
 
 
-def conv2d_img(pass_, x_shape, w, stride, pad, dil, x_img=None, dy_img=None, x=None, bias=None, accumulate_into=None):
+def row_image(x, mode=0, x2=None, table=None, masked=False, out=None):
+    """Row image of a fp32 NCHW tensor (p3d_fx_row_image): uint8 tensor of 4 bytes per element = the fp32 values as [N][C/16][H*W][16]; modes as act_image.
+    C in steps of 16, H * W in steps of 4."""
+    _need_gpu(x)
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    nbytes = lib().p3d_fx_row_image_bytes(n, c, h * w)
+    img = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if out is None else out
+    if img.numel() != nbytes or img.dtype != torch.uint8 or not img.is_contiguous():
+        raise P3DError('row_image: `out` must be a contiguous uint8 tensor of %d bytes' % nbytes)
+    check(lib().p3d_fx_row_image(mode, _p(x), None if x2 is None else _p(x2.contiguous()), None if table is None else _p(table.contiguous()), int(bool(masked)),
+                                 _p(img), n, c, h * w, _stream()), 'p3d_fx_row_image')
+    return img
+
+
+def open_images(x, gmask, partial, count, sides, rows=False):
+    """The image passes that open a block's backward pass (p3d_fx_open_images; tests): x the upstream gradient, gmask the closing ReLU's mask bytes or None, partial the
+    fp64 sums [C][nrows][3], sides one or two tuples (c, table, gamma).  Returns per side (image, dgamma, dbeta); two sides run as the one pair pass."""
+    _need_gpu(x)
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    L = lib()
+    nbytes = (L.p3d_fx_row_image_bytes if rows else L.p3d_fx_act_image_bytes)(n, c, h * w)
+    out, args = [], []
+    for (ct, tab, gamma) in sides:
+        img = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        dg, db = torch.empty(c, dtype=torch.float32, device=x.device), torch.empty(c, dtype=torch.float32, device=x.device)
+        out.append((img, dg, db))
+        args += [_p(ct.contiguous()), _p(tab.contiguous()), _p(gamma.contiguous()), _p(dg), _p(db), _p(img)]
+    if len(sides) == 1:
+        args += [None] * 6
+    assert partial.dtype == torch.float64 and partial.is_contiguous() and partial.shape[0] == c and partial.shape[2] == 3
+    check(L.p3d_fx_open_images(int(bool(rows)), _p(x), None if gmask is None else _p(gmask), _p(partial), partial.shape[1], float(count), *args, n, c, h * w, _stream()),
+          'p3d_fx_open_images')
+    return out
+
+
+def conv2d_img(pass_, x_shape, w, stride, pad, dil, x_img=None, dy_img=None, x=None, bias=None, accumulate_into=None, rows=False):
     """One pass of a convolution on pre-split image operands (p3d_fx_conv_*_img; what the block executor launches): 'fwd' -> y from x_img,
-    'dgrad' -> dx from dy_img, 'wgrad' -> dw from dy_img and x_img (or the fp32 x).  For tests and tools/conv_bench.py."""
+    'dgrad' -> dx from dy_img, 'wgrad' -> dw from dy_img and x_img (or the fp32 x).  rows: the images are row images (row_image; p3d_fx_conv_*_rows).
+    For tests and tools/conv_bench.py."""
     _need_gpu(w)
     w = w.contiguous()
     d = _desc(x_shape, w.shape, stride, pad, dil)
     which = {'fwd': 0, 'dgrad': 1, 'wgrad': 2}[pass_]
-    ws = workspace(w.device, lib().p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), which))
+    L, form = lib(), 'rows' if rows else 'img'
+    ws = workspace(w.device, L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), which))
     if which == 0:
         y = torch.empty((d.N, d.K, d.Ho, d.Wo), dtype=torch.float32, device=w.device)
-        check(lib().p3d_fx_conv_fwd_img(ctypes.byref(d), _p(x_img), _p(w), None, None if bias is None else _p(bias), _p(y), _p(ws), ws.numel(), _stream()), 'p3d_fx_conv_fwd_img')
+        check(getattr(L, 'p3d_fx_conv_fwd_' + form)(ctypes.byref(d), _p(x_img), _p(w), None, None if bias is None else _p(bias), _p(y), _p(ws), ws.numel(), _stream()),
+              'p3d_fx_conv_fwd_' + form)
         return y
     if which == 1:
         dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=w.device) if accumulate_into is None else accumulate_into
         d.accumulate = int(accumulate_into is not None)
-        check(lib().p3d_fx_conv_dgrad_img(ctypes.byref(d), _p(dy_img), _p(w), None, _p(dx), _p(ws), ws.numel(), _stream()), 'p3d_fx_conv_dgrad_img')
+        check(getattr(L, 'p3d_fx_conv_dgrad_' + form)(ctypes.byref(d), _p(dy_img), _p(w), None, _p(dx), _p(ws), ws.numel(), _stream()), 'p3d_fx_conv_dgrad_' + form)
         return dx
     dw = torch.empty_like(w)
-    check(lib().p3d_fx_conv_wgrad_img(ctypes.byref(d), _p(dy_img), None if x is None else _p(x.contiguous()), None if x_img is None else _p(x_img), _p(dw), _p(ws),
-                                      ws.numel(), _stream()), 'p3d_fx_conv_wgrad_img')
+    check(getattr(L, 'p3d_fx_conv_wgrad_' + form)(ctypes.byref(d), _p(dy_img), None if x is None else _p(x.contiguous()), None if x_img is None else _p(x_img), _p(dw), _p(ws),
+                                                  ws.numel(), _stream()), 'p3d_fx_conv_wgrad_' + form)
     return dw
 
 

@@ -81,6 +81,9 @@ class _Plan:
             check(lib().p3d_block_workspace_bytes(ctypes.byref(d), ctypes.byref(m), ctypes.byref(s)), 'p3d_block_workspace_bytes')
             self.main_bytes, self.side_bytes = m.value, s.value
         self.slots = [slot for slot, _, _ in _layers(block)]
+        # bytes of the image of a tensor shaped like c_slot (a_slot, d c_slot): fp32 rows, 4 B per element, for a dense block; three bf16 planes, 6 B, for a masked one
+        self.image_bytes = {slot: lib().p3d_block_image_bytes(ctypes.byref(d), self.shapes[slot][0], self.shapes[slot][1], self.shapes[slot][2] * self.shapes[slot][3])
+                            for slot in self.slots}
         # one table for the block's BatchNorm layers, [K_slot][8] floats each, in slot order
         self.table_offset, self.table_rows = {}, 0
         for slot in self.slots:
@@ -133,8 +136,8 @@ class _Buffers(_BufferSet):
         f32 = dict(dtype=torch.float32, device=device)
         self.tables = torch.empty((plan.table_rows, 8), **f32)
         self.c = {slot: torch.empty(plan.shapes[slot], **f32) for slot in plan.slots}
-        # a_slot = relu(bn(c_slot)) exists only as a pre-split image (three bf16 planes: 6 B per element)
-        self.act = {slot: torch.empty(6 * self.c[slot].numel(), dtype=torch.uint8, device=device) for slot in plan.slots if slot < plan.desc.nconv - 1}
+        # a_slot = relu(bn(c_slot)) exists only as an image (plan.image_bytes: fp32 rows, or three bf16 planes)
+        self.act = {slot: torch.empty(plan.image_bytes[slot], dtype=torch.uint8, device=device) for slot in plan.slots if slot < plan.desc.nconv - 1}
         # which outputs the closing ReLU let through: one byte per four elements, all the backward pass needs of `out`
         n_out = plan.out_shape[0] * plan.out_shape[1] * plan.out_shape[2] * plan.out_shape[3]
         self.mask = torch.empty(n_out // 4, dtype=torch.uint8, device=device) if (plan.desc.relu_out and USE_OUT_MASK) else None
@@ -149,7 +152,7 @@ class _Buffers(_BufferSet):
     def backward_scratch(self, plan):
         if self.bwd is None:
             f32 = dict(dtype=torch.float32, device=self.device)
-            dcimg = {slot: torch.empty(6 * self.c[slot].numel(), dtype=torch.uint8, device=self.device) for slot in plan.slots}    # image of d c_slot: what conv slot's wgrad and dgrad read
+            dcimg = {slot: torch.empty(plan.image_bytes[slot], dtype=torch.uint8, device=self.device) for slot in plan.slots}    # image of d c_slot: what conv slot's wgrad and dgrad read
             da = {slot: torch.empty(plan.shapes[slot], **f32) for slot in plan.slots if slot < plan.desc.nconv - 1}
             # g = dout * [out > 0]: with an identity shortcut it IS dx (a fresh tensor per call); with a downsample branch and mask bytes nobody needs it as a tensor
             gbuf = torch.empty(plan.out_shape, **f32) if (plan.desc.has_downsample and self.mask is None) else None
@@ -316,11 +319,23 @@ def release_buffers(model):
     return dropped
 
 
+_plane_images = False
+
+
+def plane_images(on):
+    """Test hook (p3d_fx_tune(6, on)): the executor keeps the images of dense blocks as three bf16 planes, as masked blocks do, instead of fp32 rows.  Plans made
+    under the other format are not used again (their buffers have its size).  Returns the previous setting."""
+    global _plane_images
+    before, _plane_images = _plane_images, bool(on)
+    lib().p3d_fx_tune(6, int(_plane_images))
+    return before
+
+
 def plan_for(block, x, masked=False):
     cache = block.__dict__.get('_blk_plans')
     if cache is None:
         cache = block.__dict__['_blk_plans'] = _Transient()
-    key = (tuple(x.shape), ops.X3_EPOCH, bool(masked))
+    key = (tuple(x.shape), ops.X3_EPOCH, bool(masked), _plane_images)
     plan = cache.pop(key, None)
     if plan is None:
         # a plan owns device buffers: keep those of the PLAN_LIMIT most recently used input shapes (a training loop has one or two: the batch and the epoch's

@@ -128,6 +128,8 @@ int32_t p3d_conv2d_wgrad_masked_any_supported(const p3d_conv_desc* d);
  *   2  forced block target of the weight-gradient split plan               (tools/split_sweep.py)
  *   3  0: the two opening image passes of a downsample block as two launches instead of the pair pass (default 1; tests/test_block_gpu.py)
  *   5  1: one launch per parity class of a strided data gradient instead of one launch for all (tests/test_geometry_gpu.py)
+ *   6  1: p3d_block_* keep the activation / gradient images of dense blocks as three bf16 planes (6 B per element) instead of fp32 row images (4 B); changes what
+ *         p3d_block_image_bytes reports, so set it before the buffers of a block are sized (tests/test_row_images_gpu.py, the A/B of profiles/row_images.md)
  * Any other code is ignored. */
 void p3d_fx_tune(int32_t what, int32_t value);
 /* How many conv launches took which path since the last reset: counts / flops [0..2] = forward, data gradient, weight gradient on the bf16-pipe kernels,
@@ -193,7 +195,7 @@ typedef struct p3d_block_io {
     const void* wimg[4];        /* pre-split weight images (p3d_fx_weight_images) of w[i] for the forward pass / the data gradient, or NULL: the kernels split */
     const void* wimgT[4];       /*   the fp32 weights on the fly.  The caller rebuilds an image whenever its weight changes. */
     float* c[4];
-    void* aimg[4];              /* pre-split activation image (p3d_fx_act_image_bytes(N, K_i, Ho_i * Wo_i) bytes) of a[i] = relu(bn_i(c[i])), i < nconv-1: written by
+    void* aimg[4];              /* activation image (p3d_block_image_bytes(b, N, K_i, Ho_i * Wo_i) bytes: an fp32 row image in a dense block, three bf16 planes in a masked one) of a[i] = relu(bn_i(c[i])), i < nconv-1: written by
                                    forward; read by conv i+1 in forward and by its weight gradient in backward.  a[i] itself never exists as fp32. */
     float* table[4];
     const float* gamma[4];
@@ -204,7 +206,7 @@ typedef struct p3d_block_io {
     const float* dout;
     float* gbuf;                /* may be NULL when the block has a downsample branch and out_mask is given (g is then never needed as a tensor) */
     void* dcimg[4];             /* scratch, one per convolution (slot 3: the downsample branch): image of d c_i, the gradient w.r.t. conv i's raw output
-                                   (p3d_fx_act_image_bytes(N, K_i, Ho_i * Wo_i) bytes); read by conv i's weight gradient and data gradient */
+                                   (p3d_block_image_bytes(b, N, K_i, Ho_i * Wo_i) bytes: an fp32 row image in a dense block, three bf16 planes in a masked one); read by conv i's weight gradient and data gradient */
     float* da[4];
     float* dx;
     float* dw[4];
@@ -276,6 +278,28 @@ int32_t p3d_fx_weight_images_batched(const void* jobs, int32_t njobs, int32_t bl
  * BatchNorm-backward map of the gradient x at the raw conv output x2.  table: the layer's [C][8] floats {sc, sh, mean, invstd, A, B, K, 0} as p3d_block_io.table. */
 size_t p3d_fx_act_image_bytes(int32_t N, int32_t C, int32_t HW);
 int32_t p3d_fx_act_image(int32_t mode, const float* x, const float* x2, const float* table, int32_t masked, void* img, int32_t N, int32_t C, int32_t HW, void* stream);
+/* Row images: the same tensor in the same channel-blocked rows, holding the fp32 value itself: [N][C/16][HW][16] floats, 4 * N * C * HW bytes.  Every filter tap and
+ * stride still lands on an aligned row of 16 channels (64 B); the row-fed kernel instances cut a value into its three bf16 pieces between their fetch registers and
+ * LDS, with the function the plane passes use, so every result is bit-identical to the plane-fed one.  Modes and arguments as p3d_fx_act_image.
+ * p3d_fx_conv_*_rows: p3d_fx_conv_*_img on row images (x_rows / dy_rows from p3d_fx_row_image); dense convolutions that p3d_fx_conv_img_supported admits, same
+ * workspace (p3d_fx_conv_img_workspace_bytes).
+ * p3d_block_image_bytes: bytes of one p3d_block_io.aimg / dcimg buffer of N x C x HW elements for this block: 4 per element for a dense block, 6 for a masked one
+ * (and for every block under p3d_fx_tune(6, 1)). */
+size_t p3d_fx_row_image_bytes(int32_t N, int32_t C, int32_t HW);
+int32_t p3d_fx_row_image(int32_t mode, const float* x, const float* x2, const float* table, int32_t masked, void* img, int32_t N, int32_t C, int32_t HW, void* stream);
+int32_t p3d_fx_conv_fwd_rows(const p3d_conv_desc* d, const void* x_rows, const float* w, const void* wimg, const float* bias, float* y, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int32_t p3d_fx_conv_dgrad_rows(const p3d_conv_desc* d, const void* dy_rows, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int32_t p3d_fx_conv_wgrad_rows(const p3d_conv_desc* d, const void* dy_rows, const float* x, const void* x_rows, float* dw, void* workspace, size_t workspace_bytes,
+                               void* stream);
+size_t p3d_block_image_bytes(const p3d_block_desc* b, int32_t N, int32_t C, int32_t HW);
+/* The image passes that open a block's backward pass, alone (tests/test_row_images_gpu.py): d c = A g + B c + K, g = x with the mask bytes applied (gmask: bit e of byte i
+ * lets element 4 i + e pass; NULL: none), the constants finalized in the prologue from fp64 partial sums [C][nrows][3] = (sum g, sum g (c_a - mean_a), sum g (c_b - mean_b))
+ * and the tables' mean / invstd; d gamma and d beta are written.  c_b NULL: one image (side a); otherwise both images in one pass.  rows: 0 three planes, 1 row images. */
+int32_t p3d_fx_open_images(int32_t rows, const float* x, const unsigned char* gmask, const double* partial, int32_t nrows, double count, const float* c_a, const float* table_a,
+                           const float* gamma_a, float* dgamma_a, float* dbeta_a, void* img_a, const float* c_b, const float* table_b, const float* gamma_b, float* dgamma_b,
+                           float* dbeta_b, void* img_b, int32_t N, int32_t C, int32_t HW, void* stream);
 /* The three passes of a convolution on image operands (what p3d_block_* launches inside a block).  pass: 0 forward, 1 data gradient, 2 weight gradient.
  * wimg / wimgT: the p3d_fx_weight_images image of w for that pass, or NULL (built into the workspace).  wgrad: x (fp32) is read when x_img is NULL. */
 size_t p3d_fx_conv_img_workspace_bytes(const p3d_conv_desc* d, int32_t pass);

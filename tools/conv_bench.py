@@ -44,6 +44,7 @@ def main():
     ap.add_argument('--only', default='')
     ap.add_argument('--mode', default='all', help='all | fwd | dgrad | wgrad')
     ap.add_argument('--img', action='store_true', help='also time the image-fed instances (pre-split activation / gradient images, pre-built weight images: what the block executor launches)')
+    ap.add_argument('--rows', action='store_true', help='with --img: feed fp32 row images (p3d_fx_row_image, p3d_fx_conv_*_rows) instead of three-plane images')
     ap.add_argument('--tune', default='', help='p3d_fx_tune settings for this run, e.g. "1=4,5=1" (the codes of include/p3d_hip.h: 0 / 1 forced split counts, 2 wgrad block target, 3 pair pass, 5 per-class launches)')
     a = ap.parse_args()
     for kv in filter(None, a.tune.split(',')):
@@ -91,17 +92,19 @@ def main():
             L.p3d_fx_weight_image_bytes(k, c, ks * ks, ctypes.byref(fb), ctypes.byref(bb))
             wf, wb = torch.empty(fb.value, dtype=torch.uint8, device='cuda'), torch.empty(bb.value, dtype=torch.uint8, device='cuda')
             L.p3d_fx_weight_images(p(w), k, c, ks * ks, p(wf), p(wb), st_)
-            xi, dyi = ops.act_image(x), ops.act_image(dy)
+            image = ops.row_image if a.rows else ops.act_image
+            e_f, e_d, e_w = (L.p3d_fx_conv_fwd_rows, L.p3d_fx_conv_dgrad_rows, L.p3d_fx_conv_wgrad_rows) if a.rows else (L.p3d_fx_conv_fwd_img, L.p3d_fx_conv_dgrad_img, L.p3d_fx_conv_wgrad_img)
+            xi, dyi = image(x), image(dy)
             w0 = torch.empty(max(L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 0), 16), dtype=torch.uint8, device='cuda')
             w1 = torch.empty(max(L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 1), 16), dtype=torch.uint8, device='cuda')
             w2 = torch.empty(max(L.p3d_fx_conv_img_workspace_bytes(ctypes.byref(d), 2), 16), dtype=torch.uint8, device='cuda')
-            i_f = timeit(lambda: L.p3d_fx_conv_fwd_img(ctypes.byref(d), p(xi), p(w), p(wf), None, p(y), p(w0), w0.numel(), st_), a.iters)
-            i_d = timeit(lambda: L.p3d_fx_conv_dgrad_img(ctypes.byref(d), p(dyi), p(w), p(wb), p(dx), p(w1), w1.numel(), st_), a.iters)
-            i_w = timeit(lambda: L.p3d_fx_conv_wgrad_img(ctypes.byref(d), p(dyi), None, p(xi), p(dw), p(w2), w2.numel(), st_), a.iters)
-            i_w2 = timeit(lambda: L.p3d_fx_conv_wgrad_img(ctypes.byref(d), p(dyi), p(x), None, p(dw), p(w2), w2.numel(), st_), a.iters)
-            t_img = timeit(lambda: ops.act_image(dy), a.iters)
+            i_f = timeit(lambda: e_f(ctypes.byref(d), p(xi), p(w), p(wf), None, p(y), p(w0), w0.numel(), st_), a.iters)
+            i_d = timeit(lambda: e_d(ctypes.byref(d), p(dyi), p(w), p(wb), p(dx), p(w1), w1.numel(), st_), a.iters)
+            i_w = timeit(lambda: e_w(ctypes.byref(d), p(dyi), None, p(xi), p(dw), p(w2), w2.numel(), st_), a.iters)
+            i_w2 = timeit(lambda: e_w(ctypes.byref(d), p(dyi), p(x), None, p(dw), p(w2), w2.numel(), st_), a.iters)
+            t_img = timeit(lambda: image(dy), a.iters)
             print('%-34s %8s | %8.3f %6.1f | %8.3f %6.1f | %8.3f %6.1f   wgrad(fp32 x) %.3f %.1f   image pass of dy %.3f ms (%.0f GB/s)'
-                  % ('  image-fed', '', i_f, gflop / i_f, i_d, gflop / i_d, i_w, gflop / i_w, i_w2, gflop / i_w2, t_img, dy.numel() * 10 / t_img / 1e6))
+                  % ('  row-fed' if a.rows else '  image-fed', '', i_f, gflop / i_f, i_d, gflop / i_d, i_w, gflop / i_w, i_w2, gflop / i_w2, t_img, dy.numel() * (8 if a.rows else 10) / t_img / 1e6))
             for key, v in (('fwd', i_f), ('dgrad', i_d), ('wgrad', i_w)):
                 tot_img[key] += v * cnt
         tot['fwd'] += t_f * cnt
