@@ -28,6 +28,12 @@ class FoldJob(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ('K', 'C', 'RS', 'c_offset', 'c_total', 'kind')] + [('eps', ctypes.c_float), ('reserved', ctypes.c_int32)]
 
 
+class FxFuse(ctypes.Structure):
+    """struct p3d_fx_fuse (p3d_fx_conv_fused, a test hook)"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ('act_img', 'wimg', 'partial', 'ep_c', 'ep_tab', 'pmask', 'emask', 'acc_src', 'acc_mask', 'res')] + \
+               [(n, ctypes.c_int32) for n in ('rows', 'infer', 'relu', 'ragged')]
+
+
 _i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _ptr, _sz = ctypes.c_void_p, ctypes.c_size_t
 _desc = ctypes.POINTER(ConvDesc)
@@ -94,6 +100,11 @@ SIGNATURES = {
     'p3d_fx_conv_fwd_img_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_fx_conv_dgrad_img_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_fx_conv_wgrad_img_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    'p3d_fx_launch_log': (_i32, [ctypes.POINTER(_i32), _i32, _i32]),
+    'p3d_fx_conv_instances': (_i32, [ctypes.POINTER(_i32), _i32]),
+    'p3d_fx_conv_fused_workspace_bytes': (_sz, [_i32, _desc, _i32]),
+    'p3d_fx_conv_fused_partial_rows': (_i32, [_i32, _desc]),
+    'p3d_fx_conv_fused': (_i32, [_i32, _desc, ctypes.POINTER(FxFuse), _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     'p3d_stem_supported': (_i32, [_i32] * 5),
     'p3d_stem_image_bytes': (_sz, [_i32] * 3),
     'p3d_stem_weight_image_bytes': (_sz, [_i32]),

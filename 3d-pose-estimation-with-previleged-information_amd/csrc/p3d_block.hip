@@ -1071,6 +1071,46 @@ int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, co
     return name_entry("fx_conv_wgrad_img_any", wgrad_finish(d, (float*)workspace, splits, d->R * d->S > 1, dw, (hipStream_t)stream));
 }
 
+// What the forward / data-gradient launchers launched, and what they can launch (include/p3d_hip.h)
+int32_t p3d_fx_launch_log(int32_t* out, int32_t max_records, int32_t reset) { return fx_launch_log(out, out && max_records > 0 ? max_records : 0, reset); }
+int32_t p3d_fx_conv_instances(int32_t* out, int32_t max_records) { return fx_conv_instances(out, out && max_records > 0 ? max_records : 0); }
+
+// Test hook: fx_conv_fwd / fx_conv_dgrad with any FxFuse (include/p3d_hip.h).  Checks what the launchers take for granted from their callers -- the pointers, a
+// well-formed descriptor, the shape rule of the pass -- and leaves every other refusal to them.  No zero fill of dead parity classes, no path count.
+static bool fused_desc_ok(const p3d_conv_desc* d) {
+    if (!d || d->N <= 0 || d->C <= 0 || d->K <= 0 || d->H <= 0 || d->W <= 0 || d->R <= 0 || d->S <= 0 || d->stride < 1 || d->dil < 1 || d->pad < 0) return false;
+    if (d->accumulate < 0 || d->accumulate > 1 || d->c_total < d->C) return false;
+    return d->Ho > 0 && d->Wo > 0 && d->Ho == (d->H + 2 * d->pad - d->dil * (d->R - 1) - 1) / d->stride + 1 && d->Wo == (d->W + 2 * d->pad - d->dil * (d->S - 1) - 1) / d->stride + 1;
+}
+// (0 from both queries: a descriptor, or a shape, the hook refuses -- the dense rule; a call with a factor needs 64 result channels on top)
+size_t p3d_fx_conv_fused_workspace_bytes(int32_t pass, const p3d_conv_desc* d, int32_t ragged) {
+    if (!fused_desc_ok(d) || pass < 0 || pass > 1 || !fx_applies(pass == 0 ? FX_FWD : FX_DGRAD, d, 32, ragged != 0)) return 0;
+    return fx_workspace(pass == 0 ? FX_FWD : FX_DGRAD, d, ragged != 0);
+}
+int32_t p3d_fx_conv_fused_partial_rows(int32_t pass, const p3d_conv_desc* d) {
+    if (!fused_desc_ok(d) || pass < 0 || pass > 1) return 0;
+    if (!fx_applies(pass == 0 ? FX_FWD : FX_DGRAD, d, 32, false) && !fx_applies(pass == 0 ? FX_FWD : FX_DGRAD, d, 32, true)) return 0;
+    return fx_partial_rows(pass == 0 ? FX_FWD : FX_DGRAD, d);
+}
+int32_t p3d_fx_conv_fused(int32_t pass, const p3d_conv_desc* d, const p3d_fx_fuse* f, const float* src, const float* w, const float* bias, float* out, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    P3D_REQUIRE(d && f && w && out && (src || f->act_img) && (pass == 0 || pass == 1), "fx_conv_fused: null argument, or a pass other than 0 / 1");
+    P3D_REQUIRE(fused_desc_ok(d), "fx_conv_fused: malformed descriptor");
+    P3D_REQUIRE(pass == 0 || !bias, "fx_conv_fused: the data gradient takes no bias");
+    P3D_REQUIRE(!f->partial || pass == 0 || (f->ep_c && f->ep_tab), "fx_conv_fused: the backward sums need ep_c and ep_tab");
+    P3D_REQUIRE(!f->acc_mask || f->acc_src, "fx_conv_fused: mask bytes without an accumulation source");
+    const FxPass ps = pass == 0 ? FX_FWD : FX_DGRAD;
+    const bool masked = f->pmask || f->emask, rag = f->ragged != 0;
+    P3D_REQUIRE(masked ? fx_masked_applies(ps, d, rag) : fx_applies(ps, d, 32, rag), "fx_conv_fused: shape outside the x3 kernels");
+    P3D_REQUIRE(aligned16(src, f->act_img, f->wimg, out, workspace, f->ep_c, f->acc_src, f->res) && (rag || aligned16(f->pmask, f->emask)),
+                "fx_conv_fused: operands, result and workspace must be 16-B aligned");
+    FxFuse x{};
+    x.act_img = f->act_img; x.wimg = f->wimg; x.partial = f->partial; x.ep_c = f->ep_c; x.ep_tab = f->ep_tab; x.pmask = f->pmask; x.emask = f->emask;
+    x.acc_src = f->acc_src; x.acc_mask = f->acc_mask; x.infer = f->infer != 0; x.res = f->res; x.relu = f->relu != 0; x.rows = f->rows != 0; x.ragged = rag;
+    return name_entry("fx_conv_fused", pass == 0 ? fx_conv_fwd(d, src, w, bias, out, workspace, workspace_bytes, &x, (hipStream_t)stream)
+                                                 : fx_conv_dgrad(d, src, w, out, workspace, workspace_bytes, &x, (hipStream_t)stream));
+}
+
 // Inference with folded BatchNorm (include/p3d_hip.h): the fold of a whole network in one launch, and the forward on the folded images with the inference epilogue.
 int32_t p3d_fx_fold_bn_images(const void* jobs, int32_t njobs, int32_t blocks, void* stream) {
     P3D_REQUIRE(jobs && njobs > 0 && blocks > 0, "fold_bn_images: bad argument");

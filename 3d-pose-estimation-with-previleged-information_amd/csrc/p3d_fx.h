@@ -130,6 +130,9 @@ bool fx_any_images_enabled();           // p3d_x3_any_images_enable / P3D_X3_ANY
 int fx_set_any_images_enabled(int on);
 void fx_count(int kind, const p3d_conv_desc* d);
 void fx_stats(unsigned long long* counts, double* flops, int reset);
+// the log of forward / data-gradient conv-kernel launches and the list of compiled instances (p3d_fx_launch_log, p3d_fx_conv_instances: include/p3d_hip.h)
+int32_t fx_launch_log(int32_t* out, int32_t max_records, int32_t reset);
+int32_t fx_conv_instances(int32_t* out, int32_t max_records);
 // Which convolutions the x3 kernels take, per pass: one rule each (p3d_fx.hip).  min_m: the least channel count of the result's tile rows the caller finds worth it (96:
 // the per-layer entries; 64: the block executor; 32: image-fed and inference callers).  ragged: the instances that take any map width -- the same rule without its
 // width / alignment clauses (forward: W % 4, Wo % 4; data gradient: those, and stride 1 only; weight gradient: (Ho Wo) % 16, Wo % 4, W % 4), so it cannot drift

@@ -2082,7 +2082,8 @@ constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool 
 // Every compiled instance of the two convolution kernels, once: X(AMODE, PRO, EPIX, TAPI, RAG, ROWS) of fx_conv_kernel, X(BM, EPI, TAPI, ROWS) of fx16_conv_kernel.  The
 // row-fed (ROWS) instances are those the dense block executor launches: the plain epilogue (its split-K slabs too) and the two BatchNorm ones, either K order, every tile.
 // (A block's image-fed 3x3 is planes -> planes, so the tap-inner 96-row BatchNorm twins <96, STATS | BWD_SUMS, true, true> are reached by no block today: they are there so
-// that a launch gets the same K order -- the same bits -- in both formats, like their plane-fed twins.)  The tap-inner
+// that a launch gets the same K order -- the same bits -- in both formats, like their plane-fed twins; tests/test_fx_instances_gpu.py runs them, and every other
+// instance of the two lists, through p3d_fx_conv_fused against float64, and tests/test_fx_instances_host.py fails when a new entry here has no row.)  The tap-inner
 // twins exist where the layers that want them land: 128-row tiles with the plain / BatchNorm epilogues, and the 96-row fx16 tile (the regressor).
 #define P3D_FX_CONV_INSTANCES(X)                                                                                                                              \
     X(0, 0, FX_EPI_STORE, false, false, false) X(0, 0, FX_EPI_STATS, false, false, false) X(0, 0, FX_EPI_BWD_SUMS, false, false, false) X(0, 0, FX_EPI_INFER, false, false, false)        \
@@ -2368,8 +2369,46 @@ int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_f
     return check_launch("fx_build_weight_images");
 }
 
-// the one place that launches a convolution kernel: the instance of (tile, operand, prologue, epilogue, K order, ragged), P3D_EINVAL if none was compiled
-static int32_t fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi, int bm, dim3 grid, hipStream_t st, bool rag = false, bool rows = false) {
+// ---- what was launched (p3d_fx_launch_log): one record per conv-kernel launch, layout documented in include/p3d_hip.h -------------------------------
+enum { FXL_KERNEL = 0, FXL_AMODE, FXL_PRO, FXL_EPI, FXL_TAPI, FXL_RAG, FXL_ROWS, FXL_GRID_X, FXL_GRID_Y, FXL_GRID_Z, FXL_KCHUNK, FXL_FINISH, FXL_FINISH_GROUPS,
+       FXL_FIELDS = P3D_FX_LAUNCH_FIELDS };
+static_assert(FXL_FINISH_GROUPS < FXL_FIELDS && FXL_ROWS + 1 == P3D_FX_INSTANCE_FIELDS, "the record of p3d_fx_launch_log outgrew its documented length");
+enum { FX_FINISH_NONE = 0, FX_FINISH_REDUCE0, FX_FINISH_REDUCE1, FX_FINISH_REDUCE2, FX_FINISH_REDUCE_ANY };       // FXL_FINISH
+constexpr int FX_LOG_MAX = 256;
+static std::mutex g_fx_log_mu;
+static int32_t g_fx_log[FX_LOG_MAX][FXL_FIELDS];
+static int64_t g_fx_log_n = 0;          // launches since the last reset (the first FX_LOG_MAX are kept)
+int32_t fx_launch_log(int32_t* out, int32_t max_records, int32_t reset) {
+    std::lock_guard<std::mutex> lock(g_fx_log_mu);
+    const int64_t kept = g_fx_log_n < FX_LOG_MAX ? g_fx_log_n : FX_LOG_MAX;
+    for (int64_t i = 0; out && i < kept && i < max_records; ++i)
+        for (int f = 0; f < FXL_FIELDS; ++f) out[i * FXL_FIELDS + f] = g_fx_log[i][f];
+    const int32_t n = (int32_t)(g_fx_log_n < INT32_MAX ? g_fx_log_n : INT32_MAX);
+    if (reset) g_fx_log_n = 0;
+    return n;
+}
+int32_t fx_conv_instances(int32_t* out, int32_t max_records) {
+    int32_t n = 0;
+    auto put = [&](int kernel, int am, int pro, int epi, bool tapi, bool rag, bool rows) {
+        if (out && n < max_records) {
+            const int32_t rec[P3D_FX_INSTANCE_FIELDS] = {kernel, am, pro, epi, tapi ? 1 : 0, rag ? 1 : 0, rows ? 1 : 0};
+            for (int f = 0; f < P3D_FX_INSTANCE_FIELDS; ++f) out[n * P3D_FX_INSTANCE_FIELDS + f] = rec[f];
+        }
+        ++n;
+    };
+#define P3D_X(AM, PRO, EPI, TAPI, RAG, ROWS) put(0, AM, PRO, EPI, TAPI, RAG, ROWS);
+    P3D_FX_CONV_INSTANCES(P3D_X)
+#undef P3D_X
+#define P3D_X(BM, EPI, TAPI, ROWS) put(BM, 1, 0, EPI, TAPI, false, ROWS);
+    P3D_FX16_CONV_INSTANCES(P3D_X)
+#undef P3D_X
+    return n;
+}
+
+// the one place that launches a convolution kernel: the instance of (tile, operand, prologue, epilogue, K order, ragged), P3D_EINVAL if none was compiled.
+// finish / finish_groups: the pass fx_launch_split queues behind the slabs, for the record only
+static int32_t fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int epi, int bm, dim3 grid, hipStream_t st, bool rag = false, bool rows = false,
+                              int finish = FX_FINISH_NONE, int finish_groups = 0) {
     FxConvParams p = p_in;
     // only the STORE and backward instances of the aligned kernels hold the strided store: a parity class on any other would be written at dense addresses
     P3D_REQUIRE(!(rag || fx_epi_sums(epi) == 1 || fx_epi_infer(epi)) || (p.oxs == 1 && p.oys == 1 && p.oy0 == 0 && p.ox0 == 0 && p.YW == p.OW && p.YH == p.OH && p.ncls == 0),
@@ -2378,6 +2417,18 @@ static int32_t fx_launch_conv(const FxConvParams& p_in, bool img, int pro, int e
     const FxKernel kernel = fx_instance(bm, img, pro, epi, p.tap_inner != 0, rag, rows);
     if (!kernel) { set_error("fx_launch_conv: no kernel instance for img=%d pro=%d epi=%d bm=%d rows=%d", img ? 1 : 0, pro, epi, bm, rows ? 1 : 0); return P3D_EINVAL; }
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, p);
+    {
+        std::lock_guard<std::mutex> lock(g_fx_log_mu);
+        if (g_fx_log_n < FX_LOG_MAX) {
+            int32_t* r = g_fx_log[g_fx_log_n];
+            for (int f = 0; f < FXL_FIELDS; ++f) r[f] = 0;
+            r[FXL_KERNEL] = bm; r[FXL_AMODE] = img ? 1 : 0; r[FXL_PRO] = pro; r[FXL_EPI] = bm && !p.tap_inner ? fx16_epi(epi) : epi;       // (as fx_instance looked it up)
+            r[FXL_TAPI] = p.tap_inner ? 1 : 0; r[FXL_RAG] = rag ? 1 : 0; r[FXL_ROWS] = rows ? 1 : 0;
+            r[FXL_GRID_X] = (int32_t)grid.x; r[FXL_GRID_Y] = (int32_t)grid.y; r[FXL_GRID_Z] = (int32_t)grid.z; r[FXL_KCHUNK] = p.kchunk;
+            r[FXL_FINISH] = finish; r[FXL_FINISH_GROUPS] = finish_groups;
+        }
+        ++g_fx_log_n;
+    }
     return P3D_OK;
 }
 
@@ -2388,7 +2439,9 @@ static int32_t fx_launch_split(FxConvParams p, const FxPlan& pl, bool img, int p
     const float* const bias = p.bias, * const em = p.emask;
     const int OHW = p.OH * p.OW;
     p.kchunk = pl.kchunk; p.slab_stride = pl.slab_stride; p.Y = slabs; p.bias = nullptr; p.emask = nullptr;
-    if (int32_t e = fx_launch_conv(p, img, pro == 4 ? 4 : 0, FX_EPI_STORE, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), (unsigned)pl.splits), st, rag, rows)) return e;
+    const int finish = rag ? FX_FINISH_REDUCE_ANY : FX_FINISH_REDUCE0 + fx_epi_sums(epi);
+    if (int32_t e = fx_launch_conv(p, img, pro == 4 ? 4 : 0, FX_EPI_STORE, bm, dim3((unsigned)(p.tiles_m * pl.tiles_n), (unsigned)pl.splits), st, rag, rows, finish,
+                                   rag ? 1 : pl.partial_rows)) return e;
     prof_kernel_done(st);
     if (rag) {
         const unsigned total = (unsigned)((size_t)p.N * p.M * OHW);          // (fx_common: below 2^31)

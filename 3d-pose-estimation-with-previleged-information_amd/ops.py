@@ -1103,6 +1103,30 @@ def conv_last_fp32_launch():
     return {n: int(out[i]) for i, n in enumerate(LAST_FP32_FIELDS)}
 
 
+# the record of p3d_fx_launch_log, and (its first FX_INSTANCE_LEN fields) of p3d_fx_conv_instances: include/p3d_hip.h and the enum of csrc/p3d_fx.hip define the layout;
+# tests/test_fx_instances_host.py holds these to them
+FX_LAUNCH_FIELDS = ('kernel', 'amode', 'pro', 'epi', 'tapi', 'rag', 'rows', 'grid_x', 'grid_y', 'grid_z', 'kchunk', 'finish', 'finish_groups')
+FX_LAUNCH_LEN = 16          # P3D_FX_LAUNCH_FIELDS
+FX_INSTANCE_LEN = 7         # P3D_FX_INSTANCE_FIELDS
+FX_LOG_MAX = 256            # records the library keeps between two resets
+
+
+def fx_launch_log(reset=True):
+    """The forward / data-gradient conv-kernel launches of the x3 path since the last reset (p3d_fx_launch_log), oldest first: (records, count) with one dict of
+    FX_LAUNCH_FIELDS per kept record; count > len(records) when more than FX_LOG_MAX were made."""
+    out = (ctypes.c_int32 * (FX_LAUNCH_LEN * FX_LOG_MAX))()
+    count = lib().p3d_fx_launch_log(out, FX_LOG_MAX, int(bool(reset)))
+    return [{n: int(out[i * FX_LAUNCH_LEN + j]) for j, n in enumerate(FX_LAUNCH_FIELDS)} for i in range(min(count, FX_LOG_MAX))], count
+
+
+def fx_conv_instances():
+    """Every compiled instance of fx_conv_kernel / fx16_conv_kernel (p3d_fx_conv_instances) as a tuple of the first FX_INSTANCE_LEN values of FX_LAUNCH_FIELDS."""
+    n = lib().p3d_fx_conv_instances(None, 0)
+    out = (ctypes.c_int32 * (FX_INSTANCE_LEN * n))()
+    assert lib().p3d_fx_conv_instances(out, n) == n
+    return [tuple(int(out[i * FX_INSTANCE_LEN + j]) for j in range(FX_INSTANCE_LEN)) for i in range(n)]
+
+
 def reproject_crops(frames, params20, out_hw, round_u8=True):
     """Batch of cameralib.reproject_image calls (cameralib.py:378-443): frames [B,Hs,Ws,C] uint8 / fp32 as decoded, params20 [B,20] fp32
     (cameralib.reproject_params) -> [B,C,Ho,Wo] fp32."""

@@ -332,6 +332,57 @@ int32_t p3d_fx_conv_dgrad_img_any(const p3d_conv_desc* d, const void* dy_img, co
                                   void* stream);
 int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
                                   void* stream);
+/* What the x3 path launched: one record per launch of a forward / data-gradient convolution kernel, written where the launch is made (every caller: p3d_conv2d_*, the
+ * image entries, the inference entries, p3d_block_*, p3d_fx_conv_fused).  Host-side bookkeeping only.  A record is P3D_FX_LAUNCH_FIELDS int32:
+ *   [0] kernel: 0 fx_conv_kernel (128-row tile), 96 / 64: fx16_conv_kernel with that tile
+ *   [1] AMODE (1: image-fed)   [2] PRO (4: the operand times its per-pixel factor)   [3] EPI: the epilogue code the instance was compiled with -- on the fx16 kernel a
+ *       factor code is the instance without the factor (0 store, 1 statistics, 2 backward sums, 4 factor, 5 / 6 factor with 1 / 2, 7 factor image-fed, 8 inference,
+ *       9 inference with factor)   [4] TAPI (1: taps innermost), as launched   [5] RAG (any map width)   [6] ROWS (fp32 row image)  -- the kernel's template arguments
+ *   [7] grid.x   [8] grid.y (split-K slabs)   [9] grid.z (parity classes of a strided data gradient in one launch)   [10] kchunk: K steps per slab, 0 unsplit
+ *   [11] the pass that followed: 0 none, 1 fx_reduce_kernel<0>, 2 fx_reduce_kernel<1>, 3 fx_reduce_kernel<2>, 4 fx_reduce_any_kernel   [12] its grid.y (the image groups
+ *        of fx_reduce_kernel = the rows of its partial sums; 1 for fx_reduce_any_kernel; 0 with [11] 0)
+ *   [13..15] 0
+ * p3d_fx_launch_log: copies the records since the last reset into out, oldest first, at most max_records of them (the library keeps the first 256), and returns how
+ * many launches there were since then -- more than max_records, or than 256, shows as a count above what was copied.  reset != 0: the log starts anew afterwards.
+ * out may be NULL with max_records 0.
+ * p3d_fx_conv_instances: every compiled instance of the two kernels as P3D_FX_INSTANCE_FIELDS int32 each -- fields [0..6] of a record --, generated from the lists
+ * the instances are compiled from; returns their number (copies at most max_records). */
+#define P3D_FX_LAUNCH_FIELDS 16
+#define P3D_FX_INSTANCE_FIELDS 7
+int32_t p3d_fx_launch_log(int32_t* out, int32_t max_records, int32_t reset);
+int32_t p3d_fx_conv_instances(int32_t* out, int32_t max_records);
+/* TEST HOOK (tests/test_fx_instances_gpu.py; nothing in the package calls it): one forward (pass 0) or data-gradient (pass 1) call of the x3 kernels with any of the
+ * fusions the block executor and the inference entries use, so that each can be checked alone.  src: x (forward) / dy (data gradient), fp32, ignored when f->act_img is
+ * set; out: y / dx.  The fields of p3d_fx_fuse, NULL / 0 = not used:
+ *   act_img  the operand as a p3d_fx_act_image image (rows = 1: a p3d_fx_row_image one; ragged = 1: p3d_fx_act_image_any)
+ *   wimg     the p3d_fx_weight_images image of w for this pass, or NULL: built into the workspace
+ *   partial  [p3d_fx_conv_fused_partial_rows][M][2] partial sums per result channel: forward (sum y, sum y^2); data gradient (sum g, sum g (ep_c - mean)) with
+ *            g = dx * [ep_c * sc + sh > 0], ep_c laid out like dx and ep_tab [M][8] = {sc, sh, mean, ...}.  The summed value is the convolution (+ bias) (* emask);
+ *            what an unsplit accumulating call adds to it is not in the sums
+ *   pmask, emask  partial convolution: per-pixel factor of the operand ([N][1][.][.] of src; fp32 operand only -- an image carries it) and of the result
+ *   acc_src, acc_mask  data gradient with d->accumulate, stride 1, unsplit: out = dgrad + acc_src * [bit (i & 3) of acc_mask[i >> 2]] instead of out += dgrad
+ *   infer, res, relu   forward with a folded weight image: out = relu?(conv * emask + bias (+ out when accumulating) (+ res))
+ * Checks the null arguments, the descriptor and the shape rule of the pass (32 result channels; with a factor the partial-convolution rule) and passes everything else to
+ * the launcher, which refuses the combinations it has no instance for (P3D_EINVAL with a message).  Does not zero the pixels of a strided 1x1 data gradient that no tap
+ * reaches, and does not count in p3d_conv_path_stats.  Workspace: p3d_fx_conv_fused_workspace_bytes (under the p3d_fx_tune settings in force).  Both queries are
+ * host-only and return 0 for a pass, a descriptor or a shape the hook refuses (the rule without a factor). */
+typedef struct p3d_fx_fuse {
+    const void* act_img;
+    const void* wimg;
+    float* partial;
+    const float* ep_c;
+    const float* ep_tab;
+    const float* pmask;
+    const float* emask;
+    const float* acc_src;
+    const unsigned char* acc_mask;
+    const float* res;
+    int32_t rows, infer, relu, ragged;
+} p3d_fx_fuse;
+size_t p3d_fx_conv_fused_workspace_bytes(int32_t pass, const p3d_conv_desc* d, int32_t ragged);
+int32_t p3d_fx_conv_fused_partial_rows(int32_t pass, const p3d_conv_desc* d);
+int32_t p3d_fx_conv_fused(int32_t pass, const p3d_conv_desc* d, const p3d_fx_fuse* f, const float* src, const float* w, const float* bias, float* out, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* Inference with eval-mode BatchNorm folded into the convolutions (infer.py): s = gamma / sqrt(var + eps), w' = w * s, b' = beta - mean * s (+ s * conv bias).
  * p3d_fx_fold_bn_images: ONE launch for a table of jobs (device array of p3d_fold_job); per job kind 0 writes the forward weight image of w' over the input
