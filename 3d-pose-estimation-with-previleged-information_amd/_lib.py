@@ -105,6 +105,7 @@ SIGNATURES = {
     'p3d_fx_conv_fused_workspace_bytes': (_sz, [_i32, _desc, _i32]),
     'p3d_fx_conv_fused_partial_rows': (_i32, [_i32, _desc]),
     'p3d_fx_conv_fused': (_i32, [_i32, _desc, ctypes.POINTER(FxFuse), _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    'p3d_fx_wgrad_plan': (_i32, [_desc, _i32, ctypes.POINTER(_i32)]),
     'p3d_stem_supported': (_i32, [_i32] * 5),
     'p3d_stem_image_bytes': (_sz, [_i32] * 3),
     'p3d_stem_weight_image_bytes': (_sz, [_i32]),

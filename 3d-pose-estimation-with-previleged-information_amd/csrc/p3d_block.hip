@@ -532,6 +532,7 @@ struct BwdCtx {
     void* ws; size_t conv_ws;       // the launch stream's workspace: conv scratch
     void* partial;                  //   and the partial sums behind it
     float* side_ws;                 // the weight-gradient stream's slabs
+    size_t side_bytes;
     hipStream_t st, ss;
     bool two;                       // ss is a stream of its own
     bool rows;                      // aimg / dcimg are fp32 row images (block_row_images)
@@ -560,7 +561,7 @@ static int32_t bwd_map(const BwdCtx& x, const float* gin, int slot, int masked, 
 
 // `ready`: the launch stream's position when the gradient image of this convolution was complete (the data gradient of the same layer has been queued on
 // the launch stream since: it is the critical path and gets to the GPU first; the weight gradient only feeds the optimizer)
-static int32_t launch_wgrad(const BwdCtx& x, int slot, const float* xin, const void* ximg, bool tapm, hipEvent_t ready) {
+static int32_t launch_wgrad(const BwdCtx& x, int slot, const float* xin, const void* ximg, hipEvent_t ready) {
     const p3d_conv_desc* d = &x.b->conv[slot];
     if (x.two && (!ready || hipStreamWaitEvent(x.ss, ready, 0) != hipSuccess)) { set_error("block_bwd: event failure"); return P3D_ELAUNCH; }
     ProfScope ps(2, d, x.ss);
@@ -568,11 +569,7 @@ static int32_t launch_wgrad(const BwdCtx& x, int slot, const float* xin, const v
     FxFuse fw{};
     fw.dy_img = x.io->dcimg[slot]; fw.x_img = ximg; fw.rows = x.rows;
     if (x.b->masked && slot != 3 && !ximg) fw.emask = x.io->pix_in[slot];      // the block input is fp32: x * mask_in in the kernel's split (an image carries it)
-    const int splits = fx_wgrad_splits(d, ximg != nullptr);
-    if (int32_t e = fx_conv_wgrad_slabs(d, nullptr, xin, x.side_ws, splits, &fw, x.ss)) return e;
-    p3d_conv_desc dw_desc = *d;
-    dw_desc.accumulate = x.acc;
-    return wgrad_finish(&dw_desc, x.side_ws, splits, tapm, x.io->dw[slot], x.ss);
+    return fx_conv_wgrad(d, nullptr, xin, x.io->dw[slot], x.acc, x.side_ws, x.side_bytes, &fw, "block_bwd", x.ss);
 }
 
 static int32_t bwd_dgrad(const BwdCtx& x, int slot, const p3d_conv_desc* dd, float* dx, const FxFuse* f) {
@@ -633,7 +630,7 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
             dd.accumulate = 0;
             P3D_REQUIRE(io->da[i - 1], "block_bwd: null gradient buffer %d", i - 1);
             if (int32_t e = bwd_dgrad(x, i, &dd, io->da[i - 1], &f)) return e;
-            if (int32_t e = launch_wgrad(x, i, nullptr, io->aimg[i - 1], d->R * d->S > 1, ready)) return e;
+            if (int32_t e = launch_wgrad(x, i, nullptr, io->aimg[i - 1], ready)) return e;
             const double cnt = (double)dp->N * dp->Ho * dp->Wo;
             if (epi) {
                 if (int32_t e = bwd_map(x, io->da[i - 1], i - 1, 1, 2, fx_partial_rows(FX_DGRAD, d), 0, cnt)) return e;
@@ -661,7 +658,7 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
             }
             if (int32_t e = bwd_dgrad(x, 0, &dd, dx, &f)) return e;
         }
-        if (int32_t e = launch_wgrad(x, 0, io->x, nullptr, d->R * d->S > 1, ready)) return e;
+        if (int32_t e = launch_wgrad(x, 0, io->x, nullptr, ready)) return e;
     }
     return P3D_OK;
 }
@@ -676,7 +673,7 @@ static int32_t bwd_downsample(const BwdCtx& x, hipEvent_t ready) {
         dd.accumulate = 1;
         if (int32_t e = bwd_dgrad(x, 3, &dd, x.io->dx, &f)) return e;
     }
-    return launch_wgrad(x, 3, x.io->x, nullptr, false, ready);
+    return launch_wgrad(x, 3, x.io->x, nullptr, ready);
 }
 
 // dout -> dx (+ every parameter gradient, accumulated into io->dw / dgamma / dbeta when b->accumulate_grads, else written).
@@ -696,7 +693,7 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
         set_error("block_bwd: workspaces %zu / %zu B < required %zu / %zu B", workspace_bytes, side_bytes, lay.main_bytes, lay.side_bytes);
         return P3D_EWORKSPACE;
     }
-    x.ws = workspace; x.conv_ws = lay.conv_ws; x.partial = (char*)workspace + lay.conv_ws; x.side_ws = (float*)side_workspace;
+    x.ws = workspace; x.conv_ws = lay.conv_ws; x.partial = (char*)workspace + lay.conv_ws; x.side_ws = (float*)side_workspace; x.side_bytes = side_bytes;
     x.st = (hipStream_t)stream; x.ss = side_stream ? (hipStream_t)side_stream : x.st;
     x.two = x.ss != x.st;
     x.acc = b->accumulate_grads; x.last = b->nconv - 1; x.rows = block_row_images(b);
@@ -980,15 +977,11 @@ static int32_t conv_wgrad_img(const char* name, bool rows, const p3d_conv_desc* 
                               size_t workspace_bytes, void* stream) {
     P3D_REQUIRE(d && dy_img && (x || x_img) && dw, "%s: null argument", name);
     P3D_REQUIRE(fx_applies(FX_WGRAD, d, 32) && d->K % 16 == 0 && (!x_img || d->C % 16 == 0), "%s: shape outside the x3 kernels", name);
-    const int splits = fx_wgrad_splits(d, x_img != nullptr);
-    const size_t need = (size_t)splits * d->K * d->C * d->R * d->S * sizeof(float);
-    if (!workspace || workspace_bytes < need) { set_error("%s: workspace %zu B < required %zu B", name, workspace_bytes, need); return P3D_EWORKSPACE; }
     FxFuse f{};
     f.dy_img = dy_img; f.x_img = x_img; f.rows = rows;
     ProfScope ps(2, d, (hipStream_t)stream);
     fx_count(2, d);
-    if (int32_t e = fx_conv_wgrad_slabs(d, nullptr, x, (float*)workspace, splits, &f, (hipStream_t)stream)) return e;
-    return wgrad_finish(d, (float*)workspace, splits, d->R * d->S > 1, dw, (hipStream_t)stream);
+    return fx_conv_wgrad(d, nullptr, x, dw, d->accumulate, workspace, workspace_bytes, &f, name, (hipStream_t)stream);
 }
 int32_t p3d_fx_conv_wgrad_img(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
                               void* stream) {
@@ -1060,15 +1053,11 @@ int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, co
     P3D_REQUIRE(d->accumulate == 0 || d->accumulate == 1, "fx_conv_wgrad_img_any: accumulate must be 0 or 1");
     // (dw may sit anywhere on a 4-B line -- a view into a flat gradient buffer: wgrad_finish picks its accesses by the address)
     P3D_REQUIRE(aligned16(dy_img, x_img, workspace) && (reinterpret_cast<uintptr_t>(dw) & 3) == 0, "fx_conv_wgrad_img_any: the images and the workspace must be 16-B aligned");
-    const int splits = fx_wgrad_splits(d, true, true);
-    const size_t need = (size_t)splits * d->K * d->C * d->R * d->S * sizeof(float);
-    if (!workspace || workspace_bytes < need) { set_error("fx_conv_wgrad_img_any: workspace %zu B < required %zu B", workspace_bytes, need); return P3D_EWORKSPACE; }
     FxFuse f{};
     f.dy_img = dy_img; f.x_img = x_img; f.ragged = 1;
     ProfScope ps(2, d, (hipStream_t)stream);
     fx_count(2, d);
-    if (int32_t e = name_entry("fx_conv_wgrad_img_any", fx_conv_wgrad_slabs(d, nullptr, nullptr, (float*)workspace, splits, &f, (hipStream_t)stream))) return e;
-    return name_entry("fx_conv_wgrad_img_any", wgrad_finish(d, (float*)workspace, splits, d->R * d->S > 1, dw, (hipStream_t)stream));
+    return fx_conv_wgrad(d, nullptr, nullptr, dw, d->accumulate, workspace, workspace_bytes, &f, "fx_conv_wgrad_img_any", (hipStream_t)stream);
 }
 
 // What the forward / data-gradient launchers launched, and what they can launch (include/p3d_hip.h)
@@ -1109,6 +1098,13 @@ int32_t p3d_fx_conv_fused(int32_t pass, const p3d_conv_desc* d, const p3d_fx_fus
     x.acc_src = f->acc_src; x.acc_mask = f->acc_mask; x.infer = f->infer != 0; x.res = f->res; x.relu = f->relu != 0; x.rows = f->rows != 0; x.ragged = rag;
     return name_entry("fx_conv_fused", pass == 0 ? fx_conv_fwd(d, src, w, bias, out, workspace, workspace_bytes, &x, (hipStream_t)stream)
                                                  : fx_conv_dgrad(d, src, w, out, workspace, workspace_bytes, &x, (hipStream_t)stream));
+}
+
+// Test hook: how a weight gradient would be planned, as a record (include/p3d_hip.h).  Host-only.
+int32_t p3d_fx_wgrad_plan(const p3d_conv_desc* d, int32_t operands, int32_t* out) {
+    P3D_REQUIRE(d && out && operands >= 0 && operands < 128, "fx_wgrad_plan: null argument, or operand bits beyond bit 6");
+    P3D_REQUIRE(fused_desc_ok(d), "fx_wgrad_plan: malformed descriptor");
+    return fx_wgrad_plan_record(d, operands, out);
 }
 
 // Inference with folded BatchNorm (include/p3d_hip.h): the fold of a whole network in one launch, and the forward on the folded images with the inference epilogue.

@@ -1202,7 +1202,9 @@ static ConvRoute conv_route(FxPass pass, const p3d_conv_desc* d, int masks /* fa
     else if (fx_any_enabled() && any_ok(pass, d)) r.family = ConvRoute::X3_RAGGED;
     if (r.family == ConvRoute::FP32_MFMA) return r;
     const bool ragged = r.family == ConvRoute::X3_RAGGED || r.family == ConvRoute::X3_MASKED_RAGGED;
-    r.x3_bytes = pass == FX_WGRAD ? (size_t)fx_wgrad_splits(d, false, ragged) * d->K * d->C * d->R * d->S * sizeof(float) : fx_workspace(pass, d, ragged);
+    FxWgradOperands fp32_fed{};
+    fp32_fed.ragged = ragged;
+    r.x3_bytes = pass == FX_WGRAD ? fx_wgrad_plan(d, fp32_fed).slab_bytes : fx_workspace(pass, d, ragged);
     if (pass != FX_WGRAD && workspace_bytes < r.x3_bytes) return ConvRoute{ConvRoute::FP32_MFMA, 0};
     return r;
 }
@@ -1431,13 +1433,18 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
     if (int32_t e = validate(d)) return e;
     P3D_REQUIRE(dy && x && dw, "conv2d_wgrad: null tensor");
     ProfScope ps(2, d, (hipStream_t)stream);
-    const bool masked = mask_in || mult;
-    WgradPlan pl = plan_wgrad(d, masked);
     // (a short workspace does not move the route: see conv_route)
     const ConvRoute route = conv_route(FX_WGRAD, d, (mask_in != nullptr) + (mult != nullptr), false, false, aligned16(dy, x, workspace, mask_in, mult), workspace_bytes);
-    const bool fx = route.family != ConvRoute::FP32_MFMA;
-    if (fx) { pl.splits = fx_wgrad_splits(d, false, route.family == ConvRoute::X3_RAGGED || route.family == ConvRoute::X3_MASKED_RAGGED); pl.tapm = d->R * d->S > 1; }      // slabs [split][k][tap][c]: the tap-major columns of wgrad_reduce_tapm_kernel
-    fx_count(fx ? 2 : 5, d);
+    if (route.family != ConvRoute::FP32_MFMA) {
+        // the x3 kernels' 32-bit byte offsets span whole tensors (fx_applies keeps both under 2^29 elements: this holds the route to it)
+        P3D_REQUIRE((int64_t)d->N * d->C * d->H * d->W < (1ll << 29) && (int64_t)d->N * d->K * d->Ho * d->Wo < (1ll << 29), "conv2d_wgrad: a tensor exceeds 2 GiB");
+        fx_count(2, d);
+        const FxFuse f = route_fuse(route, mult, mask_in);
+        return fx_conv_wgrad(d, dy, x, dw, d->accumulate, workspace, workspace_bytes, &f, "conv2d_wgrad", (hipStream_t)stream);
+    }
+    fx_count(5, d);
+    const bool masked = mask_in || mult;
+    const WgradPlan pl = plan_wgrad(d, masked);
     const size_t need = (size_t)pl.splits * d->K * d->C * d->R * d->S * sizeof(float);
     if (!workspace || workspace_bytes < need) {
         set_error("conv2d_wgrad: workspace %zu B < required %zu B", workspace_bytes, need);
@@ -1458,15 +1465,12 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
         wv = 1;
         if (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0 && aligned16(x, mask_in)) wv = 2;
     }
-    if (fx) {
-        const FxFuse f = route_fuse(route, mult, mask_in);
-        if (int32_t e = fx_conv_wgrad_slabs(d, dy, x, (float*)workspace, pl.splits, &f, (hipStream_t)stream)) return e;
-    }
-    else { launch_igemm<MODE_WGRAD>(pl.cfg, pl.tapm, masked, p, pl.splits, (hipStream_t)stream, wv); last_set(LAST_Y_MEANS, Y_SLABS); }
+    launch_igemm<MODE_WGRAD>(pl.cfg, pl.tapm, masked, p, pl.splits, (hipStream_t)stream, wv);
+    last_set(LAST_Y_MEANS, Y_SLABS);
     if (int32_t e = check_launch("conv2d_wgrad")) return e;
     int32_t finish = 0;
     const int32_t e = wgrad_finish(d, (float*)workspace, pl.splits, pl.tapm, dw, (hipStream_t)stream, &finish);
-    if (!fx) last_or(LAST_FINISH, finish);
+    last_or(LAST_FINISH, finish);
     return e;
 }
 

@@ -146,8 +146,6 @@ int fx_partial_rows(FxPass pass, const p3d_conv_desc* d);                       
 bool fx_dgrad_has_dead_classes(const p3d_conv_desc* d);
 int32_t fx_dgrad_zero_dead_classes(const p3d_conv_desc* d, float* dx, hipStream_t st);      // zero-fills dx when the call does not accumulate and leaves such pixels untouched
 bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d);      // stride 1 and no split-K: FxFuse::acc_src is honoured
-int fx_wgrad_splits(const p3d_conv_desc* d, bool images = false, bool ragged = false);      // images: dy AND x arrive as images (the slab count of fx_wgrad_two_taps layers differs)
-int fx_wgrad_two_taps(const p3d_conv_desc* d, bool images);      // taps per column tile: 0 (one-tap tiles), 2 or 3
 int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, const float* bias, float* y, void* workspace, size_t workspace_bytes,
                     const FxFuse* fuse, hipStream_t st);
 int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, float* dx, void* workspace, size_t workspace_bytes, const FxFuse* fuse,
@@ -160,7 +158,33 @@ int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_f
 int32_t fx_build_weight_images_batched(const void* jobs, int njobs, int blocks, hipStream_t st);      // jobs: device array of {w, fwd, bwd, K, C, RS, pad} (40 B each)
 // eval-mode BatchNorm folded into forward weight images (p3d_fx_fold_bn_images): jobs = device array of p3d_fold_job
 int32_t fx_fold_bn_images(const void* jobs, int njobs, int blocks, hipStream_t st);
-int32_t fx_conv_wgrad_slabs(const p3d_conv_desc* d, const float* dy, const float* x, float* slabs, int splits, const FxFuse* fuse, hipStream_t st);
+// The weight gradient.  fx_wgrad_plan is the single description of a call, derived from the descriptor and from the kinds of its operands -- what the FxFuse HOLDS (null:
+// two fp32 operands on aligned maps): the workspace queries, fx_conv_wgrad and the test hook p3d_fx_wgrad_plan all read it, so the slab count, the grid and the kernel
+// cannot disagree.  Everything but `ok` is filled for any operands -- a query asks before an operand exists.
+enum : int { FX_WG_ALIGNED = 0, FX_WG_ANY = 1, FX_WG_ANY_MASKED = 2, FX_WG_ANY_IMG = 3 };
+struct FxWgradOperands { bool aimg, bimg, pm, em, rows, ragged; };      // dy / x is an image; dy / x has a per-pixel factor; the images are row images; any map width
+struct FxWgradPlan {
+    bool ok;                // an instance takes this combination of operands (fx_wgrad_operands_ok); fx_conv_wgrad refuses the others with P3D_EINVAL
+    int family;             // the kernel: FX_WG_ALIGNED fx_wgrad_kernel; FX_WG_ANY, _ANY_MASKED, _ANY_IMG fx_wgrad_any_kernel, _any_masked_kernel, _any_img_kernel
+    bool aimg, bimg, masked;        // FX_WG_ALIGNED: the template arguments of fx_wgrad_kernel<aimg, bimg, masked, taps, rows>; 0 for the other families
+    int taps;
+    bool rows;
+    int tile_taps;          // filter taps per column tile: 0 (one tap per block), 2 or 3 (image-fed multi-tap layers with 64 input channels), 8 (the stem)
+    int splits, spb;        // slabs the pixel reduction is cut into, and K steps (16 pixels each) per slab
+    dim3 grid;
+    int order;              // FxWgradParams::order
+    size_t slab_bytes;      // `splits` slabs of [K][taps][C] floats: the workspace of the call
+    bool tapm;              // a slab's columns are tap-major (wgrad_finish transposes them into the weight's order)
+};
+FxWgradPlan fx_wgrad_plan(const p3d_conv_desc* d, const FxWgradOperands& o);
+inline FxWgradPlan fx_wgrad_plan(const p3d_conv_desc* d, const FxFuse* f) {
+    return fx_wgrad_plan(d, f ? FxWgradOperands{f->dy_img != nullptr, f->x_img != nullptr, f->pmask != nullptr, f->emask != nullptr, f->rows != 0, f->ragged != 0} : FxWgradOperands{});
+}
+int32_t fx_wgrad_plan_record(const p3d_conv_desc* d, int operands, int32_t* out);      // the test hook p3d_fx_wgrad_plan (include/p3d_hip.h)
+// plan -> workspace check ("<entry>: workspace %zu B < required %zu B", P3D_EWORKSPACE) -> slabs -> wgrad_finish: dw = (or +=, by `accumulate`) the weight gradient.
+// dy / x: the fp32 operands, ignored where the FxFuse holds the image.
+int32_t fx_conv_wgrad(const p3d_conv_desc* d, const float* dy, const float* x, float* dw, int accumulate, void* workspace, size_t workspace_bytes, const FxFuse* fuse,
+                      const char* entry, hipStream_t st);
 // Pre-split activation images: a fp32 NCHW tensor [N][C][HW] (C % 16 == 0, HW % 4 == 0) as three bf16 planes [N][C/16][HW][16] (hi + mid + lo == value exactly):
 // what the x3 kernels stage into LDS with plain 16-B copies.  mode 0: the tensor itself; 1: relu(x * sc + sh) with the table's constants per channel;
 // 2: A * (masked ? g * [c * sc + sh > 0] : g) + B * c + K (x = g, x2 = c): the BatchNorm-backward map.

@@ -2197,11 +2197,15 @@ bool fx_masked_applies(FxPass pass, const p3d_conv_desc* d, bool ragged) {
     static const int min_m[3] = {64, 64, 96};          // FX_FWD, FX_DGRAD, FX_WGRAD
     return on && fx_applies(pass, d, min_m[pass], ragged);
 }
-// FX_WGRAD: slab bytes for the larger of the two split counts (fp32- or image-fed x): what a caller reserves before it knows which
+// FX_WGRAD: the slabs of the larger of the two plans (fp32- or image-fed): what a caller reserves before it knows which
 size_t fx_workspace(FxPass pass, const p3d_conv_desc* d, bool ragged) {
     if (pass != FX_WGRAD) return fx_plan(d, pass == FX_DGRAD, ragged).workspace;
-    const int a = fx_wgrad_splits(d, false, ragged), b = fx_wgrad_splits(d, true, ragged);
-    return (size_t)(a > b ? a : b) * d->K * d->C * d->R * d->S * sizeof(float);
+    FxWgradOperands o{};
+    o.ragged = ragged;
+    const size_t a = fx_wgrad_plan(d, o).slab_bytes;
+    o.aimg = o.bimg = true;
+    const size_t b = fx_wgrad_plan(d, o).slab_bytes;
+    return a > b ? a : b;
 }
 int fx_partial_rows(FxPass pass, const p3d_conv_desc* d) { return fx_plan(d, pass == FX_DGRAD).partial_rows; }
 
@@ -2617,7 +2621,7 @@ bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d) { return d->stride
 // 144-tile classes and 3 % on the regressor; other tile counts aim at one full round of three blocks per CU.
 // image-fed weight gradients of 64-input-channel multi-tap layers pack two taps into a column tile (fx_wgrad_kernel<.., TAPS 2>)
 // (returns the taps per column tile: 0 = the ordinary one-tap tiles, 2, or 3 when the output channels fit half an A image too)
-int fx_wgrad_two_taps(const p3d_conv_desc* d, bool images) {
+static int fx_wgrad_two_taps(const p3d_conv_desc* d, bool images) {
     if (!images || d->C != 64 || d->R * d->S <= 1 || (d->Wo & 15)) return 0;
     return d->K <= 64 ? 3 : 2;
 }
@@ -2625,8 +2629,8 @@ int fx_wgrad_two_taps(const p3d_conv_desc* d, bool images) {
 // fp32-MFMA plan (plan_wgrad, p3d_conv.hip).  A slab is one chain of 6 dependent fp32 accumulations per K step; at the small batches where the floor binds, 32 steps leave a
 // whole reduction in one or two slabs on a handful of blocks, and its rounding error at several times that of the fp32-MFMA kernel, which sums many short slabs
 // (profiles/train_anysize.md).  At batch 64 the floor binds for one class only (four tiles at 33 x 33).
-int fx_wgrad_splits(const p3d_conv_desc* d, bool images, bool ragged) {
-    const int tt = ragged ? 0 : fx_wgrad_two_taps(d, images);          // (the ragged kernels, image-fed or not, run one tap per block: one plan for both)
+// tt: the taps per column tile (the ragged kernels, image-fed or not, run one tap per block: 0)
+static int fx_wgrad_splits(const p3d_conv_desc* d, int tt, bool ragged) {
     const int64_t tiles = tt ? ceil_div(d->K, FX_BM) * ceil_div(d->R * d->S, tt) : ceil_div(d->K, FX_BM) * ceil_div(d->C, FX_BN) * d->R * d->S;
     const int64_t total = ragged ? ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BK) : (int64_t)d->N * (d->Ho * d->Wo / FX_BK);
     int64_t target;
@@ -2651,68 +2655,100 @@ int fx_wgrad_splits(const p3d_conv_desc* d, bool images, bool ragged) {
     return (int)ceil_div(total, spb);
 }
 
-// slabs [split][k][tap][c]
-int32_t fx_conv_wgrad_slabs(const p3d_conv_desc* d, const float* dy, const float* x, float* slabs, int splits, const FxFuse* fuse, hipStream_t st) {
+// Which operands an instance takes: the one validity rule of a weight-gradient call.  Aligned maps: a factor (dw = wgrad(dy * pmask, x * emask)) goes with an fp32
+// operand -- an image carries its own --, never with two images; row images feed the dense image-fed instances; an image needs its channel count in steps of 16, and an
+// x image a dy image beside it.  Any map width: two fp32 operands, with both factors of a partial convolution or neither, or two images without factors, their channel
+// counts in steps of 16 and the map at least one K step (16 pixels); `rows` is not looked at there.
+constexpr bool fx_wgrad_operands_ok(bool ragged, bool aimg, bool bimg, bool pm, bool em, bool rows, int K, int C, int ohw) {
+    if (ragged) return aimg == bimg && pm == em && !(aimg && pm) && !(aimg && ((K & 15) || (C & 15) || ohw < FX_BK));
+    if ((pm || em) && (pm == aimg || em == bimg || (aimg && bimg))) return false;
+    if (rows && (!aimg || pm || em)) return false;
+    return !((aimg && (K & 15)) || (bimg && (C & 15)) || (bimg && !aimg));
+}
+
+// Every compiled weight-gradient kernel, once: X(AIMG, BIMG, MASKED, TAPS, ROWS) of fx_wgrad_kernel (the last two are the stem's, fx_stem_wgrad) and X(family, kernel)
+// of the three for any map width.  fx_wgrad_instance is the only place that names one.
+#define P3D_FX_WGRAD_INSTANCES(X)                                                                                                    \
+    X(1, 1, 0, 3, 1) X(1, 1, 0, 3, 0) X(1, 1, 0, 2, 1) X(1, 1, 0, 2, 0) X(1, 0, 1, 0, 0) X(0, 0, 1, 0, 0) X(1, 1, 0, 0, 1) X(1, 1, 0, 0, 0) \
+    X(1, 0, 0, 0, 1) X(1, 0, 0, 0, 0) X(0, 0, 0, 0, 0) X(0, 1, 1, 1, 0) X(0, 1, 0, 1, 0)
+#define P3D_FX_WGRAD_ANY_INSTANCES(X) X(FX_WG_ANY_IMG, fx_wgrad_any_img_kernel) X(FX_WG_ANY_MASKED, fx_wgrad_any_masked_kernel) X(FX_WG_ANY, fx_wgrad_any_kernel)
+using FxWgradKernel = void (*)(const FxWgradParams);
+constexpr FxWgradKernel fx_wgrad_instance(int family, bool aimg, bool bimg, bool masked, int taps, bool rows) {
+#define P3D_X(FAMILY, KERNEL) if (family == FAMILY) return KERNEL;
+    P3D_FX_WGRAD_ANY_INSTANCES(P3D_X)
+#undef P3D_X
+#define P3D_X(AIMG, BIMG, MASKED, TAPS, ROWS) if (aimg == AIMG && bimg == BIMG && masked == MASKED && taps == TAPS && rows == ROWS) return fx_wgrad_kernel<AIMG, BIMG, MASKED, TAPS, ROWS>;
+    if (family == FX_WG_ALIGNED) { P3D_FX_WGRAD_INSTANCES(P3D_X) }
+#undef P3D_X
+    return nullptr;
+}
+// The instance of an operand combination the rule above admits: on aligned maps the operands ARE the template values, with the taps per column tile; at any map width
+// one kernel per kind of operand.  Every such combination has its instance, on each column tile fx_wgrad_two_taps can ask for; and so have the stem's two.
+constexpr int fx_wgrad_family(bool ragged, bool aimg, bool masked) { return !ragged ? FX_WG_ALIGNED : aimg ? FX_WG_ANY_IMG : masked ? FX_WG_ANY_MASKED : FX_WG_ANY; }
+constexpr bool fx_wgrad_covered() {
+    for (int c = 0; c < 64; ++c) {
+        const bool ragged = c & 1, aimg = c & 2, bimg = c & 4, pm = c & 8, em = c & 16, rows = c & 32;
+        if (!fx_wgrad_operands_ok(ragged, aimg, bimg, pm, em, rows, 64, 64, 256)) continue;
+        for (int tt = 0; tt <= 3; tt += tt ? 1 : 2) {
+            if (tt && !(aimg && bimg && !pm && !em && !ragged)) continue;          // (fx_wgrad_two_taps: image-fed dense launches only)
+            if (!fx_wgrad_instance(fx_wgrad_family(ragged, aimg, pm || em), aimg, bimg, pm || em, tt, rows)) return false;
+        }
+    }
+    return fx_wgrad_instance(FX_WG_ALIGNED, false, true, true, 1, false) && fx_wgrad_instance(FX_WG_ALIGNED, false, true, false, 1, false);
+}
+static_assert(fx_wgrad_covered(), "the weight-gradient plan can name an instance that is not compiled");
+
+// The single description of a weight-gradient call (p3d_fx.h), from the descriptor and the kinds of its operands
+FxWgradPlan fx_wgrad_plan(const p3d_conv_desc* d, const FxWgradOperands& o) {
+    const bool ragged = o.ragged, aimg = o.aimg, bimg = o.bimg, masked = o.pm || o.em;
+    const int RS = d->R * d->S, tt = ragged ? 0 : fx_wgrad_two_taps(d, aimg && bimg && !masked);
+    FxWgradPlan pl{};
+    pl.ok = fx_wgrad_operands_ok(ragged, aimg, bimg, o.pm, o.em, o.rows, d->K, d->C, d->Ho * d->Wo);
+    pl.family = fx_wgrad_family(ragged, aimg, masked);
+    if (!ragged) { pl.aimg = aimg; pl.bimg = bimg; pl.masked = masked; pl.taps = tt; pl.rows = o.rows; }
+    pl.tile_taps = tt;
+    pl.splits = fx_wgrad_splits(d, tt, ragged);
+    // K steps: 16 consecutive output pixels of one image, or (any map width) of the flat pixel index, the last one partial
+    pl.spb = (int)ceil_div(ragged ? ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BK) : (int64_t)d->N * (d->Ho * d->Wo / FX_BK), pl.splits);
+    pl.grid = tt ? dim3((unsigned)ceil_div(RS, tt), (unsigned)ceil_div(d->K, FX_BM), (unsigned)pl.splits)
+                 : dim3((unsigned)ceil_div(d->C, FX_BN), (unsigned)ceil_div(d->K, FX_BM), (unsigned)(pl.splits * RS));
+    pl.order = fx_wgrad_order(d);
+    pl.slab_bytes = (size_t)pl.splits * d->K * d->C * RS * sizeof(float);
+    pl.tapm = RS > 1;
+    return pl;
+}
+
+// the only launch of a weight-gradient kernel in the library (a plan that is `ok`, or the stem's: fx_wgrad_covered has its instance)
+static void fx_launch_wgrad(const FxWgradParams& p, const FxWgradPlan& pl, hipStream_t st) {
+    hipLaunchKernelGGL(fx_wgrad_instance(pl.family, pl.aimg, pl.bimg, pl.masked, pl.taps, pl.rows), pl.grid, dim3(256), 0, st, p);
+    prof_kernel_done(st);
+}
+
+// dw (=|+= by `accumulate`) of one convolution: plan -> workspace check (in the name of `entry`) -> slabs [split][k][tap][c] -> wgrad_finish
+int32_t fx_conv_wgrad(const p3d_conv_desc* d, const float* dy, const float* x, float* dw, int accumulate, void* workspace, size_t workspace_bytes, const FxFuse* fuse,
+                      const char* entry, hipStream_t st) {
+    const FxWgradPlan pl = fx_wgrad_plan(d, fuse);
+    if (!workspace || workspace_bytes < pl.slab_bytes) { set_error("%s: workspace %zu B < required %zu B", entry, workspace_bytes, pl.slab_bytes); return P3D_EWORKSPACE; }
+    if (!pl.ok) {
+        set_error("fx_conv_wgrad: no instance takes these operands (a factor goes with an fp32 operand, row images feed dense image-fed launches, an image needs channel counts in "
+                  "steps of 16 and an x image a dy image; any map width: fp32 operands with both factors or neither, or two such images of 16 pixels or more without factors)");
+        return P3D_EINVAL;
+    }
     FxWgradParams p{};
-    p.DY = dy; p.X = x; p.slabs = slabs;
+    p.DY = dy; p.X = x; p.slabs = (float*)workspace;
     p.N = d->N; p.K = d->K; p.C = d->C; p.Hi = d->H; p.Wi = d->W; p.OH = d->Ho; p.OW = d->Wo; p.R = d->R; p.S = d->S;
     p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    p.nsplit = splits;
-    p.spb = (int)ceil_div((int64_t)d->N * (d->Ho * d->Wo / FX_BK), splits);
-    p.order = fx_wgrad_order(d);
-    if (fuse && fuse->ragged) {          // any map width: K steps over the flat pixel index, the last one partial (fx_wgrad_any_kernel)
-        const bool imgs = fuse->dy_img && fuse->x_img;          // both operands as activation images (fx_wgrad_any_img_kernel), or both fp32
-        if ((fuse->dy_img != nullptr) != (fuse->x_img != nullptr) || (fuse->pmask != nullptr) != (fuse->emask != nullptr) || (imgs && fuse->pmask) ||
-            (imgs && ((d->K & 15) || (d->C & 15) || d->Ho * d->Wo < FX_BK))) {
-            set_error("fx_conv_wgrad: the ragged weight gradient takes fp32 operands (with both factors of a partial convolution or neither) or two images (channel counts in "
-                      "steps of 16, maps of at least 16 pixels, no factors)"); return P3D_EINVAL;
-        }
-        p.amask = fuse->pmask; p.bmask = fuse->emask;
-        p.spb = (int)ceil_div(ceil_div((int64_t)d->N * d->Ho * d->Wo, FX_BK), splits);
-        const dim3 grid((unsigned)ceil_div(d->C, FX_BN), (unsigned)ceil_div(d->K, FX_BM), (unsigned)(splits * d->R * d->S));
-        if (imgs) {
-            p.DYimg = (const unsigned char*)fuse->dy_img; p.dy_plane = (size_t)d->N * d->K * d->Ho * d->Wo * 2;
-            p.Ximg = (const unsigned char*)fuse->x_img; p.x_plane = (size_t)d->N * d->C * d->H * d->W * 2;
-            hipLaunchKernelGGL(fx_wgrad_any_img_kernel, grid, dim3(256), 0, st, p);
-        } else if (fuse->pmask) hipLaunchKernelGGL(fx_wgrad_any_masked_kernel, grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(fx_wgrad_any_kernel, grid, dim3(256), 0, st, p);
-        prof_kernel_done(st);
-        return check_launch("fx_conv_wgrad");
-    }
-    bool aimg = false, bimg = false, masked = false;
+    p.nsplit = pl.splits; p.spb = pl.spb; p.order = pl.order;
     if (fuse) {
-        if (fuse->dy_img) { aimg = true; p.DYimg = (const unsigned char*)fuse->dy_img; p.dy_plane = (size_t)d->N * d->K * d->Ho * d->Wo * 2; }
-        if (fuse->x_img) { bimg = true; p.Ximg = (const unsigned char*)fuse->x_img; p.x_plane = (size_t)d->N * d->C * d->H * d->W * 2; }
-        if (fuse->pmask || fuse->emask) {
-            // dw = wgrad(dy * pmask, x * emask): a factor goes with an fp32 operand (an image carries its own)
-            if ((fuse->pmask != nullptr) == aimg || (fuse->emask != nullptr) == bimg || (aimg && bimg)) {
-                set_error("fx_conv_wgrad: a partial-convolution factor belongs to an fp32 operand (pmask: dy, emask: x)"); return P3D_EINVAL;
-            }
-            masked = true; p.amask = fuse->pmask; p.bmask = fuse->emask;
-        }
+        if (fuse->dy_img) { p.DYimg = (const unsigned char*)fuse->dy_img; p.dy_plane = (size_t)d->N * d->K * d->Ho * d->Wo * 2; }
+        if (fuse->x_img) { p.Ximg = (const unsigned char*)fuse->x_img; p.x_plane = (size_t)d->N * d->C * d->H * d->W * 2; }
+        p.amask = fuse->pmask; p.bmask = fuse->emask;
     }
-    const bool rows = fuse && fuse->rows;           // the image operands are fp32 row images
-    if (rows && (!aimg || masked)) { set_error("fx_conv_wgrad: row images feed the dense image-fed instances only"); return P3D_EINVAL; }
-    if ((aimg && (d->K & 15)) || (bimg && (d->C & 15)) || (bimg && !aimg)) { set_error("fx_conv_wgrad: image operands need channel counts in steps of 16 (and a dy image beside an x image)"); return P3D_EINVAL; }
-    const dim3 grid((unsigned)ceil_div(d->C, FX_BN), (unsigned)ceil_div(d->K, FX_BM), (unsigned)(splits * d->R * d->S));
-    if (const int tt = fx_wgrad_two_taps(d, aimg && bimg && !masked)) {
-        const dim3 tg((unsigned)ceil_div(d->R * d->S, tt), (unsigned)ceil_div(d->K, FX_BM), (unsigned)splits);
-        if (tt == 3 && rows) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 3, true>), tg, dim3(256), 0, st, p);
-        else if (tt == 3) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 3>), tg, dim3(256), 0, st, p);
-        else if (rows) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 2, true>), tg, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 2>), tg, dim3(256), 0, st, p);
-        prof_kernel_done(st);
-        return check_launch("fx_conv_wgrad");
-    }
-    if (masked && aimg) hipLaunchKernelGGL((fx_wgrad_kernel<true, false, true>), grid, dim3(256), 0, st, p);
-    else if (masked) hipLaunchKernelGGL((fx_wgrad_kernel<false, false, true>), grid, dim3(256), 0, st, p);
-    else if (aimg && bimg && rows) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false, 0, true>), grid, dim3(256), 0, st, p);
-    else if (aimg && bimg) hipLaunchKernelGGL((fx_wgrad_kernel<true, true, false>), grid, dim3(256), 0, st, p);
-    else if (aimg && rows) hipLaunchKernelGGL((fx_wgrad_kernel<true, false, false, 0, true>), grid, dim3(256), 0, st, p);
-    else if (aimg) hipLaunchKernelGGL((fx_wgrad_kernel<true, false, false>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((fx_wgrad_kernel<false, false, false>), grid, dim3(256), 0, st, p);
-    prof_kernel_done(st);
-    return check_launch("fx_conv_wgrad");
+    fx_launch_wgrad(p, pl, st);
+    if (int32_t e = check_launch("fx_conv_wgrad")) return e;
+    p3d_conv_desc dw_desc = *d;
+    dw_desc.accumulate = accumulate;
+    return wgrad_finish(&dw_desc, p.slabs, pl.splits, pl.tapm, dw, st);
 }
 
 
@@ -2847,9 +2883,21 @@ static int fx_stem_splits(int N, int H, int W) {
     const int64_t spb = ceil_div(total, splits);
     return (int)ceil_div(total, spb);
 }
+// The stem's weight gradient as a plan: fx_wgrad_kernel<false, true, MASKED, TAPS 1> over the 16 x 16 (tap, channel) columns, two tiles of eight taps; its own split
+// rule above and its own finish (fx_stem_dw_kernel)
+static FxWgradPlan fx_stem_wgrad_plan(int N, int H, int W, int K, bool masked) {
+    FxWgradPlan pl{};
+    pl.ok = true; pl.family = FX_WG_ALIGNED; pl.bimg = true; pl.masked = masked; pl.taps = 1; pl.tile_taps = 8;
+    pl.splits = fx_stem_splits(N, H, W);
+    pl.spb = (int)ceil_div((int64_t)N * ((H / 2) * (W / 2) / FX_BK), pl.splits);
+    pl.grid = dim3(2, (unsigned)ceil_div(K, FX_BM), (unsigned)pl.splits);
+    pl.slab_bytes = (size_t)pl.splits * K * 256 * sizeof(float);
+    pl.tapm = true;
+    return pl;
+}
 size_t fx_stem_workspace(int N, int H, int W, int K) {
     const size_t w2 = align256((size_t)K * 256 * sizeof(float));
-    const size_t slabs = (size_t)fx_stem_splits(N, H, W) * K * 256 * sizeof(float);
+    const size_t slabs = fx_stem_wgrad_plan(N, H, W, K, false).slab_bytes;
     return w2 > slabs ? w2 : slabs;
 }
 
@@ -2899,6 +2947,25 @@ int32_t fx_stem_fwd(const void* x_img, const void* wimg, float* y, const float* 
     return check_launch("fx_stem_fwd");
 }
 
+// The plan as the record of the test hook p3d_fx_wgrad_plan (include/p3d_hip.h): fx_wgrad_plan for the operands the bits describe, or with bit 6 the
+// stem's, the descriptor's N, C, H, W, K being its arguments
+int32_t fx_wgrad_plan_record(const p3d_conv_desc* d, int operands, int32_t* out) {
+    FxWgradPlan pl{};
+    if (operands & 64) {
+        if ((operands & ~(64 | 8)) || !fx_stem_applies(d->N, d->C, d->H, d->W, d->K)) { set_error("fx_wgrad_plan: not a stem the x3 kernels take, or operand bits the stem has not"); return P3D_EINVAL; }
+        pl = fx_stem_wgrad_plan(d->N, d->H, d->W, d->K, (operands & 8) != 0);
+    } else {
+        const FxWgradOperands o{(operands & 1) != 0, (operands & 2) != 0, (operands & 8) != 0, (operands & 16) != 0, (operands & 4) != 0, (operands & 32) != 0};
+        if (!fx_applies(FX_WGRAD, d, 32, o.ragged)) { set_error("fx_wgrad_plan: shape outside the x3 kernels"); return P3D_EINVAL; }
+        pl = fx_wgrad_plan(d, o);
+        if (!pl.ok) { set_error("fx_wgrad_plan: no instance takes these operands"); return P3D_EINVAL; }
+    }
+    const int32_t rec[P3D_FX_WGRAD_PLAN_FIELDS] = {pl.family, pl.aimg, pl.bimg, pl.masked, pl.taps, pl.rows, pl.tile_taps, pl.splits, pl.spb, (int32_t)pl.grid.x, (int32_t)pl.grid.y,
+                                                  (int32_t)pl.grid.z, pl.order, pl.tapm, (int32_t)(pl.slab_bytes & 0xFFFFFFFFu), (int32_t)(pl.slab_bytes >> 32)};
+    for (int i = 0; i < P3D_FX_WGRAD_PLAN_FIELDS; ++i) out[i] = rec[i];
+    return P3D_OK;
+}
+
 // dw [K][Cin][7][7] (=|+=) from dy [N][K][H/2][W/2] (fp32) and the space-to-depth image of x
 int32_t fx_stem_wgrad(const float* dy, const float* mult, const void* x_img, float* dw, int N, int Cin, int H, int W, int K, int accumulate, void* workspace,
                       size_t workspace_bytes, hipStream_t st) {
@@ -2907,14 +2974,10 @@ int32_t fx_stem_wgrad(const float* dy, const float* mult, const void* x_img, flo
     const int H2 = H / 2, W2 = W / 2;
     p.DY = dy; p.Ximg = (const unsigned char*)x_img; p.x_plane = (size_t)N * H2 * W2 * 32; p.slabs = (float*)workspace;
     p.N = N; p.K = K; p.C = 256; p.Hi = H2; p.Wi = W2; p.OH = H2; p.OW = W2; p.R = 4; p.S = 4; p.stride = 1; p.pad = 2; p.dil = 1;
-    p.nsplit = fx_stem_splits(N, H, W);
-    p.spb = (int)ceil_div((int64_t)N * (H2 * W2 / FX_BK), p.nsplit);
-    if (mult) {      // partial convolution: dw = wgrad(dy * mult, x * mask_in); the image holds x * mask_in, dy is scaled on its way into LDS
-        p.amask = mult;
-        hipLaunchKernelGGL((fx_wgrad_kernel<false, true, true, 1>), dim3(2, (unsigned)ceil_div(K, FX_BM), (unsigned)p.nsplit), dim3(256), 0, st, p);
-    } else
-        hipLaunchKernelGGL((fx_wgrad_kernel<false, true, false, 1>), dim3(2, (unsigned)ceil_div(K, FX_BM), (unsigned)p.nsplit), dim3(256), 0, st, p);
-    prof_kernel_done(st);
+    const FxWgradPlan pl = fx_stem_wgrad_plan(N, H, W, K, mult != nullptr);
+    p.nsplit = pl.splits; p.spb = pl.spb;
+    p.amask = mult;      // partial convolution: dw = wgrad(dy * mult, x * mask_in); the image holds x * mask_in, dy is scaled on its way into LDS
+    fx_launch_wgrad(p, pl, st);
     hipLaunchKernelGGL(fx_stem_dw_kernel, dim3((unsigned)K, 4), dim3(1024), 0, st, (const float*)workspace, p.nsplit, dw, K, Cin, accumulate);
     return check_launch("fx_stem_wgrad");
 }

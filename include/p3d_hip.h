@@ -383,6 +383,22 @@ size_t p3d_fx_conv_fused_workspace_bytes(int32_t pass, const p3d_conv_desc* d, i
 int32_t p3d_fx_conv_fused_partial_rows(int32_t pass, const p3d_conv_desc* d);
 int32_t p3d_fx_conv_fused(int32_t pass, const p3d_conv_desc* d, const p3d_fx_fuse* f, const float* src, const float* w, const float* bias, float* out, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* TEST HOOK (tests/test_wgrad_plan_host.py; nothing in the package calls it), host-only: how the x3 kernels would run the weight gradient of d -- the plan every
+ * weight-gradient entry, the block executor and the workspace queries read -- under the p3d_fx_tune settings in force.  Nothing is launched and no operand exists;
+ * `operands` says what they would be:
+ *   bit 0  dy is an activation image      bit 1  x is one      bit 2  the images are row images (p3d_fx_row_image)
+ *   bit 3  dy has a per-pixel factor (a partial convolution's mult)      bit 4  x has one (mask_in)      bit 5  the kernels for any map width
+ *   bit 6  d describes the stem instead (p3d_stem_wgrad: its N, C = Cin, H, W, K are read); bit 3 beside it: p3d_stem_wgrad_masked; no other bit
+ * out receives P3D_FX_WGRAD_PLAN_FIELDS int32:
+ *   [0] kernel family: 0 fx_wgrad_kernel (aligned maps), 1 fx_wgrad_any_kernel, 2 fx_wgrad_any_masked_kernel, 3 fx_wgrad_any_img_kernel
+ *   [1] AIMG   [2] BIMG   [3] MASKED   [4] TAPS   [5] ROWS  -- the template arguments of fx_wgrad_kernel (0 for the other families)
+ *   [6] filter taps per column tile: 0 one tap per block, 2 / 3 image-fed multi-tap layers with 64 input channels, 8 the stem
+ *   [7] slabs the pixel reduction is cut into   [8] K steps (16 pixels) per slab   [9] grid.x   [10] grid.y   [11] grid.z   [12] block order (1: taps fastest)
+ *   [13] 1: the slabs' columns are tap-major   [14] slab bytes, low 32 bits   [15] high 32 bits
+ * Returns P3D_EINVAL, out untouched, for a malformed descriptor, a shape outside the weight-gradient rule of the x3 kernels (at 32 channels on either side, the least any
+ * caller asks for; with bit 5 the rule without its width clauses; the stem: p3d_stem_supported's rule) and for operands no instance takes. */
+#define P3D_FX_WGRAD_PLAN_FIELDS 16
+int32_t p3d_fx_wgrad_plan(const p3d_conv_desc* d, int32_t operands, int32_t* out);
 
 /* Inference with eval-mode BatchNorm folded into the convolutions (infer.py): s = gamma / sqrt(var + eps), w' = w * s, b' = beta - mean * s (+ s * conv bias).
  * p3d_fx_fold_bn_images: ONE launch for a table of jobs (device array of p3d_fold_job); per job kind 0 writes the forward weight image of w' over the input
