@@ -1,10 +1,12 @@
-"""ctypes binding of libp3d_hip.so (the C ABI declared in include/p3d_hip.h).
+"""ctypes binding of libp3d_hip.so.  include/p3d_hip.h is the only statement of the C ABI: its prototypes, structs and integer
+#defines are read from it here, once, at import.
 
 There is deliberately NO fallback: if the shared library is missing or a call fails, the
 caller gets a P3DError.  PyTorch is used only to own device memory and streams.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('P3D_LIB') or os.path.join(_HERE, 'csrc', 'libp3d_hip.so')   # P3D_LIB: A/B a tuning build
@@ -15,200 +17,105 @@ class P3DError(RuntimeError):
     pass
 
 
-class ConvDesc(ctypes.Structure):
-    """struct p3d_conv_desc"""
-    _fields_ = [(n, ctypes.c_int32) for n in
-                ('N', 'C', 'H', 'W', 'K', 'R', 'S', 'stride', 'pad', 'dil', 'Ho', 'Wo', 'c_total', 'c_offset',
-                 'accumulate', 'reserved')]
+# ---- the header reader ---------------------------------------------------------------------------------------------------------------------------------------------
+# The header is plain C of a regular shape: integer #defines, `typedef struct tag { members } name;` without nesting, and prototypes `ret name(args);` whose
+# parameters are all named.  Anything outside that shape raises P3DError with the declaration's text; no type ever defaults to int.
+_SCALARS = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float, 'double': ctypes.c_double}
+_POINTEES = set(_SCALARS) | {'void', 'char', 'unsigned char', 'uint8_t', 'uint32_t', 'uint64_t'}          # what a c_void_p may stand for
+_DECLARATOR = re.compile(r'(?P<base>\w[\w\s]*?)(?P<stars>[\s*]+)(?P<name>\w+)\s*(?:\[\s*(?P<count>\d+)\s*\])?')
+_STRUCT = re.compile(r'\btypedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;')
 
 
-class FoldJob(ctypes.Structure):
-    """struct p3d_fold_job (p3d_fx_fold_bn_images)"""
-    _fields_ = [(n, ctypes.c_void_p) for n in ('w', 'conv_bias', 'gamma', 'beta', 'mean', 'var', 'out', 'bias_out')] + \
-               [(n, ctypes.c_int32) for n in ('K', 'C', 'RS', 'c_offset', 'c_total', 'kind')] + [('eps', ctypes.c_float), ('reserved', ctypes.c_int32)]
+def _declarator(text, what):
+    """'const float* w[4]' -> ('float', True, 1, 'w', 4): base type without qualifiers, whether it was const, pointer depth, name, array length or None."""
+    m = _DECLARATOR.fullmatch(text.strip())
+    if not m:
+        raise P3DError('p3d_hip.h: cannot split %s' % what)
+    words = m.group('base').split()
+    base = ' '.join(w for w in words if w not in ('const', 'struct'))
+    return base, 'const' in words, m.group('stars').count('*'), m.group('name'), m.group('count') and int(m.group('count'))
 
 
-class FxFuse(ctypes.Structure):
-    """struct p3d_fx_fuse (p3d_fx_conv_fused, a test hook)"""
-    _fields_ = [(n, ctypes.c_void_p) for n in ('act_img', 'wimg', 'partial', 'ep_c', 'ep_tab', 'pmask', 'emask', 'acc_src', 'acc_mask', 'res')] + \
-               [(n, ctypes.c_int32) for n in ('rows', 'infer', 'relu', 'ragged')]
+def _ctype(base, const, stars, structs, what, member=False):
+    if not stars:
+        if base in _SCALARS:
+            return _SCALARS[base]
+        if base in structs and member:
+            return structs[base]
+    elif base == 'char' and const and stars == 1 and not member:
+        return ctypes.c_char_p
+    elif base in structs and stars == 1 and not member:
+        return ctypes.POINTER(structs[base])
+    elif base in _POINTEES or base in structs:
+        return ctypes.c_void_p
+    raise P3DError('p3d_hip.h: unknown type `%s%s` in %s' % (base, '*' * stars, what))
 
 
-_i32, _i64, _f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-_ptr, _sz = ctypes.c_void_p, ctypes.c_size_t
-_desc = ctypes.POINTER(ConvDesc)
+def _struct(name, body, structs):
+    fields = []
+    for decl in body.split(';'):
+        if not decl.strip():
+            continue
+        what = 'member `%s` of struct %s' % (' '.join(decl.split()), name)
+        first, *more = decl.split(',')
+        base, const, stars, field, count = _declarator(first, what)
+        declared = [(stars, field, count)]
+        for extra in more:                                                                 # `int32_t N, C, H, W;`: the later declarators carry their own stars
+            m = re.fullmatch(r'\s*(\**)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*', extra)
+            if not m:
+                raise P3DError('p3d_hip.h: cannot place %s' % what)
+            declared.append((len(m.group(1)), m.group(2), m.group(3) and int(m.group(3))))
+        for stars, field, count in declared:
+            t = _ctype(base, const, stars, structs, what, member=True)
+            fields.append((field, t if count is None else t * count))
+    return type(name, (ctypes.Structure,), {'_fields_': fields, '__doc__': 'struct %s of include/p3d_hip.h' % name})
 
-# name -> (restype, argtypes); must list every function of include/p3d_hip.h (tests/test_abi.py checks)
-SIGNATURES = {
-    'p3d_version': (_i32, []),
-    'p3d_last_error': (ctypes.c_char_p, []),
-    'p3d_conv2d_fwd': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_conv2d_fwd_workspace_bytes': (_sz, [_desc]),
-    'p3d_conv2d_bn_eval_fwd_workspace_bytes': (_sz, [_desc]),
-    'p3d_conv2d_bn_eval_fwd': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
-    'p3d_conv2d_dgrad_workspace_bytes': (_sz, [_desc]),
-    'p3d_conv2d_dgrad': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_conv2d_wgrad_workspace_bytes': (_sz, [_desc]),
-    'p3d_conv2d_wgrad': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_conv2d_bgrad': (_i32, [_ptr, _i32, _i32, _i32, _ptr, _i32, _ptr]),
-    'p3d_conv2d_bgrad_masked': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _ptr, _i32, _ptr]),
-    'p3d_block_supported': (_i32, [_ptr]),
-    'p3d_block_workspace_bytes': (_i32, [_ptr, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
-    'p3d_block_fwd': (_i32, [_ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_block_bwd': (_i32, [_ptr, _ptr, _ptr, _sz, _ptr, _sz, _ptr, _ptr]),
-    'p3d_fx_weight_image_bytes': (_i32, [_i32, _i32, _i32, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
-    'p3d_fx_weight_images': (_i32, [_ptr, _i32, _i32, _i32, _ptr, _ptr, _ptr]),
-    'p3d_fx_weight_images_batched': (_i32, [_ptr, _i32, _i32, _ptr]),
-    'p3d_fx_fold_bn_images': (_i32, [_ptr, _i32, _i32, _ptr]),
-    'p3d_fx_conv_fwd_infer_supported': (_i32, [_desc, _i32]),
-    'p3d_fx_conv_fwd_infer_workspace_bytes': (_sz, [_desc]),
-    'p3d_fx_conv_fwd_infer': (_i32, [_desc, _ptr, _ptr, _ptr, _sz, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_conv_fwd_infer_any_supported': (_i32, [_desc]),
-    'p3d_fx_conv_fwd_infer_any_workspace_bytes': (_sz, [_desc]),
-    'p3d_fx_conv_fwd_infer_any': (_i32, [_desc, _ptr, _ptr, _sz, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_conv_fwd_infer_masked_supported': (_i32, [_desc]),
-    'p3d_fx_conv_fwd_infer_masked': (_i32, [_desc, _ptr, _ptr, _sz, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_conv_fwd_infer_masked_any_supported': (_i32, [_desc]),
-    'p3d_fx_conv_fwd_infer_masked_any_workspace_bytes': (_sz, [_desc]),
-    'p3d_fx_conv_fwd_infer_masked_any': (_i32, [_desc, _ptr, _ptr, _sz, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _sz, _ptr]),
-    'p3d_stem_any_padded': (_i32, [_i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
-    'p3d_stem_any_supported': (_i32, [_i32] * 5),
-    'p3d_stem_image_any': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_stem_tail_infer_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_stem_tail_infer': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_hblock_workspace_bytes': (_i32, [_ptr, _ptr, _ptr]),
-    'p3d_hblock_fwd': (_i32, [_ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_hblock_bwd': (_i32, [_ptr, _ptr, _ptr, _sz, _ptr, _sz, _ptr, _ptr]),
-    'p3d_fx_act_image_bytes': (_sz, [_i32, _i32, _i32]),
-    'p3d_fx_act_image': (_i32, [_i32, _ptr, _ptr, _ptr, _i32, _ptr, _i32, _i32, _i32, _ptr]),
-    'p3d_fx_conv_img_workspace_bytes': (_sz, [_ptr, _i32]),
-    'p3d_fx_conv_img_supported': (_i32, [_ptr]),
-    'p3d_fx_conv_fwd_img': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_conv_dgrad_img': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_conv_wgrad_img': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_row_image_bytes': (_sz, [_i32, _i32, _i32]),
-    'p3d_fx_row_image': (_i32, [_i32, _ptr, _ptr, _ptr, _i32, _ptr, _i32, _i32, _i32, _ptr]),
-    'p3d_fx_conv_fwd_rows': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_conv_dgrad_rows': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_conv_wgrad_rows': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_block_image_bytes': (_sz, [_ptr, _i32, _i32, _i32]),
-    'p3d_fx_open_images': (_i32, [_i32, _ptr, _ptr, _ptr, _i32, ctypes.c_double] + [_ptr] * 12 + [_i32, _i32, _i32, _ptr]),
-    'p3d_x3_any_images_enable': (_i32, [_i32]),
-    'p3d_fx_conv_img_any_supported': (_i32, [_ptr]),
-    'p3d_fx_conv_img_any_workspace_bytes': (_sz, [_ptr, _i32]),
-    'p3d_fx_act_image_any': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _ptr]),
-    'p3d_fx_conv_fwd_img_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_conv_dgrad_img_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_conv_wgrad_img_any': (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_launch_log': (_i32, [ctypes.POINTER(_i32), _i32, _i32]),
-    'p3d_fx_conv_instances': (_i32, [ctypes.POINTER(_i32), _i32]),
-    'p3d_fx_conv_fused_workspace_bytes': (_sz, [_i32, _desc, _i32]),
-    'p3d_fx_conv_fused_partial_rows': (_i32, [_i32, _desc]),
-    'p3d_fx_conv_fused': (_i32, [_i32, _desc, ctypes.POINTER(FxFuse), _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
-    'p3d_fx_wgrad_plan': (_i32, [_desc, _i32, ctypes.POINTER(_i32)]),
-    'p3d_stem_supported': (_i32, [_i32] * 5),
-    'p3d_stem_image_bytes': (_sz, [_i32] * 3),
-    'p3d_stem_weight_image_bytes': (_sz, [_i32]),
-    'p3d_stem_workspace_bytes': (_sz, [_i32] * 4),
-    'p3d_stem_image': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_stem_weight_image': (_i32, [_ptr, _i32, _i32, _ptr, _ptr, _sz, _ptr]),
-    'p3d_stem_fwd': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_stem_wgrad': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _i32, _ptr, _sz, _ptr]),
-    'p3d_stem_masked_supported': (_i32, [_i32] * 5),
-    'p3d_stem_image_masked': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_stem_fwd_masked': (_i32, [_ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_stem_wgrad_masked': (_i32, [_ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _i32, _ptr, _sz, _ptr]),
-    'p3d_profile_enable': (_i32, [_i32]),
-    'p3d_profile_collect': (_i32, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
-    'p3d_profile_collect2': (_i32, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
-    'p3d_mask_count_fwd': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr]),
-    'p3d_nonzero_mask': (_i32, [_ptr, _ptr, _i64, _ptr]),
-    'p3d_bn_workspace_bytes': (_sz, [_i32, _i32, _i32]),
-    'p3d_bn_train_fwd': (_i32, [_ptr] * 9 + [_i32, _i32, _i32, _f32, _f32, _i32, _ptr, _sz, _ptr]),
-    'p3d_bn_train_bwd': (_i32, [_ptr] * 11 + [_i32, _i32, _i32, _i32, _i32, _ptr, _sz, _ptr]),
-    'p3d_bn_eval_fwd': (_i32, [_ptr] * 7 + [_i32, _i32, _i32, _f32, _i32, _ptr]),
-    'p3d_bn_eval_bwd': (_i32, [_ptr] * 10 + [_i32, _i32, _i32, _f32, _i32, _i32, _ptr, _sz, _ptr]),
-    'p3d_frozen_grad_mask_workspace_bytes': (_sz, [_i32, _i32, _i32]),
-    'p3d_frozen_grad_mask': (_i32, [_ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr, _sz, _ptr]),
-    'p3d_frozen_wgrad_finish': (_i32, [_ptr] * 5 + [_f32, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr]),
-    'p3d_relu_fwd': (_i32, [_ptr, _ptr, _i64, _ptr]),
-    'p3d_relu_bwd': (_i32, [_ptr, _ptr, _ptr, _i64, _ptr]),
-    'p3d_maxpool3x3s2_fwd': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr]),
-    'p3d_maxpool3x3s2_bwd': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr]),
-    'p3d_stem_tail_supported': (_i32, [_i32, _i32, _i32, _i32]),
-    'p3d_stem_tail_fwd': (_i32, [_ptr] * 9 + [_i32, _i32, _i32, _i32, _f32, _f32, _ptr, _sz, _ptr]),
-    'p3d_stem_tail_bwd': (_i32, [_ptr] * 10 + [_i32, _i32, _i32, _i32, _i32, _ptr, _sz, _ptr]),
-    'p3d_softargmax3d_fwd': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _f32, _ptr]),
-    'p3d_softargmax3d_bwd': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _f32, _ptr]),
-    'p3d_pose_loss_fwd_bwd': (_i32, [_ptr] * 6 + [_i32, _i32, _i32, _f32, _i32, _f32, _ptr, _ptr]),
-    'p3d_masked_loss_fwd_bwd': (_i32, [_ptr] * 5 + [_i32, _i32, _i32, _ptr, _ptr]),
-    'p3d_pose_eval_stats': (_i32, [_ptr] * 5 + [_i32, _i32, _f32, _f32, _f32, _ptr, _ptr, _ptr, _ptr]),
-    'p3d_recon_cam_fwd': (_i32, [_ptr] * 4 + [_i32, _i32, _ptr]),
-    'p3d_recon_cam_bwd': (_i32, [_ptr] * 6 + [_i32, _i32, _ptr]),
-    'p3d_l2norm_sq_accum': (_i32, [_ptr, _i64, _ptr, _ptr]),
-    'p3d_adam_step': (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _ptr, _f32, _ptr]),
-    'p3d_adam_step_dev': (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _f32, _f32, _f32, _f32, _f32, _ptr, _f32, _ptr, _f32, _i32, _ptr, _ptr]),
-    'p3d_distill_workspace_bytes': (_sz, [_i32]),
-    'p3d_distill_fwd_bwd': (_i32, [_ptr] * 5 + [_i32, _i32, _i32, _i32, _f32, _ptr, _sz, _ptr]),
-    'p3d_augment_colour': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _ptr]),
-    'p3d_augment_erase': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_augment_occlude': (_i32, [_ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_warp_crops': (_i32, [_ptr, _i32, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_stream_create_beside': (_i32, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_i32)]),
-    'p3d_stream_create_cumask': (_i32, [ctypes.POINTER(ctypes.c_uint32), _i32, ctypes.POINTER(ctypes.c_void_p)]),
-    'p3d_probe_hw_ids': (_i32, [ctypes.c_void_p, ctypes.c_void_p, _i32, _i32]),
-    'p3d_stream_destroy': (_i32, [ctypes.c_void_p]),
-    'p3d_x3_enable': (_i32, [_i32]),
-    'p3d_x3_any_enable': (_i32, [_i32]),
-    'p3d_conv2d_fwd_any_supported': (_i32, [_desc]),
-    'p3d_conv2d_dgrad_any_supported': (_i32, [_desc]),
-    'p3d_conv2d_wgrad_any_supported': (_i32, [_desc]),
-    'p3d_x3_any_partial_enable': (_i32, [_i32]),
-    'p3d_conv2d_fwd_masked_any_supported': (_i32, [_desc]),
-    'p3d_conv2d_dgrad_masked_any_supported': (_i32, [_desc]),
-    'p3d_conv2d_wgrad_masked_any_supported': (_i32, [_desc]),
-    'p3d_fx_tune': (None, [_i32, _i32]),
-    'p3d_conv_path_stats': (None, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double), _i32]),
-    'p3d_conv_last_fp32_launch': (None, [ctypes.POINTER(_i32)]),
-    'p3d_reproject_crops': (_i32, [_ptr, _i32, _ptr, _ptr, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_enhance_depth': (_i32, [_ptr, _ptr, _i64, _f32, _i32, _ptr]),
-    'p3d_normalize_rgb': (_i32, [_ptr, _i32, _i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _ptr]),
-    'p3d_hconv2d_fwd': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
-    'p3d_hconv2d_fwd_infer_supported': (_i32, [_desc]),
-    'p3d_hconv2d_fwd_infer': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr]),
-    'p3d_f8conv2d_fwd_infer_supported': (_i32, [_desc]),
-    'p3d_f8conv2d_weight_bytes': (_sz, [_i32, _i32, _i32]),
-    'p3d_f8conv2d_fwd_infer': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr]),
-    'p3d_f8act_bytes': (_sz, [_i64, _i32]),
-    'p3d_f8conv2d_fwd_infer_mx_supported': (_i32, [_desc, _i32, _i32]),
-    'p3d_f8conv2d_fwd_infer_mx': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _ptr]),
-    'p3d_hscale_pixels': (_i32, [_ptr, _ptr, _ptr, _i64, _i32, _ptr]),
-    'p3d_hconv2d_dgrad': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr]),
-    'p3d_hblock_fuse_sums': (_i32, [_i32]),
-    'p3d_hconv2d_sum_rows': (_i32, [_desc, _i32]),
-    'p3d_hconv2d_fwd_stats': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr]),
-    'p3d_hconv2d_dgrad_sums': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
-    'p3d_hconv2d_wgrad_workspace_bytes': (_sz, [_desc]),
-    'p3d_hconv2d_wgrad': (_i32, [_desc, _ptr, _ptr, _ptr, _ptr, _i32, _f32, _ptr, _sz, _ptr]),
-    'p3d_hconv2d_bgrad': (_i32, [_ptr, _i32, _i32, _ptr, _f32, _i32, _ptr]),
-    'p3d_nchw_f32_to_nhwc_f16': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _i32, _f32, _ptr]),
-    'p3d_nhwc_f16_to_nchw_f32': (_i32, [_ptr, _ptr, _i32, _i32, _i32, _f32, _ptr]),
-    'p3d_weight_images_f16': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_weight_images_f16_batched': (_i32, [_ptr, _ptr, _ptr, _i32, _ptr]),
-    'p3d_hbn_workspace_bytes': (_sz, [_i32]),
-    'p3d_hbn_train_fwd': (_i32, [_ptr] * 8 + [_i32, _i32, _f32, _f32, _i32, _ptr, _sz, _ptr]),
-    'p3d_hbn_eval_fwd': (_i32, [_ptr] * 7 + [_i32, _i32, _f32, _i32, _ptr, _sz, _ptr]),
-    'p3d_hbn_train_bwd': (_i32, [_ptr] * 8 + [_i32, _i32, _i32, _i32, _ptr, _sz, _ptr]),
-    'p3d_hbn_frozen_bwd': (_i32, [_ptr] * 8 + [_i32, _i32, _i32, _i32, _ptr, _sz, _ptr]),
-    'p3d_hbn_train_fwd_partial': (_i32, [_ptr] * 8 + [_i32, _i32, _f32, _f32, _i32, _ptr, _i32, _ptr, _ptr]),
-    'p3d_hbn_train_bwd_mask': (_i32, [_ptr] * 8 + [_i32, _i32, _i32, _ptr, _sz, _ptr]),
-    'p3d_hbn_train_bwd_partial': (_i32, [_ptr] * 6 + [_i32, _i32, _i32, _ptr, _i32, _ptr, _ptr]),
-    'p3d_hbn_eval_coef': (_i32, [_ptr] * 5 + [_i32, _f32, _ptr]),
-    'p3d_hconcat': (_i32, [_ptr, _ptr, _ptr, _i64, _i32, _i32, _i32, _ptr]),
-    'p3d_hrelu': (_i32, [_ptr, _ptr, _ptr, _i64, _ptr]),
-    'p3d_hmaxpool3x3s2_fwd': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
-    'p3d_hmaxpool3x3s2_bwd': (_i32, [_ptr, _ptr, _ptr, _i32, _i32, _i32, _i32, _ptr]),
-}
+
+def _prototype(text, structs):
+    what = 'prototype `%s`' % text
+    m = re.fullmatch(r'([^()]+)\(([^()]*)\)', text)
+    if not m:
+        raise P3DError('p3d_hip.h: cannot split %s' % what)
+    base, const, stars, name, count = _declarator(m.group(1), what)
+    if count is not None:
+        raise P3DError('p3d_hip.h: cannot split %s' % what)
+    res = None if (base, stars) == ('void', 0) else _ctype(base, const, stars, structs, what)
+    args = []
+    if m.group(2).strip() not in ('', 'void'):
+        for arg in m.group(2).split(','):
+            a_base, a_const, a_stars, _, a_count = _declarator(arg, what)
+            args.append(_ctype(a_base, a_const, a_stars + (a_count is not None), structs, what))      # an array parameter is a pointer
+    return name, (res, args)
+
+
+def parse_header(text):
+    """The ABI a header text declares: (constants, structs, signatures) = {macro: int}, {typedef name: ctypes.Structure subclass},
+    {function: (restype, argtypes)}."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    constants = {m.group(1): int(m.group(2) or m.group(3))
+                 for m in re.finditer(r'^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(?:(-?\d+)|\([ \t]*(-?\d+)[ \t]*\))[ \t]*$', text, re.M)}
+    text = re.sub(r'^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif[^\n]*$', ' ', text, flags=re.S | re.M)         # extern "C" { ... }
+    text = re.sub(r'^[ \t]*#[^\n]*$', ' ', text, flags=re.M)
+    structs = {}
+    for m in _STRUCT.finditer(text):                                                       # in the header's order: a later struct may hold an earlier one
+        structs[m.group(2)] = _struct(m.group(2), m.group(1), structs)
+    text = _STRUCT.sub(' ', text)
+    signatures = dict(_prototype(' '.join(decl.split()), structs) for decl in text.split(';') if decl.strip())
+    return constants, structs, signatures
+
+
+def read_header(path):
+    try:
+        with open(path) as f:
+            text = f.read()
+    except OSError as e:
+        raise P3DError('the C ABI header %s cannot be read (%s)' % (path, e))
+    return parse_header(text)
+
+
+# CONSTANTS: the header's integer #defines (P3D_OK, P3D_EINVAL, P3D_FX_LAUNCH_FIELDS, P3D_EVAL_ROW, ...); SIGNATURES: name -> (restype, argtypes) of every function
+CONSTANTS, STRUCTS, SIGNATURES = read_header(HEADER_PATH)
+ConvDesc, FoldJob, FxFuse = STRUCTS['p3d_conv_desc'], STRUCTS['p3d_fold_job'], STRUCTS['p3d_fx_fuse']
 
 _lib = None
 

@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from ._lib import ConvDesc, P3DError, check, lib
+from ._lib import CONSTANTS, ConvDesc, P3DError, check, lib
 
 CRITERIA = {'SmoothL1': 0, 'L1': 1, 'MSE': 2}
 
@@ -736,7 +736,8 @@ def masked_loss(pred, target, valid, criterion='SmoothL1', count_override=None):
 
 
 # columns of a row of p3d_pose_eval_stats (include/p3d_hip.h P3D_EVAL_*)
-EVAL_VALID, EVAL_SUM_DIST, EVAL_PCK, EVAL_SUM_AUC, EVAL_SOLID, EVAL_LOSS, EVAL_BATCH, EVAL_PRESENT, EVAL_ROW = 0, 1, 2, 3, 4, 10, 11, 12, 13
+EVAL_VALID, EVAL_SUM_DIST, EVAL_PCK, EVAL_SUM_AUC, EVAL_SOLID, EVAL_LOSS, EVAL_BATCH, EVAL_PRESENT, EVAL_ROW = (
+    CONSTANTS['P3D_EVAL_' + n] for n in ('VALID', 'SUM_DIST', 'PCK', 'SUM_AUC', 'SOLID', 'LOSS', 'BATCH', 'PRESENT', 'ROW'))
 EVAL_CLASSES = ('solid', 'close', 'depth', 'jitter', 'switch', 'fail')           # columns EVAL_SOLID + 0..5
 
 
@@ -1092,7 +1093,7 @@ def conv_path_stats(reset=False):
 
 # the record of p3d_conv_last_fp32_launch: include/p3d_hip.h and the enum of csrc/p3d_conv.hip define the layout; tests/test_fp32_mfma_instances_host.py holds these to them
 LAST_FP32_FIELDS = ('pass_', 'tile', 'tapm', 'masked', 'wv', 'grid_x', 'grid_y', 'y_means', 'weight_image', 'finish', 'eval', 'no_room')
-LAST_FP32_LEN = 16          # P3D_FP32_LAUNCH_FIELDS
+LAST_FP32_LEN = CONSTANTS['P3D_FP32_LAUNCH_FIELDS']
 
 
 def conv_last_fp32_launch():
@@ -1106,8 +1107,8 @@ def conv_last_fp32_launch():
 # the record of p3d_fx_launch_log, and (its first FX_INSTANCE_LEN fields) of p3d_fx_conv_instances: include/p3d_hip.h and the enum of csrc/p3d_fx.hip define the layout;
 # tests/test_fx_instances_host.py holds these to them
 FX_LAUNCH_FIELDS = ('kernel', 'amode', 'pro', 'epi', 'tapi', 'rag', 'rows', 'grid_x', 'grid_y', 'grid_z', 'kchunk', 'finish', 'finish_groups')
-FX_LAUNCH_LEN = 16          # P3D_FX_LAUNCH_FIELDS
-FX_INSTANCE_LEN = 7         # P3D_FX_INSTANCE_FIELDS
+FX_LAUNCH_LEN = CONSTANTS['P3D_FX_LAUNCH_FIELDS']
+FX_INSTANCE_LEN = CONSTANTS['P3D_FX_INSTANCE_FIELDS']
 FX_LOG_MAX = 256            # records the library keeps between two resets
 
 

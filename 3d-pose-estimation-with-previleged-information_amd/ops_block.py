@@ -11,9 +11,7 @@ import os
 import torch
 
 from . import ops
-from ._lib import ConvDesc, P3DError, check, lib
-
-_vp = ctypes.c_void_p
+from ._lib import STRUCTS, P3DError, check, lib
 
 # P3D_BLOCK_SIDE=0: keep the weight-gradient kernels of the block executor on the launch stream.  By default they run on the second HIP stream
 # (p3d_block_bwd orders them with events), as in the per-layer path; the step is bitwise reproducible either way
@@ -22,20 +20,7 @@ BLOCK_SIDE_STREAM = os.environ.get('P3D_BLOCK_SIDE', '1') != '0'
 # P3D_OUT_MASK=0: the backward pass reads the block's fp32 output for the closing ReLU's mask instead of the mask bytes forward leaves (p3d_block_io.out_mask = NULL)
 USE_OUT_MASK = os.environ.get('P3D_OUT_MASK', '1') != '0'
 
-
-class BlockDesc(ctypes.Structure):
-    """struct p3d_block_desc"""
-    _fields_ = [('nconv', ctypes.c_int32), ('has_downsample', ctypes.c_int32), ('relu_out', ctypes.c_int32), ('need_dx', ctypes.c_int32),
-                ('accumulate_grads', ctypes.c_int32), ('masked', ctypes.c_int32), ('reserved', ctypes.c_int32 * 2), ('eps', ctypes.c_float * 4), ('momentum', ctypes.c_float * 4),
-                ('conv', ConvDesc * 4)]
-
-
-class BlockIO(ctypes.Structure):
-    """struct p3d_block_io"""
-    _fields_ = [('x', _vp), ('out', _vp), ('w', _vp * 4), ('wimg', _vp * 4), ('wimgT', _vp * 4), ('c', _vp * 4), ('aimg', _vp * 4), ('table', _vp * 4), ('gamma', _vp * 4), ('beta', _vp * 4),
-                ('running_mean', _vp * 4), ('running_var', _vp * 4), ('dout', _vp), ('gbuf', _vp), ('dcimg', _vp * 4), ('da', _vp * 4), ('dx', _vp), ('dw', _vp * 4),
-                ('dgamma', _vp * 4), ('dbeta', _vp * 4), ('out_mask', _vp),
-                ('pix_in', _vp * 4), ('pix_out', _vp * 4)]
+BlockDesc, BlockIO = STRUCTS['p3d_block_desc'], STRUCTS['p3d_block_io']
 
 
 def _one(v):

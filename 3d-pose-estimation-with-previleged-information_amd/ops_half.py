@@ -10,7 +10,7 @@ import ctypes
 import torch
 
 from . import ops
-from ._lib import P3DError, check, lib
+from ._lib import STRUCTS, P3DError, check, lib
 from .ops import _GradOut, _desc, _p, _side_launch, _side_launched, _stream, workspace
 
 CL = torch.channels_last
@@ -373,14 +373,7 @@ def relu(x):
 import os as _os
 
 HALF_BLOCKS = _os.environ.get('P3D_HALF_BLOCKS', '1') != '0'
-_vp = ctypes.c_void_p
-
-
-class HBlockIO(ctypes.Structure):
-    """struct p3d_hblock_io"""
-    _fields_ = [('x', _vp), ('out', _vp), ('w_krsc', _vp * 4), ('w_crsk', _vp * 4), ('c', _vp * 4), ('a', _vp * 4), ('coef', _vp * 4), ('gamma', _vp * 4), ('beta', _vp * 4),
-                ('running_mean', _vp * 4), ('running_var', _vp * 4), ('dout', _vp), ('dc', _vp * 4), ('da', _vp * 4), ('dx', _vp), ('dw', _vp * 4), ('dgamma', _vp * 4),
-                ('dbeta', _vp * 4), ('c_real', ctypes.c_int32 * 4), ('out_mask', _vp)]
+HBlockIO = STRUCTS['p3d_hblock_io']
 
 
 class _HPlan:
