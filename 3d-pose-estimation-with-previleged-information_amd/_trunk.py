@@ -65,6 +65,8 @@ class _ResidualBlock(nn.Module):
             return x, join
         if fold and ops_frozen.admits(x, self.downsample[0], self.downsample[1]):
             return ops_frozen.conv_bn(x, self.downsample[0], self.downsample[1], join_put=join), None
+        if fold and ops.FROZEN_FOLD_HALF and ops_frozen.admits_half(x, self.downsample[0], self.downsample[1]):      # the same under -half_acc
+            return ops_frozen.conv_bn_half(x, self.downsample[0], self.downsample[1], join_put=join), None
         return self.downsample[1](self.downsample[0](x, join_put=join)), None
 
     def forward(self, x):
@@ -82,12 +84,17 @@ class _ResidualBlock(nn.Module):
         last = len(self._chain) - 1
         for i, (cname, bname) in enumerate(self._chain):
             conv, bn = getattr(self, cname), getattr(self, bname)
+            folded = None
             if ops.FROZEN_FOLD and ops_frozen.admits(out, conv, bn):      # a frozen BatchNorm folded into its conv: one node, no BatchNorm pass (ops_frozen.py)
+                folded = ops_frozen.conv_bn
+            elif ops.FROZEN_FOLD_HALF and ops_frozen.admits_half(out, conv, bn):      # the same under -half_acc, behind its own switch
+                folded = ops_frozen.conv_bn_half
+            if folded is not None:
                 if i < last:
-                    out = ops_frozen.conv_bn(out, conv, bn, relu=True, join_take=join if i == 0 else None)
+                    out = folded(out, conv, bn, relu=True, join_take=join if i == 0 else None)
                 else:
                     res, res_join = self._shortcut(x, join, fold=True)
-                    out = ops_frozen.conv_bn(out, conv, bn, res=res, relu=not self.skip_relu, join_take=join if i == 0 else None, res_join=res_join)
+                    out = folded(out, conv, bn, res=res, relu=not self.skip_relu, join_take=join if i == 0 else None, res_join=res_join)
                 continue
             out = conv(out, join_take=join) if i == 0 else conv(out)
             if i < last:
@@ -171,6 +178,8 @@ def _frozen_fold(module, inputs):
     """Forward pre-hook of the whole network: under ops.frozen_fold the plan of its frozen conv + BatchNorm pairs is made, and folded again when stale, once here."""
     if ops.FROZEN_FOLD:
         ops_frozen.prepare(module)
+    if ops.FROZEN_FOLD_HALF and module._p3d_half:            # -half_acc: the fp16 plan, under its own switch
+        ops_frozen.prepare(module, half=True)
 
 
 class TrunkBase(nn.Module):

@@ -2271,7 +2271,8 @@ int32_t fx_build_weight_images_batched(const void* jobs, int njobs, int blocks, 
 // w * s over input channels [c_offset, c_offset + C) (fx_weight_image_chunks, the layout p3d_fx_weight_images produces), kind 1 the folded fp32 weights
 // [K][C][RS] (the stem, whose image p3d_stem_weight_image restates), kind 2 the fp16 forward image [K][RS][Cpad] of the fp16 path (the layout of
 // p3d_weight_images_f16; Cpad in `reserved`, channels C .. Cpad - 1 written as 0), kind 3 the MXFP8 image of the fp8 path (elements [K][RS][Cpad], then the
-// scale bytes [K][RS][Cpad / 32], by the MX rule of p3d_common.h from the same products as kind 2; Cpad in `reserved`, a multiple of 32).  Block 0 also writes
+// scale bytes [K][RS][Cpad / 32], by the MX rule of p3d_common.h from the same products as kind 2; Cpad in `reserved`, a multiple of 32), kind 4 kind 2's values as the fp16 data-gradient image [Cpad][RS][K] (the crsk layout of
+// p3d_weight_images_f16: training through a frozen BatchNorm under -half_acc, ops_frozen.py).  Block 0 also writes
 // b' = beta - mean * s (+ s * conv bias) when bias_out is given.
 // The operation order is fixed (a division, a correctly rounded sqrtf, one product per weight), so the image equals the one built from the fold done in torch.
 constexpr int FX_FOLD_MAX_K = 2048;
@@ -2279,7 +2280,7 @@ __global__ __launch_bounds__(256) void fx_fold_bn_kernel(const p3d_fold_job* __r
     const p3d_fold_job j = jobs[blockIdx.y];
     __shared__ float sc[FX_FOLD_MAX_K];
     if (j.K <= 0 || j.K > FX_FOLD_MAX_K || j.C <= 0 || j.RS <= 0 || j.c_offset < 0 || j.c_offset + j.C > j.c_total || (j.kind == 0 && j.C % FX_BK != 0) ||
-        (j.kind == 2 && (j.reserved < j.C || j.reserved % 8 != 0)) || (j.kind == 3 && (j.reserved < j.C || j.reserved % 32 != 0))) return;      // (checked by the caller)
+        ((j.kind == 2 || j.kind == 4) && (j.reserved < j.C || j.reserved % 8 != 0)) || (j.kind == 3 && (j.reserved < j.C || j.reserved % 32 != 0))) return;      // (checked by the caller)
     const bool bn = j.gamma != nullptr;
     for (int m = threadIdx.x; m < j.K; m += 256) {
         const float s = bn ? j.gamma[m] / sqrtf(j.var[m] + j.eps) : 1.f;
@@ -2343,6 +2344,22 @@ __global__ __launch_bounds__(256) void fx_fold_bn_kernel(const p3d_fold_job* __r
             *reinterpret_cast<i32x4*>(out + i * 32) = i32x4{(int)q[0], (int)q[1], (int)q[2], (int)q[3]};
             *reinterpret_cast<i32x4*>(out + i * 32 + 16) = i32x4{(int)q[4], (int)q[5], (int)q[6], (int)q[7]};
             scales[i] = (unsigned char)sb;
+        }
+    } else if (j.kind == 4) {
+        // the fp16 data-gradient image [Cpad][RS][K] of w * s: kind 2's values (one product, one rounding to half) in the crsk layout of p3d_weight_images_f16;
+        // the output index runs fastest over K, so the stores are contiguous
+        _Float16* out = (_Float16*)j.out;
+        const size_t total = (size_t)j.reserved * j.RS * j.K;
+        for (size_t i = first; i < total; i += step) {
+            const int m = (int)(i % j.K);
+            const int tap = (int)((i / j.K) % j.RS);
+            const int c = (int)(i / ((size_t)j.K * j.RS));
+            float x = 0.f;
+            if (c < j.C) {
+                x = j.w[((size_t)m * j.c_total + j.c_offset + c) * j.RS + tap];
+                if (bn) x = x * sc[m];
+            }
+            out[i] = (_Float16)x;
         }
     } else {
         float* out = (float*)j.out;

@@ -40,6 +40,9 @@ class GraphedStep:
         if ops.FROZEN_FOLD and ops_frozen.has_frozen(self.trainer.model):
             raise ops.P3DError('GraphedStep: ops.frozen_fold is on and the model has a frozen (eval-mode) BatchNorm; the fold is refreshed from the host and '
                                'cannot be captured.  Turn the switch off (ops.frozen_fold(False)) for whole-step capture')
+        if ops.FROZEN_FOLD_HALF and ops_frozen.has_frozen(self.trainer.model):      # the -half_acc switch: the same fold, refreshed from the host the same way
+            raise ops.P3DError('GraphedStep: ops.frozen_fold_half is on and the model has a frozen (eval-mode) BatchNorm; the fold is refreshed from the host and '
+                               'cannot be captured.  Turn the switch off (ops.frozen_fold_half(False)) for whole-step capture')
 
     def _capture(self, batch):
         tr = self.trainer

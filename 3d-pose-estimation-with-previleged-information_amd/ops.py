@@ -255,7 +255,8 @@ class GradJoin:
     raises P3DError when the pass ends (`check_joins`), whoever called .backward().
     `after`: an event the producer may leave beside `buf` when a kernel on the second stream still reads the stashed buffer (ops_frozen.FrozenConvBnFn, whose
     stashed gradient is also its weight gradient's operand); the consumer orders its stream behind it before it writes (`_take`).  Only the fp32 consumers
-    (Conv2dFn, FrozenConvBnFn) go through `_take`; the fp16 path (ops_half) reads `buf` itself, and no producer there or for it ever leaves an event."""
+    (Conv2dFn, FrozenConvBnFn) and HFrozenConvBnFn go through `_take`; ops_half.HConv2dFn reads `buf` itself and waits for `after` the same way (only
+    HFrozenConvBnFn, under ops.frozen_fold_half, ever leaves one for it)."""
     __slots__ = ('buf', 'taken', 'after', '__weakref__')
     _live = None
 
@@ -969,6 +970,19 @@ def frozen_fold(on):
     in either direction and no conv output kept (ops_frozen.py).  Returns the previous setting."""
     global FROZEN_FOLD
     previous, FROZEN_FOLD = FROZEN_FOLD, bool(on)
+    return previous
+
+
+FROZEN_FOLD_HALF = os.environ.get('P3D_FROZEN_FOLD_HALF', '0') == '1'
+
+
+def frozen_fold_half(on):
+    """frozen_fold for -half_acc, a switch of its own, OFF by default (P3D_FROZEN_FOLD_HALF=1 turns it on): a frozen conv + BatchNorm pair of a dense residual
+    block that runs on fp16 NHWC activations trains on the folded fp16 convolution -- one p3d_hconv2d_fwd_infer launch with b', the residual and the ReLU in its
+    epilogue, no BatchNorm pass in either direction and no conv output kept (ops_frozen.HFrozenConvBnFn).  frozen_fold and ops_frozen.admits keep their meaning:
+    fp16 input is still refused there.  Returns the previous setting."""
+    global FROZEN_FOLD_HALF
+    previous, FROZEN_FOLD_HALF = FROZEN_FOLD_HALF, bool(on)
     return previous
 
 

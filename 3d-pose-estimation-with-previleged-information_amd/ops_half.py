@@ -192,6 +192,9 @@ class HConv2dFn(torch.autograd.Function):
             if joined is not None and (joined.shape != x.shape or joined.dtype != torch.float16):
                 raise P3DError('GradJoin: the shortcut gradient %s does not match the block input %s' % (tuple(joined.shape), tuple(x.shape)))
             if joined is not None:
+                if join_take.after is not None:                # a folded frozen layer's weight gradient still reads the stashed buffer on the second stream (ops_frozen)
+                    torch.cuda.current_stream(x.device).wait_event(join_take.after)
+                    join_take.after = None
                 dx, join_take.buf = _cl(joined), None          # accumulate onto the shortcut's gradient (ops.GradJoin)
                 d.accumulate = 1
             else:

@@ -408,7 +408,9 @@ int32_t p3d_fx_wgrad_plan(const p3d_conv_desc* d, int32_t operands, int32_t* out
  * (s = 1, b' = the conv bias or 0).  Kind 3 writes the MXFP8 image of w' (infer.fold_fp8, p3d_f8conv2d_fwd_infer): per (row k, tap, 32 input channels) one block
  * by OCP MX v1.0 with e4m3fn elements -- e = floor(log2(amax)) from the exponent bits, scale byte E8M0 = clamp(e - 8 + 127, 0, 254), X = 2^(byte - 127),
  * q = e4m3fn(RNE(clamp(w' / X, -448, 448))) (amax 0: byte 0, elements 0) -- out holds the elements [K][RS][Cpad] (bytes), then the scale bytes [K][RS][Cpad / 32]
- * (p3d_f8conv2d_weight_bytes in all); channels C .. Cpad - 1 are 0.  Kinds may be mixed in one table.  blocks: grid width per job.  K <= 2048. */
+ * (p3d_f8conv2d_weight_bytes in all); channels C .. Cpad - 1 are 0.  Kind 4 writes the fp16 DATA-GRADIENT image [Cpad][RS][K] of w' (training through a frozen BatchNorm under
+ * -half_acc, ops_frozen.py): the `crsk` image p3d_weight_images_f16 builds from the folded fp32 weight (kind 1), bit for bit; Cpad in `reserved` as for kind 2,
+ * channels C .. Cpad - 1 are 0.  Any other kind value is taken as kind 1.  Kinds may be mixed in one table.  blocks: grid width per job.  K <= 2048. */
 typedef struct p3d_fold_job {
     const float* w;             /* conv weight [K][c_total][RS] */
     const float* conv_bias;     /* [K] or NULL */
@@ -416,11 +418,11 @@ typedef struct p3d_fold_job {
     const float* beta;
     const float* mean;
     const float* var;
-    void* out;                  /* kind 0: p3d_fx_weight_image_bytes(K, C, RS) forward bytes; kind 1: K * C * RS floats; kind 2: K * RS * Cpad halves */
+    void* out;                  /* kind 0: p3d_fx_weight_image_bytes(K, C, RS) forward bytes; kind 1: K * C * RS floats; kinds 2 and 4: K * RS * Cpad halves */
     float* bias_out;            /* [K] or NULL */
     int32_t K, C, RS, c_offset, c_total, kind;
     float eps;
-    int32_t reserved;           /* kind 2: Cpad, the padded channel count of the fp16 image (>= C, multiple of 8); kind 3: Cpad (>= C, multiple of 32); kinds 0 / 1: unused */
+    int32_t reserved;           /* kinds 2 and 4: Cpad, the padded channel count of the fp16 image (>= C, multiple of 8); kind 3: Cpad (>= C, multiple of 32); kinds 0 / 1: unused */
 } p3d_fold_job;
 int32_t p3d_fx_fold_bn_images(const void* jobs, int32_t njobs, int32_t blocks, void* stream);
 /* y = conv(x, w') + b' (+ y when d->accumulate) (+ res) (then ReLU when relu != 0) from a folded forward weight image of exactly this descriptor's C input channels
@@ -762,6 +764,16 @@ int32_t p3d_hconv2d_wgrad(const p3d_conv_desc* d, const void* dy_nhwc, const voi
                           void* workspace, size_t workspace_bytes, void* stream);
 /* db[K] (fp32) = (accumulate ? db : 0) + scale * sum over the P pixels of dy[P][K] */
 int32_t p3d_hconv2d_bgrad(const void* dy_nhwc, int32_t P, int32_t K, float* db, float scale, int32_t accumulate, void* stream);
+/* Training through a frozen BatchNorm folded into its fp16 convolution (ops_frozen.HFrozenConvBnFn; csrc/p3d_hfrozen.hip): the mask-and-sum pass of
+ * p3d_frozen_grad_mask on NHWC fp16.  dy, y, g are [P][K] halves.  With y: g = dy where y > 0, else +0.  y == NULL (then g == NULL too): nothing is written, dy is
+ * g.  Either way sums[k] (fp32, overwritten) = sum over the P pixels of g[p][k].  One pass of 16-B accesses (8 channels of one pixel per lane); no element beyond
+ * P * K is touched.  The sums never pass through fp16 (gradients carry the loss scale): every half is widened to fp64 and accumulated there in a fixed order --
+ * per-thread accumulators, the block's pixel rows through LDS, per-block partials in the workspace, one ordered sum per channel -- without atomics: bitwise
+ * reproducible.  Shape rule: K % 8 == 0, 8 <= K <= 2048, 0 < P < 2^31, dy / y / g on 16-B lines; P3D_EINVAL with a message outside it, nothing launched.
+ * Workspace: p3d_hfrozen_grad_mask_workspace_bytes (0 outside the rule), on an 8-B line. */
+size_t p3d_hfrozen_grad_mask_workspace_bytes(int64_t P, int32_t K);
+int32_t p3d_hfrozen_grad_mask(const void* dy_nhwc, const void* y_nhwc, void* g_nhwc, float* sums, int64_t P, int32_t K, void* workspace, size_t workspace_bytes,
+                              void* stream);
 /* layout / precision converters: dst = scale * src; Cpad >= C, multiple of 8, the padding channels are written as 0 */
 int32_t p3d_nchw_f32_to_nhwc_f16(const float* src, void* dst, int32_t N, int32_t C, int32_t HW, int32_t Cpad, float scale, void* stream);
 int32_t p3d_nhwc_f16_to_nchw_f32(const void* src, float* dst, int32_t N, int32_t C, int32_t HW, float scale, void* stream);

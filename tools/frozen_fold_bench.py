@@ -8,6 +8,8 @@
   --distill   the same for one -do_teach -do_freeze -do_fusion distillation step: a depthnet student under a fusionnet teacher of the same depth.
   --classes   per conv + BatchNorm class of the trunk at --side's maps, each pass alone: today's conv forward + p3d_bn_eval_fwd against the folded forward, and
               p3d_bn_eval_bwd against p3d_frozen_grad_mask + p3d_frozen_wgrad_finish (the conv gradients are the same launches in both legs).
+  --half      with any of the three: the same under -half_acc, ops.frozen_fold_half off and on (profiles/train_frozen_fold_half.md); --classes then compares the
+              fp16 kernels and adds the mask pass alone with its achieved TB/s.
 GPU box only."""
 import argparse
 import ctypes
@@ -122,9 +124,91 @@ def classes(a):
         print('sum over the classes x their layer counts, %-6s: off %.2f ms  on %.2f ms' % (name, total.get((name, 'off'), 0.0), total.get((name, 'on'), 0.0)))
 
 
+def classes_half(a):
+    """--classes --half: the same table on the fp16 kernels.  Today's p3d_hconv2d_fwd + p3d_hbn_eval_fwd against p3d_hconv2d_fwd_infer on the plan's kind-2 image, and
+    p3d_hbn_frozen_bwd against p3d_hfrozen_grad_mask + p3d_frozen_wgrad_finish; the mask pass also alone, with its achieved TB/s (2 B read per element of dy, and
+    with a ReLU 2 B of y read and 2 B of g written)."""
+    L, P, stream = pkg._lib.lib(), ops._p, ops._stream()
+    oh, of = pkg.ops_half, pkg.ops_frozen
+    total = {}
+    for (c, h, k, ks, st, dil, relu, res, cnt) in R50:
+        h = (a.side - 1) // (256 // h) + 1
+        tag = 'c%d h%d k%d %dx%d s%d d%d%s%s x%d' % (c, h, k, ks, ks, st, dil, ' relu' if relu else '', ' res' if res else '', cnt)
+        if a.only and a.only not in tag:
+            continue
+        torch.manual_seed(c + k)
+        pad = dil * (ks - 1) // 2
+        conv = pkg.nn.Conv2d(c, k, ks, stride=st, padding=pad, dilation=dil, bias=False).cuda()
+        bn = pkg.nn.BatchNorm2d(k).cuda().eval()
+        bn.running_var.uniform_(0.5, 2.0)
+        bn.running_mean.normal_()
+        oh.refresh_weights(conv)
+        half = lambda *s: torch.randn(*s, device='cuda').half().contiguous(memory_format=torch.channels_last)
+        x = half(a.batch, c, h, h)
+        d = ops._desc(x.shape, conv.weight.shape, st, pad, dil)
+        b = ctypes.byref(d)
+        pixels = a.batch * d.Ho * d.Wo
+        dy = half(a.batch, k, d.Ho, d.Wo)
+        rs = half(a.batch, k, d.Ho, d.Wo) if res else None
+        z, y, g, dz, dres = (torch.empty_like(dy) for _ in range(5))
+        dw, raw = torch.empty_like(conv.weight), torch.randn_like(conv.weight)
+        dgamma, dbeta, sums = (torch.empty(k, device='cuda') for _ in range(3))
+        coef = torch.empty(k, 4, device='cuda')
+        unit = of._unit(conv, bn, of._HUnit)
+        plan = unit.plan.refresh()
+        if unit.entry(tuple(x.shape)) is None:
+            print('%-36s refused by p3d_hconv2d_fwd_infer' % tag)
+            continue
+        ws = torch.empty(max(L.p3d_hbn_workspace_bytes(k), L.p3d_hfrozen_grad_mask_workspace_bytes(pixels, k), 16), dtype=torch.uint8, device='cuda')
+        w, gm, bt, rm, rv = (t.detach() for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+        assert L.p3d_hbn_eval_coef(P(gm), P(bt), P(rm), P(rv), P(coef), k, bn.eps, stream) == 0, L.p3d_last_error()
+        kept = y if (relu and res) else None                 # (what HBatchNormActFn keeps: y only where the mask cannot be had from z)
+
+        def fwd_off():
+            L.p3d_hconv2d_fwd(b, P(x), P(conv._h_images.krsc), None, None, None, P(z), stream)
+            return L.p3d_hbn_eval_fwd(P(z), P(rs), P(gm), P(bt), P(rm), P(rv), P(y), pixels, k, bn.eps, relu, P(ws), ws.numel(), stream)
+
+        def fwd_on():
+            return L.p3d_hconv2d_fwd_infer(b, P(x), plan.at(unit.img_off), plan.at(unit.bias_off), None, None, P(rs), relu, P(y), stream)
+
+        def bwd_off():
+            return L.p3d_hbn_frozen_bwd(P(dy), P(z), P(kept), P(coef), P(dz), P(dres) if (res and relu) else None, P(dgamma), P(dbeta), pixels, k, relu, 0, P(ws), ws.numel(),
+                                        stream)
+
+        def mask():
+            return L.p3d_hfrozen_grad_mask(P(dy), P(y) if relu else None, P(g) if relu else None, P(sums), pixels, k, P(ws), ws.numel(), stream)
+
+        def bwd_on():
+            mask()
+            return L.p3d_frozen_wgrad_finish(P(raw), P(w), P(gm), P(rm), P(rv), bn.eps, P(sums), P(dw), P(dgamma), P(dbeta), k, c * ks * ks, 0, stream)
+
+        for name, legs in (('fwd', (fwd_off, fwd_on)), ('bn-bwd', (bwd_off, bwd_on)), ('mask', (mask,))):
+            ms = [[] for _ in legs]
+            for fn in legs:
+                for _ in range(3):
+                    assert fn() == 0, L.p3d_last_error()
+            for _ in range(a.rounds):
+                for i, fn in enumerate(legs):
+                    ms[i].append(timed(fn, a.iters))
+            if name == 'mask':
+                m = med(ms[0])
+                nbytes = pixels * k * 2 * (3 if relu else 1)
+                print('%-36s %-6s | %.4f [%.4f..%.4f] ms | %.1f MB | %.2f TB/s' % ((tag, name) + m + (nbytes / 1e6, nbytes / (m[0] * 1e-3) / 1e12)), flush=True)
+                continue
+            m0, m1 = med(ms[0]), med(ms[1])
+            print('%-36s %-6s | off %.3f [%.3f..%.3f] ms | on %.3f [%.3f..%.3f] ms | on/off %.2f' % ((tag, name) + m0 + m1 + (m1[0] / m0[0],)), flush=True)
+            total[(name, 'off')] = total.get((name, 'off'), 0.0) + m0[0] * cnt
+            total[(name, 'on')] = total.get((name, 'on'), 0.0) + m1[0] * cnt
+    for name in ('fwd', 'bn-bwd'):
+        print('sum over the classes x their layer counts, %-6s: off %.2f ms  on %.2f ms' % (name, total.get((name, 'off'), 0.0), total.get((name, 'on'), 0.0)))
+
+
 def step(a, distill):
     flags = ['-model', a.model, '-suffix', 'bench', '-data_name', 'h36m', '-save_path', '/tmp/p3d_bench', '-criterion', 'SmoothL1', '-num_joints', '17', '-side_in', str(a.side),
              '-stride', '16', '-depth', '16', '-depth_range', '1000', '-loss_div', '10', '-learn_rate', '5e-5', '-weight_decay', '4e-5', '-grad_norm', '5']
+    switch = ops.frozen_fold_half if a.half else ops.frozen_fold
+    if a.half:
+        flags += ['-half_acc']
     if distill:
         flags += ['-do_teach', '-do_fusion', '-do_freeze']
     args = pkg.opts.parse(flags)
@@ -164,20 +248,20 @@ def step(a, distill):
     legs = ('off', 'on')
     ms, peak = {leg: [] for leg in legs}, {}
     for leg in legs:
-        ops.frozen_fold(leg == 'on')
+        switch(leg == 'on')
         run(a.warmup)
         torch.cuda.synchronize()
     for r in range(a.rounds):
         for leg in legs:
-            ops.frozen_fold(leg == 'on')
+            switch(leg == 'on')
             run(2)
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             ms[leg].append(timed(lambda: run(a.iters), 1) / a.iters)
             peak[leg] = max(peak.get(leg, 0), torch.cuda.max_memory_allocated())
             print('round %d %-3s %.3f ms/step' % (r, leg, ms[leg][-1]), flush=True)
-    ops.frozen_fold(False)
-    out = {'what': 'distill' if distill else 'step', 'side': a.side, 'batch': a.batch, 'model': a.model}
+    switch(False)
+    out = {'what': 'distill' if distill else 'step', 'half': bool(a.half), 'side': a.side, 'batch': a.batch, 'model': a.model}
     for leg in legs:
         m = med(ms[leg])
         out[leg] = {'median_ms': round(m[0], 3), 'min_ms': round(m[1], 3), 'max_ms': round(m[2], 3), 'peak_allocated_mib': round(peak[leg] / 2 ** 20, 1)}
@@ -200,9 +284,10 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--only', default='')
+    ap.add_argument('--half', action='store_true', help='-half_acc: ops.frozen_fold_half off and on, on the fp16 kernels')
     a = ap.parse_args()
     if a.classes:
-        classes(a)
+        (classes_half if a.half else classes)(a)
     if a.step:
         step(a, False)
     if a.distill:
