@@ -725,6 +725,64 @@ __global__ __launch_bounds__(256) void dgrad_interleave2_kernel(const float* __r
     }
 }
 
+// Stride 2 at ANY map height and width (the 65 / 33 / 17 maps of a 257 crop), from tight class planes [N C][hc][wc] (hc = (H - ph + 1) / 2, wc = (W - pw + 1) / 2):
+// what dgrad_interleave_kernel computes, bit for bit (the same value, factor and accumulate arithmetic in the same order), shaped for a pass that only moves bytes.
+// A thread owns four consecutive floats of dx by FLAT index, so its store (and its read under `accumulate`) is one 16-B access whatever W is; the flat index is taken
+// apart into (plane, row, column) once per chunk with 32-bit divisions (the tensor is below 2^31 elements) and walked from there.  A chunk inside one row takes two
+// consecutive floats from each of the row's two class rows (pair loads: neighbouring lanes read neighbouring pairs, whole cache lines); a chunk that runs over a row
+// end, a plane end or the tensor's end goes element by element.  The planes of classes no tap reaches are never read: their pixels get +0 (what they held, under
+// `accumulate`).  vec == 0 (dx off a 16-B line: the test hook only): dword accesses to dx.
+typedef float f32x2_dw __attribute__((ext_vector_type(2), aligned(4)));      // two floats on a dword line: the compiler picks the widest load the target allows there
+__global__ __launch_bounds__(256) void dgrad_interleave_rows_kernel(const float* __restrict__ stage, float* __restrict__ dx, const float* __restrict__ mask_in,
+                                                                    unsigned total, int C, int H, int W, size_t cls_stride, int live_mask, int accumulate, int vec) {
+    const unsigned HW = (unsigned)H * W;
+    const int hc1 = H >> 1, hc0 = H - hc1, wc1 = W >> 1, wc0 = W - wc1;
+    const unsigned step = gridDim.x * 256u * 4u;
+    for (unsigned i = (blockIdx.x * 256u + threadIdx.x) * 4u; i < total; i += step) {
+        unsigned nc = i / HW;
+        const unsigned rem = i - nc * HW;
+        int hi = (int)(rem / (unsigned)W), wi = (int)(rem - (unsigned)hi * W);
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        const bool whole = i + 3 < total;
+        if (whole && wi + 3 < W) {
+            // one row: even columns from class (ph, 0) at iw = wi / 2 (+ 1 from an odd start), odd columns from class (ph, 1)
+            const int ph = hi & 1, q = wi & 1, iw = wi >> 1;
+            const unsigned row = nc * (unsigned)(ph ? hc1 : hc0) + (unsigned)(hi >> 1);
+            f32x2_dw a = {0.f, 0.f}, b = {0.f, 0.f};
+            if ((live_mask >> (ph * 2)) & 1) a = *reinterpret_cast<const f32x2_dw*>(stage + (size_t)(ph * 2) * cls_stride + row * (unsigned)wc0 + (unsigned)(iw + q));
+            if ((live_mask >> (ph * 2 + 1)) & 1) b = *reinterpret_cast<const f32x2_dw*>(stage + (size_t)(ph * 2 + 1) * cls_stride + row * (unsigned)wc1 + (unsigned)iw);
+            v[0] = q ? b.x : a.x; v[1] = q ? a.x : b.x; v[2] = q ? b.y : a.y; v[3] = q ? a.y : b.y;
+            if (mask_in) {
+                const float* m = mask_in + (size_t)(nc / (unsigned)C) * HW + rem;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] *= m[e];
+            }
+        } else {
+            unsigned n = mask_in ? nc / (unsigned)C : 0u;
+            int c = (int)(nc - n * (unsigned)C);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (i + e < total) {
+                    const int ph = hi & 1, pw = wi & 1, cls = ph * 2 + pw;
+                    if ((live_mask >> cls) & 1)
+                        v[e] = stage[(size_t)cls * cls_stride + (nc * (unsigned)(ph ? hc1 : hc0) + (unsigned)(hi >> 1)) * (unsigned)(pw ? wc1 : wc0) + (unsigned)(wi >> 1)];
+                    if (mask_in) v[e] *= mask_in[(size_t)n * HW + (unsigned)hi * W + wi];
+                }
+                if (++wi == W) { wi = 0; if (++hi == H) { hi = 0; ++nc; if (++c == C) { c = 0; ++n; } } }      // the next flat element: next row, next plane, next image
+            }
+        }
+        if (whole && vec) {
+            float4* o = reinterpret_cast<float4*>(dx + i);
+            if (accumulate) { const float4 p = *o; v[0] = p.x + v[0]; v[1] = p.y + v[1]; v[2] = p.z + v[2]; v[3] = p.w + v[3]; }
+            *o = float4{v[0], v[1], v[2], v[3]};
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i + e < total) dx[i + e] = accumulate ? dx[i + e] + v[e] : v[e];
+        }
+    }
+}
+
 // First stage of a deep split-K reduction: slab[g] <- sum of slabs g, g+G, g+2G, ... (in place; only group g touches slab[g]).
 // A small dw with ~1000 slabs would otherwise be summed by a handful of blocks, each chasing 1000 dependent loads.
 __global__ __launch_bounds__(256) void slab_fold_kernel(float* __restrict__ slab, size_t total, int splits, int G) {
@@ -1184,10 +1242,12 @@ static SplitPlan plan_dgrad1(const p3d_conv_desc* d, bool may_split) { return pl
 //              beside the predicate, as the entries always had it (the predicate implies it);
 //   X3_MASKED_RAGGED  partial convolution the masked predicate refuses for the map width alone, p3d_x3_any_partial_enable is on, no bias and whole weights: the masked
 //              instances for any map width (the data gradient: stride 1 only).  Independent of p3d_x3_any_enable;
+//   X3_STRIDED_RAGGED  dense stride-2 data gradient the aligned predicate refuses, p3d_x3_any_strided_enable is on and fx_dgrad_strided_any_applies admits (whole
+//              weights, 96 input channels): one ragged launch per parity class into tight class planes, then dgrad_interleave_rows_kernel.  Independent of the others;
 //   FP32_MFMA  everything else: an eval epilogue (the x3 entries of p3d_block.hip have their own), an operand off a 16-B line, a refused shape.
 // A forward or data gradient whose workspace is too small for its x3 family quietly runs on fp32-MFMA instead.  The weight gradient does NOT look at workspace_bytes
 // here: it stays on x3 and its entry fails with P3D_EWORKSPACE (both paths need slabs; the x3 plan usually the larger).
-struct ConvRoute { enum Family { FP32_MFMA, X3, X3_RAGGED, X3_MASKED, X3_MASKED_RAGGED } family; size_t x3_bytes; };
+struct ConvRoute { enum Family { FP32_MFMA, X3, X3_RAGGED, X3_MASKED, X3_MASKED_RAGGED, X3_STRIDED_RAGGED } family; size_t x3_bytes; };
 static bool whole_weight(const p3d_conv_desc* d) { return d->c_offset == 0 && d->c_total == d->C; }
 static bool any_ok(FxPass pass, const p3d_conv_desc* d) { return whole_weight(d) && fx_applies(pass, d, 96, true); }      // (the public p3d_conv2d_*_any_supported: not the switch)
 static bool masked_any_ok(FxPass pass, const p3d_conv_desc* d) { return whole_weight(d) && fx_masked_applies(pass, d, true); }      // (p3d_conv2d_*_masked_any_supported)
@@ -1200,7 +1260,12 @@ static ConvRoute conv_route(FxPass pass, const p3d_conv_desc* d, int masks /* fa
     }
     else if (fx_applies(pass, d)) r.family = ConvRoute::X3;
     else if (fx_any_enabled() && any_ok(pass, d)) r.family = ConvRoute::X3_RAGGED;
+    else if (pass == FX_DGRAD && fx_any_strided_enabled() && fx_dgrad_strided_any_applies(d)) r.family = ConvRoute::X3_STRIDED_RAGGED;
     if (r.family == ConvRoute::FP32_MFMA) return r;
+    if (r.family == ConvRoute::X3_STRIDED_RAGGED) {
+        r.x3_bytes = fx_dgrad_strided_any_plan(d).workspace;
+        return workspace_bytes < r.x3_bytes ? ConvRoute{ConvRoute::FP32_MFMA, 0} : r;
+    }
     const bool ragged = r.family == ConvRoute::X3_RAGGED || r.family == ConvRoute::X3_MASKED_RAGGED;
     FxWgradOperands fp32_fed{};
     fp32_fed.ragged = ragged;
@@ -1208,9 +1273,10 @@ static ConvRoute conv_route(FxPass pass, const p3d_conv_desc* d, int masks /* fa
     if (pass != FX_WGRAD && workspace_bytes < r.x3_bytes) return ConvRoute{ConvRoute::FP32_MFMA, 0};
     return r;
 }
-// what a query reserves for the x3 families: the larger of the dense and the masked route
+// what a query reserves for the x3 families: the larger of the dense and the masked route (but for X3_STRIDED_RAGGED, which the data-gradient query adds itself)
 static size_t x3_query_bytes(FxPass pass, const p3d_conv_desc* d) {
-    const size_t dense = conv_route(pass, d, 0, false, false, true, SIZE_MAX).x3_bytes, masked = conv_route(pass, d, 2, false, false, true, SIZE_MAX).x3_bytes;
+    const ConvRoute dr = conv_route(pass, d, 0, false, false, true, SIZE_MAX);
+    const size_t dense = dr.family == ConvRoute::X3_STRIDED_RAGGED ? 0 : dr.x3_bytes, masked = conv_route(pass, d, 2, false, false, true, SIZE_MAX).x3_bytes;
     return dense > masked ? dense : masked;
 }
 // the FxFuse of a routed call (pmask: the operand's factor, emask: the result's; the weight gradient: dy's and x's)
@@ -1317,9 +1383,15 @@ int32_t p3d_conv2d_bn_eval_fwd(const p3d_conv_desc* d, const float* x, const flo
     return conv2d_fwd_impl(d, x, w, nullptr, nullptr, nullptr, y, (char*)workspace + head, workspace_bytes - head, stream, coef, coef + d->K, res, relu);
 }
 
-size_t p3d_conv2d_dgrad_workspace_bytes(const p3d_conv_desc* d) {
-    if (validate(d)) return 0;
-    const size_t fx = x3_query_bytes(FX_DGRAD, d);
+// strided_any false: what the query answers with p3d_x3_any_strided_enable off -- all the fp32-MFMA strided path asks for, so a call that fell back to it for a
+// workspace too small for the class planes of X3_STRIDED_RAGGED runs as it does with the switch off.  true: while that switch is on, the class-plane plan too for
+// every shape its predicate admits (aligned ones included, which never use it: one rule for the caller)
+static size_t dgrad_workspace_bytes(const p3d_conv_desc* d, bool strided_any) {
+    size_t fx = x3_query_bytes(FX_DGRAD, d);
+    if (strided_any && fx_any_strided_enabled() && fx_dgrad_strided_any_applies(d)) {
+        const size_t planes = fx_dgrad_strided_any_plan(d).workspace;
+        if (planes > fx) fx = planes;
+    }
     if (d->stride == 1) {
         const SplitPlan pl = plan_dgrad1(d, true);
         const size_t base = weight_image_bytes(d) + (pl.splits > 1 ? (size_t)pl.splits * d->N * d->C * d->H * d->W * sizeof(float) : 0);
@@ -1329,6 +1401,20 @@ size_t p3d_conv2d_dgrad_workspace_bytes(const p3d_conv_desc* d) {
     const size_t staged = (size_t)d->stride * d->stride * d->N * d->C * hc * wc * sizeof(float);
     return staged > fx ? staged : fx;
 }
+size_t p3d_conv2d_dgrad_workspace_bytes(const p3d_conv_desc* d) {
+    if (validate(d)) return 0;
+    return dgrad_workspace_bytes(d, true);
+}
+
+// the finishing pass of X3_STRIDED_RAGGED (and kernel 1 of the test hook p3d_dgrad_interleave): a bounded grid, the kernel strides over the rest
+static int32_t launch_interleave_rows(const float* stage, float* dx, const float* mask_in, int N, int C, int H, int W, size_t cls_stride, int live, int accumulate, hipStream_t st) {
+    const int64_t total = (int64_t)N * C * H * W;
+    P3D_REQUIRE(total < (1ll << 31), "dgrad_interleave_rows: the tensor exceeds 2^31 elements");
+    const int64_t blocks = ceil_div(ceil_div(total, 4), 256);
+    hipLaunchKernelGGL(dgrad_interleave_rows_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, stage, dx, mask_in, (unsigned)total, C, H, W, cls_stride,
+                       live, accumulate, aligned16(dx) ? 1 : 0);
+    return check_launch("conv2d_dgrad interleave rows");
+}
 
 int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, const float* mult,
                          const float* mask_in, float* dx, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1337,6 +1423,14 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
     P3D_REQUIRE(dy && w && dx, "conv2d_dgrad: null tensor");
     ProfScope ps(1, d, (hipStream_t)stream);
     const ConvRoute route = conv_route(FX_DGRAD, d, (mask_in != nullptr) + (mult != nullptr), false, false, aligned16(dy, w, dx, workspace, mask_in, mult), workspace_bytes);
+    if (route.family == ConvRoute::X3_STRIDED_RAGGED) {      // the parity classes as ragged launches into class planes; the interleave writes the dead classes' zeros
+        fx_count(1, d);
+        int live = 0;
+        if (int32_t e = fx_conv_dgrad_strided_any(d, dy, w, workspace, workspace_bytes, &live, (hipStream_t)stream)) return e;
+        const FxStridedPlan pl = fx_dgrad_strided_any_plan(d);
+        return launch_interleave_rows((const float*)((const char*)workspace + pl.stage_offset), dx, nullptr, d->N, d->C, d->H, d->W, pl.cls_stride, live, d->accumulate,
+                                      (hipStream_t)stream);
+    }
     if (route.family != ConvRoute::FP32_MFMA) {
         fx_count(1, d);
         if (int32_t e = fx_dgrad_zero_dead_classes(d, dx, (hipStream_t)stream)) return e;      // input pixels no tap reaches (1x1, stride 2) must read zero
@@ -1390,7 +1484,7 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
     }
     // stride > 1: parity classes of input pixels, each a dense GEMM over the taps that reach it, written class-major to the
     // staging buffer with full-line stores, then interleaved into dx (mask and accumulate applied there) in one streaming pass
-    const size_t need = p3d_conv2d_dgrad_workspace_bytes(d);
+    const size_t need = dgrad_workspace_bytes(d, false);
     if (!workspace || workspace_bytes < need) {
         set_error("conv2d_dgrad: strided path needs a %zu B workspace (got %zu)", need, workspace_bytes);
         return P3D_EWORKSPACE;
@@ -1485,6 +1579,20 @@ int32_t p3d_x3_any_partial_enable(int32_t on) { return fx_set_any_partial_enable
 int32_t p3d_conv2d_fwd_masked_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && masked_any_ok(FX_FWD, d) ? 1 : 0; }
 int32_t p3d_conv2d_dgrad_masked_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && masked_any_ok(FX_DGRAD, d) ? 1 : 0; }
 int32_t p3d_conv2d_wgrad_masked_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && masked_any_ok(FX_WGRAD, d) ? 1 : 0; }
+int32_t p3d_x3_any_strided_enable(int32_t on) { return fx_set_any_strided_enabled(on); }
+// what the stride-2 class launches admit, whatever the switch says
+int32_t p3d_conv2d_dgrad_strided_any_supported(const p3d_conv_desc* d) { return d && !validate(d) && fx_dgrad_strided_any_applies(d) ? 1 : 0; }
+// Test hook: the two interleave kernels alone on the same class planes, at stride 2
+int32_t p3d_dgrad_interleave(int32_t kernel, const float* stage, float* dx, const float* mask_in, int32_t N, int32_t C, int32_t H, int32_t W, size_t cls_stride,
+                             int32_t live_mask, int32_t accumulate, void* stream) {
+    P3D_REQUIRE(stage && dx && N > 0 && C > 0 && H > 0 && W > 0 && (kernel == 0 || kernel == 1), "dgrad_interleave: null tensor, empty shape, or a kernel other than 0 / 1");
+    P3D_REQUIRE(cls_stride >= (size_t)N * C * ((H + 1) / 2) * ((W + 1) / 2) && live_mask >= 0 && live_mask < 16, "dgrad_interleave: the class planes overlap, or a bad class mask");
+    if (kernel == 1) return launch_interleave_rows(stage, dx, mask_in, N, C, H, W, cls_stride, live_mask, accumulate, (hipStream_t)stream);
+    const int64_t total = (int64_t)N * C * H * W;
+    const unsigned blocks = (unsigned)(ceil_div(total, 256) < 8192 ? ceil_div(total, 256) : 8192);
+    hipLaunchKernelGGL(dgrad_interleave_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, stage, dx, mask_in, N * C, C, H, W, 2, cls_stride, live_mask, accumulate);
+    return check_launch("dgrad_interleave");
+}
 void p3d_fx_tune(int32_t what, int32_t value) { fx_tune(what, value); }
 
 void p3d_conv_last_fp32_launch(int32_t* out) {

@@ -128,6 +128,8 @@ bool fx_any_partial_enabled();          // p3d_x3_any_partial_enable / P3D_X3_AN
 int fx_set_any_partial_enabled(int on);
 bool fx_any_images_enabled();           // p3d_x3_any_images_enable / P3D_X3_ANY_IMAGES=1 (default off): image-feeding callers (ops_block.ConvImagesFn) use the ragged image-fed entries where the aligned query refuses; kept for them, read by no entry point
 int fx_set_any_images_enabled(int on);
+bool fx_any_strided_enabled();          // p3d_x3_any_strided_enable / P3D_X3_ANY_STRIDED=1 (default off): p3d_conv2d_dgrad runs dense stride-2 data gradients the aligned predicate refuses as ragged class launches
+int fx_set_any_strided_enabled(int on);
 void fx_count(int kind, const p3d_conv_desc* d);
 void fx_stats(unsigned long long* counts, double* flops, int reset);
 // the log of forward / data-gradient conv-kernel launches and the list of compiled instances (p3d_fx_launch_log, p3d_fx_conv_instances: include/p3d_hip.h)
@@ -140,6 +142,14 @@ int32_t fx_conv_instances(int32_t* out, int32_t max_records);
 enum FxPass { FX_FWD, FX_DGRAD, FX_WGRAD };
 bool fx_applies(FxPass pass, const p3d_conv_desc* d, int min_m = 96, bool ragged = false);
 bool fx_masked_applies(FxPass pass, const p3d_conv_desc* d, bool ragged = false);      // partial convolutions: the masked instances take no bias (ragged: all three passes -- inference and, under p3d_x3_any_partial_enable, training; the data gradient stride 1 only)
+// the stride-2 data gradient at any map side: fx_applies(FX_DGRAD) for stride 2 without its H % 2, W % 8 and width clauses, whole weights only
+bool fx_dgrad_strided_any_applies(const p3d_conv_desc* d, int min_m = 96);
+// ... its workspace (the weight image, then four tight class planes [N C][OHc][OWc] cls_stride floats apart, plane ph * 2 + pw; each part on a 256-B line) and its class
+// launches: one ragged fp32-fed launch per live, non-empty parity class into its plane.  live_mask: bit cls set where a tap reaches the class.  The caller interleaves
+// the planes into dx (dgrad_interleave_rows_kernel, p3d_conv.hip)
+struct FxStridedPlan { size_t stage_offset, cls_stride, workspace; };      // bytes, floats, bytes
+FxStridedPlan fx_dgrad_strided_any_plan(const p3d_conv_desc* d);
+int32_t fx_conv_dgrad_strided_any(const p3d_conv_desc* d, const float* dy, const float* w, void* workspace, size_t workspace_bytes, int* live_mask, hipStream_t st);
 size_t fx_workspace(FxPass pass, const p3d_conv_desc* d, bool ragged = false);         // FX_FWD / FX_DGRAD: weight image + split-K slabs of the call's plan; FX_WGRAD: slabs for the larger of the two
                                                                                        // split counts (fp32- or image-fed x), what a caller reserves before it knows which
 int fx_partial_rows(FxPass pass, const p3d_conv_desc* d);                              // FX_FWD / FX_DGRAD: rows of the per-channel partial sums of a launch with a sums epilogue

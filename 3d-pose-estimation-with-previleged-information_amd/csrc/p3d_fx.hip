@@ -1994,6 +1994,14 @@ bool fx_any_images_enabled() {
     return g_fx_any_images == 1;
 }
 int fx_set_any_images_enabled(int on) { const int before = fx_any_images_enabled() ? 1 : 0; g_fx_any_images = on ? 1 : 0; return before; }
+// p3d_x3_any_strided_enable: p3d_conv2d_dgrad offers dense stride-2 data gradients the aligned predicate refuses to the ragged instances, one launch per parity class
+// into tight class planes (fx_conv_dgrad_strided_any).  A switch of its own: it looks at none of the other three and none of them at it
+static int g_fx_any_strided = -1;
+bool fx_any_strided_enabled() {
+    if (g_fx_any_strided < 0) { const char* e = getenv("P3D_X3_ANY_STRIDED"); g_fx_any_strided = (e && atoi(e) == 1) ? 1 : 0; }      // default OFF
+    return g_fx_any_strided == 1;
+}
+int fx_set_any_strided_enabled(int on) { const int before = fx_any_strided_enabled() ? 1 : 0; g_fx_any_strided = on ? 1 : 0; return before; }
 
 // coverage counters (launches routed here vs to the fp32-MFMA kernel), read by bench.py so that no fallback goes uncounted
 static std::mutex g_fx_count_mu;
@@ -2019,6 +2027,10 @@ static bool fx_common(const p3d_conv_desc* d) {
 // The shape rule of each pass, written once.  `ragged`: the instances that take any map width (fx_conv_kernel's RAG instances, fx_wgrad_any_kernel) -- the same rule
 // with its width / alignment clauses switched off, and for the data gradient "stride 1 only" switched on (the parity classes of an odd map differ in size: the
 // fp32-MFMA kernel keeps those).
+// the data gradient's clauses that do not look at the map: reduction channels K in steps of 16, a reasonably filled channel tile; and, of a stride-2 one, that
+// every parity class is a dense GEMM over an arithmetic progression of taps
+static bool fx_dgrad_channels(const p3d_conv_desc* d, int min_m) { return d->K % FX_BK == 0 && d->K >= 32 && d->C % 4 == 0 && d->C >= min_m; }
+static bool fx_dgrad_class_taps(const p3d_conv_desc* d) { return d->pad == d->dil * (d->R - 1) / 2 && (d->R == 1 || d->dil == 1); }
 bool fx_applies(FxPass pass, const p3d_conv_desc* d, int min_m, bool ragged) {
     if (!fx_common(d)) return false;
     const bool widths = ragged || (d->W % 4 == 0 && d->Wo % 4 == 0);      // four consecutive pixels of one row per 16-B access
@@ -2026,14 +2038,19 @@ bool fx_applies(FxPass pass, const p3d_conv_desc* d, int min_m, bool ragged) {
         case FX_FWD:          // reduction channels C in steps of 16, a reasonably filled channel tile
             return widths && d->C % FX_BK == 0 && d->C >= 32 && d->K >= min_m;
         case FX_DGRAD:        // reduction channels K in steps of 16; the GEMM columns are the pixels of one stride^2 parity class of the input
-            if (!(widths && d->K % FX_BK == 0 && d->K >= 32 && d->C % 4 == 0 && d->C >= min_m)) return false;
+            if (!(widths && fx_dgrad_channels(d, min_m))) return false;
             if (d->stride == 1) return true;
-            return !ragged && d->H % 2 == 0 && d->W % 8 == 0 && d->pad == d->dil * (d->R - 1) / 2 && (d->R == 1 || d->dil == 1);      // stride 2: classes of equal size
+            return !ragged && d->H % 2 == 0 && d->W % 8 == 0 && fx_dgrad_class_taps(d);      // stride 2: classes of equal size
         case FX_WGRAD:        // the reduction runs over pixels in steps of 16; 32-bit byte offsets into whole tensors
             if ((int64_t)d->N * d->C * d->H * d->W >= (1ll << 29) || (int64_t)d->N * d->K * d->Ho * d->Wo >= (1ll << 29)) return false;
             return (ragged || (widths && (d->Ho * d->Wo) % FX_BK == 0)) && d->K >= min_m && d->C >= min_m && (d->R == 1 || d->C % 64 == 0);
     }
     return false;
+}
+// The stride-2 data gradient at ANY map side (p3d_x3_any_strided_enable): fx_applies(FX_DGRAD) for stride 2 without its H % 2, W % 8 and width clauses, whole weights
+// only (the call builds its weight image; nothing that feeds a channel window lands here).  It admits aligned shapes too; those stay on the aligned instances.
+bool fx_dgrad_strided_any_applies(const p3d_conv_desc* d, int min_m) {
+    return fx_common(d) && d->c_offset == 0 && d->c_total == d->C && d->stride == 2 && fx_dgrad_channels(d, min_m) && fx_dgrad_class_taps(d);
 }
 
 // p3d_fx_tune(0 / 1 / 2, n): forced split counts (weight gradient, forward / data gradient) and a forced weight-gradient block target; 0 = the built-in plan
@@ -2394,7 +2411,7 @@ int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_f
 enum { FXL_KERNEL = 0, FXL_AMODE, FXL_PRO, FXL_EPI, FXL_TAPI, FXL_RAG, FXL_ROWS, FXL_GRID_X, FXL_GRID_Y, FXL_GRID_Z, FXL_KCHUNK, FXL_FINISH, FXL_FINISH_GROUPS,
        FXL_FIELDS = P3D_FX_LAUNCH_FIELDS };
 static_assert(FXL_FINISH_GROUPS < FXL_FIELDS && FXL_ROWS + 1 == P3D_FX_INSTANCE_FIELDS, "the record of p3d_fx_launch_log outgrew its documented length");
-enum { FX_FINISH_NONE = 0, FX_FINISH_REDUCE0, FX_FINISH_REDUCE1, FX_FINISH_REDUCE2, FX_FINISH_REDUCE_ANY };       // FXL_FINISH
+enum { FX_FINISH_NONE = 0, FX_FINISH_REDUCE0, FX_FINISH_REDUCE1, FX_FINISH_REDUCE2, FX_FINISH_REDUCE_ANY, FX_FINISH_INTERLEAVE_ROWS };       // FXL_FINISH
 constexpr int FX_LOG_MAX = 256;
 static std::mutex g_fx_log_mu;
 static int32_t g_fx_log[FX_LOG_MAX][FXL_FIELDS];
@@ -2618,6 +2635,66 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
         if (int32_t e = fx_launch_conv(p, img, pro, epi, bm, dim3((unsigned)(p.tiles_m * tiles_n), 1, (unsigned)ncls), st, false, rows)) return e;
     }
     return check_launch("fx_conv_dgrad");
+}
+
+// The stride-2 data gradient at any map side (fx_dgrad_strided_any_applies): parity class (ph, pw) of the input is a dense [N][C][OHc][OWc] result of its own,
+// OHc = (H - ph + 1) / 2 rows of OWc = (W - pw + 1) / 2 pixels, so each live, non-empty class is ONE launch of the ragged fp32-fed instance over dy -- the taps that reach
+// the class from fill_class, as in fx_conv_dgrad -- into its tight plane stage + cls * cls_stride (cls = ph * 2 + pw), the layout the fp32-MFMA path stages its classes
+// in.  The caller interleaves the planes into dx (p3d_conv.hip: dgrad_interleave_rows_kernel, which also writes the zeros of the classes no tap reaches and adds under
+// `accumulate`).  The workspace: the data-gradient weight image, built here, then the four planes, each part on a 256-B line; cls_stride is rounded up to four floats,
+// so every plane starts on a 16-B line.  No class launch is split along K.
+FxStridedPlan fx_dgrad_strided_any_plan(const p3d_conv_desc* d) {
+    FxStridedPlan s{};
+    s.cls_stride = ((size_t)d->N * d->C * ((d->H + 1) / 2) * ((d->W + 1) / 2) + 3) & ~(size_t)3;
+    s.stage_offset = align256(fx_weight_image_bytes(d->K, d->C, d->R * d->S, true));
+    s.workspace = s.stage_offset + align256(4 * s.cls_stride * sizeof(float));
+    return s;
+}
+int32_t fx_conv_dgrad_strided_any(const p3d_conv_desc* d, const float* dy, const float* w, void* workspace, size_t workspace_bytes, int* live_mask, hipStream_t st) {
+    P3D_REQUIRE(fx_dgrad_strided_any_applies(d, 32), "fx_conv_dgrad_strided_any: shape outside the stride-2 rule of the x3 kernels");
+    const FxStridedPlan pl = fx_dgrad_strided_any_plan(d);
+    if (!workspace || workspace_bytes < pl.workspace) { set_error("fx_conv_dgrad_strided_any: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
+    char* ws = (char*)workspace;
+    const int RS = d->R * d->S;
+    if (int32_t e = fx_build_weight_images(w, d->K, d->C, RS, nullptr, ws, st, d->c_total, d->c_offset)) return e;
+    float* stage = (float*)(ws + pl.stage_offset);
+    FxConvParams p{};
+    p.X = dy; p.Wimg = (const unsigned char*)ws;
+    p.N = d->N; p.Cred = d->K; p.Hi = d->Ho; p.Wi = d->Wo; p.M = d->C;
+    p.R = d->R; p.S = d->S;
+    p.oy0 = 0; p.ox0 = 0; p.oys = 1; p.oxs = 1; p.hmul = 1; p.wmul = 1;
+    p.tiles_m = (int)ceil_div(d->C, FX_BM);
+    struct { int r0, step, n, off0, offstep; } ax[2][2];      // fill_class per axis (rows, columns) and parity
+    for (int par = 0; par < 2; ++par) {
+        fill_class(par, d->R, 2, d->pad, d->dil, &ax[0][par].r0, &ax[0][par].step, &ax[0][par].n, &ax[0][par].off0, &ax[0][par].offstep);
+        fill_class(par, d->S, 2, d->pad, d->dil, &ax[1][par].r0, &ax[1][par].step, &ax[1][par].n, &ax[1][par].off0, &ax[1][par].offstep);
+    }
+    FxConvParams cls[4];
+    int ncls = 0, live = 0;
+    for (int ph = 0; ph < 2; ++ph)
+        for (int pw = 0; pw < 2; ++pw) {
+            const auto &ty = ax[0][ph], &tx = ax[1][pw];
+            if (ty.n == 0 || tx.n == 0) continue;      // no tap reaches the class: the interleave writes its zeros, the plane is never read
+            live |= 1 << (ph * 2 + pw);
+            FxConvParams c = p;
+            c.OH = c.YH = (d->H - ph + 1) / 2; c.OW = c.YW = (d->W - pw + 1) / 2; c.NP = d->N * c.OH * c.OW;
+            if (c.NP == 0) continue;                   // (a map one pixel high or wide has no odd row or column)
+            c.nR = ty.n; c.nS = tx.n; c.ntap = ty.n * tx.n; c.r0 = ty.r0; c.rstep = ty.step; c.s0 = tx.r0; c.sstep = tx.step;
+            c.hoff = ty.off0; c.hstep = -ty.offstep;
+            c.woff = tx.off0; c.wstep = -tx.offstep;
+            c.Y = stage + (size_t)(ph * 2 + pw) * pl.cls_stride;
+            cls[ncls++] = c;
+        }
+    // the classes with the most taps first: the short ones fill the tail
+    for (int i = 1; i < ncls; ++i)
+        for (int j = i; j > 0 && cls[j].ntap > cls[j - 1].ntap; --j) { const FxConvParams t = cls[j]; cls[j] = cls[j - 1]; cls[j - 1] = t; }
+    for (int i = 0; i < ncls; ++i) {
+        const dim3 grid((unsigned)(cls[i].tiles_m * ceil_div(cls[i].NP, FX_BN)), 1);
+        if (int32_t e = fx_launch_conv(cls[i], false, 0, FX_EPI_STORE, 0, grid, st, true, false, i == ncls - 1 ? FX_FINISH_INTERLEAVE_ROWS : FX_FINISH_NONE, 0)) return e;
+    }
+    prof_kernel_done(st);
+    if (live_mask) *live_mask = live;
+    return check_launch("fx_conv_dgrad_strided_any");
 }
 
 // input pixels of a strided 1x1 that no tap reaches: fx_conv_dgrad leaves them untouched, so a caller that does not accumulate zero-fills dx first

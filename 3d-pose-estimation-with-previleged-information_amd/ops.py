@@ -942,6 +942,13 @@ def x3_any_partial(on):
     return bool(lib().p3d_x3_any_partial_enable(int(bool(on))))
 
 
+def x3_any_strided(on):
+    """Opt-in, OFF by default (P3D_X3_ANY_STRIDED=1 turns it on), independent of x3_any, x3_any_partial and x3_any_images: the per-layer training path runs dense
+    STRIDE-2 data gradients on the x3 kernels at maps the aligned kernels refuse -- the 129 -> 65 -> 33 -> 17 transitions of the default 257 crop, layers of 96 input
+    channels or more -- as one ragged launch per parity class and one interleave pass, instead of the fp32-MFMA kernels.  Returns the previous setting."""
+    return bool(lib().p3d_x3_any_strided_enable(int(bool(on))))
+
+
 def x3_any_images(on):
     """Opt-in, OFF by default (P3D_X3_ANY_IMAGES=1 turns it on), independent of x3_any and x3_any_partial: multi-tap convolutions that travel as pre-split images
     (ops_block.ConvImagesFn: nn.Conv2d called without a join, 64 input channels or more -- the regressor and the stride-1 3x3 layers of the per-layer path) do so at

@@ -122,6 +122,27 @@ int32_t p3d_x3_any_partial_enable(int32_t on);
 int32_t p3d_conv2d_fwd_masked_any_supported(const p3d_conv_desc* d);
 int32_t p3d_conv2d_dgrad_masked_any_supported(const p3d_conv_desc* d);
 int32_t p3d_conv2d_wgrad_masked_any_supported(const p3d_conv_desc* d);
+/* Opt-in, a switch of its own (default OFF; P3D_X3_ANY_STRIDED=1 in the environment turns it on; independent of the other three): p3d_conv2d_dgrad runs a dense
+ * STRIDE-2 data gradient that the aligned predicate refuses (an odd side, W no multiple of 8: the 129 -> 65 -> 33 -> 17 maps of the default 257 crop) on the x3 kernels
+ * instead of the fp32-MFMA kernels: one launch of the ragged fp32-fed instance per parity class of the input -- class (ph, pw) has (H - ph + 1) / 2 rows of
+ * (W - pw + 1) / 2 pixels -- into tight class planes in the workspace, then one streaming pass (dgrad_interleave_rows_kernel) that interleaves the planes into dx, writes
+ * +0 to the pixels no tap reaches (a 1x1: three of four) and adds what dx held under `accumulate` ("Stride-2 data gradients at any map width").
+ * While it is on, p3d_conv2d_dgrad_workspace_bytes reports for the shapes the predicate admits at least the data-gradient weight image plus four class planes of
+ * N C ceil(H / 2) ceil(W / 2) floats (rounded up to 4), each part on a 256-B line.  A workspace that is too small, or an operand off a 16-B line, quietly runs on
+ * fp32-MFMA as with the switch off.  Partial convolutions, aligned shapes, stride-1 calls and every other entry are launched exactly as with the switch off.  Returns
+ * the previous setting.
+ * p3d_conv2d_dgrad_strided_any_supported: 1 where the class launches admit the convolution (whatever the switch says; aligned shapes too, which the entry keeps on the
+ * aligned instances): the stride-2 data-gradient rule of the x3 kernels without its clauses on H and W -- whole weights, odd square filter, K in steps of 16 and >= 32,
+ * C in steps of 4 and >= 96, pad == dil (R - 1) / 2, R == 1 or dil == 1.  0 otherwise, for stride 1 and for a NULL or malformed descriptor. */
+int32_t p3d_x3_any_strided_enable(int32_t on);
+int32_t p3d_conv2d_dgrad_strided_any_supported(const p3d_conv_desc* d);
+/* TEST HOOK (tests/test_strided_any_gpu.py, tools/train_anysize_bench.py; nothing in the package calls it): the finishing pass of a stride-2 data gradient alone.
+ * dx[n][c][hi][wi] (=|+=, by accumulate) stage[cls * cls_stride + ((n C + c) hc + hi / 2) wc + wi / 2] (* mask_in[n][hi][wi] when given), cls = (hi & 1) * 2 + (wi & 1),
+ * hc = (H - (hi & 1) + 1) / 2, wc = (W - (wi & 1) + 1) / 2; a class whose bit in live_mask is clear contributes 0 and its plane is not read.  kernel 0:
+ * dgrad_interleave_kernel (the fp32-MFMA path's, one element per thread); kernel 1: dgrad_interleave_rows_kernel (p3d_x3_any_strided_enable's).  The two are bit-equal.
+ * cls_stride in floats, at least N C ceil(H / 2) ceil(W / 2); N C H W < 2^31 for kernel 1. */
+int32_t p3d_dgrad_interleave(int32_t kernel, const float* stage, float* dx, const float* mask_in, int32_t N, int32_t C, int32_t H, int32_t W, size_t cls_stride,
+                             int32_t live_mask, int32_t accumulate, void* stream);
 /* Test and tuning hooks of the x3 path; value 0 restores the built-in behaviour unless noted.  Codes:
  *   0  forced split count of the weight-gradient launches                  (tools/split_sweep.py, tests/test_kernels_gpu.py)
  *   1  forced split count of the forward / data-gradient launches          (the same)
@@ -339,8 +360,9 @@ int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, co
  *       factor code is the instance without the factor (0 store, 1 statistics, 2 backward sums, 4 factor, 5 / 6 factor with 1 / 2, 7 factor image-fed, 8 inference,
  *       9 inference with factor)   [4] TAPI (1: taps innermost), as launched   [5] RAG (any map width)   [6] ROWS (fp32 row image)  -- the kernel's template arguments
  *   [7] grid.x   [8] grid.y (split-K slabs)   [9] grid.z (parity classes of a strided data gradient in one launch)   [10] kchunk: K steps per slab, 0 unsplit
- *   [11] the pass that followed: 0 none, 1 fx_reduce_kernel<0>, 2 fx_reduce_kernel<1>, 3 fx_reduce_kernel<2>, 4 fx_reduce_any_kernel   [12] its grid.y (the image groups
- *        of fx_reduce_kernel = the rows of its partial sums; 1 for fx_reduce_any_kernel; 0 with [11] 0)
+ *   [11] the pass that followed: 0 none, 1 fx_reduce_kernel<0>, 2 fx_reduce_kernel<1>, 3 fx_reduce_kernel<2>, 4 fx_reduce_any_kernel, 5 dgrad_interleave_rows_kernel (the
+ *        class launches of a stride-2 data gradient under p3d_x3_any_strided_enable: on the record of the LAST class launch)   [12] its grid.y (the image groups
+ *        of fx_reduce_kernel = the rows of its partial sums; 1 for fx_reduce_any_kernel; 0 with [11] 0 or 5)
  *   [13..15] 0
  * p3d_fx_launch_log: copies the records since the last reset into out, oldest first, at most max_records of them (the library keeps the first 256), and returns how
  * many launches there were since then -- more than max_records, or than 256, shows as a count above what was copied.  reset != 0: the log starts anew afterwards.

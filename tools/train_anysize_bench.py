@@ -16,6 +16,12 @@
               cached weight images, as ops_block.ConvImagesFn calls them), each pass alone, the image passes of x and dy on lines of their own and inside a per-layer
               total.  With --step: legs `any` (ops.x3_any alone) and `images` (ops.x3_any and ops.x3_any_images) alternating; `images` wins when it beats `any` by more
               than their combined spread.  (The `any` leg of a build without ops.x3_any_images: --step without --images, whose `on` leg it is.)
+  --strided   (depthnet; profiles/train_anysize_strided.md) stride-2 data gradients on the x3 kernels at the odd maps, ops.x3_any_strided.  With --classes: the four
+              stride-2 classes of ResNet-50 through p3d_conv2d_dgrad, the switch off (the fp32-MFMA kernel and its interleave) and on (the class launches and
+              dgrad_interleave_rows_kernel) alternating; then the finishing pass alone, p3d_dgrad_interleave kernel 0 against kernel 1 on the same planes, in ms and in
+              TB/s of the bytes it has to move (the live planes read, dx written); the class launches are the call less its interleave.  With --step: legs `any`
+              (ops.x3_any and ops.x3_any_images) and `strided` (those and ops.x3_any_strided) alternating, `strided` wins when it beats `any` by more than their
+              combined spread; --frozen: the same two legs of the frozen-fold step (model.freeze_batchnorm(), ops.frozen_fold).
 GPU box only."""
 import argparse
 import ctypes
@@ -58,12 +64,16 @@ def switch(on, partial=False):
         raise SystemExit('this build has no ops.x3_any_partial')
 
 
-def switch_leg(leg):
-    switch(leg in ('on', 'any', 'both', 'images'), leg == 'both')
+def switch_leg(leg, strided=False):
+    switch(leg in ('on', 'any', 'both', 'images', 'strided'), leg == 'both')
     if hasattr(ops, 'x3_any_images'):
-        ops.x3_any_images(leg == 'images')
+        ops.x3_any_images(leg == 'images' or strided)
     elif leg == 'images':
         raise SystemExit('this build has no ops.x3_any_images')
+    if hasattr(ops, 'x3_any_strided'):
+        ops.x3_any_strided(leg == 'strided')
+    elif leg == 'strided':
+        raise SystemExit('this build has no ops.x3_any_strided')
 
 
 def timed(fn, iters):
@@ -252,6 +262,63 @@ def classes_images(a):
     print('all passes: any %.2f ms  img %.2f ms' % (sum(total[(r, 'any')] for r in rows), sum(total[(r, 'img')] for r in rows)))
 
 
+def classes_strided(a):
+    """the stride-2 data gradients of ResNet-50 at the odd maps: the call with ops.x3_any_strided off and on, and the two interleave kernels alone"""
+    L = pkg._lib.lib()
+    P, stream = ops._p, ops._stream()
+    total = {'off': 0.0, 'on': 0.0}
+    for (c, h, k, ks, st, dil, cnt) in R50:
+        tag = 'c%d h%d k%d %dx%d s%d' % (c, h, k, ks, ks, st)
+        if st != 2 or (a.only and a.only not in tag):
+            continue
+        torch.manual_seed(c + k)
+        x_shape, w = (a.batch, c, h, h), torch.randn(k, c, ks, ks, device='cuda') / (k * ks * ks) ** 0.5
+        d = ops._desc(x_shape, w.shape, st, ks // 2, 1)
+        b = ctypes.byref(d)
+        assert L.p3d_conv2d_dgrad_strided_any_supported(b) == 1, tag
+        dy, dx = torch.randn(a.batch, k, d.Ho, d.Wo, device='cuda'), torch.empty(x_shape, device='cuda')
+        ops.x3_any_strided(True)
+        ws = torch.empty(L.p3d_conv2d_dgrad_workspace_bytes(b), dtype=torch.uint8, device='cuda')
+        fn = lambda: L.p3d_conv2d_dgrad(b, P(dy), P(w), None, None, P(dx), P(ws), ws.numel(), stream)
+        # the finishing pass alone, on planes of its own
+        hc = (h + 1) // 2
+        cls_stride = (a.batch * c * hc * hc + 3) // 4 * 4
+        stage = torch.randn(4 * cls_stride, device='cuda')
+        live = 0b1111 if ks > 1 else 0b0001
+        pixels = h * h if ks > 1 else hc * hc
+        nbytes = 4.0 * a.batch * c * (pixels + h * h)           # the live planes read, dx written
+        fin = {kern: (lambda kern=kern: L.p3d_dgrad_interleave(kern, P(stage), P(dx), None, a.batch, c, h, h, cls_stride, live, 0, stream)) for kern in (0, 1)}
+        ms, ran = {leg: [] for leg in ('off', 'on', 0, 1)}, {}
+        for leg in ('off', 'on'):
+            ops.x3_any_strided(leg == 'on')
+            ops.conv_path_stats(reset=True)
+            for _ in range(3):
+                assert fn() == 0, L.p3d_last_error()
+            ran[leg] = family(ops.conv_path_stats(reset=True), 'dgrad')
+        for kern in (0, 1):
+            for _ in range(3):
+                assert fin[kern]() == 0, L.p3d_last_error()
+        assert (ran['off'], ran['on']) == ('fp32', 'x3'), (tag, ran)
+        for _ in range(a.rounds):
+            for leg in ('off', 'on'):
+                ops.x3_any_strided(leg == 'on')
+                ms[leg].append(timed(fn, a.iters))
+            for kern in (0, 1):
+                ms[kern].append(timed(fin[kern], a.iters))
+        ops.x3_any_strided(False)
+        gf = 2.0 * a.batch * k * c * ks * ks * d.Ho * d.Wo / 1e9
+        m = {leg: med(v) for leg, v in ms.items()}
+        print('%-24s dgrad %7.2f GF | off %.3f [%.3f..%.3f] ms %5.1f TF | on %.3f [%.3f..%.3f] ms %5.1f TF | on/off %.2f' % (
+            (tag, gf) + m['off'] + (gf / m['off'][0],) + m['on'] + (gf / m['on'][0], m['on'][0] / m['off'][0])), flush=True)
+        print('%-24s interleave %6.1f MB | kernel 0 %.3f [%.3f..%.3f] ms %.2f TB/s | kernel 1 %.3f [%.3f..%.3f] ms %.2f TB/s | 1/0 %.2f' % (
+            (tag, nbytes / 1e6) + m[0] + (nbytes / m[0][0] / 1e9,) + m[1] + (nbytes / m[1][0] / 1e9, m[1][0] / m[0][0])), flush=True)
+        print('%-24s the call less its interleave | off %.3f ms %5.1f TF | on (weight image + class launches) %.3f ms %5.1f TF' % (
+            tag, m['off'][0] - m[0][0], gf / (m['off'][0] - m[0][0]), m['on'][0] - m[1][0], gf / (m['on'][0] - m[1][0])), flush=True)
+        total['off'] += m['off'][0] * cnt
+        total['on'] += m['on'][0] * cnt
+    print('sum over the classes x their layer counts, dgrad: off %.3f ms  on %.3f ms' % (total['off'], total['on']))
+
+
 def step(a):
     flags = ['-model', a.model, '-suffix', 'bench', '-data_name', 'h36m', '-save_path', '/tmp/p3d_bench', '-criterion', 'SmoothL1', '-num_joints', '17', '-side_in', str(a.side),
              '-stride', '16', '-depth', '16', '-depth_range', '1000', '-loss_div', '10', '-learn_rate', '5e-5', '-weight_decay', '4e-5', '-grad_norm', '5'] + FAMILY_FLAGS[a.family]
@@ -259,6 +326,9 @@ def step(a):
     torch.manual_seed(0)
     model, _ = pkg.depth_main.create_model(args)
     model = model.cuda().train()
+    if a.frozen:
+        model.freeze_batchnorm()
+        ops.frozen_fold(True)
     trainer = pkg.depth_train.Trainer(args, model, pkg.utils.get_info())
     trainer.verbose = False
     trainer.adapt_learn_rate(1)
@@ -271,6 +341,8 @@ def step(a):
         legs = ('off', 'any', 'both') if hasattr(ops, 'x3_any_partial') else ('off', 'any')
     if a.images:
         legs = ('any', 'images')
+    if a.strided:
+        legs = ('any', 'strided')
 
     def run(n):
         for i in range(n):
@@ -279,7 +351,7 @@ def step(a):
 
     ms, counts = {leg: [] for leg in legs}, {}
     for leg in legs:
-        switch_leg(leg)
+        switch_leg(leg, a.strided)
         run(a.warmup)
         torch.cuda.synchronize()
         ops.conv_path_stats(reset=True)
@@ -289,13 +361,16 @@ def step(a):
         counts[leg] = {fam: {p: st[fam][p][0] for p in PASSES} for fam in ('x3', 'fp32')}
     for r in range(a.rounds):
         for leg in legs:
-            switch_leg(leg)
+            switch_leg(leg, a.strided)
             run(2)
             torch.cuda.synchronize()
             ms[leg].append(timed(lambda: run(a.iters), 1) / a.iters)
             print('round %d %-3s %.3f ms/step' % (r, leg, ms[leg][-1]), flush=True)
-    switch(False)
+    switch_leg('off')
     out = {'side': a.side, 'batch': a.batch, 'model': a.model, 'launches_per_step': counts}
+    if a.frozen:
+        out['frozen_fold'] = True
+        ops.frozen_fold(False)
     if a.family != 'depthnet':
         out['family'] = a.family
     for leg in legs:
@@ -311,6 +386,11 @@ def step(a):
         out['gain_ms'] = round(out['any']['median_ms'] - out['images']['median_ms'], 3)
         out['combined_spread_ms'] = round(spread, 3)
         out['images_wins'] = bool(out['gain_ms'] > spread)
+    elif legs == ('any', 'strided'):
+        spread = (out['any']['max_ms'] - out['any']['min_ms']) + (out['strided']['max_ms'] - out['strided']['min_ms'])
+        out['gain_ms'] = round(out['any']['median_ms'] - out['strided']['median_ms'], 3)
+        out['combined_spread_ms'] = round(spread, 3)
+        out['strided_wins'] = bool(out['gain_ms'] > spread)
     elif legs == ('off', 'on'):
         spread = (out['off']['max_ms'] - out['off']['min_ms']) + (out['on']['max_ms'] - out['on']['min_ms'])
         out['gain_ms'] = round(out['off']['median_ms'] - out['on']['median_ms'], 3)
@@ -332,12 +412,16 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--only', default='')
     ap.add_argument('--images', action='store_true', help='the image-fed ragged path (ops.x3_any_images): see above')
+    ap.add_argument('--strided', action='store_true', help='stride-2 data gradients on the x3 kernels (ops.x3_any_strided): see above')
+    ap.add_argument('--frozen', action='store_true', help='--step --strided: the frozen-fold step (every BatchNorm frozen, ops.frozen_fold)')
     ap.add_argument('--family', default='depthnet', choices=sorted(FAMILY_FLAGS))
     a = ap.parse_args()
-    if a.images and a.family != 'depthnet':
-        raise SystemExit('--images measures the dense family')
+    if (a.images or a.strided) and a.family != 'depthnet':
+        raise SystemExit('--images and --strided measure the dense family')
+    if a.frozen and not (a.strided and a.step):
+        raise SystemExit('--frozen goes with --step --strided')
     if a.classes:
-        (classes_images if a.images else classes if a.family == 'depthnet' else classes_partial)(a)
+        (classes_strided if a.strided else classes_images if a.images else classes if a.family == 'depthnet' else classes_partial)(a)
     if a.step:
         step(a)
 
