@@ -115,7 +115,7 @@ def read_header(path):
 
 # CONSTANTS: the header's integer #defines (P3D_OK, P3D_EINVAL, P3D_FX_LAUNCH_FIELDS, P3D_EVAL_ROW, ...); SIGNATURES: name -> (restype, argtypes) of every function
 CONSTANTS, STRUCTS, SIGNATURES = read_header(HEADER_PATH)
-ConvDesc, FoldJob, FxFuse = STRUCTS['p3d_conv_desc'], STRUCTS['p3d_fold_job'], STRUCTS['p3d_fx_fuse']
+ConvDesc, FoldJob, FxFuse, FxWgradFuse = STRUCTS['p3d_conv_desc'], STRUCTS['p3d_fold_job'], STRUCTS['p3d_fx_fuse'], STRUCTS['p3d_fx_wgrad_fuse']
 
 _lib = None
 

@@ -1107,6 +1107,34 @@ int32_t p3d_fx_wgrad_plan(const p3d_conv_desc* d, int32_t operands, int32_t* out
     return fx_wgrad_plan_record(d, operands, out);
 }
 
+// What the weight-gradient launcher launched (include/p3d_hip.h)
+int32_t p3d_fx_wgrad_launch_log(int32_t* out, int32_t max_records, int32_t reset) { return fx_wgrad_launch_log(out, out && max_records > 0 ? max_records : 0, reset); }
+
+// Test hook: fx_conv_wgrad with any operands (include/p3d_hip.h).  Like p3d_fx_conv_fused it checks the pointers, the descriptor, the shape rule and the alignment, and
+// leaves every other refusal (the operand rule, the workspace) to the launcher.  No path count.
+static FxFuse wgrad_fuse(const p3d_fx_wgrad_fuse* f) {
+    FxFuse x{};
+    x.dy_img = f->dy_img; x.x_img = f->x_img; x.pmask = f->pmask; x.emask = f->emask; x.rows = f->rows != 0; x.ragged = f->ragged != 0;
+    return x;
+}
+// (0: a descriptor or a shape the hook refuses)
+size_t p3d_fx_conv_wgrad_fused_workspace_bytes(const p3d_conv_desc* d, const p3d_fx_wgrad_fuse* f) {
+    if (!f || !fused_desc_ok(d) || !fx_applies(FX_WGRAD, d, 32, f->ragged != 0)) return 0;
+    const FxFuse x = wgrad_fuse(f);
+    return fx_wgrad_plan(d, &x).slab_bytes;
+}
+int32_t p3d_fx_conv_wgrad_fused(const p3d_conv_desc* d, const p3d_fx_wgrad_fuse* f, const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    P3D_REQUIRE(d && f && dw && (dy || f->dy_img) && (x || f->x_img), "fx_conv_wgrad_fused: null argument");
+    P3D_REQUIRE(fused_desc_ok(d), "fx_conv_wgrad_fused: malformed descriptor");
+    P3D_REQUIRE(fx_applies(FX_WGRAD, d, 32, f->ragged != 0), "fx_conv_wgrad_fused: shape outside the x3 kernels");
+    // (dw may sit anywhere on a 4-B line, and be a channel window of a wider weight: wgrad_finish picks its accesses by the address)
+    P3D_REQUIRE(aligned16(dy, x, f->dy_img, f->x_img, workspace) && (f->ragged || aligned16(f->pmask, f->emask)) && (reinterpret_cast<uintptr_t>(dw) & 3) == 0,
+                "fx_conv_wgrad_fused: operands and workspace must be 16-B aligned, dw 4-B aligned");
+    const FxFuse fuse = wgrad_fuse(f);
+    return fx_conv_wgrad(d, dy, x, dw, d->accumulate, workspace, workspace_bytes, &fuse, "fx_conv_wgrad_fused", (hipStream_t)stream);
+}
+
 // Inference with folded BatchNorm (include/p3d_hip.h): the fold of a whole network in one launch, and the forward on the folded images with the inference epilogue.
 int32_t p3d_fx_fold_bn_images(const void* jobs, int32_t njobs, int32_t blocks, void* stream) {
     P3D_REQUIRE(jobs && njobs > 0 && blocks > 0, "fold_bn_images: bad argument");

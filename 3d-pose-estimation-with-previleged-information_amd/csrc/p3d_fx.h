@@ -191,6 +191,8 @@ inline FxWgradPlan fx_wgrad_plan(const p3d_conv_desc* d, const FxFuse* f) {
     return fx_wgrad_plan(d, f ? FxWgradOperands{f->dy_img != nullptr, f->x_img != nullptr, f->pmask != nullptr, f->emask != nullptr, f->rows != 0, f->ragged != 0} : FxWgradOperands{});
 }
 int32_t fx_wgrad_plan_record(const p3d_conv_desc* d, int operands, int32_t* out);      // the test hook p3d_fx_wgrad_plan (include/p3d_hip.h)
+// the log of weight-gradient launches (p3d_fx_wgrad_launch_log: include/p3d_hip.h): the plan that was launched, the finishing kernels behind it, `accumulate`
+int32_t fx_wgrad_launch_log(int32_t* out, int32_t max_records, int32_t reset);
 // plan -> workspace check ("<entry>: workspace %zu B < required %zu B", P3D_EWORKSPACE) -> slabs -> wgrad_finish: dw = (or +=, by `accumulate`) the weight gradient.
 // dy / x: the fp32 operands, ignored where the FxFuse holds the image.
 int32_t fx_conv_wgrad(const p3d_conv_desc* d, const float* dy, const float* x, float* dw, int accumulate, void* workspace, size_t workspace_bytes, const FxFuse* fuse,

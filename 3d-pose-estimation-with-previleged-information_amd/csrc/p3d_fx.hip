@@ -2812,10 +2812,52 @@ FxWgradPlan fx_wgrad_plan(const p3d_conv_desc* d, const FxWgradOperands& o) {
     return pl;
 }
 
-// the only launch of a weight-gradient kernel in the library (a plan that is `ok`, or the stem's: fx_wgrad_covered has its instance)
-static void fx_launch_wgrad(const FxWgradParams& p, const FxWgradPlan& pl, hipStream_t st) {
+// a plan as the 16 values of p3d_fx_wgrad_plan (include/p3d_hip.h): the hook's answer and the head of a launch record
+static void fx_wgrad_plan_fields(const FxWgradPlan& pl, int32_t* out) {
+    const int32_t rec[P3D_FX_WGRAD_PLAN_FIELDS] = {pl.family, pl.aimg, pl.bimg, pl.masked, pl.taps, pl.rows, pl.tile_taps, pl.splits, pl.spb, (int32_t)pl.grid.x, (int32_t)pl.grid.y,
+                                                  (int32_t)pl.grid.z, pl.order, pl.tapm, (int32_t)(pl.slab_bytes & 0xFFFFFFFFu), (int32_t)(pl.slab_bytes >> 32)};
+    for (int i = 0; i < P3D_FX_WGRAD_PLAN_FIELDS; ++i) out[i] = rec[i];
+}
+
+// ---- what the weight gradient launched (p3d_fx_wgrad_launch_log): one record per fx_launch_wgrad, layout documented in include/p3d_hip.h ----------------
+enum { FXWL_FINISH = P3D_FX_WGRAD_PLAN_FIELDS, FXWL_ACCUMULATE, FXWL_FIELDS = P3D_FX_WGRAD_LAUNCH_FIELDS };
+static_assert(FXWL_ACCUMULATE < FXWL_FIELDS, "the record of p3d_fx_wgrad_launch_log outgrew its documented length");
+constexpr int32_t FX_WGRAD_FIN_STEM = 256;       // fx_stem_dw_kernel, beside the FIN_ bits of wgrad_finish (p3d_conv.hip: 8 .. 128)
+static std::mutex g_fx_wlog_mu;
+static int32_t g_fx_wlog[FX_LOG_MAX][FXWL_FIELDS];
+static int64_t g_fx_wlog_n = 0;         // launches since the last reset (the first FX_LOG_MAX are kept)
+static int64_t g_fx_wlog_resets = 0;    // a reset between a launch and its finishing pass must not put the finishing bits onto another call's record
+struct FxWgradLogSlot { int64_t slot, resets; };
+int32_t fx_wgrad_launch_log(int32_t* out, int32_t max_records, int32_t reset) {
+    std::lock_guard<std::mutex> lock(g_fx_wlog_mu);
+    const int64_t kept = g_fx_wlog_n < FX_LOG_MAX ? g_fx_wlog_n : FX_LOG_MAX;
+    for (int64_t i = 0; out && i < kept && i < max_records; ++i)
+        for (int f = 0; f < FXWL_FIELDS; ++f) out[i * FXWL_FIELDS + f] = g_fx_wlog[i][f];
+    const int32_t n = (int32_t)(g_fx_wlog_n < INT32_MAX ? g_fx_wlog_n : INT32_MAX);
+    if (reset) { g_fx_wlog_n = 0; ++g_fx_wlog_resets; }
+    return n;
+}
+// the finishing kernels that followed a launch, onto its record: `at` is what fx_launch_wgrad returned (nothing to do for a launch the log did not keep)
+static void fx_wgrad_log_finish(FxWgradLogSlot at, int32_t finish) {
+    std::lock_guard<std::mutex> lock(g_fx_wlog_mu);
+    if (at.slot >= 0 && at.resets == g_fx_wlog_resets) g_fx_wlog[at.slot][FXWL_FINISH] = finish;
+}
+
+// the only launch of a weight-gradient kernel in the library (a plan that is `ok`, or the stem's: fx_wgrad_covered has its instance).  Writes the launch record from
+// the plan it launches; returns the record's place for fx_wgrad_log_finish (slot -1 where the log is full)
+static FxWgradLogSlot fx_launch_wgrad(const FxWgradParams& p, const FxWgradPlan& pl, int accumulate, hipStream_t st) {
     hipLaunchKernelGGL(fx_wgrad_instance(pl.family, pl.aimg, pl.bimg, pl.masked, pl.taps, pl.rows), pl.grid, dim3(256), 0, st, p);
     prof_kernel_done(st);
+    std::lock_guard<std::mutex> lock(g_fx_wlog_mu);
+    const FxWgradLogSlot at{g_fx_wlog_n < FX_LOG_MAX ? g_fx_wlog_n : -1, g_fx_wlog_resets};
+    if (at.slot >= 0) {
+        int32_t* r = g_fx_wlog[at.slot];
+        for (int f = 0; f < FXWL_FIELDS; ++f) r[f] = 0;
+        fx_wgrad_plan_fields(pl, r);
+        r[FXWL_ACCUMULATE] = accumulate;
+    }
+    ++g_fx_wlog_n;
+    return at;
 }
 
 // dw (=|+= by `accumulate`) of one convolution: plan -> workspace check (in the name of `entry`) -> slabs [split][k][tap][c] -> wgrad_finish
@@ -2838,11 +2880,14 @@ int32_t fx_conv_wgrad(const p3d_conv_desc* d, const float* dy, const float* x, f
         if (fuse->x_img) { p.Ximg = (const unsigned char*)fuse->x_img; p.x_plane = (size_t)d->N * d->C * d->H * d->W * 2; }
         p.amask = fuse->pmask; p.bmask = fuse->emask;
     }
-    fx_launch_wgrad(p, pl, st);
+    const FxWgradLogSlot at = fx_launch_wgrad(p, pl, accumulate, st);
     if (int32_t e = check_launch("fx_conv_wgrad")) return e;
     p3d_conv_desc dw_desc = *d;
     dw_desc.accumulate = accumulate;
-    return wgrad_finish(&dw_desc, p.slabs, pl.splits, pl.tapm, dw, st);
+    int32_t finish = 0;
+    const int32_t e = wgrad_finish(&dw_desc, p.slabs, pl.splits, pl.tapm, dw, st, &finish);
+    fx_wgrad_log_finish(at, finish);
+    return e;
 }
 
 
@@ -3054,9 +3099,7 @@ int32_t fx_wgrad_plan_record(const p3d_conv_desc* d, int operands, int32_t* out)
         pl = fx_wgrad_plan(d, o);
         if (!pl.ok) { set_error("fx_wgrad_plan: no instance takes these operands"); return P3D_EINVAL; }
     }
-    const int32_t rec[P3D_FX_WGRAD_PLAN_FIELDS] = {pl.family, pl.aimg, pl.bimg, pl.masked, pl.taps, pl.rows, pl.tile_taps, pl.splits, pl.spb, (int32_t)pl.grid.x, (int32_t)pl.grid.y,
-                                                  (int32_t)pl.grid.z, pl.order, pl.tapm, (int32_t)(pl.slab_bytes & 0xFFFFFFFFu), (int32_t)(pl.slab_bytes >> 32)};
-    for (int i = 0; i < P3D_FX_WGRAD_PLAN_FIELDS; ++i) out[i] = rec[i];
+    fx_wgrad_plan_fields(pl, out);
     return P3D_OK;
 }
 
@@ -3071,8 +3114,9 @@ int32_t fx_stem_wgrad(const float* dy, const float* mult, const void* x_img, flo
     const FxWgradPlan pl = fx_stem_wgrad_plan(N, H, W, K, mult != nullptr);
     p.nsplit = pl.splits; p.spb = pl.spb;
     p.amask = mult;      // partial convolution: dw = wgrad(dy * mult, x * mask_in); the image holds x * mask_in, dy is scaled on its way into LDS
-    fx_launch_wgrad(p, pl, st);
+    const FxWgradLogSlot at = fx_launch_wgrad(p, pl, accumulate, st);
     hipLaunchKernelGGL(fx_stem_dw_kernel, dim3((unsigned)K, 4), dim3(1024), 0, st, (const float*)workspace, p.nsplit, dw, K, Cin, accumulate);
+    fx_wgrad_log_finish(at, FX_WGRAD_FIN_STEM);
     return check_launch("fx_stem_wgrad");
 }
 

@@ -1141,6 +1141,20 @@ def fx_launch_log(reset=True):
     return [{n: int(out[i * FX_LAUNCH_LEN + j]) for j, n in enumerate(FX_LAUNCH_FIELDS)} for i in range(min(count, FX_LOG_MAX))], count
 
 
+# the record of p3d_fx_wgrad_launch_log: the plan of p3d_fx_wgrad_plan, the finishing kernels, `accumulate`; tests/test_x3_wgrad_instances_host.py holds these to the header
+FX_WGRAD_LAUNCH_FIELDS = ('family', 'aimg', 'bimg', 'masked', 'taps', 'rows', 'tile_taps', 'splits', 'spb', 'grid_x', 'grid_y', 'grid_z', 'order', 'tapm', 'slab_bytes_lo',
+                          'slab_bytes_hi', 'finish', 'accumulate')
+FX_WGRAD_LAUNCH_LEN = CONSTANTS['P3D_FX_WGRAD_LAUNCH_FIELDS']
+
+
+def fx_wgrad_launch_log(reset=True):
+    """The weight-gradient launches of the x3 path since the last reset (p3d_fx_wgrad_launch_log), oldest first: (records, count) with one tuple of FX_WGRAD_LAUNCH_LEN
+    values per kept record (the first of them named by FX_WGRAD_LAUNCH_FIELDS, the rest 0); count > len(records) when more than FX_LOG_MAX were made."""
+    out = (ctypes.c_int32 * (FX_WGRAD_LAUNCH_LEN * FX_LOG_MAX))()
+    count = lib().p3d_fx_wgrad_launch_log(out, FX_LOG_MAX, int(bool(reset)))
+    return [tuple(int(v) for v in out[i * FX_WGRAD_LAUNCH_LEN:(i + 1) * FX_WGRAD_LAUNCH_LEN]) for i in range(min(count, FX_LOG_MAX))], count
+
+
 def fx_conv_instances():
     """Every compiled instance of fx_conv_kernel / fx16_conv_kernel (p3d_fx_conv_instances) as a tuple of the first FX_INSTANCE_LEN values of FX_LAUNCH_FIELDS."""
     n = lib().p3d_fx_conv_instances(None, 0)

@@ -421,6 +421,39 @@ int32_t p3d_fx_conv_fused(int32_t pass, const p3d_conv_desc* d, const p3d_fx_fus
  * caller asks for; with bit 5 the rule without its width clauses; the stem: p3d_stem_supported's rule) and for operands no instance takes. */
 #define P3D_FX_WGRAD_PLAN_FIELDS 16
 int32_t p3d_fx_wgrad_plan(const p3d_conv_desc* d, int32_t operands, int32_t* out);
+/* What the x3 weight gradient launched: one record per launch of a weight-gradient kernel, written where the launch is made (every caller: p3d_conv2d_wgrad on the x3
+ * family, the image entries, p3d_block_bwd, p3d_stem_wgrad(_masked), p3d_fx_conv_wgrad_fused).  Host-side bookkeeping only, apart from p3d_fx_launch_log (which keeps the
+ * forward / data-gradient launches).  A record is P3D_FX_WGRAD_LAUNCH_FIELDS int32:
+ *   [0..15] the plan that was launched, in the layout of p3d_fx_wgrad_plan -- taken from the launch itself, not planned a second time
+ *   [16] the finishing kernels that followed, as bits: 8 wgrad_reduce_kernel, 16 wgrad_reduce_tapm_kernel, 32 wgrad_reduce16_kernel, 64 wgrad_reduce16_tapm_kernel,
+ *        128 slab_fold_kernel (then 8 or 16 over the 16 folded slabs) -- the finishing bits of p3d_conv_last_fp32_launch --, 256 fx_stem_dw_kernel (the stem)
+ *   [17] accumulate: dw += instead of dw =
+ *   [18..23] 0
+ * p3d_fx_wgrad_launch_log behaves like p3d_fx_launch_log: copies the records since the last reset into out, oldest first, at most max_records of them (the library keeps
+ * the first 256), returns how many launches there were since then, and with reset != 0 starts the log anew.  out may be NULL with max_records 0. */
+#define P3D_FX_WGRAD_LAUNCH_FIELDS 24
+int32_t p3d_fx_wgrad_launch_log(int32_t* out, int32_t max_records, int32_t reset);
+/* TEST HOOK (tests/test_x3_wgrad_instances_gpu.py; nothing in the package calls it): one weight-gradient call of the x3 kernels with any operands, so that every
+ * instance of fx_wgrad_kernel and the kernels for any map width can be checked alone.  dw (= or +=, by d->accumulate) = wgrad(dy * pmask, x * emask), into the input
+ * channels [d->c_offset, d->c_offset + C) of a weight with d->c_total of them.  dy / x: the fp32 operands, ignored where the image is set.  The fields of
+ * p3d_fx_wgrad_fuse, NULL / 0 = not used:
+ *   dy_img, x_img  the operand as a p3d_fx_act_image image (rows = 1: p3d_fx_row_image ones; ragged = 1: p3d_fx_act_image_any)
+ *   pmask, emask   partial convolution: per-pixel factor of dy ([N][1][Ho][Wo]) and of x ([N][1][H][W]); fp32 operands only -- an image carries its factor
+ *   rows           the images are row images      ragged  the kernels for any map width
+ * Checks the null arguments, the descriptor, the weight-gradient shape rule (32 channels on either side; ragged: without its width clauses) and the alignment: operands
+ * and workspace on 16-B lines, dw on a 4-B line.  Everything else is the launcher's: operands no instance takes give P3D_EINVAL, a short workspace P3D_EWORKSPACE, both
+ * before anything is launched.  Does not count in p3d_conv_path_stats.  Workspace: p3d_fx_conv_wgrad_fused_workspace_bytes (host-only; under the p3d_fx_tune settings in
+ * force; 0 for a descriptor or a shape the hook refuses). */
+typedef struct p3d_fx_wgrad_fuse {
+    const void* dy_img;
+    const void* x_img;
+    const float* pmask;
+    const float* emask;
+    int32_t rows, ragged;
+} p3d_fx_wgrad_fuse;
+size_t p3d_fx_conv_wgrad_fused_workspace_bytes(const p3d_conv_desc* d, const p3d_fx_wgrad_fuse* f);
+int32_t p3d_fx_conv_wgrad_fused(const p3d_conv_desc* d, const p3d_fx_wgrad_fuse* f, const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes,
+                                void* stream);
 
 /* Inference with eval-mode BatchNorm folded into the convolutions (infer.py): s = gamma / sqrt(var + eps), w' = w * s, b' = beta - mean * s (+ s * conv bias).
  * p3d_fx_fold_bn_images: ONE launch for a table of jobs (device array of p3d_fold_job); per job kind 0 writes the forward weight image of w' over the input

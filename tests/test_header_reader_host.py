@@ -9,7 +9,7 @@ import pytest
 import test_abi
 
 I32, I64, SZ, F32, F64, VP = ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
-STRUCTS = ('p3d_conv_desc', 'p3d_fold_job', 'p3d_fx_fuse', 'p3d_block_desc', 'p3d_block_io', 'p3d_hblock_io')
+STRUCTS = ('p3d_conv_desc', 'p3d_fold_job', 'p3d_fx_fuse', 'p3d_block_desc', 'p3d_block_io', 'p3d_hblock_io', 'p3d_fx_wgrad_fuse')
 
 
 def fields(cls):
@@ -126,7 +126,7 @@ def test_the_constants_and_the_class_names(pkg):
         (0, 1, 2, 3, 4, 10, 11, 12, 13)
     assert 'P3D_HIP_H' not in c
     assert set(L.STRUCTS) == set(STRUCTS)
-    assert (L.ConvDesc, L.FoldJob, L.FxFuse, pkg.ops_block.BlockDesc, pkg.ops_block.BlockIO, pkg.ops_half.HBlockIO) == tuple(L.STRUCTS[n] for n in STRUCTS)
+    assert (L.ConvDesc, L.FoldJob, L.FxFuse, pkg.ops_block.BlockDesc, pkg.ops_block.BlockIO, pkg.ops_half.HBlockIO, L.FxWgradFuse) == tuple(L.STRUCTS[n] for n in STRUCTS)
 
 
 def test_struct_layouts_are_the_c_compilers(pkg, tmp_path):
