@@ -997,23 +997,57 @@ static IgemmParams base_params(const p3d_conv_desc* d) {
 }
 
 // ---- what the last call launched (p3d_conv_last_fp32_launch) ---------------------------------------------
-// Host bookkeeping like fx_count: each of the four entries clears the record first, launch_igemm and the finishing launches write the values they launch with
-// (wgrad_finish, which the x3 and block paths share, hands its bits to the caller; only the fp32 branch of p3d_conv2d_wgrad records them).
+// Host bookkeeping like fx_count: each of the four entries clears the record first and writes it from its Fp32Plan once the igemm launch is queued (last_record);
+// the test hook p3d_conv2d_fp32_plan writes the same record from the same plan without launching.
 enum { LAST_PASS = 0, LAST_TILE, LAST_TAPM, LAST_MASKED, LAST_WV, LAST_GRID_X, LAST_GRID_Y, LAST_Y_MEANS, LAST_WEIGHT_IMAGE, LAST_FINISH, LAST_EVAL, LAST_NO_ROOM,
        LAST_FIELDS = P3D_FP32_LAUNCH_FIELDS };
 enum { Y_ONE = 0, Y_SLABS = 1, Y_CLASSES = 2 };
 enum { FIN_FWD_REDUCE = 1, FIN_INTERLEAVE = 2, FIN_INTERLEAVE2 = 4, FIN_WGRAD_REDUCE = 8, FIN_WGRAD_REDUCE_TAPM = 16, FIN_WGRAD_REDUCE16 = 32,
        FIN_WGRAD_REDUCE16_TAPM = 64, FIN_SLAB_FOLD = 128 };
 enum { NO_ROOM_SLABS = 1, NO_ROOM_WEIGHT_IMAGE = 2 };
+
+// How one call of p3d_conv2d_fwd / _bn_eval_fwd / _dgrad / _wgrad runs on the fp32-MFMA family: everything decided between conv_route answering FP32_MFMA and the
+// last launch.  fp32_plan_fwd / _dgrad / _wgrad (below, beside the rules they apply) compute it from the descriptor and an Fp32Call; the entries fill IgemmParams
+// from it, the workspace queries read `need` of the call with unlimited room, and the record of p3d_conv_last_fp32_launch is fp32_record of it.
+struct Fp32Call {           // what a planner may know of the operands
+    bool mask, mult;        // mask_in / mult given
+    bool eval;              // through p3d_conv2d_bn_eval_fwd, which keeps its coefficients ahead of the workspace it passes on (eval_head_bytes)
+    bool dy_aligned, x_aligned;      // weight gradient: dy and mult / x and mask_in on 16-B lines (WV)
+    bool out_aligned;       // strided data gradient: dx, workspace and mask_in; weight gradient: dw and the slabs (the vector finishing kernels)
+    size_t room;            // workspace bytes; 0: none given
+};
+struct Fp32Plan {
+    int pass;               // MODE_*
+    bool eval;              // Fp32Call::eval
+    int cfg;                // tile: index into kCfgs
+    bool tapm, masked;      // the kernel's TAPM and MASKED
+    int wv;                 // and WV
+    int rows, cols;         // the GEMM's M and Ncols
+    int splits, kchunk, cpad;        // IgemmParams::kchunk / cpad; splits 1: the reduction is not cut
+    unsigned grid_x;
+    int grid_y, y_means;    // grid.y and what it counts (Y_*)
+    bool weight_image;      // operand A is the tap-major weight image, laid at the head of the workspace
+    size_t out_offset, out_stride;   // the slabs or staged classes: grid_y of out_stride floats each (Y_ONE: the kernel writes the result itself)
+    int live;               // data gradient: the parity classes a tap reaches, as bits
+    size_t need;            // bytes the call asks for with nothing dropped for lack of room
+    int finish, no_room;    // FIN_* / NO_ROOM_* bits
+    bool refused;           // room < need where the call cannot do without: the staged classes, the weight-gradient slabs (P3D_EWORKSPACE)
+    bool window_2gib;       // weight gradient: a block's window of images exceeds 2 GiB (P3D_EINVAL)
+};
+static void fp32_record(const Fp32Plan& pl, int32_t* out) {
+    for (int i = 0; i < LAST_FIELDS; ++i) out[i] = 0;
+    out[LAST_PASS] = pl.pass; out[LAST_TILE] = pl.cfg < 5 ? pl.cfg : 5; out[LAST_TAPM] = pl.tapm; out[LAST_MASKED] = pl.masked; out[LAST_WV] = pl.wv;
+    out[LAST_GRID_X] = (int32_t)pl.grid_x; out[LAST_GRID_Y] = pl.grid_y; out[LAST_Y_MEANS] = pl.y_means; out[LAST_WEIGHT_IMAGE] = pl.weight_image;
+    out[LAST_FINISH] = pl.finish; out[LAST_EVAL] = pl.eval; out[LAST_NO_ROOM] = pl.no_room;
+}
+static void fp32_record_empty(bool eval, int32_t* out) {
+    for (int i = 0; i < LAST_FIELDS; ++i) out[i] = 0;
+    out[LAST_PASS] = -1; out[LAST_TILE] = -1; out[LAST_EVAL] = eval;
+}
 static std::mutex g_last_mu;
 static int32_t g_last[LAST_FIELDS] = {-1};
-static void last_clear(int eval) {
-    std::lock_guard<std::mutex> lock(g_last_mu);
-    for (int i = 0; i < LAST_FIELDS; ++i) g_last[i] = 0;
-    g_last[LAST_PASS] = -1; g_last[LAST_TILE] = -1; g_last[LAST_EVAL] = eval;
-}
-static void last_set(int field, int value) { std::lock_guard<std::mutex> lock(g_last_mu); g_last[field] = value; }
-static void last_or(int field, int bits) { std::lock_guard<std::mutex> lock(g_last_mu); g_last[field] |= bits; }
+static void last_clear(int eval) { std::lock_guard<std::mutex> lock(g_last_mu); fp32_record_empty(eval != 0, g_last); }
+static void last_record(const Fp32Plan& pl) { std::lock_guard<std::mutex> lock(g_last_mu); fp32_record(pl, g_last); }
 
 // ---- tile configurations --------------------------------------------------------------------------------
 struct TileCfg { int bm, bn, bk; double eff; };
@@ -1073,15 +1107,13 @@ static void launch_variant(bool tapm, bool masked, int wv, dim3 grid, hipStream_
     hipLaunchKernelGGL((igemm_kernel<MODE, BM, BN, WM, WN, BK, true, false>), grid, dim3(256), 0, st, p);
 }
 
+// the igemm launch of a plan: p.M / Ncols / cpad / kchunk and the operands are the entry's to fill from the same plan
 template <int MODE>
-static void launch_igemm(int cfg, bool tapm, bool masked, IgemmParams& p, int ny, hipStream_t st, int wv = 0) {
+static void launch_igemm(const Fp32Plan& pl, IgemmParams& p, hipStream_t st) {
+    const int cfg = pl.cfg, wv = pl.wv;
+    const bool tapm = pl.tapm, masked = pl.masked;
     p.tiles_m = (int)ceil_div(p.M, kCfgs[cfg].bm);
-    dim3 grid((unsigned)(p.tiles_m * ceil_div(p.Ncols, kCfgs[cfg].bn)), (unsigned)ny);
-    {
-        std::lock_guard<std::mutex> lock(g_last_mu);
-        g_last[LAST_PASS] = MODE; g_last[LAST_TILE] = cfg < 5 ? cfg : 5; g_last[LAST_TAPM] = tapm; g_last[LAST_MASKED] = masked; g_last[LAST_WV] = wv;
-        g_last[LAST_GRID_X] = (int32_t)grid.x; g_last[LAST_GRID_Y] = ny;
-    }
+    dim3 grid(pl.grid_x, (unsigned)pl.grid_y);
     switch (cfg) {
         case 0: launch_variant<MODE, 128, 128, 2, 2, 16>(tapm, masked, wv, grid, st, p); break;
         case 1: launch_variant<MODE, 64, 256, 1, 4, 16>(tapm, masked, wv, grid, st, p); break;
@@ -1092,84 +1124,59 @@ static void launch_igemm(int cfg, bool tapm, bool masked, IgemmParams& p, int ny
     }
 }
 
-struct WgradPlan { int cfg; bool tapm; int splits; int kchunk; };
-
-static WgradPlan plan_wgrad(const p3d_conv_desc* d, bool masked) {
-    const int M = d->K, Ncols = d->C * d->R * d->S;
-    const int64_t Kd = (int64_t)d->N * d->Ho * d->Wo;
-    // choose the tile for a fully split problem (tail-free), then the split count that fills ~4 blocks per CU.
-    // Tap-major columns need every block inside one tap: C % BN == 0.
-    int cfg = -1;
-    bool tapm = false;
-    double best = 1e300;
-    for (int i = 0; i < 6; ++i) {
-        const bool tm = d->C % kCfgs[i].bn == 0;
-        double cost = (double)ceil_div(M, kCfgs[i].bm) * kCfgs[i].bm * ceil_div(Ncols, kCfgs[i].bn) * kCfgs[i].bn / kCfgs[i].eff;
-        if (!tm && d->R * d->S > 1) cost *= 1.3;          // generic per-element tap decode is slower
-        if (cost < best * 0.999) { best = cost; cfg = i; tapm = tm; }
-    }
-    {   // weight tensors of at most four 128x128 tiles (layer1, the stems): 64x64 tiles need a quarter of the splits -> less slab traffic
-        const int64_t t128 = ceil_div(M, 128) * ceil_div(Ncols, 128);
-        if (!masked && t128 <= 4 && d->C % 64 == 0) { cfg = 5; tapm = true; }
-    }
-    const int bk = kCfgs[cfg].bk;
-    const int64_t tiles = ceil_div(M, kCfgs[cfg].bm) * ceil_div(Ncols, kCfgs[cfg].bn);
-    int64_t splits = ceil_div(1024, tiles);
-    const int64_t max_splits = ceil_div(Kd, 8 * bk);        // at least 8 K-steps per block
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    int64_t kchunk = ceil_div(ceil_div(Kd, splits), bk) * bk;
-    splits = ceil_div(Kd, kchunk);
-    return {cfg, tapm, (int)splits, (int)kchunk};
-}
-
 }  // namespace p3d
 
 namespace p3d {
 // second half of every weight-gradient call: deep splits are folded to <= 16 slabs by a chip-filling grid, then one pass sums them into dw
 // (tap-major slabs [k][tap][c] are transposed to the weight's [k][c][tap] order on the way)
-int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm, float* dw, hipStream_t st, int32_t* launched) {
-    int32_t none = 0;
-    if (!launched) launched = &none;          // (the FIN_ bits of the kernels launched below, for the caller that keeps the launch record)
-    const int M = d->K, Ncols = d->C * d->R * d->S;
+// which of them, as FIN_ bits: a pure function of the descriptor, the slabs and whether dw and the slabs lie on 16-B lines, so that a plan can name the finish
+static int32_t wgrad_finish_kernels(const p3d_conv_desc* d, int nslab, bool tapm, bool aligned) {
+    const int RS = d->R * d->S;
+    const bool transpose = tapm && RS > 1;
+    const int32_t sum = transpose ? FIN_WGRAD_REDUCE_TAPM : FIN_WGRAD_REDUCE;
+    if (nslab <= 16) return sum;
+    // one launch where the destination allows it (every weight of a ResNet): same additions in the same order as fold + reduce
+    if (transpose && d->C % 16 == 0 && (size_t)(17 * RS * 16) * sizeof(float) <= 64 * 1024) return FIN_WGRAD_REDUCE16_TAPM;      // (its LDS tile: 7x7 = 53 KB; 8x8 and up take fold + reduce)
+    const size_t tot = (size_t)d->K * d->C * RS;
+    if (!transpose && d->c_total == d->C && d->c_offset == 0 && (tot & 3) == 0 && aligned) return FIN_WGRAD_REDUCE16;
+    return FIN_SLAB_FOLD | sum;
+}
+// the launches of a choice `fin` of wgrad_finish_kernels
+static int32_t wgrad_finish_launch(const p3d_conv_desc* d, float* slabs, int nslab, int32_t fin, float* dw, hipStream_t st) {
+    const int M = d->K, Ncols = d->C * d->R * d->S, RS = d->R * d->S;
     const int ldw = d->c_total * d->R * d->S, woff = d->c_offset * d->R * d->S;
-    if (nslab > 16) {
-        // one launch where the destination allows it (every weight of a ResNet): same additions in the same order as fold + reduce
-        const size_t tot = (size_t)M * Ncols;
-        if (tapm && d->R * d->S > 1 && d->C % 16 == 0 && (size_t)(17 * d->R * d->S * 16) * sizeof(float) <= 64 * 1024) {      // (its LDS tile: 7x7 = 53 KB; 8x8 and up take fold + reduce)
-            const int RS = d->R * d->S;
-            hipLaunchKernelGGL(wgrad_reduce16_tapm_kernel, dim3(d->K, d->C / 16), dim3(256), (size_t)(17 * RS * 16) * sizeof(float), st, (const float*)slabs, dw, M, d->C, RS,
-                               nslab, ldw, woff, d->accumulate);
-            *launched |= FIN_WGRAD_REDUCE16_TAPM;
-            return check_launch("conv2d_wgrad reduce16 tapm");
-        }
-        if (!(tapm && d->R * d->S > 1) && ldw == Ncols && woff == 0 && (tot & 3) == 0 && aligned16(dw, slabs)) {
-            const size_t n4 = tot >> 2;
-            const int64_t nb = ceil_div((int64_t)n4, 16);
-            hipLaunchKernelGGL(wgrad_reduce16_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, st, (const float*)slabs, dw, n4, nslab, d->accumulate);
-            *launched |= FIN_WGRAD_REDUCE16;
-            return check_launch("conv2d_wgrad reduce16");
-        }
-        const size_t total = (size_t)M * Ncols;
+    const size_t total = (size_t)M * Ncols;
+    if (fin & FIN_WGRAD_REDUCE16_TAPM) {
+        hipLaunchKernelGGL(wgrad_reduce16_tapm_kernel, dim3(d->K, d->C / 16), dim3(256), (size_t)(17 * RS * 16) * sizeof(float), st, (const float*)slabs, dw, M, d->C, RS,
+                           nslab, ldw, woff, d->accumulate);
+        return check_launch("conv2d_wgrad reduce16 tapm");
+    }
+    if (fin & FIN_WGRAD_REDUCE16) {
+        const size_t n4 = total >> 2;
+        const int64_t nb = ceil_div((int64_t)n4, 16);
+        hipLaunchKernelGGL(wgrad_reduce16_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, st, (const float*)slabs, dw, n4, nslab, d->accumulate);
+        return check_launch("conv2d_wgrad reduce16");
+    }
+    if (fin & FIN_SLAB_FOLD) {
         const int G = 16;
         const int64_t bx = ceil_div((int64_t)ceil_div((int64_t)total, 4), 256);
         hipLaunchKernelGGL(slab_fold_kernel, dim3((unsigned)(bx < 256 ? bx : 256), G), dim3(256), 0, st, slabs, total, nslab, G);
-        *launched |= FIN_SLAB_FOLD;
         if (int32_t e = check_launch("conv2d_wgrad fold")) return e;
         nslab = G;
     }
-    if (tapm && d->R * d->S > 1) {
-        const int RS = d->R * d->S;
+    if (fin & FIN_WGRAD_REDUCE_TAPM) {
         hipLaunchKernelGGL(wgrad_reduce_tapm_kernel, dim3(d->K, d->C / REDUCE_CH), dim3(256), RS * REDUCE_CH * sizeof(float), st, (const float*)slabs, dw, M, d->C, RS,
                            nslab, ldw, woff, d->accumulate);
-        *launched |= FIN_WGRAD_REDUCE_TAPM;
     } else {
-        const size_t total = (size_t)M * Ncols;
         const unsigned blocks = (unsigned)(ceil_div((int64_t)total, 256) < 2048 ? ceil_div((int64_t)total, 256) : 2048);
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)slabs, dw, M, Ncols, nslab, ldw, woff, d->accumulate);
-        *launched |= FIN_WGRAD_REDUCE;
     }
     return check_launch("conv2d_wgrad reduce");
+}
+int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm, float* dw, hipStream_t st, int32_t* launched) {
+    const int32_t fin = wgrad_finish_kernels(d, nslab, tapm, aligned16(dw, slabs));
+    if (launched) *launched |= fin;          // (for the caller that keeps a launch record)
+    return wgrad_finish_launch(d, slabs, nslab, fin, dw, st);
 }
 }  // namespace p3d
 
@@ -1234,6 +1241,37 @@ static SplitPlan plan_splitk(int rows, int cols, int red, int taps, bool may_spl
 static SplitPlan plan_fwd(const p3d_conv_desc* d, bool may_split) { return plan_splitk(d->K, d->N * d->Ho * d->Wo, d->C, d->R * d->S, may_split && d->C >= 16); }
 static SplitPlan plan_dgrad1(const p3d_conv_desc* d, bool may_split) { return plan_splitk(d->C, d->N * d->H * d->W, d->K, d->R * d->S, may_split); }
 
+struct WgradPlan { int cfg; bool tapm; int splits; int kchunk; };
+
+static WgradPlan plan_wgrad(const p3d_conv_desc* d, bool masked) {
+    const int M = d->K, Ncols = d->C * d->R * d->S;
+    const int64_t Kd = (int64_t)d->N * d->Ho * d->Wo;
+    // choose the tile for a fully split problem (tail-free), then the split count that fills ~4 blocks per CU.
+    // Tap-major columns need every block inside one tap: C % BN == 0.
+    int cfg = -1;
+    bool tapm = false;
+    double best = 1e300;
+    for (int i = 0; i < 6; ++i) {
+        const bool tm = d->C % kCfgs[i].bn == 0;
+        double cost = (double)ceil_div(M, kCfgs[i].bm) * kCfgs[i].bm * ceil_div(Ncols, kCfgs[i].bn) * kCfgs[i].bn / kCfgs[i].eff;
+        if (!tm && d->R * d->S > 1) cost *= 1.3;          // generic per-element tap decode is slower
+        if (cost < best * 0.999) { best = cost; cfg = i; tapm = tm; }
+    }
+    {   // weight tensors of at most four 128x128 tiles (layer1, the stems): 64x64 tiles need a quarter of the splits -> less slab traffic
+        const int64_t t128 = ceil_div(M, 128) * ceil_div(Ncols, 128);
+        if (!masked && t128 <= 4 && d->C % 64 == 0) { cfg = 5; tapm = true; }
+    }
+    const int bk = kCfgs[cfg].bk;
+    const int64_t tiles = ceil_div(M, kCfgs[cfg].bm) * ceil_div(Ncols, kCfgs[cfg].bn);
+    int64_t splits = ceil_div(1024, tiles);
+    const int64_t max_splits = ceil_div(Kd, 8 * bk);        // at least 8 K-steps per block
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    int64_t kchunk = ceil_div(ceil_div(Kd, splits), bk) * bk;
+    splits = ceil_div(Kd, kchunk);
+    return {cfg, tapm, (int)splits, (int)kchunk};
+}
+
 // The kernel family one call of p3d_conv2d_fwd / _dgrad / _wgrad lands on, and the workspace that family needs: decided here for the three entries and, with
 // "aligned pointers, unlimited workspace", for their workspace queries, so that a query covers whatever its entry picks.
 //   X3         dense, the aligned predicate of the pass admits;
@@ -1291,12 +1329,122 @@ static FxFuse route_fuse(const ConvRoute& r, const float* pmask, const float* em
     return f;
 }
 
+// ---- the plan of a call on the fp32-MFMA family (Fp32Plan, above) -------------------------------------------------------------------------------
+static void plan_grid(Fp32Plan& pl, int rows, int cols) {
+    pl.rows = rows; pl.cols = cols;
+    pl.grid_x = (unsigned)(ceil_div(rows, kCfgs[pl.cfg].bm) * ceil_div(cols, kCfgs[pl.cfg].bn));
+}
+// the tap-major weight image at the head of the workspace if `left` bytes hold it (`at`: where the slabs may start); else the call runs from the KCRS weight
+static void plan_weight_image(Fp32Plan& pl, const p3d_conv_desc* d, size_t& at, size_t& left) {
+    const size_t wimg = weight_image_bytes(d);
+    pl.need += wimg;
+    if (wimg && left >= wimg) {
+        pl.weight_image = true;
+        at += wimg; left -= wimg;
+    } else if (wimg) pl.no_room |= NO_ROOM_WEIGHT_IMAGE;
+}
+// `splits` slabs of out_stride floats at `at`, summed by fwd_reduce_kernel: the launch is dense and tap-major, bias / accumulate / eval epilogue move to the reduce pass
+static void plan_slabs(Fp32Plan& pl, const SplitPlan& sp, size_t at) {
+    pl.cfg = sp.cfg; pl.splits = sp.splits; pl.kchunk = sp.kchunk;
+    pl.tapm = true; pl.masked = false;
+    pl.grid_y = sp.splits; pl.y_means = Y_SLABS; pl.out_offset = at; pl.finish = FIN_FWD_REDUCE;
+}
+// Forward: [weight image][slabs].  Slabs that do not fit: planned again unsplit, which may move the tile.
+static Fp32Plan fp32_plan_fwd(const p3d_conv_desc* d, const Fp32Call& c) {
+    Fp32Plan pl{};
+    pl.pass = MODE_FWD; pl.eval = c.eval; pl.splits = 1; pl.grid_y = 1;
+    size_t at = 0, left = c.room;
+    pl.tapm = d->C >= 16;                       // (a weight image implies it)
+    pl.masked = c.mask || c.mult;
+    pl.out_stride = (size_t)d->N * d->K * d->Ho * d->Wo;
+    plan_weight_image(pl, d, at, left);
+    SplitPlan sp = plan_fwd(d, !pl.masked);
+    if (sp.splits > 1) pl.need += sp.splits * pl.out_stride * sizeof(float);
+    if (sp.splits > 1 && left < sp.splits * pl.out_stride * sizeof(float)) { sp = plan_fwd(d, false); pl.no_room |= NO_ROOM_SLABS; }      // no scratch: unsplit
+    pl.cfg = sp.cfg;
+    if (sp.splits > 1) plan_slabs(pl, sp, at);
+    pl.cpad = (int)ceil_div(d->C, kCfgs[pl.cfg].bk) * kCfgs[pl.cfg].bk;
+    plan_grid(pl, d->K, d->N * d->Ho * d->Wo);
+    return pl;
+}
+
+// how many of a filter axis' `taps` reach the input pixels of parity `par`
+static int class_taps(const p3d_conv_desc* d, int par, int taps) {
+    int first, step, n, off0, offstep;
+    fill_class(par, taps, d->stride, d->pad, d->dil, &first, &step, &n, &off0, &offstep);
+    return n;
+}
+// Data gradient.  Stride 1: [weight image][slabs]; it splits only if the slabs fit behind the image, else it launches on pick_cfg's tile.
+// Stride > 1: parity classes of input pixels, each a dense GEMM over the taps that reach it, written class-major to the staging buffer at offset 0 with full-line
+// stores, then interleaved into dx (mask_in and accumulate applied there, never in the kernel) in one streaming pass; no weight image.  It asks for what the query
+// answers with p3d_x3_any_strided_enable off -- the x3 route's bytes included --, so a call that fell back here for a workspace too small for the class planes of
+// X3_STRIDED_RAGGED runs as it does with the switch off.
+static Fp32Plan fp32_plan_dgrad(const p3d_conv_desc* d, const Fp32Call& c) {
+    Fp32Plan pl{};
+    pl.pass = MODE_DGRAD; pl.splits = 1; pl.grid_y = 1; pl.tapm = true;
+    const int st = d->stride, hc = (int)ceil_div(d->H, st), wc = (int)ceil_div(d->W, st);
+    const int rows = d->C, cols = d->N * hc * wc;                    // the largest class (0,0) sizes the grid
+    int nlive = 0;
+    for (int i = 0; i < st * st; ++i)
+        if (class_taps(d, i / st, d->R) * class_taps(d, i % st, d->S) > 0) { pl.live |= 1 << i; ++nlive; }
+    pl.cfg = pick_cfg(rows, cols, nlive > 0 ? nlive : 1);     // classes no tap reaches exit at once
+    if (st == 1) {
+        pl.masked = c.mask || c.mult;
+        pl.out_stride = (size_t)d->N * d->C * d->H * d->W;
+        size_t at = 0, left = c.room;
+        plan_weight_image(pl, d, at, left);
+        const SplitPlan sp = plan_dgrad1(d, !pl.masked);
+        if (sp.splits > 1) pl.need += sp.splits * pl.out_stride * sizeof(float);
+        if (sp.splits > 1 && left >= sp.splits * pl.out_stride * sizeof(float)) plan_slabs(pl, sp, at);
+        else if (sp.splits > 1) pl.no_room |= NO_ROOM_SLABS;
+    } else {
+        pl.masked = c.mult;
+        pl.grid_y = st * st; pl.y_means = Y_CLASSES;
+        pl.out_stride = (size_t)d->N * d->C * hc * wc;
+        const size_t staged = (size_t)pl.grid_y * pl.out_stride * sizeof(float), fx = x3_query_bytes(FX_DGRAD, d);
+        pl.need = staged > fx ? staged : fx;
+        pl.refused = c.room < pl.need;
+        pl.finish = st == 2 && d->W % 4 == 0 && c.out_aligned ? FIN_INTERLEAVE2 : FIN_INTERLEAVE;
+    }
+    pl.cpad = (int)ceil_div(d->K, kCfgs[pl.cfg].bk) * kCfgs[pl.cfg].bk;
+    plan_grid(pl, rows, cols);
+    return pl;
+}
+
+// Weight gradient: `splits` slabs of the weight's size at offset 0, then wgrad_finish.
+static Fp32Plan fp32_plan_wgrad(const p3d_conv_desc* d, const Fp32Call& c) {
+    Fp32Plan pl{};
+    pl.pass = MODE_WGRAD;
+    pl.masked = c.mask || c.mult;
+    const WgradPlan wp = plan_wgrad(d, pl.masked);
+    pl.cfg = wp.cfg; pl.tapm = wp.tapm; pl.splits = wp.splits; pl.kchunk = wp.kchunk;
+    pl.cpad = d->C;
+    if ((d->Ho * d->Wo) % 4 == 0 && c.dy_aligned) {
+        pl.wv = 1;
+        if (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0 && c.x_aligned) pl.wv = 2;
+    }
+    pl.grid_y = wp.splits; pl.y_means = Y_SLABS;
+    pl.out_stride = (size_t)d->K * d->C * d->R * d->S;
+    pl.need = (size_t)wp.splits * pl.out_stride * sizeof(float);
+    pl.refused = c.room < pl.need;
+    const int64_t span = wp.kchunk / ((int64_t)d->Ho * d->Wo) + 2;
+    const int64_t img = (int64_t)4 * (d->C * d->H * d->W > d->K * d->Ho * d->Wo ? d->C * d->H * d->W : d->K * d->Ho * d->Wo);
+    pl.window_2gib = (span < d->N ? span : d->N) * img >= (1ll << 31);
+    pl.finish = wgrad_finish_kernels(d, wp.splits, wp.tapm, c.out_aligned);
+    plan_grid(pl, d->K, d->C * d->R * d->S);
+    return pl;
+}
+
+// a query: the call with every operand aligned and unlimited room, dense and as a partial convolution, and the x3 route's bytes
+static size_t query_bytes(Fp32Plan (*plan)(const p3d_conv_desc*, const Fp32Call&), const p3d_conv_desc* d, size_t fx) {
+    const Fp32Call dense{false, false, false, true, true, true, SIZE_MAX}, partial{true, true, false, true, true, true, SIZE_MAX};
+    const size_t a = plan(d, dense).need, b = plan(d, partial).need;
+    return a > b ? (a > fx ? a : fx) : (b > fx ? b : fx);
+}
+
 size_t p3d_conv2d_fwd_workspace_bytes(const p3d_conv_desc* d) {
     if (validate(d)) return 0;
-    const SplitPlan pl = plan_fwd(d, true);
-    const size_t base = weight_image_bytes(d) + (pl.splits > 1 ? (size_t)pl.splits * d->N * d->K * d->Ho * d->Wo * sizeof(float) : 0);
-    const size_t fx = x3_query_bytes(FX_FWD, d);
-    return base > fx ? base : fx;
+    return query_bytes(fp32_plan_fwd, d, x3_query_bytes(FX_FWD, d));
 }
 
 static int32_t conv2d_fwd_impl(const p3d_conv_desc* d, const float* x, const float* w, const float* bias, const float* mask_in, const float* mult,
@@ -1313,36 +1461,29 @@ static int32_t conv2d_fwd_impl(const p3d_conv_desc* d, const float* x, const flo
         return fx_conv_fwd(d, x, w, bias, y, workspace, workspace_bytes, &f, (hipStream_t)stream);
     }
     fx_count(3, d);
+    const Fp32Plan pl = fp32_plan_fwd(d, Fp32Call{mask_in != nullptr, mult != nullptr, ep_scale != nullptr, true, true, true, workspace ? workspace_bytes : 0});
+    char* ws = (char*)workspace;
+    const hipStream_t st = (hipStream_t)stream;
     IgemmParams p = base_params(d);
     p.A = w; p.B = x; p.Cout = y; p.bias = bias; p.mask_in = mask_in; p.mult = mult;
     p.ep_scale = ep_scale; p.ep_shift = ep_shift; p.ep_res = ep_res; p.ep_relu = ep_relu;
-    p.M = d->K; p.Ncols = d->N * d->Ho * d->Wo; p.Kd = d->C * d->R * d->S;
-    const bool masked = mask_in || mult;
-    const bool tapm = d->C >= 16;
-    SplitPlan pl = plan_fwd(d, !masked);
-    const size_t ysize = (size_t)d->N * d->K * d->Ho * d->Wo;
-    const size_t wimg = weight_image_bytes(d);
-    if (wimg && tapm && workspace && workspace_bytes >= wimg) {      // tap-major weight image at the head of the workspace
-        use_weight_image(p, d, w, (float*)workspace, (hipStream_t)stream);
-        workspace = (char*)workspace + wimg; workspace_bytes -= wimg;
-        last_set(LAST_WEIGHT_IMAGE, 1);
-    } else if (wimg && tapm) last_or(LAST_NO_ROOM, NO_ROOM_WEIGHT_IMAGE);
-    if (pl.splits > 1 && (!workspace || workspace_bytes < pl.splits * ysize * sizeof(float))) { pl = plan_fwd(d, false); last_or(LAST_NO_ROOM, NO_ROOM_SLABS); }   // no scratch: unsplit
-    p.cpad = (int)ceil_div(d->C, kCfgs[pl.cfg].bk) * kCfgs[pl.cfg].bk;
-    if (pl.splits > 1) {
-        p.Cout = (float*)workspace; p.bias = nullptr; p.accumulate = 0; p.ep_scale = nullptr;      // the epilogue runs in the reduce pass
-        p.kchunk = pl.kchunk; p.cls_stride = ysize;
-        launch_igemm<MODE_FWD>(pl.cfg, true, false, p, pl.splits, (hipStream_t)stream);
-        last_set(LAST_Y_MEANS, Y_SLABS);
-        if (int32_t e = check_launch("conv2d_fwd")) return e;
+    p.M = pl.rows; p.Ncols = pl.cols; p.Kd = d->C * d->R * d->S; p.cpad = pl.cpad;
+    if (pl.weight_image) use_weight_image(p, d, w, (float*)ws, st);
+    if (pl.y_means == Y_SLABS) {
+        p.Cout = (float*)(ws + pl.out_offset); p.bias = nullptr; p.accumulate = 0; p.ep_scale = nullptr;      // the epilogue runs in the reduce pass
+        p.kchunk = pl.kchunk; p.cls_stride = pl.out_stride;
+    }
+    launch_igemm<MODE_FWD>(pl, p, st);
+    last_record(pl);
+    if (int32_t e = check_launch("conv2d_fwd")) return e;
+    if (pl.finish & FIN_FWD_REDUCE) {
+        const size_t ysize = pl.out_stride;
         const unsigned blocks = (unsigned)(ceil_div((int64_t)ysize, 1024) < 4096 ? ceil_div((int64_t)ysize, 1024) : 4096);
-        hipLaunchKernelGGL(fwd_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, y, bias, ysize, d->K,
-                           d->Ho * d->Wo, pl.splits, d->accumulate, ep_scale, ep_shift, ep_res, ep_relu);
-        last_or(LAST_FINISH, FIN_FWD_REDUCE);
+        hipLaunchKernelGGL(fwd_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)p.Cout, y, bias, ysize, d->K, d->Ho * d->Wo, pl.splits, d->accumulate,
+                           ep_scale, ep_shift, ep_res, ep_relu);
         return check_launch("conv2d_fwd reduce");
     }
-    launch_igemm<MODE_FWD>(pl.cfg, tapm, masked, p, 1, (hipStream_t)stream);
-    return check_launch("conv2d_fwd");
+    return P3D_OK;
 }
 
 int32_t p3d_conv2d_fwd(const p3d_conv_desc* d, const float* x, const float* w, const float* bias,
@@ -1363,9 +1504,11 @@ __global__ __launch_bounds__(256) void bn_eval_coef_kernel(const float* __restri
     coef[K + k] = beta[k] - rm[k] * sc;
 }
 
+// the eval entry keeps its 2 K coefficients at the head of the workspace and hands the rest to the forward
+static size_t eval_head_bytes(const p3d_conv_desc* d) { return ((size_t)2 * d->K * sizeof(float) + 255) & ~(size_t)255; }
 size_t p3d_conv2d_bn_eval_fwd_workspace_bytes(const p3d_conv_desc* d) {
     if (validate(d)) return 0;
-    return (((size_t)2 * d->K * sizeof(float) + 255) & ~(size_t)255) + p3d_conv2d_fwd_workspace_bytes(d);
+    return eval_head_bytes(d) + p3d_conv2d_fwd_workspace_bytes(d);
 }
 
 int32_t p3d_conv2d_bn_eval_fwd(const p3d_conv_desc* d, const float* x, const float* w, const float* gamma, const float* beta,
@@ -1375,7 +1518,7 @@ int32_t p3d_conv2d_bn_eval_fwd(const p3d_conv_desc* d, const float* x, const flo
     if (int32_t e = validate(d)) return e;
     P3D_REQUIRE(gamma && beta && running_mean && running_var, "conv2d_bn_eval_fwd: null BatchNorm tensor");
     P3D_REQUIRE(!d->accumulate, "conv2d_bn_eval_fwd: accumulate is not meaningful with a fused activation");
-    const size_t head = ((size_t)2 * d->K * sizeof(float) + 255) & ~(size_t)255;
+    const size_t head = eval_head_bytes(d);
     if (!workspace || workspace_bytes < head) { set_error("conv2d_bn_eval_fwd: workspace too small"); return P3D_EWORKSPACE; }
     float* coef = (float*)workspace;
     hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((unsigned)ceil_div(d->K, 256)), dim3(256), 0, (hipStream_t)stream, gamma, beta, running_mean, running_var,
@@ -1383,27 +1526,15 @@ int32_t p3d_conv2d_bn_eval_fwd(const p3d_conv_desc* d, const float* x, const flo
     return conv2d_fwd_impl(d, x, w, nullptr, nullptr, nullptr, y, (char*)workspace + head, workspace_bytes - head, stream, coef, coef + d->K, res, relu);
 }
 
-// strided_any false: what the query answers with p3d_x3_any_strided_enable off -- all the fp32-MFMA strided path asks for, so a call that fell back to it for a
-// workspace too small for the class planes of X3_STRIDED_RAGGED runs as it does with the switch off.  true: while that switch is on, the class-plane plan too for
-// every shape its predicate admits (aligned ones included, which never use it: one rule for the caller)
-static size_t dgrad_workspace_bytes(const p3d_conv_desc* d, bool strided_any) {
+// while p3d_x3_any_strided_enable is on, the class-plane plan too for every shape its predicate admits (aligned ones included, which never use it: one rule for the caller)
+size_t p3d_conv2d_dgrad_workspace_bytes(const p3d_conv_desc* d) {
+    if (validate(d)) return 0;
     size_t fx = x3_query_bytes(FX_DGRAD, d);
-    if (strided_any && fx_any_strided_enabled() && fx_dgrad_strided_any_applies(d)) {
+    if (fx_any_strided_enabled() && fx_dgrad_strided_any_applies(d)) {
         const size_t planes = fx_dgrad_strided_any_plan(d).workspace;
         if (planes > fx) fx = planes;
     }
-    if (d->stride == 1) {
-        const SplitPlan pl = plan_dgrad1(d, true);
-        const size_t base = weight_image_bytes(d) + (pl.splits > 1 ? (size_t)pl.splits * d->N * d->C * d->H * d->W * sizeof(float) : 0);
-        return base > fx ? base : fx;
-    }
-    const size_t hc = (size_t)ceil_div(d->H, d->stride), wc = (size_t)ceil_div(d->W, d->stride);
-    const size_t staged = (size_t)d->stride * d->stride * d->N * d->C * hc * wc * sizeof(float);
-    return staged > fx ? staged : fx;
-}
-size_t p3d_conv2d_dgrad_workspace_bytes(const p3d_conv_desc* d) {
-    if (validate(d)) return 0;
-    return dgrad_workspace_bytes(d, true);
+    return query_bytes(fp32_plan_dgrad, d, fx);
 }
 
 // the finishing pass of X3_STRIDED_RAGGED (and kernel 1 of the test hook p3d_dgrad_interleave): a bounded grid, the kernel strides over the rest
@@ -1438,87 +1569,54 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
         return fx_conv_dgrad(d, dy, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream);
     }
     fx_count(4, d);
-    IgemmParams p = base_params(d);
-    p.A = w; p.B = dy; p.Cout = dx; p.mask_in = mask_in; p.mult = mult;
-    p.M = d->C; p.Kd = d->K * d->R * d->S;
-    const bool masked = mask_in || mult;
-    const int st = d->stride;
-    p.ncls = st * st;
-    int live = 0;
-    for (int par = 0; par < st; ++par) {
-        fill_class(par, d->R, st, d->pad, d->dil, &p.r0[par], &p.rstep[par], &p.nr[par], &p.offr0[par], &p.offrstep[par]);
-        fill_class(par, d->S, st, d->pad, d->dil, &p.s0[par], &p.sstep[par], &p.ns[par], &p.offs0[par], &p.offsstep[par]);
-    }
-    for (int c = 0; c < p.ncls; ++c)
-        if (p.nr[c / st] * p.ns[c % st] > 0) live |= 1 << c;
-    const int hc = (int)ceil_div(d->H, st), wc = (int)ceil_div(d->W, st);
-    p.Ncols = d->N * hc * wc;                    // the largest class (0,0) sizes the grid
-    int nlive = 0;
-    for (int c = 0; c < p.ncls; ++c) nlive += (live >> c) & 1;
-    const int cfg = pick_cfg(p.M, p.Ncols, nlive > 0 ? nlive : 1);     // classes no tap reaches exit at once
-    p.cpad = (int)ceil_div(d->K, kCfgs[cfg].bk) * kCfgs[cfg].bk;
-    if (st == 1) {
-        const SplitPlan pl = plan_dgrad1(d, !masked);
-        const size_t xsize = (size_t)d->N * d->C * d->H * d->W;
-        const size_t wimg = weight_image_bytes(d);
-        if (wimg && workspace && workspace_bytes >= wimg) {
-            use_weight_image(p, d, w, (float*)workspace, (hipStream_t)stream);
-            workspace = (char*)workspace + wimg; workspace_bytes -= wimg;
-            last_set(LAST_WEIGHT_IMAGE, 1);
-        } else if (wimg) last_or(LAST_NO_ROOM, NO_ROOM_WEIGHT_IMAGE);
-        if (pl.splits > 1 && workspace && workspace_bytes >= pl.splits * xsize * sizeof(float)) {
-            p.cpad = (int)ceil_div(d->K, kCfgs[pl.cfg].bk) * kCfgs[pl.cfg].bk;
-            p.Cout = (float*)workspace; p.accumulate = 0; p.kchunk = pl.kchunk; p.cls_stride = xsize;
-            launch_igemm<MODE_DGRAD>(pl.cfg, true, false, p, pl.splits, (hipStream_t)stream);
-            last_set(LAST_Y_MEANS, Y_SLABS);
-            if (int32_t e = check_launch("conv2d_dgrad")) return e;
-            const unsigned rb = (unsigned)(ceil_div((int64_t)xsize, 1024) < 4096 ? ceil_div((int64_t)xsize, 1024) : 4096);
-            hipLaunchKernelGGL(fwd_reduce_kernel, dim3(rb), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dx, (const float*)nullptr, xsize,
-                               d->C, d->H * d->W, pl.splits, d->accumulate);
-            last_or(LAST_FINISH, FIN_FWD_REDUCE);
-            return check_launch("conv2d_dgrad reduce");
-        }
-        if (pl.splits > 1) last_or(LAST_NO_ROOM, NO_ROOM_SLABS);
-        launch_igemm<MODE_DGRAD>(cfg, true, masked, p, 1, (hipStream_t)stream);
-        return check_launch("conv2d_dgrad");
-    }
-    // stride > 1: parity classes of input pixels, each a dense GEMM over the taps that reach it, written class-major to the
-    // staging buffer with full-line stores, then interleaved into dx (mask and accumulate applied there) in one streaming pass
-    const size_t need = dgrad_workspace_bytes(d, false);
-    if (!workspace || workspace_bytes < need) {
-        set_error("conv2d_dgrad: strided path needs a %zu B workspace (got %zu)", need, workspace_bytes);
+    const Fp32Plan pl = fp32_plan_dgrad(d, Fp32Call{mask_in != nullptr, mult != nullptr, false, true, true, aligned16(dx, workspace, mask_in), workspace ? workspace_bytes : 0});
+    if (pl.refused) {
+        set_error("conv2d_dgrad: strided path needs a %zu B workspace (got %zu)", pl.need, workspace_bytes);
         return P3D_EWORKSPACE;
     }
-    p.staged = 1;
-    p.cls_stride = (size_t)d->N * d->C * hc * wc;
-    p.Cout = (float*)workspace;
-    p.mask_in = nullptr;
-    p.accumulate = 0;
-    launch_igemm<MODE_DGRAD>(cfg, true, masked && mult != nullptr, p, p.ncls, (hipStream_t)stream);
-    last_set(LAST_Y_MEANS, Y_CLASSES);
+    char* ws = (char*)workspace;
+    const hipStream_t st = (hipStream_t)stream;
+    IgemmParams p = base_params(d);
+    p.A = w; p.B = dy; p.Cout = dx; p.mask_in = mask_in; p.mult = mult;
+    p.M = pl.rows; p.Ncols = pl.cols; p.Kd = d->K * d->R * d->S; p.cpad = pl.cpad;
+    p.ncls = d->stride * d->stride;
+    for (int par = 0; par < d->stride; ++par) {
+        fill_class(par, d->R, d->stride, d->pad, d->dil, &p.r0[par], &p.rstep[par], &p.nr[par], &p.offr0[par], &p.offrstep[par]);
+        fill_class(par, d->S, d->stride, d->pad, d->dil, &p.s0[par], &p.sstep[par], &p.ns[par], &p.offs0[par], &p.offsstep[par]);
+    }
+    if (pl.weight_image) use_weight_image(p, d, w, (float*)ws, st);
+    if (pl.y_means != Y_ONE) { p.Cout = (float*)(ws + pl.out_offset); p.accumulate = 0; p.cls_stride = pl.out_stride; }
+    if (pl.y_means == Y_SLABS) p.kchunk = pl.kchunk;
+    if (pl.y_means == Y_CLASSES) { p.staged = 1; p.mask_in = nullptr; }
+    launch_igemm<MODE_DGRAD>(pl, p, st);
+    last_record(pl);
     if (int32_t e = check_launch("conv2d_dgrad")) return e;
     const int64_t total = (int64_t)d->N * d->C * d->H * d->W;
-    if (st == 2 && d->W % 4 == 0 && aligned16(dx, workspace, mask_in)) {
+    if (pl.finish & FIN_FWD_REDUCE) {
+        const unsigned rb = (unsigned)(ceil_div(total, 1024) < 4096 ? ceil_div(total, 1024) : 4096);
+        hipLaunchKernelGGL(fwd_reduce_kernel, dim3(rb), dim3(256), 0, st, (const float*)p.Cout, dx, (const float*)nullptr, (size_t)total, d->C, d->H * d->W, pl.splits,
+                           d->accumulate);
+        return check_launch("conv2d_dgrad reduce");
+    }
+    if (pl.finish & FIN_INTERLEAVE2) {
         const unsigned blocks4 = (unsigned)(ceil_div(total / 4, 256) < 8192 ? ceil_div(total / 4, 256) : 8192);
-        hipLaunchKernelGGL(dgrad_interleave2_kernel, dim3(blocks4), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dx, mask_in,
-                           d->N * d->C, d->C, d->H, d->W, p.cls_stride, live, d->accumulate);
-        last_or(LAST_FINISH, FIN_INTERLEAVE2);
+        hipLaunchKernelGGL(dgrad_interleave2_kernel, dim3(blocks4), dim3(256), 0, st, (const float*)p.Cout, dx, mask_in, d->N * d->C, d->C, d->H, d->W, p.cls_stride, pl.live,
+                           d->accumulate);
         return check_launch("conv2d_dgrad interleave");
     }
-    const unsigned blocks = (unsigned)(ceil_div(total, 256) < 8192 ? ceil_div(total, 256) : 8192);
-    hipLaunchKernelGGL(dgrad_interleave_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dx, mask_in,
-                       d->N * d->C, d->C, d->H, d->W, st, p.cls_stride, live, d->accumulate);
-    last_or(LAST_FINISH, FIN_INTERLEAVE);
-    return check_launch("conv2d_dgrad interleave");
+    if (pl.finish & FIN_INTERLEAVE) {
+        const unsigned blocks = (unsigned)(ceil_div(total, 256) < 8192 ? ceil_div(total, 256) : 8192);
+        hipLaunchKernelGGL(dgrad_interleave_kernel, dim3(blocks), dim3(256), 0, st, (const float*)p.Cout, dx, mask_in, d->N * d->C, d->C, d->H, d->W, d->stride, p.cls_stride,
+                           pl.live, d->accumulate);
+        return check_launch("conv2d_dgrad interleave");
+    }
+    return P3D_OK;
 }
 
+// (the larger of the masked / unmasked plans, so one query serves both)
 size_t p3d_conv2d_wgrad_workspace_bytes(const p3d_conv_desc* d) {
     if (validate(d)) return 0;
-    // the larger of the masked / unmasked plans, so one query serves both
-    const WgradPlan a = plan_wgrad(d, false), b = plan_wgrad(d, true);
-    const int splits = a.splits > b.splits ? a.splits : b.splits;
-    const size_t base = (size_t)splits * d->K * d->C * d->R * d->S * sizeof(float), fx = x3_query_bytes(FX_WGRAD, d);
-    return base > fx ? base : fx;
+    return query_bytes(fp32_plan_wgrad, d, x3_query_bytes(FX_WGRAD, d));
 }
 
 int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x, const float* mult,
@@ -1537,35 +1635,22 @@ int32_t p3d_conv2d_wgrad(const p3d_conv_desc* d, const float* dy, const float* x
         return fx_conv_wgrad(d, dy, x, dw, d->accumulate, workspace, workspace_bytes, &f, "conv2d_wgrad", (hipStream_t)stream);
     }
     fx_count(5, d);
-    const bool masked = mask_in || mult;
-    const WgradPlan pl = plan_wgrad(d, masked);
-    const size_t need = (size_t)pl.splits * d->K * d->C * d->R * d->S * sizeof(float);
-    if (!workspace || workspace_bytes < need) {
-        set_error("conv2d_wgrad: workspace %zu B < required %zu B", workspace_bytes, need);
+    const Fp32Plan pl = fp32_plan_wgrad(d, Fp32Call{mask_in != nullptr, mult != nullptr, false, aligned16(dy, mult), aligned16(x, mask_in), aligned16(dw, workspace),
+                                                    workspace ? workspace_bytes : 0});
+    if (pl.refused) {
+        set_error("conv2d_wgrad: workspace %zu B < required %zu B", workspace_bytes, pl.need);
         return P3D_EWORKSPACE;
     }
-    {
-        const int64_t span = pl.kchunk / ((int64_t)d->Ho * d->Wo) + 2;
-        const int64_t img = (int64_t)4 * (d->C * d->H * d->W > d->K * d->Ho * d->Wo ? d->C * d->H * d->W : d->K * d->Ho * d->Wo);
-        P3D_REQUIRE((span < d->N ? span : d->N) * img < (1ll << 31), "conv2d_wgrad: per-block window exceeds 2 GiB");
-    }
+    P3D_REQUIRE(!pl.window_2gib, "conv2d_wgrad: per-block window exceeds 2 GiB");
     IgemmParams p = base_params(d);
     p.A = dy; p.B = x; p.Cout = (float*)workspace; p.mask_in = mask_in; p.mult = mult;
-    p.M = d->K; p.Ncols = d->C * d->R * d->S; p.Kd = d->N * d->Ho * d->Wo;
+    p.M = pl.rows; p.Ncols = pl.cols; p.Kd = d->N * d->Ho * d->Wo;
     p.kchunk = pl.kchunk;
-    p.cpad = d->C;
-    int wv = 0;
-    if ((d->Ho * d->Wo) % 4 == 0 && aligned16(dy, mult)) {
-        wv = 1;
-        if (d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0 && aligned16(x, mask_in)) wv = 2;
-    }
-    launch_igemm<MODE_WGRAD>(pl.cfg, pl.tapm, masked, p, pl.splits, (hipStream_t)stream, wv);
-    last_set(LAST_Y_MEANS, Y_SLABS);
+    p.cpad = pl.cpad;
+    launch_igemm<MODE_WGRAD>(pl, p, (hipStream_t)stream);
+    last_record(pl);
     if (int32_t e = check_launch("conv2d_wgrad")) return e;
-    int32_t finish = 0;
-    const int32_t e = wgrad_finish(d, (float*)workspace, pl.splits, pl.tapm, dw, (hipStream_t)stream, &finish);
-    last_or(LAST_FINISH, finish);
-    return e;
+    return wgrad_finish_launch(d, p.Cout, pl.splits, pl.finish, dw, (hipStream_t)stream);
 }
 
 int32_t p3d_x3_enable(int32_t on) { return fx_set_enabled(on); }
@@ -1599,6 +1684,24 @@ void p3d_conv_last_fp32_launch(int32_t* out) {
     if (!out) return;
     std::lock_guard<std::mutex> lock(g_last_mu);
     for (int i = 0; i < LAST_FIELDS; ++i) out[i] = g_last[i];
+}
+
+// Test hook (include/p3d_hip.h): the record the entry would leave, from the plan the entry follows; nothing is launched
+int32_t p3d_conv2d_fp32_plan(int32_t entry, const p3d_conv_desc* d, int32_t options, size_t workspace_bytes, int32_t* out) {
+    if (int32_t e = validate(d)) return e;
+    P3D_REQUIRE(out && entry >= 0 && entry <= 3 && options >= 0 && options < 32 && (entry != 1 || (options & 3) == 0),
+                "conv2d_fp32_plan: null record, an entry other than 0..3, unknown option bits, or a factor given to the eval entry");
+    const size_t head = entry == 1 ? eval_head_bytes(d) : 0;
+    const Fp32Call c{(options & 1) != 0, (options & 2) != 0, entry == 1, !(options & 4), !(options & 8), !(options & 16), workspace_bytes < head ? 0 : workspace_bytes - head};
+    Fp32Plan pl = entry <= 1 ? fp32_plan_fwd(d, c) : entry == 2 ? fp32_plan_dgrad(d, c) : fp32_plan_wgrad(d, c);
+    pl.refused |= workspace_bytes < head;
+    if (pl.refused || pl.window_2gib) {
+        fp32_record_empty(c.eval, out);
+        set_error("conv2d_fp32_plan: the entry refuses this call (%s)", pl.refused ? "workspace" : "per-block window exceeds 2 GiB");
+        return pl.refused ? P3D_EWORKSPACE : P3D_EINVAL;
+    }
+    fp32_record(pl, out);
+    return P3D_OK;
 }
 
 void p3d_conv_path_stats(uint64_t* counts, double* flops, int32_t reset) {

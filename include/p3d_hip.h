@@ -170,6 +170,17 @@ void p3d_conv_path_stats(uint64_t* counts, double* flops, int32_t reset);
  *   [12..15] 0 */
 #define P3D_FP32_LAUNCH_FIELDS 16
 void p3d_conv_last_fp32_launch(int32_t* out);
+/* TEST HOOK (tests/test_fp32_mfma_plan_host.py; nothing in the package calls it), host-only: how the fp32-MFMA family would run one call of an entry -- the plan the
+ * entry itself follows and the workspace queries read -- as the record p3d_conv_last_fp32_launch would give after that call.  Nothing is launched, no operand exists
+ * and the route is not consulted (the call is taken to have landed on this family).  entry: 0 p3d_conv2d_fwd, 1 p3d_conv2d_bn_eval_fwd, 2 p3d_conv2d_dgrad,
+ * 3 p3d_conv2d_wgrad.  `options` says what the operands would be:
+ *   bit 0  mask_in is given      bit 1  mult is given      (neither with entry 1)
+ *   bit 2  dy (weight gradient) is 4 B off a 16-B line      bit 3  x (weight gradient) is      bit 4  the result is: dx of a strided data gradient, dw
+ * workspace_bytes: what the call would be given; 0: no workspace.
+ * Returns P3D_EWORKSPACE where the entry would (the eval head, the staged classes of a strided data gradient or the weight-gradient slabs do not fit) and P3D_EINVAL
+ * for a malformed descriptor, an unknown entry or option and a weight gradient whose per-block window exceeds 2 GiB; out then holds the empty record (pass -1), or
+ * is untouched when the arguments themselves were refused. */
+int32_t p3d_conv2d_fp32_plan(int32_t entry, const p3d_conv_desc* d, int32_t options, size_t workspace_bytes, int32_t* out);
 /* db[k] (=|+=) sum_{n,h,w} dy[n,k,h,w]  (bias gradient of the regressor conv, depthnet.py:156). */
 int32_t p3d_conv2d_bgrad(const float* dy, int32_t N, int32_t K, int32_t HW, float* db, int32_t accumulate, void* stream);
 /* bias gradient of a PartialConv with bias (partial_conv.py:48-51: out = ((raw - b) * mult + b) * mask_out, so d out / d b = mask_out):
