@@ -594,8 +594,9 @@ class StemTailFn(torch.autograd.Function):
         x = x.contiguous()
         n, c, h, w = x.shape
         L, st = lib(), _stream()
-        y = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
-        idx = torch.empty((n, c, h // 2, w // 2), dtype=torch.uint8, device=x.device)
+        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1         # (h // 2, w // 2 at the even sides; the odd ones come with bn_any)
+        y = torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device)
+        idx = torch.empty((n, c, ho, wo), dtype=torch.uint8, device=x.device)
         mean = torch.empty(c, dtype=torch.float32, device=x.device)
         invstd = torch.empty_like(mean)
         ws = workspace(x.device, L.p3d_bn_workspace_bytes(n, c, h * w))
@@ -629,7 +630,12 @@ def stem_tail_usable(x, bn, pool):
     if (one(pool.kernel_size), one(pool.stride), one(pool.padding), one(pool.dilation)) != (3, 2, 1, 1) or pool.ceil_mode:
         return False
     n, c, h, w = x.shape
-    return bool(lib().p3d_stem_tail_supported(n, c, h, w))
+    L = lib()
+    if L.p3d_stem_tail_supported(n, c, h, w):
+        return True
+    on = L.p3d_bn_any_enable(0)         # (read the switch: set, then put back)
+    L.p3d_bn_any_enable(on)
+    return bool(on and L.p3d_stem_tail_any_supported(n, c, h, w))
 
 
 def stem_tail(x, bn):
@@ -947,6 +953,21 @@ def x3_any_strided(on):
     STRIDE-2 data gradients on the x3 kernels at maps the aligned kernels refuse -- the 129 -> 65 -> 33 -> 17 transitions of the default 257 crop, layers of 96 input
     channels or more -- as one ragged launch per parity class and one interleave pass, instead of the fp32-MFMA kernels.  Returns the previous setting."""
     return bool(lib().p3d_x3_any_strided_enable(int(bool(on))))
+
+
+def bn_any(on):
+    """Opt-in, OFF by default (P3D_BN_ANY=1 turns it on), independent of every other switch: BatchNorm calls whose rows start on no 16-B line (H * W no multiple
+    of 4: the 129 / 65 / 33 / 17 maps of the default 257 crop) run on the peeled 16-B instances of csrc/p3d_bn.hip instead of the element-by-element ones, and the
+    stem's maxpool(relu(bn(c))) stays one node (stem_tail) at any sides.  Returns the previous setting."""
+    return bool(lib().p3d_bn_any_enable(int(bool(on))))
+
+
+def bn_last_launch():
+    """What the last BatchNorm / stem-tail call launched (p3d_bn_last_launch): dict of entry (1 train_fwd, 2 train_bwd, 3 eval_fwd, 4 eval_bwd, 5 stem_tail_fwd,
+    6 stem_tail_bwd), instance (0 vector, 1 scalar, 2 peeled) and grid (x, y)."""
+    out = (ctypes.c_int32 * 4)()
+    lib().p3d_bn_last_launch(out)
+    return {'entry': out[0], 'instance': out[1], 'grid': (out[2], out[3])}
 
 
 def x3_any_images(on):

@@ -604,6 +604,20 @@ int32_t p3d_bn_eval_bwd(const float* dy, const float* x, const float* y, const f
                         const float* running_mean, const float* running_var, float* dx, float* dres,
                         float* dgamma, float* dbeta, int32_t N, int32_t C, int32_t HW, float eps, int32_t relu, int32_t accumulate,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* Opt-in, a switch of its own (default OFF; P3D_BN_ANY=1 in the environment turns it on; independent of every other switch): the four entries above run a call
+ * that their 16-B instances refuse (HW % 4 != 0, or a tensor off a 16-B line) on PEELED instances: a row -- the HW floats of one (n, c) -- is read as up to three
+ * single elements up to its first 16-B line, 16-B accesses, and up to three single elements behind its last full line (by one wavefront for rows of at most 1024
+ * elements, by the block for longer ones), so the 129 / 65 / 33 / 17 maps of the default 257 crop stream 16 B per lane instead of one dword.  Taken when every non-NULL tensor of the call is on a 4-B line and all are congruent mod 16 B (one peel
+ * serves them all); otherwise, and with the switch off, the entries launch exactly what they launched before.  Same per-element expressions, fp64 sums in an
+ * order fixed by the shape and the grid (two runs are bit-equal); the element-wise results (eval forward, dres, eval backward dx) are bit-equal to the
+ * element-by-element instance's, the sums of a training layer are added in another order.  p3d_bn_workspace_bytes is unchanged.  With the switch on
+ * p3d_stem_tail_fwd / _bwd also take the shapes of p3d_stem_tail_any_supported (below).  Returns the previous setting. */
+int32_t p3d_bn_any_enable(int32_t on);
+/* What the last call of p3d_bn_train_fwd / _train_bwd / _eval_fwd / _eval_bwd / p3d_stem_tail_fwd / _bwd of the process launched.  Host-side bookkeeping only.
+ * out[4]:  [0] the entry: 1 train_fwd, 2 train_bwd, 3 eval_fwd, 4 eval_bwd, 5 stem_tail_fwd, 6 stem_tail_bwd (0: none yet)
+ *          [1] the instance: 0 vector (16-B accesses), 1 scalar (element by element), 2 peeled (for the stem tail: the any-sides kernels)
+ *          [2] grid.x   [3] grid.y */
+void p3d_bn_last_launch(int32_t* out);
 
 /* Training through a frozen BatchNorm folded into its convolution (ops_frozen.py; csrc/p3d_frozen.hip): with s = gamma / sqrtf(var + eps), w' = w * s,
  * b' = beta - mean * s the layer is y = relu?(conv(x, w') + b' (+ res)), and its backward is g = dy * [y > 0] (g = dy without a ReLU), dres = g,
@@ -638,8 +652,13 @@ int32_t p3d_maxpool3x3s2_bwd(const float* dy, const uint8_t* idx, float* dx, int
  * route the pooled gradient through the argmax bytes on the fly.  Bit-identical to p3d_bn_train_fwd + p3d_maxpool3x3s2_fwd and their backward calls.
  * x [N,C,H,W] (H, W even, W % 4 == 0) -> y [N,C,H/2,W/2], idx [N,C,H/2,W/2] bytes; save_mean / save_invstd [C] feed backward.
  * workspace: p3d_bn_workspace_bytes(N, C, H * W).
+ * p3d_stem_tail_any_supported: N, C > 0, H >= 2, W >= 2, any parity (whatever the switch says).  While p3d_bn_any_enable is on, the two entries take a shape that
+ * p3d_stem_tail_supported refuses and this query admits: y and idx are [N,C,Ho,Wo] with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, idx in the encoding of
+ * p3d_maxpool3x3s2_fwd; x, y, dy on 4-B lines, x and dx congruent mod 16 B.  Bit-identical to the three calls under the same switch (tensors congruent mod 16 B).
+ * p3d_stem_tail_supported answers the same with the switch on or off.
  * ------------------------------------------------------------------------------------------ */
 int32_t p3d_stem_tail_supported(int32_t N, int32_t C, int32_t H, int32_t W);
+int32_t p3d_stem_tail_any_supported(int32_t N, int32_t C, int32_t H, int32_t W);
 int32_t p3d_stem_tail_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y, uint8_t* idx,
                           float* save_mean, float* save_invstd, int32_t N, int32_t C, int32_t H, int32_t W, float momentum, float eps, void* workspace,
                           size_t workspace_bytes, void* stream);

@@ -22,6 +22,13 @@
               TB/s of the bytes it has to move (the live planes read, dx written); the class launches are the call less its interleave.  With --step: legs `any`
               (ops.x3_any and ops.x3_any_images) and `strided` (those and ops.x3_any_strided) alternating, `strided` wins when it beats `any` by more than their
               combined spread; --frozen: the same two legs of the frozen-fold step (model.freeze_batchnorm(), ops.frozen_fold).
+  --bn        (depthnet; profiles/bn_anysize.md) BatchNorm and the stem tail on the peeled 16-B instances at the odd maps, ops.bn_any.  With --classes: every
+              (channels, map) of ResNet-50 at 257 -- p3d_bn_train_fwd (plain, ReLU, ReLU + residual), p3d_bn_train_bwd (ReLU with the recomputed mask; ReLU + residual),
+              p3d_bn_eval_fwd / _bwd (ReLU) --, the switch off (the element-by-element instance) and on (the peeled one) alternating with the aligned neighbour map
+              (128 / 64 / 32 / 16: the <true> instance, the yardstick), in ms and in TB/s of the tensors the pass has to read and write; then the stem at 64 x 129^2:
+              the three nodes with the switch off and on against the fused tail, and the fused tail at 128^2.  With --step: legs `any` (ops.x3_any and
+              ops.x3_any_images) and `bn` (those and ops.bn_any) alternating, `bn` wins when it beats `any` by more than their combined spread; --frozen: the two legs
+              of the frozen step, --no-fold: without ops.frozen_fold (every frozen BatchNorm is then a p3d_bn_eval_fwd / _bwd pair).
 GPU box only."""
 import argparse
 import ctypes
@@ -65,7 +72,11 @@ def switch(on, partial=False):
 
 
 def switch_leg(leg, strided=False):
-    switch(leg in ('on', 'any', 'both', 'images', 'strided'), leg == 'both')
+    switch(leg in ('on', 'any', 'both', 'images', 'strided', 'bn'), leg == 'both')
+    if hasattr(ops, 'bn_any'):
+        ops.bn_any(leg == 'bn')
+    elif leg == 'bn':
+        raise SystemExit('this build has no ops.bn_any')
     if hasattr(ops, 'x3_any_images'):
         ops.x3_any_images(leg == 'images' or strided)
     elif leg == 'images':
@@ -319,6 +330,109 @@ def classes_strided(a):
     print('sum over the classes x their layer counts, dgrad: off %.3f ms  on %.3f ms' % (total['off'], total['on']))
 
 
+# channels, odd map of ResNet-50 depthnet at 257 (its aligned neighbour is the map less one)
+BN_R50 = [(64, 129), (64, 65), (128, 65), (256, 65), (128, 33), (256, 33), (512, 33), (256, 17), (512, 17), (1024, 17), (2048, 17)]
+INSTANCE = {0: 'vector', 1: 'scalar', 2: 'peeled'}
+
+
+def classes_bn(a):
+    """every BatchNorm class of ResNet-50 at the odd maps: the entries with ops.bn_any off and on and at the aligned neighbour map; then the stem"""
+    L = pkg._lib.lib()
+    P, stream = ops._p, ops._stream()
+    legs = ('off', 'on', 'aligned')
+    total = {leg: 0.0 for leg in legs}
+    for (c, h) in BN_R50:
+        tag = 'c%d %dx%d' % (c, h, h)
+        if a.only and a.only not in tag:
+            continue
+        torch.manual_seed(c + h)
+        gamma, beta = torch.rand(c, device='cuda') + 0.5, torch.randn(c, device='cuda')
+        mean, invstd, dgamma, dbeta = (torch.empty(c, device='cuda') for _ in range(4))
+        ws = torch.empty(L.p3d_bn_workspace_bytes(a.batch, c, h * h), dtype=torch.uint8, device='cuda')
+        calls = {}
+        for leg, side in (('odd', h), ('aligned', h - 1)):
+            n, hw = a.batch, side * side
+            x, res, dy = (torch.randn(n, c, side, side, device='cuda') for _ in range(3))
+            y, dx, dres = (torch.empty_like(x) for _ in range(3))
+            rm, rv = torch.zeros(c, device='cuda'), torch.ones(c, device='cuda')
+            t = 4.0 * x.numel()
+
+            def make(x=x, res=res, dy=dy, y=y, dx=dx, dres=dres, rm=rm, rv=rv, n=n, hw=hw, t=t):
+                fwd = lambda r, relu: (lambda: L.p3d_bn_train_fwd(P(x), P(r), P(gamma), P(beta), P(rm), P(rv), P(y), P(mean), P(invstd), n, c, hw, 0.1, 1e-5, relu,
+                                                                  P(ws), ws.numel(), stream))
+                bwd = lambda yy, dr: (lambda: L.p3d_bn_train_bwd(P(dy), P(x), P(yy), P(gamma), P(beta), P(mean), P(invstd), P(dx), P(dr), P(dgamma), P(dbeta), n, c, hw,
+                                                                 1, 0, P(ws), ws.numel(), stream))
+                # the pass and the bytes it has to move: x is read by both kernels of a training pass, dy / x / y by both of a backward pass
+                return [('train_fwd plain', fwd(None, 0), 3 * t), ('train_fwd relu', fwd(None, 1), 3 * t), ('train_fwd relu+res', fwd(res, 1), 4 * t),
+                        ('train_bwd relu', bwd(None, None), 5 * t), ('train_bwd relu+res', bwd(y, dres), 8 * t),
+                        ('eval_fwd relu', lambda: L.p3d_bn_eval_fwd(P(x), None, P(gamma), P(beta), P(rm), P(rv), P(y), n, c, hw, 1e-5, 1, stream), 2 * t),
+                        ('eval_bwd relu', lambda: L.p3d_bn_eval_bwd(P(dy), P(x), P(y), P(gamma), P(rm), P(rv), P(dx), None, P(dgamma), P(dbeta), n, c, hw, 1e-5, 1, 0,
+                                                                    P(ws), ws.numel(), stream), 7 * t)]
+            calls[leg] = make()
+        for i, (name, _, _) in enumerate(calls['odd']):
+            fns = {'off': calls['odd'][i], 'on': calls['odd'][i], 'aligned': calls['aligned'][i]}
+            ms, ran = {leg: [] for leg in legs}, {}
+            for leg in legs:
+                ops.bn_any(leg == 'on')
+                for _ in range(3):
+                    assert fns[leg][1]() == 0, L.p3d_last_error()
+                ran[leg] = ops.bn_last_launch()['instance']
+            assert (ran['off'], ran['on'], ran['aligned']) == (1, 2, 0), (tag, name, ran)
+            for _ in range(a.rounds):
+                for leg in legs:
+                    ops.bn_any(leg == 'on')
+                    ms[leg].append(timed(fns[leg][1], a.iters))
+            ops.bn_any(False)
+            m = {leg: med(ms[leg]) for leg in legs}
+            spread = (m['off'][2] - m['off'][1]) + (m['on'][2] - m['on'][1])
+            verdict = 'on wins' if m['off'][0] - m['on'][0] > spread else 'on LOSES' if m['on'][0] - m['off'][0] > spread else 'tie'
+            print('%-14s %-18s | off %.3f [%.3f..%.3f] ms %.2f TB/s | on %.3f [%.3f..%.3f] ms %.2f TB/s | aligned %dx%d %.3f [%.3f..%.3f] ms %.2f TB/s | on/off %.2f  %s' % (
+                (tag, name) + m['off'] + (fns['off'][2] / m['off'][0] / 1e9,) + m['on'] + (fns['on'][2] / m['on'][0] / 1e9,) + (h - 1, h - 1) + m['aligned'] +
+                (fns['aligned'][2] / m['aligned'][0] / 1e9, m['on'][0] / m['off'][0], verdict)), flush=True)
+            for leg in legs:
+                total[leg] += m[leg][0]
+        del calls
+        torch.cuda.empty_cache()
+    print('sum over the classes and passes (one of each): off %.2f ms  on %.2f ms  aligned neighbours %.2f ms' % (total['off'], total['on'], total['aligned']))
+    if a.only and a.only != 'stem':
+        return
+    # the stem: maxpool(relu(bn(c))) forward + backward through autograd, as the network runs it
+    pool = pkg.nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+    bn = pkg.nn.BatchNorm2d(64).cuda().train()
+    legs = (('nodes off', 129, False, False), ('nodes on', 129, True, False), ('fused on', 129, True, True), ('fused 128x128', 128, False, True))
+    data = {}
+    for side in (129, 128):
+        x = torch.randn(a.batch, 64, side, side, device='cuda').requires_grad_(True)
+        data[side] = (x, torch.randn(a.batch, 64, (side - 1) // 2 + 1, (side - 1) // 2 + 1, device='cuda'))
+
+    def run(leg, backward):
+        name, side, on, fused = leg
+        x, dy = data[side]
+        ops.bn_any(on)
+        assert ops.stem_tail_usable(x, bn, pool) == (on or side == 128), leg
+        y = ops.stem_tail(x, bn) if fused else pool(bn(x, relu=True))
+        if backward:
+            x.grad = bn.weight.grad = bn.bias.grad = None
+            y.backward(dy)
+    for backward in (False, True):
+        ms = {leg: [] for leg in legs}
+        for leg in legs:
+            for _ in range(3):
+                run(leg, backward)
+        for _ in range(a.rounds):
+            for leg in legs:
+                ms[leg].append(timed(lambda: run(leg, backward), a.iters))
+        ops.bn_any(False)
+        for leg in legs:
+            x, dy = data[leg[1]]
+            moved = 4.0 * (2 * x.numel() + dy.numel()) + dy.numel()                     # forward: x twice, the pooled map and the argmax bytes
+            if backward:
+                moved += 4.0 * (3 * x.numel() + 2 * dy.numel()) + 2 * dy.numel()        # backward: x twice, dx, the pooled gradient and the bytes twice
+            m = med(ms[leg])
+            print('stem 64 ch, %s %-14s | %.3f [%.3f..%.3f] ms  %.2f TB/s of what the fused node has to move' % (
+                ('forward + backward' if backward else 'forward           ', leg[0]) + m + (moved / m[0] / 1e9,)), flush=True)
+
+
 def step(a):
     flags = ['-model', a.model, '-suffix', 'bench', '-data_name', 'h36m', '-save_path', '/tmp/p3d_bench', '-criterion', 'SmoothL1', '-num_joints', '17', '-side_in', str(a.side),
              '-stride', '16', '-depth', '16', '-depth_range', '1000', '-loss_div', '10', '-learn_rate', '5e-5', '-weight_decay', '4e-5', '-grad_norm', '5'] + FAMILY_FLAGS[a.family]
@@ -328,7 +442,7 @@ def step(a):
     model = model.cuda().train()
     if a.frozen:
         model.freeze_batchnorm()
-        ops.frozen_fold(True)
+        ops.frozen_fold(not a.no_fold)
     trainer = pkg.depth_train.Trainer(args, model, pkg.utils.get_info())
     trainer.verbose = False
     trainer.adapt_learn_rate(1)
@@ -343,6 +457,8 @@ def step(a):
         legs = ('any', 'images')
     if a.strided:
         legs = ('any', 'strided')
+    if a.bn:
+        legs = ('any', 'bn')
 
     def run(n):
         for i in range(n):
@@ -351,7 +467,7 @@ def step(a):
 
     ms, counts = {leg: [] for leg in legs}, {}
     for leg in legs:
-        switch_leg(leg, a.strided)
+        switch_leg(leg, a.strided or a.bn)
         run(a.warmup)
         torch.cuda.synchronize()
         ops.conv_path_stats(reset=True)
@@ -361,7 +477,7 @@ def step(a):
         counts[leg] = {fam: {p: st[fam][p][0] for p in PASSES} for fam in ('x3', 'fp32')}
     for r in range(a.rounds):
         for leg in legs:
-            switch_leg(leg, a.strided)
+            switch_leg(leg, a.strided or a.bn)
             run(2)
             torch.cuda.synchronize()
             ms[leg].append(timed(lambda: run(a.iters), 1) / a.iters)
@@ -369,7 +485,7 @@ def step(a):
     switch_leg('off')
     out = {'side': a.side, 'batch': a.batch, 'model': a.model, 'launches_per_step': counts}
     if a.frozen:
-        out['frozen_fold'] = True
+        out['frozen_fold'] = not a.no_fold
         ops.frozen_fold(False)
     if a.family != 'depthnet':
         out['family'] = a.family
@@ -391,6 +507,11 @@ def step(a):
         out['gain_ms'] = round(out['any']['median_ms'] - out['strided']['median_ms'], 3)
         out['combined_spread_ms'] = round(spread, 3)
         out['strided_wins'] = bool(out['gain_ms'] > spread)
+    elif legs == ('any', 'bn'):
+        spread = (out['any']['max_ms'] - out['any']['min_ms']) + (out['bn']['max_ms'] - out['bn']['min_ms'])
+        out['gain_ms'] = round(out['any']['median_ms'] - out['bn']['median_ms'], 3)
+        out['combined_spread_ms'] = round(spread, 3)
+        out['bn_wins'] = bool(out['gain_ms'] > spread)
     elif legs == ('off', 'on'):
         spread = (out['off']['max_ms'] - out['off']['min_ms']) + (out['on']['max_ms'] - out['on']['min_ms'])
         out['gain_ms'] = round(out['off']['median_ms'] - out['on']['median_ms'], 3)
@@ -413,15 +534,19 @@ def main():
     ap.add_argument('--only', default='')
     ap.add_argument('--images', action='store_true', help='the image-fed ragged path (ops.x3_any_images): see above')
     ap.add_argument('--strided', action='store_true', help='stride-2 data gradients on the x3 kernels (ops.x3_any_strided): see above')
-    ap.add_argument('--frozen', action='store_true', help='--step --strided: the frozen-fold step (every BatchNorm frozen, ops.frozen_fold)')
+    ap.add_argument('--bn', action='store_true', help='BatchNorm and the stem tail on the peeled instances (ops.bn_any): see above')
+    ap.add_argument('--frozen', action='store_true', help='--step --strided / --bn: the frozen-fold step (every BatchNorm frozen, ops.frozen_fold)')
+    ap.add_argument('--no-fold', action='store_true', help='--step --bn --frozen: every BatchNorm frozen, ops.frozen_fold off')
     ap.add_argument('--family', default='depthnet', choices=sorted(FAMILY_FLAGS))
     a = ap.parse_args()
-    if (a.images or a.strided) and a.family != 'depthnet':
-        raise SystemExit('--images and --strided measure the dense family')
-    if a.frozen and not (a.strided and a.step):
-        raise SystemExit('--frozen goes with --step --strided')
+    if (a.images or a.strided or a.bn) and a.family != 'depthnet':
+        raise SystemExit('--images, --strided and --bn measure the dense family')
+    if a.frozen and not ((a.strided or a.bn) and a.step):
+        raise SystemExit('--frozen goes with --step --strided or --step --bn')
+    if a.no_fold and not (a.frozen and a.bn):
+        raise SystemExit('--no-fold goes with --step --bn --frozen')
     if a.classes:
-        (classes_strided if a.strided else classes_images if a.images else classes if a.family == 'depthnet' else classes_partial)(a)
+        (classes_bn if a.bn else classes_strided if a.strided else classes_images if a.images else classes if a.family == 'depthnet' else classes_partial)(a)
     if a.step:
         step(a)
 
