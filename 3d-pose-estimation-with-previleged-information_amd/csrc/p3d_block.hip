@@ -38,6 +38,21 @@ static bool block_conv_ok(const p3d_conv_desc* d, bool main_chain) {
     return fx_applies(FX_FWD, d, BLOCK_MIN_M) && fx_applies(FX_DGRAD, d, BLOCK_MIN_M) && fx_applies(FX_WGRAD, d, BLOCK_MIN_M) && (d->Ho * d->Wo) % 4 == 0 &&
            (d->H * d->W) % 4 == 0 && d->C % 16 == 0 && d->K % 16 == 0 && !(main_chain && fx_dgrad_has_dead_classes(d));
 }
+// The same at any map width (p3d_block_any_enable / P3D_BLOCK_ANY=1, default off): the rule above without its map-size clauses, on the ragged instances -- all three passes
+// of every convolution at stride 1 (the ragged data gradient has no parity classes), whole weights, and a map of at least one K step of the image-fed weight gradient
+static int g_block_any = -1;       // -1: not decided yet (environment), 0 / 1: set
+static bool block_any_enabled() {
+    if (g_block_any < 0) { const char* e = getenv("P3D_BLOCK_ANY"); g_block_any = (e && atoi(e) == 1) ? 1 : 0; }
+    return g_block_any == 1;
+}
+static bool block_conv_any_ok(const p3d_conv_desc* d) {
+    // (the last clause is the operand rule of the weight gradient every slot of a ragged block runs -- both operands images, any map width: fx_wgrad_operands_ok,
+    // which is where "a map of at least one K step" is stated; asked of the plan so that the two cannot drift apart)
+    FxWgradOperands both_images{};
+    both_images.aimg = both_images.bimg = both_images.ragged = true;
+    return d->stride == 1 && fx_applies(FX_FWD, d, BLOCK_MIN_M, true) && fx_applies(FX_DGRAD, d, BLOCK_MIN_M, true) && fx_applies(FX_WGRAD, d, BLOCK_MIN_M, true) &&
+           d->C % 16 == 0 && d->K % 16 == 0 && d->c_offset == 0 && d->c_total == d->C && fx_wgrad_plan(d, both_images).ok;
+}
 
 __device__ __forceinline__ void blk_sum3(double& a, double& b, double& c, double* red /*[12]*/) {
     a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
@@ -276,6 +291,52 @@ __global__ __launch_bounds__(256) void block_open_bwd_kernel(const float* __rest
     }
 }
 
+// The two passes at any HW (a ragged block: a channel plane of odd length is only 4-B aligned): one element per lane over the same flat index, the same grid,
+// expressions and fp64 sums.  No mask bytes (a plane's last byte would be shared with the next plane's first): backward takes [out > 0] from `out`, and g is
+// always written when the block ends in a ReLU.
+__global__ __launch_bounds__(256) void block_close_fwd_any_kernel(const float* __restrict__ c, const CloseFin fin, const float* __restrict__ res, const CloseFin rfin,
+                                                                  float* __restrict__ out, int N, int C, int HW, int relu, double count) {
+    const int ch = blockIdx.x, s = blockIdx.y, split = gridDim.y;
+    __shared__ double red[12];
+    float sc, sh, rsc = 1.f, rsh = 0.f;
+    close_finalize(fin, ch, C, count, s == 0, red, sc, sh);
+    const bool ds = rfin.partial != nullptr;
+    if (ds) close_finalize(rfin, ch, C, count, s == 0, red, rsc, rsh);
+    const int nimg = (N - s + split - 1) / split, total = nimg * HW;
+    for (int j = threadIdx.x; j < total; j += 256) {
+        const int k = j / HW;
+        const size_t i = ((size_t)(s + k * split) * C + ch) * (size_t)HW + (j - k * HW);
+        const float r = res[i], v = fmaf(c[i], sc, sh) + (ds ? fmaf(r, rsc, rsh) : r);
+        out[i] = relu ? fmaxf(v, 0.f) : v;
+    }
+}
+
+__global__ __launch_bounds__(256) void block_open_bwd_any_kernel(const float* __restrict__ dout, const float* __restrict__ out, const float* __restrict__ c,
+                                                                 const float* __restrict__ tab, const float* __restrict__ rc, const float* __restrict__ rtab,
+                                                                 float* __restrict__ gbuf, double* __restrict__ partial, int N, int C, int HW, int relu) {
+    const int ch = blockIdx.x, s = blockIdx.y, split = gridDim.y;
+    const float mean = tab[ch * FX_TAB + 2], rmean = rtab ? rtab[ch * FX_TAB + 2] : 0.f;
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    const int nimg = (N - s + split - 1) / split, total = nimg * HW;
+    for (int j = threadIdx.x; j < total; j += 256) {
+        const int k = j / HW;
+        const size_t i = ((size_t)(s + k * split) * C + ch) * (size_t)HW + (j - k * HW);
+        float g = dout[i];
+        if (relu) {
+            g = out[i] > 0.f ? g : 0.f;
+            gbuf[i] = g;
+        }
+        s1 += g; s2 += g * (c[i] - mean);
+        if (rc) s3 += g * (rc[i] - rmean);
+    }
+    __shared__ double red[12];
+    blk_sum3(s1, s2, s3, red);
+    if (threadIdx.x == 0) {
+        double* dst = partial + ((size_t)ch * split + s) * 3;
+        dst[0] = s1; dst[1] = s2; dst[2] = s3;
+    }
+}
+
 // BatchNorm-backward sums for a data gradient whose kernel could not take them in its epilogue (strided dgrad): (sum gg, sum gg (c - mean)) with
 // gg = g * [c * sc + sh > 0]; partial [C][split][3] fp64 like the opening pass
 __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const float* __restrict__ g, const float* __restrict__ c, const float* __restrict__ tab,
@@ -366,7 +427,7 @@ static bool masked_conv_ok(const p3d_conv_desc* d) { return fx_masked_applies(FX
 
 // The admission predicate of the executor (b non-null, nconv 2 or 3): 0 = every slot is taken; otherwise *slot is the first one refused, 1 = its shape is outside
 // the fused path, 2 = it is a partial convolution outside the masked instances
-static int block_refusal(const p3d_block_desc* b, int* slot) {
+static int block_refusal_aligned(const p3d_block_desc* b, int* slot) {
     for (int i = 0; i < 4; ++i) {
         if (!block_slot(b, i)) continue;
         *slot = i;
@@ -374,6 +435,20 @@ static int block_refusal(const p3d_block_desc* b, int* slot) {
         if (b->masked && i != 3 && !masked_conv_ok(&b->conv[i])) return 2;
     }
     return 0;
+}
+// A RAGGED block: a dense block the rule above refuses, under p3d_block_any_enable, whose every convolution (downsample included) block_conv_any_ok takes -- refused for
+// its map size only.  Derived from the descriptor wherever it matters (the admission, the image format, the workspace layout, both directions): an aligned block never
+// is one, whatever the switch says; strided and masked blocks at odd maps stay refused.
+static bool block_ragged(const p3d_block_desc* b) {
+    int slot = 0;
+    if (!block_any_enabled() || b->masked || block_refusal_aligned(b, &slot) != 1) return false;
+    for (int i = 0; i < 4; ++i)
+        if (block_slot(b, i) && !block_conv_any_ok(&b->conv[i])) return false;
+    return true;
+}
+static int block_refusal(const p3d_block_desc* b, int* slot) {
+    const int why = block_refusal_aligned(b, slot);
+    return why == 1 && block_ragged(b) ? 0 : why;
 }
 static int32_t check_block(const p3d_block_desc* b) {
     P3D_REQUIRE(b != nullptr, "block: null descriptor");
@@ -388,7 +463,8 @@ static int32_t check_block(const p3d_block_desc* b) {
 
 // The form of a block's activation images a_i and gradient images d c_i: fp32 row images (4 B per element; the row-fed kernel instances cut the pieces themselves) for
 // dense blocks, three bf16 planes (6 B) for masked blocks -- the partial-convolution instances are plane-fed -- and for every block under p3d_fx_tune(6, 1)
-static bool block_row_images(const p3d_block_desc* b) { return !b->masked && fx_block_row_images(); }
+// (a ragged block: planes too -- the ragged image-fed instances are plane-fed)
+static bool block_row_images(const p3d_block_desc* b) { return !b->masked && fx_block_row_images() && !block_ragged(b); }
 
 // The executor's two workspaces.  main (the launch stream's) = [conv scratch: weight images, split-K slabs | partial sums | the downsample conv's partial sums]: the
 // closing conv's and the downsample conv's sums live side by side until the closing pass has read both; side (the weight-gradient stream's) = slabs.
@@ -396,15 +472,16 @@ struct BlockLayout { size_t conv_ws, part_bytes, main_bytes, side_bytes; };
 static BlockLayout block_layout(const p3d_block_desc* b) {
     size_t mw = 0, sw = 0, part = 0;
     auto atleast = [](size_t& m, size_t v) { if (v > m) m = v; };
+    const bool rag = block_ragged(b);          // the ragged plans: slabs on 16-B lines, partial rows = 128-pixel tiles (a launch with sums is never split)
     for (int i = 0; i < 4; ++i) {
         if (!block_slot(b, i)) continue;
         const p3d_conv_desc* d = &b->conv[i];
-        atleast(mw, fx_workspace(FX_FWD, d));
-        atleast(mw, fx_workspace(FX_DGRAD, d));
-        atleast(part, (size_t)fx_partial_rows(FX_FWD, d) * d->K * 2 * sizeof(float));
-        atleast(part, (size_t)fx_partial_rows(FX_DGRAD, d) * d->C * 2 * sizeof(float));
+        atleast(mw, fx_workspace(FX_FWD, d, rag));
+        atleast(mw, fx_workspace(FX_DGRAD, d, rag));
+        atleast(part, (size_t)fx_partial_rows(FX_FWD, d, rag) * d->K * 2 * sizeof(float));
+        atleast(part, (size_t)fx_partial_rows(FX_DGRAD, d, rag) * d->C * 2 * sizeof(float));
         atleast(part, (size_t)(d->K > d->C ? d->K : d->C) * CLOSE_MAX_SPLIT * 3 * sizeof(double));      // the opening pass's and bn_bwd_sums_kernel's fp64 sums
-        atleast(sw, fx_workspace(FX_WGRAD, d));
+        atleast(sw, fx_workspace(FX_WGRAD, d, rag));
     }
     return BlockLayout{align256(mw), align256(part), align256(mw) + 2 * align256(part), align256(sw)};
 }
@@ -459,6 +536,18 @@ int32_t p3d_block_supported(const p3d_block_desc* b) {
     return fx_enabled() && b && (b->nconv == 2 || b->nconv == 3) && block_refusal(b, &slot) == 0 ? 1 : 0;
 }
 
+// on = 1 / 0: the executor also takes ragged blocks (block_ragged) / refuses them as ever.  Returns the previous setting.
+int32_t p3d_block_any_enable(int32_t on) {
+    const int32_t before = block_any_enabled() ? 1 : 0;
+    g_block_any = on ? 1 : 0;
+    return before;
+}
+
+// 1: p3d_block_supported admits the block as a ragged one (host-only)
+int32_t p3d_block_any_supported(const p3d_block_desc* b) {
+    return fx_enabled() && b && (b->nconv == 2 || b->nconv == 3) && block_ragged(b) ? 1 : 0;
+}
+
 size_t p3d_block_image_bytes(const p3d_block_desc* b, int32_t N, int32_t C, int32_t HW) {
     if (!b || N <= 0 || C <= 0 || HW <= 0) return 0;
     return block_row_images(b) ? fx_row_image_bytes(N, C, HW) : fx_act_image_bytes(N, C, HW);
@@ -482,6 +571,13 @@ int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
     float* partial2 = (float*)((char*)partial + lay.part_bytes);      // the downsample conv's partial sums
     const int last = b->nconv - 1;
     const bool rows = block_row_images(b);
+    // a ragged block: every convolution image-fed on the ragged instances (STATS epilogue); the block input as a plane image of its own, written once here and kept
+    // in aimg[3] for the weight gradients of conv 0 and of the downsample conv
+    const bool rag = block_ragged(b);
+    if (rag) {
+        P3D_REQUIRE(io->aimg[3], "block_fwd: null image of the block input (aimg[3]: a block at a map width outside the aligned kernels)");
+        if (int32_t e = fx_act_image_any(io->x, io->aimg[3], b->conv[0].N, b->conv[0].C, b->conv[0].H * b->conv[0].W, st)) return e;
+    }
     for (int i = 0; i < 4; ++i) {
         const bool ds = i == 3;
         if (!block_slot(b, i)) continue;
@@ -490,8 +586,9 @@ int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
         const bool from_x = ds || i == 0;          // the block input arrives as fp32 (split in the kernel); everything produced inside the block as an image
         if (!from_x) P3D_REQUIRE(io->aimg[i - 1], "block_fwd: null activation image %d", i - 1);
         FxFuse f{};
-        f.act_img = from_x ? nullptr : io->aimg[i - 1];
+        f.act_img = from_x ? (rag ? io->aimg[3] : nullptr) : io->aimg[i - 1];
         f.rows = !from_x && rows;
+        f.ragged = rag;
         f.partial = ds ? partial2 : partial;
         f.wimg = io->wimg[i];
         const bool mk = b->masked && !ds;
@@ -509,15 +606,24 @@ int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
         // a_i = relu(bn_i(c_i)), written once, as the image the next convolution (and, in backward, its weight gradient) copies into LDS
         P3D_REQUIRE(io->aimg[i], "block_fwd: null activation image %d", i);
         const double cnt = (double)d->N * d->Ho * d->Wo;
-        const CloseFin cf = finalize_fwd(block_bn(b, io, i), partial, fx_partial_rows(FX_FWD, d), d->K, cnt, st);
+        const CloseFin cf = finalize_fwd(block_bn(b, io, i), partial, fx_partial_rows(FX_FWD, d, rag), d->K, cnt, st);
         const FxFinalize fin = act_finalize(cf, cnt);
+        if (rag) {
+            if (int32_t e = fx_act_image_any_map(1, io->c[i], nullptr, io->table[i], 0, io->aimg[i], d->N, d->K, d->Ho * d->Wo, st, cf.rows ? &fin : nullptr)) return e;
+            continue;
+        }
         if (int32_t e = fx_act_image(1, io->c[i], nullptr, io->table[i], 0, io->aimg[i], d->N, d->K, d->Ho * d->Wo, st, cf.rows ? &fin : nullptr, mk ? io->pix_in[i + 1] : nullptr, rows)) return e;
     }
     const p3d_conv_desc* dl = &b->conv[last];
     const int HW = dl->Ho * dl->Wo;
     const double cnt_close = (double)dl->N * HW;
-    const CloseFin cf = finalize_fwd(block_bn(b, io, last), partial, fx_partial_rows(FX_FWD, dl), dl->K, cnt_close, st);
-    const CloseFin rf = b->has_downsample ? finalize_fwd(block_bn(b, io, 3), partial2, fx_partial_rows(FX_FWD, &b->conv[3]), dl->K, cnt_close, st) : CloseFin{};
+    const CloseFin cf = finalize_fwd(block_bn(b, io, last), partial, fx_partial_rows(FX_FWD, dl, rag), dl->K, cnt_close, st);
+    const CloseFin rf = b->has_downsample ? finalize_fwd(block_bn(b, io, 3), partial2, fx_partial_rows(FX_FWD, &b->conv[3], rag), dl->K, cnt_close, st) : CloseFin{};
+    if (rag) {
+        hipLaunchKernelGGL(block_close_fwd_any_kernel, dim3(dl->K, close_split(dl->N, dl->K)), dim3(256), 0, st, (const float*)io->c[last], cf,
+                           b->has_downsample ? (const float*)io->c[3] : io->x, rf, io->out, dl->N, dl->K, HW, b->relu_out, cnt_close);
+        return check_launch("block_fwd");
+    }
     hipLaunchKernelGGL(block_close_fwd_kernel, dim3(dl->K, close_split(dl->N, dl->K)), dim3(256), 0, st, (const float*)io->c[last], cf,
                        b->has_downsample ? (const float*)io->c[3] : io->x, rf, io->out, b->relu_out ? io->out_mask : (unsigned char*)nullptr, dl->N, dl->K, HW, b->relu_out, cnt_close);
     return check_launch("block_fwd");
@@ -536,6 +642,7 @@ struct BwdCtx {
     hipStream_t st, ss;
     bool two;                       // ss is a stream of its own
     bool rows;                      // aimg / dcimg are fp32 row images (block_row_images)
+    bool rag;                       // a ragged block (block_ragged): plane images, the ragged instances, the passes for any HW; no mask bytes, g always in memory
     int acc, last;
     // g = dout * [out > 0] never exists as a tensor when forward left mask bytes: the two opening image passes mask dout themselves, and with an identity
     // shortcut the first convolution's data gradient adds the masked dout in its epilogue (dx = dgrad + dout * mask) instead of accumulating into a copy of g
@@ -556,6 +663,7 @@ static int32_t bwd_map(const BwdCtx& x, const float* gin, int slot, int masked, 
     P3D_REQUIRE(io->dcimg[slot], "block_bwd: null gradient image %d", slot);
     FxFinalize fin = finalize_bwd(block_bn(x.b, io, slot), kind, x.partial, rows, which, dc->K, cnt, x.acc, x.st);
     fin.gmask = front_mask;
+    if (x.rag) return fx_act_image_any_map(2, gin, io->c[slot], io->table[slot], masked, io->dcimg[slot], dc->N, dc->K, dc->Ho * dc->Wo, x.st, fin.kind ? &fin : nullptr);
     return fx_act_image(2, gin, io->c[slot], io->table[slot], masked, io->dcimg[slot], dc->N, dc->K, dc->Ho * dc->Wo, x.st, fin.kind ? &fin : nullptr, bwd_pixmul(x, slot), x.rows);
 }
 
@@ -567,7 +675,7 @@ static int32_t launch_wgrad(const BwdCtx& x, int slot, const float* xin, const v
     ProfScope ps(2, d, x.ss);
     fx_count(2, d);
     FxFuse fw{};
-    fw.dy_img = x.io->dcimg[slot]; fw.x_img = ximg; fw.rows = x.rows;
+    fw.dy_img = x.io->dcimg[slot]; fw.x_img = ximg; fw.rows = x.rows; fw.ragged = x.rag;
     if (x.b->masked && slot != 3 && !ximg) fw.emask = x.io->pix_in[slot];      // the block input is fp32: x * mask_in in the kernel's split (an image carries it)
     return fx_conv_wgrad(d, nullptr, xin, x.io->dw[slot], x.acc, x.side_ws, x.side_bytes, &fw, "block_bwd", x.ss);
 }
@@ -583,6 +691,12 @@ static int32_t bwd_open(const BwdCtx& x) {
     const p3d_block_desc* b = x.b;
     const p3d_block_io* io = x.io;
     const p3d_conv_desc* dl = &b->conv[x.last];
+    if (x.rag) {
+        hipLaunchKernelGGL(block_open_bwd_any_kernel, dim3(dl->K, close_split(dl->N, dl->K)), dim3(256), 0, x.st, io->dout, (const float*)io->out, (const float*)io->c[x.last],
+                           (const float*)io->table[x.last], b->has_downsample ? (const float*)io->c[3] : (const float*)nullptr,
+                           b->has_downsample ? (const float*)io->table[3] : (const float*)nullptr, io->gbuf, (double*)x.partial, dl->N, dl->K, dl->Ho * dl->Wo, b->relu_out);
+        return check_launch("block_bwd open");
+    }
     hipLaunchKernelGGL(block_open_bwd_kernel, dim3(dl->K, close_split(dl->N, dl->K)), dim3(256), 0, x.st, io->dout, (const float*)io->out, (const float*)io->c[x.last],
                        (const float*)io->table[x.last], b->has_downsample ? (const float*)io->c[3] : (const float*)nullptr,
                        b->has_downsample ? (const float*)io->table[3] : (const float*)nullptr, x.g_in_memory ? io->gbuf : (float*)nullptr, (double*)x.partial,
@@ -599,7 +713,7 @@ static int32_t bwd_open_images(const BwdCtx& x) {
     const int split = close_split(dl->N, dl->K);
     const double cnt = (double)dl->N * dl->Ho * dl->Wo;
     for (int i = 0; b->masked && i < b->nconv; ++i) P3D_REQUIRE(io->pix_in[i] && io->pix_out[i], "block_bwd: null per-pixel factor of partial convolution %d", i);
-    if (b->has_downsample && fx_pair_map_enabled()) {
+    if (b->has_downsample && fx_pair_map_enabled() && !x.rag) {             // (the pair pass is aligned-only: a ragged block takes the two passes below)
         // both images in one pass: g (dout and the mask bytes) is read once
         P3D_REQUIRE(io->dcimg[last] && io->dcimg[3], "block_bwd: null gradient image");
         const FxFinalize fa = finalize_bwd(block_bn(b, io, last), 3, x.partial, split, 0, dl->K, cnt, x.acc, x.st);
@@ -620,7 +734,7 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
         if (i > 0) P3D_REQUIRE(io->aimg[i - 1], "block_bwd: null activation image %d", i - 1);
         FxFuse f{};
         f.wimg = io->wimgT[i];
-        f.act_img = io->dcimg[i]; f.rows = x.rows;
+        f.act_img = io->dcimg[i]; f.rows = x.rows; f.ragged = x.rag;
         p3d_conv_desc dd = *d;
         if (i > 0) {
             const p3d_conv_desc* dp = &b->conv[i - 1];                       // producer of this conv's input
@@ -633,7 +747,7 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
             if (int32_t e = launch_wgrad(x, i, nullptr, io->aimg[i - 1], ready)) return e;
             const double cnt = (double)dp->N * dp->Ho * dp->Wo;
             if (epi) {
-                if (int32_t e = bwd_map(x, io->da[i - 1], i - 1, 1, 2, fx_partial_rows(FX_DGRAD, d), 0, cnt)) return e;
+                if (int32_t e = bwd_map(x, io->da[i - 1], i - 1, 1, 2, fx_partial_rows(FX_DGRAD, d, x.rag), 0, cnt)) return e;
             } else {
                 // a strided data gradient takes no sums in its epilogue: a pass of their own
                 const int sp = close_split(dp->N, dp->K);
@@ -658,7 +772,7 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
             }
             if (int32_t e = bwd_dgrad(x, 0, &dd, dx, &f)) return e;
         }
-        if (int32_t e = launch_wgrad(x, 0, io->x, nullptr, ready)) return e;
+        if (int32_t e = launch_wgrad(x, 0, io->x, x.rag ? io->aimg[3] : nullptr, ready)) return e;      // (ragged: against the image of x kept from forward)
     }
     return P3D_OK;
 }
@@ -668,12 +782,12 @@ static int32_t bwd_downsample(const BwdCtx& x, hipEvent_t ready) {
     if (x.b->need_dx) {
         FxFuse f{};
         f.wimg = x.io->wimgT[3];
-        f.act_img = x.io->dcimg[3]; f.rows = x.rows;
+        f.act_img = x.io->dcimg[3]; f.rows = x.rows; f.ragged = x.rag;
         p3d_conv_desc dd = x.b->conv[3];
         dd.accumulate = 1;
         if (int32_t e = bwd_dgrad(x, 3, &dd, x.io->dx, &f)) return e;
     }
-    return launch_wgrad(x, 3, x.io->x, nullptr, ready);
+    return launch_wgrad(x, 3, x.io->x, x.rag ? x.io->aimg[3] : nullptr, ready);
 }
 
 // dout -> dx (+ every parameter gradient, accumulated into io->dw / dgamma / dbeta when b->accumulate_grads, else written).
@@ -686,7 +800,9 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
     P3D_REQUIRE(io && io->x && io->out && io->dout, "block_bwd: null tensor");
     BwdCtx x{};
     x.b = b; x.io = io;
-    x.g_in_memory = !(b->relu_out && io->out_mask && (b->has_downsample || !b->need_dx || fx_dgrad_accumulates_from_source(&b->conv[0])));
+    x.rag = block_ragged(b);
+    P3D_REQUIRE(!x.rag || io->aimg[3], "block_bwd: null image of the block input (aimg[3])");
+    x.g_in_memory = x.rag || !(b->relu_out && io->out_mask && (b->has_downsample || !b->need_dx || fx_dgrad_accumulates_from_source(&b->conv[0])));
     P3D_REQUIRE(!x.g_in_memory || !b->relu_out || io->gbuf, "block_bwd: null gradient buffer");
     const BlockLayout lay = block_layout(b);
     if (!workspace || workspace_bytes < lay.main_bytes || !side_workspace || side_bytes < lay.side_bytes) {
@@ -698,7 +814,7 @@ int32_t p3d_block_bwd(const p3d_block_desc* b, const p3d_block_io* io, void* wor
     x.two = x.ss != x.st;
     x.acc = b->accumulate_grads; x.last = b->nconv - 1; x.rows = block_row_images(b);
     x.g = (b->relu_out && x.g_in_memory) ? io->gbuf : io->dout;
-    x.gmask = x.g_in_memory ? nullptr : io->out_mask;
+    x.gmask = x.g_in_memory ? nullptr : io->out_mask;          // (a ragged block has no mask bytes: io->out_mask is not looked at)
 
     if (int32_t e = bwd_open(x)) return e;
     if (int32_t e = bwd_open_images(x)) return e;
@@ -1063,6 +1179,7 @@ int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, co
 // What the forward / data-gradient launchers launched, and what they can launch (include/p3d_hip.h)
 int32_t p3d_fx_launch_log(int32_t* out, int32_t max_records, int32_t reset) { return fx_launch_log(out, out && max_records > 0 ? max_records : 0, reset); }
 int32_t p3d_fx_conv_instances(int32_t* out, int32_t max_records) { return fx_conv_instances(out, out && max_records > 0 ? max_records : 0); }
+int32_t p3d_fx_conv_any_sums_instances(int32_t* out, int32_t max_records) { return fx_conv_any_sums_instances(out, out && max_records > 0 ? max_records : 0); }
 
 // Test hook: fx_conv_fwd / fx_conv_dgrad with any FxFuse (include/p3d_hip.h).  Checks what the launchers take for granted from their callers -- the pointers, a
 // well-formed descriptor, the shape rule of the pass -- and leaves every other refusal to them.  No zero fill of dead parity classes, no path count.
@@ -1081,6 +1198,10 @@ int32_t p3d_fx_conv_fused_partial_rows(int32_t pass, const p3d_conv_desc* d) {
     if (!fx_applies(pass == 0 ? FX_FWD : FX_DGRAD, d, 32, false) && !fx_applies(pass == 0 ? FX_FWD : FX_DGRAD, d, 32, true)) return 0;
     return fx_partial_rows(pass == 0 ? FX_FWD : FX_DGRAD, d);
 }
+int32_t p3d_fx_conv_fused_partial_rows_any(int32_t pass, const p3d_conv_desc* d) {
+    if (!fused_desc_ok(d) || pass < 0 || pass > 1 || d->stride != 1 || !fx_applies(pass == 0 ? FX_FWD : FX_DGRAD, d, 32, true)) return 0;
+    return fx_partial_rows(pass == 0 ? FX_FWD : FX_DGRAD, d, true);
+}
 int32_t p3d_fx_conv_fused(int32_t pass, const p3d_conv_desc* d, const p3d_fx_fuse* f, const float* src, const float* w, const float* bias, float* out, void* workspace,
                           size_t workspace_bytes, void* stream) {
     P3D_REQUIRE(d && f && w && out && (src || f->act_img) && (pass == 0 || pass == 1), "fx_conv_fused: null argument, or a pass other than 0 / 1");
@@ -1098,6 +1219,22 @@ int32_t p3d_fx_conv_fused(int32_t pass, const p3d_conv_desc* d, const p3d_fx_fus
     x.acc_src = f->acc_src; x.acc_mask = f->acc_mask; x.infer = f->infer != 0; x.res = f->res; x.relu = f->relu != 0; x.rows = f->rows != 0; x.ragged = rag;
     return name_entry("fx_conv_fused", pass == 0 ? fx_conv_fwd(d, src, w, bias, out, workspace, workspace_bytes, &x, (hipStream_t)stream)
                                                  : fx_conv_dgrad(d, src, w, out, workspace, workspace_bytes, &x, (hipStream_t)stream));
+}
+
+// Test hook: one image pass of mode 1 / 2 with its finalize prologue, aligned or at any HW (include/p3d_hip.h)
+int32_t p3d_fx_act_image_fused(int32_t any, int32_t mode, const float* x, const float* x2, float* table, int32_t masked, void* img, int32_t N, int32_t C, int32_t HW,
+                               int32_t kind, const void* partial, int32_t rows, int32_t which, double count, const float* gamma, const float* beta, float* running_mean,
+                               float* running_var, float momentum, float eps, float* dgamma, float* dbeta, int32_t accumulate, void* stream) {
+    P3D_REQUIRE(mode == 1 || mode == 2, "fx_act_image_fused: modes 1 and 2");
+    P3D_REQUIRE(kind == 0 || (kind >= 1 && kind <= 3 && count > 0 && (which == 0 || which == 1)), "fx_act_image_fused: bad finalize request (kind %d)", kind);
+    FxFinalize f{};
+    if (kind != 0) {
+        f.kind = kind; f.partial = partial; f.rows = rows; f.which = which; f.count = count; f.gamma = gamma; f.beta = beta; f.running_mean = running_mean;
+        f.running_var = running_var; f.momentum = momentum; f.eps = eps; f.dgamma = dgamma; f.dbeta = dbeta; f.accumulate = accumulate; f.table = table;
+    }
+    const FxFinalize* fp = kind ? &f : nullptr;
+    return any ? fx_act_image_any_map(mode, x, x2, table, masked, img, N, C, HW, (hipStream_t)stream, fp)
+               : fx_act_image(mode, x, x2, table, masked, img, N, C, HW, (hipStream_t)stream, fp);
 }
 
 // Test hook: how a weight gradient would be planned, as a record (include/p3d_hip.h).  Host-only.

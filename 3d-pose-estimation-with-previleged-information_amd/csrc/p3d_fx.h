@@ -80,8 +80,8 @@ struct FxFuse {
     int relu;
     int rows;               // 1: act_img / dy_img / x_img are fp32 ROW images (fx_row_image: [N][C/16][HW][16] floats, 4 B per element) that the kernel cuts into the three
                             // pieces itself -- dense aligned training launches only (no factor, not ragged, not inference): what the block executor keeps a_i and d c_i as
-    int ragged;             // 1: the ragged instances (any map width), for inference and training alike; fp32 operands, or (dense training launches only, nothing else set:
-                            // p3d_fx_conv_*_img_any) act_img for FWD / DGRAD (stride 1) and dy_img AND x_img for WGRAD (fx_wgrad_any_img_kernel).  With `infer`: dense, or a partial convolution
+    int ragged;             // 1: the ragged instances (any map width), for inference and training alike; fp32 operands, or (dense training launches only, nothing else set
+                            // but `partial` with its ep_c / ep_tab -- the ragged residual blocks: one unsplit launch; p3d_fx_conv_*_img_any) act_img for FWD / DGRAD (stride 1) and dy_img AND x_img for WGRAD (fx_wgrad_any_img_kernel).  With `infer`: dense, or a partial convolution
                             // with pmask and emask.  Without: FWD / DGRAD (stride 1) with the plain epilogue, WGRAD on fx_wgrad_any_kernel -- dense fp32-fed training
                             // launches (p3d_x3_any_enable), no other field set; or the same three as a partial convolution (p3d_x3_any_partial_enable): pmask AND
                             // emask set, nothing else -- the factor epilogue, fx_wgrad_any_masked_kernel
@@ -135,6 +135,7 @@ void fx_stats(unsigned long long* counts, double* flops, int reset);
 // the log of forward / data-gradient conv-kernel launches and the list of compiled instances (p3d_fx_launch_log, p3d_fx_conv_instances: include/p3d_hip.h)
 int32_t fx_launch_log(int32_t* out, int32_t max_records, int32_t reset);
 int32_t fx_conv_instances(int32_t* out, int32_t max_records);
+int32_t fx_conv_any_sums_instances(int32_t* out, int32_t max_records);      // the ragged image-fed BatchNorm instances, a list of their own (p3d_fx_conv_any_sums_instances)
 // Which convolutions the x3 kernels take, per pass: one rule each (p3d_fx.hip).  min_m: the least channel count of the result's tile rows the caller finds worth it (96:
 // the per-layer entries; 64: the block executor; 32: image-fed and inference callers).  ragged: the instances that take any map width -- the same rule without its
 // width / alignment clauses (forward: W % 4, Wo % 4; data gradient: those, and stride 1 only; weight gradient: (Ho Wo) % 16, Wo % 4, W % 4), so it cannot drift
@@ -152,7 +153,7 @@ FxStridedPlan fx_dgrad_strided_any_plan(const p3d_conv_desc* d);
 int32_t fx_conv_dgrad_strided_any(const p3d_conv_desc* d, const float* dy, const float* w, void* workspace, size_t workspace_bytes, int* live_mask, hipStream_t st);
 size_t fx_workspace(FxPass pass, const p3d_conv_desc* d, bool ragged = false);         // FX_FWD / FX_DGRAD: weight image + split-K slabs of the call's plan; FX_WGRAD: slabs for the larger of the two
                                                                                        // split counts (fp32- or image-fed x), what a caller reserves before it knows which
-int fx_partial_rows(FxPass pass, const p3d_conv_desc* d);                              // FX_FWD / FX_DGRAD: rows of the per-channel partial sums of a launch with a sums epilogue
+int fx_partial_rows(FxPass pass, const p3d_conv_desc* d, bool ragged = false);         // FX_FWD / FX_DGRAD: rows of the per-channel partial sums of a launch with a sums epilogue (ragged: never split, one row per 128-pixel tile)
 bool fx_dgrad_has_dead_classes(const p3d_conv_desc* d);
 int32_t fx_dgrad_zero_dead_classes(const p3d_conv_desc* d, float* dx, hipStream_t st);      // zero-fills dx when the call does not accumulate and leaves such pixels untouched
 bool fx_dgrad_accumulates_from_source(const p3d_conv_desc* d);      // stride 1 and no split-K: FxFuse::acc_src is honoured
@@ -235,6 +236,9 @@ int32_t fx_act_image(int mode, const float* x, const float* x2, const float* tab
                      const FxFinalize* fin = nullptr, const float* pixmul = nullptr, bool rows = false);
 // mode 0 at any HW (the same bytes; x read with dword loads where a row is not 16-B aligned, the last pixel group of an image partial)
 int32_t fx_act_image_any(const float* x, void* img, int N, int C, int HW, hipStream_t st);
+// modes 1 and 2 at any HW, plane images only: the maps and the optional finalize prologue of fx_act_image (kinds 1, 2, 3; null: the table), no mask bytes, no pixmul
+int32_t fx_act_image_any_map(int mode, const float* x, const float* x2, const float* table, int masked, void* img, int N, int C, int HW, hipStream_t st,
+                             const FxFinalize* fin = nullptr);
 
 // The 7x7 stride-2 stem (Cin = 1..4) as a 4x4 stride-1 convolution over a space-to-depth image of the input (p3d_fx.hip)
 bool fx_stem_applies(int N, int Cin, int H, int W, int K);

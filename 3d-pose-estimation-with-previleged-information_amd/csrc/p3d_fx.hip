@@ -170,15 +170,18 @@ __device__ __forceinline__ FxConvParams fx_class_params(const FxConvParams& in) 
 // the result held.
 // Image-fed (AMODE 1, p3d_x3_any_images_enable), epilogue 0 only, either K order: the operand side is the AMODE 1 fetch as it is -- one pixel's 32-B row per thread, its
 // position from the flat column, so nothing there knows of four-pixel groups -- and the result side the staged store above.
+// Image-fed with epilogue 1 / 2 (tap-outer only; the ragged residual blocks of p3d_block_any_enable): the sums run in the register view, where a lane's four flat
+// pixels may lie in two images or end beyond NP -- an element enters a sum only below NP, and for sums 2 its ep_c is read at its own (image, pixel), by the walk of
+// the staged store.  red[][][] and partial[tile_n][M][2] as in the aligned instances: a fixed order, no atomics.  Never split along K (fx_conv_fwd / fx_conv_dgrad).
 // ROWS (image-fed, the dense block executor's launches): the activation operand is an fp32 row image [N][Cred/16][Hi][Wi][16] (fx_row_image); a thread fetches its half of a
 // pixel's 64-B row (two 16-B loads instead of three plane loads) and cuts it into the three pieces on the way from registers to LDS: same stores, same LDS image.
 template <int AMODE, int PRO, int EPIX, bool TAPI = false, bool RAG = false, bool ROWS = false>
 __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in) {
     static_assert(!TAPI || AMODE == 1, "the tap-inner K order is an image-fed instance");
     static_assert(!ROWS || (AMODE == 1 && !RAG), "row images feed the aligned image-fed instances");
-    static_assert(!RAG || (AMODE == 1 && PRO == 0 && EPIX == FX_EPI_STORE) ||
+    static_assert(!RAG || (AMODE == 1 && PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_STATS || EPIX == FX_EPI_BWD_SUMS)) ||
                       (AMODE == 0 && ((PRO == 0 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER)) || (PRO == 4 && (EPIX == FX_EPI_STORE || EPIX == FX_EPI_INFER_FACTOR || EPIX == FX_EPI_FACTOR)))),
-                  "the ragged instances are the fp32-fed forward with the plain / inference epilogue, dense or as a partial convolution, and the image-fed forward with the plain one");
+                  "the ragged instances are the fp32-fed forward with the plain / inference epilogue, dense or as a partial convolution, and the image-fed forward with the plain or a BatchNorm one");
     constexpr int SUMS = fx_epi_sums(EPIX);
     constexpr bool EM = fx_epi_factor(EPIX) && !RAG;          // (ragged: four pixels of the register view may lie in two images or end beyond the factor -- the staged store applies it)
     constexpr bool EM_RAG = RAG && EPIX == FX_EPI_FACTOR;
@@ -519,13 +522,27 @@ __global__ __launch_bounds__(256, 3) void fx_conv_kernel(const FxConvParams p_in
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[a][b][4 * g + e] = v[e];
-                if constexpr (SUMS == 1) {
+                if constexpr (RAG && SUMS != 0) {
+                    // the four flat pixels one by one: none beyond NP, each at its own (image, pixel) (launched unsplit only)
+                    int ne = n, re = rem;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e, ++re) {
+                        if (c4 + e >= p.NP) break;
+                        while (re >= OHW) { re -= OHW; ++ne; }
+                        if constexpr (SUMS == 1) { ssum[b] += v[e]; ssq[b] = fmaf(v[e], v[e], ssq[b]); }
+                        else {
+                            const float c2 = p.ep_c[((size_t)ne * p.M + m) * OHW + re];
+                            const float gg = fmaf(c2, esc[b], esh[b]) > 0.f ? v[e] : 0.f;
+                            ssum[b] += gg; ssq[b] = fmaf(gg, c2 - emean[b], ssq[b]);
+                        }
+                    }
+                } else if constexpr (SUMS == 1) {
                     if (!split) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { ssum[b] += v[e]; ssq[b] = fmaf(v[e], v[e], ssq[b]); }
                     }
                 }
-                if constexpr (SUMS == 2) {
+                if constexpr (SUMS == 2 && !RAG) {
                     if (!split) {
                         const f32x4 c2 = *reinterpret_cast<const f32x4*>(p.ep_c + ((size_t)n * p.M + m) * OHW + rem);
 #pragma unroll
@@ -1597,6 +1614,83 @@ __global__ __launch_bounds__(256, 3) void fx_wgrad_any_img_kernel(const FxWgradP
         }
 }
 
+// The prologue of fx_act_image_any_map_kernel<MODE 1 / 2>: the constants of the block's 16 channels (blockIdx.y) into cst -- the table's (fin.kind == 0) or those of the
+// fused finalize step (FxFinalize, p3d_fx.h), which block x == 0 also writes out.  Ends with a barrier.  Statement for statement the prologue of fx_act_image_kernel
+// below (same expressions, same summation order: the same constants from the same partials; tests/test_block_anysize_gpu.py compares the two passes byte for byte), which
+// keeps its copy inline: calling this function there changes the code of its four instances with a prologue, which every aligned step runs (tools/isa_diff.py).
+template <int MODE>
+__device__ __forceinline__ void fx_image_constants(const FxFinalize& fin, const float* __restrict__ tab, int C, float (&cst)[16][FX_TAB], double (&fred)[2][16][16]) {
+    const int cg = blockIdx.y, t = threadIdx.x;
+    if (fin.kind == 0) {
+        if (t < 16 * FX_TAB) cst[t >> 3][t & 7] = tab[(size_t)(cg * 16) * FX_TAB + t];
+    } else {
+        // fused finalize: thread (cl, rl) sums rows rl, rl + 16, ... of channel cl in fp64, lane 0 of each channel adds the 16 lanes in order
+        const int cl = t & 15, rl = t >> 4, c = cg * 16 + cl;
+        // (four rows per trip with independent loads: up to 32 dependent round trips otherwise, in the prologue of EVERY block of the pass)
+        double s1 = 0.0, s2 = 0.0, u1 = 0.0, u2 = 0.0, v1 = 0.0, v2 = 0.0, w1 = 0.0, w2 = 0.0;
+        int r = rl;
+        if (fin.kind == 3) {
+            const double* pd = (const double*)fin.partial + (size_t)c * fin.rows * 3;
+            const int o = 1 + fin.which;
+            for (; r + 48 < fin.rows; r += 64) {
+                const double a0 = pd[r * 3], b0 = pd[r * 3 + o], a1 = pd[(r + 16) * 3], b1 = pd[(r + 16) * 3 + o];
+                const double a2 = pd[(r + 32) * 3], b2 = pd[(r + 32) * 3 + o], a3 = pd[(r + 48) * 3], b3 = pd[(r + 48) * 3 + o];
+                s1 += a0; s2 += b0; u1 += a1; u2 += b1; v1 += a2; v2 += b2; w1 += a3; w2 += b3;
+            }
+            for (; r < fin.rows; r += 16) { s1 += pd[r * 3]; s2 += pd[r * 3 + o]; }
+        } else {
+            const float* pf = (const float*)fin.partial + (size_t)c * 2;
+            const size_t row = (size_t)C * 2;
+            for (; r + 48 < fin.rows; r += 64) {
+                const f32x2 a0 = *reinterpret_cast<const f32x2*>(pf + r * row), a1 = *reinterpret_cast<const f32x2*>(pf + (r + 16) * row);
+                const f32x2 a2 = *reinterpret_cast<const f32x2*>(pf + (r + 32) * row), a3 = *reinterpret_cast<const f32x2*>(pf + (r + 48) * row);
+                s1 += a0[0]; s2 += a0[1]; u1 += a1[0]; u2 += a1[1]; v1 += a2[0]; v2 += a2[1]; w1 += a3[0]; w2 += a3[1];
+            }
+            for (; r < fin.rows; r += 16) { const f32x2 v = *reinterpret_cast<const f32x2*>(pf + r * row); s1 += v[0]; s2 += v[1]; }
+        }
+        s1 = (s1 + u1) + (v1 + w1);
+        s2 = (s2 + u2) + (v2 + w2);
+        fred[0][rl][cl] = s1; fred[1][rl][cl] = s2;
+        __syncthreads();
+        if (rl == 0) {
+            s1 = s2 = 0.0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { s1 += fred[0][i][cl]; s2 += fred[1][i][cl]; }
+            const bool owner = blockIdx.x == 0;
+            if constexpr (MODE == 1) {          // as bn_finalize_fwd_kernel (p3d_block.hip)
+                const double mean = s1 / fin.count;
+                double var = s2 / fin.count - mean * mean;
+                if (var < 0.0) var = 0.0;
+                const float invstd = (float)(1.0 / sqrt(var + (double)fin.eps));
+                const float fmean = (float)mean;
+                const float sc = invstd * fin.gamma[c], sh = __fmaf_rn(-fmean, sc, fin.beta[c]);
+                cst[cl][0] = sc; cst[cl][1] = sh;
+                if (owner) {
+                    float* tt = fin.table + (size_t)c * FX_TAB;
+                    tt[0] = sc; tt[1] = sh; tt[2] = fmean; tt[3] = invstd;
+                    if (fin.running_mean) {
+                        const double unbiased = fin.count > 1.0 ? var * fin.count / (fin.count - 1.0) : var;
+                        fin.running_mean[c] = (float)((1.0 - fin.momentum) * fin.running_mean[c] + fin.momentum * mean);
+                        fin.running_var[c] = (float)((1.0 - fin.momentum) * fin.running_var[c] + fin.momentum * unbiased);
+                    }
+                }
+            } else {                             // as bn_finalize_bwd_kernel
+                const float* tt = fin.table + (size_t)c * FX_TAB;
+                const float sc = tt[0], sh = tt[1], mean = tt[2], is = tt[3];
+                const double dg = (double)is * s2;
+                if (owner) {
+                    fin.dbeta[c] = fin.accumulate ? fin.dbeta[c] + (float)s1 : (float)s1;
+                    fin.dgamma[c] = fin.accumulate ? fin.dgamma[c] + (float)dg : (float)dg;
+                }
+                const float m1 = (float)(s1 / fin.count), m2 = (float)(dg / fin.count);
+                const float A = fin.gamma[c] * is;
+                cst[cl][0] = sc; cst[cl][1] = sh; cst[cl][4] = A; cst[cl][5] = -A * is * m2; cst[cl][6] = A * (mean * is * m2 - m1);
+            }
+        }
+    }
+    __syncthreads();
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // Activation images: fp32 NCHW [N][C][HW] -> three bf16 planes [N][C/16][HW][16], optionally through the BatchNorm + ReLU of the forward pass (MODE 1) or
 // the BatchNorm-backward map (MODE 2) of the layer the tensor belongs to (depthnet.py:98-116: out = relu(bn(conv(x))) and its autograd).
@@ -1963,6 +2057,85 @@ int32_t fx_act_image_any(const float* x, void* img, int N, int C, int HW, hipStr
     return check_launch("fx_act_image_any");
 }
 
+// Modes 1 and 2 at any HW (the residual blocks at any map width): the thread / group / row-access scheme of fx_act_image_any_kernel, the constants from
+// fx_image_constants (table or fused finalize, the expressions and summation order of fx_act_image_kernel: the same constants from the same partials) and the maps of
+// fx_act_image_kernel<1 / 2> element by element.  Plane images only; no mask bytes (a channel row of odd length shares its last mask byte with the next row's first) and no
+// per-pixel factor.  A pixel beyond its image's HW is neither read nor written.
+template <int MODE>
+__global__ __launch_bounds__(256) void fx_act_image_any_map_kernel(const float* __restrict__ X, const float* __restrict__ X2, const float* __restrict__ tab,
+                                                                   unsigned char* __restrict__ img, size_t plane_bytes, int N, int C, int HW, int masked, const FxFinalize fin) {
+    static_assert(MODE == 1 || MODE == 2, "mode 0 is fx_act_image_any_kernel");
+    __shared__ float cst[16][FX_TAB];
+    __shared__ double fred[2][16][16];
+    const int cg = blockIdx.y, t = threadIdx.x, ih = t & 1;
+    fx_image_constants<MODE>(fin, tab, C, cst, fred);
+    const int q4 = (HW + 3) >> 2;
+    const long long quad = ((long long)blockIdx.x * 256 + t) >> 1;
+    if (quad >= (long long)N * q4) return;
+    const int n = (int)(quad / q4), pq = (int)(quad - (long long)n * q4);
+    const int left = HW - 4 * pq;                  // pixels of this group: 4, or 1 .. 3 in the last group of an image
+    const size_t in0 = ((size_t)n * C + cg * 16 + 8 * ih) * HW + 4 * pq;
+    f32x4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float* src = X + in0 + (size_t)j * HW;
+        const float* src2 = MODE == 2 ? X2 + in0 + (size_t)j * HW : nullptr;
+        f32x4 c2 = {0.f, 0.f, 0.f, 0.f};
+        if (left >= 4 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(src2)) & 15) == 0) {
+            v[j] = *reinterpret_cast<const f32x4*>(src);
+            if constexpr (MODE == 2) c2 = *reinterpret_cast<const f32x4*>(src2);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[j][e] = e < left ? src[e] : 0.f;
+                if constexpr (MODE == 2) c2[e] = e < left ? src2[e] : 0.f;
+            }
+        }
+        const float sc = cst[8 * ih + j][0], sh = cst[8 * ih + j][1];
+        if constexpr (MODE == 1) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[j][e] = fmaxf(fmaf(v[j][e], sc, sh), 0.f);
+        } else {
+            const float A = cst[8 * ih + j][4], B = cst[8 * ih + j][5], K = cst[8 * ih + j][6];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float gg = (!masked || fmaf(c2[e], sc, sh) > 0.f) ? v[j][e] : 0.f;
+                v[j][e] = fmaf(A, gg, fmaf(B, c2[e], K));
+            }
+        }
+    }
+    unsigned char* dst = img + (((size_t)n * (C >> 4) + cg) * HW + 4 * pq) * 32 + 16 * ih;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (e >= left) continue;
+        unsigned hp[4], mp[4], lp[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) fx_split2(v[2 * jj][e], v[2 * jj + 1][e], hp[jj], mp[jj], lp[jj]);
+        *reinterpret_cast<i32x4*>(dst + 32 * e) = i32x4{(int)hp[0], (int)hp[1], (int)hp[2], (int)hp[3]};
+        *reinterpret_cast<i32x4*>(dst + plane_bytes + 32 * e) = i32x4{(int)mp[0], (int)mp[1], (int)mp[2], (int)mp[3]};
+        *reinterpret_cast<i32x4*>(dst + 2 * plane_bytes + 32 * e) = i32x4{(int)lp[0], (int)lp[1], (int)lp[2], (int)lp[3]};
+    }
+}
+
+int32_t fx_act_image_any_map(int mode, const float* x, const float* x2, const float* table, int masked, void* img, int N, int C, int HW, hipStream_t st, const FxFinalize* fin) {
+    if (!x || !img || N <= 0 || C <= 0 || (C & 15) || HW <= 0 || (mode != 1 && mode != 2) || (!table && !fin) || (mode == 2 && !x2) ||
+        (reinterpret_cast<uintptr_t>(img) & 15) || (reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(x2) & 3) || (int64_t)N * C * HW >= (1ll << 31)) {
+        set_error("fx_act_image_any_map: bad argument (N=%d C=%d HW=%d mode=%d; modes 1 and 2, C %% 16 == 0 and a 16-B aligned image are required)", N, C, HW, mode); return P3D_EINVAL;
+    }
+    FxFinalize f{};
+    if (fin) {
+        f = *fin;
+        if (!((f.kind == 1 && mode == 1 && f.beta) || ((f.kind == 2 || f.kind == 3) && mode == 2 && f.dgamma && f.dbeta)) || !f.partial || f.rows <= 0 || !f.gamma || !f.table || f.gmask) {
+            set_error("fx_act_image_any_map: inconsistent fused-finalize request (kind %d, mode %d; no mask bytes at any HW)", f.kind, mode); return P3D_EINVAL;
+        }
+    }
+    const size_t plane = (size_t)N * C * HW * 2;
+    const dim3 grid((unsigned)ceil_div((int64_t)N * ((HW + 3) >> 2) * 2, 256), (unsigned)(C >> 4));
+    if (mode == 1) hipLaunchKernelGGL(fx_act_image_any_map_kernel<1>, grid, dim3(256), 0, st, x, x2, table, (unsigned char*)img, plane, N, C, HW, masked, f);
+    else hipLaunchKernelGGL(fx_act_image_any_map_kernel<2>, grid, dim3(256), 0, st, x, x2, table, (unsigned char*)img, plane, N, C, HW, masked, f);
+    return check_launch("fx_act_image_any_map");
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -2112,6 +2285,10 @@ constexpr FxSelect fx_select(bool dgrad, bool img, bool masked, bool sums, bool 
     X(1, 0, FX_EPI_STORE, false, true, false) X(1, 0, FX_EPI_STORE, true, true, false)                                                                      \
     X(1, 0, FX_EPI_STORE, false, false, true) X(1, 0, FX_EPI_STATS, false, false, true) X(1, 0, FX_EPI_BWD_SUMS, false, false, true)                        \
     X(1, 0, FX_EPI_STORE, true, false, true) X(1, 0, FX_EPI_STATS, true, false, true) X(1, 0, FX_EPI_BWD_SUMS, true, false, true)
+// The ragged image-fed instances with the BatchNorm epilogues (the residual blocks at any map width, p3d_block_any_enable), X as above.  A list of their own: reported by
+// p3d_fx_conv_any_sums_instances, NOT by p3d_fx_conv_instances, and each run alone by tests/test_block_anysize_gpu.py (tests/test_block_anysize_host.py fails
+// when a new entry here has no case there).  Tap-outer only: no 3x3 inside a block of the reference's networks has 1024 channels.
+#define P3D_FX_CONV_ANY_SUMS_INSTANCES(X) X(1, 0, FX_EPI_STATS, false, true, false) X(1, 0, FX_EPI_BWD_SUMS, false, true, false)
 #define P3D_FX16_CONV_INSTANCES(X)                                                                                             \
     X(96, FX_EPI_STORE, false, false) X(96, FX_EPI_STATS, false, false) X(96, FX_EPI_BWD_SUMS, false, false) X(96, FX_EPI_INFER, false, false)             \
     X(64, FX_EPI_STORE, false, false) X(64, FX_EPI_STATS, false, false) X(64, FX_EPI_BWD_SUMS, false, false) X(64, FX_EPI_INFER, false, false)             \
@@ -2126,6 +2303,7 @@ constexpr FxKernel fx_instance(int bm, bool img, int pro, int epi, bool tapi, bo
     const int am = img ? 1 : 0, e = bm && !tapi ? fx16_epi(epi) : epi;
 #define P3D_X(AM, PRO, EPI, TAPI, RAG, ROWS) if (bm == 0 && am == AM && pro == PRO && e == EPI && tapi == TAPI && rag == RAG && rows == ROWS) return fx_conv_kernel<AM, PRO, EPI, TAPI, RAG, ROWS>;
     P3D_FX_CONV_INSTANCES(P3D_X)
+    P3D_FX_CONV_ANY_SUMS_INSTANCES(P3D_X)
 #undef P3D_X
 #define P3D_X(BM, EPI, TAPI, ROWS) if (bm == BM && am == 1 && pro == 0 && e == EPI && tapi == TAPI && !rag && rows == ROWS) return fx16_conv_kernel<BM, EPI, TAPI, ROWS>;
     P3D_FX16_CONV_INSTANCES(P3D_X)
@@ -2153,7 +2331,9 @@ constexpr bool fx_select_covered() {
            fx_instance(0, false, fx_select(false, false, true, false, false).pro, fx_select(false, false, true, false, false).epi, false, true) &&      //  training: the partial
            fx_instance(0, false, fx_select(true, false, true, false, false).pro, fx_select(true, false, true, false, false).epi, false, true) &&        //  convolution's two passes;
            fx_instance(0, true, fx_select(false, true, false, false, false).pro, fx_select(false, true, false, false, false).epi, false, true) &&       //  the image-fed dense one,
-           fx_instance(0, true, fx_select(true, true, false, false, false).pro, fx_select(true, true, false, false, false).epi, true, true);            //  either K order)
+           fx_instance(0, true, fx_select(true, true, false, false, false).pro, fx_select(true, true, false, false, false).epi, true, true) &&          //  either K order;
+           fx_instance(0, true, fx_select(false, true, false, true, false).pro, fx_select(false, true, false, true, false).epi, false, true) &&         //  and with the BatchNorm
+           fx_instance(0, true, fx_select(true, true, false, true, false).pro, fx_select(true, true, false, true, false).epi, false, true);             //  epilogues, tap-outer)
 }
 static_assert(fx_select_covered(), "fx_select returns a code without a compiled instance");
 void fx_tune(int what, int value) {
@@ -2184,14 +2364,15 @@ size_t fx_weight_image_bytes(int K, int C, int RS, bool bwd) {
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // dgrad: rows = input channels, reduction = output channels, pixels = the input map; only stride 1 splits (a strided one writes its parity classes in place).
-// ragged (the forward at any map width): each slab starts on a 16-B line.
-static FxPlan fx_plan(const p3d_conv_desc* d, bool dgrad, bool ragged = false) {
+// ragged (the forward at any map width): each slab starts on a 16-B line.  ragged_sums: a ragged launch that takes BatchNorm sums is never split (the pass that sums
+// ragged slabs takes none), so its partial rows are always the pixel tiles.
+static FxPlan fx_plan(const p3d_conv_desc* d, bool dgrad, bool ragged = false, bool ragged_sums = false) {
     const int rows = dgrad ? d->C : d->K, red = dgrad ? d->K : d->C, RS = d->R * d->S, nk = RS * (red / FX_BK);
     const int64_t pixels = dgrad ? (int64_t)d->N * d->H * d->W : (int64_t)d->N * d->Ho * d->Wo;
     FxPlan s{1};
     s.tiles_n = (int)ceil_div(dgrad && d->stride > 1 ? (int64_t)d->N * (d->H / d->stride) * (d->W / d->stride) : pixels, FX_BN);
     const int64_t tiles = ceil_div(rows, FX_BM) * s.tiles_n;
-    const bool may_split = !dgrad || d->stride == 1;
+    const bool may_split = (!dgrad || d->stride == 1) && !ragged_sums;
     int64_t want = 1;
     if (may_split && g_force_conv_splits > 0) want = g_force_conv_splits < nk ? g_force_conv_splits : nk;
     else if (may_split && tiles <= 400 && nk >= 64) {
@@ -2224,7 +2405,7 @@ size_t fx_workspace(FxPass pass, const p3d_conv_desc* d, bool ragged) {
     const size_t b = fx_wgrad_plan(d, o).slab_bytes;
     return a > b ? a : b;
 }
-int fx_partial_rows(FxPass pass, const p3d_conv_desc* d) { return fx_plan(d, pass == FX_DGRAD).partial_rows; }
+int fx_partial_rows(FxPass pass, const p3d_conv_desc* d, bool ragged) { return fx_plan(d, pass == FX_DGRAD, ragged, ragged).partial_rows; }
 
 // Pre-split weight images of one conv weight w [K][C][R*S] (fp32): blockIdx.y = 0 the forward image (rows = output channels, reduction = input channels),
 // 1 the data-gradient image (rows = input channels, reduction = output channels); a null image pointer skips that direction.  One thread per 16-B chunk
@@ -2425,15 +2606,24 @@ int32_t fx_launch_log(int32_t* out, int32_t max_records, int32_t reset) {
     if (reset) g_fx_log_n = 0;
     return n;
 }
+// (the ragged image-fed BatchNorm instances are not in this list: fx_conv_any_sums_instances)
+static void fx_put_instance(int32_t* out, int32_t max_records, int32_t& n, int kernel, int am, int pro, int epi, bool tapi, bool rag, bool rows) {
+    if (out && n < max_records) {
+        const int32_t rec[P3D_FX_INSTANCE_FIELDS] = {kernel, am, pro, epi, tapi ? 1 : 0, rag ? 1 : 0, rows ? 1 : 0};
+        for (int f = 0; f < P3D_FX_INSTANCE_FIELDS; ++f) out[n * P3D_FX_INSTANCE_FIELDS + f] = rec[f];
+    }
+    ++n;
+}
+int32_t fx_conv_any_sums_instances(int32_t* out, int32_t max_records) {
+    int32_t n = 0;
+#define P3D_X(AM, PRO, EPI, TAPI, RAG, ROWS) fx_put_instance(out, max_records, n, 0, AM, PRO, EPI, TAPI, RAG, ROWS);
+    P3D_FX_CONV_ANY_SUMS_INSTANCES(P3D_X)
+#undef P3D_X
+    return n;
+}
 int32_t fx_conv_instances(int32_t* out, int32_t max_records) {
     int32_t n = 0;
-    auto put = [&](int kernel, int am, int pro, int epi, bool tapi, bool rag, bool rows) {
-        if (out && n < max_records) {
-            const int32_t rec[P3D_FX_INSTANCE_FIELDS] = {kernel, am, pro, epi, tapi ? 1 : 0, rag ? 1 : 0, rows ? 1 : 0};
-            for (int f = 0; f < P3D_FX_INSTANCE_FIELDS; ++f) out[n * P3D_FX_INSTANCE_FIELDS + f] = rec[f];
-        }
-        ++n;
-    };
+    auto put = [&](int kernel, int am, int pro, int epi, bool tapi, bool rag, bool rows) { fx_put_instance(out, max_records, n, kernel, am, pro, epi, tapi, rag, rows); };
 #define P3D_X(AM, PRO, EPI, TAPI, RAG, ROWS) put(0, AM, PRO, EPI, TAPI, RAG, ROWS);
     P3D_FX_CONV_INSTANCES(P3D_X)
 #undef P3D_X
@@ -2518,8 +2708,10 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
                 "fx_conv_fwd: the inference epilogue takes a cached folded weight image, no other fusion, and a partial convolution only from an fp32 operand");
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
     P3D_REQUIRE(!(rag && img) || (!infer && !masked), "fx_conv_fwd: the ragged forward takes an image operand only as the dense training launch");
-    P3D_REQUIRE(!(rag && !infer) || !fuse->partial, "fx_conv_fwd: the ragged training forward takes no statistics");
-    const FxPlan pl = fx_plan(d, false, rag);
+    const bool rag_sums = rag && fuse->partial;     // FX_EPI_STATS on the ragged image-fed instance (the residual blocks at any map width): one unsplit launch
+    P3D_REQUIRE(!rag_sums || (img && !infer && !masked && d->stride == 1),
+                "fx_conv_fwd: the ragged training forward takes statistics only as the dense image-fed stride-1 launch");
+    const FxPlan pl = fx_plan(d, false, rag, rag_sums);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     FxConvParams p{};
     p.X = x; p.Y = y; p.bias = bias;
@@ -2563,9 +2755,10 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
     const bool rows = fuse && fuse->rows;           // act_img is an fp32 row image
     P3D_REQUIRE(!rows || (img && !masked && !(fuse && fuse->ragged)), "fx_conv_dgrad: a row image feeds the dense aligned launches only");
     const bool rag = fuse && fuse->ragged;          // the ragged forward instances over dy (p3d_x3_any_enable; masked: p3d_x3_any_partial_enable): any map width, stride 1, fp32-fed
-    P3D_REQUIRE(!rag || (d->stride == 1 && !(img && masked) && !fuse->partial && !fuse->acc_src),
-                "fx_conv_dgrad: the ragged data gradient is the stride-1 one, dense (fp32- or image-fed) or masked (fp32-fed), without sums");
-    const FxPlan pl = fx_plan(d, true, rag);
+    const bool rag_sums = rag && fuse->partial;     // FX_EPI_BWD_SUMS on the ragged image-fed instance (the residual blocks at any map width): one unsplit launch
+    P3D_REQUIRE(!rag || (d->stride == 1 && !(img && masked) && (!rag_sums || (img && !masked)) && !fuse->acc_src),
+                "fx_conv_dgrad: the ragged data gradient is the stride-1 one, dense (fp32- or image-fed) or masked (fp32-fed), with sums only as the dense image-fed launch");
+    const FxPlan pl = fx_plan(d, true, rag, rag_sums);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_dgrad: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     if (fuse && fuse->acc_src && !(d->accumulate && fx_dgrad_accumulates_from_source(d))) {
         set_error("fx_conv_dgrad: an accumulation source needs accumulate = 1, stride 1 and an unsplit launch"); return P3D_EINVAL;

@@ -989,6 +989,15 @@ def x3_any_images_enabled():
     return bool(on)
 
 
+def block_any(on):
+    """Opt-in, OFF by default (P3D_BLOCK_ANY=1 turns it on), independent of every other switch: the residual-block executor (ops_block.residual_block) also takes
+    dense blocks whose convolutions all have stride 1 at map sizes the aligned kernels refuse -- the 65 / 33 / 17 maps of the default 257 crop: 14 of ResNet-50's
+    16 blocks at -stride 16 -- on the ragged image-fed instances, instead of leaving them to the per-layer path.  Returns the previous setting."""
+    global X3_EPOCH
+    X3_EPOCH += 1                       # (ops_block caches per-block plans that depend on it)
+    return bool(lib().p3d_block_any_enable(int(bool(on))))
+
+
 FROZEN_FOLD = os.environ.get('P3D_FROZEN_FOLD', '0') == '1'
 
 
@@ -1181,6 +1190,14 @@ def fx_conv_instances():
     n = lib().p3d_fx_conv_instances(None, 0)
     out = (ctypes.c_int32 * (FX_INSTANCE_LEN * n))()
     assert lib().p3d_fx_conv_instances(out, n) == n
+    return [tuple(int(out[i * FX_INSTANCE_LEN + j]) for j in range(FX_INSTANCE_LEN)) for i in range(n)]
+
+
+def fx_conv_any_sums_instances():
+    """The instances fx_conv_instances leaves out (p3d_fx_conv_any_sums_instances), in the same form: the ragged image-fed ones with the BatchNorm epilogues."""
+    n = lib().p3d_fx_conv_any_sums_instances(None, 0)
+    out = (ctypes.c_int32 * (FX_INSTANCE_LEN * n))()
+    assert lib().p3d_fx_conv_any_sums_instances(out, n) == n
     return [tuple(int(out[i * FX_INSTANCE_LEN + j]) for j in range(FX_INSTANCE_LEN)) for i in range(n)]
 
 

@@ -3,7 +3,8 @@ through p3d_block_fwd / p3d_block_bwd (csrc/p3d_block.hip): the BatchNorm layers
 and the host makes one C call per block and direction instead of a dozen per-layer autograd nodes.
 
 Used by _trunk._ResidualBlock.forward for dense fp32 blocks whose BatchNorm layers are in training mode; everything else (partial convolutions,
--half_acc, frozen / evaluation BatchNorm, shapes the fused kernels do not take) stays on the per-layer path of ops.py.
+-half_acc, frozen / evaluation BatchNorm, shapes the fused kernels do not take) stays on the per-layer path of ops.py.  Under ops.block_any(True) the executor also
+takes stride-1 dense blocks at map sizes outside the aligned kernels ("ragged" blocks: _Plan.ragged); all that changes here is the buffers such a block owns.
 """
 import ctypes
 import os
@@ -60,6 +61,8 @@ class _Plan:
         self.ok = bool(lib().p3d_block_supported(ctypes.byref(d))) and (block.downsample is not None or not block.skip_relu)
         if self.ok and block.downsample is not None and self.shapes[3] != shape:
             self.ok = False
+        # a block the executor takes only under ops.block_any (a map size outside the aligned kernels): plane images, no mask bytes, and an image of the input x
+        self.ragged = self.ok and bool(lib().p3d_block_any_supported(ctypes.byref(d)))
         self.main_bytes = self.side_bytes = 0
         if self.ok:
             m, s = ctypes.c_size_t(), ctypes.c_size_t()
@@ -69,6 +72,7 @@ class _Plan:
         # bytes of the image of a tensor shaped like c_slot (a_slot, d c_slot): fp32 rows, 4 B per element, for a dense block; three bf16 planes, 6 B, for a masked one
         self.image_bytes = {slot: lib().p3d_block_image_bytes(ctypes.byref(d), self.shapes[slot][0], self.shapes[slot][1], self.shapes[slot][2] * self.shapes[slot][3])
                             for slot in self.slots}
+        self.x_image_bytes = lib().p3d_block_image_bytes(ctypes.byref(d), x_shape[0], x_shape[1], x_shape[2] * x_shape[3]) if self.ragged else 0
         # one table for the block's BatchNorm layers, [K_slot][8] floats each, in slot order
         self.table_offset, self.table_rows = {}, 0
         for slot in self.slots:
@@ -125,7 +129,9 @@ class _Buffers(_BufferSet):
         self.act = {slot: torch.empty(plan.image_bytes[slot], dtype=torch.uint8, device=device) for slot in plan.slots if slot < plan.desc.nconv - 1}
         # which outputs the closing ReLU let through: one byte per four elements, all the backward pass needs of `out`
         n_out = plan.out_shape[0] * plan.out_shape[1] * plan.out_shape[2] * plan.out_shape[3]
-        self.mask = torch.empty(n_out // 4, dtype=torch.uint8, device=device) if (plan.desc.relu_out and USE_OUT_MASK) else None
+        self.mask = torch.empty(n_out // 4, dtype=torch.uint8, device=device) if (plan.desc.relu_out and USE_OUT_MASK and not plan.ragged) else None
+        # a ragged block: the plane image of the block input, written by forward, read by the weight gradients of conv 0 and the downsample conv (p3d_block_io.aimg[3])
+        self.x_img = torch.empty(plan.x_image_bytes, dtype=torch.uint8, device=device) if plan.ragged else None
         # the block's output (= the next block's input) and its gradient stay with the caching allocator; a little slack per distinct shape keeps the few
         # `record_stream`ed tensors that remain (the block input) from ever forcing a hipMalloc in steady state
         key = (plan.out_shape, str(device))
@@ -363,6 +369,8 @@ def _fill_io(io, plan, bufs, layers, images_index):
         io.gamma[slot], io.beta[slot] = bn.weight.data_ptr(), bn.bias.data_ptr()
     if bufs.mask is not None:
         io.out_mask = bufs.mask.data_ptr()
+    if bufs.x_img is not None:
+        io.aimg[3] = bufs.x_img.data_ptr()
 
 
 class ResidualBlockFn(torch.autograd.Function):

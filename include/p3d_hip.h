@@ -228,7 +228,10 @@ typedef struct p3d_block_io {
     const void* wimgT[4];       /*   the fp32 weights on the fly.  The caller rebuilds an image whenever its weight changes. */
     float* c[4];
     void* aimg[4];              /* activation image (p3d_block_image_bytes(b, N, K_i, Ho_i * Wo_i) bytes: an fp32 row image in a dense block, three bf16 planes in a masked one) of a[i] = relu(bn_i(c[i])), i < nconv-1: written by
-                                   forward; read by conv i+1 in forward and by its weight gradient in backward.  a[i] itself never exists as fp32. */
+                                   forward; read by conv i+1 in forward and by its weight gradient in backward.  a[i] itself never exists as fp32.
+                                   aimg[3]: read by nothing in an aligned block.  In a RAGGED block (p3d_block_any_enable) it carries the plane image of the block input x
+                                   (p3d_block_image_bytes(b, N, C_in, H * W) bytes): written once by p3d_block_fwd, which feeds conv 0 and the downsample conv from it, and read by
+                                   their weight gradients in p3d_block_bwd -- the caller keeps it between the two calls. */
     float* table[4];
     const float* gamma[4];
     const float* beta[4];
@@ -256,6 +259,15 @@ typedef struct p3d_block_io {
 /* 1 when every convolution of the block can run on the fused kernels (dense, channel counts in steps of 16 and >= 64, four-pixel-aligned rows, maps of a
  * multiple of 16 pixels, stride <= 2 and never on a 1x1 of the main chain) */
 int32_t p3d_block_supported(const p3d_block_desc* b);
+/* The executor at any map width (default OFF; P3D_BLOCK_ANY=1 in the environment turns it on; independent of every p3d_x3_any_* switch).  Returns the previous setting.
+ * While it is on, p3d_block_supported / p3d_block_* also take a RAGGED block: a dense block (masked == 0) that is refused only for its map size (H * W or Ho * Wo no multiple
+ * of 4, rows of no multiple of 4 pixels: the 129 / 65 / 33 / 17 maps of the default 257 crop), every convolution of which, downsample included, has stride 1, whole weights,
+ * channel counts in steps of 16 and >= 64 and a map of >= 16 pixels.  Aligned blocks run exactly what they run with the switch off; strided blocks and masked blocks at such
+ * maps stay refused.  For a ragged block: every image is three bf16 planes (p3d_block_image_bytes: 6 B per element), io->aimg[3] holds the image of x (see there),
+ * io->out_mask is not used (backward reads `out`), io->gbuf is required whenever relu_out, and the convolutions run on the ragged image-fed instances of the x3 kernels,
+ * the BatchNorm sums in their epilogues (p3d_fx_conv_any_sums_instances), never split along K.  DESIGN.md section 3, "Residual blocks at any map width". */
+int32_t p3d_block_any_enable(int32_t on);
+int32_t p3d_block_any_supported(const p3d_block_desc* b);       /* 1: p3d_block_supported admits b, as a ragged block (host-only; 0 while the switch is off and for every aligned block) */
 int32_t p3d_block_workspace_bytes(const p3d_block_desc* b, size_t* main_bytes, size_t* side_bytes);
 int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* workspace, size_t workspace_bytes, void* stream);
 /* side_stream: NULL, or a second stream for the weight-gradient kernels (ordered by events inside the call; the caller joins the streams before it reads dw) */
@@ -316,7 +328,7 @@ int32_t p3d_fx_act_image(int32_t mode, const float* x, const float* x2, const fl
  * p3d_fx_conv_*_rows: p3d_fx_conv_*_img on row images (x_rows / dy_rows from p3d_fx_row_image); dense convolutions that p3d_fx_conv_img_supported admits, same
  * workspace (p3d_fx_conv_img_workspace_bytes).
  * p3d_block_image_bytes: bytes of one p3d_block_io.aimg / dcimg buffer of N x C x HW elements for this block: 4 per element for a dense block, 6 for a masked one
- * (and for every block under p3d_fx_tune(6, 1)). */
+ * (and for every block under p3d_fx_tune(6, 1), and for a ragged block: p3d_block_any_enable). */
 size_t p3d_fx_row_image_bytes(int32_t N, int32_t C, int32_t HW);
 int32_t p3d_fx_row_image(int32_t mode, const float* x, const float* x2, const float* table, int32_t masked, void* img, int32_t N, int32_t C, int32_t HW, void* stream);
 int32_t p3d_fx_conv_fwd_rows(const p3d_conv_desc* d, const void* x_rows, const float* w, const void* wimg, const float* bias, float* y, void* workspace,
@@ -379,15 +391,21 @@ int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, co
  * many launches there were since then -- more than max_records, or than 256, shows as a count above what was copied.  reset != 0: the log starts anew afterwards.
  * out may be NULL with max_records 0.
  * p3d_fx_conv_instances: every compiled instance of the two kernels as P3D_FX_INSTANCE_FIELDS int32 each -- fields [0..6] of a record --, generated from the lists
- * the instances are compiled from; returns their number (copies at most max_records). */
+ * the instances are compiled from; returns their number (copies at most max_records).  Two instances are NOT in it: the ragged image-fed ones with the BatchNorm
+ * epilogues, which have a list and a hook of their own (p3d_fx_conv_any_sums_instances, below). */
 #define P3D_FX_LAUNCH_FIELDS 16
 #define P3D_FX_INSTANCE_FIELDS 7
 int32_t p3d_fx_launch_log(int32_t* out, int32_t max_records, int32_t reset);
 int32_t p3d_fx_conv_instances(int32_t* out, int32_t max_records);
+/* The instances p3d_fx_conv_instances leaves out, in the same record shape: the ragged image-fed fx_conv_kernel<1, 0, 1 | 2, false, true, false> with the BatchNorm
+ * epilogues, which the ragged residual blocks launch (p3d_block_any_enable).  A list of their own in csrc/p3d_fx.hip; p3d_fx_launch_log records their launches like any
+ * other ([3] 1 / 2, [5] 1).  tests/test_block_anysize_gpu.py runs each alone. */
+int32_t p3d_fx_conv_any_sums_instances(int32_t* out, int32_t max_records);
 /* TEST HOOK (tests/test_fx_instances_gpu.py; nothing in the package calls it): one forward (pass 0) or data-gradient (pass 1) call of the x3 kernels with any of the
  * fusions the block executor and the inference entries use, so that each can be checked alone.  src: x (forward) / dy (data gradient), fp32, ignored when f->act_img is
  * set; out: y / dx.  The fields of p3d_fx_fuse, NULL / 0 = not used:
- *   act_img  the operand as a p3d_fx_act_image image (rows = 1: a p3d_fx_row_image one; ragged = 1: p3d_fx_act_image_any)
+ *   act_img  the operand as a p3d_fx_act_image image (rows = 1: a p3d_fx_row_image one; ragged = 1: p3d_fx_act_image_any -- with `partial` the ragged BatchNorm
+ *            instances of p3d_fx_conv_any_sums_instances: dense, stride 1, one unsplit launch, rows from p3d_fx_conv_fused_partial_rows_any)
  *   wimg     the p3d_fx_weight_images image of w for this pass, or NULL: built into the workspace
  *   partial  [p3d_fx_conv_fused_partial_rows][M][2] partial sums per result channel: forward (sum y, sum y^2); data gradient (sum g, sum g (ep_c - mean)) with
  *            g = dx * [ep_c * sc + sh > 0], ep_c laid out like dx and ep_tab [M][8] = {sc, sh, mean, ...}.  The summed value is the convolution (+ bias) (* emask);
@@ -414,8 +432,22 @@ typedef struct p3d_fx_fuse {
 } p3d_fx_fuse;
 size_t p3d_fx_conv_fused_workspace_bytes(int32_t pass, const p3d_conv_desc* d, int32_t ragged);
 int32_t p3d_fx_conv_fused_partial_rows(int32_t pass, const p3d_conv_desc* d);
+/* ... of a call with ragged = 1, an act_img and `partial` (dense, stride 1): such a call is ONE unsplit launch whatever the plan of the plain call, so its rows are the
+ * 128-pixel tiles of the result.  0 as above. */
+int32_t p3d_fx_conv_fused_partial_rows_any(int32_t pass, const p3d_conv_desc* d);
 int32_t p3d_fx_conv_fused(int32_t pass, const p3d_conv_desc* d, const p3d_fx_fuse* f, const float* src, const float* w, const float* bias, float* out, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* TEST HOOK (tests/test_block_anysize_gpu.py; nothing in the package calls it): one image pass of mode 1 or 2 with the finalize step of its BatchNorm layer in the prologue, as
+ * the block executor runs it.  any = 0: the aligned pass (p3d_fx_act_image's kernel; HW % 4 == 0); any = 1: the pass at any HW the ragged blocks use (plane images, C % 16 == 0,
+ * img 16-B aligned).  Modes, x, x2, table, masked as p3d_fx_act_image.  kind 0: the constants come from `table` and the arguments behind `kind` are ignored.  Otherwise they are computed from partial sums,
+ * every block in the same fixed order, and block x == 0 writes them out:
+ *   kind 1 (mode 1)  partial = float [rows][C][2] (sum y, sum y^2): table {sc, sh, mean, invstd} and, if given, the running statistics (momentum, eps, unbiased variance)
+ *   kind 2 (mode 2)  partial = float [rows][C][2] (sum g, sum g (c - mean)); table holds {sc, sh, mean, invstd}: d gamma, d beta written (added with `accumulate`)
+ *   kind 3 (mode 2)  the same from double [C][rows][3], the second sum at index 1 + which
+ * count = N * H * W of the layer. */
+int32_t p3d_fx_act_image_fused(int32_t any, int32_t mode, const float* x, const float* x2, float* table, int32_t masked, void* img, int32_t N, int32_t C, int32_t HW,
+                               int32_t kind, const void* partial, int32_t rows, int32_t which, double count, const float* gamma, const float* beta, float* running_mean,
+                               float* running_var, float momentum, float eps, float* dgamma, float* dbeta, int32_t accumulate, void* stream);
 /* TEST HOOK (tests/test_wgrad_plan_host.py; nothing in the package calls it), host-only: how the x3 kernels would run the weight gradient of d -- the plan every
  * weight-gradient entry, the block executor and the workspace queries read -- under the p3d_fx_tune settings in force.  Nothing is launched and no operand exists;
  * `operands` says what they would be:

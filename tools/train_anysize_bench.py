@@ -29,6 +29,11 @@
               the three nodes with the switch off and on against the fused tail, and the fused tail at 128^2.  With --step: legs `any` (ops.x3_any and
               ops.x3_any_images) and `bn` (those and ops.bn_any) alternating, `bn` wins when it beats `any` by more than their combined spread; --frozen: the two legs
               of the frozen step, --no-fold: without ops.frozen_fold (every frozen BatchNorm is then a p3d_bn_eval_fwd / _bwd pair).
+  --block     (depthnet; profiles/block_anysize.md) the residual-block executor at the odd maps, ops.block_any.  With --classes: forward + backward of ONE block for each
+              of ResNet-50's eight block geometries at 65 / 33 / 17 (batch --batch), legs `layer` (ops.x3_any, ops.x3_any_images and ops.bn_any: the per-layer path) and
+              `block` (those and ops.block_any) alternating, median [min .. max] ms, and whether the executor takes the block.  With --step: legs `rec` (the recommended configuration
+              without it: ops.x3_any, ops.x3_any_images and ops.bn_any) and `block` (those and ops.block_any) alternating; `block` wins when it beats `rec` by more than
+              their combined spread.  Also the peak of allocated device memory of each leg's warm-up, the plan-owned buffers of the other leg released first.
 GPU box only."""
 import argparse
 import ctypes
@@ -72,15 +77,20 @@ def switch(on, partial=False):
 
 
 def switch_leg(leg, strided=False):
-    switch(leg in ('on', 'any', 'both', 'images', 'strided', 'bn'), leg == 'both')
+    rec = leg in ('rec', 'block')               # the recommended any-width configuration: x3_any, x3_any_images, bn_any
+    switch(leg in ('on', 'any', 'both', 'images', 'strided', 'bn') or rec, leg == 'both')
     if hasattr(ops, 'bn_any'):
-        ops.bn_any(leg == 'bn')
-    elif leg == 'bn':
+        ops.bn_any(leg == 'bn' or rec)
+    elif leg == 'bn' or rec:
         raise SystemExit('this build has no ops.bn_any')
     if hasattr(ops, 'x3_any_images'):
-        ops.x3_any_images(leg == 'images' or strided)
-    elif leg == 'images':
+        ops.x3_any_images(leg == 'images' or strided or rec)
+    elif leg == 'images' or rec:
         raise SystemExit('this build has no ops.x3_any_images')
+    if hasattr(ops, 'block_any'):
+        ops.block_any(leg == 'block')
+    elif leg == 'block':
+        raise SystemExit('this build has no ops.block_any')
     if hasattr(ops, 'x3_any_strided'):
         ops.x3_any_strided(leg == 'strided')
     elif leg == 'strided':
@@ -433,6 +443,47 @@ def classes_bn(a):
                 ('forward + backward' if backward else 'forward           ', leg[0]) + m + (moved / m[0] / 1e9,)), flush=True)
 
 
+# name, inplanes, planes, stride, dilation, odd map, downsample: ResNet-50's block geometries behind the stem at 257 (-stride 16)
+R50_BLOCKS = [('layer1.0', 64, 64, 1, 1, 65, True), ('layer1.1', 256, 64, 1, 1, 65, False), ('layer2.0', 256, 128, 2, 1, 65, True), ('layer2.1', 512, 128, 1, 1, 33, False),
+              ('layer3.0', 512, 256, 2, 1, 33, True), ('layer3.1', 1024, 256, 1, 1, 17, False), ('layer4.0', 1024, 512, 1, 2, 17, True), ('layer4.1', 2048, 512, 1, 1, 17, False)]
+
+
+def classes_block(a):
+    tr = pkg._trunk
+    for name, inplanes, planes, stride, dil, h, with_ds in R50_BLOCKS:
+        if a.only and a.only not in name:
+            continue
+        ds = tr.Sequential(pkg.nn.Conv2d(inplanes, planes * 4, kernel_size=1, stride=stride, bias=False), pkg.nn.BatchNorm2d(planes * 4)) if with_ds else None
+        torch.manual_seed(1)
+        block = tr.Bottleneck(inplanes, planes, stride, dil, ds).cuda().train()
+        x = torch.randn(a.batch, inplanes, h, h, device='cuda').relu_().requires_grad_(True)
+        with torch.no_grad():
+            dy = torch.randn(block(x).shape, device='cuda')
+
+        def one():
+            block.zero_grad(set_to_none=True)
+            x.grad = None
+            block(x).backward(dy)
+            ops.join_side_stream()
+        ms, takes = {'layer': [], 'block': []}, {}
+        for _ in range(a.rounds):
+            for leg in ms:
+                switch_leg('block' if leg == 'block' else 'rec')
+                takes[leg] = bool(pkg.ops_block.usable(block, x))
+                for _ in range(a.warmup):
+                    one()
+                torch.cuda.synchronize()
+                ms[leg].append(timed(one, a.iters))
+        switch_leg('off')
+        out = {'block': name, 'map': h, 'batch': a.batch, 'executor_takes_it': takes['block']}
+        for leg in ms:
+            m = med(ms[leg])
+            out[leg] = {'median_ms': round(m[0], 3), 'min_ms': round(m[1], 3), 'max_ms': round(m[2], 3)}
+        print(json.dumps(out), flush=True)
+        del block, x, dy
+        torch.cuda.empty_cache()
+
+
 def step(a):
     flags = ['-model', a.model, '-suffix', 'bench', '-data_name', 'h36m', '-save_path', '/tmp/p3d_bench', '-criterion', 'SmoothL1', '-num_joints', '17', '-side_in', str(a.side),
              '-stride', '16', '-depth', '16', '-depth_range', '1000', '-loss_div', '10', '-learn_rate', '5e-5', '-weight_decay', '4e-5', '-grad_norm', '5'] + FAMILY_FLAGS[a.family]
@@ -459,17 +510,25 @@ def step(a):
         legs = ('any', 'strided')
     if a.bn:
         legs = ('any', 'bn')
+    if a.block:
+        legs = ('rec', 'block')
 
     def run(n):
         for i in range(n):
             trainer.train_step(*batches[i % 3])
         ops.join_side_stream()
 
-    ms, counts = {leg: [] for leg in legs}, {}
+    ms, counts, peak = {leg: [] for leg in legs}, {}, {}
     for leg in legs:
         switch_leg(leg, a.strided or a.bn)
+        if a.block:
+            torch.cuda.synchronize()
+            pkg.ops_block.release_buffers(model)
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
         run(a.warmup)
         torch.cuda.synchronize()
+        peak[leg] = round(torch.cuda.max_memory_allocated() / 2 ** 20)
         ops.conv_path_stats(reset=True)
         run(1)
         torch.cuda.synchronize()
@@ -492,7 +551,13 @@ def step(a):
     for leg in legs:
         m = med(ms[leg])
         out[leg] = {'median_ms': round(m[0], 3), 'min_ms': round(m[1], 3), 'max_ms': round(m[2], 3)}
-    if legs == ('off', 'any', 'both'):
+    if legs == ('rec', 'block'):
+        spread = (out['rec']['max_ms'] - out['rec']['min_ms']) + (out['block']['max_ms'] - out['block']['min_ms'])
+        out['gain_ms'] = round(out['rec']['median_ms'] - out['block']['median_ms'], 3)
+        out['combined_spread_ms'] = round(spread, 3)
+        out['block_wins'] = bool(out['gain_ms'] > spread)
+        out['peak_allocated_mib'] = peak
+    elif legs == ('off', 'any', 'both'):
         spread = (out['any']['max_ms'] - out['any']['min_ms']) + (out['both']['max_ms'] - out['both']['min_ms'])
         out['gain_ms'] = round(out['any']['median_ms'] - out['both']['median_ms'], 3)
         out['combined_spread_ms'] = round(spread, 3)
@@ -535,18 +600,21 @@ def main():
     ap.add_argument('--images', action='store_true', help='the image-fed ragged path (ops.x3_any_images): see above')
     ap.add_argument('--strided', action='store_true', help='stride-2 data gradients on the x3 kernels (ops.x3_any_strided): see above')
     ap.add_argument('--bn', action='store_true', help='BatchNorm and the stem tail on the peeled instances (ops.bn_any): see above')
+    ap.add_argument('--block', action='store_true', help='the residual-block executor at the odd maps (ops.block_any): see above')
     ap.add_argument('--frozen', action='store_true', help='--step --strided / --bn: the frozen-fold step (every BatchNorm frozen, ops.frozen_fold)')
     ap.add_argument('--no-fold', action='store_true', help='--step --bn --frozen: every BatchNorm frozen, ops.frozen_fold off')
     ap.add_argument('--family', default='depthnet', choices=sorted(FAMILY_FLAGS))
     a = ap.parse_args()
-    if (a.images or a.strided or a.bn) and a.family != 'depthnet':
-        raise SystemExit('--images, --strided and --bn measure the dense family')
+    if (a.images or a.strided or a.bn or a.block) and a.family != 'depthnet':
+        raise SystemExit('--images, --strided, --bn and --block measure the dense family')
+    if a.block and not (a.step or a.classes):
+        raise SystemExit('--block goes with --classes or --step')
     if a.frozen and not ((a.strided or a.bn) and a.step):
         raise SystemExit('--frozen goes with --step --strided or --step --bn')
     if a.no_fold and not (a.frozen and a.bn):
         raise SystemExit('--no-fold goes with --step --bn --frozen')
     if a.classes:
-        (classes_bn if a.bn else classes_strided if a.strided else classes_images if a.images else classes if a.family == 'depthnet' else classes_partial)(a)
+        (classes_block if a.block else classes_bn if a.bn else classes_strided if a.strided else classes_images if a.images else classes if a.family == 'depthnet' else classes_partial)(a)
     if a.step:
         step(a)
 
