@@ -14,6 +14,11 @@
 // HBM passes that are BatchNorm's own, per block: forward, per inner layer the image pass (reads c_i, writes the image of a_i) and one pass that closes
 // the block (out = act(bn(c_last) + shortcut)); backward, one pass that opens it (g = dout * [out > 0] plus the channel sums of the closing BN and of
 // the downsample BN) and per layer the image pass of d c_i (reads g and c_i).
+//
+// Blocks at map sizes the aligned kernels refuse ("ragged" blocks, block_ragged: plane images, the ragged image-fed conv instances, passes for any HW) are opt-in:
+// p3d_block_any_enable takes the ones whose convolutions all have stride 1, p3d_block_any_strided_enable the ones that carry a stride-2 convolution -- there a data
+// gradient is a set of class launches into tight class planes, and a main-chain one costs one more pass of BatchNorm's own, block_strided_join_any_kernel (the
+// planes -> the gradient w.r.t. a_{i-1} and its channel sums at once).
 #include "p3d_common.h"
 #include "p3d_fx.h"
 #include <vector>
@@ -52,6 +57,22 @@ static bool block_conv_any_ok(const p3d_conv_desc* d) {
     both_images.aimg = both_images.bimg = both_images.ragged = true;
     return d->stride == 1 && fx_applies(FX_FWD, d, BLOCK_MIN_M, true) && fx_applies(FX_DGRAD, d, BLOCK_MIN_M, true) && fx_applies(FX_WGRAD, d, BLOCK_MIN_M, true) &&
            d->C % 16 == 0 && d->K % 16 == 0 && d->c_offset == 0 && d->c_total == d->C && fx_wgrad_plan(d, both_images).ok;
+}
+// Ragged blocks that carry a stride-2 convolution (p3d_block_any_strided_enable / P3D_BLOCK_ANY_STRIDED=1, default off; a switch of its own: it looks at no other and no
+// other at it -- the executor never reads p3d_x3_any_strided_enable).  The any-width rule of a stride-2 slot: the image-fed ragged forward and weight gradient take the
+// stride as they are; the data gradient is the class launches of fx_conv_dgrad_strided_any, image-fed, into tight class planes in the conv scratch, finished by
+// block_strided_join_any_kernel (a main-chain slot: da and the BatchNorm-backward sums in one pass) or by the interleave (conv 0 and the downsample conv: no sums to take).
+// A main-chain 1x1 stride 2 is refused as in the aligned rule.
+static int g_block_any_strided = -1;
+static bool block_any_strided_enabled() {
+    if (g_block_any_strided < 0) { const char* e = getenv("P3D_BLOCK_ANY_STRIDED"); g_block_any_strided = (e && atoi(e) == 1) ? 1 : 0; }
+    return g_block_any_strided == 1;
+}
+static bool block_conv_any_strided_ok(const p3d_conv_desc* d, bool main_chain) {
+    FxWgradOperands both_images{};
+    both_images.aimg = both_images.bimg = both_images.ragged = true;
+    return d->stride == 2 && fx_applies(FX_FWD, d, BLOCK_MIN_M, true) && fx_dgrad_strided_any_applies(d, BLOCK_MIN_M) && fx_applies(FX_WGRAD, d, BLOCK_MIN_M, true) &&
+           d->C % 16 == 0 && d->K % 16 == 0 && d->c_offset == 0 && d->c_total == d->C && fx_wgrad_plan(d, both_images).ok && !(main_chain && fx_dgrad_has_dead_classes(d));
 }
 
 __device__ __forceinline__ void blk_sum3(double& a, double& b, double& c, double* red /*[12]*/) {
@@ -364,11 +385,100 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const float* __restric
     }
 }
 
+// The finishing pass behind the class launches of a main-chain stride-2 data gradient of a ragged block (fx_conv_dgrad_strided_any, image-fed): one streaming pass that
+//   * writes g = the gradient w.r.t. a_{i-1}, [N][C][H][W] fp32, from the four tight class planes [N C][hc][wc] (hc = (H - ph + 1) / 2, wc = (W - pw + 1) / 2, plane
+//     ph * 2 + pw at stage + cls * cls_stride) -- every value the one dgrad_interleave_rows_kernel writes, bit for bit (a move; the pixels of a class no tap reaches
+//     get +0 and that plane is never read), and
+//   * takes the BatchNorm-backward sums of the layer in front, (sum gg, sum gg (c - mean)) with gg = g * [c * sc + sh > 0], into the fp64 partials [C][split][3]
+//     that bn_bwd_sums_kernel writes (bwd_map, kind 3, consumes them unchanged)
+// instead of an interleave and a sums pass that reads g again.  grid (C, split) like the passes beside it: block (ch, s) owns the planes of channel ch in images
+// s, s + split, ...  A plane of an odd map starts only on a 4-B line, so it is cut into slots: slot 0 the head up to g's next 16-B line (0 .. 3 elements), then the
+// body in groups of four -- one 16-B store each, c in one 16-B-wide load --, then the tail (0 .. 3 elements); head and tail go element by element.  One flat index over
+// (this block's images, slots) keeps the block busy on small planes.  A body group inside one row takes two consecutive floats from each of the row's two class rows
+// (pair loads, as in dgrad_interleave_rows_kernel); one that runs over a row end gathers element by element and still stores 16 B.  The sums: per slot an fp32 partial
+// of at most four terms (fmaf, as bn_bwd_sums_kernel keeps them), added in fp64 per thread, then blk_sum3 -- a fixed order, no atomics.
+typedef float f32x2_dw __attribute__((ext_vector_type(2), aligned(4)));      // on a dword line: the compiler picks the widest load the target allows there
+typedef float f32x4_dw __attribute__((ext_vector_type(4), aligned(4)));
+__global__ __launch_bounds__(256) void block_strided_join_any_kernel(const float* __restrict__ stage, const float* __restrict__ c, const float* __restrict__ tab,
+                                                                     float* __restrict__ g, double* __restrict__ partial, int N, int C, int H, int W, size_t cls_stride,
+                                                                     int live_mask) {
+    const int ch = blockIdx.x, s = blockIdx.y, split = gridDim.y;
+    const float sc = tab[ch * FX_TAB], sh = tab[ch * FX_TAB + 1], mean = tab[ch * FX_TAB + 2];
+    const int HW = H * W, hc1 = H >> 1, hc0 = H - hc1, wc1 = W >> 1, wc0 = W - wc1;
+    const int SL = (HW >> 2) + 2;                   // slots per plane: head, at most HW / 4 body groups, tail
+    const int nimg = (N - s + split - 1) / split, total = nimg * SL;
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int j = threadIdx.x; j < total; j += 256) {
+        const int k = j / SL, slot = j - k * SL;
+        const unsigned nc = (unsigned)(s + k * split) * (unsigned)C + (unsigned)ch;
+        const size_t off = (size_t)nc * HW;
+        int head = (int)((0u - (unsigned)(reinterpret_cast<uintptr_t>(g + off) >> 2)) & 3u);      // elements in front of g's next 16-B line
+        if (head > HW) head = HW;
+        const int nbody = (HW - head) >> 2;
+        int e0, cnt;
+        if (slot == 0) { e0 = 0; cnt = head; }
+        else if (slot <= nbody) { e0 = head + 4 * (slot - 1); cnt = 4; }
+        else if (slot == nbody + 1) { e0 = head + 4 * nbody; cnt = HW - e0; }
+        else continue;
+        if (cnt == 0) continue;
+        int hi = e0 / W, wi = e0 - hi * W;
+        const float* cp = c + off + e0;
+        float* gp = g + off + e0;
+        float v[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+        if (cnt == 4 && wi + 3 < W) {
+            // one row: even columns from class (ph, 0) at iw = wi / 2 (+ 1 from an odd start), odd columns from class (ph, 1)
+            const int ph = hi & 1, o = wi & 1, iw = wi >> 1;
+            const unsigned row = nc * (unsigned)(ph ? hc1 : hc0) + (unsigned)(hi >> 1);
+            f32x2_dw a = {0.f, 0.f}, b = {0.f, 0.f};
+            if ((live_mask >> (ph * 2)) & 1) a = *reinterpret_cast<const f32x2_dw*>(stage + (size_t)(ph * 2) * cls_stride + row * (unsigned)wc0 + (unsigned)(iw + o));
+            if ((live_mask >> (ph * 2 + 1)) & 1) b = *reinterpret_cast<const f32x2_dw*>(stage + (size_t)(ph * 2 + 1) * cls_stride + row * (unsigned)wc1 + (unsigned)iw);
+            v[0] = o ? b.x : a.x; v[1] = o ? a.x : b.x; v[2] = o ? b.y : a.y; v[3] = o ? a.y : b.y;
+            const f32x4_dw qq = *reinterpret_cast<const f32x4_dw*>(cp);
+            q[0] = qq.x; q[1] = qq.y; q[2] = qq.z; q[3] = qq.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (e < cnt) {
+                    const int ph = hi & 1, pw = wi & 1, cls = ph * 2 + pw;
+                    if ((live_mask >> cls) & 1)
+                        v[e] = stage[(size_t)cls * cls_stride + (nc * (unsigned)(ph ? hc1 : hc0) + (unsigned)(hi >> 1)) * (unsigned)(pw ? wc1 : wc0) + (unsigned)(wi >> 1)];
+                    q[e] = cp[e];
+                }
+                if (++wi == W) { wi = 0; ++hi; }      // (a slot never leaves its plane)
+            }
+        }
+        if (cnt == 4) *reinterpret_cast<f32x4*>(gp) = f32x4{v[0], v[1], v[2], v[3]};
+        else {
+#pragma unroll
+            for (int e = 0; e < 3; ++e)
+                if (e < cnt) gp[e] = v[e];
+        }
+        float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e < cnt) { const float gg = fmaf(q[e], sc, sh) > 0.f ? v[e] : 0.f; a1 += gg; a2 = fmaf(gg, q[e] - mean, a2); }
+        s1 += a1; s2 += a2;
+    }
+    __shared__ double red[12];
+    blk_sum3(s1, s2, s3, red);
+    if (threadIdx.x == 0) {
+        double* dst = partial + ((size_t)ch * split + s) * 3;
+        dst[0] = s1; dst[1] = s2; dst[2] = 0.0;
+    }
+}
+
 static int close_split(int N, int C) {
     int split = (int)ceil_div(2048, C);
     if (split > N) split = N;
     if (split > CLOSE_MAX_SPLIT) split = CLOSE_MAX_SPLIT;
     return split < 1 ? 1 : split;
+}
+// (the executor and the test hook p3d_block_strided_join; partial: [C][split][3] doubles)
+static int32_t launch_strided_join(const float* stage, const float* c, const float* tab, float* g, double* partial, int N, int C, int H, int W, size_t cls_stride, int live,
+                                   int split, hipStream_t st) {
+    P3D_REQUIRE((int64_t)N * C * H * W < (1ll << 31), "block_strided_join: the tensor exceeds 2^31 elements");
+    hipLaunchKernelGGL(block_strided_join_any_kernel, dim3((unsigned)C, (unsigned)split), dim3(256), 0, st, stage, c, tab, g, partial, N, C, H, W, cls_stride, live);
+    return check_launch("block_strided_join");
 }
 
 // ---- events for the second stream -------------------------------------------------------------------------------------------------------
@@ -438,13 +548,19 @@ static int block_refusal_aligned(const p3d_block_desc* b, int* slot) {
 }
 // A RAGGED block: a dense block the rule above refuses, under p3d_block_any_enable, whose every convolution (downsample included) block_conv_any_ok takes -- refused for
 // its map size only.  Derived from the descriptor wherever it matters (the admission, the image format, the workspace layout, both directions): an aligned block never
-// is one, whatever the switch says; strided and masked blocks at odd maps stay refused.
+// is one, whatever the switch says; masked blocks at odd maps stay refused.  Every slot passes the any-width rule of its stride; a block whose slots all have stride 1
+// is taken under p3d_block_any_enable, one that carries a stride-2 slot under p3d_block_any_strided_enable -- each switch admits exactly its own kind.
 static bool block_ragged(const p3d_block_desc* b) {
     int slot = 0;
-    if (!block_any_enabled() || b->masked || block_refusal_aligned(b, &slot) != 1) return false;
-    for (int i = 0; i < 4; ++i)
-        if (block_slot(b, i) && !block_conv_any_ok(&b->conv[i])) return false;
-    return true;
+    if (b->masked || block_refusal_aligned(b, &slot) != 1) return false;
+    bool strided = false;
+    for (int i = 0; i < 4; ++i) {
+        if (!block_slot(b, i)) continue;
+        const p3d_conv_desc* d = &b->conv[i];
+        if (d->stride == 2) strided = true;
+        if (!(d->stride == 2 ? block_conv_any_strided_ok(d, i < 3) : block_conv_any_ok(d))) return false;
+    }
+    return strided ? block_any_strided_enabled() : block_any_enabled();
 }
 static int block_refusal(const p3d_block_desc* b, int* slot) {
     const int why = block_refusal_aligned(b, slot);
@@ -478,6 +594,9 @@ static BlockLayout block_layout(const p3d_block_desc* b) {
         const p3d_conv_desc* d = &b->conv[i];
         atleast(mw, fx_workspace(FX_FWD, d, rag));
         atleast(mw, fx_workspace(FX_DGRAD, d, rag));
+        // a stride-2 slot of a ragged block: the class planes of its data gradient live in the conv scratch between the class launches and the pass that finishes
+        // them (stream-ordered, like the split-K slabs)
+        if (rag && d->stride == 2) atleast(mw, fx_dgrad_strided_any_plan(d).workspace);
         atleast(part, (size_t)fx_partial_rows(FX_FWD, d, rag) * d->K * 2 * sizeof(float));
         atleast(part, (size_t)fx_partial_rows(FX_DGRAD, d, rag) * d->C * 2 * sizeof(float));
         atleast(part, (size_t)(d->K > d->C ? d->K : d->C) * CLOSE_MAX_SPLIT * 3 * sizeof(double));      // the opening pass's and bn_bwd_sums_kernel's fp64 sums
@@ -541,6 +660,24 @@ int32_t p3d_block_any_enable(int32_t on) {
     const int32_t before = block_any_enabled() ? 1 : 0;
     g_block_any = on ? 1 : 0;
     return before;
+}
+
+// on = 1 / 0: the executor also takes ragged blocks that carry a stride-2 convolution / refuses them as ever.  Returns the previous setting.
+int32_t p3d_block_any_strided_enable(int32_t on) {
+    const int32_t before = block_any_strided_enabled() ? 1 : 0;
+    g_block_any_strided = on ? 1 : 0;
+    return before;
+}
+
+// Test hook: block_strided_join_any_kernel alone on given class planes (include/p3d_hip.h)
+int32_t p3d_block_strided_join(const float* stage, const float* c, const float* table, float* g, double* partial, int32_t N, int32_t C, int32_t H, int32_t W,
+                               size_t cls_stride, int32_t live_mask, int32_t split, void* stream) {
+    P3D_REQUIRE(stage && c && table && g && partial && N > 0 && C > 0 && H > 0 && W > 0, "block_strided_join: null tensor or empty shape");
+    P3D_REQUIRE(cls_stride >= (size_t)N * C * ((H + 1) / 2) * ((W + 1) / 2) && live_mask >= 0 && live_mask < 16, "block_strided_join: the class planes overlap, or a bad class mask");
+    P3D_REQUIRE(split >= 1 && split <= N && split <= CLOSE_MAX_SPLIT, "block_strided_join: split must be in 1 .. min(N, %d)", CLOSE_MAX_SPLIT);
+    P3D_REQUIRE((reinterpret_cast<uintptr_t>(partial) & 7) == 0 && ((reinterpret_cast<uintptr_t>(stage) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(g)) & 3) == 0,
+                "block_strided_join: misaligned tensor");
+    return launch_strided_join(stage, c, table, g, partial, N, C, H, W, cls_stride, live_mask, split, (hipStream_t)stream);
 }
 
 // 1: p3d_block_supported admits the block as a ragged one (host-only)
@@ -686,6 +823,23 @@ static int32_t bwd_dgrad(const BwdCtx& x, int slot, const p3d_conv_desc* dd, flo
     return fx_conv_dgrad(dd, nullptr, x.io->w[slot], dx, x.ws, x.conv_ws, f, x.st);
 }
 
+// The data gradient of a stride-2 slot of a ragged block (p3d_block_any_strided_enable): the class launches, image-fed from dcimg[slot] with the cached wimgT[slot], into
+// tight class planes in the conv scratch, then the pass that finishes them on the same stream -- join_c set (a main-chain slot i >= 1): block_strided_join_any_kernel
+// writes dx = da[i - 1] and the BatchNorm-backward sums of the layer in front (its raw output join_c, its table join_tab) into x.partial as [C][join_split][3]
+// doubles; otherwise (conv 0 of a BasicBlock, the downsample conv: no sums to take) the interleave, which writes the zeros of the classes no tap reaches and adds
+// onto dx under `accumulate`.
+static int32_t bwd_dgrad_strided(const BwdCtx& x, int slot, float* dx, int accumulate, const float* join_c, const float* join_tab, int join_split) {
+    const p3d_conv_desc* d = &x.b->conv[slot];
+    ProfScope ps(1, d, x.st);
+    fx_count(1, d);
+    const FxStridedPlan pl = fx_dgrad_strided_any_plan(d);
+    int live = 0;
+    if (int32_t e = fx_conv_dgrad_strided_any(d, nullptr, x.io->w[slot], x.ws, x.conv_ws, &live, x.st, x.io->dcimg[slot], x.io->wimgT[slot], join_c != nullptr)) return e;
+    const float* stage = (const float*)((const char*)x.ws + pl.stage_offset);
+    if (join_c) return launch_strided_join(stage, join_c, join_tab, dx, (double*)x.partial, d->N, d->C, d->H, d->W, pl.cls_stride, live, join_split, x.st);
+    return fx_dgrad_interleave_rows(stage, dx, nullptr, d->N, d->C, d->H, d->W, pl.cls_stride, live, accumulate, x.st);
+}
+
 // 1. open: g = dout * [out > 0]; channel sums of the closing BN (and of the downsample BN)
 static int32_t bwd_open(const BwdCtx& x) {
     const p3d_block_desc* b = x.b;
@@ -743,9 +897,18 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
             if (b->masked) f.emask = io->pix_in[i];            // dx = dgrad(d raw) * mask_in: the gradient w.r.t. a_{i-1}, of which the BatchNorm-backward sums are taken
             dd.accumulate = 0;
             P3D_REQUIRE(io->da[i - 1], "block_bwd: null gradient buffer %d", i - 1);
+            const double cnt = (double)dp->N * dp->Ho * dp->Wo;
+            if (x.rag && !epi) {
+                // a ragged block's strided data gradient: class launches, then one pass that writes da[i - 1] and takes the sums (bwd_dgrad_strided)
+                const int sp = close_split(dp->N, dp->K);
+                if (int32_t e = bwd_dgrad_strided(x, i, io->da[i - 1], 0, (const float*)io->c[i - 1], (const float*)io->table[i - 1], sp)) return e;
+                if (int32_t e = launch_wgrad(x, i, nullptr, io->aimg[i - 1], ready)) return e;
+                if (int32_t e = bwd_map(x, io->da[i - 1], i - 1, 1, 3, sp, 0, cnt)) return e;
+                ready = x.two ? mark_position(x.st) : nullptr;
+                continue;
+            }
             if (int32_t e = bwd_dgrad(x, i, &dd, io->da[i - 1], &f)) return e;
             if (int32_t e = launch_wgrad(x, i, nullptr, io->aimg[i - 1], ready)) return e;
-            const double cnt = (double)dp->N * dp->Ho * dp->Wo;
             if (epi) {
                 if (int32_t e = bwd_map(x, io->da[i - 1], i - 1, 1, 2, fx_partial_rows(FX_DGRAD, d, x.rag), 0, cnt)) return e;
             } else {
@@ -770,7 +933,9 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
                 dx = io->gbuf; dd.accumulate = 1;
                 if (!x.g_in_memory) { f.acc_src = io->dout; f.acc_mask = io->out_mask; }      // gbuf is written here for the first time
             }
-            if (int32_t e = bwd_dgrad(x, 0, &dd, dx, &f)) return e;
+            if (x.rag && d->stride == 2) {              // (a BasicBlock's strided conv 0: no BatchNorm in front of it, the interleave finishes the classes)
+                if (int32_t e = bwd_dgrad_strided(x, 0, dx, dd.accumulate, nullptr, nullptr, 0)) return e;
+            } else if (int32_t e = bwd_dgrad(x, 0, &dd, dx, &f)) return e;
         }
         if (int32_t e = launch_wgrad(x, 0, io->x, x.rag ? io->aimg[3] : nullptr, ready)) return e;      // (ragged: against the image of x kept from forward)
     }
@@ -779,7 +944,10 @@ static int32_t bwd_chain(const BwdCtx& x, hipEvent_t ready) {
 
 // 4. downsample branch: data gradient added onto dx, weight gradient (its gradient image was written with the closing BatchNorm's: `ready` is the chain's first event)
 static int32_t bwd_downsample(const BwdCtx& x, hipEvent_t ready) {
-    if (x.b->need_dx) {
+    if (x.b->need_dx && x.rag && x.b->conv[3].stride == 2) {
+        // the strided 1x1 of a ragged block: class (0, 0) alone is live; the interleave adds its plane onto dx and leaves the other pixels as they are
+        if (int32_t e = bwd_dgrad_strided(x, 3, x.io->dx, 1, nullptr, nullptr, 0)) return e;
+    } else if (x.b->need_dx) {
         FxFuse f{};
         f.wimg = x.io->wimgT[3];
         f.act_img = x.io->dcimg[3]; f.rows = x.rows; f.ragged = x.rag;
@@ -1158,6 +1326,32 @@ int32_t p3d_fx_conv_dgrad_img_any(const p3d_conv_desc* d, const void* dy_img, co
     ProfScope ps(1, d, (hipStream_t)stream);
     fx_count(1, d);
     return name_entry("fx_conv_dgrad_img_any", fx_conv_dgrad(d, nullptr, w, dx, workspace, workspace_bytes, &f, (hipStream_t)stream));
+}
+
+// The stride-2 data gradient on an image operand at any map side (include/p3d_hip.h): the class launches of fx_conv_dgrad_strided_any on the image-fed ragged
+// instance, then the interleave.  Entries of their own: p3d_fx_conv_dgrad_img_any and p3d_fx_conv_img_any_supported keep refusing stride 2.
+static bool strided_img_any_ok(const p3d_conv_desc* d) {
+    if (!d || d->N <= 0 || d->C <= 0 || d->K <= 0 || d->H <= 0 || d->W <= 0 || d->R <= 0 || d->S <= 0 || d->stride != 2 || d->dil < 1 || d->pad < 0) return false;
+    if (d->Ho <= 0 || d->Wo <= 0 || d->Ho != (d->H + 2 * d->pad - d->dil * (d->R - 1) - 1) / d->stride + 1 || d->Wo != (d->W + 2 * d->pad - d->dil * (d->S - 1) - 1) / d->stride + 1) return false;
+    return d->C % 16 == 0 && d->K % 16 == 0 && fx_dgrad_strided_any_applies(d, 32);      // (whole weights: the rule itself)
+}
+int32_t p3d_fx_conv_dgrad_strided_img_any_supported(const p3d_conv_desc* d) { return strided_img_any_ok(d) ? 1 : 0; }
+size_t p3d_fx_conv_dgrad_strided_img_any_workspace_bytes(const p3d_conv_desc* d) { return strided_img_any_ok(d) ? fx_dgrad_strided_any_plan(d).workspace : 0; }
+int32_t p3d_fx_conv_dgrad_strided_img_any(const p3d_conv_desc* d, const void* dy_img, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+    P3D_REQUIRE(d && dy_img && w && dx, "fx_conv_dgrad_strided_img_any: null argument");
+    P3D_REQUIRE(strided_img_any_ok(d), "fx_conv_dgrad_strided_img_any: shape outside the stride-2 class launches of the ragged image-fed kernels");
+    P3D_REQUIRE(d->accumulate == 0 || d->accumulate == 1, "fx_conv_dgrad_strided_img_any: accumulate must be 0 or 1");
+    P3D_REQUIRE(aligned16(dy_img, wimgT, workspace) && (reinterpret_cast<uintptr_t>(dx) & 3) == 0,
+                "fx_conv_dgrad_strided_img_any: the image, the weight image and the workspace must be 16-B aligned");
+    const FxStridedPlan pl = fx_dgrad_strided_any_plan(d);
+    if (!workspace || workspace_bytes < pl.workspace) { set_error("fx_conv_dgrad_strided_img_any: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
+    ProfScope ps(1, d, (hipStream_t)stream);
+    fx_count(1, d);
+    int live = 0;
+    if (int32_t e = name_entry("fx_conv_dgrad_strided_img_any", fx_conv_dgrad_strided_any(d, nullptr, w, workspace, workspace_bytes, &live, (hipStream_t)stream, dy_img, wimgT))) return e;
+    return fx_dgrad_interleave_rows((const float*)((const char*)workspace + pl.stage_offset), dx, nullptr, d->N, d->C, d->H, d->W, pl.cls_stride, live, d->accumulate,
+                                    (hipStream_t)stream);
 }
 
 // x: ignored (the signature of p3d_fx_conv_wgrad_img; there is no fp32 fallback here)

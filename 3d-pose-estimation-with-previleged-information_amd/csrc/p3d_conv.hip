@@ -1178,6 +1178,16 @@ int32_t wgrad_finish(const p3d_conv_desc* d, float* slabs, int nslab, bool tapm,
     if (launched) *launched |= fin;          // (for the caller that keeps a launch record)
     return wgrad_finish_launch(d, slabs, nslab, fin, dw, st);
 }
+// the finishing pass of X3_STRIDED_RAGGED (kernel 1 of the test hook p3d_dgrad_interleave; the block executor's strided data gradients that take no sums, p3d_fx.h):
+// a bounded grid, the kernel strides over the rest
+int32_t fx_dgrad_interleave_rows(const float* stage, float* dx, const float* mask_in, int N, int C, int H, int W, size_t cls_stride, int live, int accumulate, hipStream_t st) {
+    const int64_t total = (int64_t)N * C * H * W;
+    P3D_REQUIRE(total < (1ll << 31), "dgrad_interleave_rows: the tensor exceeds 2^31 elements");
+    const int64_t blocks = ceil_div(ceil_div(total, 4), 256);
+    hipLaunchKernelGGL(dgrad_interleave_rows_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, stage, dx, mask_in, (unsigned)total, C, H, W, cls_stride,
+                       live, accumulate, aligned16(dx) ? 1 : 0);
+    return check_launch("conv2d_dgrad interleave rows");
+}
 }  // namespace p3d
 
 using namespace p3d;
@@ -1537,16 +1547,6 @@ size_t p3d_conv2d_dgrad_workspace_bytes(const p3d_conv_desc* d) {
     return query_bytes(fp32_plan_dgrad, d, fx);
 }
 
-// the finishing pass of X3_STRIDED_RAGGED (and kernel 1 of the test hook p3d_dgrad_interleave): a bounded grid, the kernel strides over the rest
-static int32_t launch_interleave_rows(const float* stage, float* dx, const float* mask_in, int N, int C, int H, int W, size_t cls_stride, int live, int accumulate, hipStream_t st) {
-    const int64_t total = (int64_t)N * C * H * W;
-    P3D_REQUIRE(total < (1ll << 31), "dgrad_interleave_rows: the tensor exceeds 2^31 elements");
-    const int64_t blocks = ceil_div(ceil_div(total, 4), 256);
-    hipLaunchKernelGGL(dgrad_interleave_rows_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, stage, dx, mask_in, (unsigned)total, C, H, W, cls_stride,
-                       live, accumulate, aligned16(dx) ? 1 : 0);
-    return check_launch("conv2d_dgrad interleave rows");
-}
-
 int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, const float* mult,
                          const float* mask_in, float* dx, void* workspace, size_t workspace_bytes, void* stream) {
     last_clear(0);
@@ -1559,7 +1559,7 @@ int32_t p3d_conv2d_dgrad(const p3d_conv_desc* d, const float* dy, const float* w
         int live = 0;
         if (int32_t e = fx_conv_dgrad_strided_any(d, dy, w, workspace, workspace_bytes, &live, (hipStream_t)stream)) return e;
         const FxStridedPlan pl = fx_dgrad_strided_any_plan(d);
-        return launch_interleave_rows((const float*)((const char*)workspace + pl.stage_offset), dx, nullptr, d->N, d->C, d->H, d->W, pl.cls_stride, live, d->accumulate,
+        return fx_dgrad_interleave_rows((const float*)((const char*)workspace + pl.stage_offset), dx, nullptr, d->N, d->C, d->H, d->W, pl.cls_stride, live, d->accumulate,
                                       (hipStream_t)stream);
     }
     if (route.family != ConvRoute::FP32_MFMA) {
@@ -1672,7 +1672,7 @@ int32_t p3d_dgrad_interleave(int32_t kernel, const float* stage, float* dx, cons
                              int32_t live_mask, int32_t accumulate, void* stream) {
     P3D_REQUIRE(stage && dx && N > 0 && C > 0 && H > 0 && W > 0 && (kernel == 0 || kernel == 1), "dgrad_interleave: null tensor, empty shape, or a kernel other than 0 / 1");
     P3D_REQUIRE(cls_stride >= (size_t)N * C * ((H + 1) / 2) * ((W + 1) / 2) && live_mask >= 0 && live_mask < 16, "dgrad_interleave: the class planes overlap, or a bad class mask");
-    if (kernel == 1) return launch_interleave_rows(stage, dx, mask_in, N, C, H, W, cls_stride, live_mask, accumulate, (hipStream_t)stream);
+    if (kernel == 1) return fx_dgrad_interleave_rows(stage, dx, mask_in, N, C, H, W, cls_stride, live_mask, accumulate, (hipStream_t)stream);
     const int64_t total = (int64_t)N * C * H * W;
     const unsigned blocks = (unsigned)(ceil_div(total, 256) < 8192 ? ceil_div(total, 256) : 8192);
     hipLaunchKernelGGL(dgrad_interleave_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, stage, dx, mask_in, N * C, C, H, W, 2, cls_stride, live_mask, accumulate);

@@ -81,7 +81,7 @@ struct FxFuse {
     int rows;               // 1: act_img / dy_img / x_img are fp32 ROW images (fx_row_image: [N][C/16][HW][16] floats, 4 B per element) that the kernel cuts into the three
                             // pieces itself -- dense aligned training launches only (no factor, not ragged, not inference): what the block executor keeps a_i and d c_i as
     int ragged;             // 1: the ragged instances (any map width), for inference and training alike; fp32 operands, or (dense training launches only, nothing else set
-                            // but `partial` with its ep_c / ep_tab -- the ragged residual blocks: one unsplit launch; p3d_fx_conv_*_img_any) act_img for FWD / DGRAD (stride 1) and dy_img AND x_img for WGRAD (fx_wgrad_any_img_kernel).  With `infer`: dense, or a partial convolution
+                            // but `partial` with its ep_c / ep_tab -- the ragged residual blocks: one unsplit launch; p3d_fx_conv_*_img_any) act_img for FWD (either stride, with `partial` too) / DGRAD (stride 1; a stride-2 one is the class launches of fx_conv_dgrad_strided_any with dy_img) and dy_img AND x_img for WGRAD (fx_wgrad_any_img_kernel, either stride).  With `infer`: dense, or a partial convolution
                             // with pmask and emask.  Without: FWD / DGRAD (stride 1) with the plain epilogue, WGRAD on fx_wgrad_any_kernel -- dense fp32-fed training
                             // launches (p3d_x3_any_enable), no other field set; or the same three as a partial convolution (p3d_x3_any_partial_enable): pmask AND
                             // emask set, nothing else -- the factor epilogue, fx_wgrad_any_masked_kernel
@@ -150,7 +150,13 @@ bool fx_dgrad_strided_any_applies(const p3d_conv_desc* d, int min_m = 96);
 // the planes into dx (dgrad_interleave_rows_kernel, p3d_conv.hip)
 struct FxStridedPlan { size_t stage_offset, cls_stride, workspace; };      // bytes, floats, bytes
 FxStridedPlan fx_dgrad_strided_any_plan(const p3d_conv_desc* d);
-int32_t fx_conv_dgrad_strided_any(const p3d_conv_desc* d, const float* dy, const float* w, void* workspace, size_t workspace_bytes, int* live_mask, hipStream_t st);
+// dy_img (optional): the plane image of dy (fx_act_image_any) instead of dy -- the class launches on the image-fed ragged FX_EPI_STORE instance, same geometry, same
+// planes; wimgT (with dy_img, optional): the cached data-gradient weight image, nothing is built; join: the caller finishes with block_strided_join_any_kernel
+// (p3d_block.hip) instead of the interleave, which the record of the last class launch says
+int32_t fx_conv_dgrad_strided_any(const p3d_conv_desc* d, const float* dy, const float* w, void* workspace, size_t workspace_bytes, int* live_mask, hipStream_t st,
+                                  const void* dy_img = nullptr, const void* wimgT = nullptr, bool join = false);
+// the interleave behind the class launches (p3d_conv.hip: dgrad_interleave_rows_kernel on a bounded grid), for p3d_conv2d_dgrad and the block executor alike
+int32_t fx_dgrad_interleave_rows(const float* stage, float* dx, const float* mask_in, int N, int C, int H, int W, size_t cls_stride, int live, int accumulate, hipStream_t st);
 size_t fx_workspace(FxPass pass, const p3d_conv_desc* d, bool ragged = false);         // FX_FWD / FX_DGRAD: weight image + split-K slabs of the call's plan; FX_WGRAD: slabs for the larger of the two
                                                                                        // split counts (fp32- or image-fed x), what a caller reserves before it knows which
 int fx_partial_rows(FxPass pass, const p3d_conv_desc* d, bool ragged = false);         // FX_FWD / FX_DGRAD: rows of the per-channel partial sums of a launch with a sums epilogue (ragged: never split, one row per 128-pixel tile)

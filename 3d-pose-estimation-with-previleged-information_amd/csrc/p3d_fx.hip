@@ -2592,7 +2592,7 @@ int32_t fx_build_weight_images(const float* w, int K, int C, int RS, void* img_f
 enum { FXL_KERNEL = 0, FXL_AMODE, FXL_PRO, FXL_EPI, FXL_TAPI, FXL_RAG, FXL_ROWS, FXL_GRID_X, FXL_GRID_Y, FXL_GRID_Z, FXL_KCHUNK, FXL_FINISH, FXL_FINISH_GROUPS,
        FXL_FIELDS = P3D_FX_LAUNCH_FIELDS };
 static_assert(FXL_FINISH_GROUPS < FXL_FIELDS && FXL_ROWS + 1 == P3D_FX_INSTANCE_FIELDS, "the record of p3d_fx_launch_log outgrew its documented length");
-enum { FX_FINISH_NONE = 0, FX_FINISH_REDUCE0, FX_FINISH_REDUCE1, FX_FINISH_REDUCE2, FX_FINISH_REDUCE_ANY, FX_FINISH_INTERLEAVE_ROWS };       // FXL_FINISH
+enum { FX_FINISH_NONE = 0, FX_FINISH_REDUCE0, FX_FINISH_REDUCE1, FX_FINISH_REDUCE2, FX_FINISH_REDUCE_ANY, FX_FINISH_INTERLEAVE_ROWS, FX_FINISH_STRIDED_JOIN };       // FXL_FINISH
 constexpr int FX_LOG_MAX = 256;
 static std::mutex g_fx_log_mu;
 static int32_t g_fx_log[FX_LOG_MAX][FXL_FIELDS];
@@ -2709,8 +2709,9 @@ int32_t fx_conv_fwd(const p3d_conv_desc* d, const float* x, const float* w, cons
     P3D_REQUIRE(!(fuse && (fuse->res || fuse->relu)) || infer, "fx_conv_fwd: a residual / ReLU needs the inference epilogue");
     P3D_REQUIRE(!(rag && img) || (!infer && !masked), "fx_conv_fwd: the ragged forward takes an image operand only as the dense training launch");
     const bool rag_sums = rag && fuse->partial;     // FX_EPI_STATS on the ragged image-fed instance (the residual blocks at any map width): one unsplit launch
-    P3D_REQUIRE(!rag_sums || (img && !infer && !masked && d->stride == 1),
-                "fx_conv_fwd: the ragged training forward takes statistics only as the dense image-fed stride-1 launch");
+    // (at either stride: the AMODE 1 fetch takes a pixel's position from the flat output column through hmul / wmul, the sums run over the result's flat pixels)
+    P3D_REQUIRE(!rag_sums || (img && !infer && !masked),
+                "fx_conv_fwd: the ragged training forward takes statistics only as the dense image-fed launch");
     const FxPlan pl = fx_plan(d, false, rag, rag_sums);
     if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) { set_error("fx_conv_fwd: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     FxConvParams p{};
@@ -2836,6 +2837,10 @@ int32_t fx_conv_dgrad(const p3d_conv_desc* d, const float* dy, const float* w, f
 // in.  The caller interleaves the planes into dx (p3d_conv.hip: dgrad_interleave_rows_kernel, which also writes the zeros of the classes no tap reaches and adds under
 // `accumulate`).  The workspace: the data-gradient weight image, built here, then the four planes, each part on a 256-B line; cls_stride is rounded up to four floats,
 // so every plane starts on a 16-B line.  No class launch is split along K.
+// Image-fed (dy_img, the block executor and p3d_fx_conv_dgrad_strided_img_any): the operand is the plane image of dy (fx_act_image_any) and the class launches go to the
+// image-fed ragged FX_EPI_STORE instance, tap-outer, with the same class geometry and the same planes; wimgT, when given, is the cached data-gradient weight image and
+// nothing is built (the room for it in front of the planes stays unused).  join: the finishing pass the caller queues behind the planes is block_strided_join_any_kernel
+// (p3d_block.hip) instead of the interleave -- for the record of the last class launch only.
 FxStridedPlan fx_dgrad_strided_any_plan(const p3d_conv_desc* d) {
     FxStridedPlan s{};
     s.cls_stride = ((size_t)d->N * d->C * ((d->H + 1) / 2) * ((d->W + 1) / 2) + 3) & ~(size_t)3;
@@ -2843,16 +2848,23 @@ FxStridedPlan fx_dgrad_strided_any_plan(const p3d_conv_desc* d) {
     s.workspace = s.stage_offset + align256(4 * s.cls_stride * sizeof(float));
     return s;
 }
-int32_t fx_conv_dgrad_strided_any(const p3d_conv_desc* d, const float* dy, const float* w, void* workspace, size_t workspace_bytes, int* live_mask, hipStream_t st) {
+int32_t fx_conv_dgrad_strided_any(const p3d_conv_desc* d, const float* dy, const float* w, void* workspace, size_t workspace_bytes, int* live_mask, hipStream_t st,
+                                  const void* dy_img, const void* wimgT, bool join) {
     P3D_REQUIRE(fx_dgrad_strided_any_applies(d, 32), "fx_conv_dgrad_strided_any: shape outside the stride-2 rule of the x3 kernels");
+    const bool img = dy_img != nullptr;
+    P3D_REQUIRE(img || (!wimgT && !join), "fx_conv_dgrad_strided_any: a cached weight image and the joining pass belong to the image-fed form");
     const FxStridedPlan pl = fx_dgrad_strided_any_plan(d);
     if (!workspace || workspace_bytes < pl.workspace) { set_error("fx_conv_dgrad_strided_any: workspace %zu B < required %zu B", workspace_bytes, pl.workspace); return P3D_EWORKSPACE; }
     char* ws = (char*)workspace;
     const int RS = d->R * d->S;
-    if (int32_t e = fx_build_weight_images(w, d->K, d->C, RS, nullptr, ws, st, d->c_total, d->c_offset)) return e;
+    if (!wimgT) {
+        if (int32_t e = fx_build_weight_images(w, d->K, d->C, RS, nullptr, ws, st, d->c_total, d->c_offset)) return e;
+        wimgT = ws;
+    }
     float* stage = (float*)(ws + pl.stage_offset);
     FxConvParams p{};
-    p.X = dy; p.Wimg = (const unsigned char*)ws;
+    p.X = dy; p.Wimg = (const unsigned char*)wimgT;
+    if (img) { p.Ximg = (const unsigned char*)dy_img; p.plane_bytes = (size_t)d->N * d->K * d->Ho * d->Wo * 2; }
     p.N = d->N; p.Cred = d->K; p.Hi = d->Ho; p.Wi = d->Wo; p.M = d->C;
     p.R = d->R; p.S = d->S;
     p.oy0 = 0; p.ox0 = 0; p.oys = 1; p.oxs = 1; p.hmul = 1; p.wmul = 1;
@@ -2883,7 +2895,8 @@ int32_t fx_conv_dgrad_strided_any(const p3d_conv_desc* d, const float* dy, const
         for (int j = i; j > 0 && cls[j].ntap > cls[j - 1].ntap; --j) { const FxConvParams t = cls[j]; cls[j] = cls[j - 1]; cls[j - 1] = t; }
     for (int i = 0; i < ncls; ++i) {
         const dim3 grid((unsigned)(cls[i].tiles_m * ceil_div(cls[i].NP, FX_BN)), 1);
-        if (int32_t e = fx_launch_conv(cls[i], false, 0, FX_EPI_STORE, 0, grid, st, true, false, i == ncls - 1 ? FX_FINISH_INTERLEAVE_ROWS : FX_FINISH_NONE, 0)) return e;
+        if (int32_t e = fx_launch_conv(cls[i], img, 0, FX_EPI_STORE, 0, grid, st, true, false,
+                                       i == ncls - 1 ? (join ? FX_FINISH_STRIDED_JOIN : FX_FINISH_INTERLEAVE_ROWS) : FX_FINISH_NONE, 0)) return e;
     }
     prof_kernel_done(st);
     if (live_mask) *live_mask = live;

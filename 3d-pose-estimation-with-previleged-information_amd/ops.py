@@ -998,6 +998,15 @@ def block_any(on):
     return bool(lib().p3d_block_any_enable(int(bool(on))))
 
 
+def block_any_strided(on):
+    """Opt-in, OFF by default (P3D_BLOCK_ANY_STRIDED=1 turns it on), independent of every other switch, block_any and x3_any_strided included: the residual-block
+    executor also takes dense blocks that carry a STRIDE-2 convolution at map sizes the aligned kernels refuse -- layer2.0 and layer3.0 at the default 257 crop, the two
+    blocks block_any leaves to the per-layer path -- with the stride-2 data gradients as image-fed class launches and one joining pass.  Returns the previous setting."""
+    global X3_EPOCH
+    X3_EPOCH += 1                       # (ops_block caches per-block plans that depend on it)
+    return bool(lib().p3d_block_any_strided_enable(int(bool(on))))
+
+
 FROZEN_FOLD = os.environ.get('P3D_FROZEN_FOLD', '0') == '1'
 
 

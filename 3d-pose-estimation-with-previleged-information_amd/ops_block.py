@@ -4,7 +4,8 @@ and the host makes one C call per block and direction instead of a dozen per-lay
 
 Used by _trunk._ResidualBlock.forward for dense fp32 blocks whose BatchNorm layers are in training mode; everything else (partial convolutions,
 -half_acc, frozen / evaluation BatchNorm, shapes the fused kernels do not take) stays on the per-layer path of ops.py.  Under ops.block_any(True) the executor also
-takes stride-1 dense blocks at map sizes outside the aligned kernels ("ragged" blocks: _Plan.ragged); all that changes here is the buffers such a block owns.
+takes stride-1 dense blocks at map sizes outside the aligned kernels ("ragged" blocks: _Plan.ragged), under ops.block_any_strided(True) the ones that carry a stride-2
+convolution; all that changes here is the buffers such a block owns.
 """
 import ctypes
 import os

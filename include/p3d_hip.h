@@ -262,12 +262,29 @@ int32_t p3d_block_supported(const p3d_block_desc* b);
 /* The executor at any map width (default OFF; P3D_BLOCK_ANY=1 in the environment turns it on; independent of every p3d_x3_any_* switch).  Returns the previous setting.
  * While it is on, p3d_block_supported / p3d_block_* also take a RAGGED block: a dense block (masked == 0) that is refused only for its map size (H * W or Ho * Wo no multiple
  * of 4, rows of no multiple of 4 pixels: the 129 / 65 / 33 / 17 maps of the default 257 crop), every convolution of which, downsample included, has stride 1, whole weights,
- * channel counts in steps of 16 and >= 64 and a map of >= 16 pixels.  Aligned blocks run exactly what they run with the switch off; strided blocks and masked blocks at such
- * maps stay refused.  For a ragged block: every image is three bf16 planes (p3d_block_image_bytes: 6 B per element), io->aimg[3] holds the image of x (see there),
+ * channel counts in steps of 16 and >= 64 and a map of >= 16 pixels.  Aligned blocks run exactly what they run with the switch off; masked blocks at such maps stay refused, and
+ * so do strided blocks under this switch (they have one of their own: p3d_block_any_strided_enable, below).  For a ragged block: every image is three bf16 planes (p3d_block_image_bytes: 6 B per element), io->aimg[3] holds the image of x (see there),
  * io->out_mask is not used (backward reads `out`), io->gbuf is required whenever relu_out, and the convolutions run on the ragged image-fed instances of the x3 kernels,
  * the BatchNorm sums in their epilogues (p3d_fx_conv_any_sums_instances), never split along K.  DESIGN.md section 3, "Residual blocks at any map width". */
 int32_t p3d_block_any_enable(int32_t on);
-int32_t p3d_block_any_supported(const p3d_block_desc* b);       /* 1: p3d_block_supported admits b, as a ragged block (host-only; 0 while the switch is off and for every aligned block) */
+int32_t p3d_block_any_supported(const p3d_block_desc* b);       /* 1: p3d_block_supported admits b, as a ragged block of either kind (host-only; 0 while its switch is off and for every aligned block) */
+/* Ragged blocks that carry a STRIDE-2 convolution -- layer2.0 / layer3.0 of the ResNets at the default 257 crop (default OFF; P3D_BLOCK_ANY_STRIDED=1 in the environment
+ * turns it on; a switch of its own: independent of p3d_block_any_enable, of p3d_x3_any_strided_enable, which the executor never reads, and of every other switch).
+ * Returns the previous setting.  Alone it admits exactly the ragged blocks with a stride-2 slot; p3d_block_any_enable alone admits exactly the ones without.  The rule
+ * of a stride-1 slot is p3d_block_any_enable's; a stride-2 slot needs the image-fed ragged forward and weight gradient to take it, the stride-2 class launches
+ * (p3d_conv2d_dgrad_strided_any_supported's rule at 64 channels), whole weights, channel counts in steps of 16 and an OUTPUT map of >= 16 pixels; a 1x1 stride 2 only as
+ * the downsample conv.  Masked strided blocks at such maps stay refused.  The block is a ragged block in every other respect (plane images, io->aimg[3], no mask bytes,
+ * gbuf).  Forward: every convolution image-fed with the statistics epilogue, as in a stride-1 ragged block.  Backward: a stride-2 data gradient is one image-fed
+ * ragged launch per parity class into tight class planes in the workspace (p3d_block_workspace_bytes covers them), finished for a main-chain slot by
+ * block_strided_join_any_kernel -- one pass that writes da[i - 1] and takes the BatchNorm-backward sums of the layer in front -- and for conv 0 / the downsample conv by
+ * dgrad_interleave_rows_kernel.  DESIGN.md section 3, "Strided residual blocks at any map width". */
+int32_t p3d_block_any_strided_enable(int32_t on);
+/* TEST HOOK (tests/test_block_anysize_strided_gpu.py, tools/train_anysize_bench.py; nothing in the package calls it): block_strided_join_any_kernel alone.
+ * g[n][ch][hi][wi] = stage[cls * cls_stride + ((n C + ch) hc + hi / 2) wc + wi / 2] as p3d_dgrad_interleave lays the planes out (a class whose bit in live_mask is clear
+ * gives +0 and is not read), and partial[ch][s][0 .. 2] = (sum gg, sum gg (c - mean), 0) over images n = s, s + split, ... with gg = g * [c * sc + sh > 0],
+ * {sc, sh, mean} = table[ch][0 .. 2] (table [C][8] floats, c laid out like g, partial [C][split][3] doubles).  1 <= split <= min(N, 64); N C H W < 2^31. */
+int32_t p3d_block_strided_join(const float* stage, const float* c, const float* table, float* g, double* partial, int32_t N, int32_t C, int32_t H, int32_t W,
+                               size_t cls_stride, int32_t live_mask, int32_t split, void* stream);
 int32_t p3d_block_workspace_bytes(const p3d_block_desc* b, size_t* main_bytes, size_t* side_bytes);
 int32_t p3d_block_fwd(const p3d_block_desc* b, const p3d_block_io* io, void* workspace, size_t workspace_bytes, void* stream);
 /* side_stream: NULL, or a second stream for the weight-gradient kernels (ordered by events inside the call; the caller joins the streams before it reads dw) */
@@ -376,6 +393,18 @@ int32_t p3d_fx_conv_dgrad_img_any(const p3d_conv_desc* d, const void* dy_img, co
                                   void* stream);
 int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, const float* x, const void* x_img, float* dw, void* workspace, size_t workspace_bytes,
                                   void* stream);
+/* The STRIDE-2 data gradient of a dense convolution on an image operand at any map side (entries of their own: the two above keep refusing stride 2).  One launch of the
+ * image-fed ragged store instance per live, non-empty parity class of the input into tight class planes in the workspace -- the geometry and the planes of
+ * p3d_x3_any_strided_enable's fp32-fed class launches --, then dgrad_interleave_rows_kernel: dx = (or +=, by d->accumulate) the gradient, +0 at the pixels no tap
+ * reaches (which keep what they held under accumulate).
+ * _supported: 1 for a well-formed stride-2 descriptor that p3d_conv2d_dgrad_strided_any_supported's rule admits at 32 input channels, with C % 16 == 0 and K % 16 == 0.
+ * _workspace_bytes: the room for the data-gradient weight image plus four class planes of N C ceil(H / 2) ceil(W / 2) floats (rounded up to 4), each part on a 256-B
+ * line; 0 where _supported answers 0.  dy_img: p3d_fx_act_image_any of dy; wimgT: the p3d_fx_weight_images data-gradient image of w, or NULL (built into the workspace).
+ * The image, the weight image and the workspace on 16-B lines; P3D_EWORKSPACE when the workspace is short.  Counts as an x3 launch. */
+int32_t p3d_fx_conv_dgrad_strided_img_any_supported(const p3d_conv_desc* d);
+size_t p3d_fx_conv_dgrad_strided_img_any_workspace_bytes(const p3d_conv_desc* d);
+int32_t p3d_fx_conv_dgrad_strided_img_any(const p3d_conv_desc* d, const void* dy_img, const float* w, const void* wimgT, float* dx, void* workspace, size_t workspace_bytes,
+                                          void* stream);
 /* What the x3 path launched: one record per launch of a forward / data-gradient convolution kernel, written where the launch is made (every caller: p3d_conv2d_*, the
  * image entries, the inference entries, p3d_block_*, p3d_fx_conv_fused).  Host-side bookkeeping only.  A record is P3D_FX_LAUNCH_FIELDS int32:
  *   [0] kernel: 0 fx_conv_kernel (128-row tile), 96 / 64: fx16_conv_kernel with that tile
@@ -384,8 +413,9 @@ int32_t p3d_fx_conv_wgrad_img_any(const p3d_conv_desc* d, const void* dy_img, co
  *       9 inference with factor)   [4] TAPI (1: taps innermost), as launched   [5] RAG (any map width)   [6] ROWS (fp32 row image)  -- the kernel's template arguments
  *   [7] grid.x   [8] grid.y (split-K slabs)   [9] grid.z (parity classes of a strided data gradient in one launch)   [10] kchunk: K steps per slab, 0 unsplit
  *   [11] the pass that followed: 0 none, 1 fx_reduce_kernel<0>, 2 fx_reduce_kernel<1>, 3 fx_reduce_kernel<2>, 4 fx_reduce_any_kernel, 5 dgrad_interleave_rows_kernel (the
- *        class launches of a stride-2 data gradient under p3d_x3_any_strided_enable: on the record of the LAST class launch)   [12] its grid.y (the image groups
- *        of fx_reduce_kernel = the rows of its partial sums; 1 for fx_reduce_any_kernel; 0 with [11] 0 or 5)
+ *        class launches of a stride-2 data gradient under p3d_x3_any_strided_enable, of p3d_fx_conv_dgrad_strided_img_any and of a strided ragged block's conv 0 /
+ *        downsample conv: on the record of the LAST class launch), 6 block_strided_join_any_kernel (a strided ragged block's main-chain data gradient, likewise)
+ *        [12] its grid.y (the image groups of fx_reduce_kernel = the rows of its partial sums; 1 for fx_reduce_any_kernel; 0 with [11] 0, 5 or 6)
  *   [13..15] 0
  * p3d_fx_launch_log: copies the records since the last reset into out, oldest first, at most max_records of them (the library keeps the first 256), and returns how
  * many launches there were since then -- more than max_records, or than 256, shows as a count above what was copied.  reset != 0: the log starts anew afterwards.
@@ -405,7 +435,8 @@ int32_t p3d_fx_conv_any_sums_instances(int32_t* out, int32_t max_records);
  * fusions the block executor and the inference entries use, so that each can be checked alone.  src: x (forward) / dy (data gradient), fp32, ignored when f->act_img is
  * set; out: y / dx.  The fields of p3d_fx_fuse, NULL / 0 = not used:
  *   act_img  the operand as a p3d_fx_act_image image (rows = 1: a p3d_fx_row_image one; ragged = 1: p3d_fx_act_image_any -- with `partial` the ragged BatchNorm
- *            instances of p3d_fx_conv_any_sums_instances: dense, stride 1, one unsplit launch, rows from p3d_fx_conv_fused_partial_rows_any)
+ *            instances of p3d_fx_conv_any_sums_instances: dense, one unsplit launch, rows from p3d_fx_conv_fused_partial_rows_any; the forward at stride 2 too,
+ *            with ceil(N Ho Wo / 128) rows -- that query keeps answering 0 for stride 2; the data gradient stride 1 only)
  *   wimg     the p3d_fx_weight_images image of w for this pass, or NULL: built into the workspace
  *   partial  [p3d_fx_conv_fused_partial_rows][M][2] partial sums per result channel: forward (sum y, sum y^2); data gradient (sum g, sum g (ep_c - mean)) with
  *            g = dx * [ep_c * sc + sh > 0], ep_c laid out like dx and ep_tab [M][8] = {sc, sh, mean, ...}.  The summed value is the convolution (+ bias) (* emask);

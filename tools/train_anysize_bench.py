@@ -34,6 +34,12 @@
               `block` (those and ops.block_any) alternating, median [min .. max] ms, and whether the executor takes the block.  With --step: legs `rec` (the recommended configuration
               without it: ops.x3_any, ops.x3_any_images and ops.bn_any) and `block` (those and ops.block_any) alternating; `block` wins when it beats `rec` by more than
               their combined spread.  Also the peak of allocated device memory of each leg's warm-up, the plan-owned buffers of the other leg released first.
+  --block-strided  (with --block; profiles/block_anysize_strided.md) strided residual blocks at the odd maps, ops.block_any_strided.  With --classes: layer2.0 and
+              layer3.0 of ResNet-50 and of ResNet-18 alone, legs `layer` (ops.x3_any, ops.x3_any_images, ops.bn_any and ops.block_any, which leaves these blocks to the
+              per-layer path), `layer_x3s` (those and ops.x3_any_strided) and `block` (the first four and ops.block_any_strided) alternating; then
+              block_strided_join_any_kernel alone on the two ResNet-50 shapes (p3d_block_strided_join) against dgrad_interleave_rows_kernel on the same planes, in ms
+              and TB/s of the bytes each has to move.  With --step: legs `block` (the four switches) and `bstrided` (those and ops.block_any_strided) alternating;
+              `bstrided` wins when it beats `block` by more than their combined spread.
 GPU box only."""
 import argparse
 import ctypes
@@ -77,7 +83,7 @@ def switch(on, partial=False):
 
 
 def switch_leg(leg, strided=False):
-    rec = leg in ('rec', 'block')               # the recommended any-width configuration: x3_any, x3_any_images, bn_any
+    rec = leg in ('rec', 'block', 'bstrided')   # the recommended any-width configuration: x3_any, x3_any_images, bn_any
     switch(leg in ('on', 'any', 'both', 'images', 'strided', 'bn') or rec, leg == 'both')
     if hasattr(ops, 'bn_any'):
         ops.bn_any(leg == 'bn' or rec)
@@ -88,9 +94,13 @@ def switch_leg(leg, strided=False):
     elif leg == 'images' or rec:
         raise SystemExit('this build has no ops.x3_any_images')
     if hasattr(ops, 'block_any'):
-        ops.block_any(leg == 'block')
-    elif leg == 'block':
+        ops.block_any(leg in ('block', 'bstrided'))
+    elif leg in ('block', 'bstrided'):
         raise SystemExit('this build has no ops.block_any')
+    if hasattr(ops, 'block_any_strided'):
+        ops.block_any_strided(leg == 'bstrided')
+    elif leg == 'bstrided':
+        raise SystemExit('this build has no ops.block_any_strided')
     if hasattr(ops, 'x3_any_strided'):
         ops.x3_any_strided(leg == 'strided')
     elif leg == 'strided':
@@ -448,14 +458,21 @@ R50_BLOCKS = [('layer1.0', 64, 64, 1, 1, 65, True), ('layer1.1', 256, 64, 1, 1, 
               ('layer3.0', 512, 256, 2, 1, 33, True), ('layer3.1', 1024, 256, 1, 1, 17, False), ('layer4.0', 1024, 512, 1, 2, 17, True), ('layer4.1', 2048, 512, 1, 1, 17, False)]
 
 
+# the strided blocks at 257: layer2.0 and layer3.0 of ResNet-50 (Bottleneck) and of ResNet-18 (BasicBlock), same columns with the block class in front
+STRIDED_BLOCKS = [('bottleneck', 'r50.layer2.0', 256, 128, 2, 1, 65, True), ('bottleneck', 'r50.layer3.0', 512, 256, 2, 1, 33, True),
+                  ('basic', 'r18.layer2.0', 64, 128, 2, 1, 65, True), ('basic', 'r18.layer3.0', 128, 256, 2, 1, 33, True)]
+
+
 def classes_block(a):
     tr = pkg._trunk
-    for name, inplanes, planes, stride, dil, h, with_ds in R50_BLOCKS:
+    blocks = STRIDED_BLOCKS if a.block_strided else [('bottleneck',) + b for b in R50_BLOCKS]
+    for kind, name, inplanes, planes, stride, dil, h, with_ds in blocks:
         if a.only and a.only not in name:
             continue
-        ds = tr.Sequential(pkg.nn.Conv2d(inplanes, planes * 4, kernel_size=1, stride=stride, bias=False), pkg.nn.BatchNorm2d(planes * 4)) if with_ds else None
+        cls = tr.Bottleneck if kind == 'bottleneck' else tr.BasicBlock
+        ds = tr.Sequential(pkg.nn.Conv2d(inplanes, planes * cls.expansion, kernel_size=1, stride=stride, bias=False), pkg.nn.BatchNorm2d(planes * cls.expansion)) if with_ds else None
         torch.manual_seed(1)
-        block = tr.Bottleneck(inplanes, planes, stride, dil, ds).cuda().train()
+        block = cls(inplanes, planes, stride, dil, ds).cuda().train()
         x = torch.randn(a.batch, inplanes, h, h, device='cuda').relu_().requires_grad_(True)
         with torch.no_grad():
             dy = torch.randn(block(x).shape, device='cuda')
@@ -465,10 +482,14 @@ def classes_block(a):
             x.grad = None
             block(x).backward(dy)
             ops.join_side_stream()
-        ms, takes = {'layer': [], 'block': []}, {}
+        ms, takes = ({'layer': [], 'layer_x3s': [], 'block': []} if a.block_strided else {'layer': [], 'block': []}), {}
         for _ in range(a.rounds):
             for leg in ms:
-                switch_leg('block' if leg == 'block' else 'rec')
+                if a.block_strided:
+                    switch_leg('bstrided' if leg == 'block' else 'block')
+                    ops.x3_any_strided(leg == 'layer_x3s')
+                else:
+                    switch_leg('block' if leg == 'block' else 'rec')
                 takes[leg] = bool(pkg.ops_block.usable(block, x))
                 for _ in range(a.warmup):
                     one()
@@ -482,6 +503,31 @@ def classes_block(a):
         print(json.dumps(out), flush=True)
         del block, x, dy
         torch.cuda.empty_cache()
+
+
+def join_bandwidth(a):
+    """block_strided_join_any_kernel alone against dgrad_interleave_rows_kernel on the same class planes: the gradient buffers in front of the strided 3x3 of
+    ResNet-50's layer2.0 and layer3.0.  Bytes each has to move: the four planes read and g written -- the join reads c too."""
+    L = pkg._lib.lib()
+    for name, c, h in (('r50.layer2.0 da[0]', 128, 65), ('r50.layer3.0 da[0]', 256, 33)):
+        n = a.batch
+        cls_stride = (n * c * ((h + 1) // 2) ** 2 + 3) // 4 * 4
+        stage, cc, g = torch.randn(4 * cls_stride, device='cuda'), torch.randn(n, c, h, h, device='cuda'), torch.empty(n, c, h, h, device='cuda')
+        tab = torch.rand(c, 8, device='cuda')
+        split = min(n, 64, -(-2048 // c))
+        partial = torch.empty(c, split, 3, dtype=torch.float64, device='cuda')
+        join = lambda: L.p3d_block_strided_join(ops._p(stage), ops._p(cc), ops._p(tab), ops._p(g), ops._p(partial), n, c, h, h, cls_stride, 15, split, ops._stream())
+        inter = lambda: L.p3d_dgrad_interleave(1, ops._p(stage), ops._p(g), None, n, c, h, h, cls_stride, 15, 0, ops._stream())
+        out = {'tensor': name, 'shape': [n, c, h, h]}
+        for leg, fn, nbytes in (('interleave', inter, 8.0 * g.numel()), ('join', join, 12.0 * g.numel())):
+            assert fn() == 0, L.p3d_last_error()
+            ms = []
+            for _ in range(a.rounds):
+                timed(fn, a.warmup)
+                ms.append(timed(fn, a.iters))
+            m = med(ms)
+            out[leg] = {'median_ms': round(m[0], 4), 'min_ms': round(m[1], 4), 'max_ms': round(m[2], 4), 'tb_per_s': round(nbytes / m[0] / 1e9, 2)}
+        print(json.dumps(out), flush=True)
 
 
 def step(a):
@@ -511,7 +557,7 @@ def step(a):
     if a.bn:
         legs = ('any', 'bn')
     if a.block:
-        legs = ('rec', 'block')
+        legs = ('block', 'bstrided') if a.block_strided else ('rec', 'block')
 
     def run(n):
         for i in range(n):
@@ -557,6 +603,12 @@ def step(a):
         out['combined_spread_ms'] = round(spread, 3)
         out['block_wins'] = bool(out['gain_ms'] > spread)
         out['peak_allocated_mib'] = peak
+    elif legs == ('block', 'bstrided'):
+        spread = (out['block']['max_ms'] - out['block']['min_ms']) + (out['bstrided']['max_ms'] - out['bstrided']['min_ms'])
+        out['gain_ms'] = round(out['block']['median_ms'] - out['bstrided']['median_ms'], 3)
+        out['combined_spread_ms'] = round(spread, 3)
+        out['bstrided_wins'] = bool(out['gain_ms'] > spread)
+        out['peak_allocated_mib'] = peak
     elif legs == ('off', 'any', 'both'):
         spread = (out['any']['max_ms'] - out['any']['min_ms']) + (out['both']['max_ms'] - out['both']['min_ms'])
         out['gain_ms'] = round(out['any']['median_ms'] - out['both']['median_ms'], 3)
@@ -601,6 +653,7 @@ def main():
     ap.add_argument('--strided', action='store_true', help='stride-2 data gradients on the x3 kernels (ops.x3_any_strided): see above')
     ap.add_argument('--bn', action='store_true', help='BatchNorm and the stem tail on the peeled instances (ops.bn_any): see above')
     ap.add_argument('--block', action='store_true', help='the residual-block executor at the odd maps (ops.block_any): see above')
+    ap.add_argument('--block-strided', action='store_true', help='with --block: strided residual blocks at the odd maps (ops.block_any_strided): see above')
     ap.add_argument('--frozen', action='store_true', help='--step --strided / --bn: the frozen-fold step (every BatchNorm frozen, ops.frozen_fold)')
     ap.add_argument('--no-fold', action='store_true', help='--step --bn --frozen: every BatchNorm frozen, ops.frozen_fold off')
     ap.add_argument('--family', default='depthnet', choices=sorted(FAMILY_FLAGS))
@@ -609,12 +662,16 @@ def main():
         raise SystemExit('--images, --strided, --bn and --block measure the dense family')
     if a.block and not (a.step or a.classes):
         raise SystemExit('--block goes with --classes or --step')
+    if a.block_strided and not a.block:
+        raise SystemExit('--block-strided goes with --block')
     if a.frozen and not ((a.strided or a.bn) and a.step):
         raise SystemExit('--frozen goes with --step --strided or --step --bn')
     if a.no_fold and not (a.frozen and a.bn):
         raise SystemExit('--no-fold goes with --step --bn --frozen')
     if a.classes:
         (classes_block if a.block else classes_bn if a.bn else classes_strided if a.strided else classes_images if a.images else classes if a.family == 'depthnet' else classes_partial)(a)
+        if a.block and a.block_strided and not a.only:
+            join_bandwidth(a)
     if a.step:
         step(a)
 
